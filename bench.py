@@ -10,8 +10,18 @@ recipe hyper-parameters of the repo's own config (blstm_ctc_100h_char.yml): rmsp
 clip_grad_norm 5, clip_activation 50, dropout 0.2.
 A step = forward + CTC loss + backward + per-variable clip + (all-reduce) + optimizer update.
 
-The complete result object goes to bench_full.json (and gpurun_out/bench_full.json); the LAST stdout line rank 0 prints is
-its compact form (compact_line: numbers only, <= 6 000 bytes, the driver keeps 8 000).  The full object holds
+A plain run does what the headline needs and no more: it sets up, warms up, times the K steps and prints the result
+line.  Its figures all come from the timed steps themselves: value / ms_per_step, step_ms, the serial kernels' event
+times and the recurrence roofline derived from them (and, at N > 1, per_rank / comm).
+  --dump-outputs DIR     after the timed steps, what the LAST timed step computed (loss, per-utterance CTC losses,
+                         logits with the frames past each utterance's length zeroed, every updated parameter) as
+                         DIR/<name>.npy in float32, <= 64 MB in all (a fixed seeded sample of each array beyond that);
+                         the same arguments give the same inputs in every run, so two builds compare output for output;
+  --full                 everything below that takes work or runs of its own (h2d_inclusive, parity, cpu_baseline, the
+                         other configurations, other_padding at N > 1) and the complete result object written to the
+                         files of FULL_RESULT_PATHS; the --no-* and --aux options select within it.
+The LAST stdout line rank 0 prints is the compact form of the result (compact_line: numbers only, <= 6 000 bytes, the
+driver keeps 8 000).  The full object holds
   value / ms_per_step    K steps bracketed by barrier + synchronize, inputs resident in HBM (the contract's number);
   step_ms                per-step durations from HIP events on the launch stream: median / min / max; the host's time
                          to ENQUEUE a step (host_issue_mean) and, apart from it, the time the host spent waiting for
@@ -387,9 +397,38 @@ def load_traffic_table():
     return json.load(open(tpath)) if os.path.exists(tpath) else None
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_LIMIT = 63 << 20     # bytes of array data in all: with the .npy headers the directory stays under 64 MB
+
+
+def dump_outputs(out_dir, model, last, seq_len, limit=DUMP_LIMIT):
+    """What the last timed step handed back to its caller, as float32 out_dir/<name>.npy: loss (0-dim), ctc_losses [B],
+    logits [T, B, C] (time-major; frames past each utterance's length set to 0, nothing defines them) and every
+    parameter after the step's update (param.<variable name with '/' -> '.'>).  Beyond `limit` bytes in all, every
+    array keeps the same fraction of its entries, flattened, at indices drawn with a fixed seed (in index order).
+    Returns {file name: bytes of array data}."""
+    arrays = {'loss': last['loss'], 'ctc_losses': model.ctc_losses, 'logits': last['logits']}
+    for n, v in model.store.state_dict().items():
+        arrays['param.' + n.replace('/', '.')] = v
+    arrays = {k: v.detach().float().cpu().contiguous().numpy() for k, v in arrays.items()}
+    lg = arrays['logits']
+    lg[np.arange(lg.shape[0])[:, None] >= np.asarray(seq_len)[None, :]] = 0.0
+    frac = min(1.0, float(limit) / sum(a.nbytes for a in arrays.values()))
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        if frac < 1.0 and a.size > 1:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, max(1, int(a.size * frac)), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        written[name + '.npy'] = a.nbytes
+    return written
+
+
 # ------------------------------------------------------------------------------------------------ BLSTM-CTC workloads
-def run_blstm_ctc(args, wl, dev, world, rank, dev_index, steps, warmup, want_parity, want_h2d, want_cpu):
-    """Times one BLSTM-CTC workload description `wl` on this rank; returns the result dict (rank 0 aggregates)."""
+def run_blstm_ctc(args, wl, dev, world, rank, dev_index, steps, warmup, want_parity, want_h2d, want_cpu, dump_dir=None):
+    """Times one BLSTM-CTC workload description `wl` on this rank; returns the result dict (rank 0 aggregates).
+    dump_dir: write what the last timed step computed there (dump_outputs), before any further leg trains the model."""
     import torch.distributed as dist
     from tensorflow_end2end_speech_recognition_amd.models.ctc.ctc import CTC
     from tensorflow_end2end_speech_recognition_amd.utils.training import multi_gpu
@@ -416,6 +455,7 @@ def run_blstm_ctc(args, wl, dev, world, rank, dev_index, steps, warmup, want_par
     sld = torch.tensor(seq_len, device=dev)
     opt = model._set_optimizer('rmsprop', 1e-3)
     cur = [xd]
+    last = {}                # what the latest step handed back to its caller (dump_dir only)
     comm_events = []
     if world > 1:     # duration of the collectives on the communication stream (HIP events on that stream)
         orig_ar = multi_gpu._allreduce_mean_
@@ -435,11 +475,16 @@ def run_blstm_ctc(args, wl, dev, world, rank, dev_index, steps, warmup, want_par
         # layers on a communication stream under the BPTT of the layers below when N > 1 (multi_gpu.BucketedAverager)
         multi_gpu.clip_and_average(model, opt, loss)
         opt.apply_gradients(None)
+        if dump_dir:
+            last['loss'], last['logits'] = loss, logits
         return loss
 
     log('%dx%d %s B=%d: timing %d steps' % (L, H, wl['dtype'], wl['batch'], steps))
     res.update(time_steps(step, steps, warmup, world, dev_index))
     log('   %.3f ms/step' % (res['elapsed'] / steps * 1e3))
+    if dump_dir:
+        res['dumped'] = dump_outputs(dump_dir, model, last, seq_len)
+        log('outputs of the last timed step: %d arrays, %.1f MB in %s' % (len(res['dumped']), sum(res['dumped'].values()) / 1e6, dump_dir))
     if world > 1:
         multi_gpu._allreduce_mean_ = orig_ar
         n_timed = len(comm_events) * steps // (steps + warmup)     # the warm-up steps' collectives come first
@@ -1085,6 +1130,13 @@ def main():
                          '(0 = skip); the headline pads to the global Tmax as the reference does')
     ap.add_argument('--cpu-tmax', type=int, default=256,
                     help='CPU legs (baseline, oracle parity): the same batch truncated to its first N frames')
+    ap.add_argument('--full', action='store_true',
+                    help='also the legs beyond the headline (h2d-inclusive timing, oracle parity, CPU baseline, cfgA, '
+                         'the auxiliary entries, at N > 1 the other padding rule) and the complete result object in '
+                         'bench_full.json; a plain run only times the headline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (loss, per-utterance losses, logits, updated '
+                         'parameters) as DIR/<name>.npy, float32, <= 64 MB in all')
     args = ap.parse_args()
 
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -1128,10 +1180,11 @@ def main():
               input_size=args.input_size, tmin=args.tmin, tmax=args.tmax, keep_prob=args.keep_prob, seed=1,
               global_tmax=not args.no_global_tmax)
     res = run_blstm_ctc(args, wl, dev, world, rank, dev_index, args.steps, args.warmup,
-                        want_parity=not args.no_parity, want_h2d=True,
-                        want_cpu=(world == 1 and not args.no_cpu_baseline))
+                        want_parity=args.full and not args.no_parity, want_h2d=args.full,
+                        want_cpu=(args.full and world == 1 and not args.no_cpu_baseline),
+                        dump_dir=args.dump_outputs if rank == 0 else None)
     # aggregate: slowest rank's time, all ranks' frames; per-rank medians so a straggler is visible
-    stats = torch.tensor([res['elapsed'], res['elapsed_h2d'], float(res['frames']), res['step_ms']['median'],
+    stats = torch.tensor([res['elapsed'], res.get('elapsed_h2d', 0.0), float(res['frames']), res['step_ms']['median'],
                           float(res['T']), res.get('comm', {}).get('allreduce_ms_per_step', 0.0)],
                          device=dev, dtype=torch.float64)
     if world > 1:
@@ -1143,7 +1196,7 @@ def main():
     elapsed, elapsed_h2d, total_frames = float(allst[:, 0].max()), float(allst[:, 1].max()), float(allst[:, 2].sum())
     value = total_frames * args.steps / elapsed
     other_padding = None
-    if world > 1 and args.own_tmax_steps > 0:
+    if args.full and world > 1 and args.own_tmax_steps > 0:
         # the same shards under the OTHER padding rule (default leg: the reference's global Tmax; this leg: every rank
         # padded to its own longest utterance -- ranks then finish their recurrences at different times and the slowest
         # one sets the step), a short run, reported beside the headline
@@ -1188,7 +1241,7 @@ def main():
                                       ms_per_step=elapsed_h2d / args.steps * 1e3, median_ms=res['h2d_median_ms'],
                                       note='batch uploaded from pinned host memory every step, double-buffered on a '
                                            'copy stream (SURVEY 8d step definition); reported next to `value`, which '
-                                           'has the inputs resident as the bench contract asks'),
+                                           'has the inputs resident as the bench contract asks') if args.full else None,
                    final_loss=res['final_loss'], cluster_handoff_flags=res['handoff_flags'],
                    parity=res.get('parity'), kernels=ks,
                    roofline=recurrence_roofline(H, res['frames'] * 2, res['T'], wl['dtype'], ks, traffic, src,
@@ -1208,7 +1261,7 @@ def main():
         del res
         torch.cuda.empty_cache()
         log('headline done: %.0f frames/s' % value)
-        if world == 1 and not args.no_cfgA:
+        if args.full and world == 1 and not args.no_cfgA:
             # BASELINE configs[0]: TIMIT-39, 2x128 BLSTM-CTC, fp32 (exact fp32 MFMA path), B=16, dropout 0.5
             wa = dict(units=128, layers=2, classes=39, dtype='f32', batch=16, input_size=120, tmin=100, tmax=778,
                       keep_prob=0.5, seed=0)
@@ -1218,7 +1271,7 @@ def main():
                                           'TIMIT 39-phone 2x128 BLSTM-CTC fp32, B=16, D=120, C=40, seq_len~U{100..778}, '
                                           'dropout 0.5, rmsprop, train step')
             del ra
-        aux = set() if (world > 1 or args.no_aux) else set(a for a in args.aux.split(',') if a)
+        aux = set() if (not args.full or world > 1 or args.no_aux) else set(a for a in args.aux.split(',') if a)
         def over_budget(name):
             if time.perf_counter() - _T0 > args.time_budget:
                 out[name] = dict(skipped='time budget of %.0f s used up' % args.time_budget)
@@ -1329,7 +1382,7 @@ def main():
                 torch.cuda.empty_cache()
             out['batch_scaling'] = dict(workload='headline model (5x256 bf16, D=120, C=62, T<=778) at larger per-GPU batches', rows=rows)
         sys.stdout.flush()
-        out['full'] = write_full(out)
+        out['full'] = write_full(out) if args.full else None
         os.write(result_fd, (compact_line(out) + '\n').encode())
     if world > 1:
         dist.barrier()

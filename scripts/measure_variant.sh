@@ -12,7 +12,7 @@ mkdir -p "$OUT"
 ASR_LSTM_DFLAGS=$FLAGS timeout 240 python -m pytest tests -m gpu -q -x -k "lstm or ctc_model or smoke" > "$OUT/tests.log" 2>&1
 echo "tests rc=$? $(tail -1 "$OUT/tests.log")"
 for f in 0 "$FLAGS"; do
-  ASR_LSTM_DFLAGS=$f timeout 120 python bench.py --no-cpu-baseline > "$OUT/bench_$f.json" 2> "$OUT/bench_$f.err"
+  ASR_LSTM_DFLAGS=$f timeout 120 python bench.py --full --no-cpu-baseline > "$OUT/bench_$f.json" 2> "$OUT/bench_$f.err"
   python - "$OUT/bench_$f.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -4,7 +4,7 @@ set -u
 OUT=$1; VAR=$2; shift 2
 mkdir -p $OUT
 for v in "$@"; do
-  env $VAR=$v timeout 300 python bench.py --steps 30 --warmup 5 --no-cpu-baseline --no-parity --no-cfgA > $OUT/bench_$v.json 2> $OUT/bench_$v.err
+  env $VAR=$v timeout 300 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline --no-parity --no-cfgA > $OUT/bench_$v.json 2> $OUT/bench_$v.err
   OUT=$OUT V=$v VAR=$VAR python - <<'PY'
 import json, os
 d = json.load(open('%s/bench_%s.json' % (os.environ['OUT'], os.environ['V']))); k = d['kernels']

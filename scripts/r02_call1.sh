@@ -8,8 +8,8 @@ echo "parity rc=$? $(tail -1 $OUT/parity.log)"
 ASR_LSTM_DFLAGS=32 timeout 900 python -m pytest tests -m gpu -q -s -k "headline or cfgB or lstm_cluster_exchange" > $OUT/parity_early.log 2>&1
 echo "parity EARLY rc=$? $(tail -1 $OUT/parity_early.log)"
 for f in 0 32; do
-  ASR_LSTM_DFLAGS=$f timeout 120 python bench.py --no-cpu-baseline > $OUT/bench_$f.json 2> $OUT/bench_$f.err
-  ASR_LSTM_DFLAGS=$f timeout 120 python bench.py --no-cpu-baseline --steps 20 --warmup 5 > $OUT/bench20_$f.json 2> $OUT/bench20_$f.err
+  ASR_LSTM_DFLAGS=$f timeout 120 python bench.py --full --no-cpu-baseline > $OUT/bench_$f.json 2> $OUT/bench_$f.err
+  ASR_LSTM_DFLAGS=$f timeout 120 python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 > $OUT/bench20_$f.json 2> $OUT/bench20_$f.err
 done
 python - <<'PY'
 import json, glob

@@ -5,10 +5,10 @@ OUT=gpurun_out/r02_c2
 mkdir -p $OUT
 timeout 1500 python -m pytest tests -m gpu -q -x --durations=15 > $OUT/gpu_tests.log 2>&1
 echo "gpu tests rc=$? $(tail -1 $OUT/gpu_tests.log)"
-timeout 600 python bench.py --steps 20 --warmup 5 > $OUT/bench20.json 2> $OUT/bench20.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $OUT/bench20.json 2> $OUT/bench20.err
 echo "bench rc=$?"
 for f in 0 32; do
-  ASR_LSTM_DFLAGS=$f timeout 200 python bench.py --units 512 --batch 32 --steps 20 --warmup 5 --no-cpu-baseline --no-parity --no-cfgA > $OUT/bench512_$f.json 2> $OUT/bench512_$f.err
+  ASR_LSTM_DFLAGS=$f timeout 200 python bench.py --full --units 512 --batch 32 --steps 20 --warmup 5 --no-cpu-baseline --no-parity --no-cfgA > $OUT/bench512_$f.json 2> $OUT/bench512_$f.err
 done
 python - <<'PY'
 import json, glob

@@ -8,7 +8,7 @@ OUT=${1:-gpurun_out/r02_dp}
 mkdir -p $OUT
 export ASR_BENCH_DEVICE=0 ASR_BENCH_BACKEND=gloo ASR_DP_COLLECTIVE=torch
 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 \
-    bench.py --gpus 2 --steps 10 --warmup 3 > $OUT/bench_dp2.json 2> $OUT/bench_dp2.err
+    bench.py --full --gpus 2 --steps 10 --warmup 3 > $OUT/bench_dp2.json 2> $OUT/bench_dp2.err
 echo "rc=$?"
 tail -3 $OUT/bench_dp2.err
 python - <<PY

@@ -9,7 +9,7 @@ timeout 200 python -m pytest tests/test_gpu_ops.py tests/test_gpu_model.py -q --
 echo "tests rc=$? $(grep -E 'passed|failed' $OUT/tests.log | tail -1)"
 grep -E "^(FAILED|ERROR)|^E  " $OUT/tests.log | head -30
 for v in 1 0; do
-  ASR_LSTM_CLUSTER_F32=$v timeout 120 python bench.py --units 128 --layers 2 --dtype f32 --classes 39 --keep-prob 0.5 \
+  ASR_LSTM_CLUSTER_F32=$v timeout 120 python bench.py --full --units 128 --layers 2 --dtype f32 --classes 39 --keep-prob 0.5 \
     --steps 20 --warmup 3 --no-cfgA --no-cpu-baseline > $OUT/bench_$v.json 2> $OUT/bench_$v.err
   OUT=$OUT V=$v python - <<'PY'
 import json, os

@@ -6,9 +6,9 @@ OUT=${1:-gpurun_out/r02_c5}
 mkdir -p $OUT
 timeout 1500 python -m pytest tests -m gpu -q --durations=15 > $OUT/gpu_tests.log 2>&1
 echo "gpu tests rc=$? $(tail -1 $OUT/gpu_tests.log)"
-timeout 600 python bench.py --steps 20 --warmup 5 > $OUT/bench20.json 2> $OUT/bench20.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $OUT/bench20.json 2> $OUT/bench20.err
 echo "bench20 rc=$?"
-timeout 300 python bench.py --no-cpu-baseline --no-parity --no-cfgA > $OUT/bench100.json 2> $OUT/bench100.err
+timeout 300 python bench.py --full --no-cpu-baseline --no-parity --no-cfgA > $OUT/bench100.json 2> $OUT/bench100.err
 echo "bench100 rc=$?"
 OUT=$OUT python - <<'PY'
 import json, glob, os

@@ -7,7 +7,7 @@ timeout 150 python -m pytest tests/test_gpu_ops.py -q --tb=short -m gpu -k "(gra
 echo "tests rc=$? $(grep -E 'passed|failed' $OUT/tests.log | tail -1)"
 grep -E "^(FAILED|ERROR)|^E  " $OUT/tests.log | head -30
 for v in 1 0; do
-  ASR_LSTM_CLUSTER_320=$v timeout 100 python bench.py --units 320 --steps 20 --warmup 3 --no-cfgA --no-cpu-baseline > $OUT/bench_$v.json 2> $OUT/bench_$v.err
+  ASR_LSTM_CLUSTER_320=$v timeout 100 python bench.py --full --units 320 --steps 20 --warmup 3 --no-cfgA --no-cpu-baseline > $OUT/bench_$v.json 2> $OUT/bench_$v.err
   OUT=$OUT V=$v python - <<'PY'
 import json, os
 d = json.load(open('%s/bench_%s.json' % (os.environ['OUT'], os.environ['V']))); k = d['kernels']; p = d.get('parity') or {}

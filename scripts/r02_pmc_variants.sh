@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 run() {
   local name=$1; shift
   for c in FETCH_SIZE WRITE_SIZE; do
-    timeout 40 rocprofv3 --pmc $c --kernel-trace -d $OUT/${name}_$c -o pmc -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-parity --no-cfgA "$@" > $OUT/${name}_$c.log 2>&1
+    timeout 40 rocprofv3 --pmc $c --kernel-trace -d $OUT/${name}_$c -o pmc -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-parity --no-cfgA "$@" > $OUT/${name}_$c.log 2>&1
     DB=$(find $OUT/${name}_$c -name '*.db' | head -1)
     python scripts/rocpd_pmc.py "$DB" lstm_ > $OUT/${name}_$c.txt
     cut -c1-150 $OUT/${name}_$c.txt

@@ -8,7 +8,7 @@ mkdir -p $OUT
 timeout 900 python -m pytest tests -m gpu -q -x -k "$KEXPR" > $OUT/tests.log 2>&1
 echo "tests rc=$? $(grep -E 'passed|failed' $OUT/tests.log | tail -1)"
 grep -E "^E |Error" $OUT/tests.log | head -20
-timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-cfgA > $OUT/bench20.json 2> $OUT/bench20.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-cfgA > $OUT/bench20.json 2> $OUT/bench20.err
 OUT=$OUT python - <<'PY'
 import json, os
 d = json.load(open(os.environ['OUT'] + '/bench20.json')); k = d['kernels']

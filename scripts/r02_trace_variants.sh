@@ -6,7 +6,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 run() {  # name, bench args...
   local name=$1; shift
-  timeout 60 rocprofv3 --kernel-trace --stats -d $OUT/$name -o bench -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-parity --no-cfgA "$@" > $OUT/$name.log 2>&1
+  timeout 60 rocprofv3 --kernel-trace --stats -d $OUT/$name -o bench -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-parity --no-cfgA "$@" > $OUT/$name.log 2>&1
   DB=$(find $OUT/$name -name '*.db' | head -1)
   python scripts/rocpd_stats.py "$DB" $OUT/${name}_stats.md > /dev/null
   head -12 $OUT/${name}_stats.md | cut -c1-160

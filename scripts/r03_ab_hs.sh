@@ -5,8 +5,8 @@ OUT=${1:-gpurun_out/r03_hs}
 mkdir -p $OUT
 Q="--no-aux --no-cfgA --no-parity --no-cpu-baseline"
 for HSV in 64 32; do
-  ASR_LSTM_FWD_HS=$HSV timeout 120 python bench.py --steps 20 --warmup 5 $Q > $OUT/b256_hs$HSV.json 2> $OUT/b256_hs$HSV.err
-  ASR_LSTM_FWD_HS=$HSV timeout 120 python bench.py --steps 10 --warmup 3 --units 512 --batch 32 $Q > $OUT/b512_hs$HSV.json 2> $OUT/b512_hs$HSV.err
+  ASR_LSTM_FWD_HS=$HSV timeout 120 python bench.py --full --steps 20 --warmup 5 $Q > $OUT/b256_hs$HSV.json 2> $OUT/b256_hs$HSV.err
+  ASR_LSTM_FWD_HS=$HSV timeout 120 python bench.py --full --steps 10 --warmup 3 --units 512 --batch 32 $Q > $OUT/b512_hs$HSV.json 2> $OUT/b512_hs$HSV.err
 done
 ASR_LSTM_FWD_HS=32 timeout 300 python -m pytest tests/test_gpu_ops.py -q -k "cluster" > $OUT/tests_hs32.log 2>&1
 echo "cluster tests with HS=32: $(tail -1 $OUT/tests_hs32.log)"

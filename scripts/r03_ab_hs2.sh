@@ -6,8 +6,8 @@ mkdir -p $OUT
 Q="--no-aux --no-cfgA --no-parity --no-cpu-baseline"
 run() {  # name, env...
   local name=$1; shift
-  env "$@" timeout 120 python bench.py --steps 20 --warmup 5 $Q > $OUT/b256_$name.json 2> $OUT/b256_$name.err
-  env "$@" timeout 120 python bench.py --steps 10 --warmup 3 --units 512 --batch 32 $Q > $OUT/b512_$name.json 2> $OUT/b512_$name.err
+  env "$@" timeout 120 python bench.py --full --steps 20 --warmup 5 $Q > $OUT/b256_$name.json 2> $OUT/b256_$name.err
+  env "$@" timeout 120 python bench.py --full --steps 10 --warmup 3 --units 512 --batch 32 $Q > $OUT/b512_$name.json 2> $OUT/b512_$name.err
 }
 run base X=1
 run fwd32 ASR_LSTM_FWD_HS=32

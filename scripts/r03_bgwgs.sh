@@ -4,7 +4,7 @@ OUT=${1:-gpurun_out/r03_bgwgs3}
 mkdir -p $OUT
 Q="--no-aux --no-cfgA --no-parity --no-cpu-baseline"
 for V in 64 96 128 192 256; do
-  ASR_BG_WGS=$V timeout 120 python bench.py --steps 20 --warmup 5 $Q > $OUT/b256_w$V.json 2>> $OUT/err.log
+  ASR_BG_WGS=$V timeout 120 python bench.py --full --steps 20 --warmup 5 $Q > $OUT/b256_w$V.json 2>> $OUT/err.log
 done
 python - <<PY
 import json, glob

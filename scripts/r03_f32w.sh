@@ -19,7 +19,7 @@ PY
 Q="--no-aux --no-cfgA --no-parity --no-cpu-baseline --dtype f32"
 run() {  # name env... -- args
   local name=$1; shift
-  env "$@" timeout 200 python bench.py $Q $ARGS > $OUT/$name.json 2> $OUT/$name.err
+  env "$@" timeout 200 python bench.py --full $Q $ARGS > $OUT/$name.json 2> $OUT/$name.err
 }
 ARGS="--steps 10 --warmup 3 --units 128 --layers 2 --classes 39 --keep-prob 0.5"; run a128 X=1
 ARGS="--steps 5 --warmup 2 --units 256 --layers 5"; run w256_on X=1; run w256_off ASR_LSTM_CLUSTER_F32_WIDE=0

@@ -5,10 +5,10 @@ set -u
 OUT=${1:-gpurun_out/r03_final}
 mkdir -p $OUT
 export TMPDIR=/tmp
-( time timeout 420 python bench.py --steps 20 --warmup 5 > $OUT/bench20.json 2> $OUT/bench20.err ) 2> $OUT/bench20.time
+( time timeout 420 python bench.py --full --steps 20 --warmup 5 > $OUT/bench20.json 2> $OUT/bench20.err ) 2> $OUT/bench20.time
 echo "bench20 rc=$? $(grep real $OUT/bench20.time)"
 grep "bench " $OUT/bench20.err | tail -30
-( time timeout 420 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err ) 2> $OUT/bench_default.time
+( time timeout 420 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err ) 2> $OUT/bench_default.time
 echo "bench default rc=$? $(grep real $OUT/bench_default.time)"
 bash scripts/r03_trace.sh $OUT/trace > $OUT/trace.log 2>&1
 bash scripts/r03_pmc.sh $OUT/pmc > $OUT/pmc.log 2>&1

@@ -7,11 +7,11 @@ mkdir -p $OUT
 Q="--no-aux --no-cfgA --no-parity --no-cpu-baseline"
 for F in 1 0 1 0; do
   for i in a; do
-  ASR_FORK_ONCE=$F timeout 120 python bench.py --steps 30 --warmup 5 $Q > $OUT/b256_f${F}_$RANDOM.json 2>> $OUT/err.log
+  ASR_FORK_ONCE=$F timeout 120 python bench.py --full --steps 30 --warmup 5 $Q > $OUT/b256_f${F}_$RANDOM.json 2>> $OUT/err.log
   done
 done
-ASR_FORK_ONCE=1 timeout 120 python bench.py --steps 10 --warmup 3 --units 512 --batch 32 $Q > $OUT/b512_f1.json 2>> $OUT/err.log
-ASR_FORK_ONCE=0 timeout 120 python bench.py --steps 10 --warmup 3 --units 512 --batch 32 $Q > $OUT/b512_f0.json 2>> $OUT/err.log
+ASR_FORK_ONCE=1 timeout 120 python bench.py --full --steps 10 --warmup 3 --units 512 --batch 32 $Q > $OUT/b512_f1.json 2>> $OUT/err.log
+ASR_FORK_ONCE=0 timeout 120 python bench.py --full --steps 10 --warmup 3 --units 512 --batch 32 $Q > $OUT/b512_f0.json 2>> $OUT/err.log
 python - <<PY
 import json, glob
 for p in sorted(glob.glob('$OUT/b*.json')):

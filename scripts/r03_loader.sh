@@ -7,11 +7,11 @@ timeout 900 python -m pytest tests/test_gpu_ops.py -q -x -m gpu -k "cluster or l
 tail -4 $OUT/tests.log
 Q="--no-aux --no-cfgA --no-parity --no-cpu-baseline"
 for F in 1 0 1 0; do
-  ASR_LSTM_LOADER=$F timeout 120 python bench.py --steps 30 --warmup 5 $Q > $OUT/b256_l${F}_$RANDOM.json 2>> $OUT/err.log
+  ASR_LSTM_LOADER=$F timeout 120 python bench.py --full --steps 30 --warmup 5 $Q > $OUT/b256_l${F}_$RANDOM.json 2>> $OUT/err.log
 done
 for F in 1 0; do
-  ASR_LSTM_LOADER=$F timeout 120 python bench.py --steps 10 --warmup 3 --units 512 --batch 32 $Q > $OUT/b512_l$F.json 2>> $OUT/err.log
-  ASR_LSTM_LOADER=$F timeout 120 python bench.py --steps 10 --warmup 3 --units 512 --batch 32 --tmax 1600 --tmin 800 $Q > $OUT/b512T_l$F.json 2>> $OUT/err.log
+  ASR_LSTM_LOADER=$F timeout 120 python bench.py --full --steps 10 --warmup 3 --units 512 --batch 32 $Q > $OUT/b512_l$F.json 2>> $OUT/err.log
+  ASR_LSTM_LOADER=$F timeout 120 python bench.py --full --steps 10 --warmup 3 --units 512 --batch 32 --tmax 1600 --tmin 800 $Q > $OUT/b512T_l$F.json 2>> $OUT/err.log
 done
 python - <<PY
 import json, glob

@@ -6,7 +6,7 @@ OUT=${1:-gpurun_out/r03_pmc_util}
 mkdir -p $OUT
 export TMPDIR=/tmp
 for c in MfmaUtil SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_BUSY_CYCLES; do
-  timeout 300 rocprofv3 --pmc $c --kernel-trace -d $OUT/h_$c -o pmc -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-cfgA --no-aux > $OUT/h_$c.log 2>&1
+  timeout 300 rocprofv3 --pmc $c --kernel-trace -d $OUT/h_$c -o pmc -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-cfgA --no-aux > $OUT/h_$c.log 2>&1
   DB=$(find $OUT/h_$c -name '*.db' | head -1)
   [ -n "$DB" ] && python scripts/rocpd_pmc.py "$DB" > $OUT/headline_$c.txt
   rm -rf $OUT/h_$c

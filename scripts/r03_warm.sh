@@ -4,7 +4,7 @@ OUT=${1:-gpurun_out/r03_warm}
 mkdir -p $OUT
 Q="--no-aux --no-cfgA --no-parity --no-cpu-baseline"
 for V in 1 0 1 0; do
-  ASR_WARM_BPTT=$V timeout 120 python bench.py --steps 20 --warmup 5 $Q > $OUT/b256_warm${V}_$RANDOM.json 2>> $OUT/err.log
+  ASR_WARM_BPTT=$V timeout 120 python bench.py --full --steps 20 --warmup 5 $Q > $OUT/b256_warm${V}_$RANDOM.json 2>> $OUT/err.log
 done
 python - <<PY
 import json, glob

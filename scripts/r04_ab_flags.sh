@@ -7,9 +7,9 @@ FLAGS=${2:-"0 1024"}
 mkdir -p $OUT
 Q="--no-aux --no-cfgA --no-parity --no-cpu-baseline"
 for F in $FLAGS; do
-  ASR_LSTM_DFLAGS=$F timeout 120 python bench.py --steps 20 --warmup 5 $Q > $OUT/b256_f$F.json 2> $OUT/b256_f$F.err
-  ASR_LSTM_DFLAGS=$F timeout 120 python bench.py --steps 10 --warmup 3 --units 512 --batch 32 $Q > $OUT/b512_f$F.json 2> $OUT/b512_f$F.err
-  ASR_LSTM_DFLAGS=$F timeout 120 python bench.py --steps 10 --warmup 3 --units 320 $Q > $OUT/b320_f$F.json 2> $OUT/b320_f$F.err
+  ASR_LSTM_DFLAGS=$F timeout 120 python bench.py --full --steps 20 --warmup 5 $Q > $OUT/b256_f$F.json 2> $OUT/b256_f$F.err
+  ASR_LSTM_DFLAGS=$F timeout 120 python bench.py --full --steps 10 --warmup 3 --units 512 --batch 32 $Q > $OUT/b512_f$F.json 2> $OUT/b512_f$F.err
+  ASR_LSTM_DFLAGS=$F timeout 120 python bench.py --full --steps 10 --warmup 3 --units 320 $Q > $OUT/b320_f$F.json 2> $OUT/b320_f$F.err
 done
 python - <<PY
 import json, glob

@@ -9,7 +9,7 @@ timeout 600 python -m pytest tests/test_gpu_configs.py -m gpu -x -q -k "cfgD or 
 tail -3 $OUT/tests_cfg.txt | cut -c1-250
 for v in "1 1" "0 1" "1 0" "0 0"; do
   set -- $v
-  ASR_DEC_CELL_GEMM=$1 ASR_ATT_TAIL=$2 timeout 300 python bench.py --steps 2 --warmup 1 --no-cfgA --no-parity --no-cpu-baseline --aux cfgD,cfgE > $OUT/b_$1$2.out 2> $OUT/b_$1$2.err
+  ASR_DEC_CELL_GEMM=$1 ASR_ATT_TAIL=$2 timeout 300 python bench.py --full --steps 2 --warmup 1 --no-cfgA --no-parity --no-cpu-baseline --aux cfgD,cfgE > $OUT/b_$1$2.out 2> $OUT/b_$1$2.err
   tail -1 $OUT/b_$1$2.out | python -c "
 import sys,json
 d=json.loads(sys.stdin.read())

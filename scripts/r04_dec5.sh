@@ -8,7 +8,7 @@ grep -E "^FAILED|passed|failed" $OUT/tests_att.txt | cut -c1-250 | tail -12
 timeout 900 python -m pytest tests/test_gpu_configs.py -m gpu -q -s -k "cfgD or cfgE" > $OUT/tests_cfg.txt 2>&1
 grep -E "^FAILED|passed|failed" $OUT/tests_cfg.txt | cut -c1-250 | tail -12
 for v in 1 0; do
-  ASR_DEC_CELL_BF16=$v timeout 300 python bench.py --steps 2 --warmup 1 --no-cfgA --no-parity --no-cpu-baseline --aux cfgD,cfgE > $OUT/b_$v.out 2> $OUT/b_$v.err
+  ASR_DEC_CELL_BF16=$v timeout 300 python bench.py --full --steps 2 --warmup 1 --no-cfgA --no-parity --no-cpu-baseline --aux cfgD,cfgE > $OUT/b_$v.out 2> $OUT/b_$v.err
   tail -1 $OUT/b_$v.out | python -c "
 import sys,json
 d=json.loads(sys.stdin.read())

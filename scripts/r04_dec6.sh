@@ -5,7 +5,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 600 python -m pytest tests/test_gpu_attention.py tests/test_gpu_ops.py -m gpu -q -x > $OUT/tests.txt 2>&1
 grep -E "^FAILED|passed|failed" $OUT/tests.txt | cut -c1-250 | tail -5
-timeout 300 python bench.py --steps 2 --warmup 1 --no-cfgA --no-parity --no-cpu-baseline --aux cfgD,cfgE > $OUT/b.out 2> $OUT/b.err
+timeout 300 python bench.py --full --steps 2 --warmup 1 --no-cfgA --no-parity --no-cpu-baseline --aux cfgD,cfgE > $OUT/b.out 2> $OUT/b.err
 tail -1 $OUT/b.out | python -c "
 import sys,json
 d=json.loads(sys.stdin.read())

@@ -7,10 +7,10 @@ export TMPDIR=/tmp
 ( time timeout 1500 python -m pytest tests -m gpu -q > $OUT/gpu_tests.txt 2>&1 ) 2> $OUT/gpu_tests.time
 grep -E "^FAILED|passed|failed" $OUT/gpu_tests.txt | cut -c1-300 | tail -8; grep real $OUT/gpu_tests.time
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 | tee $OUT/smoke.txt
-( time timeout 900 python bench.py > $OUT/bench_default.out 2> $OUT/bench_default.err ) 2> $OUT/bench_default.time
+( time timeout 900 python bench.py --full > $OUT/bench_default.out 2> $OUT/bench_default.err ) 2> $OUT/bench_default.time
 echo "bench rc=$? $(grep real $OUT/bench_default.time)"
 tail -c 8000 $OUT/bench_default.out | tail -1 | python -c "import sys,json; l=sys.stdin.read(); print(len(l)); d=json.loads(l); print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['cpu_baseline']['value']); print({k:(d[k]['ms_per_step'],d[k]['host_issue_mean'],d[k]['host_wait_for_device_mean']) for k in ('cfgA','cfgC','cfgD','cfgE') if k in d and 'ms_per_step' in d[k]})"
 cp bench_full.json $OUT/bench_full_default.json
-( time timeout 900 python bench.py --steps 20 --warmup 5 > $OUT/bench20.out 2> $OUT/bench20.err ) 2> $OUT/bench20.time
+( time timeout 900 python bench.py --full --steps 20 --warmup 5 > $OUT/bench20.out 2> $OUT/bench20.err ) 2> $OUT/bench20.time
 echo "bench20 rc=$? $(grep real $OUT/bench20.time)"; cp bench_full.json $OUT/bench20_full.json
 tail -1 $OUT/bench20.out | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['kernels'] if 'kernels' in d else '')"

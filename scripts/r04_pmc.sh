@@ -8,7 +8,7 @@ EXTRA=${2:-}
 mkdir -p $OUT
 export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $c --kernel-trace -d $OUT/$c -o pmc -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-cfgA --no-aux $EXTRA > $OUT/$c.log 2>&1
+  rocprofv3 --pmc $c --kernel-trace -d $OUT/$c -o pmc -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-cfgA --no-aux $EXTRA > $OUT/$c.log 2>&1
   DB=$(find $OUT/$c -name '*.db' | head -1)
   python scripts/rocpd_pmc.py "$DB" > $OUT/$c.txt
   head -8 $OUT/$c.txt | cut -c1-150

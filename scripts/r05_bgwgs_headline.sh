@@ -4,7 +4,7 @@ set -u
 OUT=${1:-gpurun_out/r05_bgwgs_headline}
 mkdir -p $OUT
 for W in ${WLIST:-128 16 32 64 128 32}; do
-  ASR_BG_WGS=$W python bench.py --steps 40 --warmup 10 --no-cpu-baseline --no-parity --no-cfgA --no-aux > $OUT/o.out 2> $OUT/o.err
+  ASR_BG_WGS=$W python bench.py --full --steps 40 --warmup 10 --no-cpu-baseline --no-parity --no-cfgA --no-aux > $OUT/o.out 2> $OUT/o.err
   python - <<PY | tee -a $OUT/ab.txt
 import json
 d = json.load(open('bench_full.json'))

@@ -6,7 +6,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 1200 python -m pytest tests/test_gpu_ops.py tests/test_gpu_model.py tests/test_gpu_configs.py tests/test_gpu_determinism.py -q -x -k "conv or vgg or pool or cfgC" > $OUT/tests.txt 2>&1
 tail -3 $OUT/tests.txt | cut -c1-300
-python bench.py --steps 20 --warmup 5 --no-cfgA --aux cfgC --no-cpu-baseline > $OUT/bench.out 2> $OUT/bench.err
+python bench.py --full --steps 20 --warmup 5 --no-cfgA --aux cfgC --no-cpu-baseline > $OUT/bench.out 2> $OUT/bench.err
 cp bench_full.json $OUT/bench_full.json
 python - <<PY
 import json

@@ -4,7 +4,7 @@ set -u
 OUT=${1:-gpurun_out/r05_cfgC_bench_ab}
 mkdir -p $OUT
 for A in 0 1 0 1; do
-  ASR_VGG_WGRAD_SIDE=$A python bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-parity --no-cfgA --aux cfgC --aux-steps 10 > $OUT/o.out 2> $OUT/o.err
+  ASR_VGG_WGRAD_SIDE=$A python bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-parity --no-cfgA --aux cfgC --aux-steps 10 > $OUT/o.out 2> $OUT/o.err
   python - <<PY | tee -a $OUT/ab.txt
 import json
 d = json.load(open('bench_full.json'))['cfgC']

@@ -4,7 +4,7 @@ set -u
 OUT=${1:-gpurun_out/r05_outliers}
 mkdir -p $OUT
 for G in 1 0 1 0 1 0; do
-  ASR_BENCH_GC=$G python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-parity --no-cfgA --no-aux > $OUT/o.out 2> $OUT/o.err
+  ASR_BENCH_GC=$G python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-parity --no-cfgA --no-aux > $OUT/o.out 2> $OUT/o.err
   python - <<PY | tee -a $OUT/ab.txt
 import json
 d = json.load(open('bench_full.json'))

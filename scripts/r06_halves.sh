@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 ( time timeout 1200 python -m pytest tests/test_gpu_configs.py -m gpu -q -x -k "cfgC or two_pipelines" > $OUT/tests_cfg.txt 2>&1 ) 2> $OUT/tests_cfg.time
 tail -3 $OUT/tests_cfg.txt | cut -c1-300; grep real $OUT/tests_cfg.time
 for hv in 0 1; do
-  ASR_ENC_HALVES=$hv timeout 600 python bench.py --steps 5 --warmup 2 --no-cfgA --no-cpu-baseline --no-parity --aux cfgC,cfgD,cfgE --aux-steps 8 --aux-warmup 3 > $OUT/bench_h$hv.out 2> $OUT/bench_h$hv.err
+  ASR_ENC_HALVES=$hv timeout 600 python bench.py --full --steps 5 --warmup 2 --no-cfgA --no-cpu-baseline --no-parity --aux cfgC,cfgD,cfgE --aux-steps 8 --aux-warmup 3 > $OUT/bench_h$hv.out 2> $OUT/bench_h$hv.err
   cp bench_full.json $OUT/bench_h${hv}_full.json
   python - $OUT/bench_h${hv}_full.json $hv <<'PY'
 import json, sys

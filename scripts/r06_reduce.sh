@@ -7,7 +7,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 ( time timeout 1500 python -m pytest tests/test_gpu_ops.py tests/test_gpu_determinism.py -m gpu -q -x -k "gemm or conv or vgg or determin or wgrad" > $OUT/tests.txt 2>&1 ) 2> $OUT/tests.time
 tail -2 $OUT/tests.txt | cut -c1-300; grep real $OUT/tests.time
-timeout 600 python bench.py --steps 10 --warmup 3 --no-cfgA --no-cpu-baseline --no-parity --aux cfgC,cfgD,cfgE --aux-steps 8 --aux-warmup 3 > $OUT/bench.out 2> $OUT/bench.err
+timeout 600 python bench.py --full --steps 10 --warmup 3 --no-cfgA --no-cpu-baseline --no-parity --aux cfgC,cfgD,cfgE --aux-steps 8 --aux-warmup 3 > $OUT/bench.out 2> $OUT/bench.err
 cp bench_full.json $OUT/bench_full.json
 python - $OUT/bench_full.json <<'PY'
 import json, sys

@@ -1,4 +1,4 @@
-"""Loader of tests/golden/tfshim_v1.npz: what the REFERENCE'S OWN model code computed when it was executed on the eager
+"""Loader of tests/golden/tfshim_v1[_b].npz: what the REFERENCE'S OWN model code computed when executed on the eager
 TensorFlow stand-in (generator: tests/golden/make_golden_tfshim.py, which needs /root/reference; the fixture travels).
 
 A case = one run of reference code.  Variables are not stored: each one is uniform(-scale, scale) from its own seed
@@ -9,7 +9,9 @@ import os
 
 import numpy as np
 
-PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'tfshim_v1.npz')
+# one fixture in two files (every other array by name in the second), so that each file stays under 1 MiB
+PATHS = tuple(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', n)
+              for n in ('tfshim_v1.npz', 'tfshim_v1_b.npz'))
 STRIDE = 97
 _cache = {}
 
@@ -20,8 +22,11 @@ def var_values(shape, seed, scale):
 
 def load():
     if 'z' not in _cache:
-        z = np.load(PATH)
-        _cache['z'] = {k: z[k] for k in z.files}
+        z = {}
+        for path in PATHS:
+            with np.load(path) as f:
+                z.update((k, f[k]) for k in f.files)
+        _cache['z'] = z
         _cache['meta'] = json.loads(bytes(_cache['z']['meta_json']).decode())
     return _cache['z'], _cache['meta']
 

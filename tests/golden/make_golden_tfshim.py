@@ -1,5 +1,5 @@
 """Runs the reference's OWN model code (unchanged files under /root/reference) on the eager TensorFlow stand-in of
-tests/golden/tf_shim and records what it computes: tests/golden/tfshim_v1.npz.
+tests/golden/tf_shim and records what it computes: tests/golden/tfshim_v1.npz + tfshim_v1_b.npz.
 
     python tests/golden/make_golden_tfshim.py            # needs /root/reference; the GPU box never runs this
 
@@ -420,8 +420,13 @@ def main():
         META[c]['vars'] = META_VARS[c]
     OUT['meta_json'] = np.frombuffer(json.dumps(META, sort_keys=True).encode(), dtype=np.uint8)
     path = sys.argv[sys.argv.index('--out') + 1] if '--out' in sys.argv else os.path.join(HERE, 'tfshim_v1.npz')
-    np.savez_compressed(path, **OUT)
-    print('%d arrays, %d cases -> %s (%.1f KB)' % (len(OUT), len(META), path, os.path.getsize(path) / 1024))
+    # two files, each under 1 MiB: every other array (sorted by name) goes to <path>_b.npz (tests/_tfshim.py joins them)
+    names = sorted(OUT)
+    second = path[:-len('.npz')] + '_b.npz'
+    np.savez_compressed(path, **{k: OUT[k] for k in names[0::2]})
+    np.savez_compressed(second, **{k: OUT[k] for k in names[1::2]})
+    print('%d arrays, %d cases -> %s + %s (%.1f + %.1f KB)' % (len(OUT), len(META), path, second,
+                                                         os.path.getsize(path) / 1024, os.path.getsize(second) / 1024))
     for c in sorted(META):
         print(' ', c, META[c].get('none_grads') or '')
 

@@ -1068,6 +1068,29 @@ def test_bench_compact_line_fits_the_drivers_window():
     assert len(lf) <= 6000 and df['roofline']['frac'] > 0 and df['cpu_baseline']['value'] > 0 and df['cfgC']['value'] > 0
 
 
+def test_bench_compact_line_of_a_plain_run():
+    """A plain `bench.py` run (no --full) times the headline only: its object has no h2d leg, parity, CPU baseline,
+    auxiliary entries or full-result file.  compact_line must still carry every contract key, and the entries that
+    were not run are null or absent, never invented."""
+    import json
+    bench, root = _load_bench_module()
+    r6 = json.load(open(os.path.join(root, 'profiles', 'r06_bench_default.json')))
+    keep = ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
+            'vs_baseline', 'dtype', 'data', 'config', 'step_ms', 'final_loss', 'cluster_handoff_flags', 'kernels', 'roofline')
+    plain = {k: r6[k] for k in keep}
+    plain.update(h2d_inclusive=None, parity=None, cpu_baseline=None, cfgA=None, full=None)
+    line = bench.compact_line(plain)
+    d = json.loads(line)
+    for k in keep:
+        assert k in d, k
+    assert d['metric'] == r6['metric'] and d['unit'] == 'frames/s' and d['higher_is_better'] is True
+    assert abs(d['value'] - r6['value']) < 1e-4 * r6['value'] and abs(d['ms_per_step'] - r6['ms_per_step']) < 1e-4 * r6['ms_per_step']
+    assert d['parity'] is None and d['cpu_baseline'] is None and d['full'] is None and d['h2d_inclusive'] == {}
+    for k in ('cfgA', 'cfgC', 'cfgD', 'cfgE', 'decode', 'bgru', 'blstmp', 'batch_scaling', 'headline_f32'):
+        assert k not in d, k
+    assert d['roofline']['frac'] > 0 and len(line) < 6000
+
+
 def test_bench_conv_roofline_credits_chunked_calls_with_their_own_images():
     """VERDICT r05 weak 3 / ADVICE r05: with the VGG forward going through in runs of images a step makes several calls
     per convolution kernel, each on PART of the batch; bench.conv_roofline must credit every timed call with the images
