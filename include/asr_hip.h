@@ -55,7 +55,7 @@ typedef enum {
 } asr_optimizer;
 
 /* ---- lifetime ------------------------------------------------------------ */
-int asr_abi_version(void);                                         /* 5: round 6, additive (asr_lstm_bwd_ex).  4: round 5, additive (asr_conv3x3_bwd_weight_bias, asr_conv3x3_smallc_bwd_weight_bias, asr_debug_* hooks).  3: round 4 (2: additions + the two size changes noted at asr_create_ex / asr_ctc_beam_workspace_bytes; 3: asr_att_decoder grew a trailing field) */
+int asr_abi_version(void);                                         /* 5: round 6, additive (asr_lstm_bwd_ex; later within 5: the asr_conv3x5_* / asr_maxpool3x1_* entry points of cnn_zhang).  4: round 5, additive (asr_conv3x3_bwd_weight_bias, asr_conv3x3_smallc_bwd_weight_bias, asr_debug_* hooks).  3: round 4 (2: additions + the two size changes noted at asr_create_ex / asr_ctc_beam_workspace_bytes; 3: asr_att_decoder grew a trailing field) */
 int asr_create(asr_handle** out, int device);                        /* 192 MiB scratch arena */
 int asr_create_ex(asr_handle** out, int device, size_t scratch_bytes); /* >= 96 MiB (64 MiB of it: recurrence exchange areas) */
 size_t asr_scratch_bytes(asr_handle* h);
@@ -250,6 +250,42 @@ int asr_relu_bwd(asr_handle* h, int dtype, const float* dout, const void* out, c
    asr_relu_bwd_drop over the undropped output, without forming the mask */
 int asr_relu_bwd_scaled(asr_handle* h, int dtype, const float* dout, const void* out, size_t n, float keep, void* dpre,
                         asr_stream s);
+
+/* ---- the cnn_zhang convolution stack (later within ABI version 5, additive) ------------------------- *
+ * conv_layer 3 (frequency) x 5 (time), SAME, stride 1 (cnn_util.py:50-84) of CNN2..CNN10, cnn_zhang.py:117-146, as
+ * implicit GEMMs with bf16 operands and fp32 accumulation (no patch matrix), Cin and Cout multiples of 64:
+ *   prep_weights: fp32 HWIO master [3][5][Cin][Cout] -> wt_fwd bf16 [Cout][15 Cin] and the flipped-tap image
+ *                 wt_bwd bf16 [Cin][15 Cout] of the data gradient;
+ *   fwd:          out bf16 [N,H,W,Cout] = relu?(conv(x bf16 [N,H,W,Cin]) + bias);
+ *   fwd_drop:     + tf.nn.dropout in the epilogue, bit for bit asr_dropout_apply(keep_prob, seed, offset) of fwd's output;
+ *   bwd_data:     dx fp32 [N,H,W,Cin] = conv of dy bf16 [N,H,W,Cout] with wt_bwd;
+ *   bwd_data_relu: the same with the ReLU / dropout backward of the layer below in the epilogue, exactly as
+ *                 asr_conv3x3_bwd_data_relu (use_drop 0 / 1 / 2) -> dpre_below bf16 [N,H,W,Cin];
+ *   bwd_weight_bias: dw fp32 [15 Cin, Cout] and dbias fp32 [Cout] (NULL: skipped), overwritten; pixel-range slabs in the
+ *                 handle scratch summed in a fixed order (bitwise reproducible), Cin and Cout multiples of 8. */
+int asr_conv3x5_prep_weights(asr_handle* h, const float* w_hwio, int Cin, int Cout, void* wt_fwd, void* wt_bwd,
+                             asr_stream s);
+int asr_conv3x5_fwd(asr_handle* h, const void* x, int N, int H, int W, int Cin, const void* wt_fwd, const float* bias,
+                    int Cout, int relu, void* out, asr_stream s);
+int asr_conv3x5_fwd_drop(asr_handle* h, const void* x, int N, int H, int W, int Cin, const void* wt_fwd,
+                         const float* bias, int Cout, float keep_prob, uint64_t seed, uint64_t offset, void* out,
+                         asr_stream s);
+int asr_conv3x5_bwd_data(asr_handle* h, const void* dy, int N, int H, int W, int Cout, const void* wt_bwd, int Cin,
+                         float* dx, asr_stream s);
+int asr_conv3x5_bwd_data_relu(asr_handle* h, const void* dy, int N, int H, int W, int Cout, const void* wt_bwd, int Cin,
+                              const void* act_below, float keep_prob, uint64_t seed, uint64_t offset, int use_drop,
+                              void* dpre_below, asr_stream s);
+int asr_conv3x5_bwd_weight_bias(asr_handle* h, const void* x, const void* dy, int N, int H, int W, int Cin, int Cout,
+                                float* dw, float* dbias, asr_stream s);
+/* max_pool [3,1] stride [3,1] SAME of CNN1 (cnn_zhang.py:124-128, cnn_util.py:13-28): out [N, ceil(H/3), W, C]; the pad
+ * rows go (3 ceil(H/3) - H) / 2 before and the rest after (F = 40: 1 / 1, F = 41: 0 / 1) and are never selected;
+ * argmax (uint8, 0..2 = row in the window) takes the first of equal values.  use_drop: tf.nn.dropout of the pooled output
+ * in the same pass (== asr_dropout_apply(keep_prob, seed, offset) of it).  C % 4 == 0.
+ * bwd: gather form, din (same dtype and shape as the input) = dout of the window where the row was its maximum, else 0. */
+int asr_maxpool3x1_fwd(asr_handle* h, int dtype, const void* in, int N, int H, int W, int C, void* out, uint8_t* argmax,
+                       float keep_prob, uint64_t seed, uint64_t offset, int use_drop, asr_stream s);
+int asr_maxpool3x1_bwd(asr_handle* h, int dtype, const void* dout, const uint8_t* argmax, int N, int H, int W, int C,
+                       void* din, asr_stream s);
 
 /* ---- LSTM recurrence ------------------------------------------------------ *
  * One layer, `ndir` directions (1 = LSTMEncoder, 2 = BLSTMEncoder), all T steps:

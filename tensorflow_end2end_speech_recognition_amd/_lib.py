@@ -63,6 +63,15 @@ SIGNATURES = {
     'asr_maxpool2x2_bwd': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     'asr_relu_bwd': (_i, [_vp, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
     'asr_maxpool2x2_relu_bwd': (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _f, _u64, _u64, _i, _vp]),
+    # the cnn_zhang convolution stack (later within ABI 5)
+    'asr_conv3x5_prep_weights': (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    'asr_conv3x5_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    'asr_conv3x5_fwd_drop': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _f, _u64, _u64, _vp, _vp]),
+    'asr_conv3x5_bwd_data': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    'asr_conv3x5_bwd_data_relu': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _f, _u64, _u64, _i, _vp, _vp]),
+    'asr_conv3x5_bwd_weight_bias': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'asr_maxpool3x1_fwd': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _f, _u64, _u64, _i, _vp]),
+    'asr_maxpool3x1_bwd': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     'asr_lstm_prep_weights': (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'asr_lstm_prep_layer': (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'asr_lstm_grad_finish': (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp]),

@@ -2,8 +2,8 @@
 
 The registry is the reference's plugin point: an encoder is a class with
 __call__(inputs, inputs_seq_len, keep_prob, is_training) -> (outputs, final_state).
-Keys outside the hot path and its "next" rows (cnn_zhang, vgg_wang, pyramid_blstm, student_*) are not built
-(SURVEY.md section 2 row 6): asking for them raises the same ValueError as an unknown key."""
+Keys of the reference not built here (vgg_wang, pyramid_blstm, student_*) raise the same
+ValueError as an unknown key."""
 from .core.blstm import BLSTMEncoder
 from .core.lstm import LSTMEncoder
 from .core.vgg_blstm import VGGBLSTMEncoder, VGGLSTMEncoder
@@ -11,6 +11,7 @@ from .core.multitask_blstm import MultitaskBLSTMEncoder
 from .core.multitask_lstm import MultitaskLSTMEncoder
 from .core.gru import GRUEncoder, BGRUEncoder
 from .core.cldnn_wang import CLDNNEncoder
+from .core.cnn_zhang import CNNEncoder
 
 ENCODERS = {
     "blstm": BLSTMEncoder,
@@ -22,6 +23,7 @@ ENCODERS = {
     "bgru": BGRUEncoder,
     "gru": GRUEncoder,
     "cldnn_wang": CLDNNEncoder,
+    "cnn_zhang": CNNEncoder,
 }
 
 

@@ -731,6 +731,114 @@ def relu_bwd(dout, out, mask=None, drop=None):
     return dpre
 
 
+# ---------------------------------------------------------------- cnn_zhang convolution stack (3x5 convolutions, 3x1 pool)
+def conv3x5_prep_weights(w_hwio):
+    """fp32 [3,5,Cin,Cout] -> (wt_fwd bf16 [Cout, 15*Cin], wt_bwd bf16 [Cin, 15*Cout]: the flipped-tap image)."""
+    h = _h(w_hwio)
+    _chk(w_hwio, torch.float32, 'w')
+    kh, kw, Cin, Cout = w_hwio.shape
+    if (kh, kw) != (3, 5):
+        raise ValueError('conv3x5_prep_weights: filter is %dx%d' % (kh, kw))
+    wf = torch.empty((Cout, 15 * Cin), dtype=torch.bfloat16, device=w_hwio.device)
+    wb = torch.empty((Cin, 15 * Cout), dtype=torch.bfloat16, device=w_hwio.device)
+    h.check(h.lib.asr_conv3x5_prep_weights(h.h, _p(w_hwio.contiguous()), Cin, Cout, _p(wf), _p(wb), _s()),
+            'asr_conv3x5_prep_weights')
+    return wf, wb
+
+
+def conv3x5_fwd(x_nhwc, wt_fwd, bias, relu=True, out=None):
+    """relu?(conv3x5 SAME(x) + bias): x bf16 [N,H,W,Cin] -> bf16 [N,H,W,Cout] (implicit GEMM)."""
+    h = _h(x_nhwc)
+    _chk(x_nhwc, torch.bfloat16, 'x')
+    N, H, W, Cin = x_nhwc.shape
+    Cout = wt_fwd.shape[0]
+    out = _out_like(out, (N, H, W, Cout), torch.bfloat16, x_nhwc.device, 'conv3x5_fwd')
+    h.check(h.lib.asr_conv3x5_fwd(h.h, _p(x_nhwc), N, H, W, Cin, _p(wt_fwd), _p(bias), Cout, 1 if relu else 0,
+                                  _p(out), _s()), 'asr_conv3x5_fwd')
+    return out
+
+
+def conv3x5_fwd_drop(x_nhwc, wt_fwd, bias, drop, out=None):
+    """dropout_apply(conv3x5_fwd(x, ..., relu=True), *drop) in one launch."""
+    h = _h(x_nhwc)
+    _chk(x_nhwc, torch.bfloat16, 'x')
+    N, H, W, Cin = x_nhwc.shape
+    Cout = wt_fwd.shape[0]
+    out = _out_like(out, (N, H, W, Cout), torch.bfloat16, x_nhwc.device, 'conv3x5_fwd_drop')
+    h.check(h.lib.asr_conv3x5_fwd_drop(h.h, _p(x_nhwc), N, H, W, Cin, _p(wt_fwd), _p(bias), Cout, float(drop[0]),
+                                       int(drop[1]), int(drop[2]), _p(out), _s()), 'asr_conv3x5_fwd_drop')
+    return out
+
+
+def conv3x5_bwd_data(dy_nhwc, wt_bwd):
+    """dx fp32 [N,H,W,Cin] = data gradient of the 3x5 convolution (dy bf16 [N,H,W,Cout])."""
+    h = _h(dy_nhwc)
+    _chk(dy_nhwc, torch.bfloat16, 'dy')
+    N, H, W, Cout = dy_nhwc.shape
+    Cin = wt_bwd.shape[0]
+    dx = torch.empty((N, H, W, Cin), dtype=torch.float32, device=dy_nhwc.device)
+    h.check(h.lib.asr_conv3x5_bwd_data(h.h, _p(dy_nhwc), N, H, W, Cout, _p(wt_bwd), Cin, _p(dx), _s()),
+            'asr_conv3x5_bwd_data')
+    return dx
+
+
+def conv3x5_bwd_data_relu(dy_nhwc, wt_bwd, act_below, drop=None, dropped=False):
+    """relu_bwd(conv3x5_bwd_data(dy, wt_bwd), act_below, drop=drop) in one launch -> bf16 (as conv3x3_bwd_data_relu)."""
+    h = _h(dy_nhwc)
+    _chk(dy_nhwc, torch.bfloat16, 'dy')
+    _chk(act_below, torch.bfloat16, 'act_below')
+    N, H, W, Cout = dy_nhwc.shape
+    Cin = wt_bwd.shape[0]
+    if tuple(act_below.shape) != (N, H, W, Cin):
+        raise ValueError('conv3x5_bwd_data_relu: act_below has shape %s' % (tuple(act_below.shape),))
+    dpre = torch.empty((N, H, W, Cin), dtype=torch.bfloat16, device=dy_nhwc.device)
+    k, sd, off = drop if drop is not None else (1.0, 0, 0)
+    mode = 0 if drop is None else (2 if dropped else 1)
+    h.check(h.lib.asr_conv3x5_bwd_data_relu(h.h, _p(dy_nhwc), N, H, W, Cout, _p(wt_bwd), Cin, _p(act_below), float(k),
+                                            int(sd), int(off), mode, _p(dpre), _s()), 'asr_conv3x5_bwd_data_relu')
+    return dpre
+
+
+def conv3x5_bwd_weight_bias(x_nhwc, dy_nhwc, dw, dbias=None):
+    """dw fp32 [15*Cin, Cout] view of the HWIO gradient, dbias fp32 [Cout] (both overwritten; deterministic)."""
+    h = _h(x_nhwc)
+    _chk(x_nhwc, torch.bfloat16, 'x')
+    _chk(dy_nhwc, torch.bfloat16, 'dy')
+    N, H, W, Cin = x_nhwc.shape
+    Cout = dy_nhwc.shape[3]
+    if dw.numel() != 15 * Cin * Cout or not dw.is_contiguous():
+        raise ValueError('conv3x5_bwd_weight_bias: dw must be a contiguous [15*Cin, Cout] fp32 tensor')
+    if dbias is not None and dbias.numel() != Cout:
+        raise ValueError('conv3x5_bwd_weight_bias: dbias has %d elements, Cout = %d' % (dbias.numel(), Cout))
+    h.check(h.lib.asr_conv3x5_bwd_weight_bias(h.h, _p(x_nhwc), _p(dy_nhwc), N, H, W, Cin, Cout, _p(dw), _p(dbias),
+                                              _s()), 'asr_conv3x5_bwd_weight_bias')
+    return dw, dbias
+
+
+def maxpool3x1_fwd(x_nhwc, drop=None):
+    """max_pool [3,1] / [3,1] SAME over H (+ dropout of the pooled output when drop = (keep, seed, offset)) ->
+    (out [N, ceil(H/3), W, C], argmax uint8)."""
+    h = _h(x_nhwc)
+    dt = dtype_id(x_nhwc.dtype)
+    N, H, W, Cc = x_nhwc.shape
+    out = torch.empty((N, (H + 2) // 3, W, Cc), dtype=x_nhwc.dtype, device=x_nhwc.device)
+    arg = torch.empty(out.shape, dtype=torch.uint8, device=x_nhwc.device)
+    k, sd, off = drop if drop is not None else (1.0, 0, 0)
+    h.check(h.lib.asr_maxpool3x1_fwd(h.h, dt, _p(x_nhwc), N, H, W, Cc, _p(out), _p(arg), float(k), int(sd), int(off),
+                                     int(drop is not None), _s()), 'asr_maxpool3x1_fwd')
+    return out, arg
+
+
+def maxpool3x1_bwd(dout, arg, H):
+    """Gather-form backward of maxpool3x1_fwd: dout [N, ceil(H/3), W, C] -> din [N, H, W, C] (same dtype)."""
+    h = _h(dout)
+    N, _, W, Cc = dout.shape
+    din = torch.empty((N, H, W, Cc), dtype=dout.dtype, device=dout.device)
+    h.check(h.lib.asr_maxpool3x1_bwd(h.h, dtype_id(dout.dtype), _p(dout), _p(arg), N, H, W, Cc, _p(din), _s()),
+            'asr_maxpool3x1_bwd')
+    return din
+
+
 # ---------------------------------------------------------------- LSTM
 def lstm_prep_weights(kernel, bias, din, H, dtype, out=None):
     """kernel [Din+H,4H] fp32 (TF layout), bias [4H] -> dict(wx_il [Din,4H] dtype, bias_il [4H] fp32,
