@@ -55,7 +55,7 @@ typedef enum {
 } asr_optimizer;
 
 /* ---- lifetime ------------------------------------------------------------ */
-int asr_abi_version(void);                                         /* 5: round 6, additive (asr_lstm_bwd_ex; later within 5: the asr_conv3x5_* / asr_maxpool3x1_* entry points of cnn_zhang).  4: round 5, additive (asr_conv3x3_bwd_weight_bias, asr_conv3x3_smallc_bwd_weight_bias, asr_debug_* hooks).  3: round 4 (2: additions + the two size changes noted at asr_create_ex / asr_ctc_beam_workspace_bytes; 3: asr_att_decoder grew a trailing field) */
+int asr_abi_version(void);                                         /* 5: round 6, additive (asr_lstm_bwd_ex; later within 5: the asr_conv3x5_* / asr_maxpool3x1_* entry points of cnn_zhang, then the asr_conv3x4_* / asr_bn_* / asr_softmax_xent_soft entry points of the student CNNs).  4: round 5, additive (asr_conv3x3_bwd_weight_bias, asr_conv3x3_smallc_bwd_weight_bias, asr_debug_* hooks).  3: round 4 (2: additions + the two size changes noted at asr_create_ex / asr_ctc_beam_workspace_bytes; 3: asr_att_decoder grew a trailing field) */
 int asr_create(asr_handle** out, int device);                        /* 192 MiB scratch arena */
 int asr_create_ex(asr_handle** out, int device, size_t scratch_bytes); /* >= 96 MiB (64 MiB of it: recurrence exchange areas) */
 size_t asr_scratch_bytes(asr_handle* h);
@@ -286,6 +286,47 @@ int asr_maxpool3x1_fwd(asr_handle* h, int dtype, const void* in, int N, int H, i
                        float keep_prob, uint64_t seed, uint64_t offset, int use_drop, asr_stream s);
 int asr_maxpool3x1_bwd(asr_handle* h, int dtype, const void* dout, const uint8_t* argmax, int N, int H, int W, int C,
                        void* din, asr_stream s);
+
+/* ---- the student CNNs (later within ABI version 5, additive) ------------------------------------------ *
+ * conv_layer 3 (frequency) x 4 (time), SAME (one column before, two after), stride 1, of CNN2
+ * (student_cnn_ctc.py:111-117, student_cnn_compact_ctc.py, student_cnn_xe.py:103-109, student_cnn_compact_xe.py): the
+ * asr_conv3x5_* kernels on the 12-tap geometry, Cin and Cout multiples of 64.  prep_weights: fp32 HWIO [3][4][Cin][Cout]
+ * -> wt_fwd bf16 [Cout][12 Cin], wt_bwd bf16 [Cin][12 Cout] (flipped taps); fwd: out = relu?(conv(x) + bias), bf16 or
+ * (out_f32) fp32 [N,H,W,Cout]; bwd_data: dx fp32 [N,H,W,Cin]; bwd_weight_bias: dw fp32 [12 Cin, Cout], dbias fp32 [Cout]
+ * (NULL: skipped), overwritten, fixed-order slab sum. */
+int asr_conv3x4_prep_weights(asr_handle* h, const float* w_hwio, int Cin, int Cout, void* wt_fwd, void* wt_bwd,
+                             asr_stream s);
+int asr_conv3x4_fwd(asr_handle* h, const void* x, int N, int H, int W, int Cin, const void* wt_fwd, const float* bias,
+                    int Cout, int relu, int out_f32, void* out, asr_stream s);
+int asr_conv3x4_bwd_data(asr_handle* h, const void* dy, int N, int H, int W, int Cout, const void* wt_bwd, int Cin,
+                         float* dx, asr_stream s);
+int asr_conv3x4_bwd_weight_bias(asr_handle* h, const void* x, const void* dy, int N, int H, int W, int Cin, int Cout,
+                                float* dw, float* dbias, asr_stream s);
+/* batch_normalization (cnn_util.py:87-149: eps 1e-3, momentum 0.9, non-fused) over fp32 NHWC activations
+ * [M = N H W rows, C channels], C % 64 == 0; `ws` holds asr_bn_workspace_bytes(M, C) bytes.
+ *   stats: tf.nn.moments over all M rows (biased variance), fixed-order Chan merges -> stats fp32 [5][C] = mean, var,
+ *          rstd = 1 / sqrt(var + eps), and (when avg_mean / avg_var are given) the pending moving averages
+ *          avg * momentum + stat * (1 - momentum) of the UPDATE_OPS (cnn_util.py:138-145), for the caller to commit;
+ *   apply: tf.nn.batch_normalization(x, mean, var, beta, gamma, eps) (cnn_util.py:133-134; mean / var = the batch
+ *          statistics or the moving averages) fused with the following max_pool: pool 1 = [3,1] / [3,1] SAME over H
+ *          (argmax as asr_maxpool3x1_fwd), pool 0 = [1,1] (identity); out in out_dtype;
+ *   bwd:   dz = gradient at the pooled output (fp32), stats = what asr_bn_stats returned; dgamma = sum(dy xhat), dbeta =
+ *          sum(dy) (fixed order, overwritten), dx = gamma rstd (dy - dbeta / M - xhat dgamma / M), zero where x <= 0
+ *          when relu_gate (x = the ReLU output the statistics were taken over), in out_dtype. */
+size_t asr_bn_workspace_bytes(long long M, int C);
+int asr_bn_stats(asr_handle* h, const float* x, long long M, int C, float eps, float momentum, const float* avg_mean,
+                 const float* avg_var, float* stats, void* ws, asr_stream s);
+int asr_bn_apply(asr_handle* h, int out_dtype, const float* x, int N, int H, int W, int C, const float* mean,
+                 const float* var, const float* gamma, const float* beta, float eps, int pool, void* out,
+                 uint8_t* argmax, asr_stream s);
+int asr_bn_bwd(asr_handle* h, int out_dtype, const float* dz, const uint8_t* argmax, int pool, const float* x, int N,
+               int H, int W, int C, const float* stats, const float* gamma, int relu_gate, float* dgamma, float* dbeta,
+               void* dx, void* ws, asr_stream s);
+/* tf.nn.softmax_cross_entropy_with_logits(labels = targets, logits) of StudentCTC.compute_xe_loss
+ * (student_ctc.py:321-327): row_loss[r] = -sum_c targets log softmax(logits); dlogits (NULL: skipped) = TF's gradient
+ * (softmax(logits) - targets) * grad_scale.  One block per row, fixed reduction order. */
+int asr_softmax_xent_soft(asr_handle* h, const float* logits, const float* targets, int rows, int C, float grad_scale,
+                          float* row_loss, float* dlogits, asr_stream s);
 
 /* ---- LSTM recurrence ------------------------------------------------------ *
  * One layer, `ndir` directions (1 = LSTMEncoder, 2 = BLSTMEncoder), all T steps:

@@ -72,6 +72,16 @@ SIGNATURES = {
     'asr_conv3x5_bwd_weight_bias': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     'asr_maxpool3x1_fwd': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _f, _u64, _u64, _i, _vp]),
     'asr_maxpool3x1_bwd': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    # the student CNNs (later within ABI 5): 3x4 convolutions, batch normalization, soft-target cross-entropy
+    'asr_conv3x4_prep_weights': (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    'asr_conv3x4_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    'asr_conv3x4_bwd_data': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    'asr_conv3x4_bwd_weight_bias': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'asr_bn_workspace_bytes': (_sz, [_i64, _i]),
+    'asr_bn_stats': (_i, [_vp, _vp, _i64, _i, _f, _f, _vp, _vp, _vp, _vp, _vp]),
+    'asr_bn_apply': (_i, [_vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _i, _vp, _vp, _vp]),
+    'asr_bn_bwd': (_i, [_vp, _i, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    'asr_softmax_xent_soft': (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
     'asr_lstm_prep_weights': (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'asr_lstm_prep_layer': (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'asr_lstm_grad_finish': (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp]),

@@ -13,11 +13,25 @@
 //   weight grad    dW[tap Cin + ci][co] = sum_p x[p + s_tap, ci] dOut[p, co]: pixel-range slabs in the scratch arena, then
 //                  a fixed-order sum of the slabs (no float atomics: bitwise reproducible)
 // s_tap = (tap / 5 - 1, tap % 5 - 2): row (frequency) offset -1..1, column (time) offset -2..2.
+// The same kernels run the student CNNs' 3x4 SAME convolution (asr_conv3x4_*): the tap geometry is a template argument
+// (Taps), and the 3x5 instantiations are unchanged.
 #include "common.h"
 
 namespace {
 
 constexpr int KTAPS = 15;
+
+// Tap geometry of the implicit kernels: KW columns per row, and the (row, column) origin (OY, OX) of tap 0, i.e. tap t
+// reads the pixel shifted by (t / KW - OY, t % KW - OX).  3x5 SAME: origin (1, 2) for the forward and for the flipped
+// data-gradient image alike; 3x4 SAME (TensorFlow pads one column before and two after): origin (1, 1) forward,
+// (1, 2) for the flipped image.
+template <int KH_, int KW_, int OY_, int OX_>
+struct Taps {
+  static constexpr int KH = KH_, KW = KW_, OY = OY_, OX = OX_, N = KH_ * KW_;
+};
+typedef Taps<3, 5, 1, 2> Taps35;
+typedef Taps<3, 4, 1, 1> Taps34f;
+typedef Taps<3, 4, 1, 2> Taps34b;
 
 struct Gate35 {                 // epilogue operands of conv3x5_nt_kernel, act == 2 (data gradient) / act == 3 (forward)
   const bf16_t* act;            // act == 2: activation of the layer below, [pixels, Cout of this product]
@@ -49,7 +63,7 @@ __device__ __forceinline__ void gate35_apply(int act, const Gate35& g, size_t e,
 
 // Implicit GEMM: Mpix x Cout x (15 Cin); 256 threads = 2 x 2 waves over a 128 x BN tile, k-tile 64, two LDS stages with
 // the next k-tile's global loads in flight during the MFMAs.  Requires Cin % 64 == 0, Cout % BN == 0.
-template <typename TO, int BN>
+template <typename TO, int BN, typename TP = Taps35>
 __global__ __launch_bounds__(256) void conv3x5_nt_kernel(int Mpix, int H, int W, int Cin, int Cout,
                                                          const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wt,
                                                          TO* __restrict__ Out, const float* __restrict__ bias, int act,
@@ -64,7 +78,7 @@ __global__ __launch_bounds__(256) void conv3x5_nt_kernel(int Mpix, int H, int W,
   const int wm = wave >> 1, wn = wave & 1;
   const int ntn = Cout / BN;
   const int m0 = (blockIdx.x / ntn) * BM, n0 = (blockIdx.x % ntn) * BN;
-  const int K = KTAPS * Cin, nkt = K / BK, kpt = Cin / BK;
+  const int K = TP::N * Cin, nkt = K / BK, kpt = Cin / BK;
   const int HW = H * W;
 
   int py[4], px[4];
@@ -95,7 +109,7 @@ __global__ __launch_bounds__(256) void conv3x5_nt_kernel(int Mpix, int H, int W,
   bf16x8_t ra[4], rb[NB];
   auto gload = [&](int kt) {
     const int tap = kt / kpt, ci0 = (kt - tap * kpt) * BK;
-    const int dy = tap / 5 - 1, dx = tap - (tap / 5) * 5 - 2;
+    const int dy = tap / TP::KW - TP::OY, dx = tap - (tap / TP::KW) * TP::KW - TP::OX;
     const ptrdiff_t sh = ((ptrdiff_t)dy * W + dx) * Cin + ci0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -172,8 +186,10 @@ __global__ __launch_bounds__(256) void conv3x5_nt_kernel(int Mpix, int H, int W,
 
 // weight images from the HWIO fp32 master [3][5][Cin][Cout] (tap = kh * 5 + kw):
 //   wf[co][tap Cin + ci] = w[tap][ci][co],   wb[ci][(14 - tap) Cout + co] = w[tap][ci][co]
+template <int NT = KTAPS>
 __global__ void conv3x5_prep_kernel(const float* __restrict__ w, int Cin, int Cout, bf16_t* __restrict__ wf,
                                     bf16_t* __restrict__ wb) {
+  constexpr int KTAPS = NT;
   const size_t total = (size_t)KTAPS * Cin * Cout;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int co = i % Cout, ci = (i / Cout) % Cin, tap = i / ((size_t)Cin * Cout);
@@ -186,9 +202,11 @@ __global__ void conv3x5_prep_kernel(const float* __restrict__ w, int Cin, int Co
 // Weight gradient, slab z of the pixel range [z kchunk, (z + 1) kchunk): partial[z][m][n], m = tap Cin + ci.  A tile =
 // 128 (tap, ci) columns x 64 pixels gathered from the image, B tile = 64 pixels x 128 output channels; both staged in
 // LDS as [column][pixel] (pixel pairs packed into 32-bit words), XOR-swizzled by 16-byte groups.
+template <typename TP = Taps35>
 __global__ __launch_bounds__(256) void conv3x5_wgrad_kernel(int Mpix, int H, int W, int Cin, int Cout,
                                                             const bf16_t* __restrict__ X, const bf16_t* __restrict__ dY,
                                                             int kchunk, float* __restrict__ partial) {
+  constexpr int KTAPS = TP::N;
   constexpr int BM = 128, BN = 128, BK = 64, LD = BK + 8;
   constexpr int STAGE = (BM + BN) * LD;
   __shared__ __attribute__((aligned(16))) bf16_t S[2 * STAGE];
@@ -205,7 +223,7 @@ __global__ __launch_bounds__(256) void conv3x5_wgrad_kernel(int Mpix, int H, int
   const int mcol = m0 + mvec * 8;                          // first of this thread's 8 (tap, ci) columns
   const bool a_ok = mcol + 8 <= M, b_ok = n0 + mvec * 8 + 8 <= N;
   const int tap = a_ok ? mcol / Cin : 0, ci = a_ok ? mcol - tap * Cin : 0;
-  const int dy = tap / 5 - 1, dx = tap - (tap / 5) * 5 - 2;
+  const int dy = tap / TP::KW - TP::OY, dx = tap - (tap / TP::KW) * TP::KW - TP::OX;
   const ptrdiff_t sh = ((ptrdiff_t)dy * W + dx) * Cin + ci;
   const bf16x8_t zero = {0, 0, 0, 0, 0, 0, 0, 0};
   bf16x8_t ra[2][2], rb[2][2];
@@ -383,6 +401,7 @@ static inline int grid_for(size_t total) {
   return (int)(b < 16384 ? (b ? b : 1) : 16384);
 }
 
+template <typename TP = Taps35>
 static int conv3x5_launch(asr_handle* h, const char* what, const void* x, int N, int H, int W, int Cin, const void* wt,
                           const float* bias, int Cout, int act, const Gate35& gate, bool out_f32, void* out,
                           asr_stream s) {
@@ -399,7 +418,7 @@ static int conv3x5_launch(asr_handle* h, const char* what, const void* x, int N,
   if (blocks >= (1ll << 31)) ASR_FAIL(h, ASR_ERR_UNSUPPORTED, "%s: grid too large", what);
   hipStream_t st = (hipStream_t)s;
 #define ASR_C35(TO, BN) \
-  hipLaunchKernelGGL((conv3x5_nt_kernel<TO, BN>), dim3((unsigned)blocks), dim3(256), 0, st, Mpix, H, W, Cin, Cout, \
+  hipLaunchKernelGGL((conv3x5_nt_kernel<TO, BN, TP>), dim3((unsigned)blocks), dim3(256), 0, st, Mpix, H, W, Cin, Cout, \
                      (const bf16_t*)x, (const bf16_t*)wt, (TO*)out, bias, act, gate)
   if (out_f32) { if (bn128) ASR_C35(float, 128); else ASR_C35(float, 64); }
   else { if (bn128) ASR_C35(bf16_t, 128); else ASR_C35(bf16_t, 64); }
@@ -418,7 +437,7 @@ extern "C" int asr_conv3x5_prep_weights(asr_handle* h, const float* w_hwio, int 
   if (!w_hwio || !wt_fwd || !wt_bwd || Cin < 1 || Cout < 1)
     ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_conv3x5_prep_weights: bad args");
   const size_t total = (size_t)KTAPS * Cin * Cout;
-  hipLaunchKernelGGL(conv3x5_prep_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)s, w_hwio, Cin, Cout,
+  hipLaunchKernelGGL(conv3x5_prep_kernel<KTAPS>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)s, w_hwio, Cin, Cout,
                      (bf16_t*)wt_fwd, (bf16_t*)wt_bwd);
   ASR_CHECK_LAUNCH(h, "asr_conv3x5_prep_weights");
   return ASR_OK;
@@ -457,16 +476,16 @@ extern "C" int asr_conv3x5_bwd_data_relu(asr_handle* h, const void* dy, int N, i
   return conv3x5_launch(h, "asr_conv3x5_bwd_data_relu", dy, N, H, W, Cout, wt_bwd, nullptr, Cin, 2, g, false, dpre_below, s);
 }
 
-extern "C" int asr_conv3x5_bwd_weight_bias(asr_handle* h, const void* x, const void* dy, int N, int H, int W, int Cin,
-                                           int Cout, float* dw, float* dbias, asr_stream s) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  if (!x || !dy || !dw || N < 1 || H < 1 || W < 1)
-    ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_conv3x5_bwd_weight_bias: bad args");
+// weight + bias gradient of the implicit kernels (pixel-range slabs in the scratch arena, fixed-order slab sum)
+template <typename TP>
+static int conv_wgrad_launch(asr_handle* h, const char* what, const void* x, const void* dy, int N, int H, int W, int Cin,
+                             int Cout, float* dw, float* dbias, asr_stream s) {
+  if (!x || !dy || !dw || N < 1 || H < 1 || W < 1) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "%s: bad args", what);
   if (Cin % 8 != 0 || Cout % 8 != 0)
-    ASR_FAIL(h, ASR_ERR_UNSUPPORTED, "asr_conv3x5_bwd_weight_bias: Cin=%d, Cout=%d must be multiples of 8", Cin, Cout);
+    ASR_FAIL(h, ASR_ERR_UNSUPPORTED, "%s: Cin=%d, Cout=%d must be multiples of 8", what, Cin, Cout);
   const long long mp = (long long)N * H * W;
-  if (mp >= (1ll << 31) - 128) ASR_FAIL(h, ASR_ERR_UNSUPPORTED, "asr_conv3x5_bwd_weight_bias: %lld pixels", mp);
-  const int Mpix = (int)mp, M = KTAPS * Cin;
+  if (mp >= (1ll << 31) - 128) ASR_FAIL(h, ASR_ERR_UNSUPPORTED, "%s: %lld pixels", what, mp);
+  const int Mpix = (int)mp, M = TP::N * Cin;
   const size_t slab = (size_t)M * Cout * sizeof(float);
   const size_t room = h->scratch_bytes > ASR_XCH_BYTES ? h->scratch_bytes - ASR_XCH_BYTES : 0;
   const int tm = (M + 127) / 128, tn = (Cout + 127) / 128;
@@ -475,19 +494,25 @@ extern "C" int asr_conv3x5_bwd_weight_bias(asr_handle* h, const void* x, const v
   const int maxS = (Mpix + 511) / 512;
   if (S > maxS) S = maxS;
   if ((size_t)S > room / slab) S = (int)(room / slab);
-  if (S < 1) ASR_FAIL(h, ASR_ERR_WORKSPACE, "asr_conv3x5_bwd_weight_bias: scratch too small");
+  if (S < 1) ASR_FAIL(h, ASR_ERR_WORKSPACE, "%s: scratch too small", what);
   int kchunk = (Mpix + S - 1) / S;
   kchunk = (kchunk + 63) / 64 * 64;
   S = (Mpix + kchunk - 1) / kchunk;
   float* partial = (float*)h->scratch;
   hipStream_t st = (hipStream_t)s;
-  hipLaunchKernelGGL(conv3x5_wgrad_kernel, dim3(tn, tm, S), dim3(256), 0, st, Mpix, H, W, Cin, Cout, (const bf16_t*)x,
-                     (const bf16_t*)dy, kchunk, partial);
+  hipLaunchKernelGGL(conv3x5_wgrad_kernel<TP>, dim3(tn, tm, S), dim3(256), 0, st, Mpix, H, W, Cin, Cout,
+                     (const bf16_t*)x, (const bf16_t*)dy, kchunk, partial);
   const size_t total = (size_t)M * Cout;
   hipLaunchKernelGGL(conv3x5_slab_sum_kernel, dim3(grid_for(total)), dim3(256), 0, st, partial, S, total, dw, 0);
-  ASR_CHECK_LAUNCH(h, "asr_conv3x5_bwd_weight_bias");
+  ASR_CHECK_LAUNCH(h, what);
   if (dbias) return asr_colsum(h, ASR_BF16, dy, Mpix, Cout, Cout, dbias, s);
   return ASR_OK;
+}
+
+extern "C" int asr_conv3x5_bwd_weight_bias(asr_handle* h, const void* x, const void* dy, int N, int H, int W, int Cin,
+                                           int Cout, float* dw, float* dbias, asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  return conv_wgrad_launch<Taps35>(h, "asr_conv3x5_bwd_weight_bias", x, dy, N, H, W, Cin, Cout, dw, dbias, s);
 }
 
 extern "C" int asr_maxpool3x1_fwd(asr_handle* h, int dtype, const void* in, int N, int H, int W, int C, void* out,
@@ -522,4 +547,39 @@ extern "C" int asr_maxpool3x1_bwd(asr_handle* h, int dtype, const void* dout, co
                        (const bf16_t*)dout, argmax, N, H, W, C, (bf16_t*)din);
   ASR_CHECK_LAUNCH(h, "asr_maxpool3x1_bwd");
   return ASR_OK;
+}
+
+// ---- the 3x4 SAME convolution of the student CNNs (CNN2, models/encoders/core/student_cnn_ctc.py:111-117): the same
+// kernels on the 12-tap geometry
+extern "C" int asr_conv3x4_prep_weights(asr_handle* h, const float* w_hwio, int Cin, int Cout, void* wt_fwd, void* wt_bwd,
+                                        asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  if (!w_hwio || !wt_fwd || !wt_bwd || Cin < 1 || Cout < 1)
+    ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_conv3x4_prep_weights: bad args");
+  const size_t total = (size_t)12 * Cin * Cout;
+  hipLaunchKernelGGL(conv3x5_prep_kernel<12>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)s, w_hwio, Cin, Cout,
+                     (bf16_t*)wt_fwd, (bf16_t*)wt_bwd);
+  ASR_CHECK_LAUNCH(h, "asr_conv3x4_prep_weights");
+  return ASR_OK;
+}
+
+extern "C" int asr_conv3x4_fwd(asr_handle* h, const void* x, int N, int H, int W, int Cin, const void* wt_fwd,
+                               const float* bias, int Cout, int relu, int out_f32, void* out, asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  Gate35 g = {nullptr, 1.f, 0, 0, 0};
+  return conv3x5_launch<Taps34f>(h, "asr_conv3x4_fwd", x, N, H, W, Cin, wt_fwd, bias, Cout, relu ? 1 : 0, g,
+                                 out_f32 != 0, out, s);
+}
+
+extern "C" int asr_conv3x4_bwd_data(asr_handle* h, const void* dy, int N, int H, int W, int Cout, const void* wt_bwd,
+                                    int Cin, float* dx, asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  Gate35 g = {nullptr, 1.f, 0, 0, 0};
+  return conv3x5_launch<Taps34b>(h, "asr_conv3x4_bwd_data", dy, N, H, W, Cout, wt_bwd, nullptr, Cin, 0, g, true, dx, s);
+}
+
+extern "C" int asr_conv3x4_bwd_weight_bias(asr_handle* h, const void* x, const void* dy, int N, int H, int W, int Cin,
+                                           int Cout, float* dw, float* dbias, asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  return conv_wgrad_launch<Taps34f>(h, "asr_conv3x4_bwd_weight_bias", x, dy, N, H, W, Cin, Cout, dw, dbias, s);
 }

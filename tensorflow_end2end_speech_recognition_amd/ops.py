@@ -839,6 +839,132 @@ def maxpool3x1_bwd(dout, arg, H):
     return din
 
 
+# ---------------------------------------------------------------- student CNNs (3x4 convolutions, batch normalization)
+def conv3x4_prep_weights(w_hwio):
+    """fp32 [3,4,Cin,Cout] -> (wt_fwd bf16 [Cout, 12*Cin], wt_bwd bf16 [Cin, 12*Cout]: the flipped-tap image)."""
+    h = _h(w_hwio)
+    _chk(w_hwio, torch.float32, 'w')
+    kh, kw, Cin, Cout = w_hwio.shape
+    if (kh, kw) != (3, 4):
+        raise ValueError('conv3x4_prep_weights: filter is %dx%d' % (kh, kw))
+    wf = torch.empty((Cout, 12 * Cin), dtype=torch.bfloat16, device=w_hwio.device)
+    wb = torch.empty((Cin, 12 * Cout), dtype=torch.bfloat16, device=w_hwio.device)
+    h.check(h.lib.asr_conv3x4_prep_weights(h.h, _p(w_hwio.contiguous()), Cin, Cout, _p(wf), _p(wb), _s()),
+            'asr_conv3x4_prep_weights')
+    return wf, wb
+
+
+def conv3x4_fwd(x_nhwc, wt_fwd, bias, relu=True, out_dtype=ASR_BF16):
+    """relu?(conv3x4 SAME(x) + bias): x bf16 [N,H,W,Cin] -> [N,H,W,Cout] in out_dtype (implicit GEMM)."""
+    h = _h(x_nhwc)
+    _chk(x_nhwc, torch.bfloat16, 'x')
+    N, H, W, Cin = x_nhwc.shape
+    Cout = wt_fwd.shape[0]
+    odt = dtype_id(out_dtype)
+    out = torch.empty((N, H, W, Cout), dtype=TORCH_DTYPE[odt], device=x_nhwc.device)
+    h.check(h.lib.asr_conv3x4_fwd(h.h, _p(x_nhwc), N, H, W, Cin, _p(wt_fwd), _p(bias), Cout, 1 if relu else 0,
+                                  int(odt == ASR_F32), _p(out), _s()), 'asr_conv3x4_fwd')
+    return out
+
+
+def conv3x4_bwd_data(dy_nhwc, wt_bwd):
+    """dx fp32 [N,H,W,Cin] = data gradient of the 3x4 convolution (dy bf16 [N,H,W,Cout])."""
+    h = _h(dy_nhwc)
+    _chk(dy_nhwc, torch.bfloat16, 'dy')
+    N, H, W, Cout = dy_nhwc.shape
+    Cin = wt_bwd.shape[0]
+    dx = torch.empty((N, H, W, Cin), dtype=torch.float32, device=dy_nhwc.device)
+    h.check(h.lib.asr_conv3x4_bwd_data(h.h, _p(dy_nhwc), N, H, W, Cout, _p(wt_bwd), Cin, _p(dx), _s()),
+            'asr_conv3x4_bwd_data')
+    return dx
+
+
+def conv3x4_bwd_weight_bias(x_nhwc, dy_nhwc, dw, dbias=None):
+    """dw fp32 [12*Cin, Cout] view of the HWIO gradient, dbias fp32 [Cout] (both overwritten; deterministic)."""
+    h = _h(x_nhwc)
+    _chk(x_nhwc, torch.bfloat16, 'x')
+    _chk(dy_nhwc, torch.bfloat16, 'dy')
+    N, H, W, Cin = x_nhwc.shape
+    Cout = dy_nhwc.shape[3]
+    if dw.numel() != 12 * Cin * Cout or not dw.is_contiguous():
+        raise ValueError('conv3x4_bwd_weight_bias: dw must be a contiguous [12*Cin, Cout] fp32 tensor')
+    if dbias is not None and dbias.numel() != Cout:
+        raise ValueError('conv3x4_bwd_weight_bias: dbias has %d elements, Cout = %d' % (dbias.numel(), Cout))
+    h.check(h.lib.asr_conv3x4_bwd_weight_bias(h.h, _p(x_nhwc), _p(dy_nhwc), N, H, W, Cin, Cout, _p(dw), _p(dbias),
+                                              _s()), 'asr_conv3x4_bwd_weight_bias')
+    return dw, dbias
+
+
+def _bn_ws(M, Cc, dev):
+    n = int(_lib.load().asr_bn_workspace_bytes(int(M), int(Cc)))
+    return torch.empty((max(n, 4) // 4,), dtype=torch.float32, device=dev)
+
+
+def bn_stats(x_nhwc, eps, momentum, avg_mean=None, avg_var=None):
+    """Batch statistics of fp32 NHWC activations over all N*H*W rows -> fp32 [5, C]: mean, biased variance,
+    rsqrt(var + eps), and (with the moving averages given) the pending averages avg * momentum + stat * (1 - momentum)."""
+    h = _h(x_nhwc)
+    _chk(x_nhwc, torch.float32, 'x')
+    Cc = x_nhwc.shape[-1]
+    M = x_nhwc.numel() // Cc
+    stats = torch.empty((5, Cc), dtype=torch.float32, device=x_nhwc.device)
+    if avg_mean is None:
+        stats[3:].zero_()
+    h.check(h.lib.asr_bn_stats(h.h, _p(x_nhwc), M, Cc, float(eps), float(momentum), _p(avg_mean), _p(avg_var),
+                               _p(stats), _p(_bn_ws(M, Cc, x_nhwc.device)), _s()), 'asr_bn_stats')
+    return stats
+
+
+def bn_apply(x_nhwc, mean, var, gamma, beta, eps, pool, out_dtype):
+    """tf.nn.batch_normalization(x, mean, var, beta, gamma, eps) then max_pool [3,1]/[3,1] SAME (pool=True, with its
+    uint8 argmax) or the identity -> (out [N, Ho, W, C] in out_dtype, argmax or None)."""
+    h = _h(x_nhwc)
+    _chk(x_nhwc, torch.float32, 'x')
+    N, H, W, Cc = x_nhwc.shape
+    Ho = (H + 2) // 3 if pool else H
+    odt = dtype_id(out_dtype)
+    out = torch.empty((N, Ho, W, Cc), dtype=TORCH_DTYPE[odt], device=x_nhwc.device)
+    arg = torch.empty((N, Ho, W, Cc), dtype=torch.uint8, device=x_nhwc.device) if pool else None
+    h.check(h.lib.asr_bn_apply(h.h, odt, _p(x_nhwc), N, H, W, Cc, _p(mean), _p(var), _p(gamma), _p(beta), float(eps),
+                               int(bool(pool)), _p(out), _p(arg), _s()), 'asr_bn_apply')
+    return out, arg
+
+
+def bn_bwd(dz, arg, x_nhwc, stats, gamma, dgamma, dbeta, out_dtype, relu_gate=True):
+    """Backward of bn_apply (+ pool when arg is given) and of the ReLU in front of it: dz fp32 = gradient at the pooled
+    output; writes dgamma = sum(dy * xhat), dbeta = sum(dy); returns dx [N,H,W,C] in out_dtype."""
+    h = _h(x_nhwc)
+    _chk(dz, torch.float32, 'dz')
+    _chk(x_nhwc, torch.float32, 'x')
+    N, H, W, Cc = x_nhwc.shape
+    pool = arg is not None
+    want = (N, (H + 2) // 3 if pool else H, W, Cc)
+    if dz.numel() != int(np.prod(want)):
+        raise ValueError('bn_bwd: dz has %d elements, expected %s' % (dz.numel(), want))
+    odt = dtype_id(out_dtype)
+    dx = torch.empty((N, H, W, Cc), dtype=TORCH_DTYPE[odt], device=x_nhwc.device)
+    h.check(h.lib.asr_bn_bwd(h.h, odt, _p(dz), _p(arg), int(pool), _p(x_nhwc), N, H, W, Cc, _p(stats), _p(gamma),
+                             int(bool(relu_gate)), _p(dgamma), _p(dbeta), _p(dx),
+                             _p(_bn_ws(N * H * W, Cc, x_nhwc.device)), _s()), 'asr_bn_bwd')
+    return dx
+
+
+def softmax_xent_soft(logits2d, targets2d, grad_scale=1.0, want_grad=True):
+    """tf.nn.softmax_cross_entropy_with_logits(labels=targets, logits) per row -> (row_loss fp32 [rows], TF's gradient
+    (softmax(logits) - targets) * grad_scale or None)."""
+    h = _h(logits2d)
+    _chk(logits2d, torch.float32, 'logits')
+    _chk(targets2d, torch.float32, 'targets')
+    rows, Cc = logits2d.shape
+    if tuple(targets2d.shape) != (rows, Cc):
+        raise ValueError('softmax_xent_soft: targets have shape %s, logits %s' % (tuple(targets2d.shape), (rows, Cc)))
+    loss = _f32((rows,), logits2d.device)
+    dl = torch.empty_like(logits2d) if want_grad else None
+    h.check(h.lib.asr_softmax_xent_soft(h.h, _p(logits2d), _p(targets2d), rows, Cc, float(grad_scale), _p(loss), _p(dl),
+                                        _s()), 'asr_softmax_xent_soft')
+    return loss, dl
+
+
 # ---------------------------------------------------------------- LSTM
 def lstm_prep_weights(kernel, bias, din, H, dtype, out=None):
     """kernel [Din+H,4H] fp32 (TF layout), bias [4H] -> dict(wx_il [Din,4H] dtype, bias_il [4H] fp32,

@@ -118,6 +118,44 @@ class ParamStore(object):
         self.mark_dirty()
 
 
+class StateStore(object):
+    """Non-trainable variables (trainable=False in the reference, e.g. the moving averages of batch normalization):
+    one flat fp32 device buffer beside the ParamStore, outside the optimizer, the clip and the weight decay."""
+
+    def __init__(self, device):
+        self.device = device
+        self._specs = []
+        self.views = {}
+        self.names = []
+        self.flat = None
+
+    def declare(self, name, shape, init):
+        if self.flat is not None:
+            raise RuntimeError('StateStore already finalized; cannot declare %s' % name)
+        if name in self.names:
+            raise ValueError('variable %s already exists' % name)
+        self._specs.append((name, tuple(int(s) for s in shape), np.asarray(init, dtype=np.float32).reshape(shape)))
+        self.names.append(name)
+
+    def finalize(self):
+        host = np.concatenate([init.ravel() for _, _, init in self._specs]) if self._specs else np.zeros(0, np.float32)
+        self.flat = torch.from_numpy(host.astype(np.float32)).to(self.device)
+        pos = 0
+        for name, shape, init in self._specs:
+            self.views[name] = self.flat[pos:pos + init.size].view(shape)
+            pos += init.size
+
+    def __getitem__(self, name):
+        return self.views[name]
+
+    def state_dict(self):
+        return {n: self.views[n].detach().clone() for n in self.names}
+
+    def load_state_dict(self, sd):
+        for n in self.names:
+            self.views[n].copy_(sd[n].to(self.flat.device).view(self.views[n].shape))
+
+
 class _Shadow(object):
     def __init__(self, store):
         self.store = store

@@ -72,6 +72,9 @@ class Saver(object):
             from ... import ops
             ops.check_async_errors(model.store.flat.device.index or 0)
         arrays = {n: v.detach().cpu().numpy() for n, v in model.store.state_dict().items()}
+        state = getattr(model, 'state', None)          # non-trainable variables (batch-norm moving averages)
+        if state is not None:
+            arrays.update((n, v.detach().cpu().numpy()) for n, v in state.state_dict().items())
         opt = getattr(model, 'optimizer', None)
         if opt is not None:
             arrays[_OPT + 'name'] = np.array(opt.name)
@@ -112,7 +115,14 @@ class Saver(object):
             missing = [n for n in names if n not in z.files]
             if missing:
                 raise ValueError('checkpoint %s lacks variables: %s' % (path, ', '.join(missing[:5])))
+            state = getattr(model, 'state', None)
+            if state is not None:
+                missing = [n for n in state.names if n not in z.files]
+                if missing:
+                    raise ValueError('checkpoint %s lacks non-trainable variables: %s' % (path, ', '.join(missing)))
             model.store.load_state_dict({n: torch.from_numpy(np.asarray(z[n], dtype=np.float32)) for n in names})
+            if state is not None:
+                state.load_state_dict({n: torch.from_numpy(np.asarray(z[n], dtype=np.float32)) for n in state.names})
             opt = getattr(model, 'optimizer', None)
             if (_OPT + 'name') in z.files:
                 saved = str(z[_OPT + 'name'])
