@@ -27,6 +27,7 @@ import torch
 from ... import ops
 from ..._lib import ASR_BF16, ASR_F32
 from ...utils.parameter import ParamStore, StateStore
+from ..encoders.core import cnn_util
 from ..encoders.core.student_cnn import (StudentCNNCTCEncoder, StudentCNNCompactCTCEncoder, StudentCNNXEEncoder,
                                          StudentCNNCompactXEEncoder)
 from ..model_base import ModelBase
@@ -167,11 +168,8 @@ class StudentCTC(ModelBase):
                                           self._rng_state(keep_prob, is_training))          # [N, U], b*T + t order
         U = enc.shape[1]
         # time-major rows t*Bp + b; the utterances that fill the 16-row tile read an appended zero row
-        inv = self._tm_index(B, T, Bp, dev)
-        table = torch.cat([enc, enc.new_zeros(1, U)], 0)
-        rows = table.view(torch.float32) if enc.dtype == torch.bfloat16 else table
-        x_tm = ops.embedding_gather(rows, inv)
-        x_tm = (x_tm.view(torch.bfloat16) if enc.dtype == torch.bfloat16 else x_tm).view(T * Bp, U)
+        inv, fwd = self._tm_index(B, T, Bp, dev)
+        x_tm = cnn_util.gather_time_major(torch.cat([enc, enc.new_zeros(1, U)], 0), inv)
         logits = self._head(x_tm).view(T, Bp, self.num_classes)
         inv_temp = 1.0 / float(softmax_temperature)
         ctc_in = ops.scale_(logits.clone(), inv_temp) if softmax_temperature != 1 else logits
@@ -181,11 +179,13 @@ class StudentCTC(ModelBase):
         self.ctc_losses = ctc_losses[:B]
         self.num_infeasible = ninf
         ops.defer_zero_check(ninf, _not_enough_time, blocking=not is_training)
-        self._tape = dict(kind='ctc', dlogits=grad, x=x_tm, B=B, T=T, Bp=Bp, N=N) if is_training else None
+        self._tape = dict(kind='ctc', dlogits=grad, x=x_tm, fwd=fwd, B=B, T=T, Bp=Bp, N=N) if is_training else None
         total_loss._asr_model = self
         return total_loss, logits[:, :B]
 
     def _tm_index(self, B, T, Bp, dev):
+        """(for each row t*Bp + b of the time-major padded grid its image b*T + t, or B*T = the appended zero row; for
+        each image its row of the grid), cached per batch geometry."""
         key = (B, T, Bp, str(dev))
         cache = self.__dict__.setdefault('_index_cache', {})
         if key not in cache:
@@ -195,7 +195,7 @@ class StudentCTC(ModelBase):
             if len(cache) >= 16:
                 cache.clear()
             cache[key] = (ops.to_device(inv, torch.int32, dev), ops.to_device(fwd.reshape(-1), torch.int32, dev))
-        return cache[key][0]
+        return cache[key]
 
     def compute_xe_loss(self, inputs, soft_targets, keep_prob, scope=None, softmax_temperature=1, is_training=True):
         """student_ctc.py:302-359: reduce_mean(softmax_cross_entropy_with_logits(labels=soft_targets, logits)).
@@ -229,9 +229,7 @@ class StudentCTC(ModelBase):
         ops.colsum(dl2d, out=st.g(self.head_scope + '/biases'))
         d = ops.gemm(dl_op, sh[self.head_scope + '/weights'], transB=True, out_dtype=ASR_F32)
         if tape['kind'] == 'ctc':                        # time-major padded rows back to the b*T + t images
-            B, T, Bp = tape['B'], tape['T'], tape['Bp']
-            fwd = self.__dict__['_index_cache'][(B, T, Bp, str(self.device))][1]
-            d = ops.embedding_gather(d, fwd)
+            d = ops.embedding_gather(d, tape['fwd'])
         self.encoder.backward_images(d)
         if self.weight_decay > 0:
             ops.weight_decay(st.grad, st.flat, st.plan, st.decay_mask, self.weight_decay)

@@ -20,7 +20,7 @@ from .... import ops
 from ...._lib import ASR_BF16, ASR_F32
 from ....utils.parameter import ParamStore
 from .blstm import BLSTMEncoder
-from .vgg_blstm import _trunc_normal
+from .cnn_util import _trunc_normal
 
 # (scope, kernel (kh, kw), stride (sh, sw), Cin, Cout)
 CONVS = [('CNN1/conv', (11, 21), (3, 2), 3, 32), ('CNN2/conv', (11, 11), (1, 2), 32, 32),

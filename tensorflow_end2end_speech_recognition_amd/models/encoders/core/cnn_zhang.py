@@ -26,19 +26,13 @@ import torch
 from .... import ops
 from ...._lib import ASR_BF16, ASR_F32
 from ....utils.parameter import ParamStore
-from .vgg_blstm import _trunc_normal
+from . import cnn_util
 
 CONVS = ([('CNN1/conv', 3, 128)] + [('CNN%d/conv' % i, 128, 128) for i in (2, 3, 4)] + [('CNN5/conv', 128, 256)] +
          [('CNN%d/conv' % i, 256, 256) for i in (6, 7, 8, 9, 10)])
 FCS = ['fc1', 'fc2', 'fc3']
 FC_UNITS = 1024
 KH, KW = 3, 5
-PATCH_BYTES = 1 << 30        # im2col chunks: the patch matrix of one chunk stays under 1 GiB
-
-
-def _chunk(H, W, cols, elem):
-    """frames per im2col chunk"""
-    return max(1, PATCH_BYTES // (H * W * cols * elem))
 
 
 class CNNEncoder(object):
@@ -73,12 +67,10 @@ class CNNEncoder(object):
         assert input_dim == self.F * self.W * 3, 'input_dim %d != num_channels * splice * num_stack * 3' % input_dim
         p = scope_prefix
         for name, cin, cout in CONVS:
-            store.declare(p + name + '/weight', (KH, KW, cin, cout), _trunc_normal(rng, self.parameter_init, (KH, KW, cin, cout)))
-            store.declare(p + name + '/bias', (cout,), np.zeros(cout))
+            cnn_util.declare_conv(store, p + name, KH, KW, cin, cout, rng, self.parameter_init)
         din = self.flat
         for name in FCS:
-            store.declare(p + name + '/weights', (din, FC_UNITS), _trunc_normal(rng, self.parameter_init, (din, FC_UNITS)))
-            store.declare(p + name + '/biases', (FC_UNITS,), np.zeros(FC_UNITS))
+            cnn_util.declare_fc(store, p + name, din, FC_UNITS, rng, self.parameter_init)
             din = FC_UNITS
         self.store, self._p = store, p
         self.layers = [n for n, _, _ in CONVS] + FCS
@@ -107,22 +99,16 @@ class CNNEncoder(object):
             hit = cache[key] = tuple(ops.to_device(a, torch.int32, dev) for a in (valid, rows_tm, inv)) + (len(valid),)
         return hit
 
-    # ------------------------------------------------------------------ one convolution (forward)
-    def _conv_im2col(self, x, li):
-        """relu(conv3x5(x) + b) through asr_im2col + GEMM, chunked over frames."""
+    # ------------------------------------------------------------------ one layer's views
+    def _w2d(self, li):
+        """the [15*Cin, Cout] view of layer li's weight in the operand dtype"""
         name, cin, cout = CONVS[li]
-        N, H, W, _ = x.shape
-        K = KH * KW * cin
-        ldp = (K + 7) // 8 * 8
-        w2d = self.store.shadow(self.dtype)[self._p + name + '/weight'].view(K, cout)
-        b = self.store[self._p + name + '/bias']
-        out = torch.empty((N, H, W, cout), dtype=x.dtype, device=x.device)
-        step = _chunk(H, W, ldp, x.element_size())
-        for c0 in range(0, N, step):
-            xc = x[c0:c0 + step]
-            pat = ops.im2col(xc, KH, KW, 1, 1, ldp=ldp)
-            ops.gemm(pat[:, :K], w2d, bias=b, relu=True, out=out[c0:c0 + step].view(-1, cout))
-        return out
+        return self.store.shadow(self.dtype)[self._p + name + '/weight'].view(KH * KW * cin, cout)
+
+    def _g2d(self, li):
+        """(the [15*Cin, Cout] view of layer li's weight gradient, its bias gradient)"""
+        name, cin, cout = CONVS[li]
+        return self.store.g(self._p + name + '/weight').view(KH * KW * cin, cout), self.store.g(self._p + name + '/bias')
 
     def _images(self, name):
         cache = self.ctx.setdefault('wimg', {})
@@ -176,7 +162,7 @@ class CNNEncoder(object):
             x = ops.embedding_gather(inputs.contiguous().view(B * T, D), valid).view(N, F, W, 3)
             x0 = ops.cast_from_f32(x, self.dtype) if bf else x
             # CNN1: im2col + GEMM (3 input channels), then pool + dropout in one pass
-            a1 = self._conv_im2col(x0, 0)
+            a1 = cnn_util.conv_im2col(x0, KH, KW, self._w2d(0), st[p + CONVS[0][0] + '/bias'], x0.dtype)
             p1, arg1 = ops.maxpool3x1_fwd(a1, drop=desc(1))
             path = {CONVS[0][0]: 'im2col'}
             fused = bf and all(self._implicit_ok(c[1], c[2], N * self.Hp * W) for c in CONVS[1:])
@@ -194,26 +180,17 @@ class CNNEncoder(object):
                     acts.append(y)
                     path[name] = 'implicit'
                 else:
-                    y = self._conv_im2col(x_in, li)
+                    y = cnn_util.conv_im2col(x_in, KH, KW, self._w2d(li), st[p + name + '/bias'], x_in.dtype)
                     relu_outs.append(y)
                     acts.append(ops.dropout_apply(y, *d) if d is not None else y)
                     path[name] = 'im2col'
             self.conv_path = path
-            flat = acts[-1].view(N, self.flat)
-            h_in, fc = flat, []
-            for k, name in enumerate(FCS):
-                out = table[:N] if k == len(FCS) - 1 else None
-                a = ops.gemm(h_in, sh[p + name + '/weights'], bias=st[p + name + '/biases'], relu=True, out=out)
-                d = desc(len(CONVS) + 1 + k) if k < len(FCS) - 1 else None
-                ad = ops.dropout_apply(a, *d) if d is not None else a
-                fc.append((h_in, a, d))
-                h_in = ad
+            # dropout after fc1 and fc2 (:153-164); fc3 writes the row table
+            drops = [desc(len(CONVS) + 1 + k) for k in range(len(FCS) - 1)] + [None]
+            _, fc = cnn_util.fc_forward(st, sh, [p + n for n in FCS], acts[-1].view(N, self.flat), drops, out=table[:N])
             self.ctx.update(x0=x0, a1=a1, arg1=arg1, acts=acts, relu_outs=relu_outs, fused=fused, fc=fc)
-        # back to the time-major padded grid: padded rows read the zero row (a row copy: the bf16 table moves as fp32
-        # words, two values each)
-        rows = table.view(torch.float32) if bf else table
-        out_tm = ops.embedding_gather(rows, inv)
-        out_tm = (out_tm.view(torch.bfloat16) if bf else out_tm).view(T, Bp, FC_UNITS)
+        # back to the time-major padded grid: padded rows read the zero row
+        out_tm = cnn_util.gather_time_major(table, inv).view(T, Bp, FC_UNITS)
         self._out_op = out_tm
         want = self.want_f32_outputs
         out = ops.cast_to_f32(out_tm) if (bf and want) else out_tm
@@ -224,34 +201,6 @@ class CNNEncoder(object):
         return out_user, None
 
     # ------------------------------------------------------------------ backward
-    def _wgrad_im2col(self, x_in, dpre, li):
-        name, cin, cout = CONVS[li]
-        N, H, W, _ = x_in.shape
-        K = KH * KW * cin
-        ldp = (K + 7) // 8 * 8
-        gw = self.store.g(self._p + name + '/weight').view(K, cout)
-        step = _chunk(H, W, ldp, x_in.element_size())
-        d2 = dpre.view(N * H * W, cout)
-        for ci, c0 in enumerate(range(0, N, step)):
-            pat = ops.im2col(x_in[c0:c0 + step], KH, KW, 1, 1, ldp=ldp)
-            ops.gemm(pat[:, :K], d2[c0 * H * W:(c0 + step) * H * W], transA=True, out=gw, accumulate=(ci > 0))
-        ops.colsum(d2, out=self.store.g(self._p + name + '/bias'))
-
-    def _dgrad_im2col(self, dpre, li):
-        """fp32 data gradient of layer li through GEMM + col2im, chunked."""
-        name, cin, cout = CONVS[li]
-        N, H, W, _ = dpre.shape
-        K = KH * KW * cin
-        w2d = self.store.shadow(self.dtype)[self._p + name + '/weight'].view(K, cout)
-        din = torch.empty((N, H, W, cin), dtype=torch.float32, device=dpre.device)
-        step = _chunk(H, W, K, 4)
-        for c0 in range(0, N, step):
-            dc = dpre[c0:c0 + step]
-            n = dc.shape[0]
-            dpat = ops.gemm(dc.reshape(n * H * W, cout), w2d, transB=True, out_dtype=ASR_F32)
-            din[c0:c0 + n] = ops.col2im(dpat, n, H, W, cin, KH, KW, 1, 1)
-        return din
-
     def backward(self, d_outputs, d_final=None, need_input_grad=False, d_outputs_sub=None):
         """d_outputs [T,Bp,1024] fp32 (time-major, padded batch): the gradients of every variable."""
         c, st, p = self.ctx, self.store, self._p
@@ -265,15 +214,8 @@ class CNNEncoder(object):
             self.ctx = None
             return None
         sh = st.shadow(self.dtype)
-        bf = self.dtype == ASR_BF16
         d = ops.embedding_gather(d_outputs.reshape(-1, FC_UNITS).contiguous(), c['rows_tm'])      # [N,1024] fp32
-        for k in reversed(range(len(FCS))):
-            name = FCS[k]
-            h_in, a, dr = c['fc'][k]
-            dpre = ops.relu_bwd(d, a, drop=dr)
-            ops.gemm(h_in, dpre, transA=True, out=st.g(p + name + '/weights'))
-            ops.colsum(dpre, out=st.g(p + name + '/biases'))
-            d = ops.gemm(dpre, sh[p + name + '/weights'], transB=True, out_dtype=ASR_F32)
+        d = cnn_util.fc_backward(st, sh, [p + n for n in FCS], c['fc'], d)
         acts, relu_outs, descs = c['acts'], c['relu_outs'], c['descs']
         Hp, W = self.Hp, self.W
         last = len(CONVS) - 1
@@ -289,15 +231,14 @@ class CNNEncoder(object):
             x_in = acts[li - 1]
             below_drop = descs.get(li)       # dropout of the tensor layer li consumed (pooled output for li == 1)
             if c['fused']:
-                ops.conv3x5_bwd_weight_bias(x_in, dpre, st.g(p + name + '/weight').view(KH * KW * cin, cout),
-                                            st.g(p + name + '/bias'))
+                ops.conv3x5_bwd_weight_bias(x_in, dpre, *self._g2d(li))
                 # ReLU / dropout backward of the tensor below, in the epilogue: its stored form is the dropped one (> 0
                 # where active and kept); for CNN2 that is the pooled CNN1 output, > 0 exactly where its maximum was
                 dpre = ops.conv3x5_bwd_data_relu(dpre, self._images(name)[1], x_in, drop=below_drop,
                                                  dropped=below_drop is not None)
             else:
-                self._wgrad_im2col(x_in, dpre, li)
-                din = self._dgrad_im2col(dpre, li)
+                cnn_util.wgrad_im2col(x_in, dpre, KH, KW, *self._g2d(li))
+                din = cnn_util.dgrad_im2col(dpre, KH, KW, self._w2d(li))      # fp32, through GEMM + col2im
                 below = relu_outs[li - 1] if li > 1 else None
                 if below is None:            # the pooled CNN1 output: non-negative, > 0 where its window's maximum was
                     below = self._pooled_undropped(x_in, below_drop)
@@ -305,7 +246,7 @@ class CNNEncoder(object):
         # dpre is the gradient at the pooled CNN1 output (ReLU and dropout already applied): un-pool, then CNN1's
         # weight gradient (no data gradient)
         dpre1 = ops.maxpool3x1_bwd(dpre, c['arg1'], self.F)
-        self._wgrad_im2col(c['x0'], dpre1, 0)
+        cnn_util.wgrad_im2col(c['x0'], dpre1, KH, KW, *self._g2d(0))
         ops.join_side(dev)           # the heads' gradients were issued on side lane 1
         self.ctx = None
         return None

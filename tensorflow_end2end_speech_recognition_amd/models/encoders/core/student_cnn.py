@@ -28,15 +28,8 @@ import torch
 
 from .... import ops
 from ...._lib import ASR_BF16, ASR_F32
+from . import cnn_util
 from .batch_norm import BatchNorm
-from .vgg_blstm import _trunc_normal
-
-PATCH_BYTES = 1 << 30        # im2col chunks: the patch matrix of one chunk stays under 1 GiB
-
-
-def _chunk(pix, cols, elem):
-    """images per im2col chunk"""
-    return max(1, PATCH_BYTES // (pix * cols * elem))
 
 
 class _StudentCNN(object):
@@ -56,6 +49,7 @@ class _StudentCNN(object):
         self.time_major = time_major
         self.name = name or self.NAME
         self.dtype = ops.dtype_id(dtype)
+        self.seed = 0                 # dropout stream when used without a model (StudentCTC sets its own)
         self.F = self.num_channels
         self.W = splice * num_stack
         self.Hp = (self.F + 2) // 3
@@ -79,13 +73,11 @@ class _StudentCNN(object):
         zeros = lambda n: np.zeros(n)
         ones = lambda n: np.ones(n)
         for (name, kh, kw, cin, cout), bn in zip(self.convs, self.bns):
-            store.declare(name + '/weight', (kh, kw, cin, cout), _trunc_normal(rng, self.parameter_init, (kh, kw, cin, cout)))
-            store.declare(name + '/bias', (cout,), np.zeros(cout))
+            cnn_util.declare_conv(store, name, kh, kw, cin, cout, rng, self.parameter_init)
             bn.declare(store, state, ones, zeros)
         din = self.flat
         for name in self.fcs:
-            store.declare(name + '/weights', (din, self.UNITS), _trunc_normal(rng, self.parameter_init, (din, self.UNITS)))
-            store.declare(name + '/biases', (self.UNITS,), np.zeros(self.UNITS))
+            cnn_util.declare_fc(store, name, din, self.UNITS, rng, self.parameter_init)
             din = self.UNITS
         self.store, self.state = store, state
         return self.UNITS
@@ -100,48 +92,16 @@ class _StudentCNN(object):
             out += [(name + '/weights', True), (name + '/biases', True)]
         return out
 
-    # ------------------------------------------------------------------ convolutions
-    def _conv_im2col(self, x, li):
-        """relu(conv(x) + b) through asr_im2col + GEMM, chunked over images -> fp32 [N,H,W,Cout]."""
+    # ------------------------------------------------------------------ one layer's views
+    def _w2d(self, li):
+        """the [kh*kw*Cin, Cout] view of layer li's weight in the operand dtype"""
         name, kh, kw, cin, cout = self.convs[li]
-        N, H, W, _ = x.shape
-        K = kh * kw * cin
-        ldp = (K + 7) // 8 * 8
-        w2d = self.store.shadow(self.dtype)[name + '/weight'].view(K, cout)
-        b = self.store[name + '/bias']
-        out = torch.empty((N, H, W, cout), dtype=torch.float32, device=x.device)
-        step = _chunk(H * W, ldp, x.element_size())
-        for c0 in range(0, N, step):
-            pat = ops.im2col(x[c0:c0 + step], kh, kw, 1, 1, ldp=ldp)
-            ops.gemm(pat[:, :K], w2d, bias=b, relu=True, out=out[c0:c0 + step].view(-1, cout))
-        return out
+        return self.store.shadow(self.dtype)[name + '/weight'].view(kh * kw * cin, cout)
 
-    def _wgrad_im2col(self, x_in, dpre, li):
+    def _g2d(self, li):
+        """(the [kh*kw*Cin, Cout] view of layer li's weight gradient, its bias gradient)"""
         name, kh, kw, cin, cout = self.convs[li]
-        N, H, W, _ = x_in.shape
-        K = kh * kw * cin
-        ldp = (K + 7) // 8 * 8
-        gw = self.store.g(name + '/weight').view(K, cout)
-        step = _chunk(H * W, ldp, x_in.element_size())
-        d2 = dpre.view(N * H * W, cout)
-        for ci, c0 in enumerate(range(0, N, step)):
-            pat = ops.im2col(x_in[c0:c0 + step], kh, kw, 1, 1, ldp=ldp)
-            ops.gemm(pat[:, :K], d2[c0 * H * W:(c0 + step) * H * W], transA=True, out=gw, accumulate=(ci > 0))
-        ops.colsum(d2, out=self.store.g(name + '/bias'))
-
-    def _dgrad_im2col(self, dpre, li):
-        name, kh, kw, cin, cout = self.convs[li]
-        N, H, W, _ = dpre.shape
-        K = kh * kw * cin
-        w2d = self.store.shadow(self.dtype)[name + '/weight'].view(K, cout)
-        din = torch.empty((N, H, W, cin), dtype=torch.float32, device=dpre.device)
-        step = _chunk(H * W, K, 4)
-        for c0 in range(0, N, step):
-            dc = dpre[c0:c0 + step]
-            n = dc.shape[0]
-            dpat = ops.gemm(dc.reshape(n * H * W, cout), w2d, transB=True, out_dtype=ASR_F32)
-            din[c0:c0 + n] = ops.col2im(dpat, n, H, W, cin, kh, kw, 1, 1)
-        return din
+        return self.store.g(name + '/weight').view(kh * kw * cin, cout), self.store.g(name + '/bias')
 
     def _images(self):
         c = self.ctx.setdefault('wimg', None)
@@ -161,11 +121,11 @@ class _StudentCNN(object):
         drop = is_training and keep < 1.0 and self.FC_DROPOUT
         if drop and rng_state is None:
             self._dropout_calls = getattr(self, '_dropout_calls', 0) + 1
-            rng_state = (getattr(self, 'seed', 0), self._dropout_calls << 40)
+            rng_state = (self.seed, self._dropout_calls << 40)
         self.ctx = {}
         x0 = x.contiguous().view(N, F, W, 3)
         x0 = ops.cast_from_f32(x0, ASR_BF16) if bf else x0
-        a1 = self._conv_im2col(x0, 0)                                   # fp32 ReLU output
+        a1 = cnn_util.conv_im2col(x0, 9, 9, self._w2d(0), st['CNN1/conv/bias'], torch.float32)    # fp32 ReLU output
         p1, _ = self.bns[0].forward(a1, is_training, True, self.dtype)   # [N, Hp, W, C1] operand
         path = {'CNN1/conv': 'im2col'}
         if bf and self.implicit:
@@ -173,17 +133,12 @@ class _StudentCNN(object):
             a2 = ops.conv3x4_fwd(p1, wf, st['CNN2/conv/bias'], relu=True, out_dtype=ASR_F32)
             path['CNN2/conv'] = 'implicit'
         else:
-            a2 = self._conv_im2col(p1, 1)
+            a2 = cnn_util.conv_im2col(p1, 3, 4, self._w2d(1), st['CNN2/conv/bias'], torch.float32)
             path['CNN2/conv'] = 'im2col'
         self.conv_path = path
         z2, _ = self.bns[1].forward(a2, is_training, False, self.dtype)  # [N, Hp, W, C2] operand
-        h_in, fc = z2.view(N, self.flat), []
-        for k, name in enumerate(self.fcs):
-            a = ops.gemm(h_in, sh[name + '/weights'], bias=st[name + '/biases'], relu=True)
-            d = (keep, rng_state[0] + 7, rng_state[1] + (k << 32)) if drop else None
-            ad = ops.dropout_apply(a, *d) if d is not None else a
-            fc.append((h_in, a, d))
-            h_in = ad
+        drops = [(keep, rng_state[0] + 7, rng_state[1] + (k << 32)) if drop else None for k in range(len(self.fcs))]
+        h_in, fc = cnn_util.fc_forward(st, sh, self.fcs, z2.view(N, self.flat), drops)
         self.ctx.update(x0=x0, p1=p1, a2=a2, fc=fc, implicit=path['CNN2/conv'] == 'implicit', N=N)
         return h_in
 
@@ -194,25 +149,18 @@ class _StudentCNN(object):
             raise RuntimeError('%s: backward needs a preceding forward' % self.name)
         sh = st.shadow(self.dtype)
         N = c['N']
-        for k in reversed(range(len(self.fcs))):
-            name = self.fcs[k]
-            h_in, a, dr = c['fc'][k]
-            dpre = ops.relu_bwd(d, a, drop=dr)
-            ops.gemm(h_in, dpre, transA=True, out=st.g(name + '/weights'))
-            ops.colsum(dpre, out=st.g(name + '/biases'))
-            d = ops.gemm(dpre, sh[name + '/weights'], transB=True, out_dtype=ASR_F32)
+        d = cnn_util.fc_backward(st, sh, self.fcs, c['fc'], d)
         dz2 = d.view(N, self.Hp, self.W, self.C2)
         dpre2 = self.bns[1].backward(dz2, self.dtype)
         p1 = c['p1']
         if c['implicit']:
-            ops.conv3x4_bwd_weight_bias(p1, dpre2, st.g('CNN2/conv/weight').view(12 * self.C1, self.C2),
-                                        st.g('CNN2/conv/bias'))
+            ops.conv3x4_bwd_weight_bias(p1, dpre2, *self._g2d(1))
             dp1 = ops.conv3x4_bwd_data(dpre2, self._images()[1])
         else:
-            self._wgrad_im2col(p1, dpre2, 1)
-            dp1 = self._dgrad_im2col(dpre2, 1)
+            cnn_util.wgrad_im2col(p1, dpre2, 3, 4, *self._g2d(1))
+            dp1 = cnn_util.dgrad_im2col(dpre2, 3, 4, self._w2d(1))
         dpre1 = self.bns[0].backward(dp1, self.dtype)
-        self._wgrad_im2col(c['x0'], dpre1, 0)
+        cnn_util.wgrad_im2col(c['x0'], dpre1, 9, 9, *self._g2d(0))
         self.ctx = None
 
     def commit(self):

@@ -24,6 +24,7 @@ from .... import ops
 from ...._lib import ASR_BF16, ASR_F32
 from ....utils.parameter import ParamStore
 from .blstm import BLSTMEncoder
+from .cnn_util import _trunc_normal
 from .lstm import LSTMEncoder
 
 CONVS = [('VGG1/conv1', 3, 64), ('VGG1/conv2', 64, 64), ('VGG2/conv1', 64, 128), ('VGG2/conv2', 128, 128)]
@@ -31,15 +32,6 @@ CHUNK_FRAMES = 4096
 VGG_FWD_CHUNK_MIN = 2048     # images per run below which the single pass is kept
 VGG_FWD_CHUNKS = int(_os.environ.get('ASR_VGG_FWD_CHUNKS', '2'))        # runs of images the fused bf16 forward goes through on separate lanes
 VGG_WGRAD_SIDE = _os.environ.get('ASR_VGG_WGRAD_SIDE', '1') != '0'   # weight gradients of the implicit-GEMM layers on side lane 1
-
-
-def _trunc_normal(rng, std, shape):
-    x = rng.normal(0.0, std, size=shape)
-    bad = np.abs(x) > 2 * std
-    while bad.any():
-        x[bad] = rng.normal(0.0, std, size=int(bad.sum()))
-        bad = np.abs(x) > 2 * std
-    return x
 
 
 class _VGGFrontEnd(object):

@@ -731,31 +731,78 @@ def relu_bwd(dout, out, mask=None, drop=None):
     return dpre
 
 
-# ---------------------------------------------------------------- cnn_zhang convolution stack (3x5 convolutions, 3x1 pool)
-def conv3x5_prep_weights(w_hwio):
-    """fp32 [3,5,Cin,Cout] -> (wt_fwd bf16 [Cout, 15*Cin], wt_bwd bf16 [Cin, 15*Cout]: the flipped-tap image)."""
+# ---------------------------------------------------------------- 3xK implicit-GEMM convolutions (cnn_zhang 3x5, students 3x4)
+# One implementation per wrapper, parameterised by the filter and the C symbol prefix (csrc/conv3x5.hip is templated on
+# the tap geometry); the public conv3x5_* / conv3x4_* names are bound below with their own signatures.
+_K3X5 = (3, 5, 'conv3x5')
+_K3X4 = (3, 4, 'conv3x4')
+
+
+def _conv3xk_prep_weights(geom, w_hwio):
+    kh, kw, pre = geom
+    fn = pre + '_prep_weights'
     h = _h(w_hwio)
     _chk(w_hwio, torch.float32, 'w')
-    kh, kw, Cin, Cout = w_hwio.shape
-    if (kh, kw) != (3, 5):
-        raise ValueError('conv3x5_prep_weights: filter is %dx%d' % (kh, kw))
-    wf = torch.empty((Cout, 15 * Cin), dtype=torch.bfloat16, device=w_hwio.device)
-    wb = torch.empty((Cin, 15 * Cout), dtype=torch.bfloat16, device=w_hwio.device)
-    h.check(h.lib.asr_conv3x5_prep_weights(h.h, _p(w_hwio.contiguous()), Cin, Cout, _p(wf), _p(wb), _s()),
-            'asr_conv3x5_prep_weights')
+    fh, fw, Cin, Cout = w_hwio.shape
+    if (fh, fw) != (kh, kw):
+        raise ValueError('%s: filter is %dx%d' % (fn, fh, fw))
+    wf = torch.empty((Cout, kh * kw * Cin), dtype=torch.bfloat16, device=w_hwio.device)
+    wb = torch.empty((Cin, kh * kw * Cout), dtype=torch.bfloat16, device=w_hwio.device)
+    h.check(getattr(h.lib, 'asr_' + fn)(h.h, _p(w_hwio.contiguous()), Cin, Cout, _p(wf), _p(wb), _s()), 'asr_' + fn)
     return wf, wb
 
 
-def conv3x5_fwd(x_nhwc, wt_fwd, bias, relu=True, out=None):
-    """relu?(conv3x5 SAME(x) + bias): x bf16 [N,H,W,Cin] -> bf16 [N,H,W,Cout] (implicit GEMM)."""
+def _conv3xk_fwd(geom, x_nhwc, wt_fwd, bias, relu, out, f32_out=None):
+    """f32_out: None for asr_conv3x5_fwd (bf16 output only); asr_conv3x4_fwd takes it as one more argument."""
+    fn = geom[2] + '_fwd'
     h = _h(x_nhwc)
     _chk(x_nhwc, torch.bfloat16, 'x')
     N, H, W, Cin = x_nhwc.shape
     Cout = wt_fwd.shape[0]
-    out = _out_like(out, (N, H, W, Cout), torch.bfloat16, x_nhwc.device, 'conv3x5_fwd')
-    h.check(h.lib.asr_conv3x5_fwd(h.h, _p(x_nhwc), N, H, W, Cin, _p(wt_fwd), _p(bias), Cout, 1 if relu else 0,
-                                  _p(out), _s()), 'asr_conv3x5_fwd')
+    out = _out_like(out, (N, H, W, Cout), torch.float32 if f32_out else torch.bfloat16, x_nhwc.device, fn)
+    extra = () if f32_out is None else (int(f32_out),)
+    h.check(getattr(h.lib, 'asr_' + fn)(h.h, _p(x_nhwc), N, H, W, Cin, _p(wt_fwd), _p(bias), Cout, 1 if relu else 0,
+                                        *extra, _p(out), _s()), 'asr_' + fn)
     return out
+
+
+def _conv3xk_bwd_data(geom, dy_nhwc, wt_bwd):
+    fn = geom[2] + '_bwd_data'
+    h = _h(dy_nhwc)
+    _chk(dy_nhwc, torch.bfloat16, 'dy')
+    N, H, W, Cout = dy_nhwc.shape
+    Cin = wt_bwd.shape[0]
+    dx = torch.empty((N, H, W, Cin), dtype=torch.float32, device=dy_nhwc.device)
+    h.check(getattr(h.lib, 'asr_' + fn)(h.h, _p(dy_nhwc), N, H, W, Cout, _p(wt_bwd), Cin, _p(dx), _s()), 'asr_' + fn)
+    return dx
+
+
+def _conv3xk_bwd_weight_bias(geom, x_nhwc, dy_nhwc, dw, dbias):
+    kh, kw, pre = geom
+    taps, fn = kh * kw, pre + '_bwd_weight_bias'
+    h = _h(x_nhwc)
+    _chk(x_nhwc, torch.bfloat16, 'x')
+    _chk(dy_nhwc, torch.bfloat16, 'dy')
+    N, H, W, Cin = x_nhwc.shape
+    Cout = dy_nhwc.shape[3]
+    if dw.numel() != taps * Cin * Cout or not dw.is_contiguous():
+        raise ValueError('%s: dw must be a contiguous [%d*Cin, Cout] fp32 tensor' % (fn, taps))
+    if dbias is not None and dbias.numel() != Cout:
+        raise ValueError('%s: dbias has %d elements, Cout = %d' % (fn, dbias.numel(), Cout))
+    h.check(getattr(h.lib, 'asr_' + fn)(h.h, _p(x_nhwc), _p(dy_nhwc), N, H, W, Cin, Cout, _p(dw), _p(dbias), _s()),
+            'asr_' + fn)
+    return dw, dbias
+
+
+# ---------------------------------------------------------------- cnn_zhang convolution stack (3x5 convolutions, 3x1 pool)
+def conv3x5_prep_weights(w_hwio):
+    """fp32 [3,5,Cin,Cout] -> (wt_fwd bf16 [Cout, 15*Cin], wt_bwd bf16 [Cin, 15*Cout]: the flipped-tap image)."""
+    return _conv3xk_prep_weights(_K3X5, w_hwio)
+
+
+def conv3x5_fwd(x_nhwc, wt_fwd, bias, relu=True, out=None):
+    """relu?(conv3x5 SAME(x) + bias): x bf16 [N,H,W,Cin] -> bf16 [N,H,W,Cout] (implicit GEMM)."""
+    return _conv3xk_fwd(_K3X5, x_nhwc, wt_fwd, bias, relu, out)
 
 
 def conv3x5_fwd_drop(x_nhwc, wt_fwd, bias, drop, out=None):
@@ -772,14 +819,7 @@ def conv3x5_fwd_drop(x_nhwc, wt_fwd, bias, drop, out=None):
 
 def conv3x5_bwd_data(dy_nhwc, wt_bwd):
     """dx fp32 [N,H,W,Cin] = data gradient of the 3x5 convolution (dy bf16 [N,H,W,Cout])."""
-    h = _h(dy_nhwc)
-    _chk(dy_nhwc, torch.bfloat16, 'dy')
-    N, H, W, Cout = dy_nhwc.shape
-    Cin = wt_bwd.shape[0]
-    dx = torch.empty((N, H, W, Cin), dtype=torch.float32, device=dy_nhwc.device)
-    h.check(h.lib.asr_conv3x5_bwd_data(h.h, _p(dy_nhwc), N, H, W, Cout, _p(wt_bwd), Cin, _p(dx), _s()),
-            'asr_conv3x5_bwd_data')
-    return dx
+    return _conv3xk_bwd_data(_K3X5, dy_nhwc, wt_bwd)
 
 
 def conv3x5_bwd_data_relu(dy_nhwc, wt_bwd, act_below, drop=None, dropped=False):
@@ -801,18 +841,7 @@ def conv3x5_bwd_data_relu(dy_nhwc, wt_bwd, act_below, drop=None, dropped=False):
 
 def conv3x5_bwd_weight_bias(x_nhwc, dy_nhwc, dw, dbias=None):
     """dw fp32 [15*Cin, Cout] view of the HWIO gradient, dbias fp32 [Cout] (both overwritten; deterministic)."""
-    h = _h(x_nhwc)
-    _chk(x_nhwc, torch.bfloat16, 'x')
-    _chk(dy_nhwc, torch.bfloat16, 'dy')
-    N, H, W, Cin = x_nhwc.shape
-    Cout = dy_nhwc.shape[3]
-    if dw.numel() != 15 * Cin * Cout or not dw.is_contiguous():
-        raise ValueError('conv3x5_bwd_weight_bias: dw must be a contiguous [15*Cin, Cout] fp32 tensor')
-    if dbias is not None and dbias.numel() != Cout:
-        raise ValueError('conv3x5_bwd_weight_bias: dbias has %d elements, Cout = %d' % (dbias.numel(), Cout))
-    h.check(h.lib.asr_conv3x5_bwd_weight_bias(h.h, _p(x_nhwc), _p(dy_nhwc), N, H, W, Cin, Cout, _p(dw), _p(dbias),
-                                              _s()), 'asr_conv3x5_bwd_weight_bias')
-    return dw, dbias
+    return _conv3xk_bwd_weight_bias(_K3X5, x_nhwc, dy_nhwc, dw, dbias)
 
 
 def maxpool3x1_fwd(x_nhwc, drop=None):
@@ -842,57 +871,22 @@ def maxpool3x1_bwd(dout, arg, H):
 # ---------------------------------------------------------------- student CNNs (3x4 convolutions, batch normalization)
 def conv3x4_prep_weights(w_hwio):
     """fp32 [3,4,Cin,Cout] -> (wt_fwd bf16 [Cout, 12*Cin], wt_bwd bf16 [Cin, 12*Cout]: the flipped-tap image)."""
-    h = _h(w_hwio)
-    _chk(w_hwio, torch.float32, 'w')
-    kh, kw, Cin, Cout = w_hwio.shape
-    if (kh, kw) != (3, 4):
-        raise ValueError('conv3x4_prep_weights: filter is %dx%d' % (kh, kw))
-    wf = torch.empty((Cout, 12 * Cin), dtype=torch.bfloat16, device=w_hwio.device)
-    wb = torch.empty((Cin, 12 * Cout), dtype=torch.bfloat16, device=w_hwio.device)
-    h.check(h.lib.asr_conv3x4_prep_weights(h.h, _p(w_hwio.contiguous()), Cin, Cout, _p(wf), _p(wb), _s()),
-            'asr_conv3x4_prep_weights')
-    return wf, wb
+    return _conv3xk_prep_weights(_K3X4, w_hwio)
 
 
 def conv3x4_fwd(x_nhwc, wt_fwd, bias, relu=True, out_dtype=ASR_BF16):
     """relu?(conv3x4 SAME(x) + bias): x bf16 [N,H,W,Cin] -> [N,H,W,Cout] in out_dtype (implicit GEMM)."""
-    h = _h(x_nhwc)
-    _chk(x_nhwc, torch.bfloat16, 'x')
-    N, H, W, Cin = x_nhwc.shape
-    Cout = wt_fwd.shape[0]
-    odt = dtype_id(out_dtype)
-    out = torch.empty((N, H, W, Cout), dtype=TORCH_DTYPE[odt], device=x_nhwc.device)
-    h.check(h.lib.asr_conv3x4_fwd(h.h, _p(x_nhwc), N, H, W, Cin, _p(wt_fwd), _p(bias), Cout, 1 if relu else 0,
-                                  int(odt == ASR_F32), _p(out), _s()), 'asr_conv3x4_fwd')
-    return out
+    return _conv3xk_fwd(_K3X4, x_nhwc, wt_fwd, bias, relu, None, f32_out=dtype_id(out_dtype) == ASR_F32)
 
 
 def conv3x4_bwd_data(dy_nhwc, wt_bwd):
     """dx fp32 [N,H,W,Cin] = data gradient of the 3x4 convolution (dy bf16 [N,H,W,Cout])."""
-    h = _h(dy_nhwc)
-    _chk(dy_nhwc, torch.bfloat16, 'dy')
-    N, H, W, Cout = dy_nhwc.shape
-    Cin = wt_bwd.shape[0]
-    dx = torch.empty((N, H, W, Cin), dtype=torch.float32, device=dy_nhwc.device)
-    h.check(h.lib.asr_conv3x4_bwd_data(h.h, _p(dy_nhwc), N, H, W, Cout, _p(wt_bwd), Cin, _p(dx), _s()),
-            'asr_conv3x4_bwd_data')
-    return dx
+    return _conv3xk_bwd_data(_K3X4, dy_nhwc, wt_bwd)
 
 
 def conv3x4_bwd_weight_bias(x_nhwc, dy_nhwc, dw, dbias=None):
     """dw fp32 [12*Cin, Cout] view of the HWIO gradient, dbias fp32 [Cout] (both overwritten; deterministic)."""
-    h = _h(x_nhwc)
-    _chk(x_nhwc, torch.bfloat16, 'x')
-    _chk(dy_nhwc, torch.bfloat16, 'dy')
-    N, H, W, Cin = x_nhwc.shape
-    Cout = dy_nhwc.shape[3]
-    if dw.numel() != 12 * Cin * Cout or not dw.is_contiguous():
-        raise ValueError('conv3x4_bwd_weight_bias: dw must be a contiguous [12*Cin, Cout] fp32 tensor')
-    if dbias is not None and dbias.numel() != Cout:
-        raise ValueError('conv3x4_bwd_weight_bias: dbias has %d elements, Cout = %d' % (dbias.numel(), Cout))
-    h.check(h.lib.asr_conv3x4_bwd_weight_bias(h.h, _p(x_nhwc), _p(dy_nhwc), N, H, W, Cin, Cout, _p(dw), _p(dbias),
-                                              _s()), 'asr_conv3x4_bwd_weight_bias')
-    return dw, dbias
+    return _conv3xk_bwd_weight_bias(_K3X4, x_nhwc, dy_nhwc, dw, dbias)
 
 
 def _bn_ws(M, Cc, dev):
