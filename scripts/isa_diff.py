@@ -1,12 +1,16 @@
 #!/usr/bin/env python
-"""Device-ISA identity check for kernel experiments: compile a .hip file of two source trees (or two git revisions)
-to gfx950 assembly and compare every kernel's instruction stream (labels and comments normalised).  Used to prove
-that an experimental template variant behind a default-off switch leaves the default kernels' code untouched, so it
-can be committed without a GPU run.
+"""Device-ISA identity check for kernel experiments and refactors: compile .hip files of two source trees (git revisions,
+or directories holding a tree) to gfx950 assembly and compare every kernel's instruction stream (labels and comments
+normalised).  Used to prove that an experimental template variant behind a default-off switch, or a move of kernels
+between files, leaves the kernels' code untouched, so it can be committed without a GPU run.
 
-    python scripts/isa_diff.py <rev_a> <rev_b> [path/to/file.hip]      # e.g. HEAD~1 HEAD
-Template arguments appended with a default (kernel<256, false> -> kernel<256, false, false>) are matched by trying the
-old mangled name with `ELb0` inserted before the argument-list terminator."""
+    python scripts/isa_diff.py <rev_a> <rev_b> [file.hip ...] [--b file.hip ...] [--rename old=new ...] [--work dir]
+    e.g.  isa_diff.py HEAD~1 HEAD                                   (the default file)
+          isa_diff.py HEAD~1 . csrc/gemm.hip --b csrc/gemm.hip csrc/conv.hip --rename conv3x5_nt_kernel=conv_nt_kernel
+Kernels are matched by demangled name over ALL files of a side (they may move between files), with
+`(anonymous namespace)::` dropped and the --rename substitutions (re.sub) applied to side a's names.  Template arguments appended
+with a default (kernel<256, false> -> kernel<256, false, false>) are matched by trying the old name with `, false` appended
+to the argument list.  --work keeps the trees and their assembly in a directory (and reuses what is there).  Kernels that differ are listed with their registers, scratch and LDS on both sides."""
 import os
 import re
 import subprocess
@@ -16,22 +20,50 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEFAULT = 'tensorflow_end2end_speech_recognition_amd/csrc/lstm_cluster.hip'
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value', '--cuda-device-only', '-S']
+CXXFILT = 'c++filt'
+RES = ('.vgpr_count', '.agpr_count', '.sgpr_count', '.private_segment_fixed_size', '.group_segment_fixed_size')
 
 
-def asm_of(rev, rel, tmp):
-    tree = os.path.join(tmp, rev.replace('/', '_'))
-    os.makedirs(tree)
-    subprocess.run('git -C %s archive %s include %s | tar -x -C %s' % (ROOT, rev, os.path.dirname(rel), tree), shell=True,
-                   check=True)
-    out = os.path.join(tree, 'out.s')
-    subprocess.run(['/opt/rocm/bin/hipcc'] + FLAGS + ['-I', os.path.join(tree, 'include'), '-o', out,
-                                                     os.path.join(tree, rel)], check=True, capture_output=True)
-    return open(out).read()
+def asm_of(rev, rels, tmp, tag):
+    """{mangled kernel name: (body, resources)} over the files `rels` of revision (or directory) `rev`."""
+    tree = os.path.join(tmp, tag)
+    fresh = not os.path.isdir(tree)
+    os.makedirs(tree, exist_ok=True)
+    dirs = sorted({'include'} | {os.path.dirname(r) for r in rels})
+    if not fresh:
+        pass
+    elif os.path.isdir(rev):
+        for d in dirs:
+            subprocess.run(['cp', '-r', '--parents', d, tree], cwd=os.path.abspath(rev), check=True)
+    else:
+        subprocess.run('git -C %s archive %s %s | tar -x -C %s' % (ROOT, rev, ' '.join(dirs), tree), shell=True, check=True)
+    fns = {}
+    for i, rel in enumerate(rels):
+        out = os.path.join(tree, 'out%d.s' % i)
+        if not os.path.exists(out):
+            subprocess.run(['/opt/rocm/bin/hipcc'] + FLAGS + ['-I', os.path.join(tree, 'include'), '-o', out,
+                                                             os.path.join(tree, rel)], check=True, capture_output=True)
+        txt = open(out).read()
+        res = resources(txt)
+        for name, body in functions(txt).items():
+            fns[name] = (body, res.get(name, {}))
+    return fns
 
 
 def functions(txt):
-    parts = re.split(r'\n\t\.globl\t(\S+)\s*; -- Begin function \S+\n', txt)
+    parts = re.split(r'\n\t\.(?:globl|protected|weak)\t(\S+)\s*; -- Begin function \S+\n', txt)   # (comdat templates: .protected)
     return {parts[i]: parts[i + 1][:parts[i + 1].find('; -- End function')] for i in range(1, len(parts), 2)}
+
+
+def resources(txt):
+    """{kernel: {field: value}} from the .amdgpu_metadata note."""
+    out = {}
+    for entry in re.split(r'\n  - \.agpr_count:', txt[txt.find('amdhsa.kernels:'):])[1:]:
+        entry = '    .agpr_count:' + entry
+        name = re.search(r'\n\s+\.name:\s+(\S+)', entry)
+        if name:
+            out[name.group(1)] = {k: int(m.group(1)) for k in RES for m in [re.search(r'%s:\s+(\d+)' % re.escape(k), entry)] if m}
+    return out
 
 
 def normalise(body, name):
@@ -39,29 +71,66 @@ def normalise(body, name):
     b = re.sub(r'\.Lfunc_end\d+', '.Lfunc_end', b)
     b = re.sub(r'\.LBB\d+_', '.LBB_', b)
     b = re.sub(r';.*', '', b)
-    return [line.rstrip() for line in b.splitlines() if line.strip()]
+    # (symbol binding is not code: a template kernel moved into an anonymous namespace loses its .globl / .weak line)
+    return [line.rstrip() for line in b.splitlines() if line.strip() and not re.match(r'\s*\.(globl|weak|protected|hidden)\s', line)]
+
+
+def demangled(names, renames=()):
+    """{readable name: mangled name}"""
+    if not names:
+        return {}
+    names = list(names)
+    out = subprocess.run([CXXFILT], input='\n'.join(names), capture_output=True, text=True, check=True).stdout.split('\n')
+    table = {}
+    for mangled, d in zip(names, out):
+        d = re.sub(r'^void ', '', d.replace('(anonymous namespace)::', '').replace('> >', '>>').replace('> >', '>>'))
+        for old, new in renames:
+            d = re.sub(old, new, d)
+        table[d] = mangled
+    return table
 
 
 def main():
-    if len(sys.argv) < 3:
+    args = sys.argv[1:]
+    if len(args) < 2:
         sys.exit(__doc__)
-    rel = sys.argv[3] if len(sys.argv) > 3 else DEFAULT
+    rev_a, rev_b, files_a, files_b, renames, work = args[0], args[1], [], None, [], []
+    dest = files_a
+    for a in args[2:]:
+        if a == '--b':
+            files_b = dest = []
+        elif a == '--rename':
+            dest = renames
+        elif a == '--work':
+            dest = work
+        else:
+            dest.append(a)
+    files_a = files_a or [DEFAULT]
+    files_b = files_b or files_a
+    renames = [tuple(r.split('=', 1)) for r in renames]
     with tempfile.TemporaryDirectory() as tmp:
-        a, b = functions(asm_of(sys.argv[1], rel, tmp)), functions(asm_of(sys.argv[2], rel, tmp))
+        tmp = work[0] if work else tmp
+        a, b = asm_of(rev_a, files_a, tmp, 'a'), asm_of(rev_b, files_b, tmp, 'b')
+    da, db = demangled(a, renames), demangled(b)
     same = True
-    for name in a:
-        other = name if name in b else re.sub(r'(ELb[01])EEEv', r'\1ELb0EEEv', name)
-        if other not in b:
-            print('MISSING   %s' % name[:100])
+    matched = set()
+    for name in sorted(da):
+        other = name if name in db else re.sub(r'>\(', ', false>(', name, count=1)
+        if other not in db:
+            print('MISSING   %s' % name[:160])
             same = False
             continue
-        ok = normalise(a[name], name) == normalise(b[other], other)
+        matched.add(other)
+        (body_a, res_a), (body_b, res_b) = a[da[name]], b[db[other]]
+        ok = normalise(body_a, da[name]) == normalise(body_b, db[other])
         same &= ok
-        print('%s %s' % ('IDENTICAL' if ok else 'DIFFERENT', name[:100]))
-    for name in b:
-        if name not in a and re.sub(r'ELb0EEEv', 'EEEv', name) not in a:
-            print('NEW       %s' % name[:100])
-    print('default kernels unchanged' if same else 'DEFAULT KERNELS CHANGED')
+        print('%s %s' % ('IDENTICAL' if ok else 'DIFFERENT', name[:160]))
+        if not ok:
+            print('            ' + '  '.join('%s %s -> %s' % (k[1:], res_a.get(k), res_b.get(k)) for k in RES))
+    for name in sorted(db):
+        if name not in matched:
+            print('NEW       %s' % name[:160])
+    print('kernels unchanged' if same else 'KERNELS CHANGED')
     return 0 if same else 1
 
 

@@ -1,73 +1,32 @@
-// The convolution stack of the cnn_zhang encoder (models/encoders/core/cnn_zhang.py:41-174, after Zhang et al. 2017) for
-// gfx950: conv_layer 3 (frequency) x 5 (time) SAME stride 1 (cnn_util.py:50-84) and max_pool [3,1] / [3,1] SAME
-// (cnn_util.py:13-28) over per-frame images [N, F, W, C] NHWC.
+// The implicit-GEMM convolutions of any tap geometry (conv_common.h: Taps) for gfx950, SAME padding, stride 1, over
+// per-frame images [N, H, W, C] NHWC: the 3 (frequency) x 5 (time) conv_layer of the cnn_zhang encoder
+// (models/encoders/core/cnn_zhang.py:41-174, after Zhang et al. 2017; cnn_util.py:50-84) with its max_pool [3,1] / [3,1]
+// SAME (cnn_util.py:13-28), the 3x4 convolution of the student CNNs (asr_conv3x4_*), and the tiled forms of the VGG
+// front-end's 3x3 (entry points and image-resident forms: conv3x3.hip).
 //
-// The 128 / 256-channel layers are implicit GEMMs with bf16 operands and fp32 accumulation
-// (v_mfma_f32_16x16x32_bf16): the A tile is gathered straight from the image, one 64-wide k-tile = (one tap, 64
-// consecutive input channels) = 128 contiguous bytes of the shifted pixel, zero where the shifted pixel falls off the
-// frame.  Through im2col + GEMM a 256-channel layer would write and re-read a [pixels x 3840] patch matrix (15x its
-// activation bytes); here no patch is ever stored, and the weight image of a layer (<= 1.9 MB) stays in L2.
+// bf16 operands and fp32 accumulation (v_mfma_f32_16x16x32_bf16): the A tile is gathered straight from the image, one
+// 64-wide k-tile = (one tap, 64 consecutive input channels) = 128 contiguous bytes of the shifted pixel, zero where the
+// shifted pixel falls off the frame.  Through im2col + GEMM a 256-channel 3x5 layer would write and re-read a
+// [pixels x 3840] patch matrix (15x its activation bytes); here no patch is ever stored, and the weight image of a layer
+// (<= 1.9 MB) stays in L2.
 //   forward        out[p, co] = act(sum_{tap, ci} x[p + s_tap, ci] Wf[co][tap Cin + ci] + bias[co])
-//   data gradient  the same product on dOut with the flipped-tap image Wb (s_{14 - tap} = -s_tap), the ReLU / dropout
-//                  backward of the layer below in the epilogue (same gate convention as asr_conv3x3_bwd_data_relu)
+//   data gradient  the same product on dOut with the flipped-tap image Wb (s_{ntaps - 1 - tap} = -s_tap for odd widths), the
+//                  ReLU / dropout backward of the layer below in the epilogue (conv_gate_apply)
 //   weight grad    dW[tap Cin + ci][co] = sum_p x[p + s_tap, ci] dOut[p, co]: pixel-range slabs in the scratch arena, then
 //                  a fixed-order sum of the slabs (no float atomics: bitwise reproducible)
-// s_tap = (tap / 5 - 1, tap % 5 - 2): row (frequency) offset -1..1, column (time) offset -2..2.
-// The same kernels run the student CNNs' 3x4 SAME convolution (asr_conv3x4_*): the tap geometry is a template argument
-// (Taps), and the 3x5 instantiations are unchanged.
-#include "common.h"
+// s_tap = (tap / KW - OY, tap % KW - OX); 3x5: row (frequency) offset -1..1, column (time) offset -2..2.
+#include "conv_common.h"
+#include <limits.h>
 
 namespace {
 
-constexpr int KTAPS = 15;
-
-// Tap geometry of the implicit kernels: KW columns per row, and the (row, column) origin (OY, OX) of tap 0, i.e. tap t
-// reads the pixel shifted by (t / KW - OY, t % KW - OX).  3x5 SAME: origin (1, 2) for the forward and for the flipped
-// data-gradient image alike; 3x4 SAME (TensorFlow pads one column before and two after): origin (1, 1) forward,
-// (1, 2) for the flipped image.
-template <int KH_, int KW_, int OY_, int OX_>
-struct Taps {
-  static constexpr int KH = KH_, KW = KW_, OY = OY_, OX = OX_, N = KH_ * KW_;
-};
-typedef Taps<3, 5, 1, 2> Taps35;
-typedef Taps<3, 4, 1, 1> Taps34f;
-typedef Taps<3, 4, 1, 2> Taps34b;
-
-struct Gate35 {                 // epilogue operands of conv3x5_nt_kernel, act == 2 (data gradient) / act == 3 (forward)
-  const bf16_t* act;            // act == 2: activation of the layer below, [pixels, Cout of this product]
-  float keep;
-  uint64_t seed, offset;        // dropout: element e -> Philox block offset + e / 4 (asr_dropout_apply)
-  int use_drop;                 // act == 2: 0 = ReLU gate only, 1 = form the mask, 2 = `act` is the DROPPED output
-};
-
-// act: 0 none, 1 ReLU, 2 gate by the layer below (v = act > 0 ? v * mask : 0), 3 ReLU, round to bf16, then dropout
-__device__ __forceinline__ void gate35_apply(int act, const Gate35& g, size_t e, float (&v)[4]) {
-  typedef __attribute__((ext_vector_type(4))) unsigned short us4_t;
-  if (act == 1) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-  } else if (act == 2) {
-    const us4_t a = *reinterpret_cast<const us4_t*>(g.act + e);
-    float mk[4] = {1.f, 1.f, 1.f, 1.f};
-    if (g.use_drop == 1) asr_dropout_words(g.offset + e / 4, g.seed, g.keep, 1.f / g.keep, mk);
-    else if (g.use_drop == 2) { const float inv = 1.f / g.keep; mk[0] = mk[1] = mk[2] = mk[3] = inv; }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] = bf16_to_f32(a[r]) > 0.f ? v[r] * mk[r] : 0.f;
-  } else if (act == 3) {
-    float mk[4];
-    asr_dropout_words(g.offset + e / 4, g.seed, g.keep, 1.f / g.keep, mk);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] = bf16_to_f32(f32_to_bf16(fmaxf(v[r], 0.f))) * mk[r];
-  }
-}
-
-// Implicit GEMM: Mpix x Cout x (15 Cin); 256 threads = 2 x 2 waves over a 128 x BN tile, k-tile 64, two LDS stages with
+// Implicit GEMM: Mpix x Cout x (TP::N Cin); 256 threads = 2 x 2 waves over a 128 x BN tile, k-tile 64, two LDS stages with
 // the next k-tile's global loads in flight during the MFMAs.  Requires Cin % 64 == 0, Cout % BN == 0.
-template <typename TO, int BN, typename TP = Taps35>
-__global__ __launch_bounds__(256) void conv3x5_nt_kernel(int Mpix, int H, int W, int Cin, int Cout,
-                                                         const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wt,
-                                                         TO* __restrict__ Out, const float* __restrict__ bias, int act,
-                                                         Gate35 gate) {
+template <typename TO, int BN, typename TP>
+__global__ __launch_bounds__(256) void conv_nt_kernel(int Mpix, int H, int W, int Cin, int Cout,
+                                                      const bf16_t* __restrict__ X, const bf16_t* __restrict__ Wt,
+                                                      TO* __restrict__ Out, const float* __restrict__ bias, int act,
+                                                      ConvGate gate) {
   constexpr int BM = 128, BK = 64, LD = BK + 8;
   constexpr int STAGE = (BM + BN) * LD;
   constexpr int WN = BN / 2, TN = WN / 16;
@@ -173,7 +132,7 @@ __global__ __launch_bounds__(256) void conv3x5_nt_kernel(int Mpix, int H, int W,
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] += bv[r];
       }
-      if (act) gate35_apply(act, gate, (size_t)m * Cout + nb, v);
+      if (act) conv_gate_apply(act, gate, (size_t)m * Cout + nb, v);
       if constexpr (sizeof(TO) == 4) {
         *reinterpret_cast<f32x4_t*>(cp) = (f32x4_t){v[0], v[1], v[2], v[3]};
       } else {
@@ -184,12 +143,12 @@ __global__ __launch_bounds__(256) void conv3x5_nt_kernel(int Mpix, int H, int W,
   }
 }
 
-// weight images from the HWIO fp32 master [3][5][Cin][Cout] (tap = kh * 5 + kw):
-//   wf[co][tap Cin + ci] = w[tap][ci][co],   wb[ci][(14 - tap) Cout + co] = w[tap][ci][co]
-template <int NT = KTAPS>
-__global__ void conv3x5_prep_kernel(const float* __restrict__ w, int Cin, int Cout, bf16_t* __restrict__ wf,
-                                    bf16_t* __restrict__ wb) {
-  constexpr int KTAPS = NT;
+// weight images from the HWIO fp32 master [KH][KW][Cin][Cout] (tap = kh * KW + kw, KTAPS = KH KW):
+//   wf[co][tap Cin + ci] = w[tap][ci][co]                    (forward:   B^T of x * W)
+//   wb[ci][(KTAPS - 1 - tap) Cout + co] = w[tap][ci][co]     (data grad: B^T of dOut * flipped W)
+template <int KTAPS>
+__global__ void conv_prep_kernel(const float* __restrict__ w, int Cin, int Cout, bf16_t* __restrict__ wf,
+                                 bf16_t* __restrict__ wb) {
   const size_t total = (size_t)KTAPS * Cin * Cout;
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     const int co = i % Cout, ci = (i / Cout) % Cin, tap = i / ((size_t)Cin * Cout);
@@ -202,10 +161,10 @@ __global__ void conv3x5_prep_kernel(const float* __restrict__ w, int Cin, int Co
 // Weight gradient, slab z of the pixel range [z kchunk, (z + 1) kchunk): partial[z][m][n], m = tap Cin + ci.  A tile =
 // 128 (tap, ci) columns x 64 pixels gathered from the image, B tile = 64 pixels x 128 output channels; both staged in
 // LDS as [column][pixel] (pixel pairs packed into 32-bit words), XOR-swizzled by 16-byte groups.
-template <typename TP = Taps35>
-__global__ __launch_bounds__(256) void conv3x5_wgrad_kernel(int Mpix, int H, int W, int Cin, int Cout,
-                                                            const bf16_t* __restrict__ X, const bf16_t* __restrict__ dY,
-                                                            int kchunk, float* __restrict__ partial) {
+template <typename TP>
+__global__ __launch_bounds__(256) void conv_wgrad_kernel(int Mpix, int H, int W, int Cin, int Cout,
+                                                         const bf16_t* __restrict__ X, const bf16_t* __restrict__ dY,
+                                                         int kchunk, float* __restrict__ partial) {
   constexpr int KTAPS = TP::N;
   constexpr int BM = 128, BN = 128, BK = 64, LD = BK + 8;
   constexpr int STAGE = (BM + BN) * LD;
@@ -314,8 +273,8 @@ __global__ __launch_bounds__(256) void conv3x5_wgrad_kernel(int Mpix, int H, int
 }
 
 // dw[i] (+)= sum_{z = 0 .. S-1} partial[z][i], slabs added in index order (eight requests in flight)
-__global__ void conv3x5_slab_sum_kernel(const float* __restrict__ partial, int S, size_t total, float* __restrict__ dw,
-                                        int accumulate) {
+__global__ void conv_slab_sum_kernel(const float* __restrict__ partial, int S, size_t total, float* __restrict__ dw,
+                                     int accumulate) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
     float v = 0.f;
     int z = 0;
@@ -401,10 +360,11 @@ static inline int grid_for(size_t total) {
   return (int)(b < 16384 ? (b ? b : 1) : 16384);
 }
 
-template <typename TP = Taps35>
-static int conv3x5_launch(asr_handle* h, const char* what, const void* x, int N, int H, int W, int Cin, const void* wt,
-                          const float* bias, int Cout, int act, const Gate35& gate, bool out_f32, void* out,
-                          asr_stream s) {
+}  // namespace
+
+template <typename TP>
+int asr_conv_nt(asr_handle* h, const char* what, const void* x, int N, int H, int W, int Cin, const void* wt,
+                const float* bias, int Cout, int act, const ConvGate& gate, bool out_f32, void* out, asr_stream s) {
   if (!x || !wt || !out || N < 1 || H < 1 || W < 1) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "%s: bad args", what);
   // K / N: reduction and output channels of this product (the data gradient's are the layer's Cout / Cin)
   if (Cin % 64 != 0 || Cout % 64 != 0 || Cin < 64 || Cout < 64)
@@ -417,37 +377,93 @@ static int conv3x5_launch(asr_handle* h, const char* what, const void* x, int N,
   const long long blocks = (long long)((Mpix + 127) / 128) * (Cout / (bn128 ? 128 : 64));
   if (blocks >= (1ll << 31)) ASR_FAIL(h, ASR_ERR_UNSUPPORTED, "%s: grid too large", what);
   hipStream_t st = (hipStream_t)s;
-#define ASR_C35(TO, BN) \
-  hipLaunchKernelGGL((conv3x5_nt_kernel<TO, BN, TP>), dim3((unsigned)blocks), dim3(256), 0, st, Mpix, H, W, Cin, Cout, \
+#define ASR_CNT(TO, BN) \
+  hipLaunchKernelGGL((conv_nt_kernel<TO, BN, TP>), dim3((unsigned)blocks), dim3(256), 0, st, Mpix, H, W, Cin, Cout, \
                      (const bf16_t*)x, (const bf16_t*)wt, (TO*)out, bias, act, gate)
-  if (out_f32) { if (bn128) ASR_C35(float, 128); else ASR_C35(float, 64); }
-  else { if (bn128) ASR_C35(bf16_t, 128); else ASR_C35(bf16_t, 64); }
-#undef ASR_C35
+  if (out_f32) { if (bn128) ASR_CNT(float, 128); else ASR_CNT(float, 64); }
+  else { if (bn128) ASR_CNT(bf16_t, 128); else ASR_CNT(bf16_t, 64); }
+#undef ASR_CNT
+  ASR_CHECK_LAUNCH(h, what);
+  return ASR_OK;
+}
+template int asr_conv_nt<Taps33>(asr_handle*, const char*, const void*, int, int, int, int, const void*, const float*, int,
+                                 int, const ConvGate&, bool, void*, asr_stream);
+
+int asr_conv_prep(asr_handle* h, const char* what, int ntaps, const float* w_hwio, int Cin, int Cout, void* wt_fwd,
+                  void* wt_bwd, asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  if (!w_hwio || !wt_fwd || !wt_bwd || Cin < 1 || Cout < 1) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "%s: bad args", what);
+  auto k = ntaps == 9 ? conv_prep_kernel<9> : ntaps == 12 ? conv_prep_kernel<12> : ntaps == 15 ? conv_prep_kernel<15> : nullptr;
+  if (!k) ASR_FAIL(h, ASR_ERR_UNSUPPORTED, "%s: %d taps", what, ntaps);
+  hipLaunchKernelGGL(k, dim3(grid_for((size_t)ntaps * Cin * Cout)), dim3(256), 0, (hipStream_t)s, w_hwio, Cin, Cout,
+                     (bf16_t*)wt_fwd, (bf16_t*)wt_bwd);
   ASR_CHECK_LAUNCH(h, what);
   return ASR_OK;
 }
 
-}  // namespace
+int asr_conv_wgrad_plan(asr_handle* h, const char* what, int Mpix, int tiles, size_t slab_bytes, int max_slabs, int* S,
+                        int* kchunk) {
+  const size_t room = h->scratch_bytes > ASR_XCH_BYTES ? h->scratch_bytes - ASR_XCH_BYTES : 0;
+  int s = (2048 + tiles - 1) / tiles;
+  const int maxS = (Mpix + 511) / 512;
+  if (s > maxS) s = maxS;
+  if (s > max_slabs) s = max_slabs;
+  if ((size_t)s > room / slab_bytes) s = (int)(room / slab_bytes);
+  if (s < 1) ASR_FAIL(h, ASR_ERR_WORKSPACE, "%s: scratch too small", what);
+  *kchunk = ((Mpix + s - 1) / s + 63) / 64 * 64;
+  *S = (Mpix + *kchunk - 1) / *kchunk;
+  return ASR_OK;
+}
+
+template <typename TP>
+void asr_conv_wgrad_tiled(const void* x, const void* dy, int Mpix, int H, int W, int Cin, int Cout, int S, int kchunk,
+                          float* partial, hipStream_t st) {
+  hipLaunchKernelGGL(conv_wgrad_kernel<TP>, dim3((Cout + 127) / 128, (TP::N * Cin + 127) / 128, S), dim3(256), 0, st, Mpix,
+                     H, W, Cin, Cout, (const bf16_t*)x, (const bf16_t*)dy, kchunk, partial);
+}
+template void asr_conv_wgrad_tiled<Taps33>(const void*, const void*, int, int, int, int, int, int, int, float*, hipStream_t);
+
+void asr_conv_slab_sum(const float* partial, int S, size_t total, float* dw, int accumulate, hipStream_t st) {
+  hipLaunchKernelGGL(conv_slab_sum_kernel, dim3(grid_for(total)), dim3(256), 0, st, partial, S, total, dw, accumulate);
+}
 
 extern "C" int asr_colsum(asr_handle* h, int dtype, const void* a, int M, int N, int lda, float* out, asr_stream s);
 
+// weight + bias gradient of the tiled kernels
+template <typename TP>
+static int conv_wgrad_launch(asr_handle* h, const char* what, const void* x, const void* dy, int N, int H, int W, int Cin,
+                             int Cout, float* dw, float* dbias, asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  if (!x || !dy || !dw || N < 1 || H < 1 || W < 1) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "%s: bad args", what);
+  if (Cin % 8 != 0 || Cout % 8 != 0)
+    ASR_FAIL(h, ASR_ERR_UNSUPPORTED, "%s: Cin=%d, Cout=%d must be multiples of 8", what, Cin, Cout);
+  const long long mp = (long long)N * H * W;
+  if (mp >= (1ll << 31) - 128) ASR_FAIL(h, ASR_ERR_UNSUPPORTED, "%s: %lld pixels", what, mp);
+  const int Mpix = (int)mp, M = TP::N * Cin;
+  int S, kchunk;
+  const int rc = asr_conv_wgrad_plan(h, what, Mpix, ((M + 127) / 128) * ((Cout + 127) / 128),
+                                     (size_t)M * Cout * sizeof(float), INT_MAX, &S, &kchunk);
+  if (rc != ASR_OK) return rc;
+  float* partial = (float*)h->scratch;
+  asr_conv_wgrad_tiled<TP>(x, dy, Mpix, H, W, Cin, Cout, S, kchunk, partial, (hipStream_t)s);
+  asr_conv_slab_sum(partial, S, (size_t)M * Cout, dw, 0, (hipStream_t)s);
+  ASR_CHECK_LAUNCH(h, what);
+  if (dbias) return asr_colsum(h, ASR_BF16, dy, Mpix, Cout, Cout, dbias, s);
+  return ASR_OK;
+}
+
+static const ConvGate kNoGate = {nullptr, 1.f, 0, 0, 0};
+
+// ---- cnn_zhang: 3x5
 extern "C" int asr_conv3x5_prep_weights(asr_handle* h, const float* w_hwio, int Cin, int Cout, void* wt_fwd, void* wt_bwd,
                                         asr_stream s) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  if (!w_hwio || !wt_fwd || !wt_bwd || Cin < 1 || Cout < 1)
-    ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_conv3x5_prep_weights: bad args");
-  const size_t total = (size_t)KTAPS * Cin * Cout;
-  hipLaunchKernelGGL(conv3x5_prep_kernel<KTAPS>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)s, w_hwio, Cin, Cout,
-                     (bf16_t*)wt_fwd, (bf16_t*)wt_bwd);
-  ASR_CHECK_LAUNCH(h, "asr_conv3x5_prep_weights");
-  return ASR_OK;
+  return asr_conv_prep(h, "asr_conv3x5_prep_weights", 15, w_hwio, Cin, Cout, wt_fwd, wt_bwd, s);
 }
 
 extern "C" int asr_conv3x5_fwd(asr_handle* h, const void* x, int N, int H, int W, int Cin, const void* wt_fwd,
                                const float* bias, int Cout, int relu, void* out, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  Gate35 g = {nullptr, 1.f, 0, 0, 0};
-  return conv3x5_launch(h, "asr_conv3x5_fwd", x, N, H, W, Cin, wt_fwd, bias, Cout, relu ? 1 : 0, g, false, out, s);
+  return asr_conv_nt<Taps35>(h, "asr_conv3x5_fwd", x, N, H, W, Cin, wt_fwd, bias, Cout, relu ? 1 : 0, kNoGate, false, out, s);
 }
 
 extern "C" int asr_conv3x5_fwd_drop(asr_handle* h, const void* x, int N, int H, int W, int Cin, const void* wt_fwd,
@@ -455,15 +471,14 @@ extern "C" int asr_conv3x5_fwd_drop(asr_handle* h, const void* x, int N, int H, 
                                     asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
   if (!(keep_prob > 0.f && keep_prob <= 1.f)) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_conv3x5_fwd_drop: keep_prob %g", keep_prob);
-  Gate35 g = {nullptr, keep_prob, seed, offset, 1};
-  return conv3x5_launch(h, "asr_conv3x5_fwd_drop", x, N, H, W, Cin, wt_fwd, bias, Cout, 3, g, false, out, s);
+  const ConvGate g = {nullptr, keep_prob, seed, offset, 1};
+  return asr_conv_nt<Taps35>(h, "asr_conv3x5_fwd_drop", x, N, H, W, Cin, wt_fwd, bias, Cout, 3, g, false, out, s);
 }
 
 extern "C" int asr_conv3x5_bwd_data(asr_handle* h, const void* dy, int N, int H, int W, int Cout, const void* wt_bwd,
                                     int Cin, float* dx, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  Gate35 g = {nullptr, 1.f, 0, 0, 0};
-  return conv3x5_launch(h, "asr_conv3x5_bwd_data", dy, N, H, W, Cout, wt_bwd, nullptr, Cin, 0, g, true, dx, s);
+  return asr_conv_nt<Taps35>(h, "asr_conv3x5_bwd_data", dy, N, H, W, Cout, wt_bwd, nullptr, Cin, 0, kNoGate, true, dx, s);
 }
 
 extern "C" int asr_conv3x5_bwd_data_relu(asr_handle* h, const void* dy, int N, int H, int W, int Cout, const void* wt_bwd,
@@ -472,46 +487,12 @@ extern "C" int asr_conv3x5_bwd_data_relu(asr_handle* h, const void* dy, int N, i
   if (!h) return ASR_ERR_INVALID_ARG;
   if (!act_below || use_drop < 0 || use_drop > 2 || (use_drop && !(keep_prob > 0.f && keep_prob <= 1.f)))
     ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_conv3x5_bwd_data_relu: bad args");
-  Gate35 g = {(const bf16_t*)act_below, keep_prob, seed, offset, use_drop};
-  return conv3x5_launch(h, "asr_conv3x5_bwd_data_relu", dy, N, H, W, Cout, wt_bwd, nullptr, Cin, 2, g, false, dpre_below, s);
-}
-
-// weight + bias gradient of the implicit kernels (pixel-range slabs in the scratch arena, fixed-order slab sum)
-template <typename TP>
-static int conv_wgrad_launch(asr_handle* h, const char* what, const void* x, const void* dy, int N, int H, int W, int Cin,
-                             int Cout, float* dw, float* dbias, asr_stream s) {
-  if (!x || !dy || !dw || N < 1 || H < 1 || W < 1) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "%s: bad args", what);
-  if (Cin % 8 != 0 || Cout % 8 != 0)
-    ASR_FAIL(h, ASR_ERR_UNSUPPORTED, "%s: Cin=%d, Cout=%d must be multiples of 8", what, Cin, Cout);
-  const long long mp = (long long)N * H * W;
-  if (mp >= (1ll << 31) - 128) ASR_FAIL(h, ASR_ERR_UNSUPPORTED, "%s: %lld pixels", what, mp);
-  const int Mpix = (int)mp, M = TP::N * Cin;
-  const size_t slab = (size_t)M * Cout * sizeof(float);
-  const size_t room = h->scratch_bytes > ASR_XCH_BYTES ? h->scratch_bytes - ASR_XCH_BYTES : 0;
-  const int tm = (M + 127) / 128, tn = (Cout + 127) / 128;
-  // ~2048 workgroups in all, at least 512 pixels per slab, as many slabs as the scratch arena holds
-  int S = (2048 + tm * tn - 1) / (tm * tn);
-  const int maxS = (Mpix + 511) / 512;
-  if (S > maxS) S = maxS;
-  if ((size_t)S > room / slab) S = (int)(room / slab);
-  if (S < 1) ASR_FAIL(h, ASR_ERR_WORKSPACE, "%s: scratch too small", what);
-  int kchunk = (Mpix + S - 1) / S;
-  kchunk = (kchunk + 63) / 64 * 64;
-  S = (Mpix + kchunk - 1) / kchunk;
-  float* partial = (float*)h->scratch;
-  hipStream_t st = (hipStream_t)s;
-  hipLaunchKernelGGL(conv3x5_wgrad_kernel<TP>, dim3(tn, tm, S), dim3(256), 0, st, Mpix, H, W, Cin, Cout,
-                     (const bf16_t*)x, (const bf16_t*)dy, kchunk, partial);
-  const size_t total = (size_t)M * Cout;
-  hipLaunchKernelGGL(conv3x5_slab_sum_kernel, dim3(grid_for(total)), dim3(256), 0, st, partial, S, total, dw, 0);
-  ASR_CHECK_LAUNCH(h, what);
-  if (dbias) return asr_colsum(h, ASR_BF16, dy, Mpix, Cout, Cout, dbias, s);
-  return ASR_OK;
+  const ConvGate g = {(const bf16_t*)act_below, keep_prob, seed, offset, use_drop};
+  return asr_conv_nt<Taps35>(h, "asr_conv3x5_bwd_data_relu", dy, N, H, W, Cout, wt_bwd, nullptr, Cin, 2, g, false, dpre_below, s);
 }
 
 extern "C" int asr_conv3x5_bwd_weight_bias(asr_handle* h, const void* x, const void* dy, int N, int H, int W, int Cin,
                                            int Cout, float* dw, float* dbias, asr_stream s) {
-  if (!h) return ASR_ERR_INVALID_ARG;
   return conv_wgrad_launch<Taps35>(h, "asr_conv3x5_bwd_weight_bias", x, dy, N, H, W, Cin, Cout, dw, dbias, s);
 }
 
@@ -549,37 +530,26 @@ extern "C" int asr_maxpool3x1_bwd(asr_handle* h, int dtype, const void* dout, co
   return ASR_OK;
 }
 
-// ---- the 3x4 SAME convolution of the student CNNs (CNN2, models/encoders/core/student_cnn_ctc.py:111-117): the same
-// kernels on the 12-tap geometry
+// ---- the 3x4 SAME convolution of the student CNNs (CNN2, models/encoders/core/student_cnn_ctc.py:111-117)
 extern "C" int asr_conv3x4_prep_weights(asr_handle* h, const float* w_hwio, int Cin, int Cout, void* wt_fwd, void* wt_bwd,
                                         asr_stream s) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  if (!w_hwio || !wt_fwd || !wt_bwd || Cin < 1 || Cout < 1)
-    ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_conv3x4_prep_weights: bad args");
-  const size_t total = (size_t)12 * Cin * Cout;
-  hipLaunchKernelGGL(conv3x5_prep_kernel<12>, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)s, w_hwio, Cin, Cout,
-                     (bf16_t*)wt_fwd, (bf16_t*)wt_bwd);
-  ASR_CHECK_LAUNCH(h, "asr_conv3x4_prep_weights");
-  return ASR_OK;
+  return asr_conv_prep(h, "asr_conv3x4_prep_weights", 12, w_hwio, Cin, Cout, wt_fwd, wt_bwd, s);
 }
 
 extern "C" int asr_conv3x4_fwd(asr_handle* h, const void* x, int N, int H, int W, int Cin, const void* wt_fwd,
                                const float* bias, int Cout, int relu, int out_f32, void* out, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  Gate35 g = {nullptr, 1.f, 0, 0, 0};
-  return conv3x5_launch<Taps34f>(h, "asr_conv3x4_fwd", x, N, H, W, Cin, wt_fwd, bias, Cout, relu ? 1 : 0, g,
-                                 out_f32 != 0, out, s);
+  return asr_conv_nt<Taps34f>(h, "asr_conv3x4_fwd", x, N, H, W, Cin, wt_fwd, bias, Cout, relu ? 1 : 0, kNoGate, out_f32 != 0,
+                              out, s);
 }
 
 extern "C" int asr_conv3x4_bwd_data(asr_handle* h, const void* dy, int N, int H, int W, int Cout, const void* wt_bwd,
                                     int Cin, float* dx, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  Gate35 g = {nullptr, 1.f, 0, 0, 0};
-  return conv3x5_launch<Taps34b>(h, "asr_conv3x4_bwd_data", dy, N, H, W, Cout, wt_bwd, nullptr, Cin, 0, g, true, dx, s);
+  return asr_conv_nt<Taps34b>(h, "asr_conv3x4_bwd_data", dy, N, H, W, Cout, wt_bwd, nullptr, Cin, 0, kNoGate, true, dx, s);
 }
 
 extern "C" int asr_conv3x4_bwd_weight_bias(asr_handle* h, const void* x, const void* dy, int N, int H, int W, int Cin,
                                            int Cout, float* dw, float* dbias, asr_stream s) {
-  if (!h) return ASR_ERR_INVALID_ARG;
   return conv_wgrad_launch<Taps34f>(h, "asr_conv3x4_bwd_weight_bias", x, dy, N, H, W, Cin, Cout, dw, dbias, s);
 }

@@ -8,6 +8,7 @@
 // (An implicit-GEMM A-operand gather that never materialises the patches is the planned upgrade;
 // DESIGN.md.)  Everything in this file is HBM-bound data movement.
 #include "common.h"
+#include "mfma_tn.h"
 
 namespace {
 
@@ -393,17 +394,10 @@ __global__ __launch_bounds__(256) void conv3x3_smallc_wgrad_kernel(const bf16_t*
 // Weight gradient of the same layer on the matrix cores: dW[k][co] = sum_p patch[p][k] dpre[p][co] is a reduction-major
 // product with M = 32 (27 used), N = 64 and K = pixels.  A wave stages 32 pixels at a time: each lane gathers 16 patch
 // values of ONE pixel (one coordinate computation) and loads 64 bytes of that pixel's dpre row, both written as whole
-// 32-byte rows into [16-column subtile][pixel] images -- the layout gemm.hip's reduction-major GEMM uses -- from which
-// the transposing LDS reads (ds_read_b64_tr_b16) deliver the MFMA operands: 8 MFMAs per 32 pixels instead of 27 x 64
+// 32-byte rows into [16-column subtile][pixel] images -- the layout of the reduction-major GEMM (mfma_tn.h) -- from which
+// its transposing LDS reads (tn_frag) deliver the MFMA operands: 8 MFMAs per 32 pixels instead of 27 x 64
 // vector multiply-adds per pixel.  Partials per workgroup as before.
 constexpr int SCW_SUB = 32 * 32 + 32;                     // bytes from one [32 pixels][16 columns] subtile to the next
-__device__ __forceinline__ bf16x8_t scw_frag(const char* p) {
-  typedef __attribute__((ext_vector_type(4))) short s4_t;
-  typedef __attribute__((address_space(3))) s4_t lds4_t;
-  const s4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4_t*)(p));
-  const s4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds4_t*)(p + 128));
-  return (bf16x8_t){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
 template <int CIN>
 __global__ __launch_bounds__(256) void conv3x3_smallc_wgrad_mfma_kernel(const bf16_t* __restrict__ x,
                                                                         const bf16_t* __restrict__ dpre, size_t Npix, int H,
@@ -462,9 +456,9 @@ __global__ __launch_bounds__(256) void conv3x3_smallc_wgrad_mfma_kernel(const bf
     {
       bf16x8_t a[2], b[4];
 #pragma unroll
-      for (int i = 0; i < 2; ++i) a[i] = scw_frag(my + i * SCW_SUB + piece);
+      for (int i = 0; i < 2; ++i) a[i] = tn_frag(my + i * SCW_SUB + piece);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) b[j] = scw_frag(my + (2 + j) * SCW_SUB + piece);
+      for (int j = 0; j < 4; ++j) b[j] = tn_frag(my + (2 + j) * SCW_SUB + piece);
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll

@@ -457,19 +457,6 @@ def gemm(A, B, transA=False, transB=False, bias=None, out=None, out_dtype=None, 
     return out
 
 
-# ---------------------------------------------------------------- VGG front-end
-def conv3x3_prep_weights(w_hwio):
-    """fp32 [3,3,Cin,Cout] -> (wt_fwd bf16 [Cout, 9*Cin], wt_bwd bf16 [Cin, 9*Cout])."""
-    h = _h(w_hwio)
-    _chk(w_hwio, torch.float32, 'w')
-    _, _, Cin, Cout = w_hwio.shape
-    wf = torch.empty((Cout, 9 * Cin), dtype=torch.bfloat16, device=w_hwio.device)
-    wb = torch.empty((Cin, 9 * Cout), dtype=torch.bfloat16, device=w_hwio.device)
-    h.check(h.lib.asr_conv3x3_prep_weights(h.h, _p(w_hwio.contiguous()), Cin, Cout, _p(wf), _p(wb), _s()),
-            'asr_conv3x3_prep_weights')
-    return wf, wb
-
-
 def _out_like(out, shape, dtype, device, what):
     """`out` (a contiguous tensor of exactly this shape / dtype, e.g. a slice of a larger one along the first axis) or a fresh one."""
     if out is None:
@@ -479,38 +466,122 @@ def _out_like(out, shape, dtype, device, what):
     return out
 
 
-def conv3x3_fwd(x_nhwc, wt_fwd, bias, relu=True, out=None):
+# ---------------------------------------------------------------- 3xK implicit-GEMM convolutions (VGG 3x3, cnn_zhang 3x5, students 3x4)
+# One implementation per wrapper, parameterised by the filter and the C symbol prefix (csrc/conv.hip is templated on the
+# tap geometry; csrc/conv3x3.hip adds the image-resident 3x3 forms behind the same signatures); the public conv3x3_* /
+# conv3x5_* / conv3x4_* names are bound below with their own signatures.
+_K3X3 = (3, 3, 'conv3x3')
+_K3X5 = (3, 5, 'conv3x5')
+_K3X4 = (3, 4, 'conv3x4')
+
+
+def _conv3xk_prep_weights(geom, w_hwio):
+    kh, kw, pre = geom
+    fn = pre + '_prep_weights'
+    h = _h(w_hwio)
+    _chk(w_hwio, torch.float32, 'w')
+    fh, fw, Cin, Cout = w_hwio.shape
+    if (fh, fw) != (kh, kw):
+        raise ValueError('%s: filter is %dx%d' % (fn, fh, fw))
+    wf = torch.empty((Cout, kh * kw * Cin), dtype=torch.bfloat16, device=w_hwio.device)
+    wb = torch.empty((Cin, kh * kw * Cout), dtype=torch.bfloat16, device=w_hwio.device)
+    h.check(getattr(h.lib, 'asr_' + fn)(h.h, _p(w_hwio.contiguous()), Cin, Cout, _p(wf), _p(wb), _s()), 'asr_' + fn)
+    return wf, wb
+
+
+def _conv3xk_fwd(geom, x_nhwc, wt_fwd, bias, relu, out, f32_out=None):
+    """f32_out: None for asr_conv3x3_fwd / asr_conv3x5_fwd (bf16 output only); asr_conv3x4_fwd takes it as one more argument."""
+    fn = geom[2] + '_fwd'
     h = _h(x_nhwc)
     _chk(x_nhwc, torch.bfloat16, 'x')
     N, H, W, Cin = x_nhwc.shape
     Cout = wt_fwd.shape[0]
-    out = _out_like(out, (N, H, W, Cout), torch.bfloat16, x_nhwc.device, 'conv3x3_fwd')
-    h.check(h.lib.asr_conv3x3_fwd(h.h, _p(x_nhwc), N, H, W, Cin, _p(wt_fwd), _p(bias), Cout, 1 if relu else 0,
-                                  _p(out), _s()), 'asr_conv3x3_fwd')
+    out = _out_like(out, (N, H, W, Cout), torch.float32 if f32_out else torch.bfloat16, x_nhwc.device, fn)
+    extra = () if f32_out is None else (int(f32_out),)
+    h.check(getattr(h.lib, 'asr_' + fn)(h.h, _p(x_nhwc), N, H, W, Cin, _p(wt_fwd), _p(bias), Cout, 1 if relu else 0,
+                                        *extra, _p(out), _s()), 'asr_' + fn)
     return out
 
 
-def conv3x3_fwd_drop(x_nhwc, wt_fwd, bias, drop, out=None):
-    """dropout_apply(conv3x3_fwd(x, ..., relu=True), *drop) in one launch (the undropped activation is never written)."""
+def _conv3xk_fwd_drop(geom, x_nhwc, wt_fwd, bias, drop, out):
+    fn = geom[2] + '_fwd_drop'
     h = _h(x_nhwc)
     _chk(x_nhwc, torch.bfloat16, 'x')
     N, H, W, Cin = x_nhwc.shape
     Cout = wt_fwd.shape[0]
-    out = _out_like(out, (N, H, W, Cout), torch.bfloat16, x_nhwc.device, 'conv3x3_fwd_drop')
-    h.check(h.lib.asr_conv3x3_fwd_drop(h.h, _p(x_nhwc), N, H, W, Cin, _p(wt_fwd), _p(bias), Cout, float(drop[0]),
-                                       int(drop[1]), int(drop[2]), _p(out), _s()), 'asr_conv3x3_fwd_drop')
+    out = _out_like(out, (N, H, W, Cout), torch.bfloat16, x_nhwc.device, fn)
+    h.check(getattr(h.lib, 'asr_' + fn)(h.h, _p(x_nhwc), N, H, W, Cin, _p(wt_fwd), _p(bias), Cout, float(drop[0]),
+                                        int(drop[1]), int(drop[2]), _p(out), _s()), 'asr_' + fn)
     return out
 
 
-def conv3x3_bwd_data(dy_nhwc, wt_bwd):
+def _conv3xk_bwd_data(geom, dy_nhwc, wt_bwd):
+    fn = geom[2] + '_bwd_data'
     h = _h(dy_nhwc)
     _chk(dy_nhwc, torch.bfloat16, 'dy')
     N, H, W, Cout = dy_nhwc.shape
     Cin = wt_bwd.shape[0]
     dx = torch.empty((N, H, W, Cin), dtype=torch.float32, device=dy_nhwc.device)
-    h.check(h.lib.asr_conv3x3_bwd_data(h.h, _p(dy_nhwc), N, H, W, Cout, _p(wt_bwd), Cin, _p(dx), _s()),
-            'asr_conv3x3_bwd_data')
+    h.check(getattr(h.lib, 'asr_' + fn)(h.h, _p(dy_nhwc), N, H, W, Cout, _p(wt_bwd), Cin, _p(dx), _s()), 'asr_' + fn)
     return dx
+
+
+def _conv3xk_bwd_data_relu(geom, dy_nhwc, wt_bwd, act_below, drop, dropped):
+    fn = geom[2] + '_bwd_data_relu'
+    h = _h(dy_nhwc)
+    _chk(dy_nhwc, torch.bfloat16, 'dy')
+    _chk(act_below, torch.bfloat16, 'act_below')
+    N, H, W, Cout = dy_nhwc.shape
+    Cin = wt_bwd.shape[0]
+    if tuple(act_below.shape) != (N, H, W, Cin):
+        raise ValueError('%s: act_below has shape %s' % (fn, tuple(act_below.shape)))
+    dpre = torch.empty((N, H, W, Cin), dtype=torch.bfloat16, device=dy_nhwc.device)
+    k, sd, off = drop if drop is not None else (1.0, 0, 0)
+    # dropped=True: act_below is the DROPPED activation (*_fwd_drop): no mask is formed, dx * (1 / keep) where it is > 0
+    mode = 0 if drop is None else (2 if dropped else 1)
+    h.check(getattr(h.lib, 'asr_' + fn)(h.h, _p(dy_nhwc), N, H, W, Cout, _p(wt_bwd), Cin, _p(act_below), float(k), int(sd),
+                                        int(off), mode, _p(dpre), _s()), 'asr_' + fn)
+    return dpre
+
+
+def _conv3xk_bwd_weight_bias(geom, x_nhwc, dy_nhwc, dw, dbias):
+    kh, kw, pre = geom
+    taps, fn = kh * kw, pre + '_bwd_weight_bias'
+    h = _h(x_nhwc)
+    _chk(x_nhwc, torch.bfloat16, 'x')
+    _chk(dy_nhwc, torch.bfloat16, 'dy')
+    if dbias is not None:
+        _chk(dbias, torch.float32, 'dbias')
+    N, H, W, Cin = x_nhwc.shape
+    Cout = dy_nhwc.shape[3]
+    if dw.numel() != taps * Cin * Cout or not dw.is_contiguous():
+        raise ValueError('%s: dw must be a contiguous [%d*Cin, Cout] fp32 tensor' % (fn, taps))
+    if dbias is not None and dbias.numel() != Cout:
+        raise ValueError('%s: dbias has %d elements, Cout = %d' % (fn, dbias.numel(), Cout))
+    h.check(getattr(h.lib, 'asr_' + fn)(h.h, _p(x_nhwc), _p(dy_nhwc), N, H, W, Cin, Cout, _p(dw), _p(dbias), _s()),
+            'asr_' + fn)
+    return dw, dbias
+
+
+# ---------------------------------------------------------------- VGG front-end
+def conv3x3_prep_weights(w_hwio):
+    """fp32 [3,3,Cin,Cout] -> (wt_fwd bf16 [Cout, 9*Cin], wt_bwd bf16 [Cin, 9*Cout]: the flipped-tap image)."""
+    return _conv3xk_prep_weights(_K3X3, w_hwio)
+
+
+def conv3x3_fwd(x_nhwc, wt_fwd, bias, relu=True, out=None):
+    """relu?(conv3x3 SAME(x) + bias): x bf16 [N,H,W,Cin] -> bf16 [N,H,W,Cout] (implicit GEMM, image-resident where it fits)."""
+    return _conv3xk_fwd(_K3X3, x_nhwc, wt_fwd, bias, relu, out)
+
+
+def conv3x3_fwd_drop(x_nhwc, wt_fwd, bias, drop, out=None):
+    """dropout_apply(conv3x3_fwd(x, ..., relu=True), *drop) in one launch (the undropped activation is never written)."""
+    return _conv3xk_fwd_drop(_K3X3, x_nhwc, wt_fwd, bias, drop, out)
+
+
+def conv3x3_bwd_data(dy_nhwc, wt_bwd):
+    """dx fp32 [N,H,W,Cin] = data gradient of the 3x3 convolution (dy bf16 [N,H,W,Cout])."""
+    return _conv3xk_bwd_data(_K3X3, dy_nhwc, wt_bwd)
 
 
 def conv3x3_smallc_fwd(x_nhwc, w2d, bias, relu=True):
@@ -565,19 +636,7 @@ def conv3x3_smallc_bwd_weight_bias(x_nhwc, dpre_nhwc, dw, dbias):
 
 def conv3x3_bwd_data_relu(dy_nhwc, wt_bwd, act_below, drop=None, dropped=False):
     """relu_bwd(conv3x3_bwd_data(dy, wt_bwd), act_below, drop=drop) without the fp32 gradient in between -> bf16."""
-    h = _h(dy_nhwc)
-    _chk(dy_nhwc, torch.bfloat16, 'dy')
-    _chk(act_below, torch.bfloat16, 'act_below')
-    N, H, W, Cout = dy_nhwc.shape
-    Cin = wt_bwd.shape[0]
-    dpre = torch.empty((N, H, W, Cin), dtype=torch.bfloat16, device=dy_nhwc.device)
-    k, sd, off = drop if drop is not None else (1.0, 0, 0)
-    # dropped=True: act_below is the DROPPED activation (conv3x3_fwd_drop): no mask is formed, dx * (1 / keep) where it is > 0
-    mode = 0 if drop is None else (2 if dropped else 1)
-    h.check(h.lib.asr_conv3x3_bwd_data_relu(h.h, _p(dy_nhwc), N, H, W, Cout, _p(wt_bwd), Cin, _p(act_below), float(k),
-                                            int(sd), int(off), mode, _p(dpre), _s()),
-            'asr_conv3x3_bwd_data_relu')
-    return dpre
+    return _conv3xk_bwd_data_relu(_K3X3, dy_nhwc, wt_bwd, act_below, drop, dropped)
 
 
 def conv3x3_bwd_weight(x_nhwc, dy_nhwc, dw, accumulate=False):
@@ -595,17 +654,7 @@ def conv3x3_bwd_weight(x_nhwc, dy_nhwc, dw, accumulate=False):
 def conv3x3_bwd_weight_bias(x_nhwc, dy_nhwc, dw, dbias):
     """dw: fp32 [9*Cin, Cout] view of the HWIO gradient, dbias: fp32 [Cout] = column sums of dy -- one call, the bias sums
     from the dy images the weight-gradient kernel stages anyway (asr_conv3x3_bwd_weight_bias)."""
-    h = _h(x_nhwc)
-    _chk(x_nhwc, torch.bfloat16, 'x')
-    _chk(dy_nhwc, torch.bfloat16, 'dy')
-    _chk(dbias, torch.float32, 'dbias')
-    N, H, W, Cin = x_nhwc.shape
-    Cout = dy_nhwc.shape[3]
-    if dbias.numel() != Cout:
-        raise ValueError('conv3x3_bwd_weight_bias: dbias has %d elements, Cout = %d' % (dbias.numel(), Cout))
-    h.check(h.lib.asr_conv3x3_bwd_weight_bias(h.h, _p(x_nhwc), _p(dy_nhwc), N, H, W, Cin, Cout, _p(dw), _p(dbias), _s()),
-            'asr_conv3x3_bwd_weight_bias')
-    return dw, dbias
+    return _conv3xk_bwd_weight_bias(_K3X3, x_nhwc, dy_nhwc, dw, dbias)
 
 
 def im2col3x3(x_nhwc, ldp=None, out=None):
@@ -731,69 +780,6 @@ def relu_bwd(dout, out, mask=None, drop=None):
     return dpre
 
 
-# ---------------------------------------------------------------- 3xK implicit-GEMM convolutions (cnn_zhang 3x5, students 3x4)
-# One implementation per wrapper, parameterised by the filter and the C symbol prefix (csrc/conv3x5.hip is templated on
-# the tap geometry); the public conv3x5_* / conv3x4_* names are bound below with their own signatures.
-_K3X5 = (3, 5, 'conv3x5')
-_K3X4 = (3, 4, 'conv3x4')
-
-
-def _conv3xk_prep_weights(geom, w_hwio):
-    kh, kw, pre = geom
-    fn = pre + '_prep_weights'
-    h = _h(w_hwio)
-    _chk(w_hwio, torch.float32, 'w')
-    fh, fw, Cin, Cout = w_hwio.shape
-    if (fh, fw) != (kh, kw):
-        raise ValueError('%s: filter is %dx%d' % (fn, fh, fw))
-    wf = torch.empty((Cout, kh * kw * Cin), dtype=torch.bfloat16, device=w_hwio.device)
-    wb = torch.empty((Cin, kh * kw * Cout), dtype=torch.bfloat16, device=w_hwio.device)
-    h.check(getattr(h.lib, 'asr_' + fn)(h.h, _p(w_hwio.contiguous()), Cin, Cout, _p(wf), _p(wb), _s()), 'asr_' + fn)
-    return wf, wb
-
-
-def _conv3xk_fwd(geom, x_nhwc, wt_fwd, bias, relu, out, f32_out=None):
-    """f32_out: None for asr_conv3x5_fwd (bf16 output only); asr_conv3x4_fwd takes it as one more argument."""
-    fn = geom[2] + '_fwd'
-    h = _h(x_nhwc)
-    _chk(x_nhwc, torch.bfloat16, 'x')
-    N, H, W, Cin = x_nhwc.shape
-    Cout = wt_fwd.shape[0]
-    out = _out_like(out, (N, H, W, Cout), torch.float32 if f32_out else torch.bfloat16, x_nhwc.device, fn)
-    extra = () if f32_out is None else (int(f32_out),)
-    h.check(getattr(h.lib, 'asr_' + fn)(h.h, _p(x_nhwc), N, H, W, Cin, _p(wt_fwd), _p(bias), Cout, 1 if relu else 0,
-                                        *extra, _p(out), _s()), 'asr_' + fn)
-    return out
-
-
-def _conv3xk_bwd_data(geom, dy_nhwc, wt_bwd):
-    fn = geom[2] + '_bwd_data'
-    h = _h(dy_nhwc)
-    _chk(dy_nhwc, torch.bfloat16, 'dy')
-    N, H, W, Cout = dy_nhwc.shape
-    Cin = wt_bwd.shape[0]
-    dx = torch.empty((N, H, W, Cin), dtype=torch.float32, device=dy_nhwc.device)
-    h.check(getattr(h.lib, 'asr_' + fn)(h.h, _p(dy_nhwc), N, H, W, Cout, _p(wt_bwd), Cin, _p(dx), _s()), 'asr_' + fn)
-    return dx
-
-
-def _conv3xk_bwd_weight_bias(geom, x_nhwc, dy_nhwc, dw, dbias):
-    kh, kw, pre = geom
-    taps, fn = kh * kw, pre + '_bwd_weight_bias'
-    h = _h(x_nhwc)
-    _chk(x_nhwc, torch.bfloat16, 'x')
-    _chk(dy_nhwc, torch.bfloat16, 'dy')
-    N, H, W, Cin = x_nhwc.shape
-    Cout = dy_nhwc.shape[3]
-    if dw.numel() != taps * Cin * Cout or not dw.is_contiguous():
-        raise ValueError('%s: dw must be a contiguous [%d*Cin, Cout] fp32 tensor' % (fn, taps))
-    if dbias is not None and dbias.numel() != Cout:
-        raise ValueError('%s: dbias has %d elements, Cout = %d' % (fn, dbias.numel(), Cout))
-    h.check(getattr(h.lib, 'asr_' + fn)(h.h, _p(x_nhwc), _p(dy_nhwc), N, H, W, Cin, Cout, _p(dw), _p(dbias), _s()),
-            'asr_' + fn)
-    return dw, dbias
-
-
 # ---------------------------------------------------------------- cnn_zhang convolution stack (3x5 convolutions, 3x1 pool)
 def conv3x5_prep_weights(w_hwio):
     """fp32 [3,5,Cin,Cout] -> (wt_fwd bf16 [Cout, 15*Cin], wt_bwd bf16 [Cin, 15*Cout]: the flipped-tap image)."""
@@ -807,14 +793,7 @@ def conv3x5_fwd(x_nhwc, wt_fwd, bias, relu=True, out=None):
 
 def conv3x5_fwd_drop(x_nhwc, wt_fwd, bias, drop, out=None):
     """dropout_apply(conv3x5_fwd(x, ..., relu=True), *drop) in one launch."""
-    h = _h(x_nhwc)
-    _chk(x_nhwc, torch.bfloat16, 'x')
-    N, H, W, Cin = x_nhwc.shape
-    Cout = wt_fwd.shape[0]
-    out = _out_like(out, (N, H, W, Cout), torch.bfloat16, x_nhwc.device, 'conv3x5_fwd_drop')
-    h.check(h.lib.asr_conv3x5_fwd_drop(h.h, _p(x_nhwc), N, H, W, Cin, _p(wt_fwd), _p(bias), Cout, float(drop[0]),
-                                       int(drop[1]), int(drop[2]), _p(out), _s()), 'asr_conv3x5_fwd_drop')
-    return out
+    return _conv3xk_fwd_drop(_K3X5, x_nhwc, wt_fwd, bias, drop, out)
 
 
 def conv3x5_bwd_data(dy_nhwc, wt_bwd):
@@ -824,19 +803,7 @@ def conv3x5_bwd_data(dy_nhwc, wt_bwd):
 
 def conv3x5_bwd_data_relu(dy_nhwc, wt_bwd, act_below, drop=None, dropped=False):
     """relu_bwd(conv3x5_bwd_data(dy, wt_bwd), act_below, drop=drop) in one launch -> bf16 (as conv3x3_bwd_data_relu)."""
-    h = _h(dy_nhwc)
-    _chk(dy_nhwc, torch.bfloat16, 'dy')
-    _chk(act_below, torch.bfloat16, 'act_below')
-    N, H, W, Cout = dy_nhwc.shape
-    Cin = wt_bwd.shape[0]
-    if tuple(act_below.shape) != (N, H, W, Cin):
-        raise ValueError('conv3x5_bwd_data_relu: act_below has shape %s' % (tuple(act_below.shape),))
-    dpre = torch.empty((N, H, W, Cin), dtype=torch.bfloat16, device=dy_nhwc.device)
-    k, sd, off = drop if drop is not None else (1.0, 0, 0)
-    mode = 0 if drop is None else (2 if dropped else 1)
-    h.check(h.lib.asr_conv3x5_bwd_data_relu(h.h, _p(dy_nhwc), N, H, W, Cout, _p(wt_bwd), Cin, _p(act_below), float(k),
-                                            int(sd), int(off), mode, _p(dpre), _s()), 'asr_conv3x5_bwd_data_relu')
-    return dpre
+    return _conv3xk_bwd_data_relu(_K3X5, dy_nhwc, wt_bwd, act_below, drop, dropped)
 
 
 def conv3x5_bwd_weight_bias(x_nhwc, dy_nhwc, dw, dbias=None):
