@@ -437,6 +437,28 @@ int asr_debug_set_lstm_flags(int flags);
  * products on exact-fp32 MFMA where the LDS images fit; 0: the launch-per-step kernels. */
 int asr_debug_set_gru_persistent(int on);
 
+/* Tile groups of the cluster recurrences.  A cluster launch needs every workgroup resident at once, one per CU:
+ * 8 * G * ceil(clusters / 8) of them, G = workgroups per cluster (H/32 or H/64), clusters = tiles * ndir, tiles = B / 16.
+ * A batch that needs more than the chip has runs as several launches over consecutive tile ranges on the caller's
+ * stream (asr_lstm_fwd / asr_lstm_bwd / asr_gru_fwd / asr_gru_bwd do this by themselves; results are bit-identical to one
+ * launch).  This is the plan they use -- pure integer arithmetic, no handle, no GPU: the minimal number of groups
+ * {first_tile[i], ntiles[i]}, consecutive and covering [0, tiles), each with 8 * G * ceil(ntiles * ndir / 8) <= cu_budget.
+ * Returns the number of groups (at most max_groups of them are written; either array may be NULL), 0 when not even one
+ * tile fits (the callers then run the single-CU kernels), ASR_ERR_INVALID_ARG on bad arguments. */
+int asr_cluster_tile_groups(int G, int ndir, int tiles, int cu_budget, int* first_tile, int* ntiles, int max_groups);
+/* Which path the recurrence calls on this handle took since the last reset (host integers bumped at launch time, no
+ * device work, no synchronisation): out6 = {LSTM cluster launches (one per tile group), LSTM single-CU calls, LSTM calls
+ * split into more than one tile group, and the same three for the GRU (its launch-per-step form counts as one
+ * single-CU call)}.  Single-CU calls at a cluster width are the slow path (1.2 - 3.6 x per training step where
+ * measured). */
+int asr_recurrence_path_counts(asr_handle* h, unsigned long long* out6);
+int asr_reset_recurrence_path_counts(asr_handle* h);
+/* TEST ONLY (process-wide): the number of co-resident workgroups a cluster launch may use; 0 (default) = the device's CU
+ * count.  Any other value is clamped to [0, CU count] where it is used, so it can only LOWER the grid of a launch -- the
+ * tests exercise tile groups at B = 80 - 272 with it.  A plain process-wide int, not thread-safe: set it while no
+ * recurrence call is running on any handle. */
+int asr_debug_set_cluster_cu_budget(int n);
+
 /* Debug / measurement: are 16-byte per-lane stores seen whole by 16-byte loads of another CU?  Workgroup 0 stores
  * {i, i, i, i}, i = 1 .. iters, into buf[16 lane .. ] (64 lanes; plain stores, or write-through when write_through != 0);
  * workgroup `peer` (8: the same XCD as workgroup 0, 1: another one) polls them with L1-bypassing loads.

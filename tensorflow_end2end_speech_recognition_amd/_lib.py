@@ -98,6 +98,10 @@ SIGNATURES = {
     'asr_clear_async_errors': (_i, [_vp, _vp]),
     'asr_debug_set_lstm_flags': (_i, [_i]),
     'asr_debug_set_gru_persistent': (_i, [_i]),
+    'asr_cluster_tile_groups': (_i, [_i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _i]),
+    'asr_recurrence_path_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
+    'asr_reset_recurrence_path_counts': (_i, [_vp]),
+    'asr_debug_set_cluster_cu_budget': (_i, [_i]),
     'asr_debug_placement': (_i, [_vp, _vp, _i, _i, _vp]),
     'asr_debug_poison_lds': (_i, [_vp, _vp]),
     'asr_debug_tear_probe': (_i, [_vp, _vp, C.c_uint, _i, _i, _vp, _vp]),

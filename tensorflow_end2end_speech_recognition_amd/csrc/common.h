@@ -26,6 +26,9 @@ struct asr_handle {
   // asr_lstm_bwd_ex: the clip the forward applied to the cell state when a clamped state must pass no gradient
   // (tf.clip_by_value of LSTMCell); 0 = the straight-through clip of LSTMBlockCell.  Set around the kernel dispatch only.
   float bptt_clip;
+  // recurrence launches since the last asr_reset_recurrence_path_counts (plain host counters bumped at launch time):
+  // {cluster launches, single-CU calls, calls split into more than one tile group} of the LSTM, then of the GRU
+  unsigned long long rec_counts[6];
 };
 
 #define ASR_FAIL(h, code, ...)                                  \

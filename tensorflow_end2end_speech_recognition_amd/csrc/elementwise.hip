@@ -10,6 +10,8 @@
 // 3 (round 4): asr_lstm_cell_gemm_prep / _fwd and their _h forms (decoder cell product + cell in one launch).
 // 4 (rounds 5-6, additive): asr_conv3x3_bwd_weight_bias, asr_conv3x3_smallc_bwd_weight_bias (bias gradient out of the
 // weight-gradient kernels), the asr_debug_* hooks; nothing removed or re-typed.
+// still 5 (additive, backward compatible): asr_cluster_tile_groups, asr_recurrence_path_counts,
+// asr_reset_recurrence_path_counts, asr_debug_set_cluster_cu_budget (cluster recurrences in tile groups).
 extern "C" int asr_abi_version(void) { return 5; }
 
 extern "C" int asr_create(asr_handle** out, int device) { return asr_create_ex(out, device, (size_t)192 << 20); }

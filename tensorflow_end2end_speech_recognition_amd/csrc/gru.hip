@@ -513,6 +513,7 @@ extern "C" int asr_gru_fwd(asr_handle* h, int T, int B, int H, int ndir, const f
     ASR_CHECK_LAUNCH(h, "asr_gru_fwd(cluster)");
     return ASR_OK;
   }
+  h->rec_counts[4] += 1;   // single-CU path, persistent or launch-per-step (asr_recurrence_path_counts)
   if (gru_persistent_ok(h, H, ndir, (size_t)3 * 16 * (H + 4) * sizeof(float))) {
     // frames [tmax, T) of the output are beyond every utterance: zero
     if (T > tmax && hipMemsetAsync(hout + (size_t)tmax * B * ndir * H, 0, (size_t)(T - tmax) * B * ndir * H * sizeof(float), st) != hipSuccess)
@@ -572,6 +573,7 @@ extern "C" int asr_gru_bwd(asr_handle* h, int T, int B, int H, int ndir, const f
     ASR_CHECK_LAUNCH(h, "asr_gru_bwd(cluster)");
     return ASR_OK;
   }
+  h->rec_counts[4] += 1;   // single-CU path, persistent or launch-per-step (asr_recurrence_path_counts)
   if (d_h_final) {
     if (hipMemcpyAsync(dh_rec, d_h_final, sn * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
       ASR_FAIL(h, ASR_ERR_HIP, "asr_gru_bwd: copy");

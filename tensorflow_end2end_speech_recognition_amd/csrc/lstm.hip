@@ -905,6 +905,7 @@ extern "C" int asr_lstm_fwd(asr_handle* h, int dtype, int T, int B, int H, int n
     ASR_H_DISPATCH(H, T, (launch_fwd<bf16_t, HH>(T, B, ndir, xproj, wh_packed, peep, seq_len, forget_bias,
                                                  cell_clip, gates, hout, cs, c_final, h_final, st)));
   }
+  h->rec_counts[1] += 1;   // single-CU path (asr_recurrence_path_counts)
   ASR_CHECK_LAUNCH(h, "asr_lstm_fwd");
   return ASR_OK;
 }
@@ -945,6 +946,7 @@ static int lstm_bwd_impl(asr_handle* h, int dtype, int T, int B, int H, int ndir
     ASR_H_DISPATCH(H, T, (launch_bwd<bf16_t, HH>(T, B, ndir, dhout, gates, cs, wh_packed_bwd, peep, seq_len,
                                                  d_c_final, d_h_final, dgates, part, clipz, st)));
   }
+  if (!launched) h->rec_counts[1] += 1;   // single-CU path (asr_recurrence_path_counts)
   ASR_CHECK_LAUNCH(h, "asr_lstm_bwd");
   if (dpeep && !single_tile) {
     const int n = ndir * 7 * H;

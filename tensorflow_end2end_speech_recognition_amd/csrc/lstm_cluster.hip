@@ -108,16 +108,21 @@ __device__ __forceinline__ float dpp_xor1(float v) {   // quad_perm [1,0,3,2]
 // ---------------------------------------------------------------- cluster placement
 // Cluster c = tile * ndir + dir.  Block b of the 1-D grid: XCD slot x = b % 8, q = b / 8,
 // member g = q % G, round = q / G, cluster c = round * 8 + x.  grid = 8 * G * ceil(nclusters / 8).
+// A launch covers the TILE RANGE [tile0, tile0 + ntl) of the batch (one launch: tile0 = 0, ntl = B / 16; a batch that needs
+// more clusters than the chip has CUs for runs as several launches over consecutive ranges, see cluster_tile_plan).  c is
+// LOCAL to the launch (tile - tile0) * ndir + dir: it picks the cluster's exchange slots and placement header -- handed out
+// per launch -- and decides `valid`.  `tile` is the GLOBAL tile: everything in memory (B stays the batch stride of every
+// tensor; seq_len, the final states, the per-tile peephole / bias partials) is indexed with it.
 struct ClusterId { int c, g, d, tile; bool valid; };
 template <int G>
-__device__ __forceinline__ ClusterId cluster_id(int ndir, int ntiles) {
+__device__ __forceinline__ ClusterId cluster_id(int ndir, int tile0, int ntl) {
   const int b = blockIdx.x, x = b & 7, q = b >> 3;
   ClusterId r;
   r.g = q % G;
   r.c = (q / G) * 8 + x;
-  r.valid = r.c < ndir * ntiles;
+  r.valid = r.c < ndir * ntl;
   r.d = r.c % ndir;
-  r.tile = r.c / ndir;
+  r.tile = tile0 + r.c / ndir;
   return r;
 }
 static inline unsigned cluster_grid(int G, int nclusters) { return 8u * G * ((nclusters + 7) / 8); }
@@ -187,7 +192,7 @@ __global__ __launch_bounds__(HSU * 8, 1) void lstm_fwd_cluster8_kernel(
     const float* __restrict__ peep, const int32_t* __restrict__ seq_len, float forget_bias,
     float cell_clip, cbf16x4_t* __restrict__ gates, bf16_t* __restrict__ hout, float* __restrict__ cs,
     float* __restrict__ c_final, float* __restrict__ h_final, u64* __restrict__ xch,
-    unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords) {
+    unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords, int tile0, int ntl) {
   zero_next_area(znext, zwords);
   constexpr int G = H / HSU;
   constexpr int CTW = HSU * 8;                             // threads per workgroup: a wave owns 8 units
@@ -203,7 +208,7 @@ __global__ __launch_bounds__(HSU * 8, 1) void lstm_fwd_cluster8_kernel(
   // the placement is verified below and the exchange falls back to write-through stores)
   // EARLY: k-chunk index modulo KS (a mask where KS is a power of two; H = 320 has 10 chunks: x < 2 KS there)
   auto krot = [](int x) -> int { return ((KS & (KS - 1)) == 0) ? (x & (KS - 1)) : (x >= KS ? x - KS : x); };
-  const ClusterId cid = cluster_id<G>(ndir, B_ / 16);
+  const ClusterId cid = cluster_id<G>(ndir, tile0, ntl);
   if (!cid.valid) return;
   const int g = cid.g, d = cid.d, b0 = cid.tile * 16;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -672,7 +677,7 @@ __global__ __launch_bounds__(HSU * 8, 1) void lstm_bwd_cluster8_kernel(
     const float* __restrict__ cs, const bf16_t* __restrict__ whpb, const float* __restrict__ peep,
     const int32_t* __restrict__ seq_len, const float* __restrict__ d_c_final,
     const float* __restrict__ d_h_final, cbf16x4_t* __restrict__ dgates, float* __restrict__ dpeep_part,
-    u64* __restrict__ xch, unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords, float clipz) {
+    u64* __restrict__ xch, unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords, float clipz, int tile0, int ntl) {
   zero_next_area(znext, zwords);
   constexpr int PINM = PIN >= 0 ? PIN : ((HSU == 32 && H <= 320) ? (15 | 64) : 0);   // (H = 320 on eight waves: 1089 -> 1216 us with pins)
   constexpr int G = H / HSU;
@@ -687,7 +692,7 @@ __global__ __launch_bounds__(HSU * 8, 1) void lstm_bwd_cluster8_kernel(
   // parity so that ONE barrier per step orders writers and readers
   constexpr int DGB = 16 * LDG * 2;                        // bytes per buffer
 
-  const ClusterId cid = cluster_id<G>(ndir, B_ / 16);
+  const ClusterId cid = cluster_id<G>(ndir, tile0, ntl);
   if (!cid.valid) return;
   const int g = cid.g, d = cid.d, b0 = cid.tile * 16;
   const int lane = threadIdx.x & 63;
@@ -1191,7 +1196,7 @@ __global__ __launch_bounds__(HSU * 8, 1) void lstm_fwd_cluster8_f32_kernel(
     const float* __restrict__ peep, const int32_t* __restrict__ seq_len, float forget_bias,
     float cell_clip, f32x4_t* __restrict__ gates, float* __restrict__ hout, float* __restrict__ cs,
     float* __restrict__ c_final, float* __restrict__ h_final, u64* __restrict__ xch,
-    unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords) {
+    unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords, int tile0, int ntl) {
   zero_next_area(znext, zwords);
   constexpr int G = H / HSU;
   constexpr int CTW = HSU * 8;
@@ -1204,7 +1209,7 @@ __global__ __launch_bounds__(HSU * 8, 1) void lstm_fwd_cluster8_f32_kernel(
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* hs = reinterpret_cast<float*>(smem);              // [2][16][LDH]
 
-  const ClusterId cid = cluster_id<G>(ndir, B_ / 16);
+  const ClusterId cid = cluster_id<G>(ndir, tile0, ntl);
   if (!cid.valid) return;
   const int g = cid.g, d = cid.d, b0 = cid.tile * 16;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1488,7 +1493,7 @@ __global__ __launch_bounds__(HSU * 8, 1) void lstm_fwd_cluster_f32s_kernel(
     const float* __restrict__ peep, const int32_t* __restrict__ seq_len, float forget_bias,
     float cell_clip, f32x4_t* __restrict__ gates, float* __restrict__ hout, float* __restrict__ cs,
     float* __restrict__ c_final, float* __restrict__ h_final, u64* __restrict__ xch,
-    unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords) {
+    unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords, int tile0, int ntl) {
   zero_next_area(znext, zwords);
   constexpr int G = H / HSU;
   constexpr int CTW = HSU * 8;
@@ -1503,7 +1508,7 @@ __global__ __launch_bounds__(HSU * 8, 1) void lstm_fwd_cluster_f32s_kernel(
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned short* hs = reinterpret_cast<unsigned short*>(smem);   // [2 parity][3 terms][16][LDH]
 
-  const ClusterId cid = cluster_id<G>(ndir, B_ / 16);
+  const ClusterId cid = cluster_id<G>(ndir, tile0, ntl);
   if (!cid.valid) return;
   const int g = cid.g, d = cid.d, b0 = cid.tile * 16;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1767,7 +1772,7 @@ __global__ __launch_bounds__(256, 1) void gru_fwd_cluster_kernel(
     int T_, int B_, int ndir, const float* __restrict__ xg, const float* __restrict__ xc, const float* __restrict__ wgh,
     const float* __restrict__ wch, const int32_t* __restrict__ seq_len, float* __restrict__ r_out, float* __restrict__ u_out,
     float* __restrict__ c_out, float* __restrict__ rh_out, float* __restrict__ hout, float* __restrict__ h_final,
-    u64* __restrict__ xch, unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords) {
+    u64* __restrict__ xch, unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords, int tile0, int ntl) {
   zero_next_area(znext, zwords);
   constexpr int HSU = 32, G = H / HSU;
   constexpr int KS = H / 32;
@@ -1776,7 +1781,7 @@ __global__ __launch_bounds__(256, 1) void gru_fwd_cluster_kernel(
   constexpr int SLICE = 16 * HSU;                           // granules one CU publishes per exchange and step
   extern __shared__ __attribute__((aligned(16))) char smem[];   // [h parity 0][h parity 1][r * h], three term images each
 
-  const ClusterId cid = cluster_id<G>(ndir, B_ / 16);
+  const ClusterId cid = cluster_id<G>(ndir, tile0, ntl);
   if (!cid.valid) return;
   const int g = cid.g, d = cid.d, b0 = cid.tile * 16;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1997,7 +2002,7 @@ __global__ __launch_bounds__(256, 1) void gru_bwd_cluster_kernel(
     const float* __restrict__ hout, const float* __restrict__ r_in, const float* __restrict__ u_in,
     const float* __restrict__ c_in, const float* __restrict__ wghT, const float* __restrict__ wchT,
     const int32_t* __restrict__ seq_len, float* __restrict__ dgate, float* __restrict__ dcand, u64* __restrict__ xch,
-    unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords) {
+    unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords, int tile0, int ntl) {
   zero_next_area(znext, zwords);
   constexpr int HSU = 32, G = H / HSU;
   constexpr int KS = H / 32;
@@ -2007,7 +2012,7 @@ __global__ __launch_bounds__(256, 1) void gru_bwd_cluster_kernel(
   constexpr int SLICE = 16 * HSU;
   extern __shared__ __attribute__((aligned(16))) char smem[];   // [dc_pre P0][dc_pre P1][du_pre P0][du_pre P1][dr_pre]
 
-  const ClusterId cid = cluster_id<G>(ndir, B_ / 16);
+  const ClusterId cid = cluster_id<G>(ndir, tile0, ntl);
   if (!cid.valid) return;
   const int g = cid.g, d = cid.d, b0 = cid.tile * 16;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -2221,7 +2226,7 @@ __global__ __launch_bounds__(CT8, 1) void lstm_bwd_cluster8_f32_kernel(
     const float* __restrict__ cs, const float* __restrict__ whpb, const float* __restrict__ peep,
     const int32_t* __restrict__ seq_len, const float* __restrict__ d_c_final,
     const float* __restrict__ d_h_final, f32x4_t* __restrict__ dgates, float* __restrict__ dpeep_part,
-    u64* __restrict__ xch, unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords, float clipz) {
+    u64* __restrict__ xch, unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords, float clipz, int tile0, int ntl) {
   static_assert(H / HS == 2, "one foreign tile per hh = 1 wave: two CUs per direction");
   zero_next_area(znext, zwords);
   constexpr int G = H / HS;
@@ -2232,7 +2237,7 @@ __global__ __launch_bounds__(CT8, 1) void lstm_bwd_cluster8_f32_kernel(
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int DGB = 16 * LDG * 4;                        // bytes per dG image
 
-  const ClusterId cid = cluster_id<G>(ndir, B_ / 16);
+  const ClusterId cid = cluster_id<G>(ndir, tile0, ntl);
   if (!cid.valid) return;
   const int g = cid.g, d = cid.d, b0 = cid.tile * 16;
   const int lane = threadIdx.x & 63;
@@ -2474,7 +2479,7 @@ __global__ __launch_bounds__(HSU * 8, 1) void lstm_bwd_cluster_f32_kernel(
     const float* __restrict__ cs, const float* __restrict__ whpb, const float* __restrict__ peep,
     const int32_t* __restrict__ seq_len, const float* __restrict__ d_c_final,
     const float* __restrict__ d_h_final, f32x4_t* __restrict__ dgates, float* __restrict__ dpeep_part,
-    u64* __restrict__ xch, unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords, float clipz) {
+    u64* __restrict__ xch, unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords, float clipz, int tile0, int ntl) {
   zero_next_area(znext, zwords);
   constexpr int G = H / HSU;
   static_assert(G % 2 == 0 && G >= 2 && G <= XHDR, "even number of CUs per cluster");
@@ -2487,7 +2492,7 @@ __global__ __launch_bounds__(HSU * 8, 1) void lstm_bwd_cluster_f32_kernel(
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int DGB = 16 * LDG * 4;                        // bytes per dG image
 
-  const ClusterId cid = cluster_id<G>(ndir, B_ / 16);
+  const ClusterId cid = cluster_id<G>(ndir, tile0, ntl);
   if (!cid.valid) return;
   const int g = cid.g, d = cid.d, b0 = cid.tile * 16;
   const int lane = threadIdx.x & 63;
@@ -2770,7 +2775,7 @@ __global__ __launch_bounds__(HSU * 8, 1) void lstm_bwd_cluster_f32s_kernel(
     const float* __restrict__ cs, const float* __restrict__ whpb, const float* __restrict__ peep,
     const int32_t* __restrict__ seq_len, const float* __restrict__ d_c_final,
     const float* __restrict__ d_h_final, f32x4_t* __restrict__ dgates, float* __restrict__ dpeep_part,
-    u64* __restrict__ xch, unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords, float clipz) {
+    u64* __restrict__ xch, unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords, float clipz, int tile0, int ntl) {
   zero_next_area(znext, zwords);
   constexpr int G = H / HSU;
   static_assert(G % 2 == 0 && G >= 2 && G <= XHDR, "even number of CUs per cluster");
@@ -2785,7 +2790,7 @@ __global__ __launch_bounds__(HSU * 8, 1) void lstm_bwd_cluster_f32s_kernel(
   constexpr int PLB = 16 * LDG * 2;                        // bytes of one term image
   constexpr int DGB = 3 * PLB;                             // bytes per dG image (three bf16 terms)
 
-  const ClusterId cid = cluster_id<G>(ndir, B_ / 16);
+  const ClusterId cid = cluster_id<G>(ndir, tile0, ntl);
   if (!cid.valid) return;
   const int g = cid.g, d = cid.d, b0 = cid.tile * 16;
   const int lane = threadIdx.x & 63;
@@ -3143,6 +3148,81 @@ static XchAreas xch_take(asr_handle* h, char* base, size_t need, hipStream_t st)
   return x;
 }
 
+// ---------------------------------------------------------------- tile groups
+// Every member of a launch must be resident at once (one workgroup per CU), so a launch holds at most
+// 8 * floor(budget / (8 G)) clusters.  A batch with more (tile, direction) pairs runs as consecutive launches over tile
+// ranges: clusters never talk to each other, so the ranges are independent and each launch is the same kernel with a
+// first tile.  The plan is the minimal number of groups: full groups of `per` tiles and one partial group at the end.
+struct TilePlan { int per, n; };   // tiles per full group, number of groups (0: not even one tile fits)
+static TilePlan cluster_tile_plan(int G, int ndir, int tiles, int budget) {
+  TilePlan p = {0, 0};
+  if (G < 1 || ndir < 1 || ndir > 8 || tiles < 1 || budget < 1) return p;
+  const int per = (budget / (8 * G)) * 8 / ndir;          // largest m with cluster_grid(G, m * ndir) <= budget
+  if (per < 1) return p;
+  p.per = per < tiles ? per : tiles;
+  p.n = (tiles + p.per - 1) / p.per;
+  return p;
+}
+extern "C" int asr_cluster_tile_groups(int G, int ndir, int tiles, int cu_budget, int* first_tile, int* ntiles,
+                                       int max_groups) {
+  if (G < 1 || (ndir != 1 && ndir != 2) || tiles < 1 || cu_budget < 1 || max_groups < 0) return ASR_ERR_INVALID_ARG;
+  const TilePlan p = cluster_tile_plan(G, ndir, tiles, cu_budget);
+  for (int i = 0; i < p.n && i < max_groups; ++i) {
+    if (first_tile) first_tile[i] = i * p.per;
+    if (ntiles) ntiles[i] = (i + 1 < p.n) ? p.per : tiles - i * p.per;
+  }
+  return p.n;
+}
+// TEST ONLY: co-resident workgroups a cluster launch may use; 0 = the device's CU count.  Clamped to the CU count where it
+// is used -- a grid larger than the chip would leave members spinning on peers that are not resident.  Process-wide and
+// NOT thread-safe (a plain int every handle reads at launch time, like g_dflags): set it while no recurrence call runs.
+static int g_cu_budget = 0;
+extern "C" int asr_debug_set_cluster_cu_budget(int n) { g_cu_budget = n; return 0; }
+static int cluster_cu_budget(const asr_handle* h) {
+  return (g_cu_budget <= 0 || g_cu_budget > h->num_cu) ? h->num_cu : g_cu_budget;
+}
+// The plan of one launcher call: `grouped` false = exactly one launch or nothing (the shapes that fit keep their form and
+// their single launch), true = any number of groups.  cl_bytes = exchange bytes per cluster: every group's slots must fit
+// in one exchange area, so a grouped plan also shrinks its groups to what the area holds (a shape whose one launch fits the
+// CUs but not the area is split too).
+static TilePlan cluster_launch_plan(const asr_handle* h, int G, int ndir, int B, size_t cl_bytes, bool grouped) {
+  const int tiles = B / 16;
+  TilePlan p = cluster_tile_plan(G, ndir, tiles, cluster_cu_budget(h));
+  const size_t area_tiles = XCH_HALF / ((size_t)ndir * cl_bytes);   // tiles whose clusters one area has slots for
+  if (p.n && (size_t)p.per > area_tiles) {
+    p.per = (int)area_tiles;
+    p.n = p.per ? (tiles + p.per - 1) / p.per : 0;
+  }
+  if (p.n != 1 && !grouped) p.n = 0;
+  return p;
+}
+// host counters of the path a recurrence call took (asr_recurrence_path_counts); kind 0 = LSTM, 1 = GRU
+static void count_cluster_launches(asr_handle* h, int kind, int groups) {
+  h->rec_counts[3 * kind + 0] += (unsigned long long)groups;
+  if (groups > 1) h->rec_counts[3 * kind + 2] += 1;
+}
+// Runs launch(xa, ncl, t0, nt) once per tile group of the plan on `st`: an exchange area per launch (xch_take: each launch
+// zeroes what its predecessor dirtied), ncl = clusters of the group, [t0, t0 + nt) its tiles.  kind as above.
+template <typename F>
+static void run_tile_groups(asr_handle* h, char* base, const TilePlan& plan, int B, int ndir, size_t cl_bytes,
+                            hipStream_t st, int kind, F launch) {
+  for (int t0 = 0; t0 < B / 16; t0 += plan.per) {
+    const int nt = min(plan.per, B / 16 - t0), ncl = nt * ndir;
+    launch(xch_take(h, base, ncl * cl_bytes, st), ncl, t0, nt);
+  }
+  count_cluster_launches(h, kind, plan.n);
+}
+extern "C" int asr_recurrence_path_counts(asr_handle* h, unsigned long long* out6) {
+  if (!h || !out6) return ASR_ERR_INVALID_ARG;
+  for (int i = 0; i < 6; ++i) out6[i] = h->rec_counts[i];
+  return ASR_OK;
+}
+extern "C" int asr_reset_recurrence_path_counts(asr_handle* h) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  for (int i = 0; i < 6; ++i) h->rec_counts[i] = 0;
+  return ASR_OK;
+}
+
 // ASR_LSTM_FWD_HS=32: forward recurrence on clusters of H/32 CUs with four waves each (one per SIMD) instead of H/64
 // CUs with eight (A/B switch)
 // Units per CU of the H = 256 / 512 clusters: 32 (default since round 3: H/32 CUs with four waves each, one per SIMD) or
@@ -3177,16 +3257,14 @@ static bool bwd_xp_enabled(int hsu) {
 template <int H, int HSU = 64>
 static bool cluster_fwd_launch(asr_handle* h, int T, int B, int ndir, const float* xproj, const void* whp,
                                const float* peep, const int32_t* seq_len, float fb, float clip, void* gates,
-                               void* hout, float* cs, float* cf, float* hf, hipStream_t st) {
+                               void* hout, float* cs, float* cf, float* hf, hipStream_t st, bool grouped) {
   constexpr int G = H / HSU;
   static_assert(G <= XHDR, "placement header too small");
-  const int ncl = (B / 16) * ndir;
-  const size_t need = (size_t)ncl * (XHDR + 2 * G * 16 * (HSU / 2)) * sizeof(u64);
-  if ((size_t)T * B * ndir * H >= (1ull << 31) || h->scratch_bytes < XCH_BYTES || need > XCH_HALF ||
-      (int)cluster_grid(G, ncl) > h->num_cu)   // every member must be resident at once: 1 workgroup per CU
-    return false;
+  constexpr size_t cl_bytes = (XHDR + 2 * G * 16 * (HSU / 2)) * sizeof(u64);
+  if ((size_t)T * B * ndir * H >= (1ull << 31) || h->scratch_bytes < XCH_BYTES) return false;
+  const TilePlan plan = cluster_launch_plan(h, G, ndir, B, cl_bytes, grouped);   // every member of a launch must be resident at once
+  if (!plan.n) return false;
   char* base = (char*)h->scratch + (h->scratch_bytes - XCH_BYTES);
-  const XchAreas xa = xch_take(h, base, need, st);
   // EARLY (own-slice k-chunks multiplied under the L2 hop): measured at H = 256 (round 2, cfg B): 970 -> 938 us per
   // launch, at H = 320: 1069 -> 969; default at both.  ASR_LSTM_DFLAGS bit 5 (32) inverts the default for A/B measurements.
   const bool early = (H == 256 || H == 320 || HSU == 32) != ((dbg_flags() & 32) != 0);   // H = 320: 1069 -> 969 us per launch
@@ -3234,9 +3312,11 @@ static bool cluster_fwd_launch(asr_handle* h, int T, int B, int ndir, const floa
   // (padding the LDS request past half a CU so that two 4-wave members can never share one was measured: no
   // difference, 866.7 vs 867.6 us -- the dispatcher spreads the members over the CUs by itself)
   const size_t lds = (size_t)2 * 16 * (H + 8) * 2;
-  hipLaunchKernelGGL(k, dim3(cluster_grid(G, ncl)), dim3(HSU * 8), lds, st, T, B, ndir,
-                     (const f32x4_t*)xproj, (const bf16_t*)whp, peep, seq_len, fb, clip, (cbf16x4_t*)gates,
-                     (bf16_t*)hout, cs, cf, hf, xa.area, (unsigned*)base, kernel_flags(), xa.znext, xa.zwords);
+  run_tile_groups(h, base, plan, B, ndir, cl_bytes, st, 0, [&](const XchAreas& xa, int ncl, int t0, int nt) {
+    hipLaunchKernelGGL(k, dim3(cluster_grid(G, ncl)), dim3(HSU * 8), lds, st, T, B, ndir,
+                       (const f32x4_t*)xproj, (const bf16_t*)whp, peep, seq_len, fb, clip, (cbf16x4_t*)gates,
+                       (bf16_t*)hout, cs, cf, hf, xa.area, (unsigned*)base, kernel_flags(), xa.znext, xa.zwords, t0, nt);
+  });
   return true;
 }
 
@@ -3246,31 +3326,33 @@ bool asr_cluster_fwd_try(asr_handle* h, int T, int B, int H, int ndir, const flo
                          hipStream_t st) {
   if (!cluster_enabled() || (H != 256 && H != 512 && !(H == 320 && cluster_320_enabled()))) return false;
   cdbg_setup();
-  if (H == 320) return cluster_fwd_launch<320>(h, T, B, ndir, xproj, whp, peep, seq_len, fb, clip, gates, hout, cs, cf, hf, st);
-  if (fwd_units_per_cu() == 32) {
-    const bool ok = H == 512
-        ? cluster_fwd_launch<512, 32>(h, T, B, ndir, xproj, whp, peep, seq_len, fb, clip, gates, hout, cs, cf, hf, st)
-        : cluster_fwd_launch<256, 32>(h, T, B, ndir, xproj, whp, peep, seq_len, fb, clip, gates, hout, cs, cf, hf, st);
-    if (ok) return true;
-  }
-  return H == 512 ? cluster_fwd_launch<512>(h, T, B, ndir, xproj, whp, peep, seq_len, fb, clip, gates, hout, cs, cf, hf, st)
-                  : cluster_fwd_launch<256>(h, T, B, ndir, xproj, whp, peep, seq_len, fb, clip, gates, hout, cs, cf, hf, st);
+  // first every form as ONE launch, in the order of preference; tile groups only when no form fits in one launch
+  auto attempt = [&](bool grouped) -> bool {
+    if (H == 320) return cluster_fwd_launch<320>(h, T, B, ndir, xproj, whp, peep, seq_len, fb, clip, gates, hout, cs, cf, hf, st, grouped);
+    if (fwd_units_per_cu() == 32) {
+      const bool ok = H == 512
+          ? cluster_fwd_launch<512, 32>(h, T, B, ndir, xproj, whp, peep, seq_len, fb, clip, gates, hout, cs, cf, hf, st, grouped)
+          : cluster_fwd_launch<256, 32>(h, T, B, ndir, xproj, whp, peep, seq_len, fb, clip, gates, hout, cs, cf, hf, st, grouped);
+      if (ok) return true;
+    }
+    return H == 512 ? cluster_fwd_launch<512>(h, T, B, ndir, xproj, whp, peep, seq_len, fb, clip, gates, hout, cs, cf, hf, st, grouped)
+                    : cluster_fwd_launch<256>(h, T, B, ndir, xproj, whp, peep, seq_len, fb, clip, gates, hout, cs, cf, hf, st, grouped);
+  };
+  return attempt(false) || attempt(true);
 }
 
 template <int H, int HSU = 64>
 static bool cluster_bwd_launch(asr_handle* h, int T, int B, int ndir, const float* dhout, const void* gates,
                                const float* cs, const void* whpb, const float* peep, const int32_t* seq_len,
                                const float* dcf, const float* dhf, void* dgates, float* dpeep_part,
-                               hipStream_t st) {
+                               hipStream_t st, bool grouped) {
   constexpr int G = H / HSU;
   static_assert(G <= XHDR, "placement header too small");
-  const int ncl = (B / 16) * ndir;
-  const size_t need = (size_t)ncl * (XHDR + (size_t)2 * G * G * (HSU / 16) * 64 * 2) * sizeof(u64);
-  if ((size_t)T * B * ndir * H >= (1ull << 31) || h->scratch_bytes < XCH_BYTES || need > XCH_HALF ||
-      (int)cluster_grid(G, ncl) > h->num_cu)   // every member must be resident at once: 1 workgroup per CU
-    return false;
+  constexpr size_t cl_bytes = (XHDR + (size_t)2 * G * G * (HSU / 16) * 64 * 2) * sizeof(u64);
+  if ((size_t)T * B * ndir * H >= (1ull << 31) || h->scratch_bytes < XCH_BYTES) return false;
+  const TilePlan plan = cluster_launch_plan(h, G, ndir, B, cl_bytes, grouped);   // every member of a launch must be resident at once
+  if (!plan.n) return false;
   char* base = (char*)h->scratch + (h->scratch_bytes - XCH_BYTES);
-  const XchAreas xa = xch_take(h, base, need, st);
   // two dG images; the H = 512 form adds the own-tile hand-over buffer behind them
   const size_t lds = (size_t)2 * 16 * (4 * HSU + 8) * 2 + ((G == 8 && HSU == 64) ? 2 * 4 * 64 * 8 : 0);
   // reduce-scatter slots in the consumer-major paired layout (default) or one 16-byte slot per (source, tile) (ASR_LSTM_XP=0)
@@ -3302,10 +3384,12 @@ static bool cluster_bwd_launch(asr_handle* h, int T, int B, int ndir, const floa
     }
   }
 #endif
-  hipLaunchKernelGGL(k, dim3(cluster_grid(G, ncl)), dim3(HSU * 8), lds, st, T, B, ndir, dhout,
-                     (const cbf16x4_t*)gates, cs, (const bf16_t*)whpb, peep, seq_len, dcf, dhf,
-                     (cbf16x4_t*)dgates, dpeep_part, xa.area, (unsigned*)base, kernel_flags(), xa.znext, xa.zwords,
-                     h->bptt_clip);
+  run_tile_groups(h, base, plan, B, ndir, cl_bytes, st, 0, [&](const XchAreas& xa, int ncl, int t0, int nt) {
+    hipLaunchKernelGGL(k, dim3(cluster_grid(G, ncl)), dim3(HSU * 8), lds, st, T, B, ndir, dhout,
+                       (const cbf16x4_t*)gates, cs, (const bf16_t*)whpb, peep, seq_len, dcf, dhf,
+                       (cbf16x4_t*)dgates, dpeep_part, xa.area, (unsigned*)base, kernel_flags(), xa.znext, xa.zwords,
+                       h->bptt_clip, t0, nt);
+  });
   return true;
 }
 
@@ -3315,17 +3399,21 @@ bool asr_cluster_bwd_try(asr_handle* h, int T, int B, int H, int ndir, const flo
                          float* dpeep_part, hipStream_t st) {
   if (!cluster_enabled() || (H != 256 && H != 512 && !(H == 320 && cluster_320_enabled()))) return false;
   cdbg_setup();
-  if (H == 320)
-    return cluster_bwd_launch<320>(h, T, B, ndir, dhout, gates, cs, whpb, peep, seq_len, dcf, dhf, dgates, dpeep_part, st);
-  if (bwd_units_per_cu() == 32) {
-    // (falls through to the 64-unit form when the exchange area of the wider clusters does not fit)
-    const bool ok = H == 512
-        ? cluster_bwd_launch<512, 32>(h, T, B, ndir, dhout, gates, cs, whpb, peep, seq_len, dcf, dhf, dgates, dpeep_part, st)
-        : cluster_bwd_launch<256, 32>(h, T, B, ndir, dhout, gates, cs, whpb, peep, seq_len, dcf, dhf, dgates, dpeep_part, st);
-    if (ok) return true;
-  }
-  return H == 512 ? cluster_bwd_launch<512>(h, T, B, ndir, dhout, gates, cs, whpb, peep, seq_len, dcf, dhf, dgates, dpeep_part, st)
-                  : cluster_bwd_launch<256>(h, T, B, ndir, dhout, gates, cs, whpb, peep, seq_len, dcf, dhf, dgates, dpeep_part, st);
+  // first every form as ONE launch, in the order of preference; tile groups only when no form fits in one launch
+  auto attempt = [&](bool grouped) -> bool {
+    if (H == 320)
+      return cluster_bwd_launch<320>(h, T, B, ndir, dhout, gates, cs, whpb, peep, seq_len, dcf, dhf, dgates, dpeep_part, st, grouped);
+    if (bwd_units_per_cu() == 32) {
+      // (falls through to the 64-unit form when the exchange area of the wider clusters does not fit)
+      const bool ok = H == 512
+          ? cluster_bwd_launch<512, 32>(h, T, B, ndir, dhout, gates, cs, whpb, peep, seq_len, dcf, dhf, dgates, dpeep_part, st, grouped)
+          : cluster_bwd_launch<256, 32>(h, T, B, ndir, dhout, gates, cs, whpb, peep, seq_len, dcf, dhf, dgates, dpeep_part, st, grouped);
+      if (ok) return true;
+    }
+    return H == 512 ? cluster_bwd_launch<512>(h, T, B, ndir, dhout, gates, cs, whpb, peep, seq_len, dcf, dhf, dgates, dpeep_part, st, grouped)
+                    : cluster_bwd_launch<256>(h, T, B, ndir, dhout, gates, cs, whpb, peep, seq_len, dcf, dhf, dgates, dpeep_part, st, grouped);
+  };
+  return attempt(false) || attempt(true);
 }
 
 // fp32 operands: H = 128 on two CUs per (direction, tile).  ASR_LSTM_CLUSTER_F32=0 keeps the single-CU kernels (A/B).
@@ -3344,16 +3432,14 @@ static bool cluster_f32_split_enabled() {
 template <int HH, int HSU>
 static bool cluster_fwd_f32_launch(asr_handle* h, int T, int B, int ndir, const float* xproj, const void* whp,
                                    const float* peep, const int32_t* seq_len, float fb, float clip, void* gates,
-                                   void* hout, float* cs, float* cf, float* hf, hipStream_t st) {
+                                   void* hout, float* cs, float* cf, float* hf, hipStream_t st, bool grouped) {
   constexpr int G = HH / HSU;
   static_assert(G <= XHDR, "placement header too small");
-  const int ncl = (B / 16) * ndir;
-  const size_t need = (size_t)ncl * (XHDR + 2 * G * 16 * HSU) * sizeof(u64);
-  if ((size_t)T * B * ndir * HH >= (1ull << 31) || h->scratch_bytes < XCH_BYTES || need > XCH_HALF ||
-      (int)cluster_grid(G, ncl) > h->num_cu)
-    return false;
+  constexpr size_t cl_bytes = (XHDR + 2 * G * 16 * HSU) * sizeof(u64);
+  if ((size_t)T * B * ndir * HH >= (1ull << 31) || h->scratch_bytes < XCH_BYTES) return false;
+  const TilePlan plan = cluster_launch_plan(h, G, ndir, B, cl_bytes, grouped);
+  if (!plan.n) return false;
   char* base = (char*)h->scratch + (h->scratch_bytes - XCH_BYTES);
-  const XchAreas xa = xch_take(h, base, need, st);
   // EARLY own-slice products by default, except H = 512 where their extra live accumulators push the 256 weight
   // registers into scratch (measured 5.93 vs 5.36 ms per 778-step launch); ASR_LSTM_DFLAGS bit 5 inverts (A/B)
   const bool early = ((dbg_flags() & 32) == 0) != (HH >= 512);
@@ -3361,9 +3447,11 @@ static bool cluster_fwd_f32_launch(asr_handle* h, int T, int B, int ndir, const 
     if (cluster_f32_split_enabled() && T < 65536) {   // round 5: the same recurrence on the bf16 matrix pipe (three-term split; 16-bit step tags)
       auto ks = early ? lstm_fwd_cluster_f32s_kernel<HH, true, HSU> : lstm_fwd_cluster_f32s_kernel<HH, false, HSU>;
       const size_t lds_s = (size_t)2 * 3 * 16 * (HH + 8) * 2;
-      hipLaunchKernelGGL(ks, dim3(cluster_grid(G, ncl)), dim3(HSU * 8), lds_s, st, T, B, ndir, (const f32x4_t*)xproj,
-                         (const float*)whp, peep, seq_len, fb, clip, (f32x4_t*)gates, (float*)hout, cs, cf, hf, xa.area,
-                         (unsigned*)base, kernel_flags(), xa.znext, xa.zwords);
+      run_tile_groups(h, base, plan, B, ndir, cl_bytes, st, 0, [&](const XchAreas& xa, int ncl, int t0, int nt) {
+        hipLaunchKernelGGL(ks, dim3(cluster_grid(G, ncl)), dim3(HSU * 8), lds_s, st, T, B, ndir, (const f32x4_t*)xproj,
+                           (const float*)whp, peep, seq_len, fb, clip, (f32x4_t*)gates, (float*)hout, cs, cf, hf, xa.area,
+                           (unsigned*)base, kernel_flags(), xa.znext, xa.zwords, t0, nt);
+      });
       return true;
     }
   }
@@ -3371,9 +3459,11 @@ static bool cluster_fwd_f32_launch(asr_handle* h, int T, int B, int ndir, const 
   const size_t lds = (size_t)2 * 16 * (HH + 4) * 4;
   if (lds > ((size_t)64 << 10))
     (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(k, dim3(cluster_grid(G, ncl)), dim3(HSU * 8), lds, st, T, B, ndir, (const f32x4_t*)xproj,
-                     (const float*)whp, peep, seq_len, fb, clip, (f32x4_t*)gates, (float*)hout, cs, cf, hf, xa.area,
-                     (unsigned*)base, kernel_flags(), xa.znext, xa.zwords);
+  run_tile_groups(h, base, plan, B, ndir, cl_bytes, st, 0, [&](const XchAreas& xa, int ncl, int t0, int nt) {
+    hipLaunchKernelGGL(k, dim3(cluster_grid(G, ncl)), dim3(HSU * 8), lds, st, T, B, ndir, (const f32x4_t*)xproj,
+                       (const float*)whp, peep, seq_len, fb, clip, (f32x4_t*)gates, (float*)hout, cs, cf, hf, xa.area,
+                       (unsigned*)base, kernel_flags(), xa.znext, xa.zwords, t0, nt);
+  });
   return true;
 }
 
@@ -3384,11 +3474,11 @@ static bool cluster_f32_wide_enabled() {
   static const bool on = [] { const char* e = getenv("ASR_LSTM_CLUSTER_F32_WIDE"); return !(e && e[0] == '0'); }();
   return on;
 }
-#define ASR_F32_ARGS_F h, T, B, ndir, xproj, whp, peep, seq_len, fb, clip, gates, hout, cs, cf, hf, st
-bool asr_cluster_fwd_f32_try(asr_handle* h, int T, int B, int H, int ndir, const float* xproj,
+#define ASR_F32_ARGS_F h, T, B, ndir, xproj, whp, peep, seq_len, fb, clip, gates, hout, cs, cf, hf, st, grouped
+static bool cluster_fwd_f32_attempt(asr_handle* h, int T, int B, int H, int ndir, const float* xproj,
                              const void* whp, const float* peep, const int32_t* seq_len, float fb,
                              float clip, void* gates, void* hout, float* cs, float* cf, float* hf,
-                             hipStream_t st) {
+                             hipStream_t st, bool grouped) {
   if (!cluster_f32_enabled()) return false;
   if (fwd_units_per_cu() == 32) {
     if (H == 128) return cluster_fwd_f32_launch<128, 32>(ASR_F32_ARGS_F);
@@ -3401,32 +3491,44 @@ bool asr_cluster_fwd_f32_try(asr_handle* h, int T, int B, int H, int ndir, const
   return H == 128 ? cluster_fwd_f32_launch<128, 64>(ASR_F32_ARGS_F) : false;
 }
 #undef ASR_F32_ARGS_F
+bool asr_cluster_fwd_f32_try(asr_handle* h, int T, int B, int H, int ndir, const float* xproj,
+                             const void* whp, const float* peep, const int32_t* seq_len, float fb,
+                             float clip, void* gates, void* hout, float* cs, float* cf, float* hf,
+                             hipStream_t st) {
+  // one launch where it fits, tile groups otherwise
+  return cluster_fwd_f32_attempt(h, T, B, H, ndir, xproj, whp, peep, seq_len, fb, clip, gates, hout, cs, cf, hf, st, false) ||
+         cluster_fwd_f32_attempt(h, T, B, H, ndir, xproj, whp, peep, seq_len, fb, clip, gates, hout, cs, cf, hf, st, true);
+}
 
 template <int HH, int HSU>
 static bool cluster_bwd_f32_launch(asr_handle* h, int T, int B, int ndir, const float* dhout, const void* gates,
                                    const float* cs, const void* whpb, const float* peep, const int32_t* seq_len,
-                                   const float* dcf, const float* dhf, void* dgates, float* dpeep_part, hipStream_t st) {
+                                   const float* dcf, const float* dhf, void* dgates, float* dpeep_part, hipStream_t st,
+                                   bool grouped) {
   constexpr int G = HH / HSU, TPC = HSU / 16;
-  const int ncl = (B / 16) * ndir;
-  const size_t need = (size_t)ncl * (XHDR + (size_t)2 * G * G * TPC * 64 * 2) * sizeof(u64);
-  if ((size_t)T * B * ndir * HH >= (1ull << 31) || h->scratch_bytes < XCH_BYTES || need > XCH_HALF ||
-      (int)cluster_grid(G, ncl) > h->num_cu)
-    return false;
+  constexpr size_t cl_bytes = (XHDR + (size_t)2 * G * G * TPC * 64 * 2) * sizeof(u64);
+  if ((size_t)T * B * ndir * HH >= (1ull << 31) || h->scratch_bytes < XCH_BYTES) return false;
+  const TilePlan plan = cluster_launch_plan(h, G, ndir, B, cl_bytes, grouped);
+  if (!plan.n) return false;
   char* base = (char*)h->scratch + (h->scratch_bytes - XCH_BYTES);
-  const XchAreas xa = xch_take(h, base, need, st);
   if constexpr (HSU == 32 && (HH == 128 || HH == 256)) {
     if (cluster_f32_split_enabled()) {
       const size_t lds_s = (size_t)2 * 3 * 16 * (4 * HSU + 8) * 2 + (size_t)2 * TPC * 64 * 8;   // two x three term images + hand-over
-      hipLaunchKernelGGL((lstm_bwd_cluster_f32s_kernel<HH, HSU>), dim3(cluster_grid(G, ncl)), dim3(HSU * 8), lds_s, st, T,
-                         B, ndir, dhout, (const f32x4_t*)gates, cs, (const float*)whpb, peep, seq_len, dcf, dhf,
-                         (f32x4_t*)dgates, dpeep_part, xa.area, (unsigned*)base, kernel_flags(), xa.znext, xa.zwords, h->bptt_clip);
+      run_tile_groups(h, base, plan, B, ndir, cl_bytes, st, 0, [&](const XchAreas& xa, int ncl, int t0, int nt) {
+        hipLaunchKernelGGL((lstm_bwd_cluster_f32s_kernel<HH, HSU>), dim3(cluster_grid(G, ncl)), dim3(HSU * 8), lds_s, st, T,
+                           B, ndir, dhout, (const f32x4_t*)gates, cs, (const float*)whpb, peep, seq_len, dcf, dhf,
+                           (f32x4_t*)dgates, dpeep_part, xa.area, (unsigned*)base, kernel_flags(), xa.znext, xa.zwords,
+                           h->bptt_clip, t0, nt);
+      });
       return true;
     }
   }
   const size_t lds = (size_t)2 * 16 * (4 * HSU + 4) * 4 + (size_t)2 * TPC * 64 * 8;   // two dG images + the hand-over buffer
-  hipLaunchKernelGGL((lstm_bwd_cluster_f32_kernel<HH, HSU>), dim3(cluster_grid(G, ncl)), dim3(HSU * 8), lds, st, T, B, ndir,
-                     dhout, (const f32x4_t*)gates, cs, (const float*)whpb, peep, seq_len, dcf, dhf, (f32x4_t*)dgates,
-                     dpeep_part, xa.area, (unsigned*)base, kernel_flags(), xa.znext, xa.zwords, h->bptt_clip);
+  run_tile_groups(h, base, plan, B, ndir, cl_bytes, st, 0, [&](const XchAreas& xa, int ncl, int t0, int nt) {
+    hipLaunchKernelGGL((lstm_bwd_cluster_f32_kernel<HH, HSU>), dim3(cluster_grid(G, ncl)), dim3(HSU * 8), lds, st, T, B, ndir,
+                       dhout, (const f32x4_t*)gates, cs, (const float*)whpb, peep, seq_len, dcf, dhf, (f32x4_t*)dgates,
+                       dpeep_part, xa.area, (unsigned*)base, kernel_flags(), xa.znext, xa.zwords, h->bptt_clip, t0, nt);
+  });
   return true;
 }
 
@@ -3437,20 +3539,21 @@ bool asr_cluster_gru_fwd_try(asr_handle* h, int T, int B, int H, int ndir, const
                              float* rh, float* hout, float* h_final, hipStream_t st) {
   const char* env_c = getenv("ASR_GRU_CLUSTER");          // (read per call: the A-B test flips it inside one process)
   if ((env_c && env_c[0] == '0') || !cluster_f32_enabled() || (H != 64 && H != 128 && H != 256 && H != 320) || T < 1 || T >= 65536) return false;
-  const int G = H / 32, ncl = (B / 16) * ndir;
-  const size_t need = (size_t)ncl * (XHDR + (size_t)4 * G * 16 * 32) * sizeof(u64);
-  if ((size_t)T * B * ndir * 2 * H >= (1ull << 31) || h->scratch_bytes < XCH_BYTES || need > XCH_HALF ||
-      (int)cluster_grid(G, ncl) > h->num_cu)
-    return false;
+  const int G = H / 32;
+  const size_t cl_bytes = (XHDR + (size_t)4 * G * 16 * 32) * sizeof(u64);
+  if ((size_t)T * B * ndir * 2 * H >= (1ull << 31) || h->scratch_bytes < XCH_BYTES) return false;
+  const TilePlan plan = cluster_launch_plan(h, G, ndir, B, cl_bytes, true);   // one launch where it fits, tile groups otherwise
+  if (!plan.n) return false;
   char* base = (char*)h->scratch + (h->scratch_bytes - XCH_BYTES);
-  const XchAreas xa = xch_take(h, base, need, st);
   const size_t lds = (size_t)3 * 3 * 16 * (H + 8) * 2;
 #define ASR_GRU_CL(HH)                                                                                              \
   do {                                                                                                              \
     (void)hipFuncSetAttribute((const void*)gru_fwd_cluster_kernel<HH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL(gru_fwd_cluster_kernel<HH>, dim3(cluster_grid(HH / 32, ncl)), dim3(256), lds, st, T, B, ndir, xg, xc, \
-                       wgh, wch, seq_len, r, u, c, rh, hout, h_final, xa.area, (unsigned*)base, kernel_flags(), xa.znext, \
-                       xa.zwords);                                                                                   \
+    run_tile_groups(h, base, plan, B, ndir, cl_bytes, st, 1, [&](const XchAreas& xa, int ncl, int t0, int nt) {      \
+      hipLaunchKernelGGL(gru_fwd_cluster_kernel<HH>, dim3(cluster_grid(HH / 32, ncl)), dim3(256), lds, st, T, B, ndir, xg, xc, \
+                         wgh, wch, seq_len, r, u, c, rh, hout, h_final, xa.area, (unsigned*)base, kernel_flags(), xa.znext, \
+                         xa.zwords, t0, nt);                                                                         \
+    });                                                                                                             \
   } while (0)
   if (H == 64) ASR_GRU_CL(64); else if (H == 128) ASR_GRU_CL(128); else if (H == 256) ASR_GRU_CL(256); else ASR_GRU_CL(320);
 #undef ASR_GRU_CL
@@ -3462,31 +3565,32 @@ bool asr_cluster_gru_bwd_try(asr_handle* h, int T, int B, int H, int ndir, const
                              const float* wchT, const int32_t* seq_len, float* dgate, float* dcand, hipStream_t st) {
   const char* env_c = getenv("ASR_GRU_CLUSTER");          // (read per call: the A-B test flips it inside one process)
   if ((env_c && env_c[0] == '0') || !cluster_f32_enabled() || (H != 64 && H != 128 && H != 256 && H != 320) || T < 1 || T >= 65536) return false;
-  const int G = H / 32, ncl = (B / 16) * ndir;
-  const size_t need = (size_t)ncl * (XHDR + (size_t)6 * G * 16 * 32) * sizeof(u64);
-  if ((size_t)T * B * ndir * 2 * H >= (1ull << 31) || h->scratch_bytes < XCH_BYTES || need > XCH_HALF ||
-      (int)cluster_grid(G, ncl) > h->num_cu)
-    return false;
+  const int G = H / 32;
+  const size_t cl_bytes = (XHDR + (size_t)6 * G * 16 * 32) * sizeof(u64);
+  if ((size_t)T * B * ndir * 2 * H >= (1ull << 31) || h->scratch_bytes < XCH_BYTES) return false;
+  const TilePlan plan = cluster_launch_plan(h, G, ndir, B, cl_bytes, true);   // one launch where it fits, tile groups otherwise
+  if (!plan.n) return false;
   char* base = (char*)h->scratch + (h->scratch_bytes - XCH_BYTES);
-  const XchAreas xa = xch_take(h, base, need, st);
   const size_t lds = (size_t)5 * 3 * 16 * (H + 8) * 2;
 #define ASR_GRU_CLB(HH)                                                                                             \
   do {                                                                                                              \
     (void)hipFuncSetAttribute((const void*)gru_bwd_cluster_kernel<HH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL(gru_bwd_cluster_kernel<HH>, dim3(cluster_grid(HH / 32, ncl)), dim3(256), lds, st, T, B, ndir, dout,   \
-                       d_h_final, hout, r, u, c, wghT, wchT, seq_len, dgate, dcand, xa.area, (unsigned*)base,         \
-                       kernel_flags(), xa.znext, xa.zwords);                                                         \
+    run_tile_groups(h, base, plan, B, ndir, cl_bytes, st, 1, [&](const XchAreas& xa, int ncl, int t0, int nt) {      \
+      hipLaunchKernelGGL(gru_bwd_cluster_kernel<HH>, dim3(cluster_grid(HH / 32, ncl)), dim3(256), lds, st, T, B, ndir, dout, \
+                         d_h_final, hout, r, u, c, wghT, wchT, seq_len, dgate, dcand, xa.area, (unsigned*)base,       \
+                         kernel_flags(), xa.znext, xa.zwords, t0, nt);                                               \
+    });                                                                                                             \
   } while (0)
   if (H == 64) ASR_GRU_CLB(64); else if (H == 128) ASR_GRU_CLB(128); else if (H == 256) ASR_GRU_CLB(256); else ASR_GRU_CLB(320);
 #undef ASR_GRU_CLB
   return true;
 }
 
-#define ASR_F32_ARGS_B h, T, B, ndir, dhout, gates, cs, whpb, peep, seq_len, dcf, dhf, dgates, dpeep_part, st
-bool asr_cluster_bwd_f32_try(asr_handle* h, int T, int B, int H, int ndir, const float* dhout,
+#define ASR_F32_ARGS_B h, T, B, ndir, dhout, gates, cs, whpb, peep, seq_len, dcf, dhf, dgates, dpeep_part, st, grouped
+static bool cluster_bwd_f32_attempt(asr_handle* h, int T, int B, int H, int ndir, const float* dhout,
                              const void* gates, const float* cs, const void* whpb, const float* peep,
                              const int32_t* seq_len, const float* dcf, const float* dhf, void* dgates,
-                             float* dpeep_part, hipStream_t st) {
+                             float* dpeep_part, hipStream_t st, bool grouped) {
   if (!cluster_f32_enabled()) return false;
   if (bwd_units_per_cu() == 32) {
     if (H == 128) return cluster_bwd_f32_launch<128, 32>(ASR_F32_ARGS_B);
@@ -3498,20 +3602,28 @@ bool asr_cluster_bwd_f32_try(asr_handle* h, int T, int B, int H, int ndir, const
   }
   constexpr int HH = 128, G = HH / HS;
   if (H != HH) return false;
-  const int ncl = (B / 16) * ndir;
-  const size_t need = (size_t)ncl * (XHDR + (size_t)2 * G * G * 4 * 64 * 2) * sizeof(u64);
-  if ((size_t)T * B * ndir * H >= (1ull << 31) || h->scratch_bytes < XCH_BYTES || need > XCH_HALF ||
-      (int)cluster_grid(G, ncl) > h->num_cu)
-    return false;
+  constexpr size_t cl_bytes = (XHDR + (size_t)2 * G * G * 4 * 64 * 2) * sizeof(u64);
+  if ((size_t)T * B * ndir * H >= (1ull << 31) || h->scratch_bytes < XCH_BYTES) return false;
+  const TilePlan plan = cluster_launch_plan(h, G, ndir, B, cl_bytes, grouped);
+  if (!plan.n) return false;
   char* base = (char*)h->scratch + (h->scratch_bytes - XCH_BYTES);
-  const XchAreas xa = xch_take(h, base, need, st);
   const size_t lds = (size_t)2 * 16 * (4 * HS + 4) * 4 + 2 * 4 * 64 * 8;   // two dG images + the hand-over buffer
-  hipLaunchKernelGGL(lstm_bwd_cluster8_f32_kernel<HH>, dim3(cluster_grid(G, ncl)), dim3(CT8), lds, st, T, B, ndir,
-                     dhout, (const f32x4_t*)gates, cs, (const float*)whpb, peep, seq_len, dcf, dhf, (f32x4_t*)dgates,
-                     dpeep_part, xa.area, (unsigned*)base, kernel_flags(), xa.znext, xa.zwords, h->bptt_clip);
+  run_tile_groups(h, base, plan, B, ndir, cl_bytes, st, 0, [&](const XchAreas& xa, int ncl, int t0, int nt) {
+    hipLaunchKernelGGL(lstm_bwd_cluster8_f32_kernel<HH>, dim3(cluster_grid(G, ncl)), dim3(CT8), lds, st, T, B, ndir,
+                       dhout, (const f32x4_t*)gates, cs, (const float*)whpb, peep, seq_len, dcf, dhf, (f32x4_t*)dgates,
+                       dpeep_part, xa.area, (unsigned*)base, kernel_flags(), xa.znext, xa.zwords, h->bptt_clip, t0, nt);
+  });
   return true;
 }
 #undef ASR_F32_ARGS_B
+bool asr_cluster_bwd_f32_try(asr_handle* h, int T, int B, int H, int ndir, const float* dhout,
+                             const void* gates, const float* cs, const void* whpb, const float* peep,
+                             const int32_t* seq_len, const float* dcf, const float* dhf, void* dgates,
+                             float* dpeep_part, hipStream_t st) {
+  // one launch where it fits, tile groups otherwise
+  return cluster_bwd_f32_attempt(h, T, B, H, ndir, dhout, gates, cs, whpb, peep, seq_len, dcf, dhf, dgates, dpeep_part, st, false) ||
+         cluster_bwd_f32_attempt(h, T, B, H, ndir, dhout, gates, cs, whpb, peep, seq_len, dcf, dhf, dgates, dpeep_part, st, true);
+}
 
 // ---------------------------------------------------------------- debug: 16-byte exchange words, tear probe
 // Would a lane's 16-byte store be seen whole by a 16-byte load of another CU?  The clusters' exchange uses 8-byte granules

@@ -1315,6 +1315,49 @@ def debug_set_lstm_flags(flags):
     _lib.load().asr_debug_set_lstm_flags(int(flags))
 
 
+def cluster_tile_groups(G, ndir, tiles, cu_budget):
+    """asr_cluster_tile_groups: the [(first_tile, ntiles), ...] launches of a cluster recurrence with G workgroups per
+    cluster over `tiles` 16-utterance tiles when at most cu_budget workgroups are resident at once; [] = no plan.
+    Host arithmetic only (no GPU)."""
+    lib = _lib.load()
+    first, cnt = (C.c_int * max(int(tiles), 1))(), (C.c_int * max(int(tiles), 1))()
+    n = lib.asr_cluster_tile_groups(int(G), int(ndir), int(tiles), int(cu_budget), first, cnt, max(int(tiles), 1))
+    if n < 0:
+        raise ValueError('asr_cluster_tile_groups: bad arguments')
+    return [(first[i], cnt[i]) for i in range(n)]
+
+
+_PATH_KEYS = ('lstm_cluster', 'lstm_single_cu', 'lstm_split_calls', 'gru_cluster', 'gru_single_cu', 'gru_split_calls')
+
+
+def _device_handles(device):
+    dev = device.index or 0 if isinstance(device, torch.device) else int(device)
+    _lib.handle(dev)
+    return [h for (d, _lane), h in list(_lib._handles.items()) if d == dev]
+
+
+def recurrence_path_counts(device=0):
+    """Which path the recurrence calls on `device` took since the last reset, summed over its handles: cluster launches
+    (one per tile group), single-CU calls, and calls that were split into more than one tile group, for LSTM and GRU.
+    Host counters: no device work, no synchronisation."""
+    tot = [0] * 6
+    for h in _device_handles(device):
+        out = (C.c_ulonglong * 6)()
+        h.check(h.lib.asr_recurrence_path_counts(h.h, out), 'asr_recurrence_path_counts')
+        tot = [a + int(b) for a, b in zip(tot, out)]
+    return dict(zip(_PATH_KEYS, tot))
+
+
+def reset_recurrence_path_counts(device=0):
+    for h in _device_handles(device):
+        h.check(h.lib.asr_reset_recurrence_path_counts(h.h), 'asr_reset_recurrence_path_counts')
+
+
+def debug_set_cluster_cu_budget(n):
+    """TEST ONLY: co-resident workgroups a cluster launch may use (0 = the device's CU count; never more than that)."""
+    _lib.load().asr_debug_set_cluster_cu_budget(int(n))
+
+
 # ---------------------------------------------------------------- CTC
 def debug_set_gru_persistent(on):
     """asr_debug_set_gru_persistent: 1 = one persistent launch per GRU layer call (default), 0 = launch per step."""
