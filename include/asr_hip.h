@@ -453,6 +453,32 @@ int asr_cluster_tile_groups(int G, int ndir, int tiles, int cu_budget, int* firs
  * measured). */
 int asr_recurrence_path_counts(asr_handle* h, unsigned long long* out6);
 int asr_reset_recurrence_path_counts(asr_handle* h);
+/* Which kernels the attention decoder calls on this handle launched since the last reset (host integers bumped at
+ * launch time like the recurrence counters above: no device work, no synchronisation, no effect on any launch).
+ * out[i], i < min(n, ASR_ATT_PATH_N), in the order of the enum below; entries of `out` past ASR_ATT_PATH_N are zeroed.
+ * The step counters count decoder-loop steps (asr_att_decoder_fwd / _infer / _bwd); the lane-shape counters count
+ * launches, whether they come from a loop or from the single-kernel entry points (asr_att_energy_fwd, ...). */
+enum {
+  ASR_ATT_FWD_STEP_FUSED = 0,     /* energies + softmax + context as att_fused_fwd_kernel + combine */
+  ASR_ATT_FWD_STEP_4LAUNCH,       /* energy kernel, softmax, context partials, reduction */
+  ASR_ATT_FWD_CELL_BF16,          /* product + cell in one launch on the bf16 weight image */
+  ASR_ATT_FWD_CELL_F32IMG,        /* product + cell in one launch on the fp32 gate-interleaved image */
+  ASR_ATT_FWD_CELL_GEMM,          /* asr_gemm_act, then the cell kernel */
+  ASR_ATT_BWD_STEP_FUSED_Q,       /* query-FC backward + cell backward + partial sums in one launch */
+  ASR_ATT_BWD_STEP_UNFUSED,       /* reduction, GEMM or column add, cell backward */
+  ASR_ATT_BWD_CELL_BF16,          /* dpre W^T on the bf16 weight rows */
+  ASR_ATT_BWD_CELL_GEMM,          /* dpre W^T by asr_gemm_act */
+  ASR_ATT_BWD_SOFTMAX_FOLDED,     /* softmax backward inside the energy backward */
+  ASR_ATT_BWD_SOFTMAX_SEPARATE,   /* its own kernel */
+  ASR_ATT_ENERGY_FWD_L16, ASR_ATT_ENERGY_FWD_L32, ASR_ATT_ENERGY_FWD_L64, ASR_ATT_ENERGY_FWD_L64X2, ASR_ATT_ENERGY_FWD_GENERAL,
+  ASR_ATT_ENERGY_BWD_L16, ASR_ATT_ENERGY_BWD_L32, ASR_ATT_ENERGY_BWD_L64, ASR_ATT_ENERGY_BWD_L64X2, ASR_ATT_ENERGY_BWD_GENERAL,
+  ASR_ATT_LOC_FWD_L16, ASR_ATT_LOC_FWD_L32, ASR_ATT_LOC_FWD_L64, ASR_ATT_LOC_FWD_GENERAL,
+  ASR_ATT_LOC_BWD_L16, ASR_ATT_LOC_BWD_L32, ASR_ATT_LOC_BWD_L64, ASR_ATT_LOC_BWD_GENERAL,
+  ASR_ATT_FUSED_FWD_L16, ASR_ATT_FUSED_FWD_L32, ASR_ATT_FUSED_FWD_L64, ASR_ATT_FUSED_FWD_L64X2,   /* lanes of the fused step */
+  ASR_ATT_PATH_N
+};
+int asr_att_path_counts(asr_handle* h, unsigned long long* out, int n);
+int asr_reset_att_path_counts(asr_handle* h);
 /* TEST ONLY (process-wide): the number of co-resident workgroups a cluster launch may use; 0 (default) = the device's CU
  * count.  Any other value is clamped to [0, CU count] where it is used, so it can only LOWER the grid of a launch -- the
  * tests exercise tile groups at B = 80 - 272 with it.  A plain process-wide int, not thread-safe: set it while no

@@ -358,6 +358,13 @@ static inline int energy_vec_shape(int A, const void* keys, const void* qz, cons
   return nvec <= 16 ? 16 * 4 + 1 : nvec <= 32 ? 32 * 4 + 1 : nvec <= 64 ? 64 * 4 + 1 : 64 * 4 + 2;
 }
 
+// asr_att_path_counts: the counter of a lane shape behind `first` (..._L16, _L32, _L64[, _L64X2], _GENERAL); `general`
+// is the offset of the family's last entry (3 for the location kernels, which have no 64 x 2 form, else 4)
+static inline void att_count_shape(asr_handle* h, int first, int shape, int general) {
+  const int o = shape == 16 * 4 + 1 ? 0 : shape == 32 * 4 + 1 ? 1 : shape == 64 * 4 + 1 ? 2 : shape == 64 * 4 + 2 ? 3 : general;
+  h->att_counts[first + (o < general ? o : general)] += 1;
+}
+
 // masked softmax over t.  energy[B,T] -> alpha[B,T].
 // mask: e*m + (1-m)*FLT_MIN(lowest), then *sharpening (attention_layer.py:76-89).
 // norm != NULL selects the reference's sigmoid smoothing (attention_layer.py:92-96): alpha = sigmoid(e) / sum_t
@@ -1388,6 +1395,14 @@ __global__ void att_loc_reduce_both_kernel(const float* __restrict__ part, const
   }
 }
 // 0: the general kernels, else LPF * 4 + NV
+// LDS of the location kernels whose footprint grows with A (W_filter rows, the four waves' partial sums): a gfx950
+// workgroup may hold 160 KB, the 64 KB that every launch gets without asking end at A = 248 (vectorised backward, 200
+// taps) / A = 232 (general backward) -- the reference's attention_dim = 256 is past both.  More than 64 KB is asked for
+// per kernel (and device: the attribute is set at the launch that needs it, as the recurrence launchers do).
+constexpr size_t LOC_LDS_MAX = (size_t)160 * 1024;
+template <typename K> static inline void loc_lds_opt_in(K k, size_t lds) {
+  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
 static inline int loc_vec_shape(int A, const void* keys, const void* qz, const void* v, const void* wfil, const void* dkeys) {
   if (A % 4 != 0 || A > 256 ||
       ((uintptr_t)keys | (uintptr_t)qz | (uintptr_t)v | (uintptr_t)wfil | (uintptr_t)dkeys) % 16 != 0)
@@ -1786,7 +1801,9 @@ static int energy_fwd_launch(asr_handle* h, const float* keys, const float* qz, 
   const dim3 grid((T + ATT_CH - 1) / ATT_CH, B);
 #define ASR_EFWD(L, NV_) \
   hipLaunchKernelGGL((att_energy_fwd_vec_kernel<L, NV_>), grid, dim3(256), 0, (hipStream_t)s, keys, qz, v, T, B, A, mode, energy, seq_len)
-  switch (energy_vec_shape(A, keys, qz, v, nullptr)) {
+  const int shape = energy_vec_shape(A, keys, qz, v, nullptr);
+  att_count_shape(h, ASR_ATT_ENERGY_FWD_L16, shape, 4);
+  switch (shape) {
     case 16 * 4 + 1: ASR_EFWD(16, 1); break;
     case 32 * 4 + 1: ASR_EFWD(32, 1); break;
     case 64 * 4 + 1: ASR_EFWD(64, 1); break;
@@ -1831,6 +1848,7 @@ static int energy_bwd_launch(asr_handle* h, const float* denergy, const float* k
   const dim3 grid(nch, B);
   SoftmaxBwdFold f = {nullptr, nullptr, nullptr, nullptr, 0, 0.f};
   if (fold && fold->da) f = *fold;
+  att_count_shape(h, ASR_ATT_ENERGY_BWD_L16, shape, 4);
 #define ASR_EBWD(L, NV_) \
   hipLaunchKernelGGL((att_energy_bwd_vec_kernel<L, NV_>), grid, dim3(256), 0, (hipStream_t)s, denergy, keys, qz, v, T, B, A, mode, dkeys, part, seq_len, ech, f)
   switch (shape) {
@@ -1868,6 +1886,7 @@ static int loc_energy_fwd_launch(asr_handle* h, const float* alpha_prev, const f
   const dim3 grid((T + ATT_CH - 1) / ATT_CH, B);
   const int shape = loc_vec_shape(A, keys, qz, v, wfil, nullptr);
   const size_t ldsv = loc_vec_lds_floats(taps) * sizeof(float);
+  att_count_shape(h, ASR_ATT_LOC_FWD_L16, ldsv <= 64 * 1024 ? shape : 0, 3);
   if (shape && ldsv <= 64 * 1024) {
 #define ASR_LFWD(L) \
   hipLaunchKernelGGL((att_loc_energy_fwd_vec_kernel<L, 1>), grid, dim3(256), ldsv, (hipStream_t)s, alpha_prev, filt, wfil, keys, qz, v, T, B, A, taps, energy, seq_len)
@@ -1877,7 +1896,8 @@ static int loc_energy_fwd_launch(asr_handle* h, const float* alpha_prev, const f
     return ASR_OK;
   }
   const size_t lds = loc_lds_floats(taps, A) * sizeof(float);
-  if (lds > 64 * 1024) ASR_FAIL(h, ASR_ERR_UNSUPPORTED, "asr_att_loc_energy_fwd: taps=%d / A=%d need %zu B of LDS", taps, A, lds);
+  if (lds > LOC_LDS_MAX) ASR_FAIL(h, ASR_ERR_UNSUPPORTED, "asr_att_loc_energy_fwd: taps=%d / A=%d need %zu B of LDS", taps, A, lds);
+  loc_lds_opt_in(att_loc_energy_fwd_kernel, lds);
   hipLaunchKernelGGL(att_loc_energy_fwd_kernel, grid, dim3(256), lds, (hipStream_t)s, alpha_prev, filt, wfil, keys, qz, v,
                      T, B, A, taps, energy);
   ASR_CHECK_LAUNCH(h, "asr_att_loc_energy_fwd");
@@ -1909,10 +1929,12 @@ static int loc_energy_bwd_launch(asr_handle* h, const float* denergy, const floa
   const size_t ldsAv = (loc_vec_lds_floats(taps) + 4 * NP) * sizeof(float);
   const size_t ldsBv = ((size_t)(ATT_CH + ((taps + 15) & ~15)) + (size_t)taps * LOC_FS +
                         (size_t)(ATT_CH + taps - 1) * LOC_FS + 16) * sizeof(float);
-  if (shape && ldsAv <= 64 * 1024 && ldsBv <= 64 * 1024) {
+  att_count_shape(h, ASR_ATT_LOC_BWD_L16, (ldsAv <= LOC_LDS_MAX && ldsBv <= 64 * 1024) ? shape : 0, 3);
+  if (shape && ldsAv <= LOC_LDS_MAX && ldsBv <= 64 * 1024) {
 #define ASR_LBWD(L) \
+  loc_lds_opt_in(att_loc_energy_bwd_vec_kernel<L, 1>, ldsAv); \
   hipLaunchKernelGGL((att_loc_energy_bwd_vec_kernel<L, 1>), grid, dim3(256), ldsAv, (hipStream_t)s, denergy, alpha_prev, filt, wfil, keys, qz, v, T, B, A, taps, dkeys, part, dfeat, seq_len)
-    if (shape == 16 * 4 + 1) ASR_LBWD(16); else if (shape == 32 * 4 + 1) ASR_LBWD(32); else ASR_LBWD(64);
+    if (shape == 16 * 4 + 1) { ASR_LBWD(16); } else if (shape == 32 * 4 + 1) { ASR_LBWD(32); } else { ASR_LBWD(64); }
 #undef ASR_LBWD
     hipLaunchKernelGGL(att_loc_conv_bwd_vec_kernel, grid, dim3(256), ldsBv, (hipStream_t)s, dfeat, alpha_prev, filt, T, B,
                        taps, dalpha_prev, fpart, seq_len);
@@ -1924,8 +1946,9 @@ static int loc_energy_bwd_launch(asr_handle* h, const float* denergy, const floa
   }
   const size_t ldsA = (loc_lds_floats(taps, A) + 4 * NP) * sizeof(float);
   const size_t ldsB = ((size_t)(ATT_CH + taps - 1) * (1 + LOC_C) + (size_t)taps * LOC_C) * sizeof(float);
-  if (ldsA > 64 * 1024 || ldsB > 64 * 1024)
+  if (ldsA > LOC_LDS_MAX || ldsB > 64 * 1024)
     ASR_FAIL(h, ASR_ERR_UNSUPPORTED, "asr_att_loc_energy_bwd: taps=%d / A=%d need %zu / %zu B of LDS", taps, A, ldsA, ldsB);
+  loc_lds_opt_in(att_loc_energy_bwd_kernel, ldsA);
   hipLaunchKernelGGL(att_loc_energy_bwd_kernel, grid, dim3(256), ldsA, (hipStream_t)s, denergy, alpha_prev, filt,
                      wfil, keys, qz, v, T, B, A, taps, dkeys, part, dfeat);
   hipLaunchKernelGGL(att_loc_bwd_reduce_kernel, dim3((unsigned)((B * NP + 255) / 256)), dim3(256), 0, (hipStream_t)s,
@@ -2178,6 +2201,7 @@ static bool att_fused_step(asr_handle* h, const asr_att_decoder* a, const float*
   float* stat = part + (size_t)nch * B * E;
   const dim3 grid(nch, B);
   hipStream_t st = (hipStream_t)s;
+  att_count_shape(h, ASR_ATT_FUSED_FWD_L16, shape, 4);   // (shape != 0 here: never the fifth slot)
 #define ASR_FUSED(L, NV_, TE_, F_) \
   hipLaunchKernelGGL((att_fused_fwd_kernel<L, NV_, TE_, F_>), grid, dim3(256), 0, st, a->keys, qz, a->v, T, B, A, a->att_mode, \
                      a->sharpening, a->seq_len, (const TE_*)a->enc, E, alpha, part, stat)
@@ -2232,6 +2256,7 @@ static int dec_fwd_step(asr_handle* h, const asr_att_decoder* a, int k, int ks, 
   float* qz = a->qz_all + (size_t)ks * B * A;
   // the cell output (times its dropout mask) lands in av[:, :U]; without a query FC it IS the query
   if (dec_cell_gemm_h(a)) {  // product + cell as one launch on the bf16 fragment image (dec_cell_image)
+    h->att_counts[ASR_ATT_FWD_CELL_BF16] += 1;
     DEC_TRY(asr_lstm_cell_gemm_fwd_h(h, din, Din, Din, a->W_cell_h, a->c_all + (size_t)k * B * U,
                                      a->h_all + (size_t)k * B * U, a->peep, a->live + (size_t)k * B, B, U, a->forget_bias,
                                      a->cell_clip, a->gates_all + (size_t)ks * B * 4 * U, a->craw_all + (size_t)ks * B * U,
@@ -2239,6 +2264,7 @@ static int dec_fwd_step(asr_handle* h, const asr_att_decoder* a, int k, int ks, 
                                      a->dmask ? a->dmask + (size_t)k * B * U : nullptr, a->has_query_fc ? nullptr : qz,
                                      dnext ? dnext + Em + E2 : nullptr, Din, av, Dav, s));
   } else if (dec_cell_gemm(a)) {    // ... on the fp32 interleaved weight image
+    h->att_counts[ASR_ATT_FWD_CELL_F32IMG] += 1;
     DEC_TRY(asr_lstm_cell_gemm_fwd(h, din, Din, Din, a->W_cell_il, a->b_cell ? 1 : 0, a->c_all + (size_t)k * B * U,
                                    a->h_all + (size_t)k * B * U, a->peep, a->live + (size_t)k * B, B, U, a->forget_bias,
                                    a->cell_clip, a->gates_all + (size_t)ks * B * 4 * U, a->craw_all + (size_t)ks * B * U,
@@ -2246,6 +2272,7 @@ static int dec_fwd_step(asr_handle* h, const asr_att_decoder* a, int k, int ks, 
                                    a->dmask ? a->dmask + (size_t)k * B * U : nullptr, a->has_query_fc ? nullptr : qz,
                                    dnext ? dnext + Em + E2 : nullptr, Din, av, Dav, s));
   } else {
+    h->att_counts[ASR_ATT_FWD_CELL_GEMM] += 1;
     DEC_TRY(asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, B, 4 * U, Din, din, Din, a->W_cell, 4 * U, pre, 4 * U, a->b_cell, 0, 0, s));
     DEC_TRY(asr_lstm_cell_fwd_ex(h, pre, a->c_all + (size_t)k * B * U, a->h_all + (size_t)k * B * U, a->peep,
                                  a->live + (size_t)k * B, B, U, a->forget_bias, a->cell_clip,
@@ -2257,9 +2284,11 @@ static int dec_fwd_step(asr_handle* h, const asr_att_decoder* a, int k, int ks, 
   if (a->has_query_fc)
     DEC_TRY(asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, B, A, U, av, Dav, a->W_q, a->ld_wq, qz, A, a->b_q, 0, 0, s));
   if (att_fused_step(h, a, qz, a->alpha_all + (size_t)k * B * T, ctx, av + U, Dav, dnext ? dnext + Em : nullptr, Din, s)) {
+    h->att_counts[ASR_ATT_FWD_STEP_FUSED] += 1;
     ASR_CHECK_LAUNCH(h, "asr_att_decoder_fwd(fused step)");
     return ASR_OK;
   }
+  h->att_counts[ASR_ATT_FWD_STEP_4LAUNCH] += 1;
   if (a->carry_alpha)
     DEC_TRY(loc_energy_fwd_launch(h, k > 0 ? a->alpha_all + (size_t)(k - 1) * B * T : a->alpha_zero, a->filt, a->wfil,
                                   a->keys, qz, a->v, T, B, A, a->taps, energy, a->seq_len, s));
@@ -2443,6 +2472,7 @@ extern "C" int asr_att_decoder_bwd(asr_handle* h, const asr_att_decoder* a, asr_
       DEC_TRY(softmax_ctx_bwd_launch(h, dctx, nullptr, 0, nullptr, alpha_k, a->seq_len, a->sharpening, a->enc,
                                      a->enc_dtype, T, B, E2, denergy, nullptr, snorm, dalpha_next, fp, s));
     }
+    h->att_counts[(fp && fp->da) ? ASR_ATT_BWD_SOFTMAX_FOLDED : ASR_ATT_BWD_SOFTMAX_SEPARATE] += 1;
     if (a->carry_alpha) {
       float* dap = dalp[k & 1];
       DEC_TRY(loc_energy_bwd_launch(h, denergy, k > 0 ? a->alpha_all + (size_t)(k - 1) * B * T : a->alpha_zero, a->filt,
@@ -2460,6 +2490,7 @@ extern "C" int asr_att_decoder_bwd(asr_handle* h, const asr_att_decoder* a, asr_
     const bool fused_q = !a->carry_alpha && a->has_query_fc && (A == 64 || A == 128 || A == 256 || A == 512) && U % DQ_CT == 0 &&
                          a->ld_wq % 4 == 0 && ((uintptr_t)a->W_q) % 16 == 0 && ((uintptr_t)dqz) % 16 == 0 &&
                          (!dv || ((uintptr_t)dv) % 16 == 0);
+    h->att_counts[fused_q ? ASR_ATT_BWD_STEP_FUSED_Q : ASR_ATT_BWD_STEP_UNFUSED] += 1;
     if (fused_q) {
       const float* part = nullptr;
       int nchq = 0;
@@ -2487,6 +2518,7 @@ extern "C" int asr_att_decoder_bwd(asr_handle* h, const asr_att_decoder* a, asr_
                                           // whose gradient op ignores cell_clip: the clamp is straight-through here
     }
     float* d_in = a->d_in_all + (size_t)k * B * Din;
+    h->att_counts[cell_h ? ASR_ATT_BWD_CELL_BF16 : ASR_ATT_BWD_CELL_GEMM] += 1;
     if (cell_h) DEC_TRY(asr_lstm_cell_gemm_bwd_h(h, dpre, B, Din, U, a->W_cell_h, d_in, Din, s));   // bf16 weight rows
     else DEC_TRY(asr_gemm_act(h, ASR_F32, ASR_F32, 0, 1, B, Din, 4 * U, dpre, 4 * U, a->W_cell, 4 * U, d_in, Din, nullptr, 0, 0, s));
     cur ^= 1;
@@ -2497,3 +2529,14 @@ extern "C" int asr_att_decoder_bwd(asr_handle* h, const asr_att_decoder* a, asr_
   return ASR_OK;
 }
 
+
+extern "C" int asr_att_path_counts(asr_handle* h, unsigned long long* out, int n) {
+  if (!h || !out || n < 0) return ASR_ERR_INVALID_ARG;
+  for (int i = 0; i < n; ++i) out[i] = i < ASR_ATT_PATH_N ? h->att_counts[i] : 0ull;
+  return ASR_OK;
+}
+extern "C" int asr_reset_att_path_counts(asr_handle* h) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  for (int i = 0; i < ASR_ATT_PATH_N; ++i) h->att_counts[i] = 0;
+  return ASR_OK;
+}

@@ -29,6 +29,8 @@ struct asr_handle {
   // recurrence launches since the last asr_reset_recurrence_path_counts (plain host counters bumped at launch time):
   // {cluster launches, single-CU calls, calls split into more than one tile group} of the LSTM, then of the GRU
   unsigned long long rec_counts[6];
+  // attention-decoder launches since the last asr_reset_att_path_counts, indexed by the ASR_ATT_* enum of asr_hip.h
+  unsigned long long att_counts[ASR_ATT_PATH_N];
 };
 
 #define ASR_FAIL(h, code, ...)                                  \

@@ -1353,6 +1353,36 @@ def reset_recurrence_path_counts(device=0):
         h.check(h.lib.asr_reset_recurrence_path_counts(h.h), 'asr_reset_recurrence_path_counts')
 
 
+# the ASR_ATT_* enum of include/asr_hip.h, in its order
+_ATT_PATH_KEYS = ('fwd_step_fused', 'fwd_step_4launch', 'fwd_cell_bf16', 'fwd_cell_f32img', 'fwd_cell_gemm',
+                  'bwd_step_fused_q', 'bwd_step_unfused', 'bwd_cell_bf16', 'bwd_cell_gemm', 'bwd_softmax_folded',
+                  'bwd_softmax_separate',
+                  'energy_fwd_16', 'energy_fwd_32', 'energy_fwd_64', 'energy_fwd_64x2', 'energy_fwd_general',
+                  'energy_bwd_16', 'energy_bwd_32', 'energy_bwd_64', 'energy_bwd_64x2', 'energy_bwd_general',
+                  'loc_fwd_16', 'loc_fwd_32', 'loc_fwd_64', 'loc_fwd_general',
+                  'loc_bwd_16', 'loc_bwd_32', 'loc_bwd_64', 'loc_bwd_general',
+                  'fused_fwd_16', 'fused_fwd_32', 'fused_fwd_64', 'fused_fwd_64x2')
+
+
+def att_path_counts(device=0):
+    """Which kernels the attention decoder calls on `device` launched since the last reset, summed over its handles
+    (asr_att_path_counts): decoder-loop steps by path (forward step, forward cell, backward step, backward cell product,
+    softmax backward) and energy / location / fused-step launches by lane shape.  Host counters: no device work, no
+    synchronisation."""
+    n = len(_ATT_PATH_KEYS)
+    tot = [0] * n
+    for h in _device_handles(device):
+        out = (C.c_ulonglong * n)()
+        h.check(h.lib.asr_att_path_counts(h.h, out, n), 'asr_att_path_counts')
+        tot = [a + int(b) for a, b in zip(tot, out)]
+    return dict(zip(_ATT_PATH_KEYS, tot))
+
+
+def reset_att_path_counts(device=0):
+    for h in _device_handles(device):
+        h.check(h.lib.asr_reset_att_path_counts(h.h), 'asr_reset_att_path_counts')
+
+
 def debug_set_cluster_cu_budget(n):
     """TEST ONLY: co-resident workgroups a cluster launch may use (0 = the device's CU count; never more than that)."""
     _lib.load().asr_debug_set_cluster_cu_budget(int(n))

@@ -202,10 +202,14 @@ def test_att_softmax_context_kernels_multi_chunk(cuda, T, enc_dtype, sigmoid):
     """asr_att_softmax_ctx_fwd / _bwd (attention_layer.py:75-111): mask, sharpening, softmax / sigmoid smoothing,
     context, and the gradients w.r.t. the energies and (per-step form) the encoder outputs, incl. an external
     gradient w.r.t. alpha (carried location features), vs fp64 autograd on the operands the kernel reads."""
-    from tensorflow_end2end_speech_recognition_amd import ops
     rng = np.random.RandomState(T + 7)
-    B, E, sharp = 4, 1024, 1.5
-    sl = _ragged(rng, B, T)
+    _softmax_context_case(cuda, T, 1024, enc_dtype, sigmoid, _ragged(rng, 4, T), rng)
+
+
+def _softmax_context_case(cuda, T, E, enc_dtype, sigmoid, sl, rng=None):
+    from tensorflow_end2end_speech_recognition_amd import ops
+    rng = rng if rng is not None else np.random.RandomState(T + E)
+    B, sharp = len(sl), 1.5
     enc = torch.tensor(rng.randn(T, B, E), dtype=torch.float32)
     if enc_dtype == 'bf16':
         enc = enc.to(torch.bfloat16)
@@ -279,6 +283,157 @@ def test_att_location_feature_kernels(cuda, T, taps, with_keys):
     assert rel(dap.cpu().numpy(), leaves[0].grad.numpy()) < 2e-5
     if with_keys:
         assert rel(dkeys.cpu().numpy(), k64.grad.numpy()) < 2e-5
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The same kernels across the lane shapes their launchers pick from the attention width (energy_vec_shape /
+# loc_vec_shape in csrc/attention.hip), with ops.att_path_counts saying which one ran.
+def _energy_lanes(A, aligned=True):
+    """energy_vec_shape: float4 lanes per frame (x 2 vectors per lane above 256 columns), else the general kernel."""
+    if A % 4 or A > 512 or not aligned:
+        return 'general'
+    return '16' if A <= 64 else '32' if A <= 128 else '64' if A <= 256 else '64x2'
+
+
+def _loc_lanes(A, aligned=True):
+    """loc_vec_shape: as above, no two-vector form."""
+    if A % 4 or A > 256 or not aligned:
+        return 'general'
+    return '16' if A <= 64 else '32' if A <= 128 else '64'
+
+
+def _counted(ops):
+    """The non-zero attention path counters since the last reset."""
+    return {k: v for k, v in ops.att_path_counts(0).items() if v}
+
+
+def _lane_lengths(rng, T):
+    """B = 5: a full row, one frame, exactly one 64-frame chunk, one frame more, a random length."""
+    return np.array([T, 1, 64, 65, rng.randint(66, T)], dtype=np.int32)
+
+
+def _misaligned(t, dev):
+    """`t` on `dev` at an address that is 4 but not 16 bytes aligned: a view into a buffer one float larger."""
+    buf = torch.empty(t.numel() + 1, dtype=torch.float32, device=dev)
+    out = buf[1:].view(t.shape)
+    out.copy_(t)
+    assert out.data_ptr() % 16 == 4 and out.is_contiguous()
+    return out
+
+
+@pytest.mark.parametrize('A', [4, 36, 64, 100, 130, 256, 260, 512, 516, 'qz+4B', 'keys+4B'])
+@pytest.mark.parametrize('mode,with_keys', [(0, True), (0, False), (1, True)])
+def test_att_energy_kernels_lane_shapes(cuda, A, mode, with_keys):
+    """asr_att_energy_fwd / _bwd at every lane shape of energy_vec_shape: 16 lanes (A = 4: one live lane, 36: tail lanes
+    idle, 64: all), 32 (100: tail idle), 64 (256), 64 x 2 vectors (260: one live lane in the second vector, 512: all) and
+    the general kernels (130: A % 4 != 0, 516: A > 512, and A = 128 with qz or keys 4 bytes off a 16-byte boundary), vs
+    fp64 autograd.  T = 200 (four chunks), B = 5; the entry points take no lengths, so the ragged batch (full, 1, 64, 65,
+    random frames) is expressed the way the decoder loop does it: the energy gradient is zero from a row's length on.
+    Bounds: those of test_att_energy_kernels_multi_chunk (they do not depend on A: relative to the largest entry)."""
+    from tensorflow_end2end_speech_recognition_amd import ops
+    off = A if isinstance(A, str) else None
+    if off == 'keys+4B' and not with_keys:
+        off = 'qz+4B'                                          # (no keys to misplace: the query again)
+    A = 128 if off else A
+    rng = np.random.RandomState(1000 * mode + A + (7 if with_keys else 0))
+    B, T = 5, 200
+    sl = _lane_lengths(rng, T)
+    keys = torch.tensor(rng.randn(T, B, A) * 0.5, dtype=torch.float32) if with_keys else None
+    qz = torch.tensor(rng.randn(B, A) * 0.5, dtype=torch.float32)
+    v = torch.tensor(rng.randn(A), dtype=torch.float32)
+    de = torch.tensor(rng.randn(B, T), dtype=torch.float32) * (torch.arange(T).unsqueeze(0) < torch.tensor(sl).long().unsqueeze(1))
+    k64 = keys.double().clone().requires_grad_(True) if with_keys else None
+    q64, v64 = qz.double().clone().requires_grad_(True), v.double().clone().requires_grad_(True)
+    if mode == 0:
+        z = q64.unsqueeze(0) + (k64 if with_keys else torch.zeros(T, B, A, dtype=torch.float64))
+        ref = (v64 * torch.tanh(z)).sum(2).t()
+    else:
+        ref = (k64 * q64.unsqueeze(0)).sum(2).t()
+    (ref * de.double()).sum().backward()
+    kd = None if not with_keys else _misaligned(keys, cuda) if off == 'keys+4B' else keys.to(cuda)
+    qd = _misaligned(qz, cuda) if off == 'qz+4B' else qz.to(cuda)
+    vd = v.to(cuda) if mode == 0 else None
+    lanes = _energy_lanes(A, aligned=not off)
+    ops.reset_att_path_counts(0)
+    got = ops.att_energy_fwd(kd, qd, vd, T, mode)
+    assert _counted(ops) == {'energy_fwd_' + lanes: 1}
+    assert np.abs(got.cpu().numpy() - ref.detach().numpy()).max() < 2e-5 * max(1.0, float(ref.abs().max()))
+    dkeys = torch.zeros(T, B, A, device=cuda) if with_keys else None
+    ops.reset_att_path_counts(0)
+    dqz, dv = ops.att_energy_bwd(de.to(cuda), kd, qd, vd, mode, dkeys=dkeys, want_dv=mode == 0)
+    assert _counted(ops) == {'energy_bwd_' + lanes: 1}
+    rel = lambda a, b: np.abs(a - b).max() / max(np.abs(b).max(), 1e-30)
+    assert rel(dqz.cpu().numpy(), q64.grad.numpy()) < 1e-5
+    if mode == 0:
+        assert rel(dv.sum(0).cpu().numpy(), v64.grad.numpy()) < 1e-5
+    if with_keys:
+        assert rel(dkeys.cpu().numpy(), k64.grad.numpy()) < 1e-5
+    assert ops.check_async_errors(0) == 0
+
+
+@pytest.mark.parametrize('A', [4, 36, 64, 100, 256, 260, 'qz+4B'])
+@pytest.mark.parametrize('taps,with_keys', [(201, False), (200, True)])
+def test_att_location_feature_kernels_lane_shapes(cuda, A, taps, with_keys):
+    """asr_att_loc_energy_fwd / _bwd at every lane shape of loc_vec_shape: 16 lanes (A = 4, 36, 64), 32 (100), 64 (256:
+    the backward's four-wave partial sums then need more than 64 KB of LDS) and the general kernels (260: A > 256; A = 128
+    with a misaligned query), two accumulating backward calls, vs fp64 autograd of _cpu_ops._loc_energy.  T = 200, B = 5,
+    ragged as the loop has it: the previous weights and the energy gradient are zero from a row's length on.  Bounds:
+    those of test_att_location_feature_kernels."""
+    from tensorflow_end2end_speech_recognition_amd import ops
+    from _cpu_ops import _loc_energy
+    off = isinstance(A, str)
+    A = 128 if off else A
+    rng = np.random.RandomState(taps + A)
+    B, T = 5, 200
+    sl = _lane_lengths(rng, T)
+    inside = torch.arange(T).unsqueeze(0) < torch.tensor(sl).long().unsqueeze(1)
+    keys = torch.tensor(rng.randn(T, B, A) * 0.5, dtype=torch.float32) if with_keys else None
+    qz = torch.tensor(rng.randn(B, A) * 0.5, dtype=torch.float32)
+    v = torch.tensor(rng.randn(A), dtype=torch.float32)
+    filt = torch.tensor(rng.randn(taps, 1, 10) * 0.3, dtype=torch.float32)
+    wfil = torch.tensor(rng.randn(10, A) * 0.3, dtype=torch.float32)
+    ap = torch.tensor(rng.rand(B, T), dtype=torch.float32) * inside
+    ap = ap / ap.sum(1, keepdim=True)
+    de = [torch.tensor(rng.randn(B, T), dtype=torch.float32) * inside for _ in range(2)]
+    leaves = [t.double().clone().requires_grad_(True) for t in (ap, filt, wfil, qz, v)]
+    k64 = keys.double().clone().requires_grad_(True) if with_keys else None
+    ref = _loc_energy(leaves[0], leaves[1], leaves[2], k64, leaves[3], leaves[4], T)
+    dev = lambda t: None if t is None else t.to(cuda)
+    qd = _misaligned(qz, cuda) if off else qz.to(cuda)
+    lanes = _loc_lanes(A, aligned=not off)
+    ops.reset_att_path_counts(0)
+    got = ops.att_loc_energy_fwd(dev(ap), dev(filt), dev(wfil), dev(keys), qd, dev(v), T)
+    assert _counted(ops) == {'loc_fwd_' + lanes: 1}
+    assert np.abs(got.cpu().numpy() - ref.detach().numpy()).max() < 3e-5 * max(1.0, float(ref.abs().max()))
+    (ref * (de[0] + de[1]).double()).sum().backward()
+    dw = torch.empty(B, 10, A, device=cuda)
+    df = torch.empty(B, taps, 10, device=cuda)
+    dkeys = torch.zeros(T, B, A, device=cuda) if with_keys else None
+    dq = dv = dap = 0
+    ops.reset_att_path_counts(0)
+    for i in range(2):
+        a, b_, c = ops.att_loc_energy_bwd(dev(de[i]), dev(ap), dev(filt), dev(wfil), dev(keys), qd, dev(v), dw, df,
+                                          accumulate=(i == 1), dkeys=dkeys)
+        dq, dv, dap = dq + a, dv + b_, dap + c
+    assert _counted(ops) == {'loc_bwd_' + lanes: 2}
+    rel = lambda a, b: np.abs(a - b).max() / max(np.abs(b).max(), 1e-30)
+    assert rel(dq.cpu().numpy(), leaves[3].grad.numpy()) < 2e-5
+    assert rel(dv.sum(0).cpu().numpy(), leaves[4].grad.numpy()) < 2e-5
+    assert rel(dw.sum(0).cpu().numpy(), leaves[2].grad.numpy()) < 2e-5
+    assert rel(df.sum(0).cpu().numpy().reshape(taps, 1, 10), leaves[1].grad.numpy()) < 2e-5
+    assert rel(dap.cpu().numpy(), leaves[0].grad.numpy()) < 2e-5
+    if with_keys:
+        assert rel(dkeys.cpu().numpy(), k64.grad.numpy()) < 2e-5
+    assert ops.check_async_errors(0) == 0
+
+
+@pytest.mark.parametrize('E', [64, 256, 320])
+@pytest.mark.parametrize('enc_dtype', ['f32', 'bf16'])
+def test_att_softmax_context_kernels_encoder_widths(cuda, E, enc_dtype):
+    """asr_att_softmax_ctx_fwd / _bwd at encoder widths beside 1024: 64 (a quarter of a 256-thread row), 256 and 320
+    (a partial second trip), fp32 and bf16, T = 200, on the ragged batch full / 1 / 64 / 65 / random; same statement
+    and bounds as test_att_softmax_context_kernels_multi_chunk."""
+    _softmax_context_case(cuda, 200, E, enc_dtype, False, _lane_lengths(np.random.RandomState(E), 200))
 
 
 @pytest.mark.parametrize('att,sig,B,T', [('location', False, 5, 17), ('hybrid', False, 5, 17), ('hybrid', True, 4, 150),
@@ -417,35 +572,136 @@ def test_native_greedy_inference_loop(cuda, att, prev, sig, dtype):
     assert lens[0] == 40 and lens[2] == 1 and 1 <= lens[1] <= 40
 
 
-@pytest.mark.parametrize('case', ['location_zeros_bf16', 'bahdanau_sigmoid_f32', 'location_carry_bf16', 'hybrid_carry_f32',
-                                  'luong_dot_small', 'bahdanau_sigmoid_f32/one_step', 'location_carry_bf16/one_step',
-                                  'location_zeros_bf16/em64', 'hybrid_carry_f32/em64'])
-def test_native_decoder_loop_against_the_step_by_step_statement(cuda, monkeypatch, case):
-    """asr_att_decoder_fwd / _bwd (all To steps from one call, with the fused kernels the loop uses: dctx add inside the
-    4-frame d-alpha kernel, softmax backward folded into the energy backward through partial alpha.dalpha sums, dropout
-    mask and carried-dh add inside the cell backward, length-limited vectorised energy / location kernels with exp2-rcp
-    tanh, skinny MFMA products) against tests/_cpu_ops.py's step-by-step float64 statement of the same loop -- at
-    widths that select those kernels (A = 128 -> 32 lanes x float4 per frame, 2H = 512 bf16 / 256 fp32 -> 16-byte
-    encoder vectors, T = 200 -> four 64-frame chunks), which the small model-level parity tests do not reach.  The last
-    case (A = U = 2H = 64, dot-product scoring without a query FC) takes the general fallbacks instead."""
-    import _cpu_ops as cpu
-    from tensorflow_end2end_speech_recognition_amd import ops
-    one_step = case.endswith('/one_step')                    # a single decoder step: no "next step" operands anywhere
-    em64 = case.endswith('/em64')      # cell input width % 64 == 0: product + cell as ONE launch (asr_lstm_cell_gemm_fwd)
-    case = case.split('/')[0]
-    cfg = dict(location_zeros_bf16=dict(keys=False, carry=0, sig=False, bf16=True, A=128, E2=512, mode=0, hasq=1, taps=0),
-               bahdanau_sigmoid_f32=dict(keys=True, carry=0, sig=True, bf16=False, A=128, E2=256, mode=0, hasq=1, taps=0),
-               location_carry_bf16=dict(keys=False, carry=1, sig=False, bf16=True, A=128, E2=512, mode=0, hasq=1, taps=201),
-               hybrid_carry_f32=dict(keys=True, carry=1, sig=True, bf16=False, A=32, E2=256, mode=0, hasq=1, taps=200),
-               luong_dot_small=dict(keys=True, carry=0, sig=False, bf16=False, A=64, E2=64, mode=1, hasq=0, taps=0))[case]
-    rng = np.random.RandomState(len(case))
-    B, T, To, Em = 3, 200, (1 if one_step else 5), (64 if em64 else 8)
-    A, E2 = cfg['A'], cfg['E2']
-    U = A if not cfg['hasq'] else 64
+# The decoder-loop matrix.  Per case: the scoring configuration, the shape (defaults B = 3, T = 200, U = 64, To = 5,
+# Em = 8) and `path`, the kernels every step of the case is MEANT to run -- asserted through ops.att_path_counts:
+#   fwd   'fused' (att_fused_fwd_kernel + combine) | '4launch'        cell  'bf16' | 'f32img' | 'gemm' (product, then cell)
+#   bwd   'fused_q' (att_dq_cell_bwd_kernel) | 'unfused'              bwd_cell  'bf16' (asr_lstm_cell_gemm_bwd_h) | 'gemm'
+#   fold  softmax backward inside the energy backward                 lanes  lane shape of the energy / location kernels
+# The first five (and their /one_step and /em64 forms) are the cases this test has had from the start.
+_P = lambda fwd, cell, bwd, bwd_cell, fold, lanes: dict(fwd=fwd, cell=cell, bwd=bwd, bwd_cell=bwd_cell, fold=fold, lanes=lanes)
+_LOOP_CASES = dict(
+    location_zeros_bf16=dict(keys=False, carry=0, sig=False, bf16=True, A=128, E2=512, mode=0, hasq=1, taps=0,
+                             path=_P('fused', 'gemm', 'fused_q', 'gemm', True, '32')),
+    bahdanau_sigmoid_f32=dict(keys=True, carry=0, sig=True, bf16=False, A=128, E2=256, mode=0, hasq=1, taps=0,
+                              path=_P('4launch', 'gemm', 'fused_q', 'gemm', True, '32')),
+    location_carry_bf16=dict(keys=False, carry=1, sig=False, bf16=True, A=128, E2=512, mode=0, hasq=1, taps=201,
+                             path=_P('4launch', 'gemm', 'unfused', 'gemm', False, '32')),
+    hybrid_carry_f32=dict(keys=True, carry=1, sig=True, bf16=False, A=32, E2=256, mode=0, hasq=1, taps=200,
+                          path=_P('4launch', 'gemm', 'unfused', 'gemm', False, '16')),
+    # (2H = 64 fp32 is below the 16-byte-vector context / d-alpha kernels: general ones, hence no fold)
+    luong_dot_small=dict(keys=True, carry=0, sig=False, bf16=False, A=64, E2=64, mode=1, hasq=0, taps=0,
+                         path=_P('4launch', 'gemm', 'unfused', 'gemm', False, '16')),
+    # ---- att_dq_cell_bwd_kernel's wave layouts (wpu = 8 / A x 64 waves per 64-column slice) and chunk-loop trips
+    # wpu = 8; fused forward <16,1,float>; U not a multiple of 64 (three column blocks)
+    A64=dict(keys=False, carry=0, sig=False, bf16=False, A=64, E2=256, mode=0, hasq=1, taps=0, U=48,
+             path=_P('fused', 'gemm', 'fused_q', 'gemm', True, '16')),
+    # wpu = 2; fused forward <64,1,bf16>.  (No fold: the 16-byte-vector d-alpha kernel wants 2H % 512 == 0 in bf16.)
+    A256=dict(keys=True, carry=0, sig=False, bf16=True, A=256, E2=256, mode=0, hasq=1, taps=0, B=5, T=300,
+              path=_P('fused', 'gemm', 'fused_q', 'gemm', False, '64')),
+    # wpu = 1: 10 chunks = a second trip of the chunk loop with a partial tail; <64,2,float>
+    A512_long=dict(keys=True, carry=0, sig=False, bf16=False, A=512, E2=512, mode=0, hasq=1, taps=0, T=600,
+                   path=_P('fused', 'gemm', 'fused_q', 'gemm', True, '64x2')),
+    # wpu = 4: 33 chunks = a second trip of one chunk; a single column block
+    A128_chunks33=dict(keys=False, carry=0, sig=False, bf16=True, A=128, E2=256, mode=0, hasq=1, taps=0, U=16, B=2, T=2110,
+                       path=_P('fused', 'gemm', 'fused_q', 'gemm', False, '32')),
+    # ---- batch: a second row group with clamped rows in the backward kernel, the second MFMA row tile of the one-launch
+    # cell (17, 32), and past asr_lstm_cell_gemm_ok's B <= 32 the product + cell pair while fused_q stays on (35)
+    B17=dict(keys=True, carry=0, sig=False, bf16=False, A=128, E2=256, mode=0, hasq=1, taps=0, B=17, T=130, Em=64,
+             path=_P('fused', 'f32img', 'fused_q', 'gemm', True, '32')),
+    B32=dict(keys=True, carry=0, sig=False, bf16=False, A=128, E2=256, mode=0, hasq=1, taps=0, B=32, T=130, Em=64,
+             path=_P('fused', 'f32img', 'fused_q', 'gemm', True, '32')),
+    B35=dict(keys=True, carry=0, sig=False, bf16=False, A=128, E2=256, mode=0, hasq=1, taps=0, B=35, T=130, Em=64,
+             path=_P('fused', 'gemm', 'fused_q', 'gemm', True, '32')),
+    # the benchmarked decoder width: 34 workgroups x 2 row groups in the backward kernel
+    cfgD_narrow=dict(keys=True, carry=0, sig=False, bf16=True, A=128, E2=512, mode=0, hasq=1, taps=0, B=32, U=512, Em=64, To=3,
+                     path=_P('fused', 'f32img', 'fused_q', 'gemm', True, '32')),
+    # U % 16 != 0: the fp32 image although the model is bf16 (40 + 512 + 24 = 9 x 64 input columns), no fused_q
+    cell_bf16_U24=dict(keys=False, carry=0, sig=False, bf16=True, A=128, E2=512, mode=0, hasq=1, taps=0, U=24, Em=40,
+                       cell_bf16=True, path=_P('fused', 'f32img', 'unfused', 'gemm', True, '32')),
+    # fused_q off (A = 36), four-launch forward (2H = 64), vectorised 16-lane energies with idle tail lanes
+    A36_general_q=dict(keys=True, carry=0, sig=False, bf16=False, A=36, E2=64, mode=0, hasq=1, taps=0,
+                       path=_P('4launch', 'gemm', 'unfused', 'gemm', False, '16')),
+    # A % 4 != 0: everything general
+    A130=dict(keys=True, carry=0, sig=False, bf16=False, A=130, E2=64, mode=0, hasq=1, taps=0,
+              path=_P('4launch', 'gemm', 'unfused', 'gemm', False, 'general')),
+    # T > 64 chunks: the fused forward is refused; 65 chunks = a second trip at wpu = 8 in the backward kernel
+    T4100=dict(keys=False, carry=0, sig=False, bf16=False, A=64, E2=256, mode=0, hasq=1, taps=0, B=1, T=4100, To=2,
+               path=_P('4launch', 'gemm', 'fused_q', 'gemm', True, '16')),
+    # sigmoid smoothing refuses the fused forward, the fold stays on
+    sigmoid_E256=dict(keys=False, carry=0, sig=True, bf16=False, A=128, E2=256, mode=0, hasq=1, taps=0, Em=64,
+                      path=_P('4launch', 'f32img', 'fused_q', 'gemm', True, '32')),
+    # W_q as a column slice of a [U, A + 1] array: rows 4 bytes off 16-byte alignment refuse fused_q
+    unaligned_Wq=dict(keys=False, carry=0, sig=False, bf16=False, A=128, E2=256, mode=0, hasq=1, taps=0, wq_slice=True,
+                      path=_P('fused', 'gemm', 'unfused', 'gemm', True, '32')))
+_LOOP_ORIGINAL = ['location_zeros_bf16', 'bahdanau_sigmoid_f32', 'location_carry_bf16', 'hybrid_carry_f32',
+                  'luong_dot_small', 'bahdanau_sigmoid_f32/one_step', 'location_carry_bf16/one_step',
+                  'location_zeros_bf16/em64', 'hybrid_carry_f32/em64']
+_LOOP_NEW = ['A64', 'A256', 'A512_long', 'A128_chunks33', 'B17', 'B32', 'B35', 'cfgD_narrow',
+             'cell_bf16/location_zeros_bf16/em64', 'cell_bf16/location_carry_bf16/em64', 'cell_bf16/B17', 'cell_bf16_U24',
+             'A36_general_q', 'A130', 'T4100', 'sigmoid_E256', 'unaligned_Wq', 'B17/one_step',
+             'cell_bf16/location_zeros_bf16/em64/one_step']
+
+
+def _loop_config(case):
+    """case = ['cell_bf16/'] name ['/em64'] ['/one_step'] -> the configuration dict of the loop test (B, T, U, To, Em,
+    cell_bf16, seq_len, live and the intended path included)."""
+    parts = case.split('/')
+    cell_bf16 = parts[0] == 'cell_bf16'
+    name = parts[1] if cell_bf16 else parts[0]
+    cfg = dict(_LOOP_CASES[name])
+    cfg['path'] = dict(cfg['path'])
+    cfg.update(name=name, original=case in _LOOP_ORIGINAL, one_step='one_step' in parts, em64='em64' in parts)
+    cfg['cell_bf16'] = bool(cfg.get('cell_bf16') or cell_bf16)
+    cfg['Em'] = 64 if cfg['em64'] else cfg.get('Em', 8)
+    cfg['To'] = 1 if cfg['one_step'] else cfg.get('To', 5)
+    cfg.setdefault('B', 3)
+    cfg.setdefault('T', 200)
+    cfg.setdefault('U', cfg['A'] if not cfg['hasq'] else 64)
+    B, T, To = cfg['B'], cfg['T'], cfg['To']
+    if cfg['em64'] and cfg['path']['cell'] == 'gemm':
+        cfg['path']['cell'] = 'f32img'                       # (Em = 64 makes the first cases' input width a multiple of 64)
+    if cell_bf16:
+        cfg['path'].update(cell='bf16', bwd_cell='bf16')
+    if cfg['original']:
+        cfg['seq_len'] = [T, 77, 130]
+        cfg['live'] = [[1, 1, 1], [1, 1, 1], [1, 0, 1], [1, 0, 1], [1, 0, 0]][:To]
+    else:
+        # a full row, a row that ends on a chunk boundary, a one-frame row, the rest anywhere from a third of T on
+        sl = np.random.RandomState(B + T).randint(max(1, T // 3), T + 1, size=B)
+        sl[0] = T
+        if B >= 2:
+            sl[1] = 128 if T > 128 else 64
+        if B >= 3:
+            sl[2] = 1
+        cfg['seq_len'] = [int(x) for x in sl]
+        # row b finishes at step b % (To + 1): live there for the last time (so step 0 has every row, and with B <= To
+        # the last steps have none)
+        cfg['live'] = [[1.0 if k <= b % (To + 1) else 0.0 for b in range(B)] for k in range(To)]
+    return cfg
+
+
+def _loop_expected_counts(cfg):
+    """The path counters after one forward / one backward loop of To steps on the intended path."""
+    p, To = cfg['path'], cfg['To']
+    fwd = {'fwd_step_' + p['fwd']: To, 'fwd_cell_' + p['cell']: To}
+    if p['fwd'] == 'fused':
+        fwd['fused_fwd_' + p['lanes']] = To
+    else:
+        fwd[('loc_fwd_' if cfg['carry'] else 'energy_fwd_') + p['lanes']] = To
+    bwd = {'bwd_step_' + p['bwd']: To, 'bwd_cell_' + p['bwd_cell']: To,
+           'bwd_softmax_' + ('folded' if p['fold'] else 'separate'): To,
+           ('loc_bwd_' if cfg['carry'] else 'energy_bwd_') + p['lanes']: To}
+    return fwd, bwd
+
+
+def _loop_arrays(cfg):
+    """The loop's operands on the CPU (fp32 tensors; ints / floats as they are) and the shapes of the backward's outputs."""
+    rng = np.random.RandomState(len(cfg['name']))
+    B, T, To, Em, A, E2, U = cfg['B'], cfg['T'], cfg['To'], cfg['Em'], cfg['A'], cfg['E2'], cfg['U']
     Din = Em + E2 + U
     f = lambda *s, sc=1.0: torch.tensor(rng.randn(*s) * sc, dtype=torch.float32)
-    seq_len = torch.tensor([T, 77, 130], dtype=torch.int32)
-    live = torch.tensor([[1, 1, 1], [1, 1, 1], [1, 0, 1], [1, 0, 1], [1, 0, 0]], dtype=torch.float32)[:To].contiguous()   # [To,B]
+    seq_len = torch.tensor(cfg['seq_len'], dtype=torch.int32)
+    live = torch.tensor(cfg['live'], dtype=torch.float32).contiguous()   # [To,B]
     enc = f(T, B, E2, sc=0.5)
     enc = enc * (torch.arange(T).view(T, 1, 1) < seq_len.view(1, B, 1))
     if cfg['bf16']:
@@ -456,7 +712,7 @@ def test_native_decoder_loop_against_the_step_by_step_statement(cuda, monkeypatc
              W_cell=f(Din, 4 * U, sc=0.08), b_cell=f(4 * U, sc=0.1), peep=f(3, U, sc=0.1),
              W_q=f(U, A, sc=0.1) if cfg['hasq'] else None, b_q=f(A, sc=0.1) if (cfg['hasq'] and cfg['carry']) else None,
              v=f(A, sc=0.5) if cfg['mode'] == 0 else None,
-             keys=(enc.float() if case == 'luong_dot_small' else f(T, B, A, sc=0.5)) if cfg['keys'] else None,
+             keys=(enc.float() if cfg['name'] == 'luong_dot_small' else f(T, B, A, sc=0.5)) if cfg['keys'] else None,
              enc=enc, seq_len=seq_len,
              filt=f(cfg['taps'], 1, 10, sc=0.3) if cfg['carry'] else None, wfil=f(10, A, sc=0.3) if cfg['carry'] else None,
              alpha_zero=torch.zeros(B, T) if cfg['carry'] else None, live=live,
@@ -469,43 +725,160 @@ def test_native_decoder_loop_against_the_step_by_step_statement(cuda, monkeypatc
     a['h_all'][0] = f(B, U, sc=0.3)
     a['dec_in'][0, :, Em:Em + E2] = 0.0                      # no context before the first step
     a['dec_in'][0, :, Em + E2:] = a['h_all'][0]
+    if cfg['cell_bf16']:
+        # both sides get weights that ARE bf16 values: the device's rounding into its bf16 images is then the identity
+        # and the float64 statement applies unchanged
+        a['W_cell'] = a['W_cell'].to(torch.bfloat16).float()
+        a['cell_bf16'] = True
     bwd_in = dict(dav_cell=f(To, B, U, sc=0.3), dav_ctx=f(To, B, E2, sc=0.3))
     bwd_out = dict(dctx_all=(To, B, E2), dpre_all=(To, B, 4 * U), dqz_all=(To, B, A),
                    dv_all=(To, B, A) if cfg['mode'] == 0 else None, dpeep_all=(To, B, 3 * U), d_in_all=(To, B, Din),
                    dkeys=(T, B, A) if cfg['keys'] else None, dwfil_rows=(B, 10, A) if cfg['carry'] else None,
                    dfilt_rows=(B, cfg['taps'], 10) if cfg['carry'] else None, dc0=(B, U), dh0=(B, U))
+    return a, bwd_in, bwd_out
 
-    def clone_to(dev):
-        d = {k: (v.clone().to(dev) if torch.is_tensor(v) else v) for k, v in a.items()}
-        d.update({k: v.clone().to(dev) for k, v in bwd_in.items()})
-        d.update({k: (torch.zeros(s, device=dev) if s is not None else None) for k, s in bwd_out.items()})
-        return d
 
+def _loop_clone(cfg, a, bwd_in, bwd_out, dev):
+    d = {k: (v.clone().to(dev) if torch.is_tensor(v) else v) for k, v in a.items()}
+    d.update({k: v.clone().to(dev) for k, v in bwd_in.items()})
+    d.update({k: (torch.zeros(s, device=dev) if s is not None else None) for k, s in bwd_out.items()})
+    if cfg.get('wq_slice'):            # the same values as the first A columns of a [U, A + 1] array: row stride A + 1
+        wide = torch.zeros(cfg['U'], cfg['A'] + 1, device=dev)
+        wide[:, :cfg['A']] = d['W_q']
+        d['W_q'] = wide[:, :cfg['A']]
+        assert d['W_q'].stride(0) % 4 != 0
+    return d
+
+
+_LOOP_FWD = ('alpha_all', 'av_in', 'dec_in', 'c_all', 'h_all', 'qz_all', 'gates_all', 'craw_all')
+
+
+@pytest.mark.parametrize('case', _LOOP_ORIGINAL + _LOOP_NEW)
+def test_native_decoder_loop_against_the_step_by_step_statement(cuda, monkeypatch, case):
+    """asr_att_decoder_fwd / _bwd (all To steps from one call, with the fused kernels the loop uses: dctx add inside the
+    4-frame d-alpha kernel, softmax backward folded into the energy backward through partial alpha.dalpha sums, dropout
+    mask and carried-dh add inside the cell backward, length-limited vectorised energy / location kernels with exp2-rcp
+    tanh, skinny MFMA products) against tests/_cpu_ops.py's step-by-step float64 statement of the same loop -- at
+    widths that select those kernels (A = 128 -> 32 lanes x float4 per frame, 2H = 512 bf16 / 256 fp32 -> 16-byte
+    encoder vectors, T = 200 -> four 64-frame chunks), which the small model-level parity tests do not reach.  The
+    luong_dot_small case (A = U = 2H = 64, dot-product scoring without a query FC) takes the general context kernels.
+    The cases behind the first nine walk the loop's dispatch (_LOOP_CASES says what each one reaches): every layout of
+    att_dq_cell_bwd_kernel, both trips of its chunk loop, B past one row group and past the one-launch cell, the bf16
+    cell-weight images inside both loops, every refusal of the fused forward step and of fused_q.  Every case asserts the
+    kernels it ran through ops.att_path_counts."""
+    import _cpu_ops as cpu
+    from tensorflow_end2end_speech_recognition_amd import ops
+    cfg = _loop_config(case)
+    em64 = cfg['em64'] and cfg['original']   # cell input width % 64 == 0: product + cell as ONE launch (asr_lstm_cell_gemm_fwd)
+    a, bwd_in, bwd_out = _loop_arrays(cfg)
+    clone_to = lambda dev: _loop_clone(cfg, a, bwd_in, bwd_out, dev)
+    want_fwd, want_bwd = _loop_expected_counts(cfg)
     ref, got = clone_to('cpu'), clone_to(cuda)
     cpu._att_decoder_fwd(ref)
+    ops.reset_att_path_counts(0)
     ops.att_decoder_fwd(got)
-    assert (got.get('W_cell_il') is not None) == em64
+    assert _counted(ops) == want_fwd
+    assert (got.get('W_cell_il') is not None) == (cfg['path']['cell'] == 'f32img')
+    assert (got.get('W_cell_h') is not None) == (cfg['path']['cell'] == 'bf16')
     if em64:       # the one-launch product + cell against the two launches it replaces: the whole loop bit for bit
         two = clone_to(cuda)
         monkeypatch.setattr(ops, 'FUSED_CELL_GEMM', False)
         ops.att_decoder_fwd(two)
+        monkeypatch.setattr(ops, 'FUSED_CELL_GEMM', True)
         assert two.get('W_cell_il') is None
-        for name in ('alpha_all', 'av_in', 'dec_in', 'c_all', 'h_all', 'qz_all', 'gates_all', 'craw_all'):
+        for name in _LOOP_FWD:
             assert torch.equal(got[name], two[name]), name
     # relative to the array's largest entry, with a floor: without keys and without carried location features every frame
     # has the same energy, so dqz / dv are (sum_t denergy) x const = rounding noise around zero (1e-7) on both sides
     rel = lambda x, y: float(np.abs(x.cpu().double().numpy() - y.double().numpy()).max() / max(np.abs(y.double().numpy()).max(), 1e-2))
-    for name in ('alpha_all', 'av_in', 'dec_in', 'c_all', 'h_all', 'qz_all', 'gates_all', 'craw_all') + (('snorm_all',) if cfg['sig'] else ()):
-        assert rel(got[name], ref[name]) < 2e-5, (name, rel(got[name], ref[name]))
+    for name in _LOOP_FWD + (('snorm_all',) if cfg['sig'] else ()):
+        err = rel(got[name], ref[name])
+        print('%s fwd %s %.3g' % (case, name, err))
+        assert err < 2e-5, (name, err)
     # the backward of both sides starts from the SAME saved forward (the reference's), so the comparison is per kernel
-    for name in ('alpha_all', 'av_in', 'dec_in', 'c_all', 'h_all', 'qz_all', 'gates_all', 'craw_all', 'snorm_all'):
+    for name in _LOOP_FWD + ('snorm_all',):
         if ref.get(name) is not None:
             got[name].copy_(ref[name].to(cuda))
     cpu._att_decoder_bwd(ref)
+    ops.reset_att_path_counts(0)
     ops.att_decoder_bwd(got)
+    assert _counted(ops) == want_bwd
     for name, shape in bwd_out.items():
         if shape is not None:
-            assert rel(got[name], ref[name]) < 5e-5, (name, rel(got[name], ref[name]))
+            err = rel(got[name], ref[name])
+            print('%s bwd %s %.3g' % (case, name, err))
+            assert err < 5e-5, (name, err)
+    assert ops.check_async_errors(0) == 0
+
+
+# the greedy loop at the widths of the one-launch cell: seed under which the float64 statement's top-2 logit margin
+# is above 1e-3 at every (step, row) -- asserted below, so the exact id comparison cannot be excused by a near-tie
+_INFER_SEED = 5
+
+
+def _infer_arrays(cell_bf16, seed=_INFER_SEED):
+    rng = np.random.RandomState(seed)
+    B, T, To, Em, E2, U, A, C2 = 32, 130, 12, 64, 256, 64, 128, 40
+    Din = Em + E2 + U
+    f = lambda *s, sc=1.0: torch.tensor(rng.randn(*s) * sc, dtype=torch.float32)
+    seq_len = torch.tensor(rng.randint(T // 3, T + 1, size=B), dtype=torch.int32)
+    seq_len[0], seq_len[1], seq_len[2] = T, 128, 1
+    enc = f(T, B, E2, sc=0.5) * (torch.arange(T).view(T, 1, 1) < seq_len.view(1, B, 1))
+    W_cell = f(Din, 4 * U, sc=0.08)
+    emb = f(C2, Em, sc=0.5)
+    live = torch.zeros(To + 1, B)
+    live[0] = 1.0
+    a = dict(To=To, B=B, T=T, U=U, Em=Em, E2=E2, A=A, att_mode=0, has_query_fc=1, carry_alpha=0, taps=0, enc_dtype=0,
+             forget_bias=1.0, cell_clip=3.0, sharpening=1.5,
+             W_cell=W_cell.to(torch.bfloat16).float() if cell_bf16 else W_cell, b_cell=f(4 * U, sc=0.1),
+             peep=f(3, U, sc=0.1), W_q=f(U, A, sc=0.1), v=f(A, sc=0.5), keys=f(T, B, A, sc=0.5), enc=enc, seq_len=seq_len,
+             live=live, dec_in=torch.zeros(To, B, Din), av_in=torch.zeros(To, B, U + E2), alpha_all=torch.zeros(To, B, T),
+             gates_all=torch.zeros(To, B, 4 * U), craw_all=torch.zeros(To, B, U), c_all=torch.zeros(To + 1, B, U),
+             h_all=torch.zeros(To + 1, B, U), qz_all=torch.zeros(To, B, A))
+    if cell_bf16:
+        a['cell_bf16'] = True
+    a['c_all'][0] = f(B, U, sc=0.3)
+    a['h_all'][0] = f(B, U, sc=0.3)
+    a['dec_in'][0, :, :Em] = emb[C2 - 2]                     # <SOS>
+    a['dec_in'][0, :, Em + E2:] = a['h_all'][0]
+    head = dict(W_av=f(U + E2, U, sc=0.15), W_out=f(U, C2, sc=0.6), b_out=f(C2, sc=0.3), embedding=emb)
+    head['b_out'][C2 - 1] = 2.0                              # <EOS>: rows finish at different steps
+    return a, head, C2 - 1
+
+
+@pytest.mark.parametrize('cell_bf16', [False, True])
+def test_native_inference_loop_at_the_fused_cell_widths(cuda, cell_bf16):
+    """asr_att_decoder_infer against _cpu_ops._att_decoder_infer at B = 32, Em = 64, 2H = 256, U = 64 (384 input
+    columns: product + cell in one launch, two MFMA row tiles), A = 128, 12 steps, 40 classes, on the fp32 image and on
+    the bf16 images (weights that are bf16 values on both sides).  The end-of-sequence bias makes rows finish at
+    different steps.  Logits and attentional vectors within the loop test's forward bound; ids, finished flags and live
+    counts exactly -- legitimate because the statement's top-2 logit margin is above 1e-3 everywhere (asserted first)."""
+    import _cpu_ops as cpu
+    from tensorflow_end2end_speech_recognition_amd import ops
+    a, head, eos = _infer_arrays(cell_bf16)
+    To, B = a['To'], a['B']
+    dev = lambda d: {k: (v.clone().to(cuda) if torch.is_tensor(v) else v) for k, v in d.items()}
+    cl = lambda d: {k: (v.clone() if torch.is_tensor(v) else v) for k, v in d.items()}
+    ra = cl(a)
+    ref = cpu._att_decoder_infer(ra, head['W_av'], head['W_out'], head['b_out'], head['embedding'], eos, B, check_every=0)
+    top2 = ref['logits'].double().topk(2, dim=2).values
+    assert float((top2[..., 0] - top2[..., 1]).min()) > 1e-3
+    fin = (ref['live'][:To].sum(0)).numpy()                  # steps each row was live for
+    assert len(set(fin.tolist())) >= 4 and fin.min() < To and ref['steps_issued'] == To
+    ga, gh = dev(a), dev(head)
+    ops.reset_att_path_counts(0)
+    got = ops.att_decoder_infer(ga, gh['W_av'], gh['W_out'], gh['b_out'], gh['embedding'], eos, B, check_every=0)
+    torch.cuda.synchronize()
+    assert got['steps_issued'] == To
+    assert _counted(ops) == {'fwd_step_fused': To, 'fused_fwd_32': To, ('fwd_cell_bf16' if cell_bf16 else 'fwd_cell_f32img'): To}
+    rel = lambda x, y: float(np.abs(x.cpu().double().numpy() - y.double().numpy()).max() / max(np.abs(y.double().numpy()).max(), 1e-2))
+    for name in ('logits', 'av'):
+        err = rel(got[name], ref[name])
+        print('infer %s %s %.3g' % ('bf16' if cell_bf16 else 'f32', name, err))
+        assert err < 2e-5, (name, err)
+    assert torch.equal(got['ids'].cpu(), ref['ids'])
+    assert torch.equal(got['live'].cpu(), ref['live'])
+    assert torch.equal(got['live_count'].cpu(), ref['live_count'])
     assert ops.check_async_errors(0) == 0
 
 
