@@ -479,6 +479,44 @@ enum {
 };
 int asr_att_path_counts(asr_handle* h, unsigned long long* out, int n);
 int asr_reset_att_path_counts(asr_handle* h);
+/* The same for the 3x3 convolution entry points (asr_conv3x3_fwd / _fwd_drop / _bwd_data / _bwd_data_relu / _bwd_weight /
+ * _bwd_weight_bias): which kernel instantiation each launch on this handle was, since the last reset.  Host integers
+ * bumped at the launch site; out[i], i < min(n, ASR_CONVP_N), in the order of the enum below, the rest of `out` zeroed.
+ * A forward or data-gradient launch bumps its form and the channel pair of its product (the data gradient of a Cin ->
+ * Cout layer is a Cout -> Cin product); an image-resident one also the instantiated MAXV (staged vectors per thread),
+ * the compile-time epilogue ACT, the number of LDS image buffers and STREAM / W8 when that variant ran; a tiled one the
+ * column width of its conv_nt_kernel tiles.  A weight-gradient call bumps exactly one of the WGRAD_IMG_* / WGRAD_TR_* /
+ * WGRAD_COLPIX forms, and for the image-resident forms SPLIT (two waves per input-channel group), BIAS_IN_KERNEL (bias
+ * gradient from the staged dY) and, with BIAS_IN_KERNEL, the reduce kernel that summed the slabs. */
+enum {
+  ASR_CONVP_FORM_IMG = 0,         /* conv3x3_img_kernel: the image with its border in LDS, weights in registers */
+  ASR_CONVP_FORM_TILED,           /* conv_nt_kernel on the 3x3 tap geometry */
+  ASR_CONVP_PAIR_64_64, ASR_CONVP_PAIR_64_128, ASR_CONVP_PAIR_128_128, ASR_CONVP_PAIR_128_64,
+  ASR_CONVP_PAIR_OTHER,           /* any other channel pair of the product (always tiled) */
+  ASR_CONVP_MAXV_2, ASR_CONVP_MAXV_4, ASR_CONVP_MAXV_8, ASR_CONVP_MAXV_14, ASR_CONVP_MAXV_16,
+  ASR_CONVP_ACT_0,                /* no epilogue (and every fp32 data gradient) */
+  ASR_CONVP_ACT_1,                /* ReLU */
+  ASR_CONVP_ACT_2,                /* data gradient gated by the layer below, uniform scale (use_drop 0 / 2) */
+  ASR_CONVP_ACT_3,                /* forward ReLU + dropout */
+  ASR_CONVP_ACT_4,                /* gated data gradient with the Philox mask (use_drop 1) */
+  ASR_CONVP_NBUF_1, ASR_CONVP_NBUF_2,
+  ASR_CONVP_STREAM,               /* the next image streamed into the second buffer two vectors per pixel tile */
+  ASR_CONVP_W8,                   /* eight waves (forward ReLU + dropout of small 64-channel images) */
+  ASR_CONVP_TILED_BN128, ASR_CONVP_TILED_BN64,
+  ASR_CONVP_WGRAD_IMG_64_SMALL,   /* conv3x3_wgrad_img_kernel, 64 input channels, at most 4 staged vectors per thread */
+  ASR_CONVP_WGRAD_IMG_64_LARGE,   /* ... 5 to 14 */
+  ASR_CONVP_WGRAD_IMG_128,        /* ... 128 input channels */
+  ASR_CONVP_WGRAD_SPLIT,
+  ASR_CONVP_WGRAD_BIAS_IN_KERNEL,
+  ASR_CONVP_WGRAD_REDUCE_VEC,     /* wgrad_img_reduce_kernel<1>: dw 16-byte aligned */
+  ASR_CONVP_WGRAD_REDUCE_SCALAR,  /* wgrad_img_reduce_kernel<0> */
+  ASR_CONVP_WGRAD_TR_128,         /* conv3x3_wgrad_tr_kernel<128> */
+  ASR_CONVP_WGRAD_TR_64,          /* conv3x3_wgrad_tr_kernel<64> (ASR_CONV_WGRAD_BN64=1) */
+  ASR_CONVP_WGRAD_COLPIX,         /* conv_wgrad_kernel on the [column][pixel] LDS image (ASR_CONV_WGRAD_TR=0) */
+  ASR_CONVP_N
+};
+int asr_conv_path_counts(asr_handle* h, unsigned long long* out, int n);
+int asr_reset_conv_path_counts(asr_handle* h);
 /* TEST ONLY (process-wide): the number of co-resident workgroups a cluster launch may use; 0 (default) = the device's CU
  * count.  Any other value is clamped to [0, CU count] where it is used, so it can only LOWER the grid of a launch -- the
  * tests exercise tile groups at B = 80 - 272 with it.  A plain process-wide int, not thread-safe: set it while no

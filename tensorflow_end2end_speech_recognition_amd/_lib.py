@@ -103,6 +103,8 @@ SIGNATURES = {
     'asr_reset_recurrence_path_counts': (_i, [_vp]),
     'asr_att_path_counts': (_i, [_vp, C.POINTER(C.c_ulonglong), _i]),
     'asr_reset_att_path_counts': (_i, [_vp]),
+    'asr_conv_path_counts': (_i, [_vp, C.POINTER(C.c_ulonglong), _i]),
+    'asr_reset_conv_path_counts': (_i, [_vp]),
     'asr_debug_set_cluster_cu_budget': (_i, [_i]),
     'asr_debug_placement': (_i, [_vp, _vp, _i, _i, _vp]),
     'asr_debug_poison_lds': (_i, [_vp, _vp]),

@@ -17,6 +17,7 @@
 // s_tap = (tap / KW - OY, tap % KW - OX); 3x5: row (frequency) offset -1..1, column (time) offset -2..2.
 #include "conv_common.h"
 #include <limits.h>
+#include <type_traits>
 
 namespace {
 
@@ -383,6 +384,11 @@ int asr_conv_nt(asr_handle* h, const char* what, const void* x, int N, int H, in
   if (out_f32) { if (bn128) ASR_CNT(float, 128); else ASR_CNT(float, 64); }
   else { if (bn128) ASR_CNT(bf16_t, 128); else ASR_CNT(bf16_t, 64); }
 #undef ASR_CNT
+  if constexpr (std::is_same<TP, Taps33>::value) {         // asr_conv_path_counts: the 3x3 entry points' tiled launches
+    h->conv_counts[ASR_CONVP_FORM_TILED] += 1;
+    h->conv_counts[asr_conv_pair_counter(Cin, Cout)] += 1;
+    h->conv_counts[bn128 ? ASR_CONVP_TILED_BN128 : ASR_CONVP_TILED_BN64] += 1;
+  }
   ASR_CHECK_LAUNCH(h, what);
   return ASR_OK;
 }

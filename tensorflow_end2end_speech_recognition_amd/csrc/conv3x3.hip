@@ -683,6 +683,26 @@ extern "C" int asr_debug_conv_cycles(unsigned long long* out, int n) {
   if (!g_convdbg_host || n > 64 * 4 * 8) return -1;
   return hipMemcpy(out, g_convdbg_host, n * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess ? 0 : -3;
 }
+// asr_conv_path_counts: the channel pair of a forward / data-gradient product (conv.hip's tiled launcher counts its own)
+int asr_conv_pair_counter(int Cin, int Cout) {
+  if (Cin == 64 && Cout == 64) return ASR_CONVP_PAIR_64_64;
+  if (Cin == 64 && Cout == 128) return ASR_CONVP_PAIR_64_128;
+  if (Cin == 128 && Cout == 128) return ASR_CONVP_PAIR_128_128;
+  if (Cin == 128 && Cout == 64) return ASR_CONVP_PAIR_128_64;
+  return ASR_CONVP_PAIR_OTHER;
+}
+// ... and one image-resident launch: the template arguments of the instantiation that was launched
+static void conv_count_img(asr_handle* h, int ci, int co, int maxv, int act, int nbuf, bool stream, bool w8) {
+  unsigned long long* c = h->conv_counts;
+  c[ASR_CONVP_FORM_IMG] += 1;
+  c[asr_conv_pair_counter(ci, co)] += 1;
+  c[maxv == 2 ? ASR_CONVP_MAXV_2 : maxv == 4 ? ASR_CONVP_MAXV_4 : maxv == 8 ? ASR_CONVP_MAXV_8
+    : maxv == 14 ? ASR_CONVP_MAXV_14 : ASR_CONVP_MAXV_16] += 1;
+  c[ASR_CONVP_ACT_0 + act] += 1;
+  c[nbuf == 1 ? ASR_CONVP_NBUF_1 : ASR_CONVP_NBUF_2] += 1;
+  if (stream) c[ASR_CONVP_STREAM] += 1;
+  if (w8) c[ASR_CONVP_W8] += 1;
+}
 template <typename TO>
 static int conv3x3_launch(asr_handle* h, const void* x, int Nimg, int H, int W, int Cin, const void* wt,
                           const float* bias, int Cout, int act, void* out, hipStream_t st,
@@ -717,8 +737,10 @@ static int conv3x3_launch(asr_handle* h, const void* x, int Nimg, int H, int W, 
     /* measured (profiles/r05_conv_stream.md): streaming wins 5 % for 64 -> 64 without the gate loads, loses 3 - 12 % elsewhere */ \
     constexpr bool SOK = CI == 64 && CO == 64 && (AC == 1 || AC == 3);                                               \
     auto k = conv3x3_img_kernel<TO, CI, CO, MV, AC, false>;                                                          \
-    if constexpr (SOK) { if (strm) k = conv3x3_img_kernel<TO, CI, CO, MV, AC, false, 4, true>; }                     \
-    if constexpr (AC == 1) { if (dbg_on) k = conv3x3_img_kernel<TO, CI, CO, MV, AC, true>; }                         \
+    bool streamed = false;                                                                                           \
+    if constexpr (SOK) { if (strm) { k = conv3x3_img_kernel<TO, CI, CO, MV, AC, false, 4, true>; streamed = true; } } \
+    if constexpr (AC == 1) { if (dbg_on) { k = conv3x3_img_kernel<TO, CI, CO, MV, AC, true>; streamed = false; } }   \
+    conv_count_img(h, CI, CO, MV, AC, nbuf, streamed, false);                                                        \
     (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                 \
     hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, st, Nimg, H, W, (const bf16_t*)x, (const bf16_t*)wt, (TO*)out, \
                        bias, gate, nbuf);                                                                            \
@@ -726,6 +748,7 @@ static int conv3x3_launch(asr_handle* h, const void* x, int Nimg, int H, int W, 
 #define ASR_CONV_IMG8_A(CI, CO, MV, AC)                                                                              \
   do {                                                                                                               \
     auto k = conv3x3_img_kernel<TO, CI, CO, MV, AC, false, 8>;                                                       \
+    conv_count_img(h, CI, CO, MV, AC, nbuf, false, true);                                                            \
     (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                 \
     hipLaunchKernelGGL(k, dim3(grid), dim3(512), lds, st, Nimg, H, W, (const bf16_t*)x, (const bf16_t*)wt, (TO*)out, \
                        bias, gate, nbuf);                                                                            \
@@ -873,13 +896,19 @@ static int conv3x3_bwd_weight_impl(asr_handle* h, const void* x, const void* dy,
       else if (Cin == 64) { if (mv <= 4) ASR_WGRAD_IMG(64, 4, 4, 1); else ASR_WGRAD_IMG(64, 14, 14, 1); }
       else ASR_WGRAD_IMG(128, 4, 2, 1);
 #undef ASR_WGRAD_IMG
+      h->conv_counts[Cin == 128 ? ASR_CONVP_WGRAD_IMG_128 : mv <= 4 ? ASR_CONVP_WGRAD_IMG_64_SMALL : ASR_CONVP_WGRAD_IMG_64_LARGE] += 1;
+      if (Cin == 64 && split_on) h->conv_counts[ASR_CONVP_WGRAD_SPLIT] += 1;
+      if (inb) h->conv_counts[ASR_CONVP_WGRAD_BIAS_IN_KERNEL] += 1;
       const size_t total = (size_t)M * N;
       if (inb) {
         const int rb = (int)((total / 4 + 255) / 256);
-        if (((uintptr_t)dw) % 16 == 0)
+        if (((uintptr_t)dw) % 16 == 0) {
           hipLaunchKernelGGL(wgrad_img_reduce_kernel<1>, dim3(rb), dim3(256), 0, st, partial, (int)wgs, M, G, N, dw, dbias, accumulate);
-        else
+          h->conv_counts[ASR_CONVP_WGRAD_REDUCE_VEC] += 1;
+        } else {
           hipLaunchKernelGGL(wgrad_img_reduce_kernel<0>, dim3(rb), dim3(256), 0, st, partial, (int)wgs, M, G, N, dw, dbias, accumulate);
+          h->conv_counts[ASR_CONVP_WGRAD_REDUCE_SCALAR] += 1;
+        }
       } else
         asr_conv_slab_sum(partial, (int)wgs, total, dw, accumulate, st);
       ASR_CHECK_LAUNCH(h, "asr_conv3x3_bwd_weight(image-resident)");
@@ -893,8 +922,10 @@ static int conv3x3_bwd_weight_impl(asr_handle* h, const void* x, const void* dy,
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(kern, dim3(tn, tm, S), dim3(256), lds, st, Mpix, H, W, Cin, Cout,
                        (const bf16_t*)x, (const bf16_t*)dy, kchunk, partial);
+    h->conv_counts[bn64 ? ASR_CONVP_WGRAD_TR_64 : ASR_CONVP_WGRAD_TR_128] += 1;
   } else {
     asr_conv_wgrad_tiled<Taps33>(x, dy, Mpix, H, W, Cin, Cout, S, kchunk, partial, st);
+    h->conv_counts[ASR_CONVP_WGRAD_COLPIX] += 1;
   }
   asr_conv_slab_sum(partial, S, (size_t)M * N, dw, accumulate, st);
   ASR_CHECK_LAUNCH(h, "asr_conv3x3_bwd_weight");
@@ -909,4 +940,15 @@ extern "C" int asr_conv3x3_bwd_weight_bias(asr_handle* h, const void* x, const v
                                            int Cin, int Cout, float* dw, float* dbias, asr_stream s) {
   if (h && !dbias) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_conv3x3_bwd_weight_bias: dbias is NULL");
   return conv3x3_bwd_weight_impl(h, x, dy, Nimg, H, W, Cin, Cout, dw, dbias, 0, s);
+}
+
+extern "C" int asr_conv_path_counts(asr_handle* h, unsigned long long* out, int n) {
+  if (!h || !out || n < 0) return ASR_ERR_INVALID_ARG;
+  for (int i = 0; i < n; ++i) out[i] = i < ASR_CONVP_N ? h->conv_counts[i] : 0ull;
+  return ASR_OK;
+}
+extern "C" int asr_reset_conv_path_counts(asr_handle* h) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  for (int i = 0; i < ASR_CONVP_N; ++i) h->conv_counts[i] = 0;
+  return ASR_OK;
 }

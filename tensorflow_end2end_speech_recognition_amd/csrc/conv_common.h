@@ -70,5 +70,7 @@ int asr_conv_wgrad_plan(asr_handle* h, const char* what, int Mpix, int tiles, si
 template <typename TP>
 void asr_conv_wgrad_tiled(const void* x, const void* dy, int Mpix, int H, int W, int Cin, int Cout, int S, int kchunk,
                           float* partial, hipStream_t st);
+// conv3x3.hip: the ASR_CONVP_PAIR_* counter of a Cin -> Cout product (asr_conv_path_counts)
+int asr_conv_pair_counter(int Cin, int Cout);
 // dw[i] (+)= sum_{z = 0 .. S-1} partial[z][i], slabs added in index order
 void asr_conv_slab_sum(const float* partial, int S, size_t total, float* dw, int accumulate, hipStream_t st);

@@ -12,6 +12,8 @@
 // weight-gradient kernels), the asr_debug_* hooks; nothing removed or re-typed.
 // still 5 (additive, backward compatible): asr_cluster_tile_groups, asr_recurrence_path_counts,
 // asr_reset_recurrence_path_counts, asr_debug_set_cluster_cu_budget (cluster recurrences in tile groups).
+// still 5 (additive): asr_att_path_counts / asr_reset_att_path_counts, asr_conv_path_counts / asr_reset_conv_path_counts
+// (host counters of the kernels a call launched).
 extern "C" int asr_abi_version(void) { return 5; }
 
 extern "C" int asr_create(asr_handle** out, int device) { return asr_create_ex(out, device, (size_t)192 << 20); }

@@ -1383,6 +1383,33 @@ def reset_att_path_counts(device=0):
         h.check(h.lib.asr_reset_att_path_counts(h.h), 'asr_reset_att_path_counts')
 
 
+# the ASR_CONVP_* enum of include/asr_hip.h, in its order
+_CONV_PATH_KEYS = ('img', 'tiled', 'pair_64_64', 'pair_64_128', 'pair_128_128', 'pair_128_64', 'pair_other',
+                   'maxv_2', 'maxv_4', 'maxv_8', 'maxv_14', 'maxv_16', 'act_0', 'act_1', 'act_2', 'act_3', 'act_4',
+                   'nbuf_1', 'nbuf_2', 'stream', 'w8', 'tiled_bn128', 'tiled_bn64',
+                   'wgrad_img_64_small', 'wgrad_img_64_large', 'wgrad_img_128', 'split', 'bias_in_kernel',
+                   'reduce_vec', 'reduce_scalar', 'wgrad_tr_128', 'wgrad_tr_64', 'wgrad_colpix')
+
+
+def conv_path_counts(device=0):
+    """Which kernel instantiations the conv3x3_* calls on `device` launched since the last reset, summed over its handles
+    (asr_conv_path_counts): forward / data-gradient launches by form (img / tiled), channel pair of the product, and for
+    the image-resident kernel MAXV, compile-time ACT, LDS buffers, stream / w8; weight-gradient calls by form, split,
+    bias_in_kernel and reduce kernel.  Host counters: no device work, no synchronisation."""
+    n = len(_CONV_PATH_KEYS)
+    tot = [0] * n
+    for h in _device_handles(device):
+        out = (C.c_ulonglong * n)()
+        h.check(h.lib.asr_conv_path_counts(h.h, out, n), 'asr_conv_path_counts')
+        tot = [a + int(b) for a, b in zip(tot, out)]
+    return dict(zip(_CONV_PATH_KEYS, tot))
+
+
+def reset_conv_path_counts(device=0):
+    for h in _device_handles(device):
+        h.check(h.lib.asr_reset_conv_path_counts(h.h), 'asr_reset_conv_path_counts')
+
+
 def debug_set_cluster_cu_budget(n):
     """TEST ONLY: co-resident workgroups a cluster launch may use (0 = the device's CU count; never more than that)."""
     _lib.load().asr_debug_set_cluster_cu_budget(int(n))

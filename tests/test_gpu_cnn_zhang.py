@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+from _bf16_ulp import within_bf16_ulp as _within_bf16_ulp
 from test_cnn_zhang_host import check_against_fixture, fixture_batch, fixture_model
 
 pytestmark = pytest.mark.gpu
@@ -21,15 +22,6 @@ def _conv_ref(x, w_hwio, bias=None, relu=False):
                                    None if bias is None else bias.double().cpu(), padding=(1, 2))
     y = y.permute(0, 2, 3, 1)
     return torch.relu(y) if relu else y
-
-
-def _within_bf16_ulp(got_bf16, ref64):
-    """|got - ref| <= 1 bf16 ulp of ref (+ 1e-5 max|ref| for values that cancel to ~0)."""
-    got = got_bf16.double().cpu()
-    mag = ref64.abs().clamp_min(1e-30)
-    ulp = torch.exp2(torch.floor(torch.log2(mag)) - 7)
-    err = (got - ref64).abs()
-    return bool((err <= ulp + 1e-5 * float(ref64.abs().max())).all()), float((err / (ulp + 1e-30)).max())
 
 
 def _operands(N, H, W, cin, cout, seed):

@@ -57,8 +57,9 @@ def test_conv3x3_implicit_gemm(cuda, N, H, W, Cin, Cout):
     wr = wq.permute(3, 2, 0, 1).clone().requires_grad_(True)                           # OIHW
     yr = torch.nn.functional.conv2d(xr, wr, b.double(), padding=1)
     out = ops.conv3x3_fwd(x.to(cuda), wf, b.to(cuda), relu=True)
-    ref = torch.relu(yr).permute(0, 2, 3, 1).detach().numpy()
-    assert np.abs(out.float().cpu().numpy() - ref).max() < 2e-2 * max(1.0, np.abs(ref).max())
+    from _bf16_ulp import within_bf16_ulp                        # one bf16 ulp of the fp64 value (+ 1e-5 max|ref| near zero)
+    ok, worst = within_bf16_ulp(out, torch.relu(yr).permute(0, 2, 3, 1).detach())
+    assert ok, worst
     (yr * dy.double().permute(0, 3, 1, 2)).sum().backward()
     dx = ops.conv3x3_bwd_data(dy.to(cuda), wb)
     assert _rel(dx.cpu().numpy(), xr.grad.permute(0, 2, 3, 1).numpy()) < 1e-5
