@@ -154,6 +154,31 @@ int asr_gemm_mul(asr_handle* h, int dtype, int transA, int transB, int M, int N,
 int asr_gemm_drop(asr_handle* h, int dtype, int transA, int transB, int M, int N, int K, const void* A, int lda,
                   const void* B, int ldb, float* C, int ldc, const float* bias, int accumulate, int act, float keep_prob,
                   uint64_t seed, uint64_t offset, asr_stream s);
+/* The same products (fp32 output) on LISTED ROWS only: rows[0 .. num_rows) are row numbers of the [M, N] result, int32,
+ * ASCENDING, each in [0, M), on the device.  Row rows[i] of C is computed from row rows[i] of A (with row rows[i] of
+ * mul, or with the dropout mask of row rows[i] of the full [M, N] tensor) and gets, bit for bit, the value the full
+ * product gives it.  Contract: the listed rows are written; every other row of C is EITHER left untouched OR written
+ * with the full product's value -- the caller must not care which.  mul (or NULL) as asr_gemm_mul; keep_prob == 0: no
+ * dropout, else as asr_gemm_drop (ldc == N, N % 4 == 0; not together with mul).  M, lda, ldc, ldmul describe the FULL
+ * operands.  Where the lean NT kernels would take the full product (bf16 operands, transA = 0, transB = 1, K % 64 == 0,
+ * N % 128 == 0, M >= 1024, 16-byte aligned rows) the launch covers ceil(num_rows / tile) row tiles instead of
+ * ceil(M / tile); everywhere else the list is ignored and the full product runs as asr_gemm_mul / asr_gemm_drop run it.
+ * num_rows == 0 launches nothing.  For intermediates whose unlisted rows are never used as values: the x-projection and
+ * the between-layer dx of a recurrent stack at padded frames (models/encoders/core/rnn_util.py). */
+int asr_gemm_rows(asr_handle* h, int dtype, int transA, int transB, int M, int N, int K, const void* A, int lda,
+                  const void* B, int ldb, float* C, int ldc, const float* bias, int accumulate, int act,
+                  const float* mul, int ldmul, float keep_prob, uint64_t seed, uint64_t offset, const int32_t* rows,
+                  int num_rows, asr_stream s);
+/* What the asr_gemm_rows calls on this handle ran since the last reset (host integers bumped at launch time: no device
+ * work, no synchronisation); out[i], i < min(n, ASR_GEMMP_N), in the order of the enum, the rest of `out` zeroed. */
+enum {
+  ASR_GEMMP_ROWS_128 = 0,         /* listed-row launches of the 128 x 128 NT kernel */
+  ASR_GEMMP_ROWS_256,             /* listed-row launches of the 256 x 256 NT kernel */
+  ASR_GEMMP_ROWS_FULL,            /* calls that ignored their list and ran the full product */
+  ASR_GEMMP_N
+};
+int asr_gemm_path_counts(asr_handle* h, unsigned long long* out, int n);
+int asr_reset_gemm_path_counts(asr_handle* h);
 
 /* ---- VGG front-end (models/encoders/core/vgg_blstm.py:107-177) --------------- *
  * Images are NHWC: [N = B*T frames, H = channels(40), W = splice*stack, C].

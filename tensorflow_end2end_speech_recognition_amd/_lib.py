@@ -42,6 +42,8 @@ SIGNATURES = {
     'asr_gemm_act': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp]),
     'asr_gemm_drop': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _f, _u64, _u64, _vp]),
     'asr_gemm_mul': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp]),
+    'asr_gemm_rows': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _f, _u64, _u64,
+                           _vp, _i, _vp]),
     'asr_conv3x3_prep_weights': (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     'asr_conv3x3_fwd': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
     'asr_conv3x3_fwd_drop': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _f, _u64, _u64, _vp, _vp]),
@@ -105,6 +107,8 @@ SIGNATURES = {
     'asr_reset_att_path_counts': (_i, [_vp]),
     'asr_conv_path_counts': (_i, [_vp, C.POINTER(C.c_ulonglong), _i]),
     'asr_reset_conv_path_counts': (_i, [_vp]),
+    'asr_gemm_path_counts': (_i, [_vp, C.POINTER(C.c_ulonglong), _i]),
+    'asr_reset_gemm_path_counts': (_i, [_vp]),
     'asr_debug_set_cluster_cu_budget': (_i, [_i]),
     'asr_debug_placement': (_i, [_vp, _vp, _i, _i, _vp]),
     'asr_debug_poison_lds': (_i, [_vp, _vp]),

@@ -14,6 +14,7 @@
 // asr_reset_recurrence_path_counts, asr_debug_set_cluster_cu_budget (cluster recurrences in tile groups).
 // still 5 (additive): asr_att_path_counts / asr_reset_att_path_counts, asr_conv_path_counts / asr_reset_conv_path_counts
 // (host counters of the kernels a call launched).
+// still 5 (additive): asr_gemm_rows (the NT products on listed rows), asr_gemm_path_counts / asr_reset_gemm_path_counts.
 extern "C" int asr_abi_version(void) { return 5; }
 
 extern "C" int asr_create(asr_handle** out, int device) { return asr_create_ex(out, device, (size_t)192 << 20); }

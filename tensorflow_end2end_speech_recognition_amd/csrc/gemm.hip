@@ -261,6 +261,23 @@ __global__ __launch_bounds__(256) void gemm_kernel(int M, int N, int K, const T*
 // (row stride 9 slots: 9 r + q mod 16 is a permutation of the 16 rows).
 __device__ __forceinline__ unsigned nt_swz(int row) { return (((row + 4) >> 3) & 1) ? 8u : 0u; }   // in bf16 elements
 
+// The tile a block of the NT kernels works on: block b runs on XCD b % 8, and XCD x gets a contiguous run of tiles, so that
+// the N-tiles sharing an A row-panel fetch it into ONE L2.  The full products apply this when the tile count is a multiple
+// of 8 (and take tile b otherwise).  ANY: for every count -- XCD x runs blocks x, x + 8, ..., total / 8 of them and one more
+// on the first total % 8 XCDs, and gets that many consecutive tiles (the same tiles as the other rule where that one
+// applies); the listed-row products use it, whose counts are rarely multiples of 8 (dx of the headline step: 204 tiles,
+// 46.3 -> 42.8 us).
+template <bool ANY> __device__ __forceinline__ int nt_tile_of_block(int b, int total) {
+  if constexpr (ANY) {
+    const int per = total >> 3, rem = total & 7, x = b & 7;
+    return x * per + min(x, rem) + (b >> 3);
+  } else {
+    int t = b;
+    if ((total & 7) == 0) t = (t & 7) * (total >> 3) + (t >> 3);
+    return t;
+  }
+}
+
 struct GemmDrop {               // dropout multiplier of the OUTPUT formed in the epilogue (element m*N + n of a contiguous
   float keep;                   // [M,N] tensor -> word (m*N + n) % 4 of Philox block offset + (m*N + n) / 4): asr_dropout_mask's
   uint64_t seed, offset;        // values without the mask tensor
@@ -276,13 +293,20 @@ struct GemmDrop {               // dropout multiplier of the OUTPUT formed in th
 // (one barrier per k-tile), transposed accumulators (16-byte stores).  Tiles are mapped to blocks
 // so that the N-tiles sharing an A row-panel run on ONE XCD (block b lands on XCD b % 8): the
 // panel is then fetched into one L2 instead of eight.
-template <typename TO>
+// ROWS (the listed-row form, asr_gemm_rows): M counts the entries of `rows` (ascending row numbers of A / C / mul);
+// product row i reads A[rows[i]] and is stored to C[rows[i]], the multiplier and the dropout counter are those of row
+// rows[i] of the full tensor.  Same k-loop and accumulation order: a listed row gets the bits the full product gives it.
+// (Measured and not kept: the listed-row form with the global loads of TWO k-tiles in flight -- two register sets, the
+// loop unrolled by two, 144 + 64 registers, s_waitcnt vmcnt(15..8) in the loop.  dx of the headline step 42.8 -> 42.8 us,
+// projection 32.4 -> 33.1 us, step within the run-to-run spread: the k-loop is not what these launches wait for.
+// profiles/r08_valid_rows_ab.md.)
+template <typename TO, bool ROWS = false>
 __global__ __launch_bounds__(256) void gemm_nt_bf16_kernel(int M, int N, int K, const bf16_t* __restrict__ A,
                                                            int lda, const bf16_t* __restrict__ Bt, int ldb,
                                                            TO* __restrict__ C, int ldc,
                                                            const float* __restrict__ bias, int accumulate,
                                                            int act, const float* __restrict__ mul, int ldm,
-                                                           GemmDrop drop) {
+                                                           GemmDrop drop, const int32_t* __restrict__ rows) {
   constexpr int BM = 128, BN = 128, BK = 64, LD = BK + 8;
   constexpr int STAGE = (BM + BN) * LD;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -291,8 +315,7 @@ __global__ __launch_bounds__(256) void gemm_nt_bf16_kernel(int M, int N, int K, 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int ntn = N / BN, ntm = (M + BM - 1) / BM, total = ntn * ntm;
-  int t = blockIdx.x;
-  if ((total & 7) == 0) t = (t & 7) * (total >> 3) + (t >> 3);   // XCD x gets a contiguous run of tiles
+  const int t = nt_tile_of_block<ROWS>((int)blockIdx.x, total);
   const int m0 = (t / ntn) * BM, n0 = (t % ntn) * BN;
 
   // 4 A vectors + 4 B vectors of 16 B per thread per k-tile: vector v -> row v>>3, k-offset (v&7)*8
@@ -302,7 +325,8 @@ __global__ __launch_bounds__(256) void gemm_nt_bf16_kernel(int M, int N, int K, 
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int v = tid + i * 256, r = v >> 3, kv = (v & 7) * 8;
-    pa[i] = A + (size_t)min(m0 + r, M - 1) * lda + kv;
+    const int ar = min(m0 + r, M - 1);
+    pa[i] = A + (size_t)(ROWS ? rows[ar] : ar) * lda + kv;
     pb[i] = Bt + (size_t)(n0 + r) * ldb + kv;
     so[i] = (unsigned)(r * LD) + ((unsigned)kv ^ nt_swz(r));
   }
@@ -359,8 +383,9 @@ __global__ __launch_bounds__(256) void gemm_nt_bf16_kernel(int M, int N, int K, 
   // lane holds C[m = fr][n = fq*4 .. +3] of each 16x16 tile
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int m = m0 + wm * 64 + i * 16 + fr;
-    if (m >= M) continue;
+    const int mi = m0 + wm * 64 + i * 16 + fr;
+    if (mi >= M) continue;
+    const int m = ROWS ? rows[mi] : mi;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int nb = n0 + wn * 64 + j * 16 + fq * 4;
@@ -430,13 +455,14 @@ __global__ __launch_bounds__(256) void gemm_nt_bf16_kernel(int M, int N, int K, 
 // (Round 5, measured: a PERSISTENT form -- 256 / 512 workgroups walking the tiles, the next tile's first k-tile requested
 // before the epilogue's stores -- is 2 % SLOWER on every cfg C / D projection (1178 -> 1206 us, 493 -> 516 us): the
 // dispatcher already replaces a finished workgroup faster than the epilogue drains.  scripts/bench_nt.py.)
-template <typename TO, int BM, int BN, int WM, int WN>
+// ROWS: the listed-row form, as in gemm_nt_bf16_kernel (the A descriptor then reaches to the last listed row).
+template <typename TO, int BM, int BN, int WM, int WN, bool ROWS = false>
 __global__ __launch_bounds__(WM * WN * 64, 1) void gemm_nt_bf16_big_kernel(int M, int N, int K, const bf16_t* __restrict__ A,
                                                                            int lda, const bf16_t* __restrict__ Bt, int ldb,
                                                                            TO* __restrict__ C, int ldc,
                                                                            const float* __restrict__ bias, int accumulate,
                                                                            int act, const float* __restrict__ mul, int ldm,
-                                                                           GemmDrop drop) {
+                                                                           GemmDrop drop, const int32_t* __restrict__ rows) {
   constexpr int BK = 64, LD = BK + 8, NT = WM * WN * 64;
   constexpr int STAGE = (BM + BN) * LD;
   constexpr int TM = BM / WM, TN = BN / WN, TI = TM / 16, TJ = TN / 16;
@@ -447,8 +473,7 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void gemm_nt_bf16_big_kernel(int M
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
   const int ntn = N / BN, ntm = (M + BM - 1) / BM, total = ntn * ntm;
-  int t = blockIdx.x;
-  if ((total & 7) == 0) t = (t & 7) * (total >> 3) + (t >> 3);   // XCD x gets a contiguous run of tiles
+  const int t = nt_tile_of_block<ROWS>((int)blockIdx.x, total);
   const int m0 = (t / ntn) * BM, n0 = (t % ntn) * BN;
 
   // staging vector i of a thread: row (tid >> 3) + RSTEP i, k-offset (tid & 7) * 8; rows of A past M (last tile) are
@@ -456,12 +481,16 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void gemm_nt_bf16_big_kernel(int M
   const int r0 = tid >> 3, kv = (tid & 7) * 8;
   unsigned oa[VA], ob[VB];
 #pragma unroll
-  for (int i = 0; i < VA; ++i) oa[i] = (unsigned)(((size_t)min(m0 + r0 + RSTEP * i, M - 1) * lda + kv) * sizeof(bf16_t));
+  for (int i = 0; i < VA; ++i) {
+    const int ar = min(m0 + r0 + RSTEP * i, M - 1);
+    oa[i] = (unsigned)(((size_t)(ROWS ? rows[ar] : ar) * lda + kv) * sizeof(bf16_t));
+  }
 #pragma unroll
   for (int i = 0; i < VB; ++i) ob[i] = (unsigned)(((size_t)(n0 + r0 + RSTEP * i) * ldb + kv) * sizeof(bf16_t));
   const unsigned so0 = (unsigned)(r0 * LD) + ((unsigned)kv ^ nt_swz(r0));   // (a thread's rows are RSTEP = 32 k apart: same class)
   const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<bf16_t*>(A), 0, (int)min((size_t)0xFFFFFFFFu, ((size_t)(M - 1) * lda + K) * sizeof(bf16_t)), 0x00020000);
+      const_cast<bf16_t*>(A), 0,
+      (int)min((size_t)0xFFFFFFFFu, ((size_t)(ROWS ? rows[M - 1] : M - 1) * lda + K) * sizeof(bf16_t)), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<bf16_t*>(Bt), 0, (int)min((size_t)0xFFFFFFFFu, ((size_t)(N - 1) * ldb + K) * sizeof(bf16_t)), 0x00020000);
   typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
@@ -520,8 +549,9 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void gemm_nt_bf16_big_kernel(int M
   // lane holds C[m = fr][n = fq*4 .. +3] of each 16x16 tile
 #pragma unroll
   for (int i = 0; i < TI; ++i) {
-    const int m = m0 + wm * TM + i * 16 + fr;
-    if (m >= M) continue;
+    const int mi = m0 + wm * TM + i * 16 + fr;
+    if (mi >= M) continue;
+    const int m = ROWS ? rows[mi] : mi;
 #pragma unroll
     for (int j = 0; j < TJ; ++j) {
       const int nb = n0 + wn * TN + j * 16 + fq * 4;
@@ -573,36 +603,69 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void gemm_nt_bf16_big_kernel(int M
   }
 }
 
-template <typename TO, int BM, int BN, int WM, int WN>
+template <typename TO, int BM, int BN, int WM, int WN, bool ROWS = false>
 static void launch_gemm_nt_big(int M, int N, int K, const void* A, int lda, const void* B, int ldb, void* C, int ldc,
                                const float* bias, int accumulate, hipStream_t st, int act, const float* mul, int ldm,
-                               GemmDrop drop) {
+                               GemmDrop drop, const int32_t* rows = nullptr) {
   const size_t lds = (size_t)2 * (BM + BN) * (64 + 8) * sizeof(bf16_t);
   static unsigned long long attr_done = 0;
-  auto k = gemm_nt_bf16_big_kernel<TO, BM, BN, WM, WN>;
+  auto k = gemm_nt_bf16_big_kernel<TO, BM, BN, WM, WN, ROWS>;
   if (first_on_device(attr_done)) {
     (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   }
   const long tiles = (long)(N / BN) * ((M + BM - 1) / BM);
   hipLaunchKernelGGL(k, dim3((unsigned)tiles), dim3(WM * WN * 64), lds, st, M, N, K, (const bf16_t*)A, lda,
-                     (const bf16_t*)B, ldb, (TO*)C, ldc, bias, accumulate, act, mul, ldm, drop);
+                     (const bf16_t*)B, ldb, (TO*)C, ldc, bias, accumulate, act, mul, ldm, drop, rows);
 }
 
+// the listed-row launch of the 128 x 128 kernel (its own function: its own opt-in for the dynamic LDS)
+static void launch_gemm_nt_rows128(int nrows, int N, int K, const void* A, int lda, const void* B, int ldb, float* C,
+                                   int ldc, const float* bias, int accumulate, hipStream_t st, int act,
+                                   const float* mul, int ldm, GemmDrop drop, const int32_t* rows) {
+  const size_t lds = (size_t)2 * (128 + 128) * (64 + 8) * sizeof(bf16_t);
+  static unsigned long long attr_done = 0;
+  auto k = gemm_nt_bf16_kernel<float, true>;
+  if (first_on_device(attr_done)) {
+    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  }
+  const int total = (N / 128) * ((nrows + 127) / 128);
+  hipLaunchKernelGGL(k, dim3(total), dim3(256), lds, st, nrows, N, K, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, C,
+                     ldc, bias, accumulate, act, mul, ldm, drop, rows);
+}
+
+// rows / nrows (asr_gemm_rows, fp32 output): the product of the `nrows` (>= 1) listed rows only.  Whether the lean path
+// applies is judged on the full M, as for the full product; which of the two kernels runs, on the listed count.
+// counts: the handle's gemm_counts (listed-row launches by kernel).
 template <typename TO>
 bool try_gemm_nt_bf16(int transA, int transB, int M, int N, int K, const void* A, int lda, const void* B,
                       int ldb, void* C, int ldc, const float* bias, int accumulate, hipStream_t st, int act,
-                      const float* mul, int ldm, GemmDrop drop = GemmDrop{1.f, 0, 0, 0}) {
+                      const float* mul, int ldm, GemmDrop drop = GemmDrop{1.f, 0, 0, 0}, const int32_t* rows = nullptr,
+                      int nrows = 0, unsigned long long* counts = nullptr) {
   if (transA || !transB || K % 64 != 0 || N % 128 != 0 || M < 1024) return false;
   if (drop.use && sizeof(TO) != 4) return false;
   if (mul && (sizeof(TO) != 4 || ldm % 4 != 0 || ((uintptr_t)mul) % 16 != 0)) return false;
   if (lda % 8 != 0 || ldb % 8 != 0 || ((uintptr_t)A) % 16 != 0 || ((uintptr_t)B) % 16 != 0) return false;
   if (ldc % 4 != 0 || ((uintptr_t)C) % (4 * sizeof(TO)) != 0 || (bias && ((uintptr_t)bias) % 16 != 0)) return false;
+  if (rows && (sizeof(TO) != 4 || nrows < 1 || nrows > M)) return false;
   // large products (>= 512 tiles of 256 x 256, i.e. two full rounds of the chip): 256 x 256 blocks of eight waves, see
   // gemm_nt_bf16_big_kernel; ASR_GEMM_NT_BIG=0 keeps the 128 x 128 tiles (A/B), =2 takes the big ones from M >= 2048 on
   static const int big = [] { const char* e = getenv("ASR_GEMM_NT_BIG"); return e ? atoi(e) : 1; }();
   const bool fits32 = ((size_t)(M - 1) * lda + K) * sizeof(bf16_t) < 0xFFFFFFFFull && ((size_t)(N - 1) * ldb + K) * sizeof(bf16_t) < 0xFFFFFFFFull;
-  const long tiles256 = (long)(N / 256) * ((M + 255) / 256);
-  if (big && fits32 && N % 256 == 0 && (big == 2 ? M >= 2048 : tiles256 >= 512)) {
+  const int Mk = rows ? nrows : M;                          // rows the launch computes
+  const long tiles256 = (long)(N / 256) * ((Mk + 255) / 256);
+  const bool use_big = big && fits32 && N % 256 == 0 && (big == 2 ? Mk >= 2048 : tiles256 >= 512);
+  if constexpr (sizeof(TO) == 4) {
+    if (rows) {
+      if (use_big)
+        launch_gemm_nt_big<float, 256, 256, 2, 4, true>(Mk, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, st, act, mul,
+                                                         ldm, drop, rows);
+      else
+        launch_gemm_nt_rows128(Mk, N, K, A, lda, B, ldb, (float*)C, ldc, bias, accumulate, st, act, mul, ldm, drop, rows);
+      if (counts) counts[use_big ? ASR_GEMMP_ROWS_256 : ASR_GEMMP_ROWS_128] += 1;
+      return true;
+    }
+  }
+  if (use_big) {
     launch_gemm_nt_big<TO, 256, 256, 2, 4>(M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, st, act, mul, ldm, drop);
     return true;
   }
@@ -613,7 +676,7 @@ bool try_gemm_nt_bf16(int transA, int transB, int M, int N, int K, const void* A
   }
   const int total = (N / 128) * ((M + 127) / 128);
   hipLaunchKernelGGL(gemm_nt_bf16_kernel<TO>, dim3(total), dim3(256), lds, st, M, N, K, (const bf16_t*)A, lda,
-                     (const bf16_t*)B, ldb, (TO*)C, ldc, bias, accumulate, act, mul, ldm, drop);
+                     (const bf16_t*)B, ldb, (TO*)C, ldc, bias, accumulate, act, mul, ldm, drop, (const int32_t*)nullptr);
   return true;
 }
 
@@ -1257,6 +1320,50 @@ extern "C" int asr_gemm_drop(asr_handle* h, int dtype, int transA, int transB, i
     launch_gemm<bf16_t, float>(h, transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, st, act, nullptr, 0, &fused, drop);
   ASR_CHECK_LAUNCH(h, "asr_gemm_drop");
   if (!fused) return asr_dropout_apply(h, ASR_F32, C, C, (size_t)M * N, keep_prob, seed, offset, s);
+  return ASR_OK;
+}
+
+// asr_gemm_act / asr_gemm_mul / asr_gemm_drop (fp32 output) on the `num_rows` rows of the product that `rows` lists: the
+// lean NT kernels in their listed-row form where the full product would take them (bf16 operands, NT, K % 64 == 0,
+// N % 128 == 0, M >= 1024 ...); anywhere else the full product, exactly as the entry point without a list runs it.
+extern "C" int asr_gemm_rows(asr_handle* h, int dtype, int transA, int transB, int M, int N, int K, const void* A,
+                             int lda, const void* B, int ldb, float* C, int ldc, const float* bias, int accumulate,
+                             int act, const float* mul, int ldmul, float keep_prob, uint64_t seed, uint64_t offset,
+                             const int32_t* rows, int num_rows, asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  const bool use_drop = keep_prob != 0.f;
+  if (!rows || num_rows < 0 || num_rows > M || (mul && use_drop))
+    ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_gemm_rows: bad row list (rows=%p num_rows=%d M=%d) or both mul and dropout",
+             (const void*)rows, num_rows, M);
+  if (!asr_dtype_ok(dtype) || (act != 0 && act != 1) || M < 0 || N < 0 || K < 0 || !A || !B || !C ||
+      lda < (transA ? M : K) || ldb < (transB ? K : N) || ldc < N || (mul && ldmul < N) ||
+      (use_drop && (ldc != N || N % 4 != 0 || !(keep_prob > 0.f && keep_prob <= 1.f))))
+    ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_gemm_rows: bad args M=%d N=%d K=%d lda=%d ldb=%d ldc=%d ldmul=%d keep_prob=%g",
+             M, N, K, lda, ldb, ldc, ldmul, (double)keep_prob);
+  if (M == 0 || N == 0 || num_rows == 0) return ASR_OK;
+  if (dtype == ASR_BF16) {
+    const GemmDrop drop = {use_drop ? keep_prob : 1.f, seed, offset, use_drop ? 1 : 0};
+    if (try_gemm_nt_bf16<float>(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, (hipStream_t)s, act,
+                                mul, ldmul, drop, rows, num_rows, h->gemm_counts)) {
+      ASR_CHECK_LAUNCH(h, "asr_gemm_rows");
+      return ASR_OK;
+    }
+  }
+  h->gemm_counts[ASR_GEMMP_ROWS_FULL] += 1;
+  if (use_drop)
+    return asr_gemm_drop(h, dtype, transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, act, keep_prob, seed,
+                         offset, s);
+  return asr_gemm_mul(h, dtype, transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, act, mul, ldmul, s);
+}
+
+extern "C" int asr_gemm_path_counts(asr_handle* h, unsigned long long* out, int n) {
+  if (!h || !out || n < 0) return ASR_ERR_INVALID_ARG;
+  for (int i = 0; i < n; ++i) out[i] = i < ASR_GEMMP_N ? h->gemm_counts[i] : 0ull;
+  return ASR_OK;
+}
+extern "C" int asr_reset_gemm_path_counts(asr_handle* h) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  for (int i = 0; i < ASR_GEMMP_N; ++i) h->gemm_counts[i] = 0;
   return ASR_OK;
 }
 

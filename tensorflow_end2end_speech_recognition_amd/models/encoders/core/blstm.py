@@ -87,6 +87,7 @@ class _RecurrentEncoderBase(object):
         self.halves = ENC_HALVES       # two half-batch pipelines where the batch has at least two tiles (see ENC_HALVES)
         self.layers_b = None           # twin layer objects (same variables, own tape) of the second pipeline
         self._split = 0                # rows of the first part in the last __call__ (0: one pipeline)
+        self._rows = None              # per pipeline (int32 device vector, count): valid frames of the last __call__
 
     # variables are created at graph-build time in the reference; here when the input size is known
     def build(self, store, input_dim, rng, scope_prefix=''):
@@ -133,6 +134,10 @@ class _RecurrentEncoderBase(object):
         Returns outputs [T,B,ndir*H] if time_major else [B,T,ndir*H] (fp32) and final_state of
         the last layer: ((c_fw,h_fw),(c_bw,h_bw)) for the bidirectional encoder."""
         self._ensure_built(inputs)
+        # the lengths as the caller gave them on the host (the model classes leave them in _lens_host): taken once,
+        # never read back from the device
+        lens_host = getattr(self, '_lens_host', None)
+        self._lens_host = None
         if self.num_proj is not None:
             return self._call_projected(inputs, inputs_seq_len, keep_prob, is_training, drop_masks, rng_state)
         B, T, _ = inputs.shape
@@ -173,6 +178,13 @@ class _RecurrentEncoderBase(object):
                 preps[li]['mask'] = layer.make_mask(inputs.device, Tt, Bp, keep_prob, is_training, rs_of(li), dm)
                 ready_m.append(ops.stream_event())
         self._split = self._split_rows(Bp) if drop_masks is None else 0
+        # the valid frames of each pipeline's [T, B] layout (rnn_util.VALID_ROWS): built on the host, uploaded once per
+        # call on the upload stream before the first layer is enqueued, used by every layer's projection and dx product
+        plans = rnn_util.row_plans(lens_host, B, Tt, Bp, self._split) if (self.dtype != ASR_F32 and inputs.is_cuda) \
+            else None
+        self._rows = None
+        if plans is not None:
+            self._rows = [(t, int(p.size)) for t, p in zip(ops.upload_ints(inputs.device, plans), plans)]
         if self._split:
             x, finals = self._forward_halves(inputs, seq_len, preps, ready_w, ready_m, keep_prob, is_training, ldk0)
             return self._finish_call(x, finals, seq_len, B)
@@ -187,7 +199,7 @@ class _RecurrentEncoderBase(object):
             elif li == 1:
                 ops.wait_event(ready_w[-1])
             x, final = layer.forward(x, seq_len, self.dtype, keep_prob, is_training, prep=preps[li],
-                                     mask_event=ready_m[li])
+                                     mask_event=ready_m[li], rows=self._rows[0] if self._rows else None)
             finals.append(final)
             if self.num_layers_sub is not None and li + 1 == self.num_layers_sub:
                 # blstm.py:326-328: outputs_sub IS the tensor the next layer consumes (after the dropout wrapper)
@@ -252,7 +264,7 @@ class _RecurrentEncoderBase(object):
                             ops.wait_event(ready_w[-1])
                     prep = preps[li] if not h else dict(preps[li], mask=self._second_mask(preps[li]['mask']))
                     xs[h], fin = layers[li].forward(xs[h], sl[h], self.dtype, keep_prob, is_training, prep=prep,
-                                                    mask_event=ready_m[li])
+                                                    mask_event=ready_m[li], rows=self._rows[h] if self._rows else None)
                     fins[h].append(fin)
                     if h and li + 1 == len(self.layers):
                         done = ops.stream_event()
@@ -348,7 +360,8 @@ class _RecurrentEncoderBase(object):
                 cb = None
             dx = self.layers[li].backward(dx.contiguous(), dcf, dhf, need_dx=(li > 0 or need_input_grad),
                                           dout_masked=masked, dx_mask=below, background=(li > 0),
-                                          warm=(cb['gates'], cb['cs']) if cb is not None else None)
+                                          warm=(cb['gates'], cb['cs']) if cb is not None else None,
+                                          dx_valid_only=(li > 0))
             ops.wait_event(getattr(self.layers[li], 'warm_event', None))
             masked = below is not None
             if self.grad_ready_hook is not None:      # data-parallel step: this layer's gradients are on their way
@@ -385,7 +398,7 @@ class _RecurrentEncoderBase(object):
                     dxs[h] = layers[li].backward(dxs[h].contiguous(), dcf, dhf, need_dx=(li > 0 or need_input_grad),
                                                  dout_masked=masked[h], dx_mask=below, background=(li > 0),
                                                  warm=(cb['gates'], cb['cs']) if cb is not None else None,
-                                                 acc=acc, finish=bool(h))
+                                                 acc=acc, finish=bool(h), dx_valid_only=(li > 0))
                     ops.wait_event(getattr(layers[li], 'warm_event', None))
                     masked[h] = below is not None
                     if not h:

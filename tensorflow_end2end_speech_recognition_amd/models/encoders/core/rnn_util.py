@@ -40,6 +40,41 @@ BG_WGS = int(_os.environ.get('ASR_BG_WGS', '128'))   # workgroups of a weight-gr
 # and the layer below cannot start before it, while its BPTT kernel then left half the chip idle for 2 ms.
 # ASR_DW_AFTER_DX=0: never, =1: always.
 DW_AFTER_DX_FLOPS = {'0': float('inf'), '1': 0.0}.get(_os.environ.get('ASR_DW_AFTER_DX', ''), 2e11)
+# the products between two recurrences (x W_x + b, and the dx a layer hands to the layer below) on valid frames only: the
+# recurrence kernels load the rows of padded frames and discard them through their `active` selects (as they do what they
+# derive from such a row: the gates and cell state an inactive row of the cluster forward kernel stores at its parked
+# position, a padded frame, and the BPTT kernel fetches from there), so those rows are never used as values and the lean
+# NT GEMM skips them (ops.gemm(rows=...), asr_gemm_rows; the headline batch is 46 %
+# padding: 51 row tiles instead of 94).  bf16-operand LSTMLayer stacks; ASR_GEMM_VALID_ROWS=0: the full products (A-B).
+VALID_ROWS = _os.environ.get('ASR_GEMM_VALID_ROWS', '1') != '0'
+
+
+def valid_rows(lens, T, B=None):
+    """The rows of a time-major [T, B] frame matrix that hold a valid frame, ascending: {t * B + b : t < lens[b]} as an
+    int32 numpy vector.  lens: host lengths (clamped to [0, T]); B > len(lens) appends zero-length rows (the batch
+    padding of the recurrence kernels' 16-utterance tiles), which contribute nothing."""
+    lens = np.minimum(np.maximum(np.asarray(lens, dtype=np.int64).ravel(), 0), int(T))
+    B = lens.size if B is None else int(B)
+    if B < lens.size:
+        raise ValueError('valid_rows: %d lengths for a batch of %d' % (lens.size, B))
+    if B > lens.size:
+        lens = np.concatenate([lens, np.zeros(B - lens.size, dtype=np.int64)])
+    live = np.arange(int(T), dtype=np.int64)[:, None] < lens[None, :]
+    return np.flatnonzero(live.ravel()).astype(np.int32)
+
+
+def row_plans(lens_host, batch, T, Bp, split=0):
+    """One valid_rows list per pipeline of an encoder call -- the whole padded batch [T, Bp], or with split > 0 the two
+    parts [T, split] and [T, Bp - split], each indexed in ITS OWN layout -- from the host lengths of the `batch` real
+    utterances; None (no plan: the layers run the full products) when the switch is off or the lengths are not there."""
+    if not VALID_ROWS or lens_host is None:
+        return None
+    lens = np.asarray(lens_host).ravel()
+    if lens.size != batch or batch > Bp:
+        return None
+    full = np.concatenate([lens.astype(np.int64), np.zeros(Bp - batch, dtype=np.int64)])
+    parts = ((0, split), (split, Bp)) if split else ((0, Bp),)
+    return [valid_rows(full[lo:hi], T) for lo, hi in parts]
 
 
 def declare_lstm_vars(store, scope, din, H, ndir, use_peephole, parameter_init, rng, cell_scope=None):
@@ -110,17 +145,21 @@ class LSTMLayer(object):
         return ops.dropout_apply(t, *mask) if isinstance(mask, tuple) else ops.apply_mask(t, mask)
 
     def forward(self, x, seq_len, dtype, keep_prob=1.0, is_training=True, rng_state=None,
-                drop_mask=None, save=True, prep=None, mask_event=None):
+                drop_mask=None, save=True, prep=None, mask_event=None, rows=None):
         """x [T,B,ldk] in `dtype` (ldk >= din: columns din.. are zero padding); returns
-        (out [T,B,ndir*H] in dtype, (c_final, h_final))."""
+        (out [T,B,ndir*H] in dtype, (c_final, h_final)).
+        rows: (int32 device vector, count), the valid frames of [T,B] (valid_rows) -- the x-projection is then computed
+        for those rows only (the recurrence kernel discards what it loads from the others)."""
         T, B, ldk = x.shape
         H, ndir = self.H, self.ndir
         if prep is None:
             prep = self.prepare(x.device, dtype, T, B, keep_prob, is_training, rng_state, drop_mask, ldk=ldk)
         xproj = torch.empty((T, B, ndir * 4 * H), dtype=torch.float32, device=x.device)
         # x W_x + b for both directions in ONE GEMM (N = ndir*4H), written in the interleaved layout
+        if dtype == ASR_F32:
+            rows = None   # (bf16 operands only: the fp32 products do not run on the lean NT kernels)
         ops.gemm(x.view(T * B, ldk), prep['wxT'], transB=True, bias=prep['bias'],
-                 out=xproj.view(T * B, ndir * 4 * H))
+                 out=xproj.view(T * B, ndir * 4 * H), **({'rows': rows} if rows is not None else {}))
         gates, hout, cs, cf, hf = ops.lstm_fwd(xproj, prep['whf'], prep['peep'], seq_len, H, ndir, dtype,
                                                self.forget_bias, self.cell_clip or 0.0)
         out = hout
@@ -131,11 +170,11 @@ class LSTMLayer(object):
             out = self._masked(hout, mask)
         if save:
             self.ctx = dict(x=x, gates=gates, cs=cs, hout=hout, whb=prep['whb'], peep=prep['peep'],
-                            seq_len=seq_len, dtype=dtype, mask=mask, wx_cat=prep['wx_cat'])
+                            seq_len=seq_len, dtype=dtype, mask=mask, wx_cat=prep['wx_cat'], rows=rows)
         return out, (cf, hf)
 
     def backward(self, dout, d_c_final=None, d_h_final=None, need_dx=True, dout_masked=False, dx_mask=None,
-                 background=False, warm=None, acc=None, finish=True):
+                 background=False, warm=None, acc=None, finish=True, dx_valid_only=False):
         """dout [T,B,ndir*H] fp32 -> dx [T,B,din] fp32 (or None).  Fills store.grad.
         acc / finish (the encoder's two half-batch pipelines, blstm.py): finish=False leaves the weight gradients of THIS
         part of the batch in self.acc = dict(dw_il, dpeep) instead of the variables; the twin layer that handles the other
@@ -145,7 +184,11 @@ class LSTMLayer(object):
         dx_mask: dropout mask [T,B,din] of the layer BELOW: dx comes back already multiplied with it (in the epilogue
         of the dx GEMM), i.e. ready to be passed to that layer's backward with dout_masked=True.
         background: another recurrence kernel follows (the layer below's BPTT): the weight-gradient GEMMs then have a
-        millisecond to finish beside it and run on few workgroups without split-K slabs, whose traffic would slow it."""
+        millisecond to finish beside it and run on few workgroups without split-K slabs, whose traffic would slow it.
+        dx_valid_only: dx ends in the BPTT kernel of the layer below (the encoder's loop says so), reached only through
+        elementwise steps that keep a row to itself -- the sum with a sub-task head's gradient, that layer's dropout mask:
+        with a row plan from the forward pass its padded frames are then left unwritten, and that kernel discards what it
+        loads from them.  Off (the default, and for the bottom layer's input gradient) every row of dx is written."""
         c = self.ctx
         st = self.store
         dtype = c['dtype']
@@ -172,11 +215,13 @@ class LSTMLayer(object):
         dg2d = dgates.view(T * B, ndir * 4 * H)
         dx = torch.empty((T, B, din), dtype=torch.float32, device=x.device) if need_dx else None
         if need_dx:   # the only result the layer below waits for: main stream, first
+            rows = c.get('rows') if dx_valid_only else None
+            listed = {'rows': rows} if rows is not None else {}
             if isinstance(dx_mask, tuple):
-                ops.gemm(dg2d, c['wx_cat'], transB=True, out=dx.view(T * B, din), drop=dx_mask)
+                ops.gemm(dg2d, c['wx_cat'], transB=True, out=dx.view(T * B, din), drop=dx_mask, **listed)
             else:
                 ops.gemm(dg2d, c['wx_cat'], transB=True, out=dx.view(T * B, din),
-                         mul=dx_mask.view(T * B, din) if dx_mask is not None else None)
+                         mul=dx_mask.view(T * B, din) if dx_mask is not None else None, **listed)
             if FORK_ONCE and background and 2.0 * T * B * din * ndir * 4 * H >= DW_AFTER_DX_FLOPS:
                 fork = ops.stream_event()
         # weight gradients: side streams (one per direction), concurrent with the BPTT kernel of the layer

@@ -396,6 +396,7 @@ class _VGGRecurrentMixin(object):
             lens_host = ops.host_ints(inputs_seq_len)
         x = self.front.forward(inputs.contiguous(), float(keep_prob), is_training,
                                rng_state or (self.seed, 1 << 50), seq_len=lens_host)
+        self._lens_host = lens_host   # the recurrent stack plans on the same host lengths (consumed there)
         return super(_VGGRecurrentMixin, self).__call__(x, inputs_seq_len, keep_prob, is_training, drop_masks,
                                                         rng_state)
 

@@ -409,10 +409,12 @@ def colsum(a, out=None):
 
 # ---------------------------------------------------------------- GEMM
 def gemm(A, B, transA=False, transB=False, bias=None, out=None, out_dtype=None, accumulate=False, relu=False,
-         mul=None, drop=None):
+         mul=None, drop=None, rows=None):
     """C = op(A) @ op(B) (+bias) (+C).  A, B 2-D, same dtype (f32 or bf16), row stride = ld.
     mul: fp32 [M,N] multiplier of the result (a dropout mask); drop = (keep_prob, seed, offset): the same multiplier
-    formed from the dropout generator's counter in the epilogue -- dropout_mask((M, N), ...) without the tensor."""
+    formed from the dropout generator's counter in the epilogue -- dropout_mask((M, N), ...) without the tensor.
+    rows = (int32 device vector, count): only the rows of the result that the ASCENDING list names have to be right
+    (asr_gemm_rows: fp32 output; the others are left as they were or written, the caller must not care which)."""
     h = _h(A)
     dt = dtype_id(A.dtype)
     if B.dtype != A.dtype:
@@ -433,6 +435,28 @@ def gemm(A, B, transA=False, transB=False, bias=None, out=None, out_dtype=None, 
             raise ValueError('gemm: bad out shape %s' % (tuple(out.shape),))
     if bias is not None:
         _chk(bias, torch.float32, 'bias')
+    if rows is not None:
+        rt, nr = rows
+        nr = int(nr)
+        _chk(rt, torch.int32, 'rows')
+        if odt != ASR_F32 or rt.dim() != 1 or not rt.is_contiguous() or not 0 <= nr <= min(rt.numel(), M):
+            raise ValueError('gemm: rows needs an fp32 output and a contiguous int32 vector of at least `count` <= M rows')
+        if mul is not None and drop is not None:
+            raise ValueError('gemm: rows takes mul or drop, not both')
+        if drop is not None and (not out.is_contiguous() or N % 4):
+            raise ValueError('gemm: drop needs a contiguous fp32 output with N % 4 == 0')
+        if mul is not None:
+            _chk(mul, torch.float32, 'mul')
+            if mul.dim() != 2 or mul.shape != (M, N) or mul.stride(1) != 1:
+                raise ValueError('gemm: mul needs an fp32 output and an fp32 [M,N] multiplier')
+        keep, seed, off = (float(drop[0]), int(drop[1]), int(drop[2])) if drop is not None else (0.0, 0, 0)
+        h.check(h.lib.asr_gemm_rows(h.h, dt, int(transA), int(transB), M, N, K,
+                                    C.c_void_p(A.data_ptr()), A.stride(0), C.c_void_p(B.data_ptr()), B.stride(0),
+                                    C.c_void_p(out.data_ptr()), out.stride(0), _p(bias), int(accumulate),
+                                    1 if relu else 0, C.c_void_p(mul.data_ptr()) if mul is not None else None,
+                                    mul.stride(0) if mul is not None else 0,
+                                    keep, seed, off, C.c_void_p(rt.data_ptr()), nr, _s()), 'asr_gemm_rows')
+        return out
     if drop is not None:
         if odt != ASR_F32 or not out.is_contiguous() or N % 4:
             raise ValueError('gemm: drop needs a contiguous fp32 output with N % 4 == 0')
@@ -1408,6 +1432,28 @@ def conv_path_counts(device=0):
 def reset_conv_path_counts(device=0):
     for h in _device_handles(device):
         h.check(h.lib.asr_reset_conv_path_counts(h.h), 'asr_reset_conv_path_counts')
+
+
+# the ASR_GEMMP_* enum of include/asr_hip.h, in its order
+_GEMM_PATH_KEYS = ('rows_128', 'rows_256', 'rows_full')
+
+
+def gemm_path_counts(device=0):
+    """What the listed-row products (gemm(..., rows=...)) on `device` ran since the last reset, summed over its handles
+    (asr_gemm_path_counts): listed-row launches of the 128 x 128 and of the 256 x 256 NT kernel, and calls that ignored
+    their list and ran the full product.  Host counters: no device work, no synchronisation."""
+    n = len(_GEMM_PATH_KEYS)
+    tot = [0] * n
+    for h in _device_handles(device):
+        out = (C.c_ulonglong * n)()
+        h.check(h.lib.asr_gemm_path_counts(h.h, out, n), 'asr_gemm_path_counts')
+        tot = [a + int(b) for a, b in zip(tot, out)]
+    return dict(zip(_GEMM_PATH_KEYS, tot))
+
+
+def reset_gemm_path_counts(device=0):
+    for h in _device_handles(device):
+        h.check(h.lib.asr_reset_gemm_path_counts(h.h), 'asr_reset_gemm_path_counts')
 
 
 def debug_set_cluster_cu_budget(n):
