@@ -2,7 +2,8 @@
 """Evaluate a trained attention (or joint CTC-attention) model on the TIMIT test set -- the recipe of
 examples/timit/evaluation/eval_attention.py.
 
-    python examples/timit/evaluation/eval_attention.py <model_path> [--epoch E] [--joint]
+    python examples/timit/evaluation/eval_attention.py <model_path> [--epoch E] [--joint] [--beam_width W]
+                                                        [--length_penalty_weight A]
 
 <model_path> is a run directory of train_attention.py / train_joint_ctc_attention.py."""
 import argparse
@@ -29,6 +30,10 @@ def main(argv=None):
     ap.add_argument('--eval_batch_size', type=int, default=1)
     ap.add_argument('--joint', action='store_true', help='the run is a joint CTC-attention model')
     ap.add_argument('--device', default=None)
+    # the reference's flag defaults to 20 but reaches nothing (its beam search decoder cannot be constructed): what it
+    # evaluates at its default is the greedy decode, and so does 1 here
+    ap.add_argument('--beam_width', type=int, default=1, help='beam search width (1: greedy decoding)')
+    ap.add_argument('--length_penalty_weight', type=float, default=0.0, help='length penalty of the beam search scores')
     args = ap.parse_args(argv)
     with open(join(args.model_path, 'config.yml'), 'r') as f:
         params = yaml.safe_load(f)['param']
@@ -54,7 +59,8 @@ def main(argv=None):
     _, _, test_data = make_datasets(Dataset, params, map_dir)
     print('Test Data Evaluation:')
     ev = dict(session=None, decode_op=None, model=model, dataset=test_data, label_type=params['label_type'],
-              is_test=True, eval_batch_size=args.eval_batch_size, map_dir=map_dir, is_jointctcatt=args.joint)
+              is_test=True, eval_batch_size=args.eval_batch_size, map_dir=map_dir, is_jointctcatt=args.joint,
+              beam_width=args.beam_width, length_penalty_weight=args.length_penalty_weight)
     if 'char' in params['label_type']:
         cer, wer = do_eval_cer(**ev)
         print('  CER: %f %%' % (cer * 100))

@@ -815,6 +815,70 @@ typedef struct asr_att_infer {
 } asr_att_infer;
 int asr_att_decoder_infer(asr_handle* h, const asr_att_decoder* a, const asr_att_infer* f, int* steps_issued,
                           asr_stream s);
+/* ---- beam search over the attention decoder, native (later within ABI 5) ------------------------------------ *
+ * The reference's BeamSearchDecoder (models/attention/decoders/beam_search/beam_search_decoder.py; dead code there: it
+ * imports an RNNDecoder that does not exist, the functions below are complete).  Per utterance W slots; the device batch
+ * is R = B*W rows, row b*W + w.
+ *
+ * asr_att_beam_select: beam_search_step (beam_search_decoder.py:234-332) with mask_probs (util.py:37-68) and
+ * normalize_score (util.py:71-95), one workgroup per utterance, fp32.  logits [B*W,C2]; state in: log_probs [B*W],
+ * finished / lengths [B*W] int32.  p = log_softmax(row); a finished row has p[eos] = 0 and nothing else;
+ * total = log_probs + p; candidate length = lengths + (c != eos && !finished); score = total / ((5 + len)^lpw / 6^lpw)
+ * -- QUIRK kept: lpw == 1 leaves score = total (util.py:90-91).  first_step != 0: only slot 0's candidates count
+ * (:287-290).  The W best by (score descending, flat index w*C2 + c ascending: tf.nn.top_k's order) give
+ * word = flat % C2, parent = flat / C2 [B,W], score [B,W], and the next state: log_probs = total,
+ * finished = finished[parent] | word == eos, lengths = lengths[parent] + (word != eos && !finished_next).  The state may
+ * be updated in place (out == in).  unfinished (or NULL): += the number of unfinished slots of the next state.
+ * 1 <= W <= 32, W <= C2, 0 <= eos < C2.
+ * asr_att_beam_reorder: what step k+1 reads becomes the parent's (tf.gather by beam_parent_ids, :206-212, and
+ * helper.next_inputs on the chosen ids, :224-228): row r = b*W + w of c_dst / h_dst [R,U], of columns Em.. of din_dst
+ * [R,Em+E2+U] (previous context | previous h) and, with T > 0, of alpha_dst [R,T] is row b*W + parent[r] of the *_src
+ * array; columns 0..Em of din_dst are embedding row word[r] (vocab rows).  Out of place: no dst may alias its src.
+ * asr_att_beam_backtrace: gather_tree_py (util.py:14-26) over the first `steps` rows of word / parent [To,B,W], one thread
+ * per (utterance, final slot): ids [B,W,To] = the path that ends in that slot, cut behind its first eos (zeros there),
+ * hyp_len [B,W] = ids kept (the eos included), final_score [B,W] = score[steps-1]. */
+int asr_att_beam_select(asr_handle* h, const float* logits, int B, int W, int C2, int eos, float length_penalty_weight,
+                        int first_step, const float* log_probs_in, const int32_t* finished_in, const int32_t* lengths_in,
+                        int32_t* word, int32_t* parent, float* score, float* log_probs_out, int32_t* finished_out,
+                        int32_t* lengths_out, int32_t* unfinished, asr_stream s);
+int asr_att_beam_reorder(asr_handle* h, const int32_t* parent, const int32_t* word, int B, int W, int U, int Em, int E2,
+                         int T, int vocab, const float* c_src, const float* h_src, const float* din_src,
+                         const float* alpha_src, const float* embedding, float* c_dst, float* h_dst, float* din_dst,
+                         float* alpha_dst, asr_stream s);
+int asr_att_beam_backtrace(asr_handle* h, const int32_t* word, const int32_t* parent, const float* score, int steps, int To,
+                           int B, int W, int eos, int32_t* ids, int32_t* hyp_len, float* final_score, asr_stream s);
+/* asr_att_decoder_beam: the whole search from ONE call (BeamSearchDecoder.step under dynamic_decode, :173-231; finalize,
+ * :125-150).  Per step it issues the forward step of asr_att_decoder_fwd and the output head exactly as
+ * asr_att_decoder_infer does, on all R rows (no imputation: a->live is [R] ones), then asr_att_beam_select and
+ * asr_att_beam_reorder; after the last step asr_att_beam_backtrace.  `a`: B = R, To = max_decode_length, encoder
+ * arrays tiled to R rows; the loop carries ONE step of state, so the step arrays are two row blocks -- dec_in [2,R,Din],
+ * c_all / h_all [2,R,U]: block 0 is what a step reads (the caller fills it: embedding(start) | zero context | h0; c0; h0,
+ * each utterance's row repeated W times), block 1 receives the step's raw outputs, which the reorder gathers back into
+ * block 0 -- and av_in / alpha_all / snorm_all / gates_all / craw_all / qz_all are one step long.  a->alpha_zero is not
+ * read: the carried weights are m->alpha_prev ([R,T], zeros on entry).  `f`: W_av, W_out, b_out, embedding, C2, eos,
+ * host_live_count, check_every (its array fields are not used).  Early exit as asr_att_decoder_infer, on m->unfinished
+ * ([To+1]; entry k+1 = unfinished slots after step k): surplus steps change nothing -- an utterance whose slots have
+ * all finished has exactly W finite candidates, in their standing order.  *steps_issued = the steps the back-trace
+ * covers. */
+typedef struct asr_att_beam {
+  int W;
+  float length_penalty_weight;
+  int32_t *word, *parent;                       /* [To,B/W utterances,W] per-step outputs */
+  float *score;                                 /* [To,B/W,W] */
+  float *log_probs;                             /* state [R]: zeros on entry */
+  int32_t *finished, *lengths;                  /* state [R]: zeros on entry */
+  float *alpha_prev;                            /* [R,T] (carry_alpha) or NULL */
+  float *av, *logits;                           /* scratch [R,U], [R,C2] */
+  int32_t *unfinished;                          /* [To+1] */
+  int32_t *ids, *hyp_len;                       /* [B/W,W,To], [B/W,W] */
+  float *final_score;                           /* [B/W,W] */
+} asr_att_beam;
+int asr_att_decoder_beam(asr_handle* h, const asr_att_decoder* a, const asr_att_infer* f, const asr_att_beam* m,
+                         int* steps_issued, asr_stream s);
+/* Launches of the three beam kernels on this handle since the last reset, {select, reorder, backtrace} (host integers,
+ * like asr_att_path_counts; a list of their own so that the ASR_ATT_* enum keeps its length). */
+int asr_att_beam_counts(asr_handle* h, unsigned long long* out3);
+int asr_reset_att_beam_counts(asr_handle* h);
 /* work: B*(5*U + 3*T + E2) floats.  dav_cell is consumed (its rows accumulate the query-path gradient in place). */
 int asr_att_decoder_bwd(asr_handle* h, const asr_att_decoder* a, asr_stream s);
 /* out[b, j] = x[b*ldx + j] + y[b*ldy + j], j < W (row blocks of wider arrays; out may alias x) */

@@ -144,6 +144,13 @@ SIGNATURES = {
     'asr_att_decoder_fwd': (_i, [_vp, _vp, _vp]),
     'asr_att_decoder_bwd': (_i, [_vp, _vp, _vp]),
     'asr_att_decoder_infer': (_i, [_vp, _vp, _vp, _vp, _vp]),
+    # beam search over the attention decoder (later within ABI 5)
+    'asr_att_beam_select': (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i] + [_vp] * 10 + [_vp]),
+    'asr_att_beam_reorder': (_i, [_vp, _vp, _vp] + [_i] * 7 + [_vp] * 9 + [_vp]),
+    'asr_att_beam_backtrace': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    'asr_att_decoder_beam': (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    'asr_att_beam_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
+    'asr_reset_att_beam_counts': (_i, [_vp]),
     'asr_add_cols': (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp]),
     'asr_tanh_fwd': (_i, [_vp, _vp, _vp, _sz, _vp]),
     'asr_tanh_bwd': (_i, [_vp, _vp, _vp, _vp, _sz, _vp]),

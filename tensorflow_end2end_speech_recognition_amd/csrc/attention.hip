@@ -2429,6 +2429,78 @@ extern "C" int asr_att_decoder_infer(asr_handle* h, const asr_att_decoder* a, co
   return ASR_OK;
 }
 
+// ---------------------------------------------------------------- beam search loop, native
+// BeamSearchDecoder.step under dynamic_decode (beam_search/beam_search_decoder.py:173-231) and finalize (:125-150).  The
+// loop carries one step of state: block 0 of dec_in / c_all / h_all is what a step reads, block 1 takes its raw
+// outputs, and the reorder kernel gathers block 1 back into block 0 by parent -- so every step is dec_fwd_step at
+// k = 0 with a next row, the very launches asr_att_decoder_infer issues, and the carried attention weights are the
+// `alpha_zero` of that step.  Early exit: the scheme of asr_att_decoder_infer on the count of unfinished slots.
+extern "C" int asr_att_decoder_beam(asr_handle* h, const asr_att_decoder* a_, const asr_att_infer* f, const asr_att_beam* m,
+                                    int* steps_issued, asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  if (!a_ || !m) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_beam: bad arguments");
+  asr_att_decoder d = *a_;
+  if (d.carry_alpha) d.alpha_zero = m->alpha_prev;
+  const asr_att_decoder* a = &d;
+  DEC_TRY(dec_check(h, a, false));
+  if (!f || !f->W_av || !f->W_out || !f->embedding || f->C2 < 1 || f->eos < 0 || f->eos >= f->C2 || a->dmask || m->W < 1 ||
+      m->W > 32 || m->W > f->C2 || a->B % m->W != 0 || !m->word || !m->parent || !m->score || !m->log_probs || !m->finished ||
+      !m->lengths || !m->av || !m->logits || !m->unfinished || !m->ids || !m->hyp_len || !m->final_score ||
+      (a->carry_alpha && !m->alpha_prev))
+    ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_beam: bad arguments");
+  const int R = a->B, W = m->W, Bu = R / W, U = a->U, E2 = a->E2, Em = a->Em, To = a->To, C2 = f->C2, T = a->T;
+  const int Din = Em + E2 + U, Dav = U + E2;
+  hipStream_t st = (hipStream_t)s;
+  if (hipMemsetAsync(m->unfinished, 0, (size_t)(To + 1) * sizeof(int32_t), st) != hipSuccess)
+    ASR_FAIL(h, ASR_ERR_HIP, "asr_att_decoder_beam: memset");
+  constexpr int NEV = 3;
+  hipEvent_t ev[NEV] = {nullptr, nullptr, nullptr};
+  const int every = (f->host_live_count && f->check_every > 0) ? f->check_every : 0;
+  if (every) {
+    for (int i = 0; i < NEV; ++i)
+      if (hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) != hipSuccess) {
+        for (int j = 0; j < i; ++j) (void)hipEventDestroy(ev[j]);
+        ASR_FAIL(h, ASR_ERR_HIP, "asr_att_decoder_beam: event");
+      }
+  }
+  float* din1 = a->dec_in + (size_t)R * Din;
+  float* c1 = a->c_all + (size_t)R * U;
+  float* h1 = a->h_all + (size_t)R * U;
+  int rc = dec_cell_image(h, a, s), k = 0;
+  for (; rc == ASR_OK && k < To; ++k) {
+    if (every && k % every == 0 && k > 0) {                // (see asr_att_decoder_infer)
+      const int c = k / every;
+      bool done = false;
+      if (c >= 3) {
+        (void)hipEventSynchronize(ev[(c - 2) % NEV]);
+        done = f->host_live_count[(c - 2) * every] == 0;
+      }
+      if (!done && c >= 2 && hipEventQuery(ev[(c - 1) % NEV]) == hipSuccess) done = f->host_live_count[(c - 1) * every] == 0;
+      if (done) break;
+      if (hipMemcpyAsync(f->host_live_count + k, m->unfinished + k, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
+          hipEventRecord(ev[c % NEV], st) != hipSuccess) { rc = ASR_ERR_HIP; break; }
+    }
+    if ((rc = dec_fwd_step(h, a, 0, 0, true, s)) != ASR_OK) break;
+    if ((rc = asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, R, U, Dav, a->av_in, Dav, f->W_av, U, m->av, U, nullptr, 0, 0, s)) != ASR_OK) break;
+    if ((rc = asr_tanh_fwd(h, m->av, m->av, (size_t)R * U, s)) != ASR_OK) break;
+    if ((rc = asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, R, C2, U, m->av, U, f->W_out, C2, m->logits, C2, f->b_out, 0, 0, s)) != ASR_OK) break;
+    const size_t o = (size_t)k * R;
+    if ((rc = asr_att_beam_select(h, m->logits, Bu, W, C2, f->eos, m->length_penalty_weight, k == 0, m->log_probs, m->finished,
+                                  m->lengths, m->word + o, m->parent + o, m->score + o, m->log_probs, m->finished, m->lengths,
+                                  m->unfinished + k + 1, s)) != ASR_OK) break;
+    if ((rc = asr_att_beam_reorder(h, m->parent + o, m->word + o, Bu, W, U, Em, E2, a->carry_alpha ? T : 0, C2, c1, h1, din1,
+                                   a->carry_alpha ? a->alpha_all : nullptr, f->embedding, a->c_all, a->h_all, a->dec_in,
+                                   a->carry_alpha ? m->alpha_prev : nullptr, s)) != ASR_OK) break;
+  }
+  if (every)
+    for (int i = 0; i < NEV; ++i) (void)hipEventDestroy(ev[i]);
+  if (rc != ASR_OK) return rc;                             // (the failing call has set the message)
+  if (k < 1) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_beam: no step issued");
+  DEC_TRY(asr_att_beam_backtrace(h, m->word, m->parent, m->score, k, To, Bu, W, f->eos, m->ids, m->hyp_len, m->final_score, s));
+  if (steps_issued) *steps_issued = k;
+  return ASR_OK;
+}
+
 extern "C" int asr_att_decoder_bwd(asr_handle* h, const asr_att_decoder* a, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
   DEC_TRY(dec_check(h, a, true));

@@ -37,6 +37,7 @@ from .decoders import attention_layer as AL
 from .decoders.attention_decoder import (AttentionDecoder, AttentionDecoderOutput, GreedyEmbeddingHelper,  # noqa: F401
                                          LSTMDecoderCell, TrainingHelper)
 from .decoders.attention_layer import AttentionLayer
+from .decoders.beam_search.util import check_beam_width
 
 D = 'attention_decoder/decoder/'
 AT = D + 'attention_layer/'
@@ -84,7 +85,7 @@ class AttentionSeq2Seq(ModelBase):
         self.sos_index, self.eos_index = sos_index, eos_index
         self.max_decode_length = max_decode_length
         self.logits_temperature = logits_temperature
-        self.use_beam_search = False
+        self.use_beam_search = False          # (the reference's switch, dead there; beam search is infer(beam_width=...))
         self.parameter_init = parameter_init
         self.clip_grad_norm = clip_grad_norm
         self.clip_activation_encoder = clip_activation_encoder
@@ -615,13 +616,82 @@ class AttentionSeq2Seq(ModelBase):
         outputs, _ = decoder((c, h), helper)
         return outputs.predicted_ids[:B]
 
-    def infer(self, inputs, inputs_seq_len, native=True):
-        """Greedy inference ids [B, <= max_decode_length] (numpy) for a batch of features -- what running the
-        reference's `decode_op_infer` with a feed_dict of inputs / inputs_seq_len / keep_prob = 1 returns
-        (examples/timit/metrics/attention.py:80-86).  native: see _decode_infer."""
+    def _decode_beam(self, inputs, isl, beam_width, length_penalty_weight=0.0):
+        """Beam search decode (the reference's BeamSearchDecoder, decoders/beam_search/beam_search_decoder.py, which its
+        model cannot construct -- the functions are complete and are what this runs): per utterance beam_width
+        hypotheses on a device batch of B * beam_width rows, ONE call (ops.att_decoder_beam -> asr_att_decoder_beam)
+        that issues every step -- the greedy loop's decoder step and output head, the selection, the re-ordering of
+        what the next step reads -- and the back-trace, then one read-back.  Returns the best hypothesis per utterance,
+        ids [B, <= max_decode_length], zeros behind the first <EOS>; self._beam_raw keeps every hypothesis (ids
+        [B,W,To], hyp_len, scores: slot 0 is the best) and the per-step word / parent / score arrays.  Encoder outputs
+        and keys are tiled to the B * beam_width rows here (reading them through row / W is a follow-up).
+        length_penalty_weight None is 0.0 (the reference raises); 1 leaves the scores un-normalised, its quirk."""
+        W = check_beam_width(beam_width, self.num_classes)
+        st, dev = self.store, self.device
+        B = inputs.shape[0]
+        enc, seq_p = self._encode(inputs, isl, 1.0, False)
+        T, Bp, E2 = enc.shape
+        cf, hf = self.encoder._final_ch
+        _, c, h = self._bridge(cf, hf, B)
+        U, Em, A = self.decoder_num_units, self.embedding_dim, self.key_dim
+        To, Din = int(self.max_decode_length), self.dec_in_dim
+        R = B * W
+        rows = torch.arange(B, device=dev).repeat_interleave(W)          # device row b*W + w reads utterance b
+        keys = self._keys(enc)
+        keys = keys.index_select(1, rows).contiguous() if keys is not None else None
+        enc_att = (self.encoder._out_op if self.dtype == ASR_BF16 else enc).index_select(1, rows).contiguous()
+        has_q = self.attention_type in AL.HAS_QUERY_FC
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)          # noqa: E731
+        dec_in = f32(2, R, Din)
+        emb0 = ops.embedding_gather(st['output_embedding/W_embedding'],
+                                    torch.full((R,), self.sos_index, dtype=torch.int32, device=dev))
+        h0 = h.index_select(0, rows)
+        dec_in[0, :, :Em].copy_(emb0)
+        dec_in[0, :, Em:Em + E2].zero_()
+        dec_in[0, :, Em + E2:].copy_(h0)
+        c_all, h_all = f32(2, R, U), f32(2, R, U)
+        c_all[0].copy_(c.index_select(0, rows))
+        h_all[0].copy_(h0)
+        loop = dict(To=To, B=R, T=T, U=U, Em=Em, E2=E2, A=A, att_mode=self.att_mode, has_query_fc=int(has_q),
+                    carry_alpha=int(self.carry_alpha), taps=int(st[AT + 'filter'].shape[0]) if self.carry_alpha else 0,
+                    enc_dtype=ops.dtype_id(enc_att.dtype), forget_bias=1.0,
+                    cell_clip=float(self.clip_activation_decoder or 0.0), sharpening=float(self.sharpening_factor),
+                    W_cell=self._w_cell(), b_cell=st[D + 'lstm_cell/bias'], cell_bf16=(self.dtype == ASR_BF16),
+                    peep=self._peep(),
+                    W_q=self._wq() if has_q else None,
+                    b_q=st[AT + 'W_filter/biases'] if (has_q and self.attention_type in AL.HAS_FILTER) else None,
+                    v=st[AT + 'v_a'] if self.att_mode == 0 else None, keys=keys, enc=enc_att,
+                    seq_len=seq_p.index_select(0, rows).contiguous(),
+                    filt=st[AT + 'filter'] if self.carry_alpha else None,
+                    wfil=st[AT + 'W_filter/weights'] if self.carry_alpha else None, alpha_zero=None,
+                    live=torch.ones((R,), dtype=torch.float32, device=dev), dmask=None, dec_in=dec_in,
+                    av_in=f32(1, R, U + E2), alpha_all=f32(1, R, T),
+                    snorm_all=f32(1, R) if self.sigmoid_smoothing else None,
+                    gates_all=f32(1, R, 4 * U), craw_all=f32(1, R, U), c_all=c_all, h_all=h_all, qz_all=f32(1, R, A))
+        out = ops.att_decoder_beam(loop, st[D + 'attentional_vector/weights'], st[D + 'output_layer/weights'],
+                                   st[D + 'output_layer/biases'], st['output_embedding/W_embedding'], self.eos_index,
+                                   beam_width=W, length_penalty_weight=length_penalty_weight)
+        # the ONE read-back of the decode: hypotheses, their lengths and their scores as one array
+        packed = torch.cat([out['ids'].reshape(B, W * To), out['hyp_len'],
+                            out['final_score'].contiguous().view(torch.int32)], dim=1).cpu().numpy()
+        ids = packed[:, :W * To].reshape(B, W, To)
+        hyp_len = packed[:, W * To:W * To + W]
+        scores = np.ascontiguousarray(packed[:, W * To + W:]).view(np.float32)
+        self._beam_raw = dict(out, ids=ids, hyp_len=hyp_len, scores=scores, B=B, beam_width=W)
+        return np.ascontiguousarray(ids[:, 0, :int(hyp_len[:, 0].max())])
+
+    def infer(self, inputs, inputs_seq_len, native=True, beam_width=1, length_penalty_weight=0.0):
+        """Inference ids [B, <= max_decode_length] (numpy) for a batch of features -- what running the reference's
+        `decode_op_infer` with a feed_dict of inputs / inputs_seq_len / keep_prob = 1 returns
+        (examples/timit/metrics/attention.py:80-86).  beam_width 1: greedy decoding (native: see _decode_infer);
+        beam_width > 1: the best hypothesis of the beam search (_decode_beam; it has the native form only)."""
         self.encoder._lens_host = ops.host_ints(inputs_seq_len)
         inputs = ops.to_device(inputs, torch.float32, self.device)
         isl = ops.to_device(inputs_seq_len, torch.int32, self.device)
+        if int(beam_width) != 1:
+            if not native:
+                raise ValueError('beam search decoding has the native form only')
+            return self._decode_beam(inputs, isl, beam_width, length_penalty_weight)
         return self._decode_infer(inputs, isl, native=native).cpu().numpy()
 
     def decode(self, decoder_outputs_train, decoder_outputs_infer):

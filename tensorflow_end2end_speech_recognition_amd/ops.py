@@ -1851,6 +1851,162 @@ def att_decoder_infer(a, W_av, W_out, b_out, embedding, eos, n_live, check_every
     return out
 
 
+# ---------------------------------------------------------------- beam search over the attention decoder
+MAX_BEAM_WIDTH = 32
+
+
+def _beam_width(beam_width, C2):
+    W = int(beam_width)
+    if W < 1 or W > MAX_BEAM_WIDTH:
+        raise ValueError('beam_width must be in 1 .. %d, got %d' % (MAX_BEAM_WIDTH, W))
+    if W > int(C2):
+        raise ValueError('beam_width %d exceeds the %d classes step 0 selects among' % (W, int(C2)))
+    return W
+
+
+def _i32(shape, dev):
+    return torch.empty(shape, dtype=torch.int32, device=dev)
+
+
+def att_beam_select(logits, beam_width, eos, length_penalty_weight, first_step, log_probs, finished, lengths,
+                    unfinished=None):
+    """One beam search selection per utterance (asr_att_beam_select; beam_search_step, beam_search_decoder.py:234-332).
+    logits [B*W,C2]; log_probs [B*W] fp32, finished / lengths [B*W] int32: the state before the step (left unchanged).
+    Returns word, parent [B,W] int32, score [B,W], and the next state log_probs, finished, lengths [B*W].
+    length_penalty_weight None is 0.0; unfinished: an int32 word the count of unfinished slots is added to."""
+    h = _h(logits)
+    R, C2 = logits.shape
+    W = _beam_width(beam_width, C2)
+    if R % W:
+        raise ValueError('att_beam_select: %d rows are not a multiple of beam_width %d' % (R, W))
+    B, dev = R // W, logits.device
+    _chk(logits, torch.float32, 'logits')
+    _chk(log_probs, torch.float32, 'log_probs')
+    _chk(finished, torch.int32, 'finished')
+    _chk(lengths, torch.int32, 'lengths')
+    word, parent, score = _i32((B, W), dev), _i32((B, W), dev), _f32((B, W), dev)
+    lp, fin, ln = _f32((R,), dev), _i32((R,), dev), _i32((R,), dev)
+    a = 0.0 if length_penalty_weight is None else float(length_penalty_weight)
+    h.check(h.lib.asr_att_beam_select(h.h, _p(logits), B, W, int(C2), int(eos), a, int(bool(first_step)), _p(log_probs),
+                                      _p(finished), _p(lengths), _p(word), _p(parent), _p(score), _p(lp), _p(fin), _p(ln),
+                                      _p(unfinished), _s()), 'asr_att_beam_select')
+    return word, parent, score, lp, fin, ln
+
+
+def att_beam_reorder(parent, word, c_src, h_src, din_src, alpha_src, embedding):
+    """What the next decoder step reads, gathered by parent within each utterance (asr_att_beam_reorder): parent / word
+    [B,W] int32; c_src / h_src [B*W,U], din_src [B*W,Em+E2+U], alpha_src [B*W,T] or None.  Returns new c, h, din (its
+    embedding columns = embedding[word]) and alpha (None without alpha_src)."""
+    h = _h(c_src)
+    B, W = parent.shape
+    R, U = c_src.shape
+    Em = int(embedding.shape[1])
+    E2 = din_src.shape[1] - Em - U
+    T = int(alpha_src.shape[1]) if alpha_src is not None else 0
+    for t, dt, n in ((parent, torch.int32, 'parent'), (word, torch.int32, 'word'), (c_src, torch.float32, 'c_src'),
+                     (h_src, torch.float32, 'h_src'), (din_src, torch.float32, 'din_src'), (embedding, torch.float32, 'embedding')):
+        _chk(t, dt, n)
+    if R != B * W or h_src.shape != c_src.shape or din_src.shape[0] != R or E2 < 1 or (alpha_src is not None and alpha_src.shape[0] != R):
+        raise ValueError('att_beam_reorder: shapes disagree')
+    c, hh, din = torch.empty_like(c_src), torch.empty_like(h_src), torch.empty_like(din_src)
+    alpha = torch.empty_like(alpha_src) if alpha_src is not None else None
+    h.check(h.lib.asr_att_beam_reorder(h.h, _p(parent), _p(word), B, W, U, Em, E2, T, int(embedding.shape[0]), _p(c_src),
+                                       _p(h_src), _p(din_src), _p(alpha_src), _p(embedding), _p(c), _p(hh), _p(din),
+                                       _p(alpha), _s()), 'asr_att_beam_reorder')
+    return c, hh, din, alpha
+
+
+def att_beam_backtrace(word, parent, score, steps, eos):
+    """gather_tree_py over the first `steps` rows of word / parent [To,B,W] int32, cut behind the first <EOS>
+    (asr_att_beam_backtrace).  Returns ids [B,W,To] int32, hyp_len [B,W] int32, final_score [B,W]."""
+    h = _h(word)
+    To, B, W = word.shape
+    _chk(word, torch.int32, 'word')
+    _chk(parent, torch.int32, 'parent')
+    _chk(score, torch.float32, 'score')
+    ids, n, fs = _i32((B, W, To), word.device), _i32((B, W), word.device), _f32((B, W), word.device)
+    h.check(h.lib.asr_att_beam_backtrace(h.h, _p(word), _p(parent), _p(score), int(steps), To, B, W, int(eos), _p(ids), _p(n),
+                                         _p(fs), _s()), 'asr_att_beam_backtrace')
+    return ids, n, fs
+
+
+class _AttBeam(C.Structure):
+    """struct asr_att_beam (include/asr_hip.h), field for field."""
+    _PTRS = ['word', 'parent', 'score', 'log_probs', 'finished', 'lengths', 'alpha_prev', 'av', 'logits', 'unfinished', 'ids',
+             'hyp_len', 'final_score']
+    _fields_ = [('W', C.c_int), ('length_penalty_weight', C.c_float)] + [(n, C.c_void_p) for n in _PTRS]
+
+
+def att_decoder_beam(a, W_av, W_out, b_out, embedding, eos, beam_width, length_penalty_weight=0.0, check_every=8):
+    """Beam search decode from one call (asr_att_decoder_beam).  `a`: the struct's fields as for att_decoder_fwd with
+    B = utterances * beam_width rows (row b*W + w; encoder arrays tiled by the caller), To = max_decode_length, live [R]
+    ones, and ONE step of state: dec_in [2,R,Din], c_all / h_all [2,R,U] (block 0 filled by the caller), av_in [1,R,U+E2],
+    alpha_all [1,R,T], gates_all / craw_all / qz_all one step.  Returns a dict, everything on the device and nothing
+    synchronised: word, parent [To,B,W] int32 and score [To,B,W] per step; ids [B,W,To] (0 behind the first <EOS>),
+    hyp_len [B,W], final_score [B,W] (slot 0 is the best hypothesis); the final state log_probs, finished, lengths
+    [B,W]; unfinished [To+1]; and steps_issued (host int)."""
+    h = _h(a['dec_in'])
+    dev = a['dec_in'].device
+    To, R, U = a['To'], a['B'], a['U']
+    C2 = W_out.shape[1]
+    W = _beam_width(beam_width, C2)
+    if R % W:
+        raise ValueError('att_decoder_beam: %d rows are not a multiple of beam_width %d' % (R, W))
+    B = R // W
+    if a.get('work') is None:
+        a['work'] = _f32((R * (5 * U + a['T'] + a['E2']),), dev)
+    _cell_gemm_image(h, a)
+    out = dict(word=_i32((To, B, W), dev), parent=_i32((To, B, W), dev), score=_f32((To, B, W), dev),
+               log_probs=torch.zeros((B, W), dtype=torch.float32, device=dev),
+               finished=torch.zeros((B, W), dtype=torch.int32, device=dev),
+               lengths=torch.zeros((B, W), dtype=torch.int32, device=dev), unfinished=_i32((To + 1,), dev),
+               ids=_i32((B, W, To), dev), hyp_len=_i32((B, W), dev), final_score=_f32((B, W), dev))
+    scratch = dict(av=_f32((R, U), dev), logits=_f32((R, C2), dev),
+                   alpha_prev=torch.zeros((R, a['T']), dtype=torch.float32, device=dev) if a.get('carry_alpha') else None)
+    if a.get('carry_alpha') and a.get('alpha_zero') is None:
+        a['alpha_zero'] = scratch['alpha_prev']
+    host = torch.ones((To + 1,), dtype=torch.int32).pin_memory() if check_every else None
+    st = _att_decoder_struct(a)
+    f = _AttInfer()
+    for n, t in (('W_av', W_av), ('W_out', W_out), ('b_out', b_out), ('embedding', embedding)):
+        if t is not None and (not t.is_cuda or not t.is_contiguous()):
+            raise ValueError('att_decoder_beam: %s must be a contiguous device tensor' % n)
+        setattr(f, n, t.data_ptr() if t is not None else None)
+    f.C2, f.eos, f.check_every = int(C2), int(eos), int(check_every or 0)
+    f.host_live_count = host.data_ptr() if host is not None else None
+    m = _AttBeam()
+    m.W = W
+    m.length_penalty_weight = 0.0 if length_penalty_weight is None else float(length_penalty_weight)
+    for n in _AttBeam._PTRS:
+        t = out.get(n, scratch.get(n))
+        setattr(m, n, t.data_ptr() if t is not None else None)
+    issued = C.c_int(0)
+    h.check(h.lib.asr_att_decoder_beam(h.h, C.byref(st), C.byref(f), C.byref(m), C.byref(issued), _s()), 'asr_att_decoder_beam')
+    out['steps_issued'] = issued.value
+    out['_host'] = host                      # keeps the pinned words (and the scratch) alive until the caller has synchronised
+    out['_scratch'] = scratch
+    return out
+
+
+_ATT_BEAM_KEYS = ('select', 'reorder', 'backtrace')
+
+
+def att_beam_counts(device=0):
+    """Launches of the beam search kernels on `device` since the last reset, summed over its handles
+    (asr_att_beam_counts).  Host counters: no device work, no synchronisation."""
+    tot = [0] * 3
+    for h in _device_handles(device):
+        out = (C.c_ulonglong * 3)()
+        h.check(h.lib.asr_att_beam_counts(h.h, out), 'asr_att_beam_counts')
+        tot = [x + int(y) for x, y in zip(tot, out)]
+    return dict(zip(_ATT_BEAM_KEYS, tot))
+
+
+def reset_att_beam_counts(device=0):
+    for h in _device_handles(device):
+        h.check(h.lib.asr_reset_att_beam_counts(h.h), 'asr_reset_att_beam_counts')
+
+
 def tanh_fwd(x):
     h = _h(x)
     y = torch.empty_like(x)
