@@ -3,7 +3,7 @@
 examples/timit/evaluation/eval_attention.py.
 
     python examples/timit/evaluation/eval_attention.py <model_path> [--epoch E] [--joint] [--beam_width W]
-                                                        [--length_penalty_weight A]
+                                                        [--length_penalty_weight A] [--ctc_weight L]
 
 <model_path> is a run directory of train_attention.py / train_joint_ctc_attention.py."""
 import argparse
@@ -34,7 +34,11 @@ def main(argv=None):
     # evaluates at its default is the greedy decode, and so does 1 here
     ap.add_argument('--beam_width', type=int, default=1, help='beam search width (1: greedy decoding)')
     ap.add_argument('--length_penalty_weight', type=float, default=0.0, help='length penalty of the beam search scores')
+    ap.add_argument('--ctc_weight', type=float, default=0.0,
+                    help='weight of the CTC prefix scores in the beam search (joint models only; 0: attention scores alone)')
     args = ap.parse_args(argv)
+    if args.ctc_weight != 0.0 and not args.joint:
+        ap.error('--ctc_weight needs --joint: only a joint CTC-attention model has a CTC head')
     with open(join(args.model_path, 'config.yml'), 'r') as f:
         params = yaml.safe_load(f)['param']
     if args.device:
@@ -60,7 +64,7 @@ def main(argv=None):
     print('Test Data Evaluation:')
     ev = dict(session=None, decode_op=None, model=model, dataset=test_data, label_type=params['label_type'],
               is_test=True, eval_batch_size=args.eval_batch_size, map_dir=map_dir, is_jointctcatt=args.joint,
-              beam_width=args.beam_width, length_penalty_weight=args.length_penalty_weight)
+              beam_width=args.beam_width, length_penalty_weight=args.length_penalty_weight, ctc_weight=args.ctc_weight)
     if 'char' in params['label_type']:
         cer, wer = do_eval_cer(**ev)
         print('  CER: %f %%' % (cer * 100))

@@ -879,6 +879,80 @@ int asr_att_decoder_beam(asr_handle* h, const asr_att_decoder* a, const asr_att_
  * like asr_att_path_counts; a list of their own so that the ASR_ATT_* enum keeps its length). */
 int asr_att_beam_counts(asr_handle* h, unsigned long long* out3);
 int asr_reset_att_beam_counts(asr_handle* h);
+/* ---- joint CTC / attention beam search, native (later within ABI 5, additive) ------------------------------- *
+ * EXTENSION (the reference has no such decoder): one-pass joint decoding (Watanabe et al. 2017, Hori et al. 2017), every
+ * partial hypothesis scored by (1 - ctc_weight) * log p_att + ctc_weight * log p_ctc(prefix).  Float64 statement:
+ * models/attention/decoders/beam_search/ctc_prefix_score.py.  Attention classes C2 = n_labels + 2 (<SOS> = n_labels,
+ * <EOS> = n_labels + 1), CTC classes Cc > n_labels with blank >= n_labels (the models: Cc = n_labels + 1, blank = n_labels);
+ * label c of one is label c of the other.  y [T,By,Cc] fp32 log-posteriors, utterance b < B in batch row b (By >= B: the
+ * posteriors are NOT tiled to the B*W device rows, row r reads b = r / W); seq_len [B].  Prefix state r [B*W,2,T] fp32:
+ * r[row,0,t] / r[row,1,t] = log-probability of the frame paths over 0..t that collapse to the row's hypothesis and end in a
+ * non-blank / a blank; entries t >= seq_len[b] are neither read nor written.  last [B*W] int32: the hypothesis's last
+ * label, -1 when it is empty.  1 <= W <= 32.
+ *
+ * asr_log_softmax_rows: y = x - logsumexp(x) per row of x [rows,cols] (one wave per row; log(asr_softmax_rows) would lose
+ * the small posteriors).  y may be x.
+ * asr_ctc_prefix_init: the empty hypothesis in every row -- r_n = -inf, r_b[t] = sum of y[tau,b,blank] over tau <= t,
+ * summed sequentially in ascending tau; last = -1, ctc_score = 0 (either may be NULL).
+ * asr_ctc_prefix_score: psi [B*W,K] for the candidates cand [B*W,K] (attention class ids, K <= 64): for a label the
+ * log-probability that the utterance's collapsed CTC output STARTS WITH hypothesis.label, for <EOS> log p_ctc(hypothesis),
+ * for <SOS> or an id outside 0 .. n_labels + 1 -inf; a row with finished != 0 (finished may be NULL) has -inf but for
+ * <EOS>.  An infeasible prefix is exactly -inf, never NaN.  One wave per row, a lane per candidate; psi of a label is
+ * logsumexp over t of phi[t] + y[t,b,c] (phi from r, shared by the row), summed 64 frames at a time in ascending t.
+ * asr_ctc_prefix_advance: r_dst row b*W + w = the state of (hypothesis of row b*W + parent[b,w]) . word[b,w]: the
+ * recursion's r_n' / r_b' for a label (T dependent steps of two logaddexp, one wave per row), the parent's arrays bit for
+ * bit for <EOS> (which is also every finished parent's word).  last_src is the PARENTS' array.  Out of place.
+ * asr_att_beam_select_joint: asr_att_beam_select with fused scores.  Per unfinished slot the candidates are its W best
+ * classes other than <EOS> by attention logit (ties by lower index) and <EOS> -- with attention-only scores that pruning
+ * is lossless, here it is the preselection (the "CTC pre-beam"), fixed at W; a finished slot has its <EOS> alone, p = 0;
+ * first_step: slot 0 only.  total = log_probs + log_softmax(logits)[c]; ctc = psi, or ctc_score_in of a finished slot;
+ * a candidate with ctc = -inf is dropped; score = ((1 - ctc_weight) * total + ctc_weight * ctc) / penalty(length) with the
+ * length rule and the lpw == 1 quirk of asr_att_beam_select; the W best by (score descending, flat index ascending) give
+ * word / parent / score [B,W] and the next state log_probs = total (attention alone: the weight applies to totals),
+ * ctc_score = ctc, finished, lengths, last = word (the parent's for <EOS>).  State out may be state in.  Three launches
+ * (candidates, asr_ctc_prefix_score's kernel, rank); cand / cand_total / psi: scratch [B*W,W+1].  W <= n_labels + 1,
+ * 0 < ctc_weight <= 1 (0 is asr_att_beam_select's job).  seq_len >= 1 is the caller's contract (the statement raises; the
+ * entries cannot look at device lengths).  At 0 frames nothing faults: the utterance has the empty hypothesis alone
+ * (psi(<EOS>) = 0, labels -inf), and a place no candidate with a finite CTC score reaches -- only possible there -- comes out
+ * as a finished <EOS> slot (parent = the place, the parent's ctc_score and last) with score and log_probs -inf. */
+int asr_log_softmax_rows(asr_handle* h, const float* x, float* y, size_t rows, int cols, asr_stream s);
+int asr_ctc_prefix_init(asr_handle* h, const float* y, const int32_t* seq_len, int B, int W, int T, int By, int Cc,
+                        int blank, float* r, int32_t* last, float* ctc_score, asr_stream s);
+int asr_ctc_prefix_score(asr_handle* h, const float* y, const int32_t* seq_len, int B, int W, int T, int By, int Cc,
+                         int blank, int n_labels, const float* r, const int32_t* last, const int32_t* finished,
+                         const int32_t* cand, int K, float* psi, asr_stream s);
+int asr_ctc_prefix_advance(asr_handle* h, const float* y, const int32_t* seq_len, int B, int W, int T, int By, int Cc,
+                           int blank, int n_labels, const float* r_src, const int32_t* last_src, const int32_t* parent,
+                           const int32_t* word, float* r_dst, asr_stream s);
+int asr_att_beam_select_joint(asr_handle* h, const float* logits, int B, int W, int n_labels, float length_penalty_weight,
+                              float ctc_weight, int first_step, const float* y, const int32_t* seq_len, int T, int By, int Cc,
+                              int blank, const float* r, const float* log_probs_in, const int32_t* finished_in,
+                              const int32_t* lengths_in, const int32_t* last_in, const float* ctc_score_in, int32_t* cand,
+                              float* cand_total, float* psi, int32_t* word, int32_t* parent, float* score,
+                              float* log_probs_out, int32_t* finished_out, int32_t* lengths_out, int32_t* last_out,
+                              float* ctc_score_out, int32_t* unfinished, asr_stream s);
+/* asr_att_decoder_beam_joint: asr_att_decoder_beam with asr_att_beam_select_joint as its selection and
+ * asr_ctc_prefix_advance behind it -- the same per-step issue, early exit and back-trace; a, f, m as there (f->C2 must be
+ * n_labels + 2, f->eos n_labels + 1).  The call initialises the prefix state itself (asr_ctc_prefix_init) and flips
+ * between the two blocks of r / last every step.  Surplus steps change nothing: a finished slot keeps total, ctc_score
+ * and its state.  T is a->T. */
+typedef struct asr_att_beam_ctc {
+  const float *y;                               /* [T,By,Cc] log-posteriors */
+  const int32_t *seq_len;                       /* [B/W utterances] */
+  int By, Cc, blank, n_labels;
+  float ctc_weight;                             /* in (0, 1] */
+  float *r;                                     /* state [2,R,2,T] (two blocks, no initialisation needed) */
+  int32_t *last;                                /* state [2,R] */
+  float *ctc_score;                             /* [R]: out, the hypotheses' CTC scores after the last step */
+  int32_t *cand;                                /* scratch [R,W+1] */
+  float *cand_total, *psi;                      /* scratch [R,W+1] each */
+} asr_att_beam_ctc;
+int asr_att_decoder_beam_joint(asr_handle* h, const asr_att_decoder* a, const asr_att_infer* f, const asr_att_beam* m,
+                               const asr_att_beam_ctc* j, int* steps_issued, asr_stream s);
+/* Launches on this handle since the last reset, {score, advance, joint_select}: asr_ctc_prefix_score calls (those of
+ * asr_att_beam_select_joint included), asr_ctc_prefix_advance calls, asr_att_beam_select_joint calls. */
+int asr_att_joint_counts(asr_handle* h, unsigned long long* out3);
+int asr_reset_att_joint_counts(asr_handle* h);
 /* work: B*(5*U + 3*T + E2) floats.  dav_cell is consumed (its rows accumulate the query-path gradient in place). */
 int asr_att_decoder_bwd(asr_handle* h, const asr_att_decoder* a, asr_stream s);
 /* out[b, j] = x[b*ldx + j] + y[b*ldy + j], j < W (row blocks of wider arrays; out may alias x) */

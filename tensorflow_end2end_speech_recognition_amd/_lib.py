@@ -151,6 +151,15 @@ SIGNATURES = {
     'asr_att_decoder_beam': (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     'asr_att_beam_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
     'asr_reset_att_beam_counts': (_i, [_vp]),
+    # joint CTC / attention beam search (later within ABI 5)
+    'asr_log_softmax_rows': (_i, [_vp, _vp, _vp, _sz, _i, _vp]),
+    'asr_ctc_prefix_init': (_i, [_vp, _vp, _vp] + [_i] * 6 + [_vp] * 3 + [_vp]),
+    'asr_ctc_prefix_score': (_i, [_vp, _vp, _vp] + [_i] * 7 + [_vp] * 4 + [_i, _vp] + [_vp]),
+    'asr_ctc_prefix_advance': (_i, [_vp, _vp, _vp] + [_i] * 7 + [_vp] * 5 + [_vp]),
+    'asr_att_beam_select_joint': (_i, [_vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _vp, _i, _i, _i, _i] + [_vp] * 18 + [_vp]),
+    'asr_att_decoder_beam_joint': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'asr_att_joint_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
+    'asr_reset_att_joint_counts': (_i, [_vp]),
     'asr_add_cols': (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp]),
     'asr_tanh_fwd': (_i, [_vp, _vp, _vp, _sz, _vp]),
     'asr_tanh_bwd': (_i, [_vp, _vp, _vp, _vp, _sz, _vp]),

@@ -2435,10 +2435,13 @@ extern "C" int asr_att_decoder_infer(asr_handle* h, const asr_att_decoder* a, co
 // outputs, and the reorder kernel gathers block 1 back into block 0 by parent -- so every step is dec_fwd_step at
 // k = 0 with a next row, the very launches asr_att_decoder_infer issues, and the carried attention weights are the
 // `alpha_zero` of that step.  Early exit: the scheme of asr_att_decoder_infer on the count of unfinished slots.
-extern "C" int asr_att_decoder_beam(asr_handle* h, const asr_att_decoder* a_, const asr_att_infer* f, const asr_att_beam* m,
-                                    int* steps_issued, asr_stream s) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  if (!a_ || !m) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_beam: bad arguments");
+// j != nullptr: the joint CTC / attention search (asr_att_decoder_beam_joint) -- the selection is
+// asr_att_beam_select_joint on the prefix state of block k & 1 of j->r / j->last, and asr_ctc_prefix_advance writes the
+// other block from the parents'.  Without j the calls are those this loop has always issued.
+static int att_beam_loop(asr_handle* h, const asr_att_decoder* a_, const asr_att_infer* f, const asr_att_beam* m,
+                         const asr_att_beam_ctc* j, int* steps_issued, asr_stream s) {
+  const char* who = j ? "asr_att_decoder_beam_joint" : "asr_att_decoder_beam";
+  if (!a_ || !m) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "%s: bad arguments", who);
   asr_att_decoder d = *a_;
   if (d.carry_alpha) d.alpha_zero = m->alpha_prev;
   const asr_att_decoder* a = &d;
@@ -2447,20 +2450,26 @@ extern "C" int asr_att_decoder_beam(asr_handle* h, const asr_att_decoder* a_, co
       m->W > 32 || m->W > f->C2 || a->B % m->W != 0 || !m->word || !m->parent || !m->score || !m->log_probs || !m->finished ||
       !m->lengths || !m->av || !m->logits || !m->unfinished || !m->ids || !m->hyp_len || !m->final_score ||
       (a->carry_alpha && !m->alpha_prev))
-    ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_beam: bad arguments");
+    ASR_FAIL(h, ASR_ERR_INVALID_ARG, "%s: bad arguments", who);
   const int R = a->B, W = m->W, Bu = R / W, U = a->U, E2 = a->E2, Em = a->Em, To = a->To, C2 = f->C2, T = a->T;
   const int Din = Em + E2 + U, Dav = U + E2;
   hipStream_t st = (hipStream_t)s;
+  if (j) {
+    if (!j->y || !j->seq_len || !j->r || !j->last || !j->ctc_score || !j->cand || !j->cand_total || !j->psi ||
+        C2 != j->n_labels + 2 || f->eos != j->n_labels + 1)
+      ASR_FAIL(h, ASR_ERR_INVALID_ARG, "%s: bad arguments (the CTC part)", who);
+    DEC_TRY(asr_ctc_prefix_init(h, j->y, j->seq_len, Bu, W, T, j->By, j->Cc, j->blank, j->r, j->last, j->ctc_score, s));
+  }
   if (hipMemsetAsync(m->unfinished, 0, (size_t)(To + 1) * sizeof(int32_t), st) != hipSuccess)
-    ASR_FAIL(h, ASR_ERR_HIP, "asr_att_decoder_beam: memset");
+    ASR_FAIL(h, ASR_ERR_HIP, "%s: memset", who);
   constexpr int NEV = 3;
   hipEvent_t ev[NEV] = {nullptr, nullptr, nullptr};
   const int every = (f->host_live_count && f->check_every > 0) ? f->check_every : 0;
   if (every) {
     for (int i = 0; i < NEV; ++i)
       if (hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) != hipSuccess) {
-        for (int j = 0; j < i; ++j) (void)hipEventDestroy(ev[j]);
-        ASR_FAIL(h, ASR_ERR_HIP, "asr_att_decoder_beam: event");
+        for (int e = 0; e < i; ++e) (void)hipEventDestroy(ev[e]);
+        ASR_FAIL(h, ASR_ERR_HIP, "%s: event", who);
       }
   }
   float* din1 = a->dec_in + (size_t)R * Din;
@@ -2485,9 +2494,22 @@ extern "C" int asr_att_decoder_beam(asr_handle* h, const asr_att_decoder* a_, co
     if ((rc = asr_tanh_fwd(h, m->av, m->av, (size_t)R * U, s)) != ASR_OK) break;
     if ((rc = asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, R, C2, U, m->av, U, f->W_out, C2, m->logits, C2, f->b_out, 0, 0, s)) != ASR_OK) break;
     const size_t o = (size_t)k * R;
-    if ((rc = asr_att_beam_select(h, m->logits, Bu, W, C2, f->eos, m->length_penalty_weight, k == 0, m->log_probs, m->finished,
-                                  m->lengths, m->word + o, m->parent + o, m->score + o, m->log_probs, m->finished, m->lengths,
-                                  m->unfinished + k + 1, s)) != ASR_OK) break;
+    if (j) {
+      const size_t rblk = (size_t)R * 2 * T;
+      float* r_cur = j->r + (size_t)(k & 1) * rblk;
+      float* r_nxt = j->r + (size_t)((k + 1) & 1) * rblk;
+      int32_t* last_cur = j->last + (size_t)(k & 1) * R;
+      int32_t* last_nxt = j->last + (size_t)((k + 1) & 1) * R;
+      if ((rc = asr_att_beam_select_joint(h, m->logits, Bu, W, j->n_labels, m->length_penalty_weight, j->ctc_weight, k == 0,
+                                          j->y, j->seq_len, T, j->By, j->Cc, j->blank, r_cur, m->log_probs, m->finished,
+                                          m->lengths, last_cur, j->ctc_score, j->cand, j->cand_total, j->psi, m->word + o,
+                                          m->parent + o, m->score + o, m->log_probs, m->finished, m->lengths, last_nxt,
+                                          j->ctc_score, m->unfinished + k + 1, s)) != ASR_OK) break;
+      if ((rc = asr_ctc_prefix_advance(h, j->y, j->seq_len, Bu, W, T, j->By, j->Cc, j->blank, j->n_labels, r_cur, last_cur,
+                                       m->parent + o, m->word + o, r_nxt, s)) != ASR_OK) break;
+    } else if ((rc = asr_att_beam_select(h, m->logits, Bu, W, C2, f->eos, m->length_penalty_weight, k == 0, m->log_probs,
+                                         m->finished, m->lengths, m->word + o, m->parent + o, m->score + o, m->log_probs,
+                                         m->finished, m->lengths, m->unfinished + k + 1, s)) != ASR_OK) break;
     if ((rc = asr_att_beam_reorder(h, m->parent + o, m->word + o, Bu, W, U, Em, E2, a->carry_alpha ? T : 0, C2, c1, h1, din1,
                                    a->carry_alpha ? a->alpha_all : nullptr, f->embedding, a->c_all, a->h_all, a->dec_in,
                                    a->carry_alpha ? m->alpha_prev : nullptr, s)) != ASR_OK) break;
@@ -2495,10 +2517,23 @@ extern "C" int asr_att_decoder_beam(asr_handle* h, const asr_att_decoder* a_, co
   if (every)
     for (int i = 0; i < NEV; ++i) (void)hipEventDestroy(ev[i]);
   if (rc != ASR_OK) return rc;                             // (the failing call has set the message)
-  if (k < 1) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_beam: no step issued");
+  if (k < 1) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "%s: no step issued", who);
   DEC_TRY(asr_att_beam_backtrace(h, m->word, m->parent, m->score, k, To, Bu, W, f->eos, m->ids, m->hyp_len, m->final_score, s));
   if (steps_issued) *steps_issued = k;
   return ASR_OK;
+}
+
+extern "C" int asr_att_decoder_beam(asr_handle* h, const asr_att_decoder* a, const asr_att_infer* f, const asr_att_beam* m,
+                                    int* steps_issued, asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  return att_beam_loop(h, a, f, m, nullptr, steps_issued, s);
+}
+
+extern "C" int asr_att_decoder_beam_joint(asr_handle* h, const asr_att_decoder* a, const asr_att_infer* f, const asr_att_beam* m,
+                                          const asr_att_beam_ctc* j, int* steps_issued, asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  if (!j) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_beam_joint: bad arguments");
+  return att_beam_loop(h, a, f, m, j, steps_issued, s);
 }
 
 extern "C" int asr_att_decoder_bwd(asr_handle* h, const asr_att_decoder* a, asr_stream s) {

@@ -81,7 +81,24 @@ class JointCTCAttention(AttentionSeq2Seq):
     def _ctc_head_launch(self, enc, seq_p, ctc_labels, B, lam, is_training):
         """Issue the CTC head (on whatever stream is current -- AttentionSeq2Seq.compute_loss puts it on the side lane);
         nothing here waits for the device."""
-        st, dev = self.store, self.device
+        dev = self.device
+        T, Bp, E2 = enc.shape
+        logits = self._ctc_head_logits(enc)
+        flat, offsets, max_len = CTC._labels_to_flat(ctc_labels, B)
+        if Bp > B:
+            offsets = np.concatenate([offsets, np.full(Bp - B, offsets[-1], dtype=np.int32)])
+        # pinned staging + asynchronous copies: a pageable upload would drain the stream (ops.to_device)
+        flat_d = ops.to_device(flat if len(flat) else np.zeros(1, np.int32), torch.int32, dev)
+        off_d = ops.to_device(offsets, torch.int32, dev)
+        losses, grad, ninf = ops.ctc_loss(logits, flat_d, off_d, seq_p, max_len, grad_scale=lam / B,
+                                          want_grad=is_training)
+        return logits, losses, grad, ninf, flat_d, off_d
+
+    _has_ctc_head = True
+
+    def _ctc_head_logits(self, enc):
+        """The CTC head on the encoder outputs `enc` of the last _encode: logits [T,Bp,C+1] fp32."""
+        st = self.store
         T, Bp, E2 = enc.shape
         Cc = self.ctc_num_classes
         # bf16-operand models: the head multiplies the encoder's operand copy by the operand copy of its weights, as the
@@ -92,17 +109,17 @@ class JointCTCAttention(AttentionSeq2Seq):
         else:
             x_op, w_op = enc.view(T * Bp, E2), st['ctc_output/weights']
         self._ctc_x_op = x_op
-        logits = torch.empty((T, Bp, Cc), dtype=torch.float32, device=dev)
+        logits = torch.empty((T, Bp, Cc), dtype=torch.float32, device=self.device)
         ops.gemm(x_op, w_op, bias=st['ctc_output/biases'], out=logits.view(T * Bp, Cc))
-        flat, offsets, max_len = CTC._labels_to_flat(ctc_labels, B)
-        if Bp > B:
-            offsets = np.concatenate([offsets, np.full(Bp - B, offsets[-1], dtype=np.int32)])
-        # pinned staging + asynchronous copies: a pageable upload would drain the stream (ops.to_device)
-        flat_d = ops.to_device(flat if len(flat) else np.zeros(1, np.int32), torch.int32, dev)
-        off_d = ops.to_device(offsets, torch.int32, dev)
-        losses, grad, ninf = ops.ctc_loss(logits, flat_d, off_d, seq_p, max_len, grad_scale=lam / B,
-                                          want_grad=is_training)
-        return logits, losses, grad, ninf, flat_d, off_d
+        return logits
+
+    def _ctc_log_posteriors(self, enc):
+        """log_softmax of the CTC head's logits [T,Bp,C+1] -- the training path's head on the same operands -- for joint
+        decoding (infer(ctc_weight > 0))."""
+        logits = self._ctc_head_logits(enc)
+        T, Bp, Cc = logits.shape
+        ops.log_softmax_rows(logits.view(T * Bp, Cc), out=logits.view(T * Bp, Cc))
+        return logits
 
     def _ctc_head_finish(self, pending, B):
         logits, losses, grad, ninf = pending[:4]

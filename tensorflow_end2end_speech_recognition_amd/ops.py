@@ -1937,21 +1937,17 @@ class _AttBeam(C.Structure):
     _fields_ = [('W', C.c_int), ('length_penalty_weight', C.c_float)] + [(n, C.c_void_p) for n in _PTRS]
 
 
-def att_decoder_beam(a, W_av, W_out, b_out, embedding, eos, beam_width, length_penalty_weight=0.0, check_every=8):
-    """Beam search decode from one call (asr_att_decoder_beam).  `a`: the struct's fields as for att_decoder_fwd with
-    B = utterances * beam_width rows (row b*W + w; encoder arrays tiled by the caller), To = max_decode_length, live [R]
-    ones, and ONE step of state: dec_in [2,R,Din], c_all / h_all [2,R,U] (block 0 filled by the caller), av_in [1,R,U+E2],
-    alpha_all [1,R,T], gates_all / craw_all / qz_all one step.  Returns a dict, everything on the device and nothing
-    synchronised: word, parent [To,B,W] int32 and score [To,B,W] per step; ids [B,W,To] (0 behind the first <EOS>),
-    hyp_len [B,W], final_score [B,W] (slot 0 is the best hypothesis); the final state log_probs, finished, lengths
-    [B,W]; unfinished [To+1]; and steps_issued (host int)."""
+def _beam_loop_call(what, a, W_av, W_out, b_out, embedding, eos, W, length_penalty_weight, check_every, extra_out=None,
+                    extra_scratch=None):
+    """What att_decoder_beam and att_decoder_beam_joint share: the loop's work space, its outputs and scratch, and the three
+    structs.  Returns (h, st, f, m, out, scratch, host); the caller issues the native call and finishes `out` with
+    _beam_loop_done."""
     h = _h(a['dec_in'])
     dev = a['dec_in'].device
     To, R, U = a['To'], a['B'], a['U']
     C2 = W_out.shape[1]
-    W = _beam_width(beam_width, C2)
     if R % W:
-        raise ValueError('att_decoder_beam: %d rows are not a multiple of beam_width %d' % (R, W))
+        raise ValueError('%s: %d rows are not a multiple of beam_width %d' % (what, R, W))
     B = R // W
     if a.get('work') is None:
         a['work'] = _f32((R * (5 * U + a['T'] + a['E2']),), dev)
@@ -1961,8 +1957,10 @@ def att_decoder_beam(a, W_av, W_out, b_out, embedding, eos, beam_width, length_p
                finished=torch.zeros((B, W), dtype=torch.int32, device=dev),
                lengths=torch.zeros((B, W), dtype=torch.int32, device=dev), unfinished=_i32((To + 1,), dev),
                ids=_i32((B, W, To), dev), hyp_len=_i32((B, W), dev), final_score=_f32((B, W), dev))
+    out.update(extra_out or {})
     scratch = dict(av=_f32((R, U), dev), logits=_f32((R, C2), dev),
                    alpha_prev=torch.zeros((R, a['T']), dtype=torch.float32, device=dev) if a.get('carry_alpha') else None)
+    scratch.update(extra_scratch or {})
     if a.get('carry_alpha') and a.get('alpha_zero') is None:
         a['alpha_zero'] = scratch['alpha_prev']
     host = torch.ones((To + 1,), dtype=torch.int32).pin_memory() if check_every else None
@@ -1970,7 +1968,7 @@ def att_decoder_beam(a, W_av, W_out, b_out, embedding, eos, beam_width, length_p
     f = _AttInfer()
     for n, t in (('W_av', W_av), ('W_out', W_out), ('b_out', b_out), ('embedding', embedding)):
         if t is not None and (not t.is_cuda or not t.is_contiguous()):
-            raise ValueError('att_decoder_beam: %s must be a contiguous device tensor' % n)
+            raise ValueError('%s: %s must be a contiguous device tensor' % (what, n))
         setattr(f, n, t.data_ptr() if t is not None else None)
     f.C2, f.eos, f.check_every = int(C2), int(eos), int(check_every or 0)
     f.host_live_count = host.data_ptr() if host is not None else None
@@ -1980,12 +1978,30 @@ def att_decoder_beam(a, W_av, W_out, b_out, embedding, eos, beam_width, length_p
     for n in _AttBeam._PTRS:
         t = out.get(n, scratch.get(n))
         setattr(m, n, t.data_ptr() if t is not None else None)
-    issued = C.c_int(0)
-    h.check(h.lib.asr_att_decoder_beam(h.h, C.byref(st), C.byref(f), C.byref(m), C.byref(issued), _s()), 'asr_att_decoder_beam')
+    return h, st, f, m, out, scratch, host
+
+
+def _beam_loop_done(out, issued, host, scratch):
     out['steps_issued'] = issued.value
     out['_host'] = host                      # keeps the pinned words (and the scratch) alive until the caller has synchronised
     out['_scratch'] = scratch
     return out
+
+
+def att_decoder_beam(a, W_av, W_out, b_out, embedding, eos, beam_width, length_penalty_weight=0.0, check_every=8):
+    """Beam search decode from one call (asr_att_decoder_beam).  `a`: the struct's fields as for att_decoder_fwd with
+    B = utterances * beam_width rows (row b*W + w; encoder arrays tiled by the caller), To = max_decode_length, live [R]
+    ones, and ONE step of state: dec_in [2,R,Din], c_all / h_all [2,R,U] (block 0 filled by the caller), av_in [1,R,U+E2],
+    alpha_all [1,R,T], gates_all / craw_all / qz_all one step.  Returns a dict, everything on the device and nothing
+    synchronised: word, parent [To,B,W] int32 and score [To,B,W] per step; ids [B,W,To] (0 behind the first <EOS>),
+    hyp_len [B,W], final_score [B,W] (slot 0 is the best hypothesis); the final state log_probs, finished, lengths
+    [B,W]; unfinished [To+1]; and steps_issued (host int)."""
+    W = _beam_width(beam_width, W_out.shape[1])
+    h, st, f, m, out, scratch, host = _beam_loop_call('att_decoder_beam', a, W_av, W_out, b_out, embedding, eos, W,
+                                                      length_penalty_weight, check_every)
+    issued = C.c_int(0)
+    h.check(h.lib.asr_att_decoder_beam(h.h, C.byref(st), C.byref(f), C.byref(m), C.byref(issued), _s()), 'asr_att_decoder_beam')
+    return _beam_loop_done(out, issued, host, scratch)
 
 
 _ATT_BEAM_KEYS = ('select', 'reorder', 'backtrace')
@@ -2005,6 +2021,212 @@ def att_beam_counts(device=0):
 def reset_att_beam_counts(device=0):
     for h in _device_handles(device):
         h.check(h.lib.asr_reset_att_beam_counts(h.h), 'asr_reset_att_beam_counts')
+
+
+# ---------------------------------------------------------------- joint CTC / attention beam search (an extension)
+def log_softmax_rows(x2d, out=None):
+    """x - logsumexp(x) per row of an fp32 [rows, cols] array (asr_log_softmax_rows)."""
+    h = _h(x2d)
+    _chk(x2d, torch.float32, 'x')
+    if x2d.dim() != 2 or x2d.shape[0] < 1 or x2d.shape[1] < 1:
+        raise ValueError('log_softmax_rows: x must be a non-empty [rows, cols] array')
+    out = _out_like(out, tuple(x2d.shape), torch.float32, x2d.device, 'log_softmax_rows')
+    h.check(h.lib.asr_log_softmax_rows(h.h, _p(x2d), _p(out), x2d.shape[0], x2d.shape[1], _s()), 'asr_log_softmax_rows')
+    return out
+
+
+def _joint_shapes(what, y, seq_len, R, n_labels=None, blank=None):
+    """(B, W, T, By, Cc, blank) of a joint-search call on R device rows; y [T,By,Cc] fp32, seq_len [B] int32."""
+    _chk(y, torch.float32, 'y')
+    _chk(seq_len, torch.int32, 'seq_len')
+    if y.dim() != 3 or seq_len.dim() != 1:
+        raise ValueError('%s: y must be [T,By,Cc] and seq_len [B]' % what)
+    T, By, Cc = (int(v) for v in y.shape)
+    B = int(seq_len.shape[0])
+    if B < 1 or B > By or R < B or R % B:
+        raise ValueError('%s: %d rows for %d utterances (y holds %d)' % (what, R, B, By))
+    W = R // B
+    if W > MAX_BEAM_WIDTH:
+        raise ValueError('beam_width must be in 1 .. %d, got %d' % (MAX_BEAM_WIDTH, W))
+    blank = Cc - 1 if blank is None else int(blank)
+    if n_labels is not None and not (1 <= int(n_labels) < Cc and int(n_labels) <= blank < Cc):
+        raise ValueError('%s: %d labels, blank %d, %d CTC classes' % (what, int(n_labels), blank, Cc))
+    if not 0 <= blank < Cc:
+        raise ValueError('%s: blank %d outside the %d CTC classes' % (what, blank, Cc))
+    return B, W, T, By, Cc, blank
+
+
+def _check_ctc_weight(ctc_weight):
+    lam = float(ctc_weight)
+    if not 0.0 < lam <= 1.0:
+        raise ValueError('ctc_weight must be in (0, 1] here (0 is the attention-only beam search), got %r' % (ctc_weight,))
+    return lam
+
+
+def ctc_prefix_init(y, seq_len, beam_width, blank=None):
+    """The prefix state of the empty hypothesis in each of the B * beam_width rows (asr_ctc_prefix_init): y [T,By,Cc] CTC
+    log-posteriors, seq_len [B] int32.  Returns r [R,2,T] (entries at t >= seq_len[b] are not written), last [R] int32
+    (-1) and ctc_score [R] (0)."""
+    h = _h(y)
+    W = int(beam_width)
+    if W < 1 or W > MAX_BEAM_WIDTH:
+        raise ValueError('beam_width must be in 1 .. %d, got %d' % (MAX_BEAM_WIDTH, W))
+    B, W, T, By, Cc, blank = _joint_shapes('ctc_prefix_init', y, seq_len, int(seq_len.numel()) * W, blank=blank)
+    R, dev = B * W, y.device
+    r, last, score = _f32((R, 2, T), dev), _i32((R,), dev), _f32((R,), dev)
+    h.check(h.lib.asr_ctc_prefix_init(h.h, _p(y), _p(seq_len), B, W, T, By, Cc, blank, _p(r), _p(last), _p(score), _s()),
+            'asr_ctc_prefix_init')
+    return r, last, score
+
+
+def _chk_state(what, r, last, T):
+    _chk(r, torch.float32, 'r')
+    _chk(last, torch.int32, 'last')
+    if r.dim() != 3 or r.shape[1] != 2 or r.shape[2] != T or tuple(last.shape) != (r.shape[0],):
+        raise ValueError('%s: r must be [R,2,%d] and last [R]' % (what, T))
+
+
+def ctc_prefix_score(y, seq_len, r, last, finished, cand, n_labels, blank=None):
+    """CTC prefix scores psi [R,K] of the candidates cand [R,K] (int32 attention class ids: labels, <SOS> = n_labels,
+    <EOS> = n_labels + 1) of the hypotheses whose state is r [R,2,T] / last [R] (asr_ctc_prefix_score); finished [R] int32
+    or None: a finished row scores its <EOS> alone.  An infeasible prefix and <SOS> are exactly -inf."""
+    h = _h(y)
+    _chk(cand, torch.int32, 'cand')
+    if cand.dim() != 2 or not 1 <= cand.shape[1] <= 64:
+        raise ValueError('ctc_prefix_score: cand must be [R, 1 .. 64]')
+    R, K = (int(v) for v in cand.shape)
+    B, W, T, By, Cc, blank = _joint_shapes('ctc_prefix_score', y, seq_len, R, n_labels, blank)
+    _chk_state('ctc_prefix_score', r, last, T)
+    if r.shape[0] != R or (finished is not None and tuple(finished.shape) != (R,)):
+        raise ValueError('ctc_prefix_score: state and candidates disagree on the number of rows')
+    if finished is not None:
+        _chk(finished, torch.int32, 'finished')
+    psi = _f32((R, K), y.device)
+    h.check(h.lib.asr_ctc_prefix_score(h.h, _p(y), _p(seq_len), B, W, T, By, Cc, blank, int(n_labels), _p(r), _p(last),
+                                       _p(finished), _p(cand), K, _p(psi), _s()), 'asr_ctc_prefix_score')
+    return psi
+
+
+def ctc_prefix_advance(y, seq_len, r, last, parent, word, n_labels, blank=None):
+    """The prefix state of the selected hypotheses (asr_ctc_prefix_advance): new row b*W + w extends the hypothesis of row
+    b*W + parent[b,w] (state r [R,2,T], last [R]: the parents') by word[b,w]; <EOS> copies.  Returns the new r (out of
+    place: the sources are untouched)."""
+    h = _h(y)
+    _chk(parent, torch.int32, 'parent')
+    _chk(word, torch.int32, 'word')
+    if parent.dim() != 2 or parent.shape != word.shape:
+        raise ValueError('ctc_prefix_advance: parent and word must be [B,W]')
+    R = int(parent.numel())
+    B, W, T, By, Cc, blank = _joint_shapes('ctc_prefix_advance', y, seq_len, R, n_labels, blank)
+    _chk_state('ctc_prefix_advance', r, last, T)
+    if r.shape[0] != R or tuple(parent.shape) != (B, W):
+        raise ValueError('ctc_prefix_advance: state and selection disagree on the number of rows')
+    out = torch.empty_like(r)
+    h.check(h.lib.asr_ctc_prefix_advance(h.h, _p(y), _p(seq_len), B, W, T, By, Cc, blank, int(n_labels), _p(r), _p(last),
+                                         _p(parent), _p(word), _p(out), _s()), 'asr_ctc_prefix_advance')
+    return out
+
+
+def att_beam_select_joint(logits, y, seq_len, r, last, ctc_score, n_labels, ctc_weight, length_penalty_weight, first_step,
+                          log_probs, finished, lengths, unfinished=None, blank=None):
+    """One joint CTC / attention selection per utterance (asr_att_beam_select_joint): att_beam_select on
+    ((1 - ctc_weight) * total_att + ctc_weight * ctc) / penalty over the preselected W + 1 classes of every slot.
+    logits [B*W, n_labels + 2]; y / seq_len / r / last as ctc_prefix_score; ctc_score [B*W] fp32.  Nothing is changed in
+    place.  Returns word, parent [B,W] int32, score [B,W] and the next state log_probs (attention totals), finished,
+    lengths, last, ctc_score [B*W] -- the next r is ctc_prefix_advance(y, seq_len, r, last, parent, word, n_labels)."""
+    h = _h(logits)
+    _chk(logits, torch.float32, 'logits')
+    R, C2 = (int(v) for v in logits.shape)
+    N = int(n_labels)
+    if C2 != N + 2:
+        raise ValueError('att_beam_select_joint: %d attention classes for %d labels' % (C2, N))
+    lam = _check_ctc_weight(ctc_weight)
+    B, W, T, By, Cc, blank = _joint_shapes('att_beam_select_joint', y, seq_len, R, N, blank)
+    _beam_width(W, N + 1)
+    _chk_state('att_beam_select_joint', r, last, T)
+    for t, dt, n in ((log_probs, torch.float32, 'log_probs'), (ctc_score, torch.float32, 'ctc_score'),
+                     (finished, torch.int32, 'finished'), (lengths, torch.int32, 'lengths')):
+        _chk(t, dt, n)
+        if tuple(t.shape) != (R,):
+            raise ValueError('att_beam_select_joint: %s must be [%d]' % (n, R))
+    if r.shape[0] != R:
+        raise ValueError('att_beam_select_joint: r must have %d rows' % R)
+    dev = logits.device
+    word, parent, score = _i32((B, W), dev), _i32((B, W), dev), _f32((B, W), dev)
+    lp, fin, ln, lst, cs = _f32((R,), dev), _i32((R,), dev), _i32((R,), dev), _i32((R,), dev), _f32((R,), dev)
+    cand, tot, psi = _i32((R, W + 1), dev), _f32((R, W + 1), dev), _f32((R, W + 1), dev)
+    a = 0.0 if length_penalty_weight is None else float(length_penalty_weight)
+    h.check(h.lib.asr_att_beam_select_joint(h.h, _p(logits), B, W, N, a, lam, int(bool(first_step)), _p(y), _p(seq_len), T, By,
+                                            Cc, blank, _p(r), _p(log_probs), _p(finished), _p(lengths), _p(last),
+                                            _p(ctc_score), _p(cand), _p(tot), _p(psi), _p(word), _p(parent), _p(score),
+                                            _p(lp), _p(fin), _p(ln), _p(lst), _p(cs), _p(unfinished), _s()),
+            'asr_att_beam_select_joint')
+    return word, parent, score, lp, fin, ln, lst, cs
+
+
+class _AttBeamCtc(C.Structure):
+    """struct asr_att_beam_ctc (include/asr_hip.h), field for field."""
+    _fields_ = [('y', C.c_void_p), ('seq_len', C.c_void_p), ('By', C.c_int), ('Cc', C.c_int), ('blank', C.c_int),
+                ('n_labels', C.c_int), ('ctc_weight', C.c_float), ('r', C.c_void_p), ('last', C.c_void_p),
+                ('ctc_score', C.c_void_p), ('cand', C.c_void_p), ('cand_total', C.c_void_p), ('psi', C.c_void_p)]
+
+
+def att_decoder_beam_joint(a, W_av, W_out, b_out, embedding, eos, beam_width, y, seq_len, ctc_weight,
+                           length_penalty_weight=0.0, check_every=8, blank=None):
+    """Joint CTC / attention beam search decode from one call (asr_att_decoder_beam_joint): att_decoder_beam with
+    y [T,By,Cc], the CTC log-posteriors of the B utterances (NOT tiled; T = a['T']), seq_len [B] int32 and
+    0 < ctc_weight <= 1.  Returns att_decoder_beam's dict (log_probs are the attention totals, score / final_score the
+    fused, length-normalised scores) and ctc_score [B,W].
+    Every seq_len must be >= 1 (not checked here: that would read the device; JointCTCAttention.infer checks its host
+    copy).  An utterance of 0 frames has the empty hypothesis alone: places no candidate with a finite CTC score reaches
+    come out as finished <EOS> slots with score -inf."""
+    dev = a['dec_in'].device
+    R = a['B']
+    C2 = int(W_out.shape[1])
+    N = C2 - 2
+    if int(eos) != N + 1:
+        raise ValueError('att_decoder_beam_joint: <EOS> must be the last of the %d attention classes' % C2)
+    W = _beam_width(beam_width, N + 1)
+    lam = _check_ctc_weight(ctc_weight)
+    if R % W:
+        raise ValueError('att_decoder_beam_joint: %d rows are not a multiple of beam_width %d' % (R, W))
+    B, W2, T, By, Cc, blank = _joint_shapes('att_decoder_beam_joint', y, seq_len, R, N, blank)
+    if W2 != W or T != a['T']:
+        raise ValueError('att_decoder_beam_joint: y [%d,%d,%d] / seq_len [%d] do not fit %d rows of %d frames'
+                         % (T, By, Cc, B, R, a['T']))
+    extra = dict(r=_f32((2, R, 2, T), dev), last=_i32((2, R), dev), cand=_i32((R, W + 1), dev),
+                 cand_total=_f32((R, W + 1), dev), psi=_f32((R, W + 1), dev), y=y, seq_len=seq_len)
+    h, st, f, m, out, scratch, host = _beam_loop_call('att_decoder_beam_joint', a, W_av, W_out, b_out, embedding, eos, W,
+                                                      length_penalty_weight, check_every,
+                                                      extra_out=dict(ctc_score=_f32((B, W), dev)), extra_scratch=extra)
+    j = _AttBeamCtc()
+    j.y, j.seq_len = y.data_ptr(), seq_len.data_ptr()
+    j.By, j.Cc, j.blank, j.n_labels, j.ctc_weight = By, Cc, blank, N, lam
+    j.r, j.last, j.ctc_score = scratch['r'].data_ptr(), scratch['last'].data_ptr(), out['ctc_score'].data_ptr()
+    j.cand, j.cand_total, j.psi = scratch['cand'].data_ptr(), scratch['cand_total'].data_ptr(), scratch['psi'].data_ptr()
+    issued = C.c_int(0)
+    h.check(h.lib.asr_att_decoder_beam_joint(h.h, C.byref(st), C.byref(f), C.byref(m), C.byref(j), C.byref(issued), _s()),
+            'asr_att_decoder_beam_joint')
+    return _beam_loop_done(out, issued, host, scratch)
+
+
+_ATT_JOINT_KEYS = ('score', 'advance', 'joint_select')
+
+
+def att_joint_counts(device=0):
+    """Launches of the joint-search entry points on `device` since the last reset, summed over its handles
+    (asr_att_joint_counts).  Host counters: no device work, no synchronisation."""
+    tot = [0] * 3
+    for h in _device_handles(device):
+        out = (C.c_ulonglong * 3)()
+        h.check(h.lib.asr_att_joint_counts(h.h, out), 'asr_att_joint_counts')
+        tot = [x + int(y) for x, y in zip(tot, out)]
+    return dict(zip(_ATT_JOINT_KEYS, tot))
+
+
+def reset_att_joint_counts(device=0):
+    for h in _device_handles(device):
+        h.check(h.lib.asr_reset_att_joint_counts(h.h), 'asr_reset_att_joint_counts')
 
 
 def tanh_fwd(x):
