@@ -29,9 +29,13 @@ def _unpack(data, is_multitask, is_jointctcatt):
     return inputs, labels_true, inputs_seq_len, labels_seq_len
 
 
-def _infer(model, inputs, inputs_seq_len, beam_width=1, length_penalty_weight=0.0, ctc_weight=0.0):
+def _infer(model, inputs, inputs_seq_len, beam_width=1, length_penalty_weight=0.0, ctc_weight=0.0, lm=None, lm_weight=0.0):
     """Inference ids [B, <= max_decode_length] (the decode_op_infer of the reference's drivers): greedy at beam_width 1,
     the best beam search hypothesis above."""
+    if lm is not None and float(lm_weight) != 0.0:       # shallow fusion with an RNN language model (any beam width)
+        return np.asarray(model.infer(inputs, inputs_seq_len, beam_width=beam_width,
+                                      length_penalty_weight=length_penalty_weight, ctc_weight=ctc_weight, lm=lm,
+                                      lm_weight=lm_weight))
     if float(ctc_weight) != 0.0:         # joint CTC / attention scores (JointCTCAttention only; any beam width)
         return np.asarray(model.infer(inputs, inputs_seq_len, beam_width=beam_width,
                                       length_penalty_weight=length_penalty_weight, ctc_weight=ctc_weight))
@@ -42,7 +46,7 @@ def _infer(model, inputs, inputs_seq_len, beam_width=1, length_penalty_weight=0.
 
 def do_eval_per(session, decode_op, per_op, model, dataset, label_type, is_test=False, eval_batch_size=None,
                 progressbar=False, is_multitask=False, is_jointctcatt=False, map_dir=None, beam_width=1,
-                length_penalty_weight=0.0, ctc_weight=0.0):
+                length_penalty_weight=0.0, ctc_weight=0.0, lm=None, lm_weight=0.0):
     map_dir = map_dir or '../metrics/mapping_files'
     batch_size_original = dataset.batch_size
     dataset.reset()
@@ -57,7 +61,8 @@ def do_eval_per(session, decode_op, per_op, model, dataset, label_type, is_test=
     per_sum = 0.0
     for data, is_new_epoch in dataset:
         inputs, labels_true, inputs_seq_len, labels_seq_len = _unpack(data, is_multitask, is_jointctcatt)
-        labels_pred = _infer(model, inputs[0], inputs_seq_len[0], beam_width, length_penalty_weight, ctc_weight)
+        labels_pred = _infer(model, inputs[0], inputs_seq_len[0], beam_width, length_penalty_weight, ctc_weight, lm,
+                             lm_weight)
         for b in range(inputs[0].shape[0]):
             str_pred = idx2phone_train(np.asarray(labels_pred[b])).split('>')[0].rstrip(' ')
             pred = [p for p in str_pred.split(' ') if p not in ('', '<')]
@@ -76,7 +81,7 @@ def do_eval_per(session, decode_op, per_op, model, dataset, label_type, is_test=
 
 def do_eval_cer(session, decode_op, model, dataset, label_type, is_test=False, eval_batch_size=None,
                 progressbar=False, is_multitask=False, is_jointctcatt=False, map_dir=None, beam_width=1,
-                length_penalty_weight=0.0, ctc_weight=0.0):
+                length_penalty_weight=0.0, ctc_weight=0.0, lm=None, lm_weight=0.0):
     """-> (mean CER, mean WER)."""
     map_dir = map_dir or '../metrics/mapping_files'
     batch_size_original = dataset.batch_size
@@ -92,7 +97,8 @@ def do_eval_cer(session, decode_op, model, dataset, label_type, is_test=False, e
     cer_sum = wer_sum = 0.0
     for data, is_new_epoch in dataset:
         inputs, labels_true, inputs_seq_len, labels_seq_len = _unpack(data, is_multitask, is_jointctcatt)
-        labels_pred = _infer(model, inputs[0], inputs_seq_len[0], beam_width, length_penalty_weight, ctc_weight)
+        labels_pred = _infer(model, inputs[0], inputs_seq_len[0], beam_width, length_penalty_weight, ctc_weight, lm,
+                             lm_weight)
         for b in range(inputs[0].shape[0]):
             if is_test:
                 str_true = labels_true[0][b][0]

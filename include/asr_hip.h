@@ -953,6 +953,89 @@ int asr_att_decoder_beam_joint(asr_handle* h, const asr_att_decoder* a, const as
  * asr_att_beam_select_joint included), asr_ctc_prefix_advance calls, asr_att_beam_select_joint calls. */
 int asr_att_joint_counts(asr_handle* h, unsigned long long* out3);
 int asr_reset_att_joint_counts(asr_handle* h);
+/* ---- shallow fusion with an RNN language model in the beam search, native (later within ABI 5, additive) ------ *
+ * EXTENSION.  The reference intended it and has none: models/lm/{base,char_rnnlm,word_rnnlm}.py raise NotImplementedError,
+ * models/ctc/decoders/charlm_beam_search_decoder.py is empty, and its CTC BeamSearchDecoder.__call__ takes `alpha`
+ * ("language model weight") and carries `# TODO: add LM score here` (models/ctc/decoders/beam_search_decoder.py:53,61,132).
+ * Shallow fusion as Hori et al. 2017; float64 statement: models/attention/decoders/beam_search/lm_fusion.py.
+ * The LM (models/lm/rnnlm.py): an embedding [C2,Em_lm], L unidirectional LSTMBlockCell layers of H units (forget bias 1, no
+ * peepholes, optional cell clip; gate columns i, ci, f, o), an output layer [H,C2] + bias, over the attention classes C2 =
+ * n_labels + 2.  fp32 throughout.  R = B*W device rows, row b*W + w.
+ *
+ * struct asr_att_lm.  Weights: W = the layers' kernels one behind the other, layer l [(Din_l + H), 4H] with Din_0 = Em_lm,
+ * Din_l = H; b [L,4H].  W_il (optional): the gate-interleaved images one behind the other, layer l (Din_l + H + 1) x 4H floats
+ * -- asr_lm_prep writes the images of the layers for which asr_lstm_cell_gemm_ok(R, Din_l + H, H, Din_l + H) holds, once per
+ * decode, and asr_lm_step then runs those layers' product + cell as one launch (asr_lstm_cell_gemm_fwd); the others (and
+ * every layer without W_il) run asr_gemm_act + asr_lstm_cell_fwd_ex.  asr_lstm_cell_gemm_ok needs R <= 32 and
+ * (Din_l + H) % 64 == 0: both paths are live (asr_att_path_counts: ASR_ATT_FWD_CELL_F32IMG / ASR_ATT_FWD_CELL_GEMM count
+ * these launches too).  State: c / h [2,L,R,H] -- block 0 is what a step reads, block 1 receives the step's new state (as
+ * the beam loop's c_all / h_all); in: the layers' cell-input rows one behind the other, layer 0 [R,Em_lm+H], layer l >= 1
+ * [R,2H], each row x | h_prev, so one product per layer suffices: x of layer 0 is the LM embedding of the row's last word,
+ * x of layer l >= 1 is written by layer l-1's cell (its cell_out2), h_prev by asr_lm_beam_reorder (on entry: embedding of
+ * <SOS> | zeros; c, h block 0 zeros).  live [R] ones; work: R * 10 * H floats.
+ * asr_lm_step, in this order: per layer l = 0 .. L-1 the product + cell (above) from in (layer l), c / h block 0 into c / h
+ * block 1 (and the next layer's x columns); then lm_logits [R,C2] = h block 1 of layer L-1 x W_out + b_out (asr_gemm_act),
+ * raw logits -- no log-softmax pass: the selection normalises them in its own row reduction.
+ * asr_att_beam_select_fused: asr_att_beam_select / _joint on two or three score streams.
+ *  1. candidates kernel, a wave per row: lse_att and lse_lm, each in the order of asr_att_beam_select (lane l takes classes
+ *     l, l + 64, ... ascending into a running maximum, xor butterfly 32 .. 1; the sum of exp(x - max) the same way;
+ *     lse = max + log(sum)); p_att = x - lse_att, p_lm = z - lse_lm; local = p_att + lm_weight * p_lm; the W best classes
+ *     other than <EOS> by local (ties by lower index) and <EOS> -> cand, cand_total = log_probs + p_att,
+ *     cand_lm = lm_score + p_lm [R,W+1].  A finished row: its <EOS> alone with p_att = p_lm = 0; first_step: slot 0 only.
+ *     NOTE the preselection is by the LOCAL fused score, not by the attention logit as asr_att_beam_select_joint's: without
+ *     CTC it is lossless (within a row all classes but <EOS> share length and carried totals), with CTC it is the pre-beam.
+ *  2. ctc_weight > 0: asr_ctc_prefix_score's kernel on cand, unchanged.
+ *  3. rank kernel, a workgroup per utterance: ctc = psi or a finished slot's ctc_score; fused = (1 - ctc_weight) *
+ *     cand_total, + ctc_weight * ctc when ctc_weight > 0, + lm_weight * cand_lm, added in that order;
+ *     score = fused / penalty(length) with the length rule and lpw == 1 quirk of asr_att_beam_select; a candidate with
+ *     ctc = -inf is dropped; the W best by (score descending, flat index ascending) give word / parent / score and the next
+ *     state log_probs = cand_total, lm_score = cand_lm, ctc_score, finished, lengths, last as asr_att_beam_select_joint.
+ *  1 <= W <= 32, W <= C2 - 1, lm_weight > 0 (0 is the other two selections' job), 0 <= ctc_weight <= 1.  ctc_weight == 0:
+ *  y, seq_len, r, last_*, ctc_score_*, psi are not read and may be NULL.  State out may be state in.  With CTC, at 0 frames:
+ *  the documented behaviour of asr_att_beam_select_joint (a place nothing reaches also keeps the parent's lm_score).
+ * asr_lm_beam_reorder: row r = b*W + w of every layer of c_dst / h_dst [L,R,H] is row b*W + parent[r] of c_src / h_src; the
+ * h_prev columns of every layer of in_dst receive the same h rows; the x columns of layer 0 of in_dst are LM embedding row
+ * word[r].  Out of place, one launch for all layers.
+ * asr_att_decoder_beam_lm: the loop of asr_att_decoder_beam (j NULL) / asr_att_decoder_beam_joint (j given, whose
+ * ctc_weight is then in (0, 1]) with, per step on the one stream: the decoder step and head (shared code), asr_lm_step,
+ * asr_att_beam_select_fused, asr_ctc_prefix_advance when j is given, asr_att_beam_reorder (those two in the order of
+ * asr_att_decoder_beam_joint: they are independent of each other), asr_lm_beam_reorder (block 1 -> block 0).  asr_lm_prep runs once before the first step.  Early exit, back-trace and outputs as those loops; lm_score [R]
+ * (zeros on entry) comes out as the hypotheses' LM totals.  Surplus steps change nothing: a finished slot keeps total,
+ * lm_score, ctc_score (its LM state moves on, unread). */
+typedef struct asr_att_lm {
+  int L, H, Em_lm, R, C2;
+  float cell_clip, lm_weight;
+  const float *emb;                             /* [C2,Em_lm] */
+  const float *W, *b;                           /* the layers' [Din_l+H,4H] one behind the other; [L,4H] */
+  const float *W_out, *b_out;                   /* [H,C2], [C2] */
+  float *W_il;                                  /* optional: the layers' (Din_l+H+1) x 4H images one behind the other */
+  float *c, *h;                                 /* state [2,L,R,H] */
+  float *in;                                    /* layer 0 [R,Em_lm+H], layers l >= 1 [R,2H], one behind the other */
+  const float *live;                            /* [R] ones */
+  float *work;                                  /* R * 10 * H floats */
+  float *lm_logits;                             /* [R,C2] */
+  float *lm_score;                              /* state [R]: zeros on entry, out */
+  int32_t *cand;                                /* scratch [R,W+1] (the loop uses these, not the asr_att_beam_ctc's) */
+  float *cand_total, *cand_lm;                  /* scratch [R,W+1] each */
+} asr_att_lm;
+int asr_lm_prep(asr_handle* h, const asr_att_lm* lm, asr_stream s);
+int asr_lm_step(asr_handle* h, const asr_att_lm* lm, asr_stream s);
+int asr_att_beam_select_fused(asr_handle* h, const float* logits, const float* lm_logits, int B, int W, int n_labels,
+                              float length_penalty_weight, float ctc_weight, float lm_weight, int first_step, const float* y,
+                              const int32_t* seq_len, int T, int By, int Cc, int blank, const float* r,
+                              const float* log_probs_in, const int32_t* finished_in, const int32_t* lengths_in,
+                              const int32_t* last_in, const float* ctc_score_in, const float* lm_score_in, int32_t* cand,
+                              float* cand_total, float* cand_lm, float* psi, int32_t* word, int32_t* parent, float* score,
+                              float* log_probs_out, int32_t* finished_out, int32_t* lengths_out, int32_t* last_out,
+                              float* ctc_score_out, float* lm_score_out, int32_t* unfinished, asr_stream s);
+int asr_lm_beam_reorder(asr_handle* h, const int32_t* parent, const int32_t* word, int B, int W, int L, int H, int Em_lm,
+                        int vocab, const float* c_src, const float* h_src, const float* emb, float* c_dst, float* h_dst,
+                        float* in_dst, asr_stream s);
+int asr_att_decoder_beam_lm(asr_handle* h, const asr_att_decoder* a, const asr_att_infer* f, const asr_att_beam* m,
+                            const asr_att_beam_ctc* j, const asr_att_lm* lm, int* steps_issued, asr_stream s);
+/* Calls on this handle since the last reset, {lm_step, fused_select, lm_reorder}. */
+int asr_att_lm_counts(asr_handle* h, unsigned long long* out3);
+int asr_reset_att_lm_counts(asr_handle* h);
 /* work: B*(5*U + 3*T + E2) floats.  dav_cell is consumed (its rows accumulate the query-path gradient in place). */
 int asr_att_decoder_bwd(asr_handle* h, const asr_att_decoder* a, asr_stream s);
 /* out[b, j] = x[b*ldx + j] + y[b*ldy + j], j < W (row blocks of wider arrays; out may alias x) */

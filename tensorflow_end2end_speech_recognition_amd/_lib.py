@@ -160,6 +160,14 @@ SIGNATURES = {
     'asr_att_decoder_beam_joint': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'asr_att_joint_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
     'asr_reset_att_joint_counts': (_i, [_vp]),
+    # shallow fusion with an RNN language model in the beam search (later within ABI 5)
+    'asr_lm_prep': (_i, [_vp, _vp, _vp]),
+    'asr_lm_step': (_i, [_vp, _vp, _vp]),
+    'asr_att_beam_select_fused': (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _i, _vp, _vp, _i, _i, _i, _i] + [_vp] * 21 + [_vp]),
+    'asr_lm_beam_reorder': (_i, [_vp, _vp, _vp] + [_i] * 6 + [_vp] * 6 + [_vp]),
+    'asr_att_decoder_beam_lm': (_i, [_vp] * 8),
+    'asr_att_lm_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
+    'asr_reset_att_lm_counts': (_i, [_vp]),
     'asr_add_cols': (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp]),
     'asr_tanh_fwd': (_i, [_vp, _vp, _vp, _sz, _vp]),
     'asr_tanh_bwd': (_i, [_vp, _vp, _vp, _vp, _sz, _vp]),

@@ -2438,9 +2438,14 @@ extern "C" int asr_att_decoder_infer(asr_handle* h, const asr_att_decoder* a, co
 // j != nullptr: the joint CTC / attention search (asr_att_decoder_beam_joint) -- the selection is
 // asr_att_beam_select_joint on the prefix state of block k & 1 of j->r / j->last, and asr_ctc_prefix_advance writes the
 // other block from the parents'.  Without j the calls are those this loop has always issued.
+// lm != nullptr: shallow fusion with a language model (asr_att_decoder_beam_lm, lm_fusion.hip) -- asr_lm_step behind the
+// head, asr_att_beam_select_fused as the selection (with or without j; a j whose ctc_weight is not in (0, 1] is refused:
+// the fused rank kernel would leave its `last` block unwritten), asr_lm_beam_reorder at the end of the step.  Only the
+// selection differs between the three searches; the state advance and the re-ordering behind it are shared.  Without lm
+// nothing of this is issued.
 static int att_beam_loop(asr_handle* h, const asr_att_decoder* a_, const asr_att_infer* f, const asr_att_beam* m,
-                         const asr_att_beam_ctc* j, int* steps_issued, asr_stream s) {
-  const char* who = j ? "asr_att_decoder_beam_joint" : "asr_att_decoder_beam";
+                         const asr_att_beam_ctc* j, const asr_att_lm* lm, int* steps_issued, asr_stream s) {
+  const char* who = lm ? "asr_att_decoder_beam_lm" : j ? "asr_att_decoder_beam_joint" : "asr_att_decoder_beam";
   if (!a_ || !m) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "%s: bad arguments", who);
   asr_att_decoder d = *a_;
   if (d.carry_alpha) d.alpha_zero = m->alpha_prev;
@@ -2454,6 +2459,12 @@ static int att_beam_loop(asr_handle* h, const asr_att_decoder* a_, const asr_att
   const int R = a->B, W = m->W, Bu = R / W, U = a->U, E2 = a->E2, Em = a->Em, To = a->To, C2 = f->C2, T = a->T;
   const int Din = Em + E2 + U, Dav = U + E2;
   hipStream_t st = (hipStream_t)s;
+  if (lm) {
+    if (lm->R != R || lm->C2 != C2 || f->eos != C2 - 1 || C2 < 3 || W > C2 - 1 || !lm->lm_score || !lm->cand ||
+        !lm->cand_total || !lm->cand_lm || !(lm->lm_weight > 0.f) || (j && !(j->ctc_weight > 0.f && j->ctc_weight <= 1.f)))
+      ASR_FAIL(h, ASR_ERR_INVALID_ARG, "%s: bad arguments (the language model part)", who);
+    DEC_TRY(asr_lm_prep(h, lm, s));
+  }
   if (j) {
     if (!j->y || !j->seq_len || !j->r || !j->last || !j->ctc_score || !j->cand || !j->cand_total || !j->psi ||
         C2 != j->n_labels + 2 || f->eos != j->n_labels + 1)
@@ -2494,25 +2505,43 @@ static int att_beam_loop(asr_handle* h, const asr_att_decoder* a_, const asr_att
     if ((rc = asr_tanh_fwd(h, m->av, m->av, (size_t)R * U, s)) != ASR_OK) break;
     if ((rc = asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, R, C2, U, m->av, U, f->W_out, C2, m->logits, C2, f->b_out, 0, 0, s)) != ASR_OK) break;
     const size_t o = (size_t)k * R;
-    if (j) {
-      const size_t rblk = (size_t)R * 2 * T;
-      float* r_cur = j->r + (size_t)(k & 1) * rblk;
-      float* r_nxt = j->r + (size_t)((k + 1) & 1) * rblk;
-      int32_t* last_cur = j->last + (size_t)(k & 1) * R;
-      int32_t* last_nxt = j->last + (size_t)((k + 1) & 1) * R;
+    // the prefix state of this step and the next (j): blocks k & 1 and (k + 1) & 1
+    const size_t rblk = (size_t)R * 2 * T;
+    float* r_cur = j ? j->r + (size_t)(k & 1) * rblk : nullptr;
+    float* r_nxt = j ? j->r + (size_t)((k + 1) & 1) * rblk : nullptr;
+    int32_t* last_cur = j ? j->last + (size_t)(k & 1) * R : nullptr;
+    int32_t* last_nxt = j ? j->last + (size_t)((k + 1) & 1) * R : nullptr;
+    // the selection: fused with the language model's step in front of it, joint, or attention alone
+    if (lm) {
+      if ((rc = asr_lm_step(h, lm, s)) != ASR_OK) break;
+      if ((rc = asr_att_beam_select_fused(h, m->logits, lm->lm_logits, Bu, W, C2 - 2, m->length_penalty_weight,
+                                          j ? j->ctc_weight : 0.f, lm->lm_weight, k == 0, j ? j->y : nullptr,
+                                          j ? j->seq_len : nullptr, T, j ? j->By : 0, j ? j->Cc : 0, j ? j->blank : 0, r_cur,
+                                          m->log_probs, m->finished, m->lengths, last_cur, j ? j->ctc_score : nullptr,
+                                          lm->lm_score, lm->cand, lm->cand_total, lm->cand_lm, j ? j->psi : nullptr,
+                                          m->word + o, m->parent + o, m->score + o, m->log_probs, m->finished, m->lengths,
+                                          last_nxt, j ? j->ctc_score : nullptr, lm->lm_score, m->unfinished + k + 1,
+                                          s)) != ASR_OK) break;
+    } else if (j) {
       if ((rc = asr_att_beam_select_joint(h, m->logits, Bu, W, j->n_labels, m->length_penalty_weight, j->ctc_weight, k == 0,
                                           j->y, j->seq_len, T, j->By, j->Cc, j->blank, r_cur, m->log_probs, m->finished,
                                           m->lengths, last_cur, j->ctc_score, j->cand, j->cand_total, j->psi, m->word + o,
                                           m->parent + o, m->score + o, m->log_probs, m->finished, m->lengths, last_nxt,
                                           j->ctc_score, m->unfinished + k + 1, s)) != ASR_OK) break;
-      if ((rc = asr_ctc_prefix_advance(h, j->y, j->seq_len, Bu, W, T, j->By, j->Cc, j->blank, j->n_labels, r_cur, last_cur,
-                                       m->parent + o, m->word + o, r_nxt, s)) != ASR_OK) break;
     } else if ((rc = asr_att_beam_select(h, m->logits, Bu, W, C2, f->eos, m->length_penalty_weight, k == 0, m->log_probs,
                                          m->finished, m->lengths, m->word + o, m->parent + o, m->score + o, m->log_probs,
                                          m->finished, m->lengths, m->unfinished + k + 1, s)) != ASR_OK) break;
+    // what the next step reads: the prefix state of the winners (j), the decoder's rows, the language model's rows (lm)
+    if (j && (rc = asr_ctc_prefix_advance(h, j->y, j->seq_len, Bu, W, T, j->By, j->Cc, j->blank, j->n_labels, r_cur, last_cur,
+                                          m->parent + o, m->word + o, r_nxt, s)) != ASR_OK) break;
     if ((rc = asr_att_beam_reorder(h, m->parent + o, m->word + o, Bu, W, U, Em, E2, a->carry_alpha ? T : 0, C2, c1, h1, din1,
                                    a->carry_alpha ? a->alpha_all : nullptr, f->embedding, a->c_all, a->h_all, a->dec_in,
                                    a->carry_alpha ? m->alpha_prev : nullptr, s)) != ASR_OK) break;
+    if (lm) {
+      const size_t lblk = (size_t)lm->L * R * lm->H;       // block 1 (the step's new state) -> block 0
+      if ((rc = asr_lm_beam_reorder(h, m->parent + o, m->word + o, Bu, W, lm->L, lm->H, lm->Em_lm, C2, lm->c + lblk,
+                                    lm->h + lblk, lm->emb, lm->c, lm->h, lm->in, s)) != ASR_OK) break;
+    }
   }
   if (every)
     for (int i = 0; i < NEV; ++i) (void)hipEventDestroy(ev[i]);
@@ -2526,14 +2555,21 @@ static int att_beam_loop(asr_handle* h, const asr_att_decoder* a_, const asr_att
 extern "C" int asr_att_decoder_beam(asr_handle* h, const asr_att_decoder* a, const asr_att_infer* f, const asr_att_beam* m,
                                     int* steps_issued, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  return att_beam_loop(h, a, f, m, nullptr, steps_issued, s);
+  return att_beam_loop(h, a, f, m, nullptr, nullptr, steps_issued, s);
 }
 
 extern "C" int asr_att_decoder_beam_joint(asr_handle* h, const asr_att_decoder* a, const asr_att_infer* f, const asr_att_beam* m,
                                           const asr_att_beam_ctc* j, int* steps_issued, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
   if (!j) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_beam_joint: bad arguments");
-  return att_beam_loop(h, a, f, m, j, steps_issued, s);
+  return att_beam_loop(h, a, f, m, j, nullptr, steps_issued, s);
+}
+
+extern "C" int asr_att_decoder_beam_lm(asr_handle* h, const asr_att_decoder* a, const asr_att_infer* f, const asr_att_beam* m,
+                                       const asr_att_beam_ctc* j, const asr_att_lm* lm, int* steps_issued, asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  if (!lm) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_beam_lm: bad arguments");
+  return att_beam_loop(h, a, f, m, j, lm, steps_issued, s);
 }
 
 extern "C" int asr_att_decoder_bwd(asr_handle* h, const asr_att_decoder* a, asr_stream s) {

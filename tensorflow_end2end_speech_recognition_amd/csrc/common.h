@@ -35,6 +35,8 @@ struct asr_handle {
   unsigned long long att_beam_counts[3];
   // joint CTC / attention beam search launches since the last asr_reset_att_joint_counts: {score, advance, joint_select}
   unsigned long long att_joint_counts[3];
+  // LM-fused beam search calls since the last asr_reset_att_lm_counts: {lm_step, fused_select, lm_reorder}
+  unsigned long long att_lm_counts[3];
   // 3x3 convolution launches since the last asr_reset_conv_path_counts, indexed by the ASR_CONVP_* enum of asr_hip.h
   unsigned long long conv_counts[ASR_CONVP_N];
   // listed-row GEMM calls since the last asr_reset_gemm_path_counts, indexed by the ASR_GEMMP_* enum of asr_hip.h

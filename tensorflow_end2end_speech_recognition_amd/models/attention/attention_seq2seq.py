@@ -38,6 +38,7 @@ from .decoders.attention_decoder import (AttentionDecoder, AttentionDecoderOutpu
                                          LSTMDecoderCell, TrainingHelper)
 from .decoders.attention_layer import AttentionLayer
 from .decoders.beam_search.ctc_prefix_score import check_ctc_weight
+from .decoders.beam_search.lm_fusion import check_lm_weight
 from .decoders.beam_search.util import check_beam_width
 
 D = 'attention_decoder/decoder/'
@@ -617,7 +618,7 @@ class AttentionSeq2Seq(ModelBase):
         outputs, _ = decoder((c, h), helper)
         return outputs.predicted_ids[:B]
 
-    def _decode_beam(self, inputs, isl, beam_width, length_penalty_weight=0.0, ctc_weight=0.0):
+    def _decode_beam(self, inputs, isl, beam_width, length_penalty_weight=0.0, ctc_weight=0.0, lm=None, lm_weight=0.0):
         """Beam search decode (the reference's BeamSearchDecoder, decoders/beam_search/beam_search_decoder.py, which its
         model cannot construct -- the functions are complete and are what this runs): per utterance beam_width
         hypotheses on a device batch of B * beam_width rows, ONE call (ops.att_decoder_beam -> asr_att_decoder_beam)
@@ -631,8 +632,13 @@ class AttentionSeq2Seq(ModelBase):
         by (1 - ctc_weight) * log p_att + ctc_weight * log p_ctc(prefix) (decoders/beam_search/ctc_prefix_score.py) over
         the W + 1 classes per slot the attention scores preselect (the CTC pre-beam, fixed at W); the loop is
         ops.att_decoder_beam_joint, the CTC log-posteriors are read through row / W (not tiled), and _beam_raw also keeps
-        ctc_score [B,W].  scores are then the fused scores."""
-        W = check_beam_width(beam_width, self.num_classes - (1 if ctc_weight else 0))    # (joint: <SOS> never scores)
+        ctc_score [B,W].  scores are then the fused scores.
+        lm_weight > 0 (EXTENSION): shallow fusion with the RNNLM `lm` (decoders/beam_search/lm_fusion.py) -- every step also
+        runs one LM step on the B * beam_width rows and the selection adds lm_weight * log p_lm(hypothesis); the loop is
+        ops.att_decoder_beam_lm (with or without ctc_weight), the LM's weight images are prepared once per call, outside
+        the step loop, and _beam_raw also keeps lm_score [B,W]."""
+        # (joint / fused: <SOS> never scores)
+        W = check_beam_width(beam_width, self.num_classes - (1 if (ctc_weight or lm_weight) else 0))
         st, dev = self.store, self.device
         B = inputs.shape[0]
         enc, seq_p = self._encode(inputs, isl, 1.0, False)
@@ -676,14 +682,19 @@ class AttentionSeq2Seq(ModelBase):
                     gates_all=f32(1, R, 4 * U), craw_all=f32(1, R, U), c_all=c_all, h_all=h_all, qz_all=f32(1, R, A))
         head = (st[D + 'attentional_vector/weights'], st[D + 'output_layer/weights'], st[D + 'output_layer/biases'],
                 st['output_embedding/W_embedding'], self.eos_index)
-        if ctc_weight:
+        if lm_weight:
+            kw = dict(y=self._ctc_log_posteriors(enc), seq_len=seq_p[:B].contiguous(), ctc_weight=ctc_weight) if ctc_weight \
+                else {}
+            out = ops.att_decoder_beam_lm(loop, *head, beam_width=W, lm=lm.decode_weights(), lm_weight=lm_weight,
+                                          length_penalty_weight=length_penalty_weight, **kw)
+        elif ctc_weight:
             out = ops.att_decoder_beam_joint(loop, *head, beam_width=W, y=self._ctc_log_posteriors(enc),
                                              seq_len=seq_p[:B].contiguous(), ctc_weight=ctc_weight,
                                              length_penalty_weight=length_penalty_weight)
         else:
             out = ops.att_decoder_beam(loop, *head, beam_width=W, length_penalty_weight=length_penalty_weight)
         # the ONE read-back of the decode: hypotheses, their lengths and their scores as one array
-        floats = [out['final_score']] + ([out['ctc_score']] if ctc_weight else [])
+        floats = [out['final_score']] + ([out['ctc_score']] if ctc_weight else []) + ([out['lm_score']] if lm_weight else [])
         packed = torch.cat([out['ids'].reshape(B, W * To), out['hyp_len']] +
                            [t.contiguous().view(torch.int32) for t in floats], dim=1).cpu().numpy()
         ids = packed[:, :W * To].reshape(B, W, To)
@@ -691,7 +702,9 @@ class AttentionSeq2Seq(ModelBase):
         scores = np.ascontiguousarray(packed[:, W * To + W:W * To + 2 * W]).view(np.float32)
         self._beam_raw = dict(out, ids=ids, hyp_len=hyp_len, scores=scores, B=B, beam_width=W)
         if ctc_weight:
-            self._beam_raw['ctc_score'] = np.ascontiguousarray(packed[:, W * To + 2 * W:]).view(np.float32)
+            self._beam_raw['ctc_score'] = np.ascontiguousarray(packed[:, W * To + 2 * W:W * To + 3 * W]).view(np.float32)
+        if lm_weight:
+            self._beam_raw['lm_score'] = np.ascontiguousarray(packed[:, -W:]).view(np.float32)
         return np.ascontiguousarray(ids[:, 0, :int(hyp_len[:, 0].max())])
 
     _has_ctc_head = False
@@ -699,24 +712,46 @@ class AttentionSeq2Seq(ModelBase):
     def _ctc_log_posteriors(self, enc):
         raise NotImplementedError
 
-    def infer(self, inputs, inputs_seq_len, native=True, beam_width=1, length_penalty_weight=0.0, ctc_weight=0.0):
+    def _check_lm(self, lm, lm_weight):
+        """lm_weight as a float; > 0 needs an RNNLM over this model's classes, on its device."""
+        mu = check_lm_weight(lm_weight)
+        if lm is None:
+            if mu != 0.0:
+                raise ValueError('lm_weight=%r needs a language model (lm=RNNLM(...))' % (lm_weight,))
+            return 0.0
+        got = tuple(getattr(lm, k, None) for k in ('num_classes', 'sos_index', 'eos_index'))
+        if not hasattr(lm, 'decode_weights') or got != (self.num_classes, self.sos_index, self.eos_index):
+            raise ValueError('lm must be an RNNLM over this model\'s classes: (num_classes, sos_index, eos_index) = %r, the '
+                             'model has %r' % (got, (self.num_classes, self.sos_index, self.eos_index)))
+        if torch.device(lm.device) != torch.device(self.device):
+            raise ValueError('lm lives on %s, the model on %s' % (lm.device, self.device))
+        return mu
+
+    def infer(self, inputs, inputs_seq_len, native=True, beam_width=1, length_penalty_weight=0.0, ctc_weight=0.0, lm=None,
+              lm_weight=0.0):
         """Inference ids [B, <= max_decode_length] (numpy) for a batch of features -- what running the reference's
         `decode_op_infer` with a feed_dict of inputs / inputs_seq_len / keep_prob = 1 returns
         (examples/timit/metrics/attention.py:80-86).  beam_width 1: greedy decoding (native: see _decode_infer);
         beam_width > 1: the best hypothesis of the beam search (_decode_beam; it has the native form only).
         ctc_weight in (0, 1] (EXTENSION; JointCTCAttention only -- this class has no CTC head and raises): the beam
         search on joint CTC / attention scores, at any beam width (1 is a width-1 joint search, not the greedy loop);
-        0, the default, is everything above, untouched."""
+        0, the default, is everything above, untouched.
+        lm, lm_weight (EXTENSION): shallow fusion with an RNNLM (models/lm) over the same classes on the same device --
+        lm_weight > 0 needs lm, has the native form only and runs the beam search on fused scores at any beam width (1 is
+        a width-1 fused search), alone or together with ctc_weight; lm None or lm_weight 0 is everything above, untouched."""
         lam = check_ctc_weight(ctc_weight)
+        mu = self._check_lm(lm, lm_weight)
         if lam != 0.0 and not self._has_ctc_head:
             raise ValueError('ctc_weight=%r needs a model with a CTC head (JointCTCAttention)' % (ctc_weight,))
-        if lam != 0.0 and not native:
+        if (lam != 0.0 or mu != 0.0) and not native:
             raise ValueError('beam search decoding has the native form only')
         self.encoder._lens_host = ops.host_ints(inputs_seq_len)
         if lam != 0.0 and (np.asarray(self.encoder._lens_host) < 1).any():
             raise ValueError('joint CTC / attention decoding needs at least one frame per utterance')   # (as the statement)
         inputs = ops.to_device(inputs, torch.float32, self.device)
         isl = ops.to_device(inputs_seq_len, torch.int32, self.device)
+        if mu != 0.0:
+            return self._decode_beam(inputs, isl, beam_width, length_penalty_weight, ctc_weight=lam, lm=lm, lm_weight=mu)
         if lam != 0.0:
             return self._decode_beam(inputs, isl, beam_width, length_penalty_weight, ctc_weight=lam)
         if int(beam_width) != 1:

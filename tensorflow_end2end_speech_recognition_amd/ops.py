@@ -2229,6 +2229,237 @@ def reset_att_joint_counts(device=0):
         h.check(h.lib.asr_reset_att_joint_counts(h.h), 'asr_reset_att_joint_counts')
 
 
+# ---------------------------------------------------------------- shallow fusion with an RNN language model (an extension)
+def _check_lm_weight(lm_weight):
+    mu = float(lm_weight)
+    if not (mu > 0.0 and mu != float('inf')):
+        raise ValueError('lm_weight must be a finite number > 0 here (0 is the search without a language model), got %r'
+                         % (lm_weight,))
+    return mu
+
+
+class _AttLm(C.Structure):
+    """struct asr_att_lm (include/asr_hip.h), field for field."""
+    _INTS = ['L', 'H', 'Em_lm', 'R', 'C2']
+    _PTRS = ['emb', 'W', 'b', 'W_out', 'b_out', 'W_il', 'c', 'h', 'in', 'live', 'work', 'lm_logits', 'lm_score', 'cand',
+             'cand_total', 'cand_lm']
+    _fields_ = ([(n, C.c_int) for n in _INTS] + [('cell_clip', C.c_float), ('lm_weight', C.c_float)] +
+                [(n, C.c_void_p) for n in _PTRS])
+
+
+def lm_in_layers(flat, R, Em_lm, H, L):
+    """The per-layer views [R, Din_l + H] (x | h_prev) of a language model's cell-input rows (struct asr_att_lm's `in`)."""
+    views, o = [], 0
+    for l in range(L):
+        wdt = (Em_lm if l == 0 else H) + H
+        views.append(flat[o:o + R * wdt].view(R, wdt))
+        o += R * wdt
+    return views
+
+
+def _lm_struct(lm, R, W, lm_weight):
+    """struct asr_att_lm and the tensors behind it for R device rows.  `lm`: dict(emb [C2,Em_lm], kernels = L tensors
+    [Din_l + H, 4H], biases = L tensors [4H], W_out [H,C2], b_out [C2], cell_clip) -- RNNLM.decode_weights().  The state is
+    that of the empty history: c, h zeros, the layer-0 input the embedding of lm['sos'] (when given)."""
+    emb, kernels, biases = lm['emb'], list(lm['kernels']), list(lm['biases'])
+    dev = emb.device
+    L, H = len(kernels), int(biases[0].numel()) // 4
+    C2, Em = (int(v) for v in emb.shape)
+    for t, n in [(emb, 'emb'), (lm['W_out'], 'W_out'), (lm['b_out'], 'b_out')] + [(k, 'kernel') for k in kernels] + \
+            [(b, 'bias') for b in biases]:
+        _chk(t, torch.float32, 'lm ' + n)
+    for l, k in enumerate(kernels):
+        if tuple(k.shape) != ((Em if l == 0 else H) + H, 4 * H):
+            raise ValueError('language model: kernel of layer %d is %s' % (l, tuple(k.shape)))
+    if tuple(lm['W_out'].shape) != (H, C2) or tuple(lm['b_out'].shape) != (C2,):
+        raise ValueError('language model: the output layer does not fit [%d,%d]' % (H, C2))
+    n_in = R * (Em + H) + (L - 1) * R * 2 * H
+    n_il = (Em + H + 1) * 4 * H + (L - 1) * (2 * H + 1) * 4 * H
+    t = dict(emb=emb, W=torch.cat([k.reshape(-1) for k in kernels]), b=torch.stack(biases).contiguous(), W_out=lm['W_out'],
+             b_out=lm['b_out'], W_il=_f32((n_il,), dev) if FUSED_CELL_GEMM else None,
+             c=torch.zeros((2, L, R, H), dtype=torch.float32, device=dev),
+             h=torch.zeros((2, L, R, H), dtype=torch.float32, device=dev),
+             live=torch.ones((R,), dtype=torch.float32, device=dev), work=_f32((R * 10 * H,), dev),
+             lm_logits=_f32((R, C2), dev), lm_score=torch.zeros((R,), dtype=torch.float32, device=dev),
+             cand=_i32((R, W + 1), dev), cand_total=_f32((R, W + 1), dev), cand_lm=_f32((R, W + 1), dev))
+    t['in'] = torch.zeros((n_in,), dtype=torch.float32, device=dev)
+    if lm.get('sos') is not None:
+        lm_in_layers(t['in'], R, Em, H, L)[0][:, :Em] = emb[int(lm['sos'])]
+    st = _AttLm()
+    st.L, st.H, st.Em_lm, st.R, st.C2 = L, H, Em, R, C2
+    st.cell_clip, st.lm_weight = float(lm.get('cell_clip') or 0.0), float(lm_weight)
+    for n in _AttLm._PTRS:
+        setattr(st, n, t[n].data_ptr() if t[n] is not None else None)
+    return st, t
+
+
+def lm_step(lm, words, c, h):
+    """One language model step on R rows (asr_lm_prep + asr_lm_step): words [R] int32 (each row's last word), c / h
+    [L,R,H] the state before the step.  Returns (lm_logits [R,C2] raw, c_new, h_new [L,R,H])."""
+    hd = _h(c)
+    _chk(words, torch.int32, 'words')
+    _chk(c, torch.float32, 'c')
+    _chk(h, torch.float32, 'h')
+    L, R, H = (int(v) for v in c.shape)
+    st, t = _lm_struct(lm, R, 1, 1.0)
+    if st.L != L or st.H != H or tuple(h.shape) != tuple(c.shape) or tuple(words.shape) != (R,):
+        raise ValueError('lm_step: state [%d,%d,%d] does not fit the language model' % (L, R, H))
+    t['c'][0].copy_(c)
+    t['h'][0].copy_(h)
+    ins = lm_in_layers(t['in'], R, st.Em_lm, H, L)
+    ins[0][:, :st.Em_lm] = lm['emb'].index_select(0, words.long().clamp(0, st.C2 - 1))
+    for l in range(L):
+        ins[l][:, -H:] = h[l]
+    hd.check(hd.lib.asr_lm_prep(hd.h, C.byref(st), _s()), 'asr_lm_prep')
+    hd.check(hd.lib.asr_lm_step(hd.h, C.byref(st), _s()), 'asr_lm_step')
+    return t['lm_logits'], t['c'][1], t['h'][1]
+
+
+def att_beam_select_fused(logits, lm_logits, n_labels, lm_weight, length_penalty_weight, first_step, log_probs, finished,
+                          lengths, lm_score, beam_width=None, ctc_weight=0.0, y=None, seq_len=None, r=None, last=None,
+                          ctc_score=None, unfinished=None, blank=None):
+    """One selection per utterance on fused attention / LM (/ CTC prefix) scores (asr_att_beam_select_fused):
+    ((1 - ctc_weight) * total_att + ctc_weight * ctc + lm_weight * lm_total) / penalty over the W + 1 classes per slot that
+    p_att + lm_weight * p_lm preselects.  logits / lm_logits [B*W, n_labels + 2] raw; log_probs, lm_score [B*W] fp32,
+    finished, lengths [B*W] int32; beam_width W (needed without CTC; with it W = rows / utterances); with ctc_weight > 0
+    also y / seq_len / r / last / ctc_score as att_beam_select_joint.
+    Nothing is changed in place.  Returns word, parent [B,W] int32, score [B,W], and the next state log_probs, finished,
+    lengths, lm_score [B*W], last, ctc_score [B*W] (None, None without CTC)."""
+    h = _h(logits)
+    _chk(logits, torch.float32, 'logits')
+    _chk(lm_logits, torch.float32, 'lm_logits')
+    R, C2 = (int(v) for v in logits.shape)
+    N = int(n_labels)
+    if C2 != N + 2 or tuple(lm_logits.shape) != (R, C2):
+        raise ValueError('att_beam_select_fused: logits %s / lm_logits %s for %d labels' % (tuple(logits.shape),
+                                                                                        tuple(lm_logits.shape), N))
+    mu = _check_lm_weight(lm_weight)
+    lam = float(ctc_weight)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError('ctc_weight must be in [0, 1], got %r' % (ctc_weight,))
+    state = [(log_probs, torch.float32, 'log_probs'), (lm_score, torch.float32, 'lm_score'), (finished, torch.int32, 'finished'),
+             (lengths, torch.int32, 'lengths')]
+    dev = logits.device
+    if lam > 0.0:
+        B, W, T, By, Cc, blank = _joint_shapes('att_beam_select_fused', y, seq_len, R, N, blank)
+        _chk_state('att_beam_select_fused', r, last, T)
+        if r.shape[0] != R or (beam_width is not None and int(beam_width) != W):
+            raise ValueError('att_beam_select_fused: r must have %d rows' % R)
+        state.append((ctc_score, torch.float32, 'ctc_score'))
+        psi, lst, cs = _f32((R, W + 1), dev), _i32((R,), dev), _f32((R,), dev)
+    else:
+        if beam_width is None:
+            raise ValueError('att_beam_select_fused: without CTC posteriors beam_width must be given')
+        W, blank = int(beam_width), 0
+        if W < 1 or R % W:
+            raise ValueError('att_beam_select_fused: %d rows are not a multiple of beam_width %d' % (R, W))
+        B, T, By, Cc = R // W, 0, 0, 0
+        psi = lst = cs = None
+    _beam_width(W, N + 1)
+    for t, dt, n in state:
+        _chk(t, dt, n)
+        if tuple(t.shape) != (R,):
+            raise ValueError('att_beam_select_fused: %s must be [%d]' % (n, R))
+    word, parent, score = _i32((B, W), dev), _i32((B, W), dev), _f32((B, W), dev)
+    lp, fin, ln, ls = _f32((R,), dev), _i32((R,), dev), _i32((R,), dev), _f32((R,), dev)
+    cand, tot, clm = _i32((R, W + 1), dev), _f32((R, W + 1), dev), _f32((R, W + 1), dev)
+    a = 0.0 if length_penalty_weight is None else float(length_penalty_weight)
+    h.check(h.lib.asr_att_beam_select_fused(h.h, _p(logits), _p(lm_logits), B, W, N, a, lam, mu, int(bool(first_step)), _p(y),
+                                            _p(seq_len), T, By, Cc, blank, _p(r), _p(log_probs), _p(finished), _p(lengths),
+                                            _p(last), _p(ctc_score), _p(lm_score), _p(cand), _p(tot), _p(clm), _p(psi),
+                                            _p(word), _p(parent), _p(score), _p(lp), _p(fin), _p(ln), _p(lst), _p(cs), _p(ls),
+                                            _p(unfinished), _s()), 'asr_att_beam_select_fused')
+    return word, parent, score, lp, fin, ln, ls, lst, cs
+
+
+def lm_beam_reorder(parent, word, c_src, h_src, emb):
+    """The language model state the next step reads, gathered by parent within each utterance (asr_lm_beam_reorder): parent /
+    word [B,W] int32, c_src / h_src [L,B*W,H], emb [C2,Em_lm].  Returns new c, h [L,B*W,H] and the per-layer cell-input
+    rows [B*W, Din_l + H] (x | h_prev; x of layer 0 = emb[word], x of the layers above is not written here: zeros)."""
+    hd = _h(c_src)
+    for t, dt, n in ((parent, torch.int32, 'parent'), (word, torch.int32, 'word'), (c_src, torch.float32, 'c_src'),
+                     (h_src, torch.float32, 'h_src'), (emb, torch.float32, 'emb')):
+        _chk(t, dt, n)
+    B, W = (int(v) for v in parent.shape)
+    L, R, H = (int(v) for v in c_src.shape)
+    Em = int(emb.shape[1])
+    if R != B * W or tuple(h_src.shape) != tuple(c_src.shape) or tuple(word.shape) != (B, W):
+        raise ValueError('lm_beam_reorder: shapes disagree')
+    c, hh = torch.empty_like(c_src), torch.empty_like(h_src)
+    flat = torch.zeros((R * (Em + H) + (L - 1) * R * 2 * H,), dtype=torch.float32, device=c_src.device)
+    hd.check(hd.lib.asr_lm_beam_reorder(hd.h, _p(parent), _p(word), B, W, L, H, Em, int(emb.shape[0]), _p(c_src), _p(h_src),
+                                        _p(emb), _p(c), _p(hh), _p(flat), _s()), 'asr_lm_beam_reorder')
+    return c, hh, lm_in_layers(flat, R, Em, H, L)
+
+
+def att_decoder_beam_lm(a, W_av, W_out, b_out, embedding, eos, beam_width, lm, lm_weight, length_penalty_weight=0.0,
+                        check_every=8, y=None, seq_len=None, ctc_weight=0.0, blank=None):
+    """Beam search decode with shallow LM fusion from one call (asr_att_decoder_beam_lm): att_decoder_beam -- or, with
+    ctc_weight > 0 and y / seq_len, att_decoder_beam_joint -- whose every step also runs one step of the language model
+    `lm` (dict: see RNNLM.decode_weights; its images are prepared once, before the first step) and selects on the fused
+    score.  Returns that loop's dict and lm_score [B,W], the hypotheses' LM log-probabilities."""
+    dev = a['dec_in'].device
+    R = a['B']
+    C2 = int(W_out.shape[1])
+    N = C2 - 2
+    if int(eos) != N + 1:
+        raise ValueError('att_decoder_beam_lm: <EOS> must be the last of the %d attention classes' % C2)
+    W = _beam_width(beam_width, N + 1)
+    mu = _check_lm_weight(lm_weight)
+    lam = float(ctc_weight)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError('ctc_weight must be in [0, 1], got %r' % (ctc_weight,))
+    if R % W:
+        raise ValueError('att_decoder_beam_lm: %d rows are not a multiple of beam_width %d' % (R, W))
+    if int(lm['emb'].shape[0]) != C2:
+        raise ValueError('att_decoder_beam_lm: the language model has %d classes, the decoder %d' % (int(lm['emb'].shape[0]), C2))
+    B = R // W
+    lst, lt = _lm_struct(dict(lm, sos=N), R, W, mu)
+    extra_out = dict(lm_score=lt['lm_score'].view(B, W))
+    extra = dict(lm=lt)
+    if lam > 0.0:
+        B2, W2, T, By, Cc, blank = _joint_shapes('att_decoder_beam_lm', y, seq_len, R, N, blank)
+        if W2 != W or T != a['T']:
+            raise ValueError('att_decoder_beam_lm: y [%d,%d,%d] / seq_len [%d] do not fit %d rows of %d frames'
+                             % (T, By, Cc, B2, R, a['T']))
+        extra.update(r=_f32((2, R, 2, T), dev), last=_i32((2, R), dev), cand=_i32((R, W + 1), dev),
+                     cand_total=_f32((R, W + 1), dev), psi=_f32((R, W + 1), dev), y=y, seq_len=seq_len)
+        extra_out['ctc_score'] = _f32((B, W), dev)
+    h, st, f, m, out, scratch, host = _beam_loop_call('att_decoder_beam_lm', a, W_av, W_out, b_out, embedding, eos, W,
+                                                      length_penalty_weight, check_every, extra_out=extra_out,
+                                                      extra_scratch=extra)
+    j = None
+    if lam > 0.0:
+        j = _AttBeamCtc()
+        j.y, j.seq_len = y.data_ptr(), seq_len.data_ptr()
+        j.By, j.Cc, j.blank, j.n_labels, j.ctc_weight = By, Cc, blank, N, lam
+        j.r, j.last, j.ctc_score = scratch['r'].data_ptr(), scratch['last'].data_ptr(), out['ctc_score'].data_ptr()
+        j.cand, j.cand_total, j.psi = scratch['cand'].data_ptr(), scratch['cand_total'].data_ptr(), scratch['psi'].data_ptr()
+    issued = C.c_int(0)
+    h.check(h.lib.asr_att_decoder_beam_lm(h.h, C.byref(st), C.byref(f), C.byref(m), C.byref(j) if j is not None else None,
+                                          C.byref(lst), C.byref(issued), _s()), 'asr_att_decoder_beam_lm')
+    return _beam_loop_done(out, issued, host, scratch)
+
+
+_ATT_LM_KEYS = ('lm_step', 'fused_select', 'lm_reorder')
+
+
+def att_lm_counts(device=0):
+    """Calls of the LM-fusion entry points on `device` since the last reset, summed over its handles (asr_att_lm_counts).
+    Host counters: no device work, no synchronisation."""
+    tot = [0] * 3
+    for h in _device_handles(device):
+        out = (C.c_ulonglong * 3)()
+        h.check(h.lib.asr_att_lm_counts(h.h, out), 'asr_att_lm_counts')
+        tot = [x + int(y) for x, y in zip(tot, out)]
+    return dict(zip(_ATT_LM_KEYS, tot))
+
+
+def reset_att_lm_counts(device=0):
+    for h in _device_handles(device):
+        h.check(h.lib.asr_reset_att_lm_counts(h.h), 'asr_reset_att_lm_counts')
+
+
 def tanh_fwd(x):
     h = _h(x)
     y = torch.empty_like(x)
