@@ -2,10 +2,13 @@
 """Evaluate a trained CTC model on the TIMIT test set -- the recipe of examples/timit/evaluation/eval_ctc.py:30-164.
 
     python examples/timit/evaluation/eval_ctc.py <model_path> [--epoch E] [--beam_width W] [--eval_batch_size B]
+                                                  [--lm_path DIR] [--lm_epoch E] [--lm_weight A] [--insertion_bonus BETA]
 
 <model_path> is a run directory of train_ctc.py (config.yml + checkpoint index + model.ckpt-<epoch>.npz).  The model
 is rebuilt from config.yml, the checkpoint of `--epoch` (-1: the latest) is restored, and PER on 39 phones or
-CER/WER of the test set is printed."""
+CER/WER of the test set is printed.  --lm_path: a run directory of train_lm.py (a language model over the same label
+set, fused into the prefix beam search with weight --lm_weight); --insertion_bonus: added per emitted label (both are
+extensions: the reference's decoder names them alpha and beta and never uses them).  The defaults are today's run."""
 import argparse
 import sys
 from os.path import abspath, dirname, isfile, join
@@ -23,7 +26,7 @@ from examples.timit.training.train_ctc import build_model                       
 from tensorflow_end2end_speech_recognition_amd.utils.training.checkpoint import Saver, get_checkpoint_state  # noqa: E402
 
 
-def do_eval(model, params, epoch, eval_batch_size, beam_width, model_path):
+def do_eval(model, params, epoch, eval_batch_size, beam_width, model_path, lm=None, lm_weight=0.0, insertion_bonus=0.0):
     """:30-108."""
     is_char = 'char' in params['label_type']
     test_data = Dataset(data_type='test', label_type=params['label_type'] if is_char else 'phone39', batch_size=1,
@@ -42,6 +45,8 @@ def do_eval(model, params, epoch, eval_batch_size, beam_width, model_path):
     print('Test Data Evaluation:')
     ev = dict(model=model, dataset=test_data, label_type=params['label_type'], is_test=True,
               eval_batch_size=eval_batch_size, map_dir=map_dir, beam_width=beam_width)
+    if lm is not None or insertion_bonus:
+        ev.update(lm=lm, lm_weight=lm_weight, insertion_bonus=insertion_bonus)
     if is_char:
         cer, wer = do_eval_cer(session=None, decode_op=None, **ev)
         print('  CER: %f %%' % (cer * 100))
@@ -59,14 +64,29 @@ def main(argv=None):
     ap.add_argument('--beam_width', type=int, default=20)
     ap.add_argument('--eval_batch_size', type=int, default=1)
     ap.add_argument('--device', default=None)
+    ap.add_argument('--lm_path', default=None, help='run directory of train_lm.py: the language model to fuse')
+    ap.add_argument('--lm_epoch', type=int, default=-1, help='the epoch of the language model to restore')
+    ap.add_argument('--lm_weight', type=float, default=0.0,
+                    help='weight of the language model scores in the prefix beam search (needs --lm_path; 0: no language model)')
+    ap.add_argument('--insertion_bonus', type=float, default=0.0, help='bonus per emitted label in the prefix beam search')
     args = ap.parse_args(argv)
+    if args.lm_weight != 0.0 and not args.lm_path:
+        ap.error('--lm_weight needs --lm_path')
     with open(join(args.model_path, 'config.yml'), 'r') as f:
         params = yaml.safe_load(f)['param']
     if args.device:
         params['device'] = args.device
     model = build_model(params)
     model.save_path = args.model_path
-    return do_eval(model, params, args.epoch, args.eval_batch_size, args.beam_width, args.model_path)
+    lm = None
+    if args.lm_path and args.lm_weight != 0.0:
+        from examples.timit.training.train_lm import restore_lm
+        lm = restore_lm(args.lm_path, args.lm_epoch, device=params.get('device', 'cuda:0'))
+        if lm.num_classes < model.num_classes + 1:
+            raise ValueError('the language model has %d classes; a CTC model of %d classes needs >= %d'
+                             % (lm.num_classes, model.num_classes, model.num_classes + 1))
+    return do_eval(model, params, args.epoch, args.eval_batch_size, args.beam_width, args.model_path, lm=lm,
+                   lm_weight=args.lm_weight if lm is not None else 0.0, insertion_bonus=args.insertion_bonus)
 
 
 if __name__ == '__main__':

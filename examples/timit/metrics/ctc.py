@@ -20,25 +20,36 @@ from examples.timit.metrics.mapping import Map2phone39                          
 import numpy as np
 
 
-def _decode(model, inputs, seq_len, beam_width, task=None):
-    """task: None (single-task model) | 'main' | 'sub' (MultitaskCTC: which head's decode to return)."""
+def _decode(model, inputs, seq_len, beam_width, task=None, lm_kw=None):
+    """task: None (single-task model) | 'main' | 'sub' (MultitaskCTC: which head's decode to return).  lm_kw: the
+    lm / lm_weight / insertion_bonus keywords of CTC.decoder (an extension; None or empty: today's decode)."""
+    lm_kw = lm_kw or {}
     B = inputs.shape[0]
     dummy = np.zeros((B, 1), dtype=np.int64)                    # labels are not needed for the logits
     if task is None:
         _, logits = model.compute_loss(inputs, dummy, seq_len, keep_prob=1.0, is_training=False)
-        dec = model.decoder(logits, seq_len, beam_width=beam_width)
+        dec = model.decoder(logits, seq_len, beam_width=beam_width, **lm_kw)
     else:
         _, logits_main, logits_sub = model.compute_loss(inputs, dummy, dummy, seq_len, keep_prob=1.0,
                                                         is_training=False)
-        dec = model.decoder(logits_main, logits_sub, seq_len, beam_width=beam_width)[0 if task == 'main' else 1]
+        dec = model.decoder(logits_main, logits_sub, seq_len, beam_width=beam_width, **lm_kw)[0 if task == 'main' else 1]
     return [np.asarray(h, dtype=np.int64) for h in sparsetensor2list(dec, B)]
 
 
+def _lm_kw(lm, lm_weight, insertion_bonus):
+    """CTC.decoder's fusion keywords, or {} when none is set (the call is then exactly the one without them)."""
+    if lm is None and not lm_weight and not insertion_bonus:
+        return {}
+    return dict(lm=lm, lm_weight=lm_weight, insertion_bonus=insertion_bonus)
+
+
 def do_eval_per(session, decode_op, per_op, model, dataset, label_type, is_test=False, eval_batch_size=None,
-                progressbar=False, is_multitask=False, map_dir=None, beam_width=1):
+                progressbar=False, is_multitask=False, map_dir=None, beam_width=1, lm=None, lm_weight=0.0,
+                insertion_bonus=0.0):
     """Mean phone error rate on the 39-phone set (:20-124).  map_dir: directory with <label_type>.txt and
     phone2phone.txt (the reference hard-codes '../metrics/mapping_files/')."""
     map_dir = map_dir or '../metrics/mapping_files'
+    lm_kw = _lm_kw(lm, lm_weight, insertion_bonus)
     batch_size_original = dataset.batch_size
     dataset.reset()
     if eval_batch_size is not None:
@@ -55,7 +66,7 @@ def do_eval_per(session, decode_op, per_op, model, dataset, label_type, is_test=
             inputs, _, labels_true, inputs_seq_len, _ = data
         else:
             inputs, labels_true, inputs_seq_len, _ = data
-        hyps = _decode(model, inputs[0], inputs_seq_len[0], beam_width, 'sub' if is_multitask else None)
+        hyps = _decode(model, inputs[0], inputs_seq_len[0], beam_width, 'sub' if is_multitask else None, lm_kw)
         for b in range(inputs[0].shape[0]):
             pred = to39_train(idx2phone_train(hyps[b]).split(' ')) if len(hyps[b]) else []
             if is_test:
@@ -74,9 +85,11 @@ def do_eval_per(session, decode_op, per_op, model, dataset, label_type, is_test=
 
 
 def do_eval_cer(session, decode_op, model, dataset, label_type, is_test=False, eval_batch_size=None,
-                progressbar=False, is_multitask=False, map_dir=None, beam_width=1):
+                progressbar=False, is_multitask=False, map_dir=None, beam_width=1, lm=None, lm_weight=0.0,
+                insertion_bonus=0.0):
     """(mean CER, mean WER) (:127-227): '_' separates words; punctuation is stripped before scoring."""
     map_dir = map_dir or '../metrics/mapping_files'
+    lm_kw = _lm_kw(lm, lm_weight, insertion_bonus)
     batch_size_original = dataset.batch_size
     dataset.reset()
     if eval_batch_size is not None:
@@ -93,7 +106,7 @@ def do_eval_cer(session, decode_op, model, dataset, label_type, is_test=False, e
             inputs, labels_true, _, inputs_seq_len, _ = data
         else:
             inputs, labels_true, inputs_seq_len, _ = data
-        hyps = _decode(model, inputs[0], inputs_seq_len[0], beam_width, 'main' if is_multitask else None)
+        hyps = _decode(model, inputs[0], inputs_seq_len[0], beam_width, 'main' if is_multitask else None, lm_kw)
         for b in range(inputs[0].shape[0]):
             if is_test:
                 str_true = labels_true[0][b][0]

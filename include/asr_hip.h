@@ -1036,6 +1036,44 @@ int asr_att_decoder_beam_lm(asr_handle* h, const asr_att_decoder* a, const asr_a
 /* Calls on this handle since the last reset, {lm_step, fused_select, lm_reorder}. */
 int asr_att_lm_counts(asr_handle* h, unsigned long long* out3);
 int asr_reset_att_lm_counts(asr_handle* h);
+/* ---- CTC prefix beam search with RNN language-model fusion, native (later within ABI 5, additive) ------------- *
+ * EXTENSION: the reference's CTC BeamSearchDecoder.__call__ takes alpha ("language model weight") and beta ("insertion
+ * bonus"), carries `# TODO: add LM score here` (models/ctc/decoders/beam_search_decoder.py:53,61-62,132) and ships an empty
+ * models/ctc/decoders/charlm_beam_search_decoder.py.  Float64 statement: this package's file of that name.
+ * asr_ctc_beam_decode's search in which every EXTENSION of a prefix by a class c != blank uses
+ *     p_t + alpha * log p_lm(c | <SOS>, prefix) + beta
+ * in place of p_t (both the c != last and the c == last / p_b-only branch); the blank update and the merging case get
+ * neither term.  log p_lm = log-softmax over all V classes of the LM's raw fp32 logits row, taken in fp64.  The CTC model
+ * has C classes, CTC label c is LM class c; the LM has V >= C + 1 classes, its <SOS> / <EOS> lie outside the CTC labels.
+ * No <EOS> term at the end, no word-level LM, no n-best output.  1 <= W <= 32 (the LM beam kernels' limit), W <= C - 1.
+ *
+ * asr_ctc_beam_lm_frame: frame t of the search for all B utterances (one workgroup each); the beam lives in the
+ * workspace between the calls (t = 0 initialises it, so the frames must come in order on one stream).  lm_logits [B*W,V]
+ * (row b*W + w: the LM's distribution after the prefix in slot w; NULL with alpha == 0: bonus only).  An utterance with
+ * t >= seq_len[b] is left as it is (parent = w, word = -1).  Out, per new slot: parent [B,W] (the old slot), word [B,W]
+ * (the appended label, or -1 when the slot's prefix was already in the old beam -- a stay, possibly carrying merged
+ * extension mass); optionally (may be NULL) the new state: st_pb / st_pnb [B,W] fp64, st_lm [B,W] fp32, st_nb [B].
+ * asr_ctc_beam_decode_lm: the whole search from one call, everything on the one stream, no host synchronisation:
+ * asr_lm_prep once; one asr_lm_step (the empty prefix: on entry every LM row holds <SOS>'s embedding and zero state, as
+ * for asr_att_decoder_beam_lm; lm->R == B*W, lm->C2 is V; lm_weight, lm_score, cand* of the struct are not used); then per
+ * frame t = 0 .. T-1: the frame kernel; and, unless it was the last frame, asr_lm_beam_reorder (state block 1 -> block 0
+ * by parent, x = embedding of word), asr_lm_step into the other of two logits buffers, and the commit kernel (rows with
+ * word == -1 take back their parent's state and logits row).  Then the back-trace: out_labels [B,T] padded -1, out_len [B],
+ * out_score [B] fp64 = -logsumexp(p_b, p_nb) of the best entry INCLUDING the LM and bonus terms, out_lm_score [B] fp32 =
+ * its alpha-unweighted sum of log p_lm.  lm == NULL needs alpha == 0 (no LM launches at all).  seq_len[b] == 0: the empty
+ * hypothesis, score 0.  alpha == 0 and beta == 0: asr_ctc_beam_decode's result, bit for bit. */
+size_t asr_ctc_beam_lm_workspace_bytes(int T, int B, int C, int beam_width, int V);
+int asr_ctc_beam_lm_frame(asr_handle* h, const float* logits, int t, int T, int B, int C, const int32_t* seq_len, int blank,
+                          int beam_width, double alpha, double beta, const float* lm_logits, int V, int32_t* parent,
+                          int32_t* word, double* st_pb, double* st_pnb, float* st_lm, int32_t* st_nb, void* workspace,
+                          size_t workspace_bytes, asr_stream s);
+int asr_ctc_beam_decode_lm(asr_handle* h, const float* logits, int T, int B, int C, const int32_t* seq_len, int blank,
+                           int beam_width, double alpha, double beta, const asr_att_lm* lm, int32_t* out_labels,
+                           int32_t* out_len, double* out_score, float* out_lm_score, void* workspace,
+                           size_t workspace_bytes, asr_stream s);
+/* Launches on this handle since the last reset, {frame kernels, lm steps, commits}. */
+int asr_ctc_beam_lm_counts(asr_handle* h, unsigned long long* out3);
+int asr_reset_ctc_beam_lm_counts(asr_handle* h);
 /* work: B*(5*U + 3*T + E2) floats.  dav_cell is consumed (its rows accumulate the query-path gradient in place). */
 int asr_att_decoder_bwd(asr_handle* h, const asr_att_decoder* a, asr_stream s);
 /* out[b, j] = x[b*ldx + j] + y[b*ldy + j], j < W (row blocks of wider arrays; out may alias x) */

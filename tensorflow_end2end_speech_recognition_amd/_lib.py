@@ -168,6 +168,13 @@ SIGNATURES = {
     'asr_att_decoder_beam_lm': (_i, [_vp] * 8),
     'asr_att_lm_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
     'asr_reset_att_lm_counts': (_i, [_vp]),
+    # CTC prefix beam search with LM fusion (later within ABI 5)
+    'asr_ctc_beam_lm_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
+    'asr_ctc_beam_lm_frame': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, C.c_double, C.c_double, _vp, _i] + [_vp] * 7 +
+                              [_sz, _vp]),
+    'asr_ctc_beam_decode_lm': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, C.c_double, C.c_double, _vp] + [_vp] * 5 + [_sz, _vp]),
+    'asr_ctc_beam_lm_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
+    'asr_reset_ctc_beam_lm_counts': (_i, [_vp]),
     'asr_add_cols': (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp]),
     'asr_tanh_fwd': (_i, [_vp, _vp, _vp, _sz, _vp]),
     'asr_tanh_bwd': (_i, [_vp, _vp, _vp, _vp, _sz, _vp]),

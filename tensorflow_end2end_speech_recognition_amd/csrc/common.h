@@ -41,6 +41,8 @@ struct asr_handle {
   unsigned long long conv_counts[ASR_CONVP_N];
   // listed-row GEMM calls since the last asr_reset_gemm_path_counts, indexed by the ASR_GEMMP_* enum of asr_hip.h
   unsigned long long gemm_counts[ASR_GEMMP_N];
+  // LM-fused CTC prefix search since the last asr_reset_ctc_beam_lm_counts: {frame launches, lm steps, commits}
+  unsigned long long ctc_beam_lm_counts[3];
 };
 
 #define ASR_FAIL(h, code, ...)                                  \

@@ -296,7 +296,7 @@ class CTC(ModelBase):
         return {}
 
     # ------------------------------------------------------------------ decode / eval
-    def decoder(self, logits, inputs_seq_len, beam_width=1, merge_repeated=True):
+    def decoder(self, logits, inputs_seq_len, beam_width=1, merge_repeated=True, lm=None, lm_weight=0.0, insertion_bonus=0.0):
         """ctc.py:325-352.  Returns the decoded labels as the SparseTensor triple
         [indices int64 [n,2], values int32 [n], dense_shape int64 [2]] (host numpy), i.e. what
         sess.run(decode_op) hands to sparsetensor2list in the reference.
@@ -305,12 +305,22 @@ class CTC(ModelBase):
         merge_repeated=True (ctc.py:344-346), under which consecutive equal labels of the OUTPUT beam are collapsed to
         their first occurrence -- 'a a' can never be emitted.  True (default) reproduces that
         call; False returns the prefix beam search result as it is, the semantics of the reference's numpy
-        BeamSearchDecoder (models/ctc/decoders/beam_search_decoder.py) the device search is pinned to."""
+        BeamSearchDecoder (models/ctc/decoders/beam_search_decoder.py) the device search is pinned to.
+        lm / lm_weight / insertion_bonus (extension keywords; the reference's BeamSearchDecoder names them alpha and beta
+        and never uses them): with an RNNLM (models/lm) or a non-zero bonus the prefix search runs with shallow LM fusion
+        (ops.ctc_beam_decode_lm; statement: models/ctc/decoders/charlm_beam_search_decoder.py) -- beam_width == 1 is then
+        a width-1 prefix search, not the greedy decoder.  With the defaults nothing changes."""
         assert isinstance(beam_width, int), "beam_width must be integer."
         assert beam_width >= 1, "beam_width must be >= 1"
         logits = logits.contiguous()
         seq = torch.as_tensor(inputs_seq_len, dtype=torch.int32, device=logits.device)
-        if beam_width == 1:
+        if lm is not None or float(insertion_bonus) != 0.0:
+            from .decoders.charlm_beam_search_decoder import lm_weights_of
+            lab, n, _, _ = ops.ctc_beam_decode_lm(logits, seq, beam_width, lm=lm_weights_of(lm), lm_weight=lm_weight,
+                                                  insertion_bonus=insertion_bonus)
+        elif float(lm_weight) != 0.0:
+            raise ValueError('lm_weight = %r needs a language model' % (lm_weight,))
+        elif beam_width == 1:
             lab, n = ops.ctc_greedy_decode(logits, seq)
         else:
             lab, n, _ = ops.ctc_beam_decode(logits, seq, beam_width=beam_width)

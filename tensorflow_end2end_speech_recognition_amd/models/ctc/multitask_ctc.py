@@ -137,10 +137,12 @@ class MultitaskCTC(CTC):
         return dict(d_outputs_sub=dsub.view(T, Bp, E))
 
     # ------------------------------------------------------------------ decode / eval
-    def decoder(self, logits_main, logits_sub, inputs_seq_len, beam_width=1, merge_repeated=True):
-        """:314-347 -> (decode_op_main, decode_op_sub), each the SparseTensor triple (merge_repeated: see CTC.decoder)."""
+    def decoder(self, logits_main, logits_sub, inputs_seq_len, beam_width=1, merge_repeated=True, lm=None, lm_weight=0.0,
+                insertion_bonus=0.0):
+        """:314-347 -> (decode_op_main, decode_op_sub), each the SparseTensor triple (merge_repeated, lm, lm_weight,
+        insertion_bonus: see CTC.decoder; the language model and the bonus go to the main head only)."""
         dec = super(MultitaskCTC, self).decoder
-        return (dec(logits_main, inputs_seq_len, beam_width, merge_repeated),
+        return (dec(logits_main, inputs_seq_len, beam_width, merge_repeated, lm, lm_weight, insertion_bonus),
                 dec(logits_sub, inputs_seq_len, beam_width, merge_repeated))
 
     def posteriors(self, logits_main, logits_sub):

@@ -5,6 +5,7 @@ pointers + shapes to libasr_hip.so.  No arithmetic happens in torch here and
 there is no CPU fallback: non-CUDA tensors raise.
 """
 import ctypes as C
+import math
 import os
 import time as _time
 
@@ -2458,6 +2459,120 @@ def att_lm_counts(device=0):
 def reset_att_lm_counts(device=0):
     for h in _device_handles(device):
         h.check(h.lib.asr_reset_att_lm_counts(h.h), 'asr_reset_att_lm_counts')
+
+
+# ------------------------------------------------- CTC prefix beam search with LM fusion / insertion bonus (an extension)
+def _ctc_lm_args(who, logits, seq_len, beam_width, lm_weight, insertion_bonus, blank):
+    _chk(logits, torch.float32, 'logits')
+    _chk(seq_len, torch.int32, 'seq_len')
+    T, B, Cc = (int(v) for v in logits.shape)
+    W = int(beam_width)
+    if W < 1 or W > MAX_BEAM_WIDTH or W > Cc - 1:
+        raise ValueError('%s: beam_width must be in 1 .. min(%d, C - 1 = %d), got %d' % (who, MAX_BEAM_WIDTH, Cc - 1, W))
+    alpha, beta = float(lm_weight), float(insertion_bonus)
+    if not (math.isfinite(alpha) and math.isfinite(beta)):
+        raise ValueError('%s: lm_weight / insertion_bonus must be finite, got %r / %r' % (who, lm_weight, insertion_bonus))
+    return T, B, Cc, W, alpha, beta, Cc - 1 if blank is None else int(blank)
+
+
+def _ctc_lm_check(lm, Cc):
+    """The LM must be fp32, have V >= C + 1 classes and keep <SOS> / <EOS> out of the CTC labels 0 .. C-2."""
+    if lm['emb'].dtype != torch.float32:
+        raise ValueError('ctc_beam_decode_lm: the language model must be fp32, got %s' % lm['emb'].dtype)
+    V = int(lm['emb'].shape[0])
+    if V < Cc + 1:
+        raise ValueError('ctc_beam_decode_lm: the language model has %d classes, a CTC model of %d classes needs >= %d'
+                         % (V, Cc, Cc + 1))
+    if lm.get('sos') is None:
+        raise ValueError("ctc_beam_decode_lm: the language model dict needs 'sos'")
+    for k in ('sos', 'eos'):
+        if lm.get(k) is not None and not Cc - 1 <= int(lm[k]) < V:
+            raise ValueError('ctc_beam_decode_lm: <%s> = %d of the language model lies inside the CTC labels 0 .. %d'
+                             % (k.upper(), int(lm[k]), Cc - 2))
+    return V
+
+
+def ctc_beam_decode_lm(logits, seq_len, beam_width, lm=None, lm_weight=0.0, insertion_bonus=0.0, blank=None, _poison=False):
+    """Prefix beam search with shallow LM fusion and an insertion bonus from one call (asr_ctc_beam_decode_lm; the float64
+    statement is models/ctc/decoders/charlm_beam_search_decoder.py): every extension of a prefix by a label c uses
+    p_t + lm_weight * log p_lm(c | <SOS>, prefix) + insertion_bonus in place of p_t.  logits [T,B,C] fp32; lm:
+    RNNLM.decode_weights() (fp32, V >= C + 1 classes, 'sos' -- and 'eos' when given -- outside the CTC labels) or None
+    (lm_weight must then be 0).  1 <= beam_width <= 32, <= C - 1.  Returns (labels [B,T] int32 padded -1, lengths [B],
+    scores [B] float64 = -log of the best prefix' fused total, lm_score [B] fp32 = its sum of log p_lm).
+    _poison (tests): the workspace starts as NaN bit patterns."""
+    T, B, Cc, W, alpha, beta, blank = _ctc_lm_args('ctc_beam_decode_lm', logits, seq_len, beam_width, lm_weight,
+                                                   insertion_bonus, blank)
+    if lm is None and alpha != 0.0:
+        raise ValueError('ctc_beam_decode_lm: lm_weight = %r needs a language model' % (lm_weight,))
+    V = _ctc_lm_check(lm, Cc) if lm is not None else 0
+    h = _h(logits)                                              # (after the argument checks: they hold without a device)
+    dev = logits.device
+    lst, keep = _lm_struct(lm, B * W, W, 1.0) if lm is not None else (None, None)
+    nbytes = h.lib.asr_ctc_beam_lm_workspace_bytes(T, B, Cc, W, V)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    if _poison:
+        ws.fill_(0xFF)
+    out, n = _i32((B, T), dev), _i32((B,), dev)
+    score = torch.empty((B,), dtype=torch.float64, device=dev)
+    lm_score = _f32((B,), dev)
+    h.check(h.lib.asr_ctc_beam_decode_lm(h.h, _p(logits), T, B, Cc, _p(seq_len), blank, W, alpha, beta,
+                                         C.byref(lst) if lst is not None else None, _p(out), _p(n), _p(score), _p(lm_score),
+                                         _p(ws), nbytes, _s()), 'asr_ctc_beam_decode_lm')
+    return out, n, score, lm_score
+
+
+class CtcBeamLmFrames(object):
+    """The one-frame form of ctc_beam_decode_lm (asr_ctc_beam_lm_frame), for tests and probes: the caller supplies each
+    slot's LM logits row.  frame(t, lm_logits [B*W,V] fp32 or None) must be called for t = 0, 1, ... in order; returns
+    (parent [B,W], word [B,W] int32, p_b, p_nb [B,W] float64, lm_total [B,W] fp32, entries [B] int32) of the new beam
+    (state rows of an utterance past its seq_len, and slots >= entries, are not written)."""
+
+    def __init__(self, logits, seq_len, beam_width, lm_weight=0.0, insertion_bonus=0.0, blank=None):
+        self.h = _h(logits)
+        self.logits, self.seq_len = logits, seq_len
+        self.T, self.B, self.C, self.W, self.alpha, self.beta, self.blank = _ctc_lm_args(
+            'CtcBeamLmFrames', logits, seq_len, beam_width, lm_weight, insertion_bonus, blank)
+        self.nbytes = self.h.lib.asr_ctc_beam_lm_workspace_bytes(self.T, self.B, self.C, self.W, 0)
+        self.ws = torch.empty((self.nbytes,), dtype=torch.uint8, device=logits.device)
+
+    def frame(self, t, lm_logits=None):
+        B, W, dev = self.B, self.W, self.logits.device
+        V = 0
+        if lm_logits is not None:
+            _chk(lm_logits, torch.float32, 'lm_logits')
+            V = int(lm_logits.shape[1])
+            if tuple(lm_logits.shape) != (B * W, V) or V < self.C:
+                raise ValueError('CtcBeamLmFrames: lm_logits must be [%d, V >= %d]' % (B * W, self.C))
+        elif self.alpha != 0.0:
+            raise ValueError('CtcBeamLmFrames: lm_weight = %r needs LM logits' % (self.alpha,))
+        parent, word, nb = _i32((B, W), dev), _i32((B, W), dev), torch.zeros((B,), dtype=torch.int32, device=dev)
+        pb = torch.zeros((B, W), dtype=torch.float64, device=dev)
+        pnb = torch.zeros((B, W), dtype=torch.float64, device=dev)
+        lmt = torch.zeros((B, W), dtype=torch.float32, device=dev)
+        h = self.h
+        h.check(h.lib.asr_ctc_beam_lm_frame(h.h, _p(self.logits), int(t), self.T, B, self.C, _p(self.seq_len), self.blank, W,
+                                            self.alpha, self.beta, _p(lm_logits), V, _p(parent), _p(word), _p(pb), _p(pnb),
+                                            _p(lmt), _p(nb), _p(self.ws), self.nbytes, _s()), 'asr_ctc_beam_lm_frame')
+        return parent, word, pb, pnb, lmt, nb
+
+
+_CTC_BEAM_LM_KEYS = ('frames', 'lm_steps', 'commits')
+
+
+def ctc_beam_lm_counts(device=0):
+    """Launches of the LM-fused CTC prefix search on `device` since the last reset, summed over its handles
+    (asr_ctc_beam_lm_counts): frame kernels, LM steps, commits.  Host counters: no device work, no synchronisation."""
+    tot = [0] * 3
+    for h in _device_handles(device):
+        out = (C.c_ulonglong * 3)()
+        h.check(h.lib.asr_ctc_beam_lm_counts(h.h, out), 'asr_ctc_beam_lm_counts')
+        tot = [x + int(y) for x, y in zip(tot, out)]
+    return dict(zip(_CTC_BEAM_LM_KEYS, tot))
+
+
+def reset_ctc_beam_lm_counts(device=0):
+    for h in _device_handles(device):
+        h.check(h.lib.asr_reset_ctc_beam_lm_counts(h.h), 'asr_reset_ctc_beam_lm_counts')
 
 
 def tanh_fwd(x):
