@@ -28,7 +28,10 @@ def _decode(model, inputs, seq_len, beam_width, task=None, lm_kw=None):
     dummy = np.zeros((B, 1), dtype=np.int64)                    # labels are not needed for the logits
     if task is None:
         _, logits = model.compute_loss(inputs, dummy, seq_len, keep_prob=1.0, is_training=False)
-        dec = model.decoder(logits, seq_len, beam_width=beam_width, **lm_kw)
+        # the logits of a model that subsamples in time have output_seq_len(seq_len) frames; a model object without the
+        # method (these loops take any object with compute_loss / decoder) does not subsample: seq_len
+        out_len = model.output_seq_len(seq_len) if hasattr(model, 'output_seq_len') else seq_len
+        dec = model.decoder(logits, out_len, beam_width=beam_width, **lm_kw)
     else:
         _, logits_main, logits_sub = model.compute_loss(inputs, dummy, dummy, seq_len, keep_prob=1.0,
                                                         is_training=False)

@@ -54,7 +54,8 @@ def model_kwargs(params):
         clip_activation_decoder=params['clip_activation_decoder'], weight_decay=params['weight_decay'],
         time_major=True, sharpening_factor=params['sharpening_factor'],
         logits_temperature=params['logits_temperature'], sigmoid_smoothing=params['sigmoid_smoothing'],
-        dtype=params.get('dtype', 'f32'), device=params.get('device', 'cuda:0'))
+        dtype=params.get('dtype', 'f32'), device=params.get('device', 'cuda:0'),
+        subsample_list=params.get('subsample_list'), subsample_type=params.get('subsample_type', 'drop'))
 
 
 def run_name(params):
@@ -74,6 +75,8 @@ def run_name(params):
         name += '_sharp' + str(params['sharpening_factor'])
     if params['logits_temperature'] != 1:
         name += '_temp' + str(params['logits_temperature'])
+    if params.get('subsample_list') and any(params['subsample_list']):
+        name += '_sub' + params.get('subsample_type', 'drop') + str(sum(bool(f) for f in params['subsample_list']))
     return name
 
 

@@ -91,8 +91,10 @@ def do_train(model, params):
             labels_d_st = list2sparsetensor(labels_d, padded_value=dev_data.padded_value)
             loss_train, logits_train = model.compute_loss(x, labels_st, sl, 1.0, is_training=False)
             loss_dev, logits_dev = model.compute_loss(xd, labels_d_st, sld, 1.0, is_training=False)
-            ler_train = model.compute_ler(model.decoder(logits_train, sl, params['beam_width']), labels_st)
-            ler_dev = model.compute_ler(model.decoder(logits_dev, sld, params['beam_width']), labels_d_st)
+            ler_train = model.compute_ler(model.decoder(logits_train, model.output_seq_len(sl), params['beam_width']),
+                                          labels_st)
+            ler_dev = model.compute_ler(model.decoder(logits_dev, model.output_seq_len(sld), params['beam_width']),
+                                        labels_d_st)
             csv_loss.write('%d,%f,%f\n' % (step, float(loss_train), float(loss_dev)))
             csv_ler.write('%d,%f,%f\n' % (step, ler_train, ler_dev))
             print('Step %d (epoch: %.3f): loss = %.3f (%.3f) / ler = %.3f (%.3f) / lr = %.5f (%.3f min)' %
@@ -164,7 +166,8 @@ def build_model(params):
                 use_peephole=params['use_peephole'], parameter_init=params['weight_init'],
                 clip_grad_norm=params['clip_grad_norm'], clip_activation=params['clip_activation'],
                 num_proj=params['num_proj'], weight_decay=params['weight_decay'],
-                dtype=params.get('dtype', 'bf16'), device=params.get('device', 'cuda:0'))
+                dtype=params.get('dtype', 'bf16'), device=params.get('device', 'cuda:0'),
+                subsample_list=params.get('subsample_list'), subsample_type=params.get('subsample_type', 'drop'))
     # run-directory name, as :338-351
     model.name += '_' + str(params['num_units'])
     model.name += '_' + str(params['num_layers'])
@@ -178,6 +181,8 @@ def build_model(params):
         model.name += '_stack' + str(params['num_stack'])
     if params['weight_decay'] != 0:
         model.name += '_wd' + str(params['weight_decay'])
+    if any(model.subsample_list):
+        model.name += '_sub' + model.subsample_type + str(sum(model.subsample_list))
     return model
 
 

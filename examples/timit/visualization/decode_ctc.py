@@ -59,7 +59,8 @@ def main(argv=None):
         B = inputs[0].shape[0]
         _, logits = model.compute_loss(inputs[0], np.zeros((B, 1), dtype=np.int64), inputs_seq_len[0], keep_prob=1.0,
                                        is_training=False)
-        hyps = sparsetensor2list(model.decoder(logits, inputs_seq_len[0], beam_width=args.beam_width), B)
+        hyps = sparsetensor2list(model.decoder(logits, model.output_seq_len(inputs_seq_len[0]),
+                                               beam_width=args.beam_width), B)
         for b in range(B):
             ref, hyp = labels_true[0][b][0], to_str(np.asarray(hyps[b], dtype=np.int64))
             pairs.append((str(input_names[0][b]), ref, hyp))

@@ -95,6 +95,24 @@ int asr_stack_frames(asr_handle* h, const float* x, const int32_t* seq_len, int 
  * x[B,T,D], D = channels*3*num_stack; out[B,T,D*splice], zero for t >= seq_len[b]. */
 int asr_splice(asr_handle* h, const float* x, const int32_t* seq_len, int B, int T, int D, int splice,
                int num_stack, float* out, asr_stream s);
+/* Time subsampling between two recurrent layers (later within ABI 5; subsample_list / subsample_type of
+ * examples/timit/config/ctc/regularization/blstm_ctc_subsample.yml and config/attention/att_baseline.yml; the 'concat'
+ * form is the frame stacking of models/encoders/core/pyramidal_blstm.py:160-170 with its floor-halved lengths, :120-122).
+ * One 2x reduction of the time-major x[T,Bp,W] in `dtype` (what a recurrence wrote) with frame counts len_in[Bp]:
+ *   len_out[b] = len_in[b] >> 1 for all Bp rows (len_in clamped to [0,T]; an odd trailing frame is dropped),
+ *   ASR_SUBSAMPLE_DROP  : y[b,t',:] = x[2t'+1,b,:]                  (W' = W; the forward direction has seen both frames)
+ *   ASR_SUBSAMPLE_CONCAT: y[b,t',:] = [x[2t',b,:] ; x[2t'+1,b,:]]   (W' = 2W)
+ * for t' < len_out[b] and zero for len_out[b] <= t' < T/2, written as the batch-major fp32 y[B, T/2, W'] (B <= Bp real
+ * utterances) the next layer stack takes as its input.  x is never read at frames >= 2 len_out[b].  T/2 == 0 or B == 0:
+ * only the lengths are written. */
+typedef enum { ASR_SUBSAMPLE_DROP = 0, ASR_SUBSAMPLE_CONCAT = 1 } asr_subsample_type;
+int asr_time_subsample_fwd(asr_handle* h, int dtype, int type, const void* x_tb, const int32_t* len_in, int T, int Bp,
+                           int B, int W, float* y_bt, int32_t* len_out, asr_stream s);
+/* Its exact transpose: dy[T/2,Bp,W'] fp32 time-major (the input gradient of the layer stack above) -> dx[T,Bp,W] fp32,
+ * EVERY element written: drop dx[2t'+1] = dy[t'], concat dx[2t'] = dy[t'][:W] and dx[2t'+1] = dy[t'][W:] for
+ * t' < len_out[b], zero everywhere else.  dy is never read at t' >= len_out[b]. */
+int asr_time_subsample_bwd(asr_handle* h, int type, const float* dy_tb, const int32_t* len_out, int T, int Bp, int W,
+                           float* dx_tb, asr_stream s);
 /* out[c*ld_out + r] = in[r*ld_in + c] for an [rows, cols] matrix in `dtype` (LDS-tiled, both
  * sides coalesced).  The MFMA GEMM wants both operands reduction-contiguous; the k-major ones
  * (W_x as stored by TF: [Din, 4H], models/encoders/core/blstm.py:286-320 via LSTMBlockCell's

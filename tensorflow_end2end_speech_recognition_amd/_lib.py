@@ -175,6 +175,9 @@ SIGNATURES = {
     'asr_ctc_beam_decode_lm': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, C.c_double, C.c_double, _vp] + [_vp] * 5 + [_sz, _vp]),
     'asr_ctc_beam_lm_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
     'asr_reset_ctc_beam_lm_counts': (_i, [_vp]),
+    # time subsampling between recurrent layers (later within ABI 5)
+    'asr_time_subsample_fwd': (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'asr_time_subsample_bwd': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
     'asr_add_cols': (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp]),
     'asr_tanh_fwd': (_i, [_vp, _vp, _vp, _sz, _vp]),
     'asr_tanh_bwd': (_i, [_vp, _vp, _vp, _vp, _sz, _vp]),

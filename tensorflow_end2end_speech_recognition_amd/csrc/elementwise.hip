@@ -15,6 +15,7 @@
 // still 5 (additive): asr_att_path_counts / asr_reset_att_path_counts, asr_conv_path_counts / asr_reset_conv_path_counts
 // (host counters of the kernels a call launched).
 // still 5 (additive): asr_gemm_rows (the NT products on listed rows), asr_gemm_path_counts / asr_reset_gemm_path_counts.
+// still 5 (additive): asr_time_subsample_fwd / asr_time_subsample_bwd (subsample.hip).
 extern "C" int asr_abi_version(void) { return 5; }
 
 extern "C" int asr_create(asr_handle** out, int device) { return asr_create_ex(out, device, (size_t)192 << 20); }

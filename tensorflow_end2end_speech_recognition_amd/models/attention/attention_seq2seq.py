@@ -30,6 +30,7 @@ from ..._lib import ASR_BF16, ASR_F32
 from ...utils.evaluation.edit_distance import compute_ler as _ler
 from ...utils.parameter import ParamStore
 from ..ctc.ctc import Placeholder, truncated_normal
+from ..encoders.core.subsample import check_subsample, load_subsampled, shift_lengths
 from ..encoders.load_encoder import load as load_encoder
 from ..model_base import ModelBase
 from .bridge import InitialStateBridge
@@ -57,7 +58,7 @@ class AttentionSeq2Seq(ModelBase):
                  clip_grad_norm=5.0, clip_activation_encoder=50, clip_activation_decoder=50,
                  weight_decay=0.0, time_major=True, sharpening_factor=1.0, logits_temperature=1.0,
                  sigmoid_smoothing=False, name='attention', dtype='f32', device='cuda:0', seed=0,
-                 _extra_vars=None, prev_alpha='zeros'):
+                 _extra_vars=None, prev_alpha='zeros', subsample_list=None, subsample_type='drop'):
         super(AttentionSeq2Seq, self).__init__()
         assert input_size % 3 == 0, 'input_size must be divisible by 3 (+ delta, double delta features).'
         assert splice % 2 == 1, 'splice must be the odd number'
@@ -108,10 +109,18 @@ class AttentionSeq2Seq(ModelBase):
 
         rng = np.random.RandomState(seed)
         st = self.store = ParamStore(self.device)
-        self.encoder = load_encoder(encoder_type)(
-            num_units=encoder_num_units, num_proj=None, num_layers=encoder_num_layers, lstm_impl=lstm_impl,
-            use_peephole=use_peephole, parameter_init=parameter_init, clip_activation=clip_activation_encoder,
-            time_major=True, dtype=self.dtype)
+        # subsample_list / subsample_type (extension keywords): time subsampling inside the encoder
+        # (models/encoders/core/subsample.py); None or all false builds exactly the plain encoder
+        self.subsample_list = check_subsample(subsample_list, subsample_type, encoder_num_layers)
+        self.subsample_type = subsample_type
+        enc_kw = dict(num_units=encoder_num_units, num_proj=None, num_layers=encoder_num_layers, lstm_impl=lstm_impl,
+                      use_peephole=use_peephole, parameter_init=parameter_init, clip_activation=clip_activation_encoder,
+                      time_major=True, dtype=self.dtype)
+        if any(self.subsample_list):
+            self.encoder = load_subsampled(encoder_type)(subsample_list=self.subsample_list,
+                                                         subsample_type=self.subsample_type, **enc_kw)
+        else:
+            self.encoder = load_encoder(encoder_type)(**enc_kw)
         E2 = self.enc_dim = self.encoder.build(st, input_size * splice, rng, scope_prefix='encoder/')
         H, U, A, Em, C2 = encoder_num_units, decoder_num_units, attention_dim, embedding_dim, self.num_classes
         u = lambda *s: rng.uniform(-parameter_init, parameter_init, size=s)
@@ -759,6 +768,12 @@ class AttentionSeq2Seq(ModelBase):
                 raise ValueError('beam search decoding has the native form only')
             return self._decode_beam(inputs, isl, beam_width, length_penalty_weight)
         return self._decode_infer(inputs, isl, native=native).cpu().numpy()
+
+    def output_seq_len(self, inputs_seq_len):
+        """The lengths of the encoder outputs (attention weights, the joint model's CTC logits) for input lengths
+        inputs_seq_len: the identity without subsampling, inputs_seq_len >> k with k true entries in subsample_list."""
+        k = sum(self.subsample_list)
+        return shift_lengths(inputs_seq_len, k) if k else inputs_seq_len
 
     def decode(self, decoder_outputs_train, decoder_outputs_infer):
         """attention_seq2seq.py:666-701."""

@@ -17,6 +17,7 @@ from ..._lib import ASR_BF16, ASR_F32
 from ...utils.io.labels.sparsetensor import dense_to_flat, sparse_to_flat
 from ...utils.evaluation.edit_distance import compute_ler as _ler
 from ...utils.parameter import ParamStore
+from ..encoders.core.subsample import check_subsample, load_subsampled, shift_lengths
 from ..encoders.load_encoder import load
 from ..model_base import ModelBase
 
@@ -51,7 +52,9 @@ class CTC(ModelBase):
     """Connectionist Temporal Classification (CTC) network (models/ctc/ctc.py:15-57 docstring).
 
     Extra keyword arguments of the HIP build (not in the reference): `dtype` ('f32' exact
-    fp32 MFMA path | 'bf16' operands with fp32 accumulate), `device`, `seed`.
+    fp32 MFMA path | 'bf16' operands with fp32 accumulate), `device`, `seed`; `subsample_list` / `subsample_type`
+    (time subsampling inside the blstm / lstm encoders, models/encoders/core/subsample.py -- the logits then have
+    T >> k frames and decoder() takes output_seq_len(inputs_seq_len); None or all false: the plain encoder).
     """
     head_scope = 'output'      # variable scope of the output FC (ctc.py:216-224)
 
@@ -59,7 +62,7 @@ class CTC(ModelBase):
                  lstm_impl='LSTMBlockCell', use_peephole=True, splice=1, num_stack=1,
                  parameter_init=0.1, clip_grad_norm=None, clip_activation=None, num_proj=None,
                  weight_decay=0.0, bottleneck_dim=None, time_major=True,
-                 dtype='f32', device='cuda:0', seed=0):
+                 dtype='f32', device='cuda:0', seed=0, subsample_list=None, subsample_type='drop'):
         super(CTC, self).__init__()
         assert input_size % 3 == 0, 'input_size must be divisible by 3 (+ delta, acceleration coefficients).'
         assert splice % 2 == 1, 'splice must be the odd number'
@@ -102,6 +105,10 @@ class CTC(ModelBase):
         self.seed = seed
 
         self.bottleneck_dim = int(bottleneck_dim) if bottleneck_dim not in (None, 0) else None
+        self.subsample_list = check_subsample(subsample_list, subsample_type, num_layers)
+        self.subsample_type = subsample_type
+        if any(self.subsample_list):
+            load_subsampled(encoder_type)                # ValueError for the families that have no subsampled form
 
         self.encoder = self._create_encoder(encoder_type, input_size, splice, num_stack, num_units, num_layers,
                                             lstm_impl, use_peephole, parameter_init, clip_activation)
@@ -118,6 +125,12 @@ class CTC(ModelBase):
                         use_peephole, parameter_init, clip_activation):
         """ctc.py:124-170: constructor keywords differ per encoder family."""
         if encoder_type in ['blstm', 'lstm']:
+            if any(self.subsample_list):
+                return load_subsampled(encoder_type)(
+                    num_units=num_units, num_proj=self.num_proj, num_layers=num_layers,
+                    lstm_impl=lstm_impl, use_peephole=use_peephole, parameter_init=parameter_init,
+                    clip_activation=clip_activation, time_major=True, dtype=self._requested_dtype,
+                    subsample_list=self.subsample_list, subsample_type=self.subsample_type)
             return load(encoder_type)(
                 num_units=num_units, num_proj=self.num_proj, num_layers=num_layers,
                 lstm_impl=lstm_impl, use_peephole=use_peephole, parameter_init=parameter_init,
@@ -342,6 +355,12 @@ class CTC(ModelBase):
         dense_shape = [lab.shape[0], int(n.max()) if len(n) else 0]
         return [np.array(indices, dtype=np.int64).reshape(-1, 2), np.array(values, dtype=np.int32),
                 np.array(dense_shape, dtype=np.int64)]
+
+    def output_seq_len(self, inputs_seq_len):
+        """The lengths of the logits for input lengths inputs_seq_len (numpy, list or tensor): what decoder() takes.
+        The identity without subsampling; inputs_seq_len >> k with k true entries in subsample_list."""
+        k = sum(self.subsample_list)
+        return shift_lengths(inputs_seq_len, k) if k else inputs_seq_len
 
     def posteriors(self, logits, blank_prior=1):
         """ctc.py:354-380: softmax over classes on the batch-major flattening [B*T, C]."""

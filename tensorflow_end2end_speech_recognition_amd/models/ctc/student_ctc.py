@@ -28,6 +28,7 @@ from ... import ops
 from ..._lib import ASR_BF16, ASR_F32
 from ...utils.parameter import ParamStore, StateStore
 from ..encoders.core import cnn_util
+from ..encoders.core.subsample import any_subsample, load_subsampled
 from ..encoders.core.student_cnn import (StudentCNNCTCEncoder, StudentCNNCompactCTCEncoder, StudentCNNXEEncoder,
                                          StudentCNNCompactXEEncoder)
 from ..model_base import ModelBase
@@ -47,8 +48,10 @@ class StudentCTC(ModelBase):
 
     def __init__(self, encoder_type, input_size, num_classes, splice=1, num_stack=1, parameter_init=0.1,
                  clip_grad_norm=None, weight_decay=0.0, time_major=True, dtype='f32', device='cuda:0', seed=0,
-                 world_size=None):
+                 world_size=None, subsample_list=None, subsample_type='drop'):
         super(StudentCTC, self).__init__()
+        if any_subsample(subsample_list):
+            load_subsampled(encoder_type)        # ValueError: the student CNNs have no subsampled form
         assert input_size % 3 == 0, 'input_size must be divisible by 3 (+ delta, double delta features).'
         assert splice % 2 == 1, 'splice must be the odd number'
         if clip_grad_norm is not None:

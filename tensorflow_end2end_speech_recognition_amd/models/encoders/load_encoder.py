@@ -3,7 +3,9 @@
 The registry is the reference's plugin point: an encoder is a class with
 __call__(inputs, inputs_seq_len, keep_prob, is_training) -> (outputs, final_state).
 Keys of the reference not built here (vgg_wang, pyramid_blstm, student_*) raise the same
-ValueError as an unknown key."""
+ValueError as an unknown key.  pyramid_blstm stays unknown: what the reference's unfinished pyramidal_blstm.py set out
+to do is the `blstm` encoder with subsample_type='concat' (the subsample_list / subsample_type keywords of the models,
+core/subsample.py), which needs no key of its own."""
 from .core.blstm import BLSTMEncoder
 from .core.lstm import LSTMEncoder
 from .core.vgg_blstm import VGGBLSTMEncoder, VGGLSTMEncoder

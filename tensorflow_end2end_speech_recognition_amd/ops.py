@@ -299,6 +299,53 @@ def bt_to_tb(x_btd, dtype=ASR_F32, ld=None):
     return out
 
 
+SUBSAMPLE_TYPES = {'drop': 0, 'concat': 1}     # asr_subsample_type
+
+
+def _subsample_type(kind):
+    if kind not in SUBSAMPLE_TYPES:
+        raise ValueError('subsample_type is "drop" or "concat", got %r' % (kind,))
+    return SUBSAMPLE_TYPES[kind]
+
+
+def time_subsample_fwd(x_tb, seq_len, batch, kind='drop'):
+    """One 2x reduction in time of a recurrence's time-major output x [T,Bp,W] (fp32 or bf16) with lengths seq_len [Bp]
+    (asr_time_subsample_fwd): returns (y [batch, T//2, W'] fp32 batch-major -- 'drop': frame 2t'+1, W' = W; 'concat':
+    frames 2t', 2t'+1 side by side, W' = 2W; zero from seq_len >> 1 on -- and the halved lengths [Bp] int32)."""
+    h = _h(x_tb)
+    typ = _subsample_type(kind)
+    _chk(seq_len, torch.int32, 'seq_len')
+    T, Bp, W = x_tb.shape
+    dtype = dtype_id(x_tb.dtype)
+    if seq_len.shape[0] != Bp or not 0 <= batch <= Bp:
+        raise ValueError('time_subsample_fwd: %d lengths, batch %d for a padded batch of %d' % (seq_len.shape[0], batch, Bp))
+    y = torch.empty((batch, T // 2, W * (2 if typ else 1)), dtype=torch.float32, device=x_tb.device)
+    len_out = torch.empty((Bp,), dtype=torch.int32, device=x_tb.device)
+    h.check(h.lib.asr_time_subsample_fwd(h.h, dtype, typ, _p(x_tb), _p(seq_len), T, Bp, int(batch), W, _p(y),
+                                         _p(len_out), _s()), 'asr_time_subsample_fwd')
+    return y, len_out
+
+
+def time_subsample_bwd(dy_tb, len_out, T, kind='drop', out=None):
+    """The transpose of time_subsample_fwd: dy [T//2,Bp,W'] fp32 time-major and the halved lengths [Bp] ->
+    dx [T,Bp,W] fp32 (`out` or a new tensor), every element written (asr_time_subsample_bwd)."""
+    h = _h(dy_tb)
+    typ = _subsample_type(kind)
+    _chk(dy_tb, torch.float32, 'dy')
+    _chk(len_out, torch.int32, 'len_out')
+    T2, Bp, Wo = dy_tb.shape
+    if T2 != int(T) // 2 or len_out.shape[0] != Bp or (typ and Wo % 2):
+        raise ValueError('time_subsample_bwd: dy %s does not belong to T = %d / %d lengths'
+                         % (tuple(dy_tb.shape), T, len_out.shape[0]))
+    W = Wo // 2 if typ else Wo
+    dx = out if out is not None else torch.empty((int(T), Bp, W), dtype=torch.float32, device=dy_tb.device)
+    if out is not None and (tuple(out.shape) != (int(T), Bp, W) or out.dtype != torch.float32):
+        raise ValueError('time_subsample_bwd: out must be fp32 %s' % ((int(T), Bp, W),))
+    h.check(h.lib.asr_time_subsample_bwd(h.h, typ, _p(dy_tb), _p(len_out), int(T), Bp, W, _p(dx), _s()),
+            'asr_time_subsample_bwd')
+    return dx
+
+
 def stack_frames(x_btf, seq_len, num_stack, num_skip):
     """Zero-padded batch [B,T,F] fp32 + seq_len [B] int32 -> ([B, ceil(T/num_skip), F*num_stack], new seq_len)."""
     h = _h(x_btf)
