@@ -928,7 +928,8 @@ int asr_reset_att_beam_counts(asr_handle* h);
  * length rule and the lpw == 1 quirk of asr_att_beam_select; the W best by (score descending, flat index ascending) give
  * word / parent / score [B,W] and the next state log_probs = total (attention alone: the weight applies to totals),
  * ctc_score = ctc, finished, lengths, last = word (the parent's for <EOS>).  State out may be state in.  Three launches
- * (candidates, asr_ctc_prefix_score's kernel, rank); cand / cand_total / psi: scratch [B*W,W+1].  W <= n_labels + 1,
+ * (candidates, asr_ctc_prefix_score's kernel, rank -- the kernel pair of asr_att_beam_select_fused, att_beam.hip,
+ * instantiated without the LM stream); cand / cand_total / psi: scratch [B*W,W+1].  W <= n_labels + 1,
  * 0 < ctc_weight <= 1 (0 is asr_att_beam_select's job).  seq_len >= 1 is the caller's contract (the statement raises; the
  * entries cannot look at device lengths).  At 0 frames nothing faults: the utterance has the empty hypothesis alone
  * (psi(<EOS>) = 0, labels -inf), and a place no candidate with a finite CTC score reaches -- only possible there -- comes out
@@ -994,7 +995,9 @@ int asr_reset_att_joint_counts(asr_handle* h);
  * asr_lm_step, in this order: per layer l = 0 .. L-1 the product + cell (above) from in (layer l), c / h block 0 into c / h
  * block 1 (and the next layer's x columns); then lm_logits [R,C2] = h block 1 of layer L-1 x W_out + b_out (asr_gemm_act),
  * raw logits -- no log-softmax pass: the selection normalises them in its own row reduction.
- * asr_att_beam_select_fused: asr_att_beam_select / _joint on two or three score streams.
+ * asr_att_beam_select_fused: asr_att_beam_select / _joint on two or three score streams (one templated kernel pair with
+ * asr_att_beam_select_joint, att_beam.hip: the candidates kernel with or without the LM stream, the rank kernel per set
+ * of streams).
  *  1. candidates kernel, a wave per row: lse_att and lse_lm, each in the order of asr_att_beam_select (lane l takes classes
  *     l, l + 64, ... ascending into a running maximum, xor butterfly 32 .. 1; the sum of exp(x - max) the same way;
  *     lse = max + log(sum)); p_att = x - lse_att, p_lm = z - lse_lm; local = p_att + lm_weight * p_lm; the W best classes

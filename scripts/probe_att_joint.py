@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Probes for the joint CTC / attention beam search (models/attention/decoders/beam_search/ctc_prefix_score.py,
-csrc/ctc_prefix.hip).
+csrc/ctc_prefix.hip for the prefix scorer, csrc/att_beam.hip for the selection).
 
     python scripts/probe_att_joint.py --seeds     CPU: the seeds the tests assert -- a case whose best hypothesis differs
                                                   between ctc_weight 0.5 and attention alone, and seeds of the selection

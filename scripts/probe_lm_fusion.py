@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Probes for shallow LM fusion in the attention beam search (models/attention/decoders/beam_search/lm_fusion.py,
-csrc/lm_fusion.hip).
+csrc/lm_fusion.hip for the language model, csrc/att_beam.hip for the selection).
 
     python scripts/probe_lm_fusion.py             GPU: infer() at cfg D's widths (scripts/probe_att_beam.py: 5 x 512 BLSTM,
                                                   T = 400, B = 32) at W in {1, 5, 10, 20}: without a language model, and with

@@ -1740,15 +1740,13 @@ __global__ __launch_bounds__(512) void att_dq_cell_bwd_kernel(const float* __res
 }
 }  // namespace
 
-#define ATT_NEED(cond, ...) do { if (!(cond)) ASR_FAIL(h, ASR_ERR_INVALID_ARG, __VA_ARGS__); } while (0)
-
 extern "C" int asr_lstm_cell_fwd_ex(asr_handle* h, const float* pre, const float* c_prev, const float* h_prev,
                                     const float* peep, const float* live, int B, int U, float forget_bias,
                                     float cell_clip, float* gates, float* c_raw, float* c_out, float* h_out,
                                     float* h_raw, const float* out_mask, float* cell_out, float* h_out2, int ld_h2,
                                     float* cell_out2, int ld_c2, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  ATT_NEED(pre && c_prev && h_prev && live && gates && c_raw && c_out && h_out && h_raw && B > 0 && U > 0 &&
+  ASR_NEED(pre && c_prev && h_prev && live && gates && c_raw && c_out && h_out && h_raw && B > 0 && U > 0 &&
                (!h_out2 || ld_h2 >= U) && (!cell_out2 || ld_c2 >= U), "asr_lstm_cell_fwd: bad args");
   hipLaunchKernelGGL(cell_fwd_kernel, dim3((B * U + 255) / 256), dim3(256), 0, (hipStream_t)s, pre, c_prev, h_prev,
                      peep, live, B, U, forget_bias, cell_clip, gates, c_raw, c_out, h_out, h_raw, out_mask, cell_out,
@@ -1770,7 +1768,7 @@ static int cell_bwd_launch(asr_handle* h, const float* dh_use, const float* dc_n
                            float* dpeep_rows, const float* dh_next2, int ld2, const float* use_mask, float clip,
                            asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  ATT_NEED(dh_use && dc_next && dh_next && gates && c_raw && c_prev && live && dpre && dc_prev && dh_prev_carry &&
+  ASR_NEED(dh_use && dc_next && dh_next && gates && c_raw && c_prev && live && dpre && dc_prev && dh_prev_carry &&
                B > 0 && U > 0 && (!dh_next2 || ld2 >= U), "asr_lstm_cell_bwd: bad args");
   hipLaunchKernelGGL(cell_bwd_kernel, dim3((B * U + 255) / 256), dim3(256), 0, (hipStream_t)s, dh_use, dc_next,
                      dh_next, gates, c_raw, c_prev, peep, live, B, U, dpre, dc_prev, dh_prev_carry, dpeep_rows,
@@ -1796,7 +1794,7 @@ extern "C" int asr_lstm_cell_bwd_ex(asr_handle* h, const float* dh_use, const fl
 static int energy_fwd_launch(asr_handle* h, const float* keys, const float* qz, const float* v, int T, int B, int A,
                              int mode, float* energy, const int32_t* seq_len, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  ATT_NEED(qz && energy && T > 0 && B > 0 && A > 0 && (mode == 0 ? v != nullptr : keys != nullptr),
+  ASR_NEED(qz && energy && T > 0 && B > 0 && A > 0 && (mode == 0 ? v != nullptr : keys != nullptr),
            "asr_att_energy_fwd: bad args");
   const dim3 grid((T + ATT_CH - 1) / ATT_CH, B);
 #define ASR_EFWD(L, NV_) \
@@ -1833,7 +1831,7 @@ static int energy_bwd_launch(asr_handle* h, const float* denergy, const float* k
   // load) -- no reduction launch here, dqz / dv_rows are not written
   if (!h) return ASR_ERR_INVALID_ARG;
   const int shape = energy_vec_shape(A, keys, qz, v, dkeys);
-  ATT_NEED((denergy || (fold && fold->da && shape)) && qz && dqz && T > 0 && B > 0 && A > 0,
+  ASR_NEED((denergy || (fold && fold->da && shape)) && qz && dqz && T > 0 && B > 0 && A > 0,
            "asr_att_energy_bwd: bad args");
   // frames per workgroup: 64 (measured at T = 1600, A = 128 without keys: 256-frame workgroups -- a 4x shorter
   // reduction -- run 20 us instead of 7, one wave per SIMD cannot hide the exp / rcp latency)
@@ -1881,7 +1879,7 @@ static int loc_energy_fwd_launch(asr_handle* h, const float* alpha_prev, const f
                                  const float* keys, const float* qz, const float* v, int T, int B, int A, int taps,
                                  float* energy, const int32_t* seq_len, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  ATT_NEED(alpha_prev && filt && wfil && qz && v && energy && T > 0 && B > 0 && A > 0 && taps > 0,
+  ASR_NEED(alpha_prev && filt && wfil && qz && v && energy && T > 0 && B > 0 && A > 0 && taps > 0,
            "asr_att_loc_energy_fwd: bad args");
   const dim3 grid((T + ATT_CH - 1) / ATT_CH, B);
   const int shape = loc_vec_shape(A, keys, qz, v, wfil, nullptr);
@@ -1915,7 +1913,7 @@ static int loc_energy_bwd_launch(asr_handle* h, const float* denergy, const floa
                                  float* dfilt_rows, float* dalpha_prev, int accumulate, const int32_t* seq_len,
                                  asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  ATT_NEED(denergy && alpha_prev && filt && wfil && qz && v && dqz && dwfil_rows && dfilt_rows && dalpha_prev &&
+  ASR_NEED(denergy && alpha_prev && filt && wfil && qz && v && dqz && dwfil_rows && dfilt_rows && dalpha_prev &&
                T > 0 && B > 0 && A > 0 && taps > 0, "asr_att_loc_energy_bwd: bad args");
   const int nch = (T + ATT_CH - 1) / ATT_CH;
   const size_t NP = (size_t)(2 + LOC_C) * A;
@@ -1984,7 +1982,7 @@ extern "C" int asr_att_softmax_ctx_fwd_ex(asr_handle* h, const float* energy, co
                                           float* alpha, float* ctx, float* sigmoid_norm, float* ctx2, int ld2,
                                           float* ctx3, int ld3, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  ATT_NEED(energy && seq_len && enc && alpha && ctx && T > 0 && B > 0 && E > 0 && asr_dtype_ok(enc_dtype) &&
+  ASR_NEED(energy && seq_len && enc && alpha && ctx && T > 0 && B > 0 && E > 0 && asr_dtype_ok(enc_dtype) &&
                (!ctx2 || ld2 >= E) && (!ctx3 || ld3 >= E), "asr_att_softmax_ctx_fwd: bad args");
   const size_t lds = (size_t)T * sizeof(float);
   if (lds > 64 * 1024) ASR_FAIL(h, ASR_ERR_UNSUPPORTED, "asr_att_softmax_ctx_fwd: T=%d too long", T);
@@ -2043,7 +2041,7 @@ static int softmax_ctx_bwd_launch(asr_handle* h, const float* dctx_a, const floa
                                   const float* sigmoid_norm, const float* dalpha_extra, SoftmaxBwdFold* fold,
                                   asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  ATT_NEED(dctx_a && alpha && seq_len && enc && denergy && T > 0 && B > 0 && E > 0 && asr_dtype_ok(enc_dtype) &&
+  ASR_NEED(dctx_a && alpha && seq_len && enc && denergy && T > 0 && B > 0 && E > 0 && asr_dtype_ok(enc_dtype) &&
                (!dctx_b || (dctx_out && ldb >= E)), "asr_att_softmax_ctx_bwd: bad args");
   hipStream_t st = (hipStream_t)s;
   const int nch = (T + ATT_CH - 1) / ATT_CH;
@@ -2098,7 +2096,7 @@ extern "C" int asr_att_softmax_ctx_bwd(asr_handle* h, const float* dctx, const f
 
 extern "C" int asr_tanh_fwd(asr_handle* h, const float* x, float* y, size_t n, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  ATT_NEED(x && y, "asr_tanh_fwd: null");
+  ASR_NEED(x && y, "asr_tanh_fwd: null");
   if (!n) return ASR_OK;
   hipLaunchKernelGGL(tanh_fwd_kernel, dim3(gridn(n)), dim3(256), 0, (hipStream_t)s, x, y, n);
   ASR_CHECK_LAUNCH(h, "asr_tanh_fwd");
@@ -2106,7 +2104,7 @@ extern "C" int asr_tanh_fwd(asr_handle* h, const float* x, float* y, size_t n, a
 }
 extern "C" int asr_tanh_bwd(asr_handle* h, const float* dy, const float* y, float* dx, size_t n, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  ATT_NEED(dy && y && dx, "asr_tanh_bwd: null");
+  ASR_NEED(dy && y && dx, "asr_tanh_bwd: null");
   if (!n) return ASR_OK;
   hipLaunchKernelGGL(tanh_bwd_kernel, dim3(gridn(n)), dim3(256), 0, (hipStream_t)s, dy, y, dx, n);
   ASR_CHECK_LAUNCH(h, "asr_tanh_bwd");
@@ -2115,7 +2113,7 @@ extern "C" int asr_tanh_bwd(asr_handle* h, const float* dy, const float* y, floa
 extern "C" int asr_embedding_gather(asr_handle* h, const float* W, const int32_t* ids, int rows, int E,
                                     float* out, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  ATT_NEED(W && ids && out && rows >= 0 && E > 0, "asr_embedding_gather: bad args");
+  ASR_NEED(W && ids && out && rows >= 0 && E > 0, "asr_embedding_gather: bad args");
   if (!rows) return ASR_OK;
   hipLaunchKernelGGL(emb_gather_kernel, dim3(gridn((size_t)rows * E)), dim3(256), 0, (hipStream_t)s, W, ids, rows, E, out);
   ASR_CHECK_LAUNCH(h, "asr_embedding_gather");
@@ -2124,7 +2122,7 @@ extern "C" int asr_embedding_gather(asr_handle* h, const float* W, const int32_t
 extern "C" int asr_embedding_scatter(asr_handle* h, const float* dout, const int32_t* ids, int rows, int E,
                                      int vocab, float* dW, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  ATT_NEED(dout && ids && dW && rows >= 0 && E > 0 && vocab > 0, "asr_embedding_scatter: bad args");
+  ASR_NEED(dout && ids && dW && rows >= 0 && E > 0 && vocab > 0, "asr_embedding_scatter: bad args");
   if (E % 4 == 0 && E <= 1024 && ((uintptr_t)dout) % 16 == 0) {
     const int groups = 256 / (E / 4);
     hipLaunchKernelGGL(emb_scatter_v4_kernel, dim3(vocab), dim3(256), (size_t)groups * E * sizeof(float) + (size_t)(2 * EMB_TILE + groups) * sizeof(int), (hipStream_t)s,
@@ -2139,7 +2137,7 @@ extern "C" int asr_seq_xent(asr_handle* h, const float* logits, const int32_t* t
                             int rows, int C, float eps, float dscale, float* row_loss, float* dlogits,
                             asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  ATT_NEED(logits && targets && weights && row_loss && rows >= 0 && C > 0, "asr_seq_xent: bad args");
+  ASR_NEED(logits && targets && weights && row_loss && rows >= 0 && C > 0, "asr_seq_xent: bad args");
   if (!rows) return ASR_OK;
   hipLaunchKernelGGL(seq_xent_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)s, logits, targets, weights,
                      rows, C, eps, dscale, row_loss, dlogits);
@@ -2148,7 +2146,7 @@ extern "C" int asr_seq_xent(asr_handle* h, const float* logits, const int32_t* t
 }
 extern "C" int asr_argmax_rows(asr_handle* h, const float* x, int rows, int C, int32_t* out, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  ATT_NEED(x && out && rows >= 0 && C > 0, "asr_argmax_rows: bad args");
+  ASR_NEED(x && out && rows >= 0 && C > 0, "asr_argmax_rows: bad args");
   if (!rows) return ASR_OK;
   hipLaunchKernelGGL(argmax_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)s, x, rows, C, out);
   ASR_CHECK_LAUNCH(h, "asr_argmax_rows");
@@ -2159,14 +2157,12 @@ extern "C" int asr_argmax_rows(asr_handle* h, const float* x, int rows, int C, i
 extern "C" int asr_add_cols(asr_handle* h, const float* x, int ldx, const float* y, int ldy, float* out, int ldo, int B,
                             int W, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  ATT_NEED(x && y && out && B > 0 && W > 0 && ldx >= W && ldy >= W && ldo >= W, "asr_add_cols: bad args");
+  ASR_NEED(x && y && out && B > 0 && W > 0 && ldx >= W && ldy >= W && ldo >= W, "asr_add_cols: bad args");
   hipLaunchKernelGGL(add_cols_kernel, dim3((B * W + 255) / 256), dim3(256), 0, (hipStream_t)s, x, ldx, y, ldy, out, ldo,
                      B, W);
   ASR_CHECK_LAUNCH(h, "asr_add_cols");
   return ASR_OK;
 }
-
-#define DEC_TRY(call) do { const int rc_ = (call); if (rc_ != ASR_OK) return rc_; } while (0)
 
 static int dec_check(asr_handle* h, const asr_att_decoder* a, bool bwd) {
   if (!a || a->To < 1 || a->B < 1 || a->T < 1 || a->U < 1 || a->Em < 0 || a->E2 < 1 || a->A < 1 || !a->W_cell ||
@@ -2257,7 +2253,7 @@ static int dec_fwd_step(asr_handle* h, const asr_att_decoder* a, int k, int ks, 
   // the cell output (times its dropout mask) lands in av[:, :U]; without a query FC it IS the query
   if (dec_cell_gemm_h(a)) {  // product + cell as one launch on the bf16 fragment image (dec_cell_image)
     h->att_counts[ASR_ATT_FWD_CELL_BF16] += 1;
-    DEC_TRY(asr_lstm_cell_gemm_fwd_h(h, din, Din, Din, a->W_cell_h, a->c_all + (size_t)k * B * U,
+    ASR_TRY(asr_lstm_cell_gemm_fwd_h(h, din, Din, Din, a->W_cell_h, a->c_all + (size_t)k * B * U,
                                      a->h_all + (size_t)k * B * U, a->peep, a->live + (size_t)k * B, B, U, a->forget_bias,
                                      a->cell_clip, a->gates_all + (size_t)ks * B * 4 * U, a->craw_all + (size_t)ks * B * U,
                                      a->c_all + (size_t)(k + 1) * B * U, a->h_all + (size_t)(k + 1) * B * U, hraw,
@@ -2265,7 +2261,7 @@ static int dec_fwd_step(asr_handle* h, const asr_att_decoder* a, int k, int ks, 
                                      dnext ? dnext + Em + E2 : nullptr, Din, av, Dav, s));
   } else if (dec_cell_gemm(a)) {    // ... on the fp32 interleaved weight image
     h->att_counts[ASR_ATT_FWD_CELL_F32IMG] += 1;
-    DEC_TRY(asr_lstm_cell_gemm_fwd(h, din, Din, Din, a->W_cell_il, a->b_cell ? 1 : 0, a->c_all + (size_t)k * B * U,
+    ASR_TRY(asr_lstm_cell_gemm_fwd(h, din, Din, Din, a->W_cell_il, a->b_cell ? 1 : 0, a->c_all + (size_t)k * B * U,
                                    a->h_all + (size_t)k * B * U, a->peep, a->live + (size_t)k * B, B, U, a->forget_bias,
                                    a->cell_clip, a->gates_all + (size_t)ks * B * 4 * U, a->craw_all + (size_t)ks * B * U,
                                    a->c_all + (size_t)(k + 1) * B * U, a->h_all + (size_t)(k + 1) * B * U, hraw,
@@ -2273,8 +2269,8 @@ static int dec_fwd_step(asr_handle* h, const asr_att_decoder* a, int k, int ks, 
                                    dnext ? dnext + Em + E2 : nullptr, Din, av, Dav, s));
   } else {
     h->att_counts[ASR_ATT_FWD_CELL_GEMM] += 1;
-    DEC_TRY(asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, B, 4 * U, Din, din, Din, a->W_cell, 4 * U, pre, 4 * U, a->b_cell, 0, 0, s));
-    DEC_TRY(asr_lstm_cell_fwd_ex(h, pre, a->c_all + (size_t)k * B * U, a->h_all + (size_t)k * B * U, a->peep,
+    ASR_TRY(asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, B, 4 * U, Din, din, Din, a->W_cell, 4 * U, pre, 4 * U, a->b_cell, 0, 0, s));
+    ASR_TRY(asr_lstm_cell_fwd_ex(h, pre, a->c_all + (size_t)k * B * U, a->h_all + (size_t)k * B * U, a->peep,
                                  a->live + (size_t)k * B, B, U, a->forget_bias, a->cell_clip,
                                  a->gates_all + (size_t)ks * B * 4 * U, a->craw_all + (size_t)ks * B * U,
                                  a->c_all + (size_t)(k + 1) * B * U, a->h_all + (size_t)(k + 1) * B * U, hraw,
@@ -2282,7 +2278,7 @@ static int dec_fwd_step(asr_handle* h, const asr_att_decoder* a, int k, int ks, 
                                  dnext ? dnext + Em + E2 : nullptr, Din, av, Dav, s));
   }
   if (a->has_query_fc)
-    DEC_TRY(asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, B, A, U, av, Dav, a->W_q, a->ld_wq, qz, A, a->b_q, 0, 0, s));
+    ASR_TRY(asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, B, A, U, av, Dav, a->W_q, a->ld_wq, qz, A, a->b_q, 0, 0, s));
   if (att_fused_step(h, a, qz, a->alpha_all + (size_t)k * B * T, ctx, av + U, Dav, dnext ? dnext + Em : nullptr, Din, s)) {
     h->att_counts[ASR_ATT_FWD_STEP_FUSED] += 1;
     ASR_CHECK_LAUNCH(h, "asr_att_decoder_fwd(fused step)");
@@ -2290,11 +2286,11 @@ static int dec_fwd_step(asr_handle* h, const asr_att_decoder* a, int k, int ks, 
   }
   h->att_counts[ASR_ATT_FWD_STEP_4LAUNCH] += 1;
   if (a->carry_alpha)
-    DEC_TRY(loc_energy_fwd_launch(h, k > 0 ? a->alpha_all + (size_t)(k - 1) * B * T : a->alpha_zero, a->filt, a->wfil,
+    ASR_TRY(loc_energy_fwd_launch(h, k > 0 ? a->alpha_all + (size_t)(k - 1) * B * T : a->alpha_zero, a->filt, a->wfil,
                                   a->keys, qz, a->v, T, B, A, a->taps, energy, a->seq_len, s));
   else
-    DEC_TRY(energy_fwd_launch(h, a->keys, qz, a->v, T, B, A, a->att_mode, energy, a->seq_len, s));
-  DEC_TRY(asr_att_softmax_ctx_fwd_ex(h, energy, a->seq_len, a->sharpening, a->enc, a->enc_dtype, T, B, E2,
+    ASR_TRY(energy_fwd_launch(h, a->keys, qz, a->v, T, B, A, a->att_mode, energy, a->seq_len, s));
+  ASR_TRY(asr_att_softmax_ctx_fwd_ex(h, energy, a->seq_len, a->sharpening, a->enc, a->enc_dtype, T, B, E2,
                                      a->alpha_all + (size_t)k * B * T, ctx,
                                      a->snorm_all ? a->snorm_all + (size_t)k * B : nullptr, av + U, Dav,
                                      dnext ? dnext + Em : nullptr, Din, s));
@@ -2303,11 +2299,11 @@ static int dec_fwd_step(asr_handle* h, const asr_att_decoder* a, int k, int ks, 
 
 extern "C" int asr_att_decoder_fwd(asr_handle* h, const asr_att_decoder* a, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  DEC_TRY(dec_check(h, a, false));
+  ASR_TRY(dec_check(h, a, false));
   const int B = a->B, U = a->U, T = a->T, E2 = a->E2, Em = a->Em, A = a->A;
   const int Din = Em + E2 + U, Dav = U + E2;
-  DEC_TRY(dec_cell_image(h, a, s));
-  for (int k = 0; k < a->To; ++k) DEC_TRY(dec_fwd_step(h, a, k, k, k + 1 < a->To, s));
+  ASR_TRY(dec_cell_image(h, a, s));
+  for (int k = 0; k < a->To; ++k) ASR_TRY(dec_fwd_step(h, a, k, k, k + 1 < a->To, s));
   (void)B; (void)U; (void)T; (void)E2; (void)Em; (void)A; (void)Din; (void)Dav;
   return ASR_OK;
 }
@@ -2368,7 +2364,7 @@ __global__ __launch_bounds__(256) void att_infer_select_kernel(const float* __re
 extern "C" int asr_att_decoder_infer(asr_handle* h, const asr_att_decoder* a, const asr_att_infer* f, int* steps_issued,
                                      asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  DEC_TRY(dec_check(h, a, false));
+  ASR_TRY(dec_check(h, a, false));
   if (!f || !f->W_av || !f->W_out || !f->embedding || !f->live || !f->av_all || !f->logits_all || !f->ids_all ||
       !f->live_count || f->C2 < 1 || f->eos < 0 || f->live != a->live || a->dmask)
     ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_infer: bad arguments");
@@ -2450,7 +2446,7 @@ static int att_beam_loop(asr_handle* h, const asr_att_decoder* a_, const asr_att
   asr_att_decoder d = *a_;
   if (d.carry_alpha) d.alpha_zero = m->alpha_prev;
   const asr_att_decoder* a = &d;
-  DEC_TRY(dec_check(h, a, false));
+  ASR_TRY(dec_check(h, a, false));
   if (!f || !f->W_av || !f->W_out || !f->embedding || f->C2 < 1 || f->eos < 0 || f->eos >= f->C2 || a->dmask || m->W < 1 ||
       m->W > 32 || m->W > f->C2 || a->B % m->W != 0 || !m->word || !m->parent || !m->score || !m->log_probs || !m->finished ||
       !m->lengths || !m->av || !m->logits || !m->unfinished || !m->ids || !m->hyp_len || !m->final_score ||
@@ -2463,13 +2459,13 @@ static int att_beam_loop(asr_handle* h, const asr_att_decoder* a_, const asr_att
     if (lm->R != R || lm->C2 != C2 || f->eos != C2 - 1 || C2 < 3 || W > C2 - 1 || !lm->lm_score || !lm->cand ||
         !lm->cand_total || !lm->cand_lm || !(lm->lm_weight > 0.f) || (j && !(j->ctc_weight > 0.f && j->ctc_weight <= 1.f)))
       ASR_FAIL(h, ASR_ERR_INVALID_ARG, "%s: bad arguments (the language model part)", who);
-    DEC_TRY(asr_lm_prep(h, lm, s));
+    ASR_TRY(asr_lm_prep(h, lm, s));
   }
   if (j) {
     if (!j->y || !j->seq_len || !j->r || !j->last || !j->ctc_score || !j->cand || !j->cand_total || !j->psi ||
         C2 != j->n_labels + 2 || f->eos != j->n_labels + 1)
       ASR_FAIL(h, ASR_ERR_INVALID_ARG, "%s: bad arguments (the CTC part)", who);
-    DEC_TRY(asr_ctc_prefix_init(h, j->y, j->seq_len, Bu, W, T, j->By, j->Cc, j->blank, j->r, j->last, j->ctc_score, s));
+    ASR_TRY(asr_ctc_prefix_init(h, j->y, j->seq_len, Bu, W, T, j->By, j->Cc, j->blank, j->r, j->last, j->ctc_score, s));
   }
   if (hipMemsetAsync(m->unfinished, 0, (size_t)(To + 1) * sizeof(int32_t), st) != hipSuccess)
     ASR_FAIL(h, ASR_ERR_HIP, "%s: memset", who);
@@ -2547,7 +2543,7 @@ static int att_beam_loop(asr_handle* h, const asr_att_decoder* a_, const asr_att
     for (int i = 0; i < NEV; ++i) (void)hipEventDestroy(ev[i]);
   if (rc != ASR_OK) return rc;                             // (the failing call has set the message)
   if (k < 1) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "%s: no step issued", who);
-  DEC_TRY(asr_att_beam_backtrace(h, m->word, m->parent, m->score, k, To, Bu, W, f->eos, m->ids, m->hyp_len, m->final_score, s));
+  ASR_TRY(asr_att_beam_backtrace(h, m->word, m->parent, m->score, k, To, Bu, W, f->eos, m->ids, m->hyp_len, m->final_score, s));
   if (steps_issued) *steps_issued = k;
   return ASR_OK;
 }
@@ -2574,7 +2570,7 @@ extern "C" int asr_att_decoder_beam_lm(asr_handle* h, const asr_att_decoder* a, 
 
 extern "C" int asr_att_decoder_bwd(asr_handle* h, const asr_att_decoder* a, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  DEC_TRY(dec_check(h, a, true));
+  ASR_TRY(dec_check(h, a, true));
   const int B = a->B, U = a->U, T = a->T, E2 = a->E2, Em = a->Em, A = a->A, To = a->To;
   const int Din = Em + E2 + U;
   hipStream_t st = (hipStream_t)s;
@@ -2589,7 +2585,7 @@ extern "C" int asr_att_decoder_bwd(asr_handle* h, const asr_att_decoder* a, asr_
   // the bf16 images of W_cell are written again here (one launch per loop): the call does not depend on the forward
   // loop having run with the same work space
   const bool cell_h = dec_cell_gemm_h(a);
-  if (cell_h) DEC_TRY(asr_lstm_cell_gemm_prep_h(h, a->W_cell, a->b_cell, Din, U, a->W_cell_h, s));
+  if (cell_h) ASR_TRY(asr_lstm_cell_gemm_prep_h(h, a->W_cell, a->b_cell, Din, U, a->W_cell_h, s));
   int cur = 0;
   const float* dalpha_next = nullptr;
   for (int k = To - 1; k >= 0; --k) {
@@ -2607,18 +2603,18 @@ extern "C" int asr_att_decoder_bwd(asr_handle* h, const asr_att_decoder* a, asr_
     SoftmaxBwdFold* fp = (!a->carry_alpha && energy_vec_shape(A, a->keys, qz, a->v, a->dkeys)) ? &fold : nullptr;
     const float* snorm = a->snorm_all ? a->snorm_all + (size_t)k * B : nullptr;
     if (d_in_next) {
-      DEC_TRY(softmax_ctx_bwd_launch(h, dav_ctx, d_in_next + Em, Din, dctx, alpha_k, a->seq_len, a->sharpening, a->enc,
+      ASR_TRY(softmax_ctx_bwd_launch(h, dav_ctx, d_in_next + Em, Din, dctx, alpha_k, a->seq_len, a->sharpening, a->enc,
                                      a->enc_dtype, T, B, E2, denergy, nullptr, snorm, dalpha_next, fp, s));
     } else {
       if (hipMemcpyAsync(dctx, dav_ctx, (size_t)B * E2 * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
         ASR_FAIL(h, ASR_ERR_HIP, "asr_att_decoder_bwd: copy");
-      DEC_TRY(softmax_ctx_bwd_launch(h, dctx, nullptr, 0, nullptr, alpha_k, a->seq_len, a->sharpening, a->enc,
+      ASR_TRY(softmax_ctx_bwd_launch(h, dctx, nullptr, 0, nullptr, alpha_k, a->seq_len, a->sharpening, a->enc,
                                      a->enc_dtype, T, B, E2, denergy, nullptr, snorm, dalpha_next, fp, s));
     }
     h->att_counts[(fp && fp->da) ? ASR_ATT_BWD_SOFTMAX_FOLDED : ASR_ATT_BWD_SOFTMAX_SEPARATE] += 1;
     if (a->carry_alpha) {
       float* dap = dalp[k & 1];
-      DEC_TRY(loc_energy_bwd_launch(h, denergy, k > 0 ? a->alpha_all + (size_t)(k - 1) * B * T : a->alpha_zero, a->filt,
+      ASR_TRY(loc_energy_bwd_launch(h, denergy, k > 0 ? a->alpha_all + (size_t)(k - 1) * B * T : a->alpha_zero, a->filt,
                                     a->wfil, a->keys, qz, a->v, T, B, A, a->taps, a->dkeys, dqz, dv, a->dwfil_rows,
                                     a->dfilt_rows, dap, k != To - 1, a->seq_len, s));
       dalpha_next = dap;
@@ -2637,7 +2633,7 @@ extern "C" int asr_att_decoder_bwd(asr_handle* h, const asr_att_decoder* a, asr_
     if (fused_q) {
       const float* part = nullptr;
       int nchq = 0;
-      DEC_TRY(energy_bwd_launch(h, denergy, a->keys, qz, a->v, T, B, A, a->att_mode, a->dkeys, dqz, dv, a->seq_len, fp, s,
+      ASR_TRY(energy_bwd_launch(h, denergy, a->keys, qz, a->v, T, B, A, a->att_mode, a->dkeys, dqz, dv, a->seq_len, fp, s,
                                 &part, &nchq));
       CellBwdArgs ca = {dcs[cur], dhc[cur], dh2, a->gates_all + (size_t)k * B * 4 * U, a->craw_all + (size_t)k * B * U,
                         a->c_all + (size_t)k * B * U, a->peep, a->live + (size_t)k * B, dmask,
@@ -2647,14 +2643,14 @@ extern "C" int asr_att_decoder_bwd(asr_handle* h, const asr_att_decoder* a, asr_
       ASR_CHECK_LAUNCH(h, "asr_att_decoder_bwd");
     } else {
       if (!a->carry_alpha)
-        DEC_TRY(energy_bwd_launch(h, denergy, a->keys, qz, a->v, T, B, A, a->att_mode, a->dkeys, dqz, dv, a->seq_len, fp, s));
+        ASR_TRY(energy_bwd_launch(h, denergy, a->keys, qz, a->v, T, B, A, a->att_mode, a->dkeys, dqz, dv, a->seq_len, fp, s));
       if (a->has_query_fc)
-        DEC_TRY(asr_gemm_act(h, ASR_F32, ASR_F32, 0, 1, B, U, A, dqz, A, a->W_q, a->ld_wq, dcell, U, nullptr, 1, 0, s));
+        ASR_TRY(asr_gemm_act(h, ASR_F32, ASR_F32, 0, 1, B, U, A, dqz, A, a->W_q, a->ld_wq, dcell, U, nullptr, 1, 0, s));
       else
-        DEC_TRY(asr_add_cols(h, dcell, U, dqz, A, dcell, U, B, U, s));
+        ASR_TRY(asr_add_cols(h, dcell, U, dqz, A, dcell, U, B, U, s));
       // the cell kernel applies the output dropout mask to dcell and adds the h-columns of step k+1's cell-input
       // gradient to the carried dh itself
-      DEC_TRY(cell_bwd_launch(h, dcell, dcs[cur], dhc[cur], a->gates_all + (size_t)k * B * 4 * U,
+      ASR_TRY(cell_bwd_launch(h, dcell, dcs[cur], dhc[cur], a->gates_all + (size_t)k * B * 4 * U,
                               a->craw_all + (size_t)k * B * U, a->c_all + (size_t)k * B * U, a->peep,
                               a->live + (size_t)k * B, B, U, dpre, dcs[cur ^ 1], dhc[cur ^ 1], dpeep, dh2, Din, dmask,
                               0.f, s));   // the decoder cell is tf.contrib.rnn.LSTMBlockCell (attention_seq2seq.py:354-365),
@@ -2662,11 +2658,11 @@ extern "C" int asr_att_decoder_bwd(asr_handle* h, const asr_att_decoder* a, asr_
     }
     float* d_in = a->d_in_all + (size_t)k * B * Din;
     h->att_counts[cell_h ? ASR_ATT_BWD_CELL_BF16 : ASR_ATT_BWD_CELL_GEMM] += 1;
-    if (cell_h) DEC_TRY(asr_lstm_cell_gemm_bwd_h(h, dpre, B, Din, U, a->W_cell_h, d_in, Din, s));   // bf16 weight rows
-    else DEC_TRY(asr_gemm_act(h, ASR_F32, ASR_F32, 0, 1, B, Din, 4 * U, dpre, 4 * U, a->W_cell, 4 * U, d_in, Din, nullptr, 0, 0, s));
+    if (cell_h) ASR_TRY(asr_lstm_cell_gemm_bwd_h(h, dpre, B, Din, U, a->W_cell_h, d_in, Din, s));   // bf16 weight rows
+    else ASR_TRY(asr_gemm_act(h, ASR_F32, ASR_F32, 0, 1, B, Din, 4 * U, dpre, 4 * U, a->W_cell, 4 * U, d_in, Din, nullptr, 0, 0, s));
     cur ^= 1;
   }
-  DEC_TRY(asr_add_cols(h, dhc[cur], U, a->d_in_all + Em + E2, Din, a->dh0, U, B, U, s));
+  ASR_TRY(asr_add_cols(h, dhc[cur], U, a->d_in_all + Em + E2, Din, a->dh0, U, B, U, s));
   if (hipMemcpyAsync(a->dc0, dcs[cur], (size_t)B * U * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
     ASR_FAIL(h, ASR_ERR_HIP, "asr_att_decoder_bwd: copy");
   return ASR_OK;

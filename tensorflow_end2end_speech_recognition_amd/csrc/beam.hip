@@ -63,6 +63,7 @@
 // C = 3387 / W = 100 frame now: log-softmax 8 k, stay candidates 8 k, class select 12 k, compaction 5 k, class ranks +
 // keys 15 k, top-W select 7 k, ranking + trie 5 k.
 #include "common.h"
+#include "beam_keys.h"
 #include <math.h>
 #include <stdlib.h>
 #include <type_traits>
@@ -70,32 +71,6 @@
 namespace {
 
 constexpr int BEAM_MAX = 128;
-constexpr double DNEG = -INFINITY;
-
-__device__ __forceinline__ double lse2d(double a, double b) {
-  const double m = fmax(a, b);
-  if (m == DNEG) return DNEG;
-  return m + log(exp(a - m) + exp(b - m));
-}
-__device__ __forceinline__ double lse3d(double a, double b, double c) {
-  const double m = fmax(fmax(a, b), c);
-  if (m == DNEG) return DNEG;
-  return m + log(exp(a - m) + exp(b - m) + exp(c - m));
-}
-// order-preserving map double -> uint64 (ascending)
-__device__ __forceinline__ unsigned long long okey(double x) {
-  unsigned long long u = (unsigned long long)__double_as_longlong(x);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double unokey(unsigned long long k) {
-  const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-  return __longlong_as_double((long long)u);
-}
-__device__ __forceinline__ unsigned long long hmix(unsigned long long h, int c) {
-  unsigned long long x = h * 0x9E3779B97F4A7C15ull + (unsigned long long)(c + 1);
-  x ^= x >> 32; x *= 0xD6E8FEB86659FD93ull; x ^= x >> 29;
-  return x;
-}
 
 // Inclusive prefix sum over the 64 lanes of a wave on the DPP path (row shifts by 1 / 2 / 4 / 8 with zero fill, then lane 15
 // of a row added to the next row, then lane 31 to the upper half): eight VALU operations instead of six LDS permutes.

@@ -57,6 +57,23 @@ struct asr_handle {
     if (e_ != hipSuccess) ASR_FAIL(h, ASR_ERR_HIP, "%s: %s", what, hipGetErrorString(e_)); \
   } while (0)
 
+// host entry points (a handle `h` in scope): reject an argument with a message / pass a callee's error on
+#define ASR_NEED(cond, ...) do { if (!(cond)) ASR_FAIL(h, ASR_ERR_INVALID_ARG, __VA_ARGS__); } while (0)
+#define ASR_TRY(call) do { const int rc_ = (call); if (rc_ != ASR_OK) return rc_; } while (0)
+
+// getter and reset of one of the handle's three-word launch counters: asr_<field>(h, out3), asr_reset_<field>(h)
+#define ASR_DEFINE_COUNTS3(field)                                              \
+  extern "C" int asr_##field(asr_handle* h, unsigned long long* out3) {        \
+    if (!h || !out3) return ASR_ERR_INVALID_ARG;                               \
+    for (int i = 0; i < 3; ++i) out3[i] = h->field[i];                         \
+    return ASR_OK;                                                             \
+  }                                                                            \
+  extern "C" int asr_reset_##field(asr_handle* h) {                            \
+    if (!h) return ASR_ERR_INVALID_ARG;                                        \
+    for (int i = 0; i < 3; ++i) h->field[i] = 0;                               \
+    return ASR_OK;                                                             \
+  }
+
 typedef uint16_t bf16_t;  // raw bf16 bits
 
 typedef __attribute__((ext_vector_type(8))) short bf16x8_t;  // MFMA A/B fragment (4 VGPRs)

@@ -40,6 +40,7 @@
 // move -- it takes the gathered state back (block 0 -> block 1) and its parent's logits row from the other buffer (out of
 // place: several rows may read one parent row).  Last the back-trace kernel.  T frame launches, T LM steps, T - 1 commits.
 #include "common.h"
+#include "beam_keys.h"
 #include <math.h>
 
 namespace {
@@ -47,32 +48,6 @@ namespace {
 constexpr int LMB_MAX_W = 32;     // asr_lm_beam_reorder's limit
 constexpr int LMB_NT = 512;       // beam.hip's default workgroup: the log-softmax reduces in the same order
 constexpr int LMB_CONT = 512;     // contenders the ranking of step 4 holds (<= LMB_NT: one thread each)
-constexpr double DNEG = -INFINITY;
-
-__device__ __forceinline__ double lse2d(double a, double b) {
-  const double m = fmax(a, b);
-  if (m == DNEG) return DNEG;
-  return m + log(exp(a - m) + exp(b - m));
-}
-__device__ __forceinline__ double lse3d(double a, double b, double c) {
-  const double m = fmax(fmax(a, b), c);
-  if (m == DNEG) return DNEG;
-  return m + log(exp(a - m) + exp(b - m) + exp(c - m));
-}
-// order-preserving map double -> uint64 (ascending), its inverse, and the prefix hash: as beam.hip
-__device__ __forceinline__ unsigned long long okey(double x) {
-  unsigned long long u = (unsigned long long)__double_as_longlong(x);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double unokey(unsigned long long k) {
-  const unsigned long long u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-  return __longlong_as_double((long long)u);
-}
-__device__ __forceinline__ unsigned long long hmix(unsigned long long h, int c) {
-  unsigned long long x = h * 0x9E3779B97F4A7C15ull + (unsigned long long)(c + 1);
-  x ^= x >> 32; x *= 0xD6E8FEB86659FD93ull; x ^= x >> 29;
-  return x;
-}
 
 struct LmEntry {           // one beam entry, as it lies in the workspace between the frames
   double pb, pnb;
@@ -491,8 +466,6 @@ int lmb_launch_frame(asr_handle* h, const float* logits, int t, int T, int B, in
 
 }  // namespace
 
-#define LMB_TRY(call) do { const int rc_ = (call); if (rc_ != ASR_OK) return rc_; } while (0)
-
 extern "C" size_t asr_ctc_beam_lm_workspace_bytes(int T, int B, int C, int beam_width, int V) {
   if (T < 0 || B < 0 || C < 1 || beam_width < 1 || V < 0) return 0;
   return lmb_ws_layout(T, B, C, beam_width, V).total;
@@ -503,7 +476,7 @@ extern "C" int asr_ctc_beam_lm_frame(asr_handle* h, const float* logits, int t, 
                                      int32_t* parent, int32_t* word, double* st_pb, double* st_pnb, float* st_lm,
                                      int32_t* st_nb, void* workspace, size_t workspace_bytes, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  LMB_TRY(lmb_check(h, "asr_ctc_beam_lm_frame", logits, T, B, C, seq_len, blank, beam_width, alpha, beta));
+  ASR_TRY(lmb_check(h, "asr_ctc_beam_lm_frame", logits, T, B, C, seq_len, blank, beam_width, alpha, beta));
   if (!parent || !word || t < 0 || t >= T) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_ctc_beam_lm_frame: bad args t=%d", t);
   if (lm_logits ? V < C : alpha != 0.0)
     ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_ctc_beam_lm_frame: alpha=%g needs LM logits rows of V >= C classes (V=%d)", alpha, V);
@@ -520,7 +493,7 @@ extern "C" int asr_ctc_beam_decode_lm(asr_handle* h, const float* logits, int T,
                                       int32_t* out_labels, int32_t* out_len, double* out_score, float* out_lm_score,
                                       void* workspace, size_t workspace_bytes, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  LMB_TRY(lmb_check(h, "asr_ctc_beam_decode_lm", logits, T, B, C, seq_len, blank, beam_width, alpha, beta));
+  ASR_TRY(lmb_check(h, "asr_ctc_beam_decode_lm", logits, T, B, C, seq_len, blank, beam_width, alpha, beta));
   if (!out_labels || !out_len || !out_score) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_ctc_beam_decode_lm: null output");
   const int W = beam_width, R = B * W;
   int V = 0;
@@ -545,19 +518,19 @@ extern "C" int asr_ctc_beam_decode_lm(asr_handle* h, const float* logits, int T,
   if (lm) {
     step = *lm;
     step.lm_logits = zbuf[0];
-    LMB_TRY(asr_lm_prep(h, &step, s));
-    LMB_TRY(asr_lm_step(h, &step, s));                       // the empty prefix: <SOS> from the zero state
+    ASR_TRY(asr_lm_prep(h, &step, s));
+    ASR_TRY(asr_lm_step(h, &step, s));                       // the empty prefix: <SOS> from the zero state
     h->ctc_beam_lm_counts[1] += 1;
   }
   const size_t blk = lm ? (size_t)lm->L * R * lm->H : 0;
   for (int t = 0; t < T; ++t) {
-    LMB_TRY(lmb_launch_frame(h, logits, t, T, B, C, seq_len, blank, W, alpha, beta, lm ? zbuf[t & 1] : nullptr, V, ws, w,
+    ASR_TRY(lmb_launch_frame(h, logits, t, T, B, C, seq_len, blank, W, alpha, beta, lm ? zbuf[t & 1] : nullptr, V, ws, w,
                              parent, word, nullptr, nullptr, nullptr, nullptr, st));
     if (!lm || t == T - 1) continue;
-    LMB_TRY(asr_lm_beam_reorder(h, parent, word, B, W, lm->L, lm->H, lm->Em_lm, V, lm->c + blk, lm->h + blk, lm->emb, lm->c,
+    ASR_TRY(asr_lm_beam_reorder(h, parent, word, B, W, lm->L, lm->H, lm->Em_lm, V, lm->c + blk, lm->h + blk, lm->emb, lm->c,
                                 lm->h, lm->in, s));
     step.lm_logits = zbuf[(t + 1) & 1];
-    LMB_TRY(asr_lm_step(h, &step, s));
+    ASR_TRY(asr_lm_step(h, &step, s));
     h->ctc_beam_lm_counts[1] += 1;
     hipLaunchKernelGGL(ctc_beam_lm_commit_kernel, dim3(R), dim3(256), 0, st, parent, word, R, W, lm->L, lm->H, V, lm->c, lm->h,
                        lm->c + blk, lm->h + blk, zbuf[t & 1], zbuf[(t + 1) & 1]);
@@ -570,13 +543,4 @@ extern "C" int asr_ctc_beam_decode_lm(asr_handle* h, const float* logits, int T,
   return ASR_OK;
 }
 
-extern "C" int asr_ctc_beam_lm_counts(asr_handle* h, unsigned long long* out3) {
-  if (!h || !out3) return ASR_ERR_INVALID_ARG;
-  for (int i = 0; i < 3; ++i) out3[i] = h->ctc_beam_lm_counts[i];
-  return ASR_OK;
-}
-extern "C" int asr_reset_ctc_beam_lm_counts(asr_handle* h) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  for (int i = 0; i < 3; ++i) h->ctc_beam_lm_counts[i] = 0;
-  return ASR_OK;
-}
+ASR_DEFINE_COUNTS3(ctc_beam_lm_counts)

@@ -1,7 +1,8 @@
-// One-pass joint CTC / attention beam search (Watanabe et al. 2017, Hori et al. 2017): the CTC prefix scores of the
-// candidates of a beam search step, the state they are computed from, and the selection by fused score.  The float64
-// statement is models/attention/decoders/beam_search/ctc_prefix_score.py; the loop that issues these is
-// asr_att_decoder_beam_joint (attention.hip, the beam search loop with this selection in place of asr_att_beam_select).
+// The CTC prefix scorer of the one-pass joint CTC / attention beam search (Watanabe et al. 2017, Hori et al. 2017): the CTC
+// prefix scores of the candidates of a beam search step and the state they are computed from.  The selection by fused
+// score that runs it between its two kernels is asr_att_beam_select_joint / _fused (att_beam.hip).  The float64 statement
+// is models/attention/decoders/beam_search/ctc_prefix_score.py; the loops that issue these are asr_att_decoder_beam_joint
+// and asr_att_decoder_beam_lm (attention.hip).
 //
 // Vocabularies: attention classes C2 = N + 2 (labels, <SOS> = N, <EOS> = N + 1); CTC classes Cc = N + 1 (blank = N by
 // default).  y [T, By, Cc] are log-posteriors (asr_log_softmax_rows of the CTC head's logits); device row r = b*W + w reads
@@ -13,11 +14,7 @@
 namespace {
 
 constexpr int JOINT_MAX_W = 32;
-constexpr int JOINT_CAND = JOINT_MAX_W * (JOINT_MAX_W + 1);
 constexpr int JOINT_CH = 64;                                // frames per chunk: one per lane
-
-// (value, index) order of tf.nn.top_k, as att_beam.hip
-__device__ __forceinline__ bool joint_before(float v, int i, float ov, int oi) { return v > ov || (v == ov && i < oi); }
 
 // log(exp(a) + exp(b)); -inf for two -inf (never NaN: +inf does not occur)
 __device__ __forceinline__ float lae(float a, float b) {
@@ -27,7 +24,7 @@ __device__ __forceinline__ float lae(float a, float b) {
 }
 
 // One wave per row: out = x - (max + log(sum exp(x - max))).  Lane l takes the columns l, l + 64, ... in ascending order
-// into a running maximum / sum, the 64 partials meet in a butterfly (xor 32 .. 1): the order of att_beam_select_kernel.
+// into a running maximum / sum, the 64 partials meet in a butterfly (xor 32 .. 1): the order of row_lse (att_beam.hip).
 __global__ __launch_bounds__(256) void log_softmax_rows_kernel(const float* x, float* out,     // (out may be x)
                                                                long long rows, int cols) {
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -207,147 +204,11 @@ __global__ __launch_bounds__(64) void ctc_prefix_advance_kernel(
   }
 }
 
-// Joint selection, stage 1: one wave per slot row.  The extraction of att_beam_select_kernel (same reduction order, see
-// there): the row's log-softmax, its W best classes other than <EOS> by logit (ties by lower index), and <EOS>.
-// cand [R, W+1] (-1: no candidate) and total [R, W+1] = log_probs + log_softmax(logits)[c].  A finished row has its <EOS>
-// alone (p = 0); at the first step only slot 0 has candidates.
-__global__ __launch_bounds__(64) void att_joint_candidates_kernel(
-    const float* __restrict__ logits, int W, int C2, int eos, int first_step, const float* __restrict__ lp_in,
-    const int32_t* __restrict__ fin_in, int32_t* __restrict__ cand, float* __restrict__ total) {
-  const int row = blockIdx.x, lane = threadIdx.x, w = row % W;
-  int my_c = -1;                                             // lane j <= W keeps candidate j and writes it at the end
-  float my_tot = -INFINITY;
-  const float lp = lp_in[row];
-  if (first_step && w > 0) {                                 // (wave-uniform) every slot holds the same hypothesis
-  } else if (fin_in[row] != 0) {
-    if (lane == W) { my_c = eos; my_tot = lp + 0.f; }
-  } else {
-    const float* x = logits + (size_t)row * C2;
-    float m = -INFINITY;
-    for (int c = lane; c < C2; c += 64) m = fmaxf(m, x[c]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    float sum = 0.f;
-    for (int c = lane; c < C2; c += 64) sum += expf(x[c] - m);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-    const float lse = m + logf(sum);
-    float pv = INFINITY;
-    int pi = -1;
-    for (int j = 0; j < W; ++j) {
-      float bv = -INFINITY;
-      int bi = 0x7fffffff;
-      for (int c = lane; c < C2; c += 64) {
-        const float v = x[c];
-        if (c != eos && joint_before(pv, pi, v, c) && joint_before(v, c, bv, bi)) { bv = v; bi = c; }
-      }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (joint_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-      }
-      if (bi == 0x7fffffff) break;                           // (wave-uniform) fewer than W other classes, or NaNs
-      if (lane == j) { my_c = bi; my_tot = lp + (bv - lse); }
-      pv = bv; pi = bi;
-    }
-    if (lane == W) { my_c = eos; my_tot = lp + (x[eos] - lse); }
-  }
-  if (lane <= W) {
-    const bool ok = my_c >= 0 && my_tot == my_tot;           // (no NaN takes a place)
-    cand[(size_t)row * (W + 1) + lane] = ok ? my_c : -1;
-    total[(size_t)row * (W + 1) + lane] = ok ? my_tot : -INFINITY;
-  }
-}
-
-// Joint selection, stage 3 (stage 2 is ctc_prefix_score_kernel on cand): one workgroup per utterance.  Per candidate
-// ctc = psi, or the slot's carried ctc_score if it had finished; a candidate whose ctc is -inf is dropped;
-// joint = (1 - lambda) * total + lambda * ctc; score = joint / (pow(5 + len, a) / pow(6, a)) (a == 1: joint, the quirk of
-// normalize_score).  The W best by (score descending, flat index w*C2 + c ascending) give word / parent / score and the
-// next state: log_probs = total (attention alone), ctc_score = ctc, finished, lengths as att_beam_select_kernel, last =
-// the word unless it is <EOS> (then the parent's).  All *_in state is read before the first barrier: out may be in.
-__global__ __launch_bounds__(256) void att_joint_rank_kernel(
-    const int32_t* __restrict__ cand, const float* __restrict__ total, const float* __restrict__ psi, int W, int C2, int eos,
-    float lpw, float lam, const int32_t* fin_in, const int32_t* len_in, const int32_t* last_in, const float* ctc_in,
-    int32_t* __restrict__ word, int32_t* __restrict__ parent, float* __restrict__ score, float* lp_out, int32_t* fin_out,
-    int32_t* len_out, int32_t* last_out, float* ctc_out, int32_t* __restrict__ unfinished) {
-  __shared__ int s_fin[JOINT_MAX_W], s_len[JOINT_MAX_W], s_last[JOINT_MAX_W];
-  __shared__ float s_ctc[JOINT_MAX_W];
-  __shared__ float c_score[JOINT_CAND], c_total[JOINT_CAND], c_ctc[JOINT_CAND];
-  __shared__ int c_flat[JOINT_CAND];
-  __shared__ float r_score[JOINT_MAX_W], r_total[JOINT_MAX_W], r_ctc[JOINT_MAX_W];
-  __shared__ int r_flat[JOINT_MAX_W];
-  __shared__ int s_live;
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const int ncand = W * (W + 1);
-  if (tid < W) {
-    s_fin[tid] = fin_in[b * W + tid] != 0;
-    s_len[tid] = len_in[b * W + tid];
-    s_last[tid] = last_in[b * W + tid];
-    s_ctc[tid] = ctc_in[b * W + tid];
-    r_score[tid] = -INFINITY; r_total[tid] = -INFINITY; r_ctc[tid] = -INFINITY; r_flat[tid] = -1;
-  }
-  if (tid == 0) s_live = 0;
-  __syncthreads();
-  const float pen6 = powf(6.f, lpw);
-  for (int i = tid; i < ncand; i += 256) {
-    const int w = i / (W + 1);
-    const size_t o = (size_t)b * ncand + i;
-    const int c = cand[o];
-    int flat = -1;
-    float sc = -INFINITY, tot = -INFINITY, ctc = -INFINITY;
-    if (c >= 0 && c < C2) {
-      tot = total[o];
-      ctc = s_fin[w] ? s_ctc[w] : psi[o];
-      const int len = s_len[w] + ((c != eos && !s_fin[w]) ? 1 : 0);
-      const float joint = (1.f - lam) * tot + lam * ctc;
-      sc = lpw == 1.f ? joint : joint / (powf(5.f + (float)len, lpw) / pen6);
-      if (ctc != -INFINITY && sc == sc) flat = w * C2 + c;   // (sc == sc: no NaN takes a place)
-    }
-    c_score[i] = sc; c_total[i] = tot; c_ctc[i] = ctc; c_flat[i] = flat;
-  }
-  __syncthreads();
-  // rank of every survivor among the survivors; flat indices are distinct, so are the ranks
-  for (int i = tid; i < ncand; i += 256) {
-    const int fi = c_flat[i];
-    if (fi < 0) continue;
-    const float si = c_score[i];
-    int rank = 0;
-    for (int j = 0; j < ncand; ++j) {
-      const int fj = c_flat[j];
-      if (fj >= 0 && joint_before(c_score[j], fj, si, fi)) ++rank;
-    }
-    if (rank < W) { r_score[rank] = si; r_total[rank] = c_total[i]; r_ctc[rank] = c_ctc[i]; r_flat[rank] = fi; }
-  }
-  __syncthreads();
-  if (tid < W) {
-    // (a place nothing reached -- fewer than W candidates with a finite CTC score -- repeats the slot as a finished <EOS>)
-    const bool hit = r_flat[tid] >= 0;
-    const int flat = hit ? r_flat[tid] : tid * C2 + eos;
-    const int wd = flat % C2, pa = flat / C2;
-    const int fin = (s_fin[pa] || wd == eos) ? 1 : 0;
-    const size_t o = (size_t)b * W + tid;
-    word[o] = wd;
-    parent[o] = pa;
-    score[o] = r_score[tid];
-    lp_out[o] = r_total[tid];
-    ctc_out[o] = hit ? r_ctc[tid] : s_ctc[pa];
-    fin_out[o] = fin;
-    len_out[o] = s_len[pa] + ((wd != eos && !fin) ? 1 : 0);
-    last_out[o] = wd == eos ? s_last[pa] : wd;
-    if (!fin) atomicAdd(&s_live, 1);
-  }
-  __syncthreads();
-  if (tid == 0 && unfinished && s_live) atomicAdd(unfinished, s_live);
-}
-
 }  // namespace
-
-#define JOINT_NEED(cond, msg) do { if (!(cond)) ASR_FAIL(h, ASR_ERR_INVALID_ARG, msg); } while (0)
 
 extern "C" int asr_log_softmax_rows(asr_handle* h, const float* x, float* y, size_t rows, int cols, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  JOINT_NEED(x && y && rows >= 1 && cols >= 1 && (rows + 3) / 4 <= 0x7fffffffULL, "asr_log_softmax_rows: bad arguments");
+  ASR_NEED(x && y && rows >= 1 && cols >= 1 && (rows + 3) / 4 <= 0x7fffffffULL, "asr_log_softmax_rows: bad arguments");
   hipLaunchKernelGGL(log_softmax_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)s, x, y,
                      (long long)rows, cols);
   ASR_CHECK_LAUNCH(h, "asr_log_softmax_rows");
@@ -361,8 +222,8 @@ static int joint_shape_ok(int B, int W, int T, int By, int Cc, int blank, int N)
 extern "C" int asr_ctc_prefix_init(asr_handle* h, const float* y, const int32_t* seq_len, int B, int W, int T, int By, int Cc,
                                    int blank, float* r, int32_t* last, float* ctc_score, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  JOINT_NEED(y && seq_len && r, "asr_ctc_prefix_init: null");
-  JOINT_NEED(joint_shape_ok(B, W, T, By, Cc, blank, 1), "asr_ctc_prefix_init: bad shape");
+  ASR_NEED(y && seq_len && r, "asr_ctc_prefix_init: null");
+  ASR_NEED(joint_shape_ok(B, W, T, By, Cc, blank, 1), "asr_ctc_prefix_init: bad shape");
   const int R = B * W;
   hipLaunchKernelGGL(ctc_prefix_init_kernel, dim3((R + 63) / 64), dim3(64), 0, (hipStream_t)s, y, seq_len, R, W, T, By, Cc,
                      blank, r, last, ctc_score);
@@ -374,9 +235,9 @@ extern "C" int asr_ctc_prefix_score(asr_handle* h, const float* y, const int32_t
                                     int blank, int n_labels, const float* r, const int32_t* last, const int32_t* finished,
                                     const int32_t* cand, int K, float* psi, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  JOINT_NEED(y && seq_len && r && last && cand && psi, "asr_ctc_prefix_score: null");
-  JOINT_NEED(joint_shape_ok(B, W, T, By, Cc, blank, n_labels), "asr_ctc_prefix_score: bad shape");
-  JOINT_NEED(K >= 1 && K <= 64, "asr_ctc_prefix_score: 1 .. 64 candidates per row");
+  ASR_NEED(y && seq_len && r && last && cand && psi, "asr_ctc_prefix_score: null");
+  ASR_NEED(joint_shape_ok(B, W, T, By, Cc, blank, n_labels), "asr_ctc_prefix_score: bad shape");
+  ASR_NEED(K >= 1 && K <= 64, "asr_ctc_prefix_score: 1 .. 64 candidates per row");
   h->att_joint_counts[0] += 1;
   hipLaunchKernelGGL(ctc_prefix_score_kernel, dim3(B * W), dim3(64), 0, (hipStream_t)s, y, seq_len, r, last, finished, cand, W,
                      K, T, By, Cc, blank, n_labels, psi);
@@ -388,9 +249,9 @@ extern "C" int asr_ctc_prefix_advance(asr_handle* h, const float* y, const int32
                                       int Cc, int blank, int n_labels, const float* r_src, const int32_t* last_src,
                                       const int32_t* parent, const int32_t* word, float* r_dst, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  JOINT_NEED(y && seq_len && r_src && last_src && parent && word && r_dst, "asr_ctc_prefix_advance: null");
-  JOINT_NEED(joint_shape_ok(B, W, T, By, Cc, blank, n_labels), "asr_ctc_prefix_advance: bad shape");
-  JOINT_NEED(r_src != r_dst, "asr_ctc_prefix_advance: the extension is out of place");
+  ASR_NEED(y && seq_len && r_src && last_src && parent && word && r_dst, "asr_ctc_prefix_advance: null");
+  ASR_NEED(joint_shape_ok(B, W, T, By, Cc, blank, n_labels), "asr_ctc_prefix_advance: bad shape");
+  ASR_NEED(r_src != r_dst, "asr_ctc_prefix_advance: the extension is out of place");
   h->att_joint_counts[1] += 1;
   hipLaunchKernelGGL(ctc_prefix_advance_kernel, dim3(B * W), dim3(64), 0, (hipStream_t)s, y, seq_len, r_src, last_src, parent,
                      word, W, T, By, Cc, blank, n_labels, r_dst);
@@ -398,43 +259,4 @@ extern "C" int asr_ctc_prefix_advance(asr_handle* h, const float* y, const int32
   return ASR_OK;
 }
 
-extern "C" int asr_att_beam_select_joint(asr_handle* h, const float* logits, int B, int W, int n_labels, float lpw,
-                                         float ctc_weight, int first_step, const float* y, const int32_t* seq_len, int T, int By,
-                                         int Cc, int blank, const float* r, const float* lp_in, const int32_t* fin_in,
-                                         const int32_t* len_in, const int32_t* last_in, const float* ctc_in, int32_t* cand,
-                                         float* cand_total, float* psi, int32_t* word, int32_t* parent, float* score,
-                                         float* lp_out, int32_t* fin_out, int32_t* len_out, int32_t* last_out, float* ctc_out,
-                                         int32_t* unfinished, asr_stream s) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  JOINT_NEED(logits && y && seq_len && r && lp_in && fin_in && len_in && last_in && ctc_in && cand && cand_total && psi &&
-                 word && parent && score && lp_out && fin_out && len_out && last_out && ctc_out,
-             "asr_att_beam_select_joint: null");
-  JOINT_NEED(joint_shape_ok(B, W, T, By, Cc, blank, n_labels), "asr_att_beam_select_joint: bad shape");
-  JOINT_NEED(W <= n_labels + 1, "asr_att_beam_select_joint: beam width exceeds the labels and <EOS> step 0 selects among");
-  JOINT_NEED(ctc_weight > 0.f && ctc_weight <= 1.f, "asr_att_beam_select_joint: ctc_weight must be in (0, 1]");
-  const int C2 = n_labels + 2, eos = n_labels + 1;
-  JOINT_NEED((long long)W * C2 <= 0x7fffffffLL, "asr_att_beam_select_joint: flat index overflow");
-  hipStream_t st = (hipStream_t)s;
-  h->att_joint_counts[2] += 1;
-  hipLaunchKernelGGL(att_joint_candidates_kernel, dim3(B * W), dim3(64), 0, st, logits, W, C2, eos, first_step, lp_in, fin_in,
-                     cand, cand_total);
-  ASR_CHECK_LAUNCH(h, "asr_att_beam_select_joint(candidates)");
-  const int rc = asr_ctc_prefix_score(h, y, seq_len, B, W, T, By, Cc, blank, n_labels, r, last_in, fin_in, cand, W + 1, psi, s);
-  if (rc != ASR_OK) return rc;
-  hipLaunchKernelGGL(att_joint_rank_kernel, dim3(B), dim3(256), 0, st, cand, cand_total, psi, W, C2, eos, lpw, ctc_weight,
-                     fin_in, len_in, last_in, ctc_in, word, parent, score, lp_out, fin_out, len_out, last_out, ctc_out,
-                     unfinished);
-  ASR_CHECK_LAUNCH(h, "asr_att_beam_select_joint(rank)");
-  return ASR_OK;
-}
-
-extern "C" int asr_att_joint_counts(asr_handle* h, unsigned long long* out3) {
-  if (!h || !out3) return ASR_ERR_INVALID_ARG;
-  for (int i = 0; i < 3; ++i) out3[i] = h->att_joint_counts[i];
-  return ASR_OK;
-}
-extern "C" int asr_reset_att_joint_counts(asr_handle* h) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  for (int i = 0; i < 3; ++i) h->att_joint_counts[i] = 0;
-  return ASR_OK;
-}
+ASR_DEFINE_COUNTS3(att_joint_counts)

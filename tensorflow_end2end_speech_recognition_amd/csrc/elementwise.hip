@@ -478,8 +478,6 @@ __global__ void scale_kernel(float* __restrict__ x, size_t n, float sc) {
 
 }  // namespace
 
-#define ASR_NEED(cond, ...) do { if (!(cond)) ASR_FAIL(h, ASR_ERR_INVALID_ARG, __VA_ARGS__); } while (0)
-
 template <typename T>
 __global__ __launch_bounds__(256) void transpose2d_kernel(const T* __restrict__ in, int rows, int cols, int ld_in,
                                                           T* __restrict__ out, int ld_out) {

@@ -473,8 +473,6 @@ __global__ __launch_bounds__(GP_THREADS, 1) void gru_bwd_persistent_kernel(
 
 }  // namespace
 
-#define GRU_NEED(cond, ...) do { if (!(cond)) ASR_FAIL(h, ASR_ERR_INVALID_ARG, __VA_ARGS__); } while (0)
-
 // The persistent kernels apply when the LDS images fit one CU (H <= 512 forward, H <= 480 backward) and the packed
 // weights fit the handle's scratch; ASR_GRU_PERSISTENT=0 keeps the launch-per-step form (A/B, and the tests run both).
 static int g_gru_persistent = -1;
@@ -497,7 +495,7 @@ extern "C" int asr_gru_fwd(asr_handle* h, int T, int B, int H, int ndir, const f
                            const float* wgh, const float* wch, const int32_t* seq_len, int tmax, float* r, float* u,
                            float* c, float* rh, float* hout, float* hstate2, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  GRU_NEED(xg && xc && wgh && wch && seq_len && r && u && c && rh && hout && hstate2 && T >= 0 && B > 0 && B % 16 == 0 &&
+  ASR_NEED(xg && xc && wgh && wch && seq_len && r && u && c && rh && hout && hstate2 && T >= 0 && B > 0 && B % 16 == 0 &&
                H > 0 && H % 16 == 0 && (ndir == 1 || ndir == 2) && tmax >= 0 && tmax <= T,
            "asr_gru_fwd: bad args (B=%d and H=%d must be multiples of 16, ndir=%d)", B, H, ndir);
   const size_t lds = (size_t)16 * (H + 1) * sizeof(float);
@@ -552,7 +550,7 @@ extern "C" int asr_gru_bwd(asr_handle* h, int T, int B, int H, int ndir, const f
                            const float* wchT, const int32_t* seq_len, int tmax, float* dgate, float* dcand,
                            float* work2, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  GRU_NEED(dout && hout && r && u && c && wghT && wchT && seq_len && dgate && dcand && work2 && T >= 0 && B > 0 &&
+  ASR_NEED(dout && hout && r && u && c && wghT && wchT && seq_len && dgate && dcand && work2 && T >= 0 && B > 0 &&
                B % 16 == 0 && H > 0 && H % 16 == 0 && (ndir == 1 || ndir == 2) && tmax >= 0 && tmax <= T,
            "asr_gru_bwd: bad args (B=%d and H=%d must be multiples of 16, ndir=%d)", B, H, ndir);
   const size_t lds = (size_t)16 * (2 * H + 1) * sizeof(float);

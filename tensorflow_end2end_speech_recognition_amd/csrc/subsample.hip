@@ -7,8 +7,6 @@
 
 namespace {
 
-#define ASR_NEED(cond, ...) do { if (!(cond)) ASR_FAIL(h, ASR_ERR_INVALID_ARG, __VA_ARGS__); } while (0)
-
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
 
 inline int grid_for(size_t n) {

@@ -643,12 +643,10 @@ inline int gridv(size_t n) {
 
 }  // namespace
 
-#define VGG_NEED(cond, ...) do { if (!(cond)) ASR_FAIL(h, ASR_ERR_INVALID_ARG, __VA_ARGS__); } while (0)
-
 extern "C" int asr_im2col3x3(asr_handle* h, int dtype, const void* in, int N, int H, int W, int Cin, int ldp,
                              void* patches, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  VGG_NEED(asr_dtype_ok(dtype) && in && patches && N >= 0 && H > 0 && W > 0 && Cin > 0 && ldp >= 9 * Cin,
+  ASR_NEED(asr_dtype_ok(dtype) && in && patches && N >= 0 && H > 0 && W > 0 && Cin > 0 && ldp >= 9 * Cin,
            "asr_im2col3x3: bad args");
   const size_t total = (size_t)N * H * W * 9 * Cin;
   if (!total) return ASR_OK;
@@ -660,7 +658,7 @@ extern "C" int asr_im2col3x3(asr_handle* h, int dtype, const void* in, int N, in
 extern "C" int asr_col2im3x3(asr_handle* h, const float* dpatches, int N, int H, int W, int Cin, int ldp,
                              float* din, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  VGG_NEED(dpatches && din && N >= 0 && H > 0 && W > 0 && Cin > 0 && ldp >= 9 * Cin, "asr_col2im3x3: bad args");
+  ASR_NEED(dpatches && din && N >= 0 && H > 0 && W > 0 && Cin > 0 && ldp >= 9 * Cin, "asr_col2im3x3: bad args");
   const size_t total = (size_t)N * H * W * Cin;
   if (!total) return ASR_OK;
   hipLaunchKernelGGL(col2im3x3_kernel, dim3(gridv(total)), dim3(256), 0, (hipStream_t)s, dpatches, N, H, W, Cin, ldp, din);
@@ -670,7 +668,7 @@ extern "C" int asr_col2im3x3(asr_handle* h, const float* dpatches, int N, int H,
 extern "C" int asr_maxpool2x2_fwd(asr_handle* h, int dtype, const void* in, int N, int H, int W, int C, void* out,
                                   uint8_t* argmax, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  VGG_NEED(asr_dtype_ok(dtype) && in && out && argmax && N >= 0 && H > 0 && W > 0 && C > 0, "asr_maxpool2x2_fwd: bad args");
+  ASR_NEED(asr_dtype_ok(dtype) && in && out && argmax && N >= 0 && H > 0 && W > 0 && C > 0, "asr_maxpool2x2_fwd: bad args");
   const size_t total = (size_t)N * ((H + 1) / 2) * ((W + 1) / 2) * C;
   if (!total) return ASR_OK;
   if (C % 4 == 0 && (((uintptr_t)in | (uintptr_t)out | (uintptr_t)argmax) % 16) == 0) {
@@ -687,7 +685,7 @@ extern "C" int asr_maxpool2x2_fwd(asr_handle* h, int dtype, const void* in, int 
 extern "C" int asr_maxpool2x2_fwd_drop(asr_handle* h, int dtype, const void* in, int N, int H, int W, int C, void* out,
                                        uint8_t* argmax, float keep_prob, uint64_t seed, uint64_t offset, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  VGG_NEED(asr_dtype_ok(dtype) && in && out && argmax && N >= 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 &&
+  ASR_NEED(asr_dtype_ok(dtype) && in && out && argmax && N >= 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 &&
                keep_prob > 0.f && keep_prob <= 1.f && (((uintptr_t)in | (uintptr_t)out | (uintptr_t)argmax) % 16) == 0,
            "asr_maxpool2x2_fwd_drop: bad args (C %% 4 == 0, 16-byte aligned arrays)");
   const size_t total = (size_t)N * ((H + 1) / 2) * ((W + 1) / 2) * C;
@@ -704,7 +702,7 @@ extern "C" int asr_maxpool2x2_fwd_drop(asr_handle* h, int dtype, const void* in,
 extern "C" int asr_relu_bwd_scaled(asr_handle* h, int dtype, const float* dout, const void* out, size_t n, float keep,
                                    void* dpre, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  VGG_NEED(asr_dtype_ok(dtype) && dout && out && dpre && keep > 0.f && keep <= 1.f, "asr_relu_bwd_scaled: bad args");
+  ASR_NEED(asr_dtype_ok(dtype) && dout && out && dpre && keep > 0.f && keep <= 1.f, "asr_relu_bwd_scaled: bad args");
   if (!n) return ASR_OK;
   if (dtype == ASR_F32) hipLaunchKernelGGL(relu_bwd_scaled_kernel<float>, dim3(gridv(n)), dim3(256), 0, (hipStream_t)s, dout, (const float*)out, keep, n, (float*)dpre);
   else hipLaunchKernelGGL(relu_bwd_scaled_kernel<bf16_t>, dim3(gridv(n)), dim3(256), 0, (hipStream_t)s, dout, (const bf16_t*)out, keep, n, (bf16_t*)dpre);
@@ -715,7 +713,7 @@ extern "C" int asr_relu_bwd_scaled(asr_handle* h, int dtype, const float* dout, 
 extern "C" int asr_maxpool2x2_bwd(asr_handle* h, const float* dout, const uint8_t* argmax, int N, int H, int W,
                                   int C, float* din, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  VGG_NEED(dout && argmax && din && N >= 0 && H > 0 && W > 0 && C > 0, "asr_maxpool2x2_bwd: bad args");
+  ASR_NEED(dout && argmax && din && N >= 0 && H > 0 && W > 0 && C > 0, "asr_maxpool2x2_bwd: bad args");
   const size_t total = (size_t)N * H * W * C;
   if (!total) return ASR_OK;
   hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(gridv(total)), dim3(256), 0, (hipStream_t)s, dout, argmax, N, H, W, C, din);
@@ -733,14 +731,14 @@ extern "C" int asr_conv3x3_smallc_fwd_drop(asr_handle* h, const void* x, int N, 
                                           const float* bias, int Cout, float keep_prob, uint64_t seed, uint64_t offset,
                                           void* out, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  VGG_NEED(keep_prob > 0.f && keep_prob <= 1.f, "asr_conv3x3_smallc_fwd_drop: keep_prob");
+  ASR_NEED(keep_prob > 0.f && keep_prob <= 1.f, "asr_conv3x3_smallc_fwd_drop: keep_prob");
   return smallc_fwd_launch(h, x, N, H, W, Cin, w2d, bias, Cout, 1, out, keep_prob, seed, offset, 1, s);
 }
 static int smallc_fwd_launch(asr_handle* h, const void* x, int N, int H, int W, int Cin, const void* w2d, const float* bias,
                              int Cout, int relu, void* out, float keep, uint64_t seed, uint64_t offset, int use_drop,
                              asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  VGG_NEED(x && w2d && out && N >= 0 && H > 0 && W > 0 && Cin > 0 && Cin <= 3 && Cout == SC_CO &&
+  ASR_NEED(x && w2d && out && N >= 0 && H > 0 && W > 0 && Cin > 0 && Cin <= 3 && Cout == SC_CO &&
                ((uintptr_t)out) % 16 == 0, "asr_conv3x3_smallc_fwd: needs Cin <= 3, Cout == 64");
   const size_t npix = (size_t)N * H * W;
   if (!npix) return ASR_OK;
@@ -775,7 +773,7 @@ extern "C" int asr_conv3x3_smallc_bwd_weight_bias(asr_handle* h, const void* x, 
 static int smallc_bwd_weight_impl(asr_handle* h, const void* x, const void* dpre, int N, int H, int W, int Cin, int Cout,
                                   float* dw, float* dbias, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  VGG_NEED(x && dpre && dw && N >= 0 && H > 0 && W > 0 && Cin > 0 && Cin <= 3 && Cout == SC_CO &&
+  ASR_NEED(x && dpre && dw && N >= 0 && H > 0 && W > 0 && Cin > 0 && Cin <= 3 && Cout == SC_CO &&
                ((uintptr_t)dpre) % 16 == 0, "asr_conv3x3_smallc_bwd_weight: needs Cin <= 3, Cout == 64");
   const size_t npix = (size_t)N * H * W;
   int nblk = (int)((npix + 2047) / 2048);
@@ -821,7 +819,7 @@ extern "C" int asr_maxpool2x2_relu_bwd(asr_handle* h, int dtype, const float* do
                                       const void* act, int N, int H, int W, int C, void* dpre, float keep_prob,
                                       uint64_t seed, uint64_t offset, int use_drop, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  VGG_NEED(asr_dtype_ok(dtype) && dout && argmax && act && dpre && N >= 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 &&
+  ASR_NEED(asr_dtype_ok(dtype) && dout && argmax && act && dpre && N >= 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0 &&
                (!use_drop || (keep_prob > 0.f && keep_prob <= 1.f)) && use_drop >= 0 && use_drop <= 2 &&
                (((uintptr_t)dout | (uintptr_t)argmax | (uintptr_t)act | (uintptr_t)dpre) % 16) == 0,
            "asr_maxpool2x2_relu_bwd: bad args (C %% 4 == 0, 16-byte aligned arrays)");
@@ -839,7 +837,7 @@ extern "C" int asr_maxpool2x2_relu_bwd(asr_handle* h, int dtype, const float* do
 extern "C" int asr_relu_bwd(asr_handle* h, int dtype, const float* dout, const void* out, const float* mask,
                             size_t n, void* dpre, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  VGG_NEED(asr_dtype_ok(dtype) && dout && out && dpre, "asr_relu_bwd: bad args");
+  ASR_NEED(asr_dtype_ok(dtype) && dout && out && dpre, "asr_relu_bwd: bad args");
   if (!n) return ASR_OK;
   if (dtype == ASR_F32) hipLaunchKernelGGL(relu_bwd_kernel<float>, dim3(gridv(n)), dim3(256), 0, (hipStream_t)s, dout, (const float*)out, mask, n, (float*)dpre);
   else hipLaunchKernelGGL(relu_bwd_kernel<bf16_t>, dim3(gridv(n)), dim3(256), 0, (hipStream_t)s, dout, (const bf16_t*)out, mask, n, (bf16_t*)dpre);

@@ -16,8 +16,9 @@ Candidates of a selection step: per unfinished slot the W classes other than <EO
 by lower index) plus <EOS> -- the set att_beam_select_kernel extracts.  With attention-only scores that pruning loses
 nothing; with fused scores it IS the preselection (the literature's "CTC pre-beam"), fixed here at W.
 
-This is what csrc/ctc_prefix.hip computes in fp32 (ops.ctc_prefix_score / ctc_prefix_advance / att_beam_select_joint /
-att_decoder_beam_joint) and the oracle of its tests."""
+This is what csrc/ctc_prefix.hip (the prefix scorer: ops.ctc_prefix_score / ctc_prefix_advance) and csrc/att_beam.hip (the
+selection: ops.att_beam_select_joint; the loop ops.att_decoder_beam_joint issues both) compute in fp32, and the oracle of
+their tests."""
 import collections
 
 import numpy as np

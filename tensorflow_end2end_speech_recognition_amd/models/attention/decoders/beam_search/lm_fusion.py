@@ -32,8 +32,8 @@ chosen word is the next step's input).
 Out of scope: an insertion bonus (`beta`), a word-level LM for character models, n-best rescoring, and an LM in the CTC
 prefix beam search (csrc/beam.hip).
 
-This is what csrc/lm_fusion.hip computes in fp32 (ops.lm_step / att_beam_select_fused / lm_beam_reorder /
-att_decoder_beam_lm) and the oracle of its tests."""
+This is what csrc/lm_fusion.hip (the language model: ops.lm_step / lm_beam_reorder) and csrc/att_beam.hip (the selection:
+ops.att_beam_select_fused; the loop ops.att_decoder_beam_lm issues both) compute in fp32, and the oracle of their tests."""
 import collections
 import math
 

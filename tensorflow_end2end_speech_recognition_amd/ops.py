@@ -2052,23 +2052,32 @@ def att_decoder_beam(a, W_av, W_out, b_out, embedding, eos, beam_width, length_p
     return _beam_loop_done(out, issued, host, scratch)
 
 
+def _counts3(name, keys, device):
+    """A handle's three launch counters asr_<name>, summed over the handles of `device`, under `keys`."""
+    tot = [0] * 3
+    for h in _device_handles(device):
+        out = (C.c_ulonglong * 3)()
+        h.check(getattr(h.lib, 'asr_' + name)(h.h, out), 'asr_' + name)
+        tot = [x + int(y) for x, y in zip(tot, out)]
+    return dict(zip(keys, tot))
+
+
+def _reset_counts3(name, device):
+    for h in _device_handles(device):
+        h.check(getattr(h.lib, 'asr_reset_' + name)(h.h), 'asr_reset_' + name)
+
+
 _ATT_BEAM_KEYS = ('select', 'reorder', 'backtrace')
 
 
 def att_beam_counts(device=0):
     """Launches of the beam search kernels on `device` since the last reset, summed over its handles
     (asr_att_beam_counts).  Host counters: no device work, no synchronisation."""
-    tot = [0] * 3
-    for h in _device_handles(device):
-        out = (C.c_ulonglong * 3)()
-        h.check(h.lib.asr_att_beam_counts(h.h, out), 'asr_att_beam_counts')
-        tot = [x + int(y) for x, y in zip(tot, out)]
-    return dict(zip(_ATT_BEAM_KEYS, tot))
+    return _counts3('att_beam_counts', _ATT_BEAM_KEYS, device)
 
 
 def reset_att_beam_counts(device=0):
-    for h in _device_handles(device):
-        h.check(h.lib.asr_reset_att_beam_counts(h.h), 'asr_reset_att_beam_counts')
+    _reset_counts3('att_beam_counts', device)
 
 
 # ---------------------------------------------------------------- joint CTC / attention beam search (an extension)
@@ -2175,6 +2184,40 @@ def ctc_prefix_advance(y, seq_len, r, last, parent, word, n_labels, blank=None):
     return out
 
 
+def _select_streams(what, h, logits, lm_logits, N, W, lam, mu, length_penalty_weight, first_step, state, ctc, unfinished):
+    """What att_beam_select_joint and att_beam_select_fused share behind their own argument checks: the checks of the [R]
+    state arrays `state` ((tensor, dtype, name) of log_probs, finished, lengths and, per stream, ctc_score / lm_score), the
+    outputs and the native call -- asr_att_beam_select_joint without lm_logits, asr_att_beam_select_fused with.  ctc: None
+    or (y, seq_len, r, last, T, By, Cc, blank).  Returns word, parent, score, log_probs, finished, lengths, lm_score, last,
+    ctc_score (None for a stream that is off)."""
+    R, dev = int(logits.shape[0]), logits.device
+    B = R // W
+    _beam_width(W, N + 1)
+    for t, dt, n in state:
+        _chk(t, dt, n)
+        if tuple(t.shape) != (R,):
+            raise ValueError('%s: %s must be [%d]' % (what, n, R))
+    st = {n: _p(t) for t, _, n in state}
+    y, seq_len, r, last, T, By, Cc, blank = ctc if ctc is not None else (None, None, None, None, 0, 0, 0, 0)
+    word, parent, score = _i32((B, W), dev), _i32((B, W), dev), _f32((B, W), dev)
+    lp, fin, ln = _f32((R,), dev), _i32((R,), dev), _i32((R,), dev)
+    cand, tot = _i32((R, W + 1), dev), _f32((R, W + 1), dev)
+    psi, lst, cs = (_f32((R, W + 1), dev), _i32((R,), dev), _f32((R,), dev)) if ctc is not None else (None, None, None)
+    clm, ls = (_f32((R, W + 1), dev), _f32((R,), dev)) if lm_logits is not None else (None, None)
+    a = 0.0 if length_penalty_weight is None else float(length_penalty_weight)
+    state_in = (int(bool(first_step)), _p(y), _p(seq_len), T, By, Cc, blank, _p(r), st['log_probs'], st['finished'],
+                st['lengths'], _p(last), st.get('ctc_score'))
+    out = (_p(word), _p(parent), _p(score), _p(lp), _p(fin), _p(ln), _p(lst), _p(cs))
+    if lm_logits is None:
+        rc = h.lib.asr_att_beam_select_joint(h.h, _p(logits), B, W, N, a, lam, *state_in, _p(cand), _p(tot), _p(psi), *out,
+                                             _p(unfinished), _s())
+    else:
+        rc = h.lib.asr_att_beam_select_fused(h.h, _p(logits), _p(lm_logits), B, W, N, a, lam, mu, *state_in, st['lm_score'],
+                                             _p(cand), _p(tot), _p(clm), _p(psi), *out, _p(ls), _p(unfinished), _s())
+    h.check(rc, 'asr_' + what)
+    return word, parent, score, lp, fin, ln, ls, lst, cs
+
+
 def att_beam_select_joint(logits, y, seq_len, r, last, ctc_score, n_labels, ctc_weight, length_penalty_weight, first_step,
                           log_probs, finished, lengths, unfinished=None, blank=None):
     """One joint CTC / attention selection per utterance (asr_att_beam_select_joint): att_beam_select on
@@ -2190,26 +2233,14 @@ def att_beam_select_joint(logits, y, seq_len, r, last, ctc_score, n_labels, ctc_
         raise ValueError('att_beam_select_joint: %d attention classes for %d labels' % (C2, N))
     lam = _check_ctc_weight(ctc_weight)
     B, W, T, By, Cc, blank = _joint_shapes('att_beam_select_joint', y, seq_len, R, N, blank)
-    _beam_width(W, N + 1)
     _chk_state('att_beam_select_joint', r, last, T)
-    for t, dt, n in ((log_probs, torch.float32, 'log_probs'), (ctc_score, torch.float32, 'ctc_score'),
-                     (finished, torch.int32, 'finished'), (lengths, torch.int32, 'lengths')):
-        _chk(t, dt, n)
-        if tuple(t.shape) != (R,):
-            raise ValueError('att_beam_select_joint: %s must be [%d]' % (n, R))
     if r.shape[0] != R:
         raise ValueError('att_beam_select_joint: r must have %d rows' % R)
-    dev = logits.device
-    word, parent, score = _i32((B, W), dev), _i32((B, W), dev), _f32((B, W), dev)
-    lp, fin, ln, lst, cs = _f32((R,), dev), _i32((R,), dev), _i32((R,), dev), _i32((R,), dev), _f32((R,), dev)
-    cand, tot, psi = _i32((R, W + 1), dev), _f32((R, W + 1), dev), _f32((R, W + 1), dev)
-    a = 0.0 if length_penalty_weight is None else float(length_penalty_weight)
-    h.check(h.lib.asr_att_beam_select_joint(h.h, _p(logits), B, W, N, a, lam, int(bool(first_step)), _p(y), _p(seq_len), T, By,
-                                            Cc, blank, _p(r), _p(log_probs), _p(finished), _p(lengths), _p(last),
-                                            _p(ctc_score), _p(cand), _p(tot), _p(psi), _p(word), _p(parent), _p(score),
-                                            _p(lp), _p(fin), _p(ln), _p(lst), _p(cs), _p(unfinished), _s()),
-            'asr_att_beam_select_joint')
-    return word, parent, score, lp, fin, ln, lst, cs
+    state = [(log_probs, torch.float32, 'log_probs'), (ctc_score, torch.float32, 'ctc_score'),
+             (finished, torch.int32, 'finished'), (lengths, torch.int32, 'lengths')]
+    out = _select_streams('att_beam_select_joint', h, logits, None, N, W, lam, 0.0, length_penalty_weight, first_step, state,
+                          (y, seq_len, r, last, T, By, Cc, blank), unfinished)
+    return out[:6] + out[7:]
 
 
 class _AttBeamCtc(C.Structure):
@@ -2217,6 +2248,24 @@ class _AttBeamCtc(C.Structure):
     _fields_ = [('y', C.c_void_p), ('seq_len', C.c_void_p), ('By', C.c_int), ('Cc', C.c_int), ('blank', C.c_int),
                 ('n_labels', C.c_int), ('ctc_weight', C.c_float), ('r', C.c_void_p), ('last', C.c_void_p),
                 ('ctc_score', C.c_void_p), ('cand', C.c_void_p), ('cand_total', C.c_void_p), ('psi', C.c_void_p)]
+
+
+def _beam_ctc(what, a, y, seq_len, W, N, lam, blank):
+    """The CTC part of att_decoder_beam_joint / att_decoder_beam_lm: y / seq_len checked against the loop's R rows of
+    a['T'] frames.  Returns the loop's extra scratch (prefix state r / last in two blocks, candidates, their totals and
+    psi; y and seq_len kept alive), its ctc_score [B,W] output and struct asr_att_beam_ctc over them."""
+    dev, R = a['dec_in'].device, a['B']
+    B, W2, T, By, Cc, blank = _joint_shapes(what, y, seq_len, R, N, blank)
+    if W2 != W or T != a['T']:
+        raise ValueError('%s: y [%d,%d,%d] / seq_len [%d] do not fit %d rows of %d frames' % (what, T, By, Cc, B, R, a['T']))
+    t = dict(r=_f32((2, R, 2, T), dev), last=_i32((2, R), dev), cand=_i32((R, W + 1), dev),
+             cand_total=_f32((R, W + 1), dev), psi=_f32((R, W + 1), dev), y=y, seq_len=seq_len)
+    ctc_score = _f32((B, W), dev)
+    j = _AttBeamCtc()
+    j.By, j.Cc, j.blank, j.n_labels, j.ctc_weight = By, Cc, blank, N, lam
+    for n, v in list(t.items()) + [('ctc_score', ctc_score)]:
+        setattr(j, n, v.data_ptr())
+    return t, ctc_score, j
 
 
 def att_decoder_beam_joint(a, W_av, W_out, b_out, embedding, eos, beam_width, y, seq_len, ctc_weight,
@@ -2228,7 +2277,6 @@ def att_decoder_beam_joint(a, W_av, W_out, b_out, embedding, eos, beam_width, y,
     Every seq_len must be >= 1 (not checked here: that would read the device; JointCTCAttention.infer checks its host
     copy).  An utterance of 0 frames has the empty hypothesis alone: places no candidate with a finite CTC score reaches
     come out as finished <EOS> slots with score -inf."""
-    dev = a['dec_in'].device
     R = a['B']
     C2 = int(W_out.shape[1])
     N = C2 - 2
@@ -2238,20 +2286,10 @@ def att_decoder_beam_joint(a, W_av, W_out, b_out, embedding, eos, beam_width, y,
     lam = _check_ctc_weight(ctc_weight)
     if R % W:
         raise ValueError('att_decoder_beam_joint: %d rows are not a multiple of beam_width %d' % (R, W))
-    B, W2, T, By, Cc, blank = _joint_shapes('att_decoder_beam_joint', y, seq_len, R, N, blank)
-    if W2 != W or T != a['T']:
-        raise ValueError('att_decoder_beam_joint: y [%d,%d,%d] / seq_len [%d] do not fit %d rows of %d frames'
-                         % (T, By, Cc, B, R, a['T']))
-    extra = dict(r=_f32((2, R, 2, T), dev), last=_i32((2, R), dev), cand=_i32((R, W + 1), dev),
-                 cand_total=_f32((R, W + 1), dev), psi=_f32((R, W + 1), dev), y=y, seq_len=seq_len)
+    extra, ctc_score, j = _beam_ctc('att_decoder_beam_joint', a, y, seq_len, W, N, lam, blank)
     h, st, f, m, out, scratch, host = _beam_loop_call('att_decoder_beam_joint', a, W_av, W_out, b_out, embedding, eos, W,
                                                       length_penalty_weight, check_every,
-                                                      extra_out=dict(ctc_score=_f32((B, W), dev)), extra_scratch=extra)
-    j = _AttBeamCtc()
-    j.y, j.seq_len = y.data_ptr(), seq_len.data_ptr()
-    j.By, j.Cc, j.blank, j.n_labels, j.ctc_weight = By, Cc, blank, N, lam
-    j.r, j.last, j.ctc_score = scratch['r'].data_ptr(), scratch['last'].data_ptr(), out['ctc_score'].data_ptr()
-    j.cand, j.cand_total, j.psi = scratch['cand'].data_ptr(), scratch['cand_total'].data_ptr(), scratch['psi'].data_ptr()
+                                                      extra_out=dict(ctc_score=ctc_score), extra_scratch=extra)
     issued = C.c_int(0)
     h.check(h.lib.asr_att_decoder_beam_joint(h.h, C.byref(st), C.byref(f), C.byref(m), C.byref(j), C.byref(issued), _s()),
             'asr_att_decoder_beam_joint')
@@ -2264,17 +2302,11 @@ _ATT_JOINT_KEYS = ('score', 'advance', 'joint_select')
 def att_joint_counts(device=0):
     """Launches of the joint-search entry points on `device` since the last reset, summed over its handles
     (asr_att_joint_counts).  Host counters: no device work, no synchronisation."""
-    tot = [0] * 3
-    for h in _device_handles(device):
-        out = (C.c_ulonglong * 3)()
-        h.check(h.lib.asr_att_joint_counts(h.h, out), 'asr_att_joint_counts')
-        tot = [x + int(y) for x, y in zip(tot, out)]
-    return dict(zip(_ATT_JOINT_KEYS, tot))
+    return _counts3('att_joint_counts', _ATT_JOINT_KEYS, device)
 
 
 def reset_att_joint_counts(device=0):
-    for h in _device_handles(device):
-        h.check(h.lib.asr_reset_att_joint_counts(h.h), 'asr_reset_att_joint_counts')
+    _reset_counts3('att_joint_counts', device)
 
 
 # ---------------------------------------------------------------- shallow fusion with an RNN language model (an extension)
@@ -2387,37 +2419,22 @@ def att_beam_select_fused(logits, lm_logits, n_labels, lm_weight, length_penalty
         raise ValueError('ctc_weight must be in [0, 1], got %r' % (ctc_weight,))
     state = [(log_probs, torch.float32, 'log_probs'), (lm_score, torch.float32, 'lm_score'), (finished, torch.int32, 'finished'),
              (lengths, torch.int32, 'lengths')]
-    dev = logits.device
+    ctc = None
     if lam > 0.0:
         B, W, T, By, Cc, blank = _joint_shapes('att_beam_select_fused', y, seq_len, R, N, blank)
         _chk_state('att_beam_select_fused', r, last, T)
         if r.shape[0] != R or (beam_width is not None and int(beam_width) != W):
             raise ValueError('att_beam_select_fused: r must have %d rows' % R)
         state.append((ctc_score, torch.float32, 'ctc_score'))
-        psi, lst, cs = _f32((R, W + 1), dev), _i32((R,), dev), _f32((R,), dev)
+        ctc = (y, seq_len, r, last, T, By, Cc, blank)
     else:
         if beam_width is None:
             raise ValueError('att_beam_select_fused: without CTC posteriors beam_width must be given')
-        W, blank = int(beam_width), 0
+        W = int(beam_width)
         if W < 1 or R % W:
             raise ValueError('att_beam_select_fused: %d rows are not a multiple of beam_width %d' % (R, W))
-        B, T, By, Cc = R // W, 0, 0, 0
-        psi = lst = cs = None
-    _beam_width(W, N + 1)
-    for t, dt, n in state:
-        _chk(t, dt, n)
-        if tuple(t.shape) != (R,):
-            raise ValueError('att_beam_select_fused: %s must be [%d]' % (n, R))
-    word, parent, score = _i32((B, W), dev), _i32((B, W), dev), _f32((B, W), dev)
-    lp, fin, ln, ls = _f32((R,), dev), _i32((R,), dev), _i32((R,), dev), _f32((R,), dev)
-    cand, tot, clm = _i32((R, W + 1), dev), _f32((R, W + 1), dev), _f32((R, W + 1), dev)
-    a = 0.0 if length_penalty_weight is None else float(length_penalty_weight)
-    h.check(h.lib.asr_att_beam_select_fused(h.h, _p(logits), _p(lm_logits), B, W, N, a, lam, mu, int(bool(first_step)), _p(y),
-                                            _p(seq_len), T, By, Cc, blank, _p(r), _p(log_probs), _p(finished), _p(lengths),
-                                            _p(last), _p(ctc_score), _p(lm_score), _p(cand), _p(tot), _p(clm), _p(psi),
-                                            _p(word), _p(parent), _p(score), _p(lp), _p(fin), _p(ln), _p(lst), _p(cs), _p(ls),
-                                            _p(unfinished), _s()), 'asr_att_beam_select_fused')
-    return word, parent, score, lp, fin, ln, ls, lst, cs
+    return _select_streams('att_beam_select_fused', h, logits, lm_logits, N, W, lam, mu, length_penalty_weight, first_step,
+                           state, ctc, unfinished)
 
 
 def lm_beam_reorder(parent, word, c_src, h_src, emb):
@@ -2446,7 +2463,6 @@ def att_decoder_beam_lm(a, W_av, W_out, b_out, embedding, eos, beam_width, lm, l
     ctc_weight > 0 and y / seq_len, att_decoder_beam_joint -- whose every step also runs one step of the language model
     `lm` (dict: see RNNLM.decode_weights; its images are prepared once, before the first step) and selects on the fused
     score.  Returns that loop's dict and lm_score [B,W], the hypotheses' LM log-probabilities."""
-    dev = a['dec_in'].device
     R = a['B']
     C2 = int(W_out.shape[1])
     N = C2 - 2
@@ -2465,24 +2481,13 @@ def att_decoder_beam_lm(a, W_av, W_out, b_out, embedding, eos, beam_width, lm, l
     lst, lt = _lm_struct(dict(lm, sos=N), R, W, mu)
     extra_out = dict(lm_score=lt['lm_score'].view(B, W))
     extra = dict(lm=lt)
+    j = None
     if lam > 0.0:
-        B2, W2, T, By, Cc, blank = _joint_shapes('att_decoder_beam_lm', y, seq_len, R, N, blank)
-        if W2 != W or T != a['T']:
-            raise ValueError('att_decoder_beam_lm: y [%d,%d,%d] / seq_len [%d] do not fit %d rows of %d frames'
-                             % (T, By, Cc, B2, R, a['T']))
-        extra.update(r=_f32((2, R, 2, T), dev), last=_i32((2, R), dev), cand=_i32((R, W + 1), dev),
-                     cand_total=_f32((R, W + 1), dev), psi=_f32((R, W + 1), dev), y=y, seq_len=seq_len)
-        extra_out['ctc_score'] = _f32((B, W), dev)
+        ctc_scratch, extra_out['ctc_score'], j = _beam_ctc('att_decoder_beam_lm', a, y, seq_len, W, N, lam, blank)
+        extra.update(ctc_scratch)
     h, st, f, m, out, scratch, host = _beam_loop_call('att_decoder_beam_lm', a, W_av, W_out, b_out, embedding, eos, W,
                                                       length_penalty_weight, check_every, extra_out=extra_out,
                                                       extra_scratch=extra)
-    j = None
-    if lam > 0.0:
-        j = _AttBeamCtc()
-        j.y, j.seq_len = y.data_ptr(), seq_len.data_ptr()
-        j.By, j.Cc, j.blank, j.n_labels, j.ctc_weight = By, Cc, blank, N, lam
-        j.r, j.last, j.ctc_score = scratch['r'].data_ptr(), scratch['last'].data_ptr(), out['ctc_score'].data_ptr()
-        j.cand, j.cand_total, j.psi = scratch['cand'].data_ptr(), scratch['cand_total'].data_ptr(), scratch['psi'].data_ptr()
     issued = C.c_int(0)
     h.check(h.lib.asr_att_decoder_beam_lm(h.h, C.byref(st), C.byref(f), C.byref(m), C.byref(j) if j is not None else None,
                                           C.byref(lst), C.byref(issued), _s()), 'asr_att_decoder_beam_lm')
@@ -2495,17 +2500,11 @@ _ATT_LM_KEYS = ('lm_step', 'fused_select', 'lm_reorder')
 def att_lm_counts(device=0):
     """Calls of the LM-fusion entry points on `device` since the last reset, summed over its handles (asr_att_lm_counts).
     Host counters: no device work, no synchronisation."""
-    tot = [0] * 3
-    for h in _device_handles(device):
-        out = (C.c_ulonglong * 3)()
-        h.check(h.lib.asr_att_lm_counts(h.h, out), 'asr_att_lm_counts')
-        tot = [x + int(y) for x, y in zip(tot, out)]
-    return dict(zip(_ATT_LM_KEYS, tot))
+    return _counts3('att_lm_counts', _ATT_LM_KEYS, device)
 
 
 def reset_att_lm_counts(device=0):
-    for h in _device_handles(device):
-        h.check(h.lib.asr_reset_att_lm_counts(h.h), 'asr_reset_att_lm_counts')
+    _reset_counts3('att_lm_counts', device)
 
 
 # ------------------------------------------------- CTC prefix beam search with LM fusion / insertion bonus (an extension)
@@ -2609,17 +2608,11 @@ _CTC_BEAM_LM_KEYS = ('frames', 'lm_steps', 'commits')
 def ctc_beam_lm_counts(device=0):
     """Launches of the LM-fused CTC prefix search on `device` since the last reset, summed over its handles
     (asr_ctc_beam_lm_counts): frame kernels, LM steps, commits.  Host counters: no device work, no synchronisation."""
-    tot = [0] * 3
-    for h in _device_handles(device):
-        out = (C.c_ulonglong * 3)()
-        h.check(h.lib.asr_ctc_beam_lm_counts(h.h, out), 'asr_ctc_beam_lm_counts')
-        tot = [x + int(y) for x, y in zip(tot, out)]
-    return dict(zip(_CTC_BEAM_LM_KEYS, tot))
+    return _counts3('ctc_beam_lm_counts', _CTC_BEAM_LM_KEYS, device)
 
 
 def reset_ctc_beam_lm_counts(device=0):
-    for h in _device_handles(device):
-        h.check(h.lib.asr_reset_ctc_beam_lm_counts(h.h), 'asr_reset_ctc_beam_lm_counts')
+    _reset_counts3('ctc_beam_lm_counts', device)
 
 
 def tanh_fwd(x):

@@ -75,7 +75,7 @@ def select_fused64(logits, lm_logits, n_labels, lm_weight, lpw, first_step, log_
 
 # ------------------------------------------------------------------------- float32 emulation of the kernels' order
 def lse32(x):
-    """row_lse of csrc/lm_fusion.hip (the order of att_beam_select_kernel) on one float32 row: lane l takes the columns l,
+    """row_lse of csrc/att_beam.hip (the order of att_beam_select_kernel) on one float32 row: lane l takes the columns l,
     l + 64, ... in ascending order, the 64 partials meet in a butterfly (xor 32 .. 1); max + log(sum)."""
     x = np.asarray(x, F)
     pad = (-len(x)) % 64
@@ -89,9 +89,10 @@ def lse32(x):
 
 
 def emulate_select32(step, W, n_labels, lam, mu, lpw, y32=None, seq_len=None):
-    """att_fused_candidates_kernel + (ctc_prefix_score_kernel) + att_fused_rank_kernel in numpy float32 on one step of
-    select_case, evaluated AT the float64 statement's selection (word / parent of step['out']): the fp32 score, log_probs,
-    lm_score and ctc_score of those W winners per utterance.  Returns a dict of [R] float32 arrays."""
+    """att_select_candidates_kernel<true> + (ctc_prefix_score_kernel) + att_select_rank_kernel<CTC, true> of csrc/att_beam.hip
+    in numpy float32 on one step of select_case, evaluated AT the float64 statement's selection (word / parent of
+    step['out']): the fp32 score, log_probs, lm_score and ctc_score of those W winners per utterance.  Returns a dict of
+    [R] float32 arrays."""
     o = step['out']
     N, C2, eos = n_labels, n_labels + 2, n_labels + 1
     B = o['word'].shape[0]

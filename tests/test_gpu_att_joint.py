@@ -1,4 +1,4 @@
-"""GPU: joint CTC / attention beam search (csrc/ctc_prefix.hip) -- the prefix scorer and the state advance against the
+"""GPU: joint CTC / attention beam search (csrc/ctc_prefix.hip, csrc/att_beam.hip) -- the prefix scorer and the state advance against the
 float64 statement (models/attention/decoders/beam_search/ctc_prefix_score.py through tests/_cpu_ops_att_joint.py), the
 joint selection step by step, the native loop (asr_att_decoder_beam_joint) against the step-by-step statement, and
 JointCTCAttention.infer(ctc_weight=...) against the statement driven by oracle.attention and the oracle's CTC head.

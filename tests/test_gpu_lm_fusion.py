@@ -1,4 +1,4 @@
-"""GPU: shallow fusion of an RNN language model into the attention beam search (csrc/lm_fusion.hip) -- the LM step, the
+"""GPU: shallow fusion of an RNN language model into the attention beam search (csrc/lm_fusion.hip, csrc/att_beam.hip) -- the LM step, the
 fused selection step by step and the LM-state re-ordering against the float64 statement
 (models/attention/decoders/beam_search/lm_fusion.py through tests/_cpu_ops_lm.py), the native loop
 (asr_att_decoder_beam_lm) against the step-by-step statement, infer(lm=, lm_weight=) against the statement driven by
