@@ -193,10 +193,23 @@ enum {
   ASR_GEMMP_ROWS_128 = 0,         /* listed-row launches of the 128 x 128 NT kernel */
   ASR_GEMMP_ROWS_256,             /* listed-row launches of the 256 x 256 NT kernel */
   ASR_GEMMP_ROWS_FULL,            /* calls that ignored their list and ran the full product */
+  ASR_GEMMP_TN_FRAMES,            /* asr_gemm_tn_frames calls on the lean TN kernel, padded frames not loaded */
+  ASR_GEMMP_TN_FRAMES_GENERIC,    /* asr_gemm_tn_frames calls on the generic kernel (shape outside the lean TN path) */
+  ASR_GEMMP_HEAD_BWD_LEAN,        /* asr_ctc_head_bwd calls on the lean NT kernels (listed rows where a list is given) */
+  ASR_GEMMP_HEAD_BWD_FULL,        /* asr_ctc_head_bwd calls that ran the full generic product */
   ASR_GEMMP_N
 };
 int asr_gemm_path_counts(asr_handle* h, unsigned long long* out, int n);
 int asr_reset_gemm_path_counts(asr_handle* h);
+/* C [M, N] fp32 (+= C with accumulate) = A^T B, A [K, M] and B [K, N] bf16, for operands whose K rows are the frames of a
+ * time-major [T, Bp] batch: row k is utterance k % Bp at frame frame0 + k / Bp (K % Bp == 0; frame0 > 0 for a view that
+ * starts at a later frame), seq_len [>= Bp] int32 on the device.  CONTRACT: B is exactly zero in every row of a padded
+ * frame (frame >= seq_len[utterance]) -- the dgates the BPTT kernels write.  Those rows are then not loaded from either
+ * operand (A may hold anything there), and the result is bit for bit asr_gemm's (transA = 1): the lean TN kernel with
+ * the same tiles, split-K slabs and reducer where asr_gemm would take it, elsewhere the generic kernel asr_gemm runs for
+ * the shape, with the same predicate on its loads. */
+int asr_gemm_tn_frames(asr_handle* h, int M, int N, int K, const void* A, int lda, const void* B, int ldb, float* C,
+                       int ldc, int accumulate, const int32_t* seq_len, int Bp, int frame0, asr_stream s);
 
 /* ---- VGG front-end (models/encoders/core/vgg_blstm.py:107-177) --------------- *
  * Images are NHWC: [N = B*T frames, H = channels(40), W = splice*stack, C].
@@ -620,6 +633,42 @@ int asr_ctc_loss(asr_handle* h, const float* logits, int T, int B, int C,
                  const int32_t* seq_len, int max_label_len, float grad_scale,
                  float* loss, float* grad, int32_t* num_infeasible,
                  void* workspace, size_t workspace_bytes, asr_stream s);
+/* asr_ctc_loss with two additions (same kernels, same bits in loss / grad / *num_infeasible):
+ *  lse_done != 0: asr_ctc_head_fwd has already left the row log-sum-exps, the emissions and the cleared counter in THIS
+ *    workspace for THESE logits; the first of the three launches is skipped.
+ *  grad_bf16 != NULL (needs grad): [T*B, Kp] bf16, Kp >= C a multiple of 64 -- every value written to grad is also stored
+ *    there rounded as asr_cast_from_f32 rounds it, columns C .. Kp-1 zero in every row: the operand image of the products
+ *    that consume dlogits, without a cast pass. */
+int asr_ctc_loss_ex(asr_handle* h, const float* logits, int T, int B, int C,
+                    const int32_t* labels_flat, const int32_t* label_offsets,
+                    const int32_t* seq_len, int max_label_len, float grad_scale,
+                    float* loss, float* grad, int32_t* num_infeasible,
+                    void* workspace, size_t workspace_bytes, int lse_done, void* grad_bf16, int Kp, asr_stream s);
+/* The output layer of a CTC model and the first CTC launch in ONE kernel (bf16 operands, E % 64 == 0, C <= 64):
+ *   x_op   = dropout(hout)               [T*B, E] bf16, asr_dropout_apply(keep_prob, seed, offset) bit for bit, every row
+ *                                        (keep_prob == 0: no dropout, x_op is not written and may be NULL -- hout IS the operand)
+ *   logits = x_op W + bias               [T*B, C] fp32, every row, the bits of asr_gemm on the operand image of W
+ *   and in the workspace (asr_ctc_workspace_bytes) the row log-sum-exps, the emissions along the label sequences and the
+ *   cleared *num_infeasible, as asr_ctc_loss's first launch leaves them: follow with asr_ctc_loss_ex(lse_done = 1).
+ * Wt: the class-major image of asr_ctc_head_prep.  asr_ctc_head_ok(rows, E, C): 1 where the call applies -- the shapes
+ * whose logits product asr_gemm runs in one pass over K; others return ASR_ERR_UNSUPPORTED (run the separate launches).
+ * asr_ctc_head_prep: W [E, C] fp32 -> Wt [64, E] bf16 (classes >= C zero; NULL for C > 64) and Wp [E, Kp] bf16 (Kp = C
+ * rounded up to 64, columns >= C zero: the transposed operand of dlogits W^T on the image of asr_ctc_loss_ex).
+ * asr_ctc_head_counts: {asr_ctc_head_fwd launches, asr_ctc_loss_ex calls, asr_ctc_loss calls} since the last reset. */
+int asr_ctc_head_ok(int rows, int E, int C);
+int asr_ctc_head_prep(asr_handle* h, const float* W, int E, int C, void* Wt, void* Wp, asr_stream s);
+int asr_ctc_head_fwd(asr_handle* h, const void* hout, int T, int B, int E, float keep_prob, uint64_t seed,
+                     uint64_t offset, const void* Wt, const float* bias, int C, const int32_t* labels_flat,
+                     const int32_t* label_offsets, const int32_t* seq_len, int max_label_len, void* x_op, float* logits,
+                     int32_t* num_infeasible, void* workspace, size_t workspace_bytes, asr_stream s);
+/* d(encoder output) [M, E] fp32 = dl [M, Kp] (asr_ctc_loss_ex's bf16 image) x Wp [E, Kp]^T (asr_ctc_head_prep), times the
+ * dropout mask asr_dropout_mask(M*E, keep_prob, seed, offset) of the top layer (keep_prob == 0: none), E % 4 == 0.  rows /
+ * num_rows: asr_gemm_rows' contract (NULL: every row) -- listed rows get the full product's bits, the others are left
+ * untouched or written; the same kernels, counted as ASR_GEMMP_HEAD_BWD_* of asr_gemm_path_counts. */
+int asr_ctc_head_bwd(asr_handle* h, int M, int E, int Kp, const void* dl, const void* Wp, float* denc, float keep_prob,
+                     uint64_t seed, uint64_t offset, const int32_t* rows, int num_rows, asr_stream s);
+int asr_ctc_head_counts(asr_handle* h, unsigned long long* out3);
+int asr_reset_ctc_head_counts(asr_handle* h);
 
 /* tf.nn.ctc_greedy_decoder(merge_repeated=True) -- models/ctc/ctc.py:341-342 and
  * models/ctc/decoders/greedy_decoder.py:19-50.  logits[T,B,C]; out_labels[B,T] int32

@@ -109,12 +109,21 @@ SIGNATURES = {
     'asr_reset_conv_path_counts': (_i, [_vp]),
     'asr_gemm_path_counts': (_i, [_vp, C.POINTER(C.c_ulonglong), _i]),
     'asr_reset_gemm_path_counts': (_i, [_vp]),
+    'asr_gemm_tn_frames': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _i, _vp]),
     'asr_debug_set_cluster_cu_budget': (_i, [_i]),
     'asr_debug_placement': (_i, [_vp, _vp, _i, _i, _vp]),
     'asr_debug_poison_lds': (_i, [_vp, _vp]),
     'asr_debug_tear_probe': (_i, [_vp, _vp, C.c_uint, _i, _i, _vp, _vp]),
     'asr_ctc_workspace_bytes': (_sz, [_i, _i, _i]),
     'asr_ctc_loss': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'asr_ctc_loss_ex': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _i, _vp, _i, _vp]),
+    'asr_ctc_head_ok': (_i, [_i, _i, _i]),
+    'asr_ctc_head_prep': (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    'asr_ctc_head_fwd': (_i, [_vp, _vp, _i, _i, _i, _f, _u64, _u64, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp,
+                              _sz, _vp]),
+    'asr_ctc_head_bwd': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _f, _u64, _u64, _vp, _i, _vp]),
+    'asr_ctc_head_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
+    'asr_reset_ctc_head_counts': (_i, [_vp]),
     'asr_ctc_greedy_decode': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     'asr_ctc_beam_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'asr_ctc_beam_decode': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -43,6 +43,8 @@ struct asr_handle {
   unsigned long long gemm_counts[ASR_GEMMP_N];
   // LM-fused CTC prefix search since the last asr_reset_ctc_beam_lm_counts: {frame launches, lm steps, commits}
   unsigned long long ctc_beam_lm_counts[3];
+  // CTC head since the last asr_reset_ctc_head_counts: {asr_ctc_head_fwd launches, asr_ctc_loss_ex calls, asr_ctc_loss calls}
+  unsigned long long ctc_head_counts[3];
 };
 
 #define ASR_FAIL(h, code, ...)                                  \

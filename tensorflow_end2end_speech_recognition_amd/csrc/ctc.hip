@@ -16,6 +16,18 @@
 //                    alpha beta / (y p) are summed per class in a fixed order
 //                    (blank by a wave tree reduction, labels by rank rounds) so the result
 //                    is deterministic; writes softmax - occupation   (1 read + 1 write)
+// A training step of a CTC model with a narrow head (C <= 64, E % 64 == 0, bf16 operands) runs the stretch between the last
+// forward recurrence and the first BPTT kernel as THREE launches and one small product (asr_ctc_head_fwd, then
+// asr_ctc_loss_ex):
+//   1b. head_fwd:    ctc_head_fwd_kernel -- the top layer's dropout, logits = x W + b on MFMA and pass 1 on the logits tile
+//                    while it is in LDS: replaces dropout_apply, the generic GEMM and row_lse (three launches, two queue
+//                    gaps, one read pass over the logits) with the same bits
+//   2.  alpha_beta   as above
+//   3.  grad         ctc_grad_kernel<true> also stores the bf16 operand image [T*B, Kp] of what it writes (zero columns
+//                    behind C): no cast pass; d(encoder output) is then the lean NT product image x Wp^T on valid frames
+//                    with the top layer's dropout in its epilogue (models/ctc/ctc.py)
+// Headline step (5 x 256, B = 16, T = 745, C = 39): 270 -> 221 us between the two recurrences
+// (profiles/r09_ctc_head_tn_frames.md).  Other shapes, fp32 models and asr_ctc_loss keep launches 1, 2, 3.
 #include "common.h"
 #include <math.h>
 #include <stdlib.h>
@@ -37,20 +49,12 @@ constexpr double DNEG_INF = -INFINITY;
 constexpr int ME_ZERO = -(1 << 24);      // exponent of the value 0 (any real exponent stays above -126 * T)
 struct __attribute__((aligned(8))) MantExp { float m; int e; };
 
-__global__ __launch_bounds__(256) void row_lse_kernel(const float* __restrict__ x, int rows, int C,
-                                                      double* __restrict__ lse, int T, int B,
-                                                      const int32_t* __restrict__ labels_flat,
-                                                      const int32_t* __restrict__ label_offsets,
-                                                      const int32_t* __restrict__ seq_len, int SP,
-                                                      MantExp* __restrict__ yext, MantExp* __restrict__ yrev,
-                                                      int32_t* __restrict__ zero_word = nullptr) {
-  // (the counter the recursion kernel adds to is cleared here: as a memset it was one more packet -- 5 us and a queue gap --
-  // between the output layer and the recursions)
-  if (zero_word && blockIdx.x == 0 && threadIdx.x == 0) *zero_word = 0;
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const float* p = x + (size_t)row * C;
+// One wave, one row: p = the row's C logits (global memory in row_lse_kernel, the LDS tile of ctc_head_fwd_kernel).
+__device__ __forceinline__ void row_lse_row(const float* p, int row, int lane, int C, double* __restrict__ lse, int T,
+                                            int B, const int32_t* __restrict__ labels_flat,
+                                            const int32_t* __restrict__ label_offsets,
+                                            const int32_t* __restrict__ seq_len, int SP, MantExp* __restrict__ yext,
+                                            MantExp* __restrict__ yrev) {
   float m = NEG_INF;
   for (int k = lane; k < C; k += 64) m = fmaxf(m, p[k]);
   m = wave_reduce_max(m);
@@ -83,6 +87,123 @@ __global__ __launch_bounds__(256) void row_lse_kernel(const float* __restrict__ 
     }
     out[st] = v;
     outr[st] = v;
+  }
+}
+
+__global__ __launch_bounds__(256) void row_lse_kernel(const float* __restrict__ x, int rows, int C,
+                                                      double* __restrict__ lse, int T, int B,
+                                                      const int32_t* __restrict__ labels_flat,
+                                                      const int32_t* __restrict__ label_offsets,
+                                                      const int32_t* __restrict__ seq_len, int SP,
+                                                      MantExp* __restrict__ yext, MantExp* __restrict__ yrev,
+                                                      int32_t* __restrict__ zero_word = nullptr) {
+  // (the counter the recursion kernel adds to is cleared here: as a memset it was one more packet -- 5 us and a queue gap --
+  // between the output layer and the recursions)
+  if (zero_word && blockIdx.x == 0 && threadIdx.x == 0) *zero_word = 0;
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  row_lse_row(x + (size_t)row * C, row, lane, C, lse, T, B, labels_flat, label_offsets, seq_len, SP, yext, yrev);
+}
+
+// ---- 1b. the CTC head in one launch: dropout of the top layer's output, logits = x W + b, and kernel 1 on the tile ---------
+// One workgroup (4 waves) per 16 rows of hout [rows, E] bf16 (E % 64 == 0, C <= 64):
+//   phase 1  the 16 x E tile, 16 bytes per thread and trip: the dropout multipliers of asr_dropout_apply (word e % 4 of the
+//            Philox block at offset + e / 4, e the element's index in the whole tensor; product in fp32, rounded as
+//            f32_to_bf16 rounds) -> x_op in memory (the head's weight-gradient product reads every row of it) and the A
+//            tile in LDS.  Every element of hout is loaded by exactly one workgroup: the Philox work is done once.
+//   phase 2  wave w owns the 16 classes 16 w ..: v_mfma_f32_16x16x32_bf16 over ascending k, operands (B fragment, A
+//            fragment) as gemm_kernel issues them -- a lane's eight consecutive k of row / class (lane & 15) at k-slot
+//            (lane >> 4) -- so the accumulators hold the bits of asr_gemm's 64 x 64 and 128 x 128 tiles; B fragments are
+//            16-byte loads from the class-major weight image Wt [64, E] (rows >= C zero), all of a wave's in flight at once.
+//   phase 3  + bias -> logits in memory (every row: callers receive them) and in LDS.
+//   phase 4  wave w runs row_lse_row on rows 4 w .. 4 w + 3 of the tile: lse, yext, yrev as row_lse_kernel leaves them.
+template <bool DROP>
+__global__ __launch_bounds__(256) void ctc_head_fwd_kernel(
+    const bf16_t* __restrict__ hout, int rows, int E, float keep, uint64_t seed, uint64_t offset,
+    const bf16_t* __restrict__ Wt, const float* __restrict__ bias, int C, bf16_t* __restrict__ x_op,
+    float* __restrict__ logits, double* __restrict__ lse, int T, int B, const int32_t* __restrict__ labels_flat,
+    const int32_t* __restrict__ label_offsets, const int32_t* __restrict__ seq_len, int SP, MantExp* __restrict__ yext,
+    MantExp* __restrict__ yrev, int32_t* __restrict__ zero_word) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int LDA = E + 8;                                   // bf16 elements: 16 bytes of padding per row
+  bf16_t* As = reinterpret_cast<bf16_t*>(smem);            // [16][LDA]
+  float* Ls = reinterpret_cast<float*>(smem + (size_t)16 * LDA * sizeof(bf16_t));   // [16][64]
+  if (zero_word && blockIdx.x == 0 && threadIdx.x == 0) *zero_word = 0;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r0 = blockIdx.x * 16;
+  // phase 1
+  const int vpr = E / 8;                                   // 16-byte vectors per row
+  const float inv = 1.f / keep;
+  for (int v = tid; v < 16 * vpr; v += 256) {
+    const int r = v / vpr, kv = (v - r * vpr) * 8;
+    const int row = r0 + r;
+    bf16x8_t x = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (row < rows) {
+      const size_t e0 = (size_t)row * E + kv;
+      x = *reinterpret_cast<const bf16x8_t*>(hout + e0);
+      if constexpr (DROP) {
+        float mk[8];
+        asr_dropout_words(offset + e0 / 4, seed, keep, inv, mk);
+        asr_dropout_words(offset + e0 / 4 + 1, seed, keep, inv, mk + 4);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = (short)f32_to_bf16(bf16_to_f32((bf16_t)x[j]) * mk[j]);
+        *reinterpret_cast<bf16x8_t*>(x_op + e0) = x;
+      }
+    }
+    *reinterpret_cast<bf16x8_t*>(As + r * LDA + kv) = x;
+  }
+  __syncthreads();
+  // phase 2 + 3
+  const int fr = lane & 15, fq = lane >> 4;
+  if (wave * 16 < C) {
+    f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+    const bf16_t* wp = Wt + (size_t)(wave * 16 + fr) * E + fq * 8;
+    const bf16_t* ap = As + fr * LDA + fq * 8;
+    for (int k0 = 0; k0 < E; k0 += 256) {                  // eight 32-wide steps of B fragments in flight
+      bf16x8_t b[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (k0 + u * 32 < E) b[u] = *reinterpret_cast<const bf16x8_t*>(wp + k0 + u * 32);
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (k0 + u * 32 < E) {
+          const bf16x8_t a = *reinterpret_cast<const bf16x8_t*>(ap + k0 + u * 32);
+          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[u], a, acc, 0, 0, 0);
+        }
+    }
+    // lane holds logits[row r0 + fr][class 16 wave + 4 fq + 0..3]
+    const int row = r0 + fr;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int n = wave * 16 + fq * 4 + r;
+      if (n < C) {
+        const float v = acc[r] + bias[n];
+        Ls[fr * 64 + n] = v;
+        if (row < rows) logits[(size_t)row * C + n] = v;
+      }
+    }
+  }
+  __syncthreads();
+  // phase 4
+  for (int r = wave * 4; r < wave * 4 + 4; ++r) {
+    const int row = r0 + r;
+    if (row >= rows) break;
+    row_lse_row(Ls + r * 64, row, lane, C, lse, T, B, labels_flat, label_offsets, seq_len, SP, yext, yrev);
+  }
+}
+
+// the head's weight images from the fp32 variable W [E, C]: Wt [64, E] class-major for ctc_head_fwd_kernel (rows >= C
+// zero) and Wp [E, Kp] (Kp = C rounded up to 64, columns >= C zero), the B^T operand of the lean NT product dlogits W^T;
+// rounded as the operand shadow of the variable is (f32_to_bf16)
+__global__ void ctc_head_images_kernel(const float* __restrict__ W, int E, int C, int Kp, bf16_t* __restrict__ Wt,
+                                       bf16_t* __restrict__ Wp) {
+  const size_t n = (size_t)E * Kp;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const int e = (int)(i / Kp), c = (int)(i % Kp);
+    const bf16_t v = c < C ? f32_to_bf16(W[(size_t)e * C + c]) : (bf16_t)0;
+    Wp[i] = v;
+    if (Wt && c < 64) Wt[(size_t)c * E + e] = v;
   }
 }
 
@@ -317,13 +438,17 @@ __global__ __launch_bounds__(64 * NW) void ctc_alpha_beta_kernel(
 }
 
 // ---- 3. gradient -------------------------------------------------------------
+// IMG: every value written to grad also goes, rounded as asr_cast_from_f32 rounds it, to the bf16 image gimg [T*B, Kp]
+// (Kp >= C a multiple of 64, columns C .. Kp-1 zero in every row): the operand of the products that consume dlogits,
+// without a cast pass over grad.
+template <bool IMG>
 __global__ __launch_bounds__(256) void ctc_grad_kernel(
     const float* __restrict__ logits, const double* __restrict__ lse, int T, int B, int C,
     const int32_t* __restrict__ labels_flat, const int32_t* __restrict__ label_offsets,
     const int32_t* __restrict__ seq_len, int SW, int SP, const MantExp* __restrict__ yext,
     const MantExp* __restrict__ alpha_ws, const MantExp* __restrict__ beta_ws,
     const int32_t* __restrict__ rank_ws, const double* __restrict__ ll_ws, float grad_scale,
-    float* __restrict__ grad) {
+    float* __restrict__ grad, bf16_t* __restrict__ gimg, int Kp) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   // Per wave: gam[SW] (state occupations), acc[(SW-1)/2] (occupation of a class, kept at the position of its FIRST
@@ -337,10 +462,18 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(
   const int t = blockIdx.x * 4 + wave;
   if (t >= T) return;
   float* g = grad + ((size_t)t * B + b) * C;
+  bf16_t* gi = IMG ? gimg + ((size_t)t * B + b) * Kp : nullptr;
+  auto put = [&](int k, float v) {
+    g[k] = v;
+    if constexpr (IMG) gi[k] = f32_to_bf16(v);
+  };
+  if constexpr (IMG) {
+    for (int k = C + lane; k < Kp; k += 64) gi[k] = 0;
+  }
   const int Tb = min(seq_len[b], T);
   const double ll = ll_ws[b];
   if (t >= Tb || !(ll > DNEG_INF)) {
-    for (int k = lane; k < C; k += 64) g[k] = 0.f;
+    for (int k = lane; k < C; k += 64) put(k, 0.f);
     return;
   }
   const int lo = label_offsets[b];
@@ -388,13 +521,13 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(
   }
   // classes that are not labels (and not blank): softmax only; every address below is written exactly once
   for (int k = lane; k < C; k += 64) {
-    if (k == blank) g[k] = ((float)exp((double)row[k] - z) - blank_sum) * grad_scale;
-    else if (!((bits[k >> 5] >> (k & 31)) & 1u)) g[k] = (float)exp((double)row[k] - z) * grad_scale;
+    if (k == blank) put(k, ((float)exp((double)row[k] - z) - blank_sum) * grad_scale);
+    else if (!((bits[k >> 5] >> (k & 31)) & 1u)) put(k, (float)exp((double)row[k] - z) * grad_scale);
   }
   for (int i = lane; i < L; i += 64) {
     if ((rk[i] & 0xffff) == 0) {
       const int k = lab[i];
-      g[k] = ((float)exp((double)row[k] - z) - acc[i]) * grad_scale;
+      put(k, ((float)exp((double)row[k] - z) - acc[i]) * grad_scale);
     }
   }
 }
@@ -505,11 +638,12 @@ extern "C" size_t asr_ctc_workspace_bytes(int T, int B, int max_label_len) {
   return ctc_ws_layout(T, B, max_label_len).total;
 }
 
-extern "C" int asr_ctc_loss(asr_handle* h, const float* logits, int T, int B, int C,
-                            const int32_t* labels_flat, const int32_t* label_offsets,
-                            const int32_t* seq_len, int max_label_len, float grad_scale, float* loss,
-                            float* grad, int32_t* num_infeasible, void* workspace,
-                            size_t workspace_bytes, asr_stream s) {
+// lse_done: kernel 1 has already run on this workspace (asr_ctc_head_fwd); gimg / Kp: the bf16 image of grad (or NULL)
+static int ctc_loss_impl(asr_handle* h, const float* logits, int T, int B, int C,
+                         const int32_t* labels_flat, const int32_t* label_offsets,
+                         const int32_t* seq_len, int max_label_len, float grad_scale, float* loss,
+                         float* grad, int32_t* num_infeasible, void* workspace,
+                         size_t workspace_bytes, int lse_done, void* gimg, int Kp, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
   if (!logits || !label_offsets || !seq_len || !loss || T <= 0 || B <= 0 || C < 2 ||
       max_label_len < 0 || (max_label_len > 0 && !labels_flat))
@@ -530,9 +664,11 @@ extern "C" int asr_ctc_loss(asr_handle* h, const float* logits, int T, int B, in
   hipStream_t st = (hipStream_t)s;
   const int rows = T * B;
   const int SP = 64 * w.K;
-  hipLaunchKernelGGL(row_lse_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, logits, rows, C, lse, T, B, labels_flat,
-                     label_offsets, seq_len, SP, yext, yrev, num_infeasible);
-  ASR_CHECK_LAUNCH(h, "asr_ctc_loss(row_lse)");
+  if (!lse_done) {
+    hipLaunchKernelGGL(row_lse_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, logits, rows, C, lse, T, B, labels_flat,
+                       label_offsets, seq_len, SP, yext, yrev, num_infeasible);
+    ASR_CHECK_LAUNCH(h, "asr_ctc_loss(row_lse)");
+  }
   {
 #define ASR_AB(KV, DV, NWV)                                                                              \
   hipLaunchKernelGGL((ctc_alpha_beta_kernel<KV, DV, NWV>), dim3(2 * B), dim3(64 * NWV), 0, st, yext, yrev, T, B, C, labels_flat, \
@@ -567,13 +703,103 @@ extern "C" int asr_ctc_loss(asr_handle* h, const float* logits, int T, int B, in
     const size_t lds_g = (size_t)4 * (SW + (SW - 1) / 2 + (C + 31) / 32) * sizeof(float);
     if (lds_g > 160 * 1024)
       ASR_FAIL(h, ASR_ERR_UNSUPPORTED, "asr_ctc_loss: C=%d, Lmax=%d need %zu B of LDS", C, max_label_len, lds_g);
-    (void)hipFuncSetAttribute((const void*)ctc_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g);
-    hipLaunchKernelGGL(ctc_grad_kernel, dim3((T + 3) / 4, B), dim3(256), lds_g, st, logits, lse, T, B, C,
-                       labels_flat, label_offsets, seq_len, SW, SP, yext, alpha, beta, rank, ll, grad_scale, grad);
+    if (gimg) {
+      (void)hipFuncSetAttribute((const void*)ctc_grad_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g);
+      hipLaunchKernelGGL(ctc_grad_kernel<true>, dim3((T + 3) / 4, B), dim3(256), lds_g, st, logits, lse, T, B, C,
+                         labels_flat, label_offsets, seq_len, SW, SP, yext, alpha, beta, rank, ll, grad_scale, grad,
+                         (bf16_t*)gimg, Kp);
+    } else {
+      (void)hipFuncSetAttribute((const void*)ctc_grad_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g);
+      hipLaunchKernelGGL(ctc_grad_kernel<false>, dim3((T + 3) / 4, B), dim3(256), lds_g, st, logits, lse, T, B, C,
+                         labels_flat, label_offsets, seq_len, SW, SP, yext, alpha, beta, rank, ll, grad_scale, grad,
+                         (bf16_t*)nullptr, 0);
+    }
     ASR_CHECK_LAUNCH(h, "asr_ctc_loss(grad)");
   }
   return ASR_OK;
 }
+
+extern "C" int asr_ctc_loss(asr_handle* h, const float* logits, int T, int B, int C,
+                            const int32_t* labels_flat, const int32_t* label_offsets,
+                            const int32_t* seq_len, int max_label_len, float grad_scale, float* loss,
+                            float* grad, int32_t* num_infeasible, void* workspace,
+                            size_t workspace_bytes, asr_stream s) {
+  if (h) h->ctc_head_counts[2] += 1;
+  return ctc_loss_impl(h, logits, T, B, C, labels_flat, label_offsets, seq_len, max_label_len, grad_scale, loss, grad,
+                       num_infeasible, workspace, workspace_bytes, 0, nullptr, 0, s);
+}
+
+extern "C" int asr_ctc_loss_ex(asr_handle* h, const float* logits, int T, int B, int C,
+                               const int32_t* labels_flat, const int32_t* label_offsets,
+                               const int32_t* seq_len, int max_label_len, float grad_scale, float* loss,
+                               float* grad, int32_t* num_infeasible, void* workspace,
+                               size_t workspace_bytes, int lse_done, void* grad_bf16, int Kp, asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  if (grad_bf16 && (!grad || Kp < C || Kp % 64 != 0))
+    ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_ctc_loss_ex: the bf16 image needs grad and Kp = %d >= C = %d, Kp %% 64 == 0", Kp, C);
+  h->ctc_head_counts[1] += 1;
+  return ctc_loss_impl(h, logits, T, B, C, labels_flat, label_offsets, seq_len, max_label_len, grad_scale, loss, grad,
+                       num_infeasible, workspace, workspace_bytes, lse_done, grad_bf16, Kp, s);
+}
+
+// today's logits product of the shape runs asr_gemm's generic kernel in ONE pass over K (no split-K slabs), whose
+// accumulators ctc_head_fwd_kernel reproduces; a shape it would split keeps the separate launches
+extern "C" int asr_ctc_head_ok(int rows, int E, int C) {
+  if (rows < 1 || E < 64 || E % 64 != 0 || E > 1024 || C < 2 || C > 64) return 0;
+  const long tiles128 = (long)((rows + 127) / 128) * ((C + 127) / 128);
+  const long tiles64 = (long)((rows + 63) / 64) * ((C + 63) / 64);
+  if (tiles128 < 320 && tiles64 < 256 && E >= 16 * 64) return 0;
+  return 1;
+}
+
+extern "C" int asr_ctc_head_prep(asr_handle* h, const float* W, int E, int C, void* Wt, void* Wp, asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  if (!W || !Wp || E < 1 || C < 1 || (Wt && C > 64))
+    ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_ctc_head_prep: bad args E=%d C=%d", E, C);
+  const int Kp = (C + 63) / 64 * 64;
+  const size_t n = (size_t)E * Kp;
+  int blocks = (int)((n + 255) / 256);
+  if (blocks > 1024) blocks = 1024;
+  hipLaunchKernelGGL(ctc_head_images_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)s, W, E, C, Kp, (bf16_t*)Wt, (bf16_t*)Wp);
+  ASR_CHECK_LAUNCH(h, "asr_ctc_head_prep");
+  return ASR_OK;
+}
+
+extern "C" int asr_ctc_head_fwd(asr_handle* h, const void* hout, int T, int B, int E, float keep_prob, uint64_t seed,
+                                uint64_t offset, const void* Wt, const float* bias, int C, const int32_t* labels_flat,
+                                const int32_t* label_offsets, const int32_t* seq_len, int max_label_len, void* x_op,
+                                float* logits, int32_t* num_infeasible, void* workspace, size_t workspace_bytes,
+                                asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  if (!hout || !Wt || !bias || !logits || !label_offsets || !seq_len || T <= 0 || B <= 0 || max_label_len < 0 ||
+      (max_label_len > 0 && !labels_flat) || !(keep_prob == 0.f || (keep_prob > 0.f && keep_prob <= 1.f)) ||
+      (keep_prob != 0.f && !x_op))
+    ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_ctc_head_fwd: bad args T=%d B=%d E=%d C=%d Lmax=%d keep_prob=%g", T, B, E, C,
+             max_label_len, (double)keep_prob);
+  if ((size_t)T * B > 0x7fffffffull / (size_t)(E > C ? E : C) || !asr_ctc_head_ok(T * B, E, C))
+    ASR_FAIL(h, ASR_ERR_UNSUPPORTED, "asr_ctc_head_fwd: shape rows=%d E=%d C=%d (asr_ctc_head_ok)", T * B, E, C);
+  if (((uintptr_t)hout) % 16 != 0 || ((uintptr_t)Wt) % 16 != 0 || (x_op && ((uintptr_t)x_op) % 16 != 0))
+    ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_ctc_head_fwd: operands must be 16-byte aligned");
+  const CtcWs w = ctc_ws_layout(T, B, max_label_len);
+  if (!w.K) ASR_FAIL(h, ASR_ERR_UNSUPPORTED, "asr_ctc_head_fwd: label length %d > %d", max_label_len, (64 * 32 - 1) / 2);
+  if (!workspace || workspace_bytes < w.total)
+    ASR_FAIL(h, ASR_ERR_WORKSPACE, "asr_ctc_head_fwd: workspace %zu < %zu bytes", workspace_bytes, w.total);
+  char* ws = (char*)workspace;
+  const int rows = T * B, SP = 64 * w.K;
+  const size_t lds = (size_t)16 * (E + 8) * sizeof(bf16_t) + (size_t)16 * 64 * sizeof(float);
+#define ASR_HEAD(DROP_)                                                                                                \
+  hipLaunchKernelGGL(ctc_head_fwd_kernel<DROP_>, dim3((rows + 15) / 16), dim3(256), lds, (hipStream_t)s,             \
+                     (const bf16_t*)hout, rows, E, keep_prob, seed, offset, (const bf16_t*)Wt, bias, C, (bf16_t*)x_op, \
+                     logits, (double*)(ws + w.lse), T, B, labels_flat, label_offsets, seq_len, SP,                     \
+                     (MantExp*)(ws + w.yext), (MantExp*)(ws + w.yrev), num_infeasible)
+  if (keep_prob != 0.f) ASR_HEAD(true); else ASR_HEAD(false);
+#undef ASR_HEAD
+  ASR_CHECK_LAUNCH(h, "asr_ctc_head_fwd");
+  h->ctc_head_counts[0] += 1;
+  return ASR_OK;
+}
+
+ASR_DEFINE_COUNTS3(ctc_head_counts)
 
 extern "C" int asr_ctc_greedy_decode(asr_handle* h, const float* logits, int T, int B, int C,
                                      const int32_t* seq_len, int blank, int32_t* out_labels,

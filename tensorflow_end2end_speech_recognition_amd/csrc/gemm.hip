@@ -46,6 +46,17 @@ template <typename TO> __device__ __forceinline__ float load_out(const TO* p);
 template <> __device__ __forceinline__ float load_out<float>(const float* p) { return *p; }
 template <> __device__ __forceinline__ float load_out<bf16_t>(const bf16_t* p) { return bf16_to_f32(*p); }
 
+// The k rows of a reduction-major product as frames of a time-major [T, Bp] batch (asr_gemm_tn_frames): row k is utterance
+// k % Bp at frame frame0 + k / Bp, valid while that frame is below len[utterance].
+struct TnFrames {
+  const int32_t* len;           // [>= Bp] frames per utterance, device
+  int Bp, frame0;
+};
+__device__ __forceinline__ bool tn_frame_valid(const TnFrames& fv, int k) {
+  const int t = k / fv.Bp;
+  return fv.frame0 + t < fv.len[k - t * fv.Bp];
+}
+
 // Stage one operand tile [ROWS x BK] (logical: row r, reduction index k) into registers.
 // KCONT: memory is k-contiguous (elem(r,k) = p[r*ld + k]); else r-contiguous (p[k*ld + r]).
 template <typename T, int ROWS, bool KCONT>
@@ -56,8 +67,11 @@ struct TileLoader {
   static_assert(NVEC % 256 == 0, "tile must divide over 256 threads");
   Vec16<T> reg[PER_THREAD];
 
+  // FR (reduction-major tiles only): a k row that is a padded frame of `fv` is not loaded, zeros take its place
+  template <bool FR = false>
   __device__ __forceinline__ void load(const T* __restrict__ p, int ld, int r0, int k0, int R,
-                                       int K, bool aligned) {
+                                       int K, bool aligned, TnFrames fv = TnFrames{nullptr, 1, 0}) {
+    static_assert(!FR || !KCONT, "frames: one k row per vector");
     const int tid = threadIdx.x;
 #pragma unroll
     for (int i = 0; i < PER_THREAD; ++i) {
@@ -73,6 +87,13 @@ struct TileLoader {
         k = v / (ROWS / VEC); r = (v % (ROWS / VEC)) * VEC;
         off = (size_t)(k0 + k) * ld + (r0 + r);
         nr = VEC; nk = 1;
+      }
+      if constexpr (FR) {
+        if (k0 + k >= K || !tn_frame_valid(fv, k0 + k)) {
+#pragma unroll
+          for (int j = 0; j < VEC; ++j) reg[i].v[j] = T(0);
+          continue;
+        }
       }
       const bool full = (r0 + r + nr <= R) && (k0 + k + nk <= K);
       if (full && aligned) {
@@ -106,13 +127,15 @@ struct TileLoader {
   }
 };
 
-template <typename T, typename TO, int BM, int BN, bool TA, bool TB>
+// FR (TA && !TB, asr_gemm_tn_frames): the k rows that are padded frames of `fv` are loaded from neither operand.
+template <typename T, typename TO, int BM, int BN, bool TA, bool TB, bool FR = false>
 __global__ __launch_bounds__(256) void gemm_kernel(int M, int N, int K, const T* __restrict__ A,
                                                    int lda, const T* __restrict__ B, int ldb,
                                                    TO* __restrict__ C, int ldc,
                                                    const float* __restrict__ bias, int accumulate,
                                                    int a_aligned, int b_aligned, int kchunk,
-                                                   float* __restrict__ partial, int act, int c_vec) {
+                                                   float* __restrict__ partial, int act, int c_vec,
+                                                   TnFrames fv = TnFrames{nullptr, 1, 0}) {
   constexpr int BK = GT<T>::BK, VEC = GT<T>::VEC;
   constexpr int LDS_LD = BK + VEC;  // +16 B pad
   constexpr int WM = BM / 2, WN = BN / 2, TM = WM / 16, TN = WN / 16;
@@ -142,8 +165,8 @@ __global__ __launch_bounds__(256) void gemm_kernel(int M, int N, int K, const T*
   // one barrier per k-tile orders everything (writers of buffer b at kt+1 have passed the
   // barrier of kt, which every reader of b reached only after finishing tile kt-1).
   constexpr int STAGE = (BM + BN) * LDS_LD;
-  la.load(A, lda, m0, kbeg, M, kend, a_aligned);
-  lb.load(B, ldb, n0, kbeg, N, kend, b_aligned);
+  la.template load<FR>(A, lda, m0, kbeg, M, kend, a_aligned, fv);
+  lb.template load<FR>(B, ldb, n0, kbeg, N, kend, b_aligned, fv);
   la.store(As, LDS_LD);
   lb.store(Bs, LDS_LD);
   __syncthreads();
@@ -152,8 +175,8 @@ __global__ __launch_bounds__(256) void gemm_kernel(int M, int N, int K, const T*
     const T* Ac = As + (kt & 1) * STAGE;
     const T* Bc = Bs + (kt & 1) * STAGE;
     if (kt + 1 < nkt) {
-      la.load(A, lda, m0, kbeg + (kt + 1) * BK, M, kend, a_aligned);
-      lb.load(B, ldb, n0, kbeg + (kt + 1) * BK, N, kend, b_aligned);
+      la.template load<FR>(A, lda, m0, kbeg + (kt + 1) * BK, M, kend, a_aligned, fv);
+      lb.template load<FR>(B, ldb, n0, kbeg + (kt + 1) * BK, N, kend, b_aligned, fv);
     }
     const int fr = lane & 15, fq = lane >> 4;
     if constexpr (sizeof(T) == 2) {
@@ -944,10 +967,17 @@ static bool try_gemm_skinny_f32(int transA, int transB, int M, int N, int K, con
 // a swizzled [m][k] image -- and ran the 5 x 512 weight gradients at ~200 TFLOP/s.)
 // Split-K over slabs (summed in a fixed order by splitk_reduce_kernel), 128x128x64 tiles, double-buffered LDS.
 // Requires M % 8 == 0, N % 8 == 0, lda/ldb % 8 == 0, 16-byte aligned bases.
+// FRAMES (asr_gemm_tn_frames): the k rows are frames of a time-major [T, Bp] batch -- row k is utterance k % Bp at frame
+// frame0 + k / Bp -- and B holds exact zeros in the rows of padded frames (t >= len[b]: the BPTT kernels' dgates).  Such a
+// row is not requested from either operand; zeros go to LDS as for k >= kend.  Same tiles, same MFMA sequence, same slabs:
+// a product 0 * a it drops added +-0 to an accumulator that is never -0, so the bits are those of the plain kernel.
+// Where Bp divides 64 (kbeg and the k-tile step are multiples of 64) a thread's row kr0 + 16 q is one utterance in every
+// k-tile, and "valid" is one more upper bound on k per q: the predicate costs the loop a compare against a register.
+template <bool FRAMES>
 __global__ __launch_bounds__(256) void gemm_tn_bf16_kernel(int M, int N, int K, const bf16_t* __restrict__ A,
                                                            int lda, const bf16_t* __restrict__ Bm, int ldb,
                                                            int kchunk, float* __restrict__ partial, int tn, int tm,
-                                                           int nslab, int xcd_skip) {
+                                                           int nslab, int xcd_skip, TnFrames fv) {
   constexpr int BM = 128, BN = 128, BK = 64;
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -968,13 +998,32 @@ __global__ __launch_bounds__(256) void gemm_tn_bf16_kernel(int M, int N, int K, 
   const bf16_t* pb = Bm + (size_t)(kbeg + kr0) * ldb + n0 + mvec * 8;
   const bf16x8_t zero = {0, 0, 0, 0, 0, 0, 0, 0};
   bf16x8_t ra[4], rb[4];
+  // FRAMES: klim[q] = first k past the utterance's last valid frame, for the rows kr0 + 16 q (+ 64 kt) of this thread
+  int klim[4] = {kend, kend, kend, kend};
+  const bool per_q = FRAMES && (64 % fv.Bp) == 0;
+  if constexpr (FRAMES) {
+    if (per_q) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int b = (kr0 + 16 * q) % fv.Bp;
+        const long lim = (long)max(fv.len[b] - fv.frame0, 0) * fv.Bp;
+        klim[q] = (int)min((long)kend, lim);
+      }
+    }
+  }
   auto gload = [&](int kt) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int k = kbeg + kt * BK + kr0 + 16 * q;
       const size_t ro = (size_t)(kt * BK + 16 * q);
-      ra[q] = (a_ok && k < kend) ? *reinterpret_cast<const bf16x8_t*>(pa + ro * lda) : zero;
-      rb[q] = (b_ok && k < kend) ? *reinterpret_cast<const bf16x8_t*>(pb + ro * ldb) : zero;
+      bool k_ok = k < klim[q];
+      if constexpr (FRAMES) {
+        if (!per_q && k_ok) {                              // any Bp: the row's utterance changes from k-tile to k-tile
+          k_ok = tn_frame_valid(fv, k);
+        }
+      }
+      ra[q] = (a_ok && k_ok) ? *reinterpret_cast<const bf16x8_t*>(pa + ro * lda) : zero;
+      rb[q] = (b_ok && k_ok) ? *reinterpret_cast<const bf16x8_t*>(pb + ro * ldb) : zero;
     }
   };
   // image: subtile (mvec >> 1), row k (32 bytes), half (mvec & 1)
@@ -1073,12 +1122,69 @@ __global__ void splitk_reduce_kernel(const float* __restrict__ partial, int S, i
   }
 }
 
+// The lean TN path of a bf16 product (reduction-major operands: the weight-gradient products X^T dG), or false.
+// fv.len != NULL: the frames form of the kernel (TnFrames); everything else -- tiles, kchunk, slabs, reducer -- is the same.
+template <typename TO>
+bool try_gemm_tn_bf16(asr_handle* h, int transA, int transB, int M, int N, int K, const void* A, int lda, const void* B,
+                      int ldb, void* C, int ldc, const float* bias, int accumulate, hipStream_t st, int act,
+                      TnFrames fv = TnFrames{nullptr, 1, 0}) {
+  if (!(transA && !transB && K >= 2048 && M % 8 == 0 && N % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 &&
+        ((uintptr_t)A) % 16 == 0 && ((uintptr_t)B) % 16 == 0))
+    return false;
+  const int tm = (M + 127) / 128, tn = (N + 127) / 128;
+  // workgroups (output tiles x split-K slabs) to aim at: ~2 per CU by default; a handle whose GEMMs run BESIDE a
+  // recurrence kernel asks for few (asr_set_gemm_tn_workgroups): the slabs' write + re-read traffic is what stretches
+  // the recurrence (BPTT launch 1340 / 1307 / 1285 / 1256 us with 1024 / 512 / 128 / 32 workgroups per GEMM)
+  const int tn_wgs = h->tn_wgs > 0 ? h->tn_wgs : 512;
+  int S = (tn_wgs + tm * tn - 1) / (tm * tn);
+  const int maxS = (K + 255) / 256;
+  if (S > maxS) S = maxS;
+  if (S > 256) S = 256;
+  while (S > 1 && (size_t)S * M * N * sizeof(float) > h->scratch_bytes - ASR_XCH_BYTES) --S;
+  if ((size_t)S * M * N * sizeof(float) > h->scratch_bytes - ASR_XCH_BYTES) return false;
+  int kchunk = (K + S - 1) / S;
+  kchunk = (kchunk + 63) / 64 * 64;
+  S = (K + kchunk - 1) / kchunk;
+  const size_t lds = (size_t)2 * TN_STAGE;
+  static unsigned long long attr_done = 0;
+  if (first_on_device(attr_done)) {
+    (void)hipFuncSetAttribute((const void*)gemm_tn_bf16_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)gemm_tn_bf16_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  }
+  float* partial = (float*)h->scratch;
+  const int skip = h->xcd_skip;
+  if (fv.len)
+    hipLaunchKernelGGL(gemm_tn_bf16_kernel<true>, dim3(xcd_grid((long)tn * tm * S, skip)), dim3(256), lds, st, M, N, K,
+                       (const bf16_t*)A, lda, (const bf16_t*)B, ldb, kchunk, partial, tn, tm, S, skip, fv);
+  else
+    hipLaunchKernelGGL(gemm_tn_bf16_kernel<false>, dim3(xcd_grid((long)tn * tm * S, skip)), dim3(256), lds, st, M, N, K,
+                       (const bf16_t*)A, lda, (const bf16_t*)B, ldb, kchunk, partial, tn, tm, S, skip, fv);
+  const size_t total = (size_t)M * N;
+  int blocks = (int)((total + 255) / 256);
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(splitk_reduce_kernel<TO>, dim3(xcd_grid(blocks, skip)), dim3(256), 0, st, partial, S, M, N,
+                     (TO*)C, ldc, bias, accumulate, act, skip);
+  return true;
+}
+
 template <typename T, typename TO, int BM, int BN>
 int launch_layout(int transA, int transB, dim3 grid, size_t lds, hipStream_t st, int M, int N, int K,
                   const T* A, int lda, const T* B, int ldb, TO* C, int ldc, const float* bias,
-                  int accumulate, int aa, int ba, int kchunk, float* partial, int act) {
+                  int accumulate, int aa, int ba, int kchunk, float* partial, int act,
+                  TnFrames fv = TnFrames{nullptr, 1, 0}) {
   // 4-column vector stores need the row starts of C aligned to 4 elements
   const int c_vec = (((uintptr_t)C) % (4 * sizeof(TO)) == 0) && (ldc % 4 == 0);
+  if constexpr (sizeof(T) == 2 && sizeof(TO) == 4) {
+    if (fv.len && transA && !transB) {                     // the frames form of the same kernel (asr_gemm_tn_frames)
+      auto k = gemm_kernel<T, TO, BM, BN, true, false, true>;
+      static unsigned long long attr_done = 0;             // (its own opt-in for the 128 x 128 tiles' 72 KB of LDS)
+      if (first_on_device(attr_done))
+        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL(k, grid, dim3(256), lds, st, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, aa, ba, kchunk,
+                         partial, act, c_vec, fv);
+      return 0;
+    }
+  }
 #define ASR_GEMM_LAUNCH(TA_, TB_)                                                             \
   hipLaunchKernelGGL((gemm_kernel<T, TO, BM, BN, TA_, TB_>), grid, dim3(256), lds, st, M, N, K, A, \
                      lda, B, ldb, C, ldc, bias, accumulate, aa, ba, kchunk, partial, act, c_vec)
@@ -1094,7 +1200,7 @@ template <typename T, typename TO>
 int launch_gemm(asr_handle* h, int transA, int transB, int M, int N, int K, const void* A, int lda,
                 const void* B, int ldb, void* C, int ldc, const float* bias, int accumulate,
                 hipStream_t st, int act, const float* mul = nullptr, int ldm = 0, bool* mul_done = nullptr,
-                GemmDrop drop = GemmDrop{1.f, 0, 0, 0}) {
+                GemmDrop drop = GemmDrop{1.f, 0, 0, 0}, TnFrames fv = TnFrames{nullptr, 1, 0}) {
   constexpr int VEC = GT<T>::VEC, BK = GT<T>::BK;
   if constexpr (sizeof(T) == 4 && sizeof(TO) == 4) {
     if (try_gemm_skinny_f32(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, st, act)) return 0;
@@ -1105,39 +1211,7 @@ int launch_gemm(asr_handle* h, int transA, int transB, int M, int N, int K, cons
       return 0;
     }
     // reduction-major operands (X^T dG): lean TN kernel, always through split-K slabs
-    if (transA && !transB && K >= 2048 && M % 8 == 0 && N % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0 &&
-        ((uintptr_t)A) % 16 == 0 && ((uintptr_t)B) % 16 == 0) {
-      const int tm = (M + 127) / 128, tn = (N + 127) / 128;
-      // workgroups (output tiles x split-K slabs) to aim at: ~2 per CU by default; a handle whose GEMMs run BESIDE a
-      // recurrence kernel asks for few (asr_set_gemm_tn_workgroups): the slabs' write + re-read traffic is what stretches
-      // the recurrence (BPTT launch 1340 / 1307 / 1285 / 1256 us with 1024 / 512 / 128 / 32 workgroups per GEMM)
-      const int tn_wgs = h->tn_wgs > 0 ? h->tn_wgs : 512;
-      int S = (tn_wgs + tm * tn - 1) / (tm * tn);
-      const int maxS = (K + 255) / 256;
-      if (S > maxS) S = maxS;
-      if (S > 256) S = 256;
-      while (S > 1 && (size_t)S * M * N * sizeof(float) > h->scratch_bytes - ASR_XCH_BYTES) --S;
-      if ((size_t)S * M * N * sizeof(float) <= h->scratch_bytes - ASR_XCH_BYTES) {
-        int kchunk = (K + S - 1) / S;
-        kchunk = (kchunk + 63) / 64 * 64;
-        S = (K + kchunk - 1) / kchunk;
-        const size_t lds = (size_t)2 * TN_STAGE;
-        static unsigned long long attr_done = 0;
-        if (first_on_device(attr_done)) {
-          (void)hipFuncSetAttribute((const void*)gemm_tn_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        }
-        float* partial = (float*)h->scratch;
-        const int skip = h->xcd_skip;
-        hipLaunchKernelGGL(gemm_tn_bf16_kernel, dim3(xcd_grid((long)tn * tm * S, skip)), dim3(256), lds, st, M, N, K,
-                           (const bf16_t*)A, lda, (const bf16_t*)B, ldb, kchunk, partial, tn, tm, S, skip);
-        const size_t total = (size_t)M * N;
-        int blocks = (int)((total + 255) / 256);
-        if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(splitk_reduce_kernel<TO>, dim3(xcd_grid(blocks, skip)), dim3(256), 0, st, partial, S, M, N,
-                           (TO*)C, ldc, bias, accumulate, act, skip);
-        return 0;
-      }
-    }
+    if (try_gemm_tn_bf16<TO>(h, transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, st, act, fv)) return 0;
   }
   const int aa = (((uintptr_t)A) % 16 == 0) && (lda % VEC == 0);
   const int ba = (((uintptr_t)B) % 16 == 0) && (ldb % VEC == 0);
@@ -1154,7 +1228,7 @@ int launch_gemm(asr_handle* h, int transA, int transB, int M, int N, int K, cons
       (void)hipFuncSetAttribute((const void*)gemm_kernel<T, TO, 128, 128, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
     return launch_layout<T, TO, 128, 128>(transA, transB, grid, lds, st, M, N, K, (const T*)A, lda,
-                                          (const T*)B, ldb, (TO*)C, ldc, bias, accumulate, aa, ba, K, nullptr, act);
+                                          (const T*)B, ldb, (TO*)C, ldc, bias, accumulate, aa, ba, K, nullptr, act, fv);
   }
   const long tiles64 = (long)((M + 63) / 64) * ((N + 63) / 64);
   // small output, long reduction (the dW = X^T dG products: K = T*B): split K over blockIdx.z so
@@ -1172,7 +1246,7 @@ int launch_gemm(asr_handle* h, int transA, int transB, int M, int N, int K, cons
   if (S <= 1) {
     dim3 grid((N + 63) / 64, (M + 63) / 64);
     return launch_layout<T, TO, 64, 64>(transA, transB, grid, lds, st, M, N, K, (const T*)A, lda,
-                                        (const T*)B, ldb, (TO*)C, ldc, bias, accumulate, aa, ba, K, nullptr, act);
+                                        (const T*)B, ldb, (TO*)C, ldc, bias, accumulate, aa, ba, K, nullptr, act, fv);
   }
   int kchunk = (K + S - 1) / S;
   kchunk = (kchunk + BK - 1) / BK * BK;
@@ -1180,7 +1254,7 @@ int launch_gemm(asr_handle* h, int transA, int transB, int M, int N, int K, cons
   dim3 grid((N + 63) / 64, (M + 63) / 64, S);
   float* partial = (float*)h->scratch;
   launch_layout<T, TO, 64, 64>(transA, transB, grid, lds, st, M, N, K, (const T*)A, lda, (const T*)B, ldb,
-                               (TO*)C, ldc, nullptr, 0, aa, ba, kchunk, partial, 0);
+                               (TO*)C, ldc, nullptr, 0, aa, ba, kchunk, partial, 0, fv);
   const size_t total = (size_t)M * N;
   int blocks = (int)((total + 255) / 256);
   if (blocks > 2048) blocks = 2048;
@@ -1354,6 +1428,58 @@ extern "C" int asr_gemm_rows(asr_handle* h, int dtype, int transA, int transB, i
     return asr_gemm_drop(h, dtype, transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, act, keep_prob, seed,
                          offset, s);
   return asr_gemm_mul(h, dtype, transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, act, mul, ldmul, s);
+}
+
+// C [M,N] fp32 (+= with accumulate) = A^T B on bf16 operands whose k rows are frames (see TnFrames above): the plain TN
+// product's bits wherever B is zero in the rows of padded frames, without the loads of those rows from A or B -- on the
+// lean TN kernel where asr_gemm takes it, on the generic kernel (the kernel asr_gemm runs for the shape) elsewhere.
+extern "C" int asr_gemm_tn_frames(asr_handle* h, int M, int N, int K, const void* A, int lda, const void* B, int ldb,
+                                  float* C, int ldc, int accumulate, const int32_t* seq_len, int Bp, int frame0,
+                                  asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  if (M < 0 || N < 0 || K < 0 || !A || !B || !C || lda < M || ldb < N || ldc < N || !seq_len || Bp < 1 || frame0 < 0 ||
+      K % Bp != 0)
+    ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_gemm_tn_frames: bad args M=%d N=%d K=%d lda=%d ldb=%d ldc=%d Bp=%d frame0=%d "
+             "(K %% Bp == 0)", M, N, K, lda, ldb, ldc, Bp, frame0);
+  if (M == 0 || N == 0) return ASR_OK;
+  if (try_gemm_tn_bf16<float>(h, 1, 0, M, N, K, A, lda, B, ldb, C, ldc, nullptr, accumulate, (hipStream_t)s, 0,
+                              TnFrames{seq_len, Bp, frame0})) {
+    h->gemm_counts[ASR_GEMMP_TN_FRAMES] += 1;
+    ASR_CHECK_LAUNCH(h, "asr_gemm_tn_frames");
+    return ASR_OK;
+  }
+  // shapes outside the lean TN path: the generic kernel asr_gemm runs for them, in its frames form
+  h->gemm_counts[ASR_GEMMP_TN_FRAMES_GENERIC] += 1;
+  launch_gemm<bf16_t, float>(h, 1, 0, M, N, K, A, lda, B, ldb, C, ldc, nullptr, accumulate, (hipStream_t)s, 0, nullptr, 0,
+                             nullptr, GemmDrop{1.f, 0, 0, 0}, TnFrames{seq_len, Bp, frame0});
+  ASR_CHECK_LAUNCH(h, "asr_gemm_tn_frames");
+  return ASR_OK;
+}
+
+// d(encoder output) [M, E] fp32 of a CTC head: dl [M, Kp] (the bf16 image of dlogits, asr_ctc_loss_ex) times Wp [E, Kp]^T
+// (asr_ctc_head_prep), times the top layer's dropout mask (keep_prob != 0: asr_gemm_drop's epilogue), on the rows that
+// `rows` lists (or all, rows == NULL): asr_gemm_rows' contract and kernels under counters of its own.
+extern "C" int asr_ctc_head_bwd(asr_handle* h, int M, int E, int Kp, const void* dl, const void* Wp, float* denc,
+                                float keep_prob, uint64_t seed, uint64_t offset, const int32_t* rows, int num_rows,
+                                asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  const bool use_drop = keep_prob != 0.f;
+  if (M < 0 || E < 1 || Kp < 1 || !dl || !Wp || !denc || E % 4 != 0 || (rows && (num_rows < 0 || num_rows > M)) ||
+      (use_drop && !(keep_prob > 0.f && keep_prob <= 1.f)))
+    ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_ctc_head_bwd: bad args M=%d E=%d Kp=%d num_rows=%d keep_prob=%g (E %% 4 == 0)", M, E,
+             Kp, num_rows, (double)keep_prob);
+  if (M == 0 || (rows && num_rows == 0)) return ASR_OK;
+  const GemmDrop drop = {use_drop ? keep_prob : 1.f, seed, offset, use_drop ? 1 : 0};
+  if (try_gemm_nt_bf16<float>(0, 1, M, E, Kp, dl, Kp, Wp, Kp, denc, E, nullptr, 0, (hipStream_t)s, 0, nullptr, 0, drop, rows,
+                              rows ? num_rows : 0, nullptr)) {
+    h->gemm_counts[ASR_GEMMP_HEAD_BWD_LEAN] += 1;
+    ASR_CHECK_LAUNCH(h, "asr_ctc_head_bwd");
+    return ASR_OK;
+  }
+  h->gemm_counts[ASR_GEMMP_HEAD_BWD_FULL] += 1;
+  if (use_drop)
+    return asr_gemm_drop(h, ASR_BF16, 0, 1, M, E, Kp, dl, Kp, Wp, Kp, denc, E, nullptr, 0, 0, keep_prob, seed, offset, s);
+  return asr_gemm_act(h, ASR_BF16, ASR_F32, 0, 1, M, E, Kp, dl, Kp, Wp, Kp, denc, E, nullptr, 0, 0, s);
 }
 
 extern "C" int asr_gemm_path_counts(asr_handle* h, unsigned long long* out, int n) {

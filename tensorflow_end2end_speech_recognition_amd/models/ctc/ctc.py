@@ -9,6 +9,8 @@ TF1 is deferred graph + session; this is eager: compute_loss RUNS encoder -> FC 
 CTC forward and keeps the activations; train(loss, optimizer, lr) runs backward,
 per-variable clip, weight decay and the optimizer update for that forward.
 """
+import os as _os
+
 import numpy as np
 import torch
 
@@ -42,6 +44,20 @@ class Placeholder(object):
     def feed(self, value):
         self.value = value
         return self
+
+
+# The stretch between the last forward recurrence and the first BPTT kernel of a training step in three launches plus the
+# two small products (ASR_CTC_HEAD_FUSED=0: the separate launches, A-B):
+#   ops.ctc_head_fwd   the top layer's dropout, the logits and the first CTC kernel (row log-sum-exp, emissions) in one --
+#                      where ops.ctc_head_ok takes the head: C <= 64, E % 64 == 0;
+#   ops.ctc_loss_ex    alpha / beta, and the gradient kernel also stores the bf16 operand image of dlogits (no cast pass);
+#   d(encoder output)  = image x padded head weights on the lean NT kernel, valid frames only, the top layer's dropout mask
+#                      in its epilogue (no dropout pass over the gradient): its padded frames are left UNDEFINED, and the
+#                      top layer's BPTT kernel discards what it loads from them, as every layer below does for dx
+#                      (DESIGN.md 4.2).
+# Device tensors, bf16 operands, no bottleneck layer, softmax_temperature == 1, a plain blstm / lstm encoder on one pipeline
+# whose top mask is a Philox descriptor or absent.
+HEAD_FUSED = _os.environ.get('ASR_CTC_HEAD_FUSED', '1') != '0'
 
 
 def _not_enough_time(n):
@@ -117,6 +133,9 @@ class CTC(ModelBase):
         rng = np.random.RandomState(seed)
         self.store = ParamStore(self.device)
         enc_dim = self.encoder.build(self.store, input_size * num_stack * splice, rng)
+        self._enc_dim = enc_dim
+        self._head_imgs = None                           # (Wt, Wp) of ops.ctc_head_prep, refreshed per step
+        self._head_state = None
         self._declare_heads(rng, enc_dim, parameter_init)
         self.store.finalize()
         self._tape = None
@@ -162,8 +181,27 @@ class CTC(ModelBase):
         self.store.declare(self.head_scope + '/biases', (self.num_classes,), np.zeros(self.num_classes))
 
     # ------------------------------------------------------------------ graph pieces
-    def _build(self, inputs, inputs_seq_len, keep_prob, is_training):
-        """ctc.py:175-238: encoder -> [T*B, 2H] -> output FC -> logits [T,B,C] (time-major)."""
+    def _build(self, inputs, inputs_seq_len, keep_prob, is_training, head=None):
+        """ctc.py:175-238: encoder -> [T*B, 2H] -> output FC -> logits [T,B,C] (time-major).
+        head (compute_loss of a training step, HEAD_FUSED): dict(flat, off, max_len) of the labels on the device -- where
+        the conditions at HEAD_FUSED hold, the head runs as described there and self._head_state tells compute_loss how
+        to go on (None: the separate launches)."""
+        enc = self.encoder
+        E0, Cc = self._enc_dim, self.num_classes
+        # the new launches: device tensors only (the CPU stand-ins of the tests know the separate ones)
+        want = (head is not None and HEAD_FUSED and inputs.is_cuda and self.dtype == ASR_BF16 and not self.bottleneck_dim
+                and type(enc) in (load('blstm'), load('lstm')) and E0 % 64 == 0)   # (the plain stacks: front ends and
+        #                                                     multitask / subsampled encoders keep the separate launches)
+        Bq = inputs.shape[0] + (-inputs.shape[0]) % 16
+        fuse_fwd = want and Cc <= 64 and ops.ctc_head_ok(inputs.shape[1] * Bq, E0, Cc)
+        if hasattr(enc, 'defer_top_dropout'):
+            enc.defer_top_dropout = bool(fuse_fwd)
+        self._head_state = None
+        if want and self._head_imgs is None:
+            Kp = (Cc + 63) // 64 * 64
+            self._head_imgs = (torch.empty((64, E0), dtype=torch.bfloat16, device=inputs.device) if Cc <= 64 else None,
+                               torch.empty((E0, Kp), dtype=torch.bfloat16, device=inputs.device))
+        self._want_head_imgs = want
         rng_state = None
         if is_training and keep_prob is not None and float(keep_prob) < 1.0:
             self._dropout_calls += 1
@@ -180,6 +218,23 @@ class CTC(ModelBase):
         sh = self.store.shadow(self.dtype)               # refreshed by side_extra where the encoder offers it
         x_op = self._enc_operand()                       # [T,Bp,E]
         T, Bp, E = x_op.shape
+        if want and not getattr(enc, '_split', 0) and getattr(enc, 'num_proj', None) is None:
+            top_mask = enc._top_drop if enc._top_deferred else enc.layers[-1].ctx['mask']
+            if top_mask is None or isinstance(top_mask, tuple):
+                self._head_state = dict(lse_done=False, ws=None, ninf=None, top_mask=top_mask)
+        if getattr(enc, '_top_deferred', False):
+            if self._head_state is None:
+                raise RuntimeError('CTC head: the encoder deferred its top dropout for a head that does not apply it')
+            # x_op is the top layer's output BEFORE dropout: one launch forms the dropped operand, the logits and what
+            # the first CTC kernel would leave in the workspace
+            ws = ops.ctc_workspace(T, Bp, head['max_len'], x_op.device)
+            x_op, logits, ninf = ops.ctc_head_fwd(x_op, enc._top_drop, self._head_imgs[0],
+                                                  self.store[self.head_scope + '/biases'], Cc, head['flat'], head['off'],
+                                                  enc.seq_len_padded, head['max_len'], ws)
+            self._head_state.update(lse_done=True, ws=ws, ninf=ninf)
+            self._bn = None
+            self._head_in = x_op
+            return logits
         enc = x_op
         self._bn = None
         if self.bottleneck_dim:
@@ -200,7 +255,10 @@ class CTC(ModelBase):
         return logits
 
     def _refresh_head_shadow(self):
-        """Operand-dtype copies of the head weights (cast per variable on first use after an update)."""
+        """Operand-dtype copies of the head weights (cast per variable on first use after an update), and beside them
+        the images of the fused head launches (once per step, on the encoder's side stream)."""
+        if getattr(self, '_want_head_imgs', False):
+            ops.ctc_head_prep(self.store[self.head_scope + '/weights'], out=self._head_imgs)
         sh = self.store.shadow(self.dtype)
         if sh is not self.store:
             for n in self.store.names:
@@ -248,14 +306,21 @@ class CTC(ModelBase):
         # output FC and the CTC kernels
         inputs_seq_len, off_d, flat_d = ops.upload_ints(
             dev, [inputs_seq_len, offsets, flat if len(flat) else np.zeros(1, np.int32)])
-        logits = self._build(inputs, inputs_seq_len, keep_prob, is_training)
+        head = dict(flat=flat_d, off=off_d, max_len=max_len) if (is_training and softmax_temperature == 1) else None
+        logits = self._build(inputs, inputs_seq_len, keep_prob, is_training, head=head)
         T, Bp, C = logits.shape
         ctc_in = logits
         inv_temp = 1.0 / float(softmax_temperature)
         if softmax_temperature != 1:
             ctc_in = ops.scale_(logits.clone(), inv_temp)
-        ctc_losses, grad, ninf = ops.ctc_loss(ctc_in, flat_d, off_d, self.encoder.seq_len_padded,
-                                              max_len, grad_scale=inv_temp / B, want_grad=is_training)
+        hs, img = self._head_state, None
+        if hs is not None:
+            ctc_losses, grad, img, ninf = ops.ctc_loss_ex(ctc_in, flat_d, off_d, self.encoder.seq_len_padded, max_len,
+                                                          grad_scale=inv_temp / B, ws=hs['ws'], ninf=hs['ninf'],
+                                                          lse_done=hs['lse_done'])
+        else:
+            ctc_losses, grad, ninf = ops.ctc_loss(ctc_in, flat_d, off_d, self.encoder.seq_len_padded,
+                                                  max_len, grad_scale=inv_temp / B, want_grad=is_training)
         ctc_loss = ctc_losses[:B].mean()                                   # ctc.py:298
         total_loss = ctc_loss
         if self.weight_decay > 0:
@@ -269,7 +334,8 @@ class CTC(ModelBase):
         # asynchronously while training (raises at most ops.DeferredCheck.DEPTH = 4 steps late, the rows themselves contribute 0 loss / 0 gradient) and
         # checked at once in evaluation
         ops.defer_zero_check(ninf, _not_enough_time, blocking=not is_training)
-        self._tape = dict(dlogits=grad, B=B) if is_training else None
+        self._tape = dict(dlogits=grad, B=B, img=img, top_mask=hs['top_mask'] if hs is not None else None) \
+            if is_training else None
         total_loss._asr_model = self
         return total_loss, logits[:, :B]
 
@@ -284,6 +350,25 @@ class CTC(ModelBase):
         E = x_op.shape[2]
         sh = st.shadow(self.dtype)
         dl2d = dlogits.view(T * Bp, C)
+        if tape.get('img') is not None:
+            # dlogits arrived with its bf16 image [T*Bp, Kp] (zero columns behind C): d(encoder output) = image x padded
+            # weights on the lean NT kernel where it applies -- valid frames only, the top layer's dropout in the epilogue;
+            # the padded frames of denc stay undefined and the top layer's BPTT kernel discards them
+            img, mask = tape['img'], tape['top_mask']
+            rows = getattr(self.encoder, '_rows', None)
+            listed = {'rows': rows[0]} if rows else {}
+            denc = self._new_denc(T * Bp, E, dlogits.device)
+            # (the side lane forks first: its marker on the main stream then stands in front of the product, not between
+            # the product and the top layer's BPTT kernel)
+            with ops.side_lane(dlogits.device, keep=(x_op, img, dl2d)):   # joined by encoder.backward
+                ops.gemm(x_op.view(T * Bp, E), img[:, :C], transA=True, out=st.g(self.head_scope + '/weights'))
+                ops.colsum(dl2d, out=st.g(self.head_scope + '/biases'))
+            ops.ctc_head_bwd(img, self._head_imgs[1], denc, drop=mask, **listed)
+            self.encoder.backward(denc.view(T, Bp, E), top_masked=mask is not None, **self._encoder_backward_extra())
+            if self.weight_decay > 0:
+                ops.weight_decay(st.grad, st.flat, st.plan, st.decay_mask, self.weight_decay)
+            self._tape = None
+            return
         dl_op = ops.cast_from_f32(dl2d, ASR_BF16) if self.dtype == ASR_BF16 else dl2d
         denc = ops.gemm(dl_op, sh[self.head_scope + '/weights'], transB=True, out_dtype=ASR_F32)
         with ops.side_lane(dlogits.device, keep=(x_op, dl_op, dl2d)):   # joined by encoder.backward
@@ -303,6 +388,11 @@ class CTC(ModelBase):
         if self.weight_decay > 0:
             ops.weight_decay(st.grad, st.flat, st.plan, st.decay_mask, self.weight_decay)
         self._tape = None
+
+    @staticmethod
+    def _new_denc(rows, E, device):
+        """The d(encoder output) buffer of the fused head path; only its valid frames get written."""
+        return torch.empty((rows, E), dtype=torch.float32, device=device)
 
     def _encoder_backward_extra(self):
         """Further gradients entering the encoder (the sub-task head of MultitaskCTC)."""

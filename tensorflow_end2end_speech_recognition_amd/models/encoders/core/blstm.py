@@ -83,6 +83,11 @@ class _RecurrentEncoderBase(object):
         self.grad_ready_hook = None    # callable(layer_index, LSTMLayer) fired from backward() per finished layer
         self.side_extra = None         # callable run on the side stream after the weight images (once per call)
         self.side_extra_event = None
+        # a CTC model whose head kernel applies the top layer's dropout itself (ops.ctc_head_fwd) sets this before a call;
+        # _top_deferred says whether the call did leave _out_op un-dropped (one pipeline, a dropout descriptor or none) and
+        # _top_drop is that descriptor
+        self.defer_top_dropout = False
+        self._top_deferred, self._top_drop = False, None
         self.want_f32_outputs = True   # False: __call__ returns the operand-dtype outputs (no fp32 copy is made)
         self.halves = ENC_HALVES       # two half-batch pipelines where the batch has at least two tiles (see ENC_HALVES)
         self.layers_b = None           # twin layer objects (same variables, own tape) of the second pipeline
@@ -165,12 +170,17 @@ class _RecurrentEncoderBase(object):
         # per step (side_extra: the operand-dtype shadow of the head weights), then the dropout masks (one event each)
         preps, ready_w, ready_m = [], [], []
         with ops.side_lane(inputs.device):
+            # with two layers or more, side_extra goes in front of the LAST layer's marker: the main stream waits for
+            # that one anyway (before the second layer), so the caller needs no wait of its own in front of the head
+            fold = self.side_extra is not None and len(self.layers) >= 2
+            self.side_extra_event = None
             for li, layer in enumerate(self.layers):
                 preps.append(layer.prepare(inputs.device, self.dtype, Tt, Bp, 1.0, False, None, None,
                                            ldk=ldk0 if li == 0 else None))
+                if fold and li + 1 == len(self.layers):
+                    self.side_extra()
                 ready_w.append(ops.stream_event())
-            self.side_extra_event = None
-            if self.side_extra is not None:
+            if self.side_extra is not None and not fold:
                 self.side_extra()
                 self.side_extra_event = ops.stream_event()   # the caller waits for it before using what it refreshed
             for li, layer in enumerate(self.layers):
@@ -178,6 +188,7 @@ class _RecurrentEncoderBase(object):
                 preps[li]['mask'] = layer.make_mask(inputs.device, Tt, Bp, keep_prob, is_training, rs_of(li), dm)
                 ready_m.append(ops.stream_event())
         self._split = self._split_rows(Bp) if drop_masks is None else 0
+        self._top_deferred, self._top_drop = False, None
         # the valid frames of each pipeline's [T, B] layout (rnn_util.VALID_ROWS): built on the host, uploaded once per
         # call on the upload stream before the first layer is enqueued, used by every layer's projection and dx product
         plans = rnn_util.row_plans(lens_host, B, Tt, Bp, self._split) if (self.dtype != ASR_F32 and inputs.is_cuda) \
@@ -198,8 +209,14 @@ class _RecurrentEncoderBase(object):
                 ops.wait_event(ready_w[li])
             elif li == 1:
                 ops.wait_event(ready_w[-1])
+            top = li + 1 == len(self.layers)
+            mk = preps[li]['mask']
+            defer = top and self.defer_top_dropout and self.num_layers_sub is None and (mk is None or isinstance(mk, tuple))
             x, final = layer.forward(x, seq_len, self.dtype, keep_prob, is_training, prep=preps[li],
-                                     mask_event=ready_m[li], rows=self._rows[0] if self._rows else None)
+                                     mask_event=ready_m[li], rows=self._rows[0] if self._rows else None,
+                                     defer_mask=defer)
+            if defer:
+                self._top_deferred, self._top_drop = True, mk
             finals.append(final)
             if self.num_layers_sub is not None and li + 1 == self.num_layers_sub:
                 # blstm.py:326-328: outputs_sub IS the tensor the next layer consumes (after the dropout wrapper)
@@ -323,10 +340,16 @@ class _RecurrentEncoderBase(object):
             return tuple(LSTMStateTuple(cf[d, :B], hf[d, :B]) for d in range(2))
         return tuple(LSTMStateTuple(cf[0, :B], hf[0, :B]) for cf, hf in finals[:upto])
 
-    def backward(self, d_outputs, d_final=None, need_input_grad=False, d_outputs_sub=None):
+    def backward(self, d_outputs, d_final=None, need_input_grad=False, d_outputs_sub=None, top_masked=False):
         """d_outputs: gradient w.r.t. the TIME-MAJOR padded-batch outputs [T,Bpad,ndir*H] fp32.
+        top_masked (one pipeline, no projection): d_outputs already carries the top layer's dropout mask (the CTC head's
+        product forms it in its epilogue) and only its VALID frames are defined -- the top layer's BPTT kernel then relies
+        on the invariant of DESIGN.md 4.2, as the layers below do for dx: what it loads from a padded frame is used only
+        through its `act` / `ldp` selects.
         d_outputs_sub (multitask encoders): gradient w.r.t. the sub-task outputs, joined where they branch off.
         Returns the gradient w.r.t. the (time-major) encoder input if need_input_grad."""
+        if top_masked and (self.num_proj is not None or self._split):
+            raise ValueError('backward: top_masked needs the single-pipeline LSTMLayer stack')
         if self.num_proj is not None:
             dx = d_outputs
             for li in reversed(range(len(self.layers))):
@@ -340,7 +363,7 @@ class _RecurrentEncoderBase(object):
         if self._split:
             return self._backward_halves(d_outputs, d_final, need_input_grad)
         dx = d_outputs
-        masked = False
+        masked = bool(top_masked)
         for li in reversed(range(len(self.layers))):
             if d_outputs_sub is not None and li == self.num_layers_sub - 1:
                 dx = torch.add(dx, d_outputs_sub)

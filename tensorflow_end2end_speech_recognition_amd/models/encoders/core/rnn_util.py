@@ -47,6 +47,11 @@ DW_AFTER_DX_FLOPS = {'0': float('inf'), '1': 0.0}.get(_os.environ.get('ASR_DW_AF
 # NT GEMM skips them (ops.gemm(rows=...), asr_gemm_rows; the headline batch is 46 %
 # padding: 51 row tiles instead of 94).  bf16-operand LSTMLayer stacks; ASR_GEMM_VALID_ROWS=0: the full products (A-B).
 VALID_ROWS = _os.environ.get('ASR_GEMM_VALID_ROWS', '1') != '0'
+# the four weight-gradient products of an LSTMLayer (x^T dG, h_prev^T dG per direction) do not LOAD the rows of padded
+# frames: the BPTT kernels write exact zeros to dgates there, so those rows add nothing, and with the loads gone the
+# products are quieter neighbours of the BPTT kernel of the layer below (ops.gemm_tn_frames, asr_gemm_tn_frames: same tiles,
+# slabs, reducer and bits).  Device tensors with bf16 operands; ASR_GEMM_TN_FRAMES=0: the plain products (A-B).
+TN_FRAMES = _os.environ.get('ASR_GEMM_TN_FRAMES', '1') != '0'
 
 
 def valid_rows(lens, T, B=None):
@@ -145,11 +150,13 @@ class LSTMLayer(object):
         return ops.dropout_apply(t, *mask) if isinstance(mask, tuple) else ops.apply_mask(t, mask)
 
     def forward(self, x, seq_len, dtype, keep_prob=1.0, is_training=True, rng_state=None,
-                drop_mask=None, save=True, prep=None, mask_event=None, rows=None):
+                drop_mask=None, save=True, prep=None, mask_event=None, rows=None, defer_mask=False):
         """x [T,B,ldk] in `dtype` (ldk >= din: columns din.. are zero padding); returns
         (out [T,B,ndir*H] in dtype, (c_final, h_final)).
         rows: (int32 device vector, count), the valid frames of [T,B] (valid_rows) -- the x-projection is then computed
-        for those rows only (the recurrence kernel discards what it loads from the others)."""
+        for those rows only (the recurrence kernel discards what it loads from the others).
+        defer_mask: a dropout DESCRIPTOR is not applied here -- `out` is hout, and the caller's consumer forms the dropped
+        operand itself (the CTC head's forward kernel, ops.ctc_head_fwd); backward then takes dout_masked=True."""
         T, B, ldk = x.shape
         H, ndir = self.H, self.ndir
         if prep is None:
@@ -164,7 +171,7 @@ class LSTMLayer(object):
                                                self.forget_bias, self.cell_clip or 0.0)
         out = hout
         mask = prep['mask']
-        if mask is not None:
+        if mask is not None and not (defer_mask and isinstance(mask, tuple)):
             if not isinstance(mask, tuple):
                 ops.wait_event(mask_event)   # a mask tensor may have been produced on the side stream
             out = self._masked(hout, mask)
@@ -231,17 +238,23 @@ class LSTMLayer(object):
             torch.empty((ndir, din + H, 4 * H), dtype=torch.float32, device=x.device)   # interleaved cols
         ops.set_side_gemm_workgroups(x.device, BG_WGS if background else 0)
         done = []
+        lens = c['seq_len']
+        frames = TN_FRAMES and x.is_cuda and dtype == ASR_BF16 and torch.is_tensor(lens) and lens.numel() >= B
+
+        def tn(a, dg, frame0, out):   # a^T dg; frame0: the frame of dg's first row
+            if frames:
+                ops.gemm_tn_frames(a, dg, lens, B, frame0, out=out, accumulate=add)
+            else:
+                ops.gemm(a, dg, transA=True, out=out, accumulate=add)
         for d in range(ndir):
             with ops.side_lane(x.device, keep=(x, hout, dgates, dpeep, dw_il), lane=1 + (d % DW_LANES), after=fork):
                 dg = dg2d[:, d * 4 * H:(d + 1) * 4 * H]
-                ops.gemm(x2d, dg, transA=True, out=dw_il[d, :din], accumulate=add)
+                tn(x2d, dg, 0, dw_il[d, :din])
                 if T > 1:
                     if d == 0:   # forward direction: h_prev(t) = h(t-1)
-                        ops.gemm(h2d[:(T - 1) * B, d * H:(d + 1) * H], dg[B:], transA=True, out=dw_il[d, din:],
-                                 accumulate=add)
+                        tn(h2d[:(T - 1) * B, d * H:(d + 1) * H], dg[B:], 1, dw_il[d, din:])
                     else:        # backward direction: h_prev(t) = h(t+1) (zero beyond len-1)
-                        ops.gemm(h2d[B:, d * H:(d + 1) * H], dg[:(T - 1) * B], transA=True, out=dw_il[d, din:],
-                                 accumulate=add)
+                        tn(h2d[B:, d * H:(d + 1) * H], dg[:(T - 1) * B], 0, dw_il[d, din:])
                 elif not add:
                     dw_il[d, din:].zero_()
                 if d % DW_LANES > 0:

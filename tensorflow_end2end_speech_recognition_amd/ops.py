@@ -529,6 +529,32 @@ def gemm(A, B, transA=False, transB=False, bias=None, out=None, out_dtype=None, 
     return out
 
 
+def gemm_tn_frames(A, B, seq_len, Bp, frame0=0, out=None, accumulate=False):
+    """C [M,N] fp32 = A^T @ B for bf16 A [K,M], B [K,N] whose rows are the frames of a time-major [T,Bp] batch: row k is
+    utterance k % Bp at frame frame0 + k // Bp.  B must be exactly zero in the rows of padded frames (frame >=
+    seq_len[utterance]: the BPTT kernels' dgates); those rows are then loaded from neither operand and the result has
+    the bits of gemm(A, B, transA=True) (asr_gemm_tn_frames).  seq_len: int32 device vector of at least Bp lengths."""
+    h = _h(A)
+    for t, n in ((A, 'A'), (B, 'B')):
+        if t.dtype != torch.bfloat16 or t.dim() != 2 or t.stride(1) != 1:
+            raise ValueError('gemm_tn_frames: %s must be 2-D bf16 with unit inner stride' % n)
+    K, M = A.shape
+    N = B.shape[1]
+    Bp, frame0 = int(Bp), int(frame0)
+    _chk(seq_len, torch.int32, 'seq_len')
+    if B.shape[0] != K or Bp < 1 or K % Bp or frame0 < 0 or seq_len.dim() != 1 or not seq_len.is_contiguous() \
+            or seq_len.numel() < Bp:
+        raise ValueError('gemm_tn_frames: K = %d / %d rows, Bp = %d, %d lengths' % (K, B.shape[0], Bp, seq_len.numel()))
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=A.device)
+    elif out.dtype != torch.float32 or out.shape != (M, N) or out.stride(1) != 1:
+        raise ValueError('gemm_tn_frames: bad out %s' % (tuple(out.shape),))
+    h.check(h.lib.asr_gemm_tn_frames(h.h, M, N, K, C.c_void_p(A.data_ptr()), A.stride(0), C.c_void_p(B.data_ptr()),
+                                     B.stride(0), C.c_void_p(out.data_ptr()), out.stride(0), int(accumulate),
+                                     _p(seq_len), Bp, frame0, _s()), 'asr_gemm_tn_frames')
+    return out
+
+
 def _out_like(out, shape, dtype, device, what):
     """`out` (a contiguous tensor of exactly this shape / dtype, e.g. a slice of a larger one along the first axis) or a fresh one."""
     if out is None:
@@ -1484,6 +1510,8 @@ def reset_conv_path_counts(device=0):
 
 # the ASR_GEMMP_* enum of include/asr_hip.h, in its order
 _GEMM_PATH_KEYS = ('rows_128', 'rows_256', 'rows_full')
+_TN_PATH_KEYS = ('tn_frames', 'tn_frames_generic')
+_HEAD_BWD_KEYS = ('head_bwd_lean', 'head_bwd_full')   # behind those    # behind the listed-row counters in the ASR_GEMMP_* enum
 
 
 def gemm_path_counts(device=0):
@@ -1497,6 +1525,31 @@ def gemm_path_counts(device=0):
         h.check(h.lib.asr_gemm_path_counts(h.h, out, n), 'asr_gemm_path_counts')
         tot = [a + int(b) for a, b in zip(tot, out)]
     return dict(zip(_GEMM_PATH_KEYS, tot))
+
+
+def tn_frames_path_counts(device=0):
+    """What the gemm_tn_frames calls on `device` ran since the last reset_gemm_path_counts: calls on the lean TN kernel
+    and calls on the generic kernel (shape outside the lean TN path); neither loads the rows of padded frames."""
+    n0, n = len(_GEMM_PATH_KEYS), len(_GEMM_PATH_KEYS) + len(_TN_PATH_KEYS)
+    tot = [0] * n
+    for h in _device_handles(device):
+        out = (C.c_ulonglong * n)()
+        h.check(h.lib.asr_gemm_path_counts(h.h, out, n), 'asr_gemm_path_counts')
+        tot = [a + int(b) for a, b in zip(tot, out)]
+    return dict(zip(_TN_PATH_KEYS, tot[n0:]))
+
+
+def ctc_head_bwd_counts(device=0):
+    """What the ctc_head_bwd calls on `device` ran since the last reset_gemm_path_counts: calls on the lean NT kernels
+    (on the listed rows where a list was given) and calls that ran the full generic product."""
+    n0 = len(_GEMM_PATH_KEYS) + len(_TN_PATH_KEYS)
+    n = n0 + len(_HEAD_BWD_KEYS)
+    tot = [0] * n
+    for h in _device_handles(device):
+        out = (C.c_ulonglong * n)()
+        h.check(h.lib.asr_gemm_path_counts(h.h, out, n), 'asr_gemm_path_counts')
+        tot = [a + int(b) for a, b in zip(tot, out)]
+    return dict(zip(_HEAD_BWD_KEYS, tot[n0:]))
 
 
 def reset_gemm_path_counts(device=0):
@@ -1534,6 +1587,123 @@ def ctc_loss(logits, labels_flat, label_offsets, seq_len, max_label_len, grad_sc
                                _p(seq_len), int(max_label_len), float(grad_scale), _p(loss), _p(grad),
                                _p(ninf), _p(ws), nbytes, _s()), 'asr_ctc_loss')
     return loss, grad, ninf
+
+
+def ctc_head_ok(rows, E, Cc):
+    """Whether ctc_head_fwd takes a [rows, E] x [E, Cc] head (asr_ctc_head_ok): bf16 operands, E % 64 == 0, Cc <= 64, and
+    a logits product that ops.gemm runs in one pass over E."""
+    return bool(_lib.load().asr_ctc_head_ok(int(rows), int(E), int(Cc)))
+
+
+def ctc_head_prep(W, out=None):
+    """Operand images of a CTC head's weights W [E, Cc] fp32 (asr_ctc_head_prep): (Wt [64, E] bf16 class-major for
+    ctc_head_fwd, or None for Cc > 64; Wp [E, Kp] bf16, Kp = Cc rounded up to 64, columns >= Cc zero, for the product
+    dlogits W^T on ctc_loss_ex's bf16 image)."""
+    h = _h(W)
+    _chk(W, torch.float32, 'W')
+    E, Cc = W.shape
+    Kp = (Cc + 63) // 64 * 64
+    if out is not None:
+        Wt, Wp = out
+        if (Cc <= 64 and (Wt is None or Wt.shape != (64, E) or Wt.dtype != torch.bfloat16)) or Wp.shape != (E, Kp) \
+                or Wp.dtype != torch.bfloat16:
+            raise ValueError('ctc_head_prep: bad out images for W %s' % (tuple(W.shape),))
+    else:
+        Wt = torch.empty((64, E), dtype=torch.bfloat16, device=W.device) if Cc <= 64 else None
+        Wp = torch.empty((E, Kp), dtype=torch.bfloat16, device=W.device)
+    h.check(h.lib.asr_ctc_head_prep(h.h, _p(W), E, Cc, _p(Wt), _p(Wp), _s()), 'asr_ctc_head_prep')
+    return Wt, Wp
+
+
+def ctc_workspace(T, B, max_label_len, device):
+    nbytes = _lib.load().asr_ctc_workspace_bytes(int(T), int(B), int(max_label_len))
+    return torch.empty((nbytes,), dtype=torch.uint8, device=device)
+
+
+def ctc_head_fwd(hout, drop, Wt, bias, Cc, labels_flat, label_offsets, seq_len, max_label_len, ws):
+    """The CTC head's forward in one launch (asr_ctc_head_fwd).  hout [T,B,E] bf16: the top layer's output BEFORE its
+    dropout; drop = (keep_prob, seed, offset) or None.  Returns (x_op [T,B,E] bf16 -- dropout_apply(hout, *drop), or hout
+    itself without dropout --, logits [T,B,Cc] fp32, num_infeasible [1] int32, cleared); `ws` (ctc_workspace) then holds
+    what ctc_loss_ex(lse_done=True) continues from."""
+    h = _h(hout)
+    _chk(hout, torch.bfloat16, 'hout')
+    _chk(Wt, torch.bfloat16, 'Wt')
+    _chk(bias, torch.float32, 'bias')
+    T, B, E = hout.shape
+    if Wt.shape != (64, E) or bias.numel() != Cc:
+        raise ValueError('ctc_head_fwd: weight image %s / bias %d for E = %d, C = %d' % (tuple(Wt.shape), bias.numel(), E, Cc))
+    dev = hout.device
+    x_op = torch.empty_like(hout) if drop is not None else hout
+    logits = torch.empty((T, B, Cc), dtype=torch.float32, device=dev)
+    ninf = torch.empty((1,), dtype=torch.int32, device=dev)     # zeroed by the call
+    keep, seed, off = (float(drop[0]), int(drop[1]), int(drop[2])) if drop is not None else (0.0, 0, 0)
+    h.check(h.lib.asr_ctc_head_fwd(h.h, _p(hout), T, B, E, keep, seed, off, _p(Wt), _p(bias), int(Cc), _p(labels_flat),
+                                   _p(label_offsets), _p(seq_len), int(max_label_len),
+                                   _p(x_op) if drop is not None else None, _p(logits), _p(ninf), _p(ws), ws.numel(), _s()),
+            'asr_ctc_head_fwd')
+    return x_op, logits, ninf
+
+
+def ctc_head_bwd(img, Wp, out, drop=None, rows=None):
+    """d(encoder output) of a CTC head into `out` [M,E] fp32 (asr_ctc_head_bwd): img [M,Kp] bf16 (ctc_loss_ex's image of
+    dlogits) x Wp [E,Kp]^T (ctc_head_prep), times the dropout mask drop = (keep_prob, seed, offset) of the top layer in
+    the epilogue.  rows = (int32 device vector, count): only the listed rows have to be right, as for gemm(rows=...)."""
+    h = _h(img)
+    _chk(img, torch.bfloat16, 'img')
+    _chk(Wp, torch.bfloat16, 'Wp')
+    _chk(out, torch.float32, 'out')
+    M, Kp = img.shape
+    E = Wp.shape[0]
+    if Wp.shape != (E, Kp) or out.shape != (M, E) or E % 4:
+        raise ValueError('ctc_head_bwd: img %s, Wp %s, out %s' % (tuple(img.shape), tuple(Wp.shape), tuple(out.shape)))
+    rt, nr = (rows[0], int(rows[1])) if rows is not None else (None, 0)
+    if rt is not None:
+        _chk(rt, torch.int32, 'rows')
+        if rt.dim() != 1 or not 0 <= nr <= min(rt.numel(), M):
+            raise ValueError('ctc_head_bwd: bad row list')
+    keep, seed, off = (float(drop[0]), int(drop[1]), int(drop[2])) if drop is not None else (0.0, 0, 0)
+    h.check(h.lib.asr_ctc_head_bwd(h.h, M, E, Kp, _p(img), _p(Wp), _p(out), keep, seed, off, _p(rt), nr, _s()),
+            'asr_ctc_head_bwd')
+    return out
+
+
+def ctc_loss_ex(logits, labels_flat, label_offsets, seq_len, max_label_len, grad_scale=1.0, ws=None, ninf=None,
+                lse_done=False, want_image=True):
+    """ctc_loss through asr_ctc_loss_ex: continues from ctc_head_fwd's workspace (lse_done) and also returns the bf16
+    image [T*B, Kp] of the gradient (Kp = C rounded up to 64, zero columns behind C).
+    Returns (loss [B], grad [T,B,C] fp32, grad image or None, num_infeasible)."""
+    h = _h(logits)
+    _chk(logits, torch.float32, 'logits')
+    T, B, Cc = logits.shape
+    dev = logits.device
+    if ws is None:
+        if lse_done:
+            raise ValueError('ctc_loss_ex: lse_done needs the workspace of ctc_head_fwd')
+        ws = ctc_workspace(T, B, max_label_len, dev)
+    if ninf is None:
+        ninf = torch.empty((1,), dtype=torch.int32, device=dev)
+    loss = torch.empty((B,), dtype=torch.float32, device=dev)
+    grad = torch.empty_like(logits)
+    Kp = (Cc + 63) // 64 * 64
+    img = torch.empty((T * B, Kp), dtype=torch.bfloat16, device=dev) if want_image else None
+    h.check(h.lib.asr_ctc_loss_ex(h.h, _p(logits), T, B, Cc, _p(labels_flat), _p(label_offsets), _p(seq_len),
+                                  int(max_label_len), float(grad_scale), _p(loss), _p(grad), _p(ninf), _p(ws),
+                                  ws.numel(), 1 if lse_done else 0, _p(img), Kp if want_image else 0, _s()),
+            'asr_ctc_loss_ex')
+    return loss, grad, img, ninf
+
+
+_CTC_HEAD_KEYS = ('head_fwd', 'loss_ex', 'loss')
+
+
+def ctc_head_counts(device=0):
+    """CTC head calls on `device` since the last reset (asr_ctc_head_counts): fused forward launches (ctc_head_fwd),
+    ctc_loss_ex calls, and calls of the plain ctc_loss.  Host counters: no device work, no synchronisation."""
+    return _counts3('ctc_head_counts', _CTC_HEAD_KEYS, device)
+
+
+def reset_ctc_head_counts(device=0):
+    _reset_counts3('ctc_head_counts', device)
 
 
 def ctc_greedy_decode(logits, seq_len, blank=None):
