@@ -55,7 +55,19 @@ def model_kwargs(params):
         time_major=True, sharpening_factor=params['sharpening_factor'],
         logits_temperature=params['logits_temperature'], sigmoid_smoothing=params['sigmoid_smoothing'],
         dtype=params.get('dtype', 'f32'), device=params.get('device', 'cuda:0'),
-        subsample_list=params.get('subsample_list'), subsample_type=params.get('subsample_type', 'drop'))
+        subsample_list=params.get('subsample_list'), subsample_type=params.get('subsample_type', 'drop'),
+        label_smoothing_prob=float(params.get('label_smoothing_prob') or 0.0))
+
+
+def scheduled_sampling_prob(params, step):
+    """The probability of feeding the model's own prediction at training step `step` (0-based): the config's
+    scheduled_sampling_prob, ramped linearly from 0 over scheduled_sampling_ramp_max_step steps when that key is set
+    (p * min(1, step / ramp)); without it p at once.  (Keys of the reference's att_baseline.yml that its code never reads.)"""
+    p = float(params.get('scheduled_sampling_prob') or 0.0)
+    ramp = params.get('scheduled_sampling_ramp_max_step')
+    if p == 0.0 or not ramp:
+        return p
+    return p * min(1.0, float(step) / float(ramp))
 
 
 def run_name(params):
@@ -77,6 +89,10 @@ def run_name(params):
         name += '_temp' + str(params['logits_temperature'])
     if params.get('subsample_list') and any(params['subsample_list']):
         name += '_sub' + params.get('subsample_type', 'drop') + str(sum(bool(f) for f in params['subsample_list']))
+    if params.get('scheduled_sampling_prob'):
+        name += '_ss' + str(params['scheduled_sampling_prob'])
+    if params.get('label_smoothing_prob'):
+        name += '_ls' + str(params['label_smoothing_prob'])
     return name
 
 
@@ -105,9 +121,14 @@ def do_train(model, params):
     is_char = 'char' in params['label_type']
     kp = [1 - float(params[k]) for k in ('dropout_encoder', 'dropout_decoder', 'dropout_embedding')]
 
+    steps = [0]
+
     def train_step(data, learning_rate):
         inputs, labels, inputs_seq_len, labels_seq_len, _ = data
-        loss, _, _, _ = model.compute_loss(inputs[0], labels[0], inputs_seq_len[0], labels_seq_len[0], *kp)
+        ss = scheduled_sampling_prob(params, steps[0])
+        steps[0] += 1
+        loss, _, _, _ = model.compute_loss(inputs[0], labels[0], inputs_seq_len[0], labels_seq_len[0], *kp,
+                                           **(dict(scheduled_sampling_prob=ss) if ss else {}))
         model.train(loss, optimizer=params['optimizer'], learning_rate=learning_rate)
 
     def monitor(data):

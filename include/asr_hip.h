@@ -882,6 +882,31 @@ typedef struct asr_att_infer {
 } asr_att_infer;
 int asr_att_decoder_infer(asr_handle* h, const asr_att_decoder* a, const asr_att_infer* f, int* steps_issued,
                           asr_stream s);
+/* ---- scheduled sampling in the training loop, native (later within ABI 5, additive) --------------------------- *
+ * EXTENSION: the reference names scheduled_sampling_prob / scheduled_sampling_ramp_max_step in
+ * examples/timit/config/attention/att_baseline.yml and none of its code reads them; the meaning given here is that of
+ * tf.contrib.seq2seq.ScheduledEmbeddingTrainingHelper with the argmax in place of a sample.  asr_att_decoder_fwd in which
+ * the token fed at step k may be the model's own prediction:
+ *     fed[0, b] = teacher_ids[0, b]
+ *     fed[k, b] = argmax_c logits[k-1, b, c]   if draw[k, b] != 0 and a->live[k, b] != 0      (k >= 1)
+ *               = teacher_ids[k, b]            otherwise (finished and padding rows keep the teacher's token)
+ * The argmax is over the raw logits of the previous step (no imputation, no temperature), the first maximum wins (as
+ * asr_argmax_rows).  Per step the call issues the forward step of asr_att_decoder_fwd (saved activations at row k, a->dmask
+ * honoured), the head asr_att_decoder_infer issues behind it (attentional-vector FC, tanh, output layer) and one selection
+ * kernel that writes ids_fed[k+1] and embedding[fed] * emb_mask[k+1] into the Em embedding columns of dec_in[k+1]; row 0 of
+ * dec_in and of ids_fed is the caller's, as is the drawing of `draw`.  The fed ids are constants of the backward pass
+ * (asr_att_decoder_bwd as it is; the embedding gradient scatters to ids_fed).  av_all / logits_all are not imputed. */
+typedef struct asr_att_decoder_ss {
+  const float *W_av, *W_out, *b_out;            /* [U+E2,U], [U,C2], [C2] or NULL */
+  const float *embedding;                       /* [C2, Em] */
+  int C2;
+  const int32_t *teacher_ids;                   /* [To,B], each in [0, C2) */
+  const float *draw;                            /* [To,B]: != 0 feeds the prediction (row 0 is not read) */
+  const float *emb_mask;                        /* [To,B,Em] or NULL (row 0 is not read) */
+  float *av_all, *logits_all;                   /* [To,B,U], [To,B,C2] */
+  int32_t *ids_fed;                             /* [To,B]; rows 1 .. To-1 written */
+} asr_att_decoder_ss;
+int asr_att_decoder_fwd_ss(asr_handle* h, const asr_att_decoder* a, const asr_att_decoder_ss* f, asr_stream s);
 /* ---- beam search over the attention decoder, native (later within ABI 5) ------------------------------------ *
  * The reference's BeamSearchDecoder (models/attention/decoders/beam_search/beam_search_decoder.py; dead code there: it
  * imports an RNNDecoder that does not exist, the functions below are complete).  Per utterance W slots; the device batch
@@ -1161,6 +1186,14 @@ int asr_embedding_scatter(asr_handle* h, const float* dout, const int32_t* ids, 
 int asr_seq_xent(asr_handle* h, const float* logits, const int32_t* targets, const float* weights,
                  int rows, int C, float eps, float dscale, float* row_loss, float* dlogits,
                  asr_stream s);
+/* EXTENSION (later within ABI 5): asr_seq_xent against the label-smoothed target q = (1 - smoothing) * onehot + smoothing / C
+ * (label_smoothing_prob of the reference's examples/timit/config/attention/att_baseline.yml and
+ * regularization/att_blstm_location_ls.yml; none of its code reads the key): row_loss[r] = w[r] * (lse - (1 - smoothing)
+ * (x_tgt + eps) - (smoothing / C) sum_c (x_c + eps)), dlogits = (softmax - q) * w * dscale; rows with w == 0 are exact
+ * zeros.  0 <= smoothing < 1; smoothing == 0 is asr_seq_xent bit for bit. */
+int asr_seq_xent_ls(asr_handle* h, const float* logits, const int32_t* targets, const float* weights,
+                    int rows, int C, float eps, float smoothing, float dscale, float* row_loss, float* dlogits,
+                    asr_stream s);
 int asr_argmax_rows(asr_handle* h, const float* x, int rows, int C, int32_t* out, asr_stream s);
 
 /* ---- gradient clipping + optimizers -------------------------------------- *

@@ -1532,6 +1532,46 @@ __global__ __launch_bounds__(256) void seq_xent_kernel(const float* __restrict__
   }
 }
 
+// seq_xent_kernel against the smoothed target q = (1 - ls) * onehot + ls / C (label_smoothing_prob): same row-per-wave
+// layout, one more sum over the row.  row_loss = w * (lse - (1 - ls) (x_tg + eps) - (ls / C) sum_c (x_c + eps)),
+// dlogits = (softmax - q) * w * scale.  ls == 0 gives seq_xent_kernel's values bit for bit (1 * a - 0 * b).
+__global__ __launch_bounds__(256) void seq_xent_ls_kernel(const float* __restrict__ logits,
+                                                          const int32_t* __restrict__ targets,
+                                                          const float* __restrict__ weights, int rows, int Cc,
+                                                          float eps, float ls, float dscale,
+                                                          float* __restrict__ row_loss, float* __restrict__ dlogits) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const float* p = logits + (size_t)row * Cc;
+  const float w = weights[row];
+  if (w == 0.f) {   // masked position: exact zero (never 0 * NaN)
+    if (lane == 0) row_loss[row] = 0.f;
+    if (dlogits)
+      for (int k = lane; k < Cc; k += 64) dlogits[(size_t)row * Cc + k] = 0.f;
+    return;
+  }
+  float m = -INFINITY;
+  for (int k = lane; k < Cc; k += 64) m = fmaxf(m, p[k] + eps);
+  m = wave_reduce_max(m);
+  float s = 0.f, tot = 0.f;
+  for (int k = lane; k < Cc; k += 64) {
+    s += expf(p[k] + eps - m);
+    tot += p[k] + eps;
+  }
+  s = wave_reduce_sum(s);
+  tot = wave_reduce_sum(tot);
+  const float lse = m + logf(s);
+  const int tg = targets[row];
+  const float on = 1.f - ls, off = ls / (float)Cc;
+  if (lane == 0) row_loss[row] = w * (lse - on * (p[tg] + eps) - off * tot);
+  if (dlogits) {
+    const float sc = w * dscale;
+    for (int k = lane; k < Cc; k += 64)
+      dlogits[(size_t)row * Cc + k] = (expf(p[k] + eps - lse) - ((k == tg ? on : 0.f) + off)) * sc;
+  }
+}
+
 __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restrict__ x, int rows, int Cc,
                                                           int32_t* __restrict__ out) {
   const int lane = threadIdx.x & 63;
@@ -2144,6 +2184,18 @@ extern "C" int asr_seq_xent(asr_handle* h, const float* logits, const int32_t* t
   ASR_CHECK_LAUNCH(h, "asr_seq_xent");
   return ASR_OK;
 }
+extern "C" int asr_seq_xent_ls(asr_handle* h, const float* logits, const int32_t* targets, const float* weights,
+                               int rows, int C, float eps, float smoothing, float dscale, float* row_loss,
+                               float* dlogits, asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  ASR_NEED(logits && targets && weights && row_loss && rows >= 0 && C > 0 && smoothing >= 0.f && smoothing < 1.f,
+           "asr_seq_xent_ls: bad args");
+  if (!rows) return ASR_OK;
+  hipLaunchKernelGGL(seq_xent_ls_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)s, logits, targets, weights,
+                     rows, C, eps, smoothing, dscale, row_loss, dlogits);
+  ASR_CHECK_LAUNCH(h, "asr_seq_xent_ls");
+  return ASR_OK;
+}
 extern "C" int asr_argmax_rows(asr_handle* h, const float* x, int rows, int C, int32_t* out, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
   ASR_NEED(x && out && rows >= 0 && C > 0, "asr_argmax_rows: bad args");
@@ -2422,6 +2474,88 @@ extern "C" int asr_att_decoder_infer(asr_handle* h, const asr_att_decoder* a, co
   if (rc != ASR_OK) ASR_FAIL(h, rc, "asr_att_decoder_infer: step %d failed", k);
   ASR_CHECK_LAUNCH(h, "asr_att_decoder_infer");
   if (steps_issued) *steps_issued = k;
+  return ASR_OK;
+}
+
+// ---------------------------------------------------------------- scheduled-sampling training loop, native
+namespace {
+// One workgroup per batch row, behind the output layer of decoder step k; every pointer is the row block of step k + 1
+// except `logits` (step k).  The token step k + 1 is fed: the argmax of step k's raw logits (first maximum wins, the
+// reduction of att_infer_select_kernel) where the row's draw is set and the row is still live at k + 1, the teacher's
+// token otherwise -- the reduction runs only when it is used (the test is uniform over the workgroup).  The fed id goes
+// to ids_n and its embedding, times the row's embedding-dropout mask, into the Em embedding columns of the next input row;
+// the context and h columns of that row are the loop's.
+__global__ __launch_bounds__(256) void att_ss_select_kernel(const float* __restrict__ logits, int C2,
+                                                            const float* __restrict__ draw_n, const float* __restrict__ live_n,
+                                                            const int32_t* __restrict__ teacher_n, int32_t* __restrict__ ids_n,
+                                                            const float* __restrict__ emb, int Em,
+                                                            const float* __restrict__ mask_n, float* __restrict__ dnext,
+                                                            int Din) {
+  __shared__ float sv[4];
+  __shared__ int si[4];
+  const int b = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int id = teacher_n[b];
+  if (draw_n[b] != 0.f && live_n[b] != 0.f) {
+    const float* p = logits + (size_t)b * C2;
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int k = threadIdx.x; k < C2; k += 256) {
+      const float v = p[k];
+      if (v > best || (v == best && k < bi)) { best = v; bi = k; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(best, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+    }
+    if (lane == 0) { sv[w] = best; si[w] = bi; }
+    __syncthreads();
+    best = sv[0]; bi = si[0];
+#pragma unroll
+    for (int i = 1; i < 4; ++i)
+      if (sv[i] > best || (sv[i] == best && si[i] < bi)) { best = sv[i]; bi = si[i]; }
+    id = bi == 0x7fffffff ? 0 : bi;
+  }
+  if (threadIdx.x == 0) ids_n[b] = id;
+  float* d = dnext + (size_t)b * Din;
+  const float* e = emb + (size_t)id * Em;
+  if (mask_n) {
+    const float* mk = mask_n + (size_t)b * Em;
+    for (int j = threadIdx.x; j < Em; j += 256) d[j] = e[j] * mk[j];
+  } else {
+    for (int j = threadIdx.x; j < Em; j += 256) d[j] = e[j];
+  }
+}
+}  // namespace
+
+extern "C" int asr_att_decoder_fwd_ss(asr_handle* h, const asr_att_decoder* a, const asr_att_decoder_ss* f, asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  ASR_TRY(dec_check(h, a, false));
+  if (!f || !f->W_av || !f->W_out || !f->embedding || !f->teacher_ids || !f->draw || !f->av_all || !f->logits_all ||
+      !f->ids_fed || f->C2 < 1 || a->Em < 1)
+    ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_fwd_ss: bad arguments");
+  const int B = a->B, U = a->U, E2 = a->E2, Em = a->Em, To = a->To, C2 = f->C2;
+  const int Din = Em + E2 + U, Dav = U + E2;
+  hipStream_t st = (hipStream_t)s;
+  ASR_TRY(dec_cell_image(h, a, s));
+  for (int k = 0; k < To; ++k) {
+    const bool more = k + 1 < To;
+    ASR_TRY(dec_fwd_step(h, a, k, k, more, s));
+    // the head of the step, as asr_att_decoder_infer issues it
+    float* av = f->av_all + (size_t)k * B * U;
+    float* lg = f->logits_all + (size_t)k * B * C2;
+    ASR_TRY(asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, B, U, Dav, a->av_in + (size_t)k * B * Dav, Dav, f->W_av, U, av, U, nullptr,
+                         0, 0, s));
+    ASR_TRY(asr_tanh_fwd(h, av, av, (size_t)B * U, s));
+    ASR_TRY(asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, B, C2, U, av, U, f->W_out, C2, lg, C2, f->b_out, 0, 0, s));
+    if (!more) break;
+    const size_t n = (size_t)(k + 1) * B;
+    hipLaunchKernelGGL(att_ss_select_kernel, dim3(B), dim3(256), 0, st, lg, C2, f->draw + n, a->live + n, f->teacher_ids + n,
+                       f->ids_fed + n, f->embedding, Em, f->emb_mask ? f->emb_mask + n * Em : nullptr,
+                       a->dec_in + n * Din, Din);
+  }
+  ASR_CHECK_LAUNCH(h, "asr_att_decoder_fwd_ss");
   return ASR_OK;
 }
 

@@ -58,7 +58,8 @@ class AttentionSeq2Seq(ModelBase):
                  clip_grad_norm=5.0, clip_activation_encoder=50, clip_activation_decoder=50,
                  weight_decay=0.0, time_major=True, sharpening_factor=1.0, logits_temperature=1.0,
                  sigmoid_smoothing=False, name='attention', dtype='f32', device='cuda:0', seed=0,
-                 _extra_vars=None, prev_alpha='zeros', subsample_list=None, subsample_type='drop'):
+                 _extra_vars=None, prev_alpha='zeros', subsample_list=None, subsample_type='drop',
+                 label_smoothing_prob=0.0):
         super(AttentionSeq2Seq, self).__init__()
         assert input_size % 3 == 0, 'input_size must be divisible by 3 (+ delta, double delta features).'
         assert splice % 2 == 1, 'splice must be the odd number'
@@ -67,6 +68,11 @@ class AttentionSeq2Seq(ModelBase):
         AL.check_attention_type(attention_type)
         if prev_alpha not in ('zeros', 'carry'):
             raise ValueError("prev_alpha is 'zeros' (the reference's effective graph) or 'carry'")
+        # label_smoothing_prob (extension keyword; a key of the reference's att_baseline.yml that none of its code reads):
+        # the training loss takes (1 - eps) * onehot + eps / (C + 2) as its target; the dev loss stays the plain one
+        if not 0.0 <= float(label_smoothing_prob) < 1.0:
+            raise ValueError('label_smoothing_prob must be in [0, 1), got %r' % (label_smoothing_prob,))
+        self.label_smoothing_prob = float(label_smoothing_prob)
         # carried weights only exist for the two types that have location features
         self.carry_alpha = prev_alpha == 'carry' and attention_type in AL.HAS_FILTER
         if decoder_type != 'lstm':
@@ -249,7 +255,17 @@ class AttentionSeq2Seq(ModelBase):
 
     # ------------------------------------------------------------------ forward
     def compute_loss(self, inputs, labels, inputs_seq_len, labels_seq_len, keep_prob_encoder,
-                     keep_prob_decoder, keep_prob_embedding, scope=None, is_training=True, **joint):
+                     keep_prob_decoder, keep_prob_embedding, scope=None, is_training=True, scheduled_sampling_prob=0.0,
+                     **joint):
+        """scheduled_sampling_prob (extension keyword, per call so that a recipe can ramp it; a key of the reference's
+        att_baseline.yml that none of its code reads): while training, the token fed at step k >= 1 of a live row is, with
+        this probability, the argmax of the model's own logits of step k - 1 instead of the label -- a constant of the
+        backward pass, as in tf.contrib.seq2seq.ScheduledEmbeddingTrainingHelper.  The decoder then runs the per-step loop
+        ops.att_decoder_fwd_ss; 0, or is_training False, is the teacher-forced path with its launches, untouched."""
+        ss_prob = float(scheduled_sampling_prob)
+        if not 0.0 <= ss_prob <= 1.0:
+            raise ValueError('scheduled_sampling_prob must be in [0, 1], got %r' % (scheduled_sampling_prob,))
+        sample = is_training and ss_prob > 0.0
         dev, st = self.device, self.store
         # nothing below may drain the stream (pageable uploads and device read-backs do): the host has to run ahead of the
         # device for the step to be device-bound -- ops.to_device stages through pinned memory, ops.host_ints remembers
@@ -305,7 +321,10 @@ class AttentionSeq2Seq(ModelBase):
         v = st[AT + 'v_a'] if self.att_mode == 0 else None
         alpha_all = torch.empty((To, Bp, T), dtype=torch.float32, device=dev)   # one slab: d_enc GEMMs read it strided
         use_ddrop = is_training and float(keep_prob_decoder) < 1.0
-        dec_in[:, :, :Em].copy_(emb.view(To, Bp, Em))          # the embedded inputs of all steps at once
+        if sample:         # the loop embeds what it feeds; row 0 is always the label's (<SOS>)
+            dec_in[0, :, :Em].copy_(emb[0])
+        else:
+            dec_in[:, :, :Em].copy_(emb.view(To, Bp, Em))          # the embedded inputs of all steps at once
         dmask_all = None
         if use_ddrop:                                            # one launch for the masks of every step
             self._calls += 1
@@ -337,16 +356,29 @@ class AttentionSeq2Seq(ModelBase):
                     gates_all=torch.empty((To, Bp, 4 * U), dtype=torch.float32, device=dev),
                     craw_all=torch.empty((To, Bp, U), dtype=torch.float32, device=dev), c_all=c_all, h_all=h_all,
                     qz_all=torch.empty((To, Bp, A), dtype=torch.float32, device=dev))
-        ops.att_decoder_fwd(loop)
-        av = ops.tanh_fwd(ops.gemm(av_in.view(To * Bp, U + E2), st[D + 'attentional_vector/weights']))
-        logits2d = ops.gemm(av, st[D + 'output_layer/weights'], bias=st[D + 'output_layer/biases'])
+        if sample:
+            # one launch for the draws of every step; a non-zero entry feeds the model's prediction (rows that have
+            # finished and the padding of the batch tile keep the label's token whatever their draw)
+            self._calls += 1
+            draw = ops.dropout_mask((To, Bp), ss_prob, self.seed + 3, self._calls << 40, dev)
+            av, logits3d, ids_d = ops.att_decoder_fwd_ss(
+                loop, st[D + 'attentional_vector/weights'], st[D + 'output_layer/weights'], st[D + 'output_layer/biases'],
+                st['output_embedding/W_embedding'], ids_d, draw, emb_mask)
+            av, logits2d = av.view(To * Bp, U), logits3d.view(To * Bp, C2)
+            self._ss_last = dict(draw=draw, ids_fed=ids_d)          # (what the step was fed: tests, diagnostics)
+        else:
+            ops.att_decoder_fwd(loop)
+            av = ops.tanh_fwd(ops.gemm(av_in.view(To * Bp, U + E2), st[D + 'attentional_vector/weights']))
+            logits2d = ops.gemm(av, st[D + 'output_layer/weights'], bias=st[D + 'output_layer/biases'])
         logits2d = ops.apply_mask(logits2d, live_d.view(-1, 1).expand(To * Bp, C2).contiguous())  # impute_finished
         inv_t = 1.0 / float(self.logits_temperature)
         lt = ops.scale_(logits2d.clone(), inv_t) if self.logits_temperature != 1.0 else logits2d
         wsum = float(live.sum())
         seq_scale = (1.0 - lam) if lam is not None else 1.0
         row_loss, dlogits = ops.seq_xent(lt, tgt_d.view(-1), live_d.view(-1), 1e-10,
-                                         seq_scale * inv_t / (wsum + 1e-12), want_grad=is_training)
+                                         seq_scale * inv_t / (wsum + 1e-12), want_grad=is_training,
+                                         **(dict(smoothing=self.label_smoothing_prob)
+                                            if (is_training and self.label_smoothing_prob > 0.0) else {}))
         seq_loss = row_loss.sum() / (wsum + 1e-12)
         total = seq_loss
         ctc_logits = None

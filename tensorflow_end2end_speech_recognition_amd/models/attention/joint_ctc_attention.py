@@ -71,12 +71,13 @@ class JointCTCAttention(AttentionSeq2Seq):
             logits_temperature=logits_temperature, name=name, _extra_vars=extra, **kw)
 
     def compute_loss(self, inputs, labels, ctc_labels, inputs_seq_len, labels_seq_len, keep_prob_encoder,
-                     keep_prob_decoder, keep_prob_embedding, scope=None, is_training=True):
-        """:237-346.  Returns (total_loss, logits, ctc_logits [T,B,C+1], dec_out_train, dec_out_infer)."""
+                     keep_prob_decoder, keep_prob_embedding, scope=None, is_training=True, scheduled_sampling_prob=0.0):
+        """:237-346.  Returns (total_loss, logits, ctc_logits [T,B,C+1], dec_out_train, dec_out_infer).
+        scheduled_sampling_prob (extension keyword): as AttentionSeq2Seq.compute_loss; the CTC head is not touched."""
         return super(JointCTCAttention, self).compute_loss(
             inputs, labels, inputs_seq_len, labels_seq_len, keep_prob_encoder, keep_prob_decoder,
-            keep_prob_embedding, scope=scope, is_training=is_training, lambda_weight=self.lambda_weight,
-            ctc_labels=ctc_labels)
+            keep_prob_embedding, scope=scope, is_training=is_training, scheduled_sampling_prob=scheduled_sampling_prob,
+            lambda_weight=self.lambda_weight, ctc_labels=ctc_labels)
 
     def _ctc_head_launch(self, enc, seq_p, ctc_labels, B, lam, is_training):
         """Issue the CTC head (on whatever stream is current -- AttentionSeq2Seq.compute_loss puts it on the side lane);

@@ -2020,6 +2020,57 @@ def att_decoder_fwd(a):
     h.check(h.lib.asr_att_decoder_fwd(h.h, C.byref(st), _s()), 'asr_att_decoder_fwd')
 
 
+class _AttDecoderSS(C.Structure):
+    """struct asr_att_decoder_ss (include/asr_hip.h), field for field."""
+    _fields_ = [('W_av', C.c_void_p), ('W_out', C.c_void_p), ('b_out', C.c_void_p), ('embedding', C.c_void_p),
+                ('C2', C.c_int), ('teacher_ids', C.c_void_p), ('draw', C.c_void_p), ('emb_mask', C.c_void_p),
+                ('av_all', C.c_void_p), ('logits_all', C.c_void_p), ('ids_fed', C.c_void_p)]
+
+
+def att_decoder_fwd_ss(a, W_av, W_out, b_out, embedding, teacher_ids, draw, emb_mask, out=None):
+    """The training loop with scheduled sampling (asr_att_decoder_fwd_ss): `a` as for att_decoder_fwd (row 0 of dec_in
+    filled by the caller), teacher_ids [To,B] int32, draw [To,B] float (non-zero: feed the previous step's argmax where the
+    row is live), emb_mask [To,B,Em] or None.  Returns (av [To,B,U], logits [To,B,C2], ids_fed [To,B] int32), not imputed;
+    the per-step arrays of `a` are filled in place.  out: the three result tensors, when the caller brings its own."""
+    h = _h(a['dec_in'])
+    dev = a['dec_in'].device
+    To, B, U, Em = int(a['To']), int(a['B']), int(a['U']), int(a['Em'])
+    C2 = int(W_out.shape[1])
+    _chk(teacher_ids, torch.int32, 'teacher_ids')
+    _chk(draw, torch.float32, 'draw')
+    if tuple(teacher_ids.shape) != (To, B) or tuple(draw.shape) != (To, B):
+        raise ValueError('att_decoder_fwd_ss: teacher_ids and draw are [To,B] = [%d,%d]' % (To, B))
+    if emb_mask is not None and tuple(emb_mask.shape) != (To, B, Em):
+        raise ValueError('att_decoder_fwd_ss: emb_mask is [To,B,Em] = [%d,%d,%d]' % (To, B, Em))
+    if tuple(W_av.shape) != (U + int(a['E2']), U) or W_out.shape[0] != U or tuple(embedding.shape) != (C2, Em) or \
+            (b_out is not None and tuple(b_out.shape) != (C2,)):
+        raise ValueError('att_decoder_fwd_ss: W_av [U+E2,U], W_out [U,C2], b_out [C2], embedding [C2,Em]')
+    if a.get('work') is None:
+        a['work'] = _f32((B * (5 * U + a['T'] + a['E2']),), dev)
+    _cell_gemm_image(h, a)
+    if out is not None:
+        av, logits, ids_fed = out
+        if tuple(av.shape) != (To, B, U) or tuple(logits.shape) != (To, B, C2) or tuple(ids_fed.shape) != (To, B) or \
+                ids_fed.dtype != torch.int32:
+            raise ValueError('att_decoder_fwd_ss: out is (av [To,B,U], logits [To,B,C2], ids_fed [To,B] int32)')
+    else:
+        av, logits = _f32((To, B, U), dev), _f32((To, B, C2), dev)
+        ids_fed = torch.empty((To, B), dtype=torch.int32, device=dev)
+    ids_fed[0].copy_(teacher_ids[0])
+    st = _att_decoder_struct(a)
+    f = _AttDecoderSS()
+    for n, t in (('W_av', W_av), ('W_out', W_out), ('b_out', b_out), ('embedding', embedding), ('teacher_ids', teacher_ids),
+                 ('draw', draw), ('emb_mask', emb_mask), ('av_all', av), ('logits_all', logits), ('ids_fed', ids_fed)):
+        if t is not None and (not t.is_cuda or not t.is_contiguous()):
+            raise ValueError('att_decoder_fwd_ss: %s must be a contiguous device tensor' % n)
+        if t is not None and n not in ('teacher_ids', 'ids_fed') and t.dtype != torch.float32:
+            raise ValueError('att_decoder_fwd_ss: %s must be float32' % n)
+        setattr(f, n, t.data_ptr() if t is not None else None)
+    f.C2 = C2
+    h.check(h.lib.asr_att_decoder_fwd_ss(h.h, C.byref(st), C.byref(f), _s()), 'asr_att_decoder_fwd_ss')
+    return av, logits, ids_fed
+
+
 def att_decoder_bwd(a):
     """The reverse loop (asr_att_decoder_bwd): fills dctx_all, dpre_all, dqz_all, dv_all, dpeep_all, d_in_all, dc0, dh0
     (and adds into dkeys / the filter gradients)."""
@@ -2816,13 +2867,33 @@ def embedding_scatter(dout, ids, vocab, out):
     return out
 
 
-def seq_xent(logits2d, targets, weights, eps, dscale, want_grad=True):
+def seq_xent(logits2d, targets, weights, eps, dscale, want_grad=True, smoothing=0.0):
+    """smoothing > 0 (label_smoothing_prob): the target is (1 - smoothing) * onehot + smoothing / C (asr_seq_xent_ls);
+    0 is asr_seq_xent, untouched."""
+    if float(smoothing) > 0.0:
+        return seq_xent_ls(logits2d, targets, weights, eps, smoothing, dscale, want_grad=want_grad)
+    if float(smoothing) != 0.0:
+        raise ValueError('smoothing must be in [0, 1), got %r' % (smoothing,))
     h = _h(logits2d)
     rows, Cc = logits2d.shape
     row_loss = _f32((rows,), logits2d.device)
     dl = torch.empty_like(logits2d) if want_grad else None
     h.check(h.lib.asr_seq_xent(h.h, _p(logits2d), _p(targets), _p(weights), rows, Cc, float(eps), float(dscale),
                                _p(row_loss), _p(dl), _s()), 'asr_seq_xent')
+    return row_loss, dl
+
+
+def seq_xent_ls(logits2d, targets, weights, eps, smoothing, dscale, want_grad=True):
+    """asr_seq_xent_ls: the masked sequence cross-entropy against (1 - smoothing) * onehot + smoothing / C, 0 <= smoothing < 1."""
+    smoothing = float(smoothing)
+    if not 0.0 <= smoothing < 1.0:
+        raise ValueError('smoothing must be in [0, 1), got %r' % (smoothing,))
+    h = _h(logits2d)
+    rows, Cc = logits2d.shape
+    row_loss = _f32((rows,), logits2d.device)
+    dl = torch.empty_like(logits2d) if want_grad else None
+    h.check(h.lib.asr_seq_xent_ls(h.h, _p(logits2d), _p(targets), _p(weights), rows, Cc, float(eps), smoothing,
+                                  float(dscale), _p(row_loss), _p(dl), _s()), 'asr_seq_xent_ls')
     return row_loss, dl
 
 
