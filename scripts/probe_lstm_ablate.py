@@ -1,11 +1,14 @@
 #!/usr/bin/env python
-"""Ablation table of the headline recurrence kernels (lstm_{fwd,bwd}_cluster8_kernel<256, ..., 32>): launch time with one
+"""Ablation table of the headline recurrence kernels (lstm_{fwd,bwd}_cluster8_kernel<256, ..., 32>, and
+lstm_fwd_cluster16_kernel when the 16-CU forward form is selected: ASR_LSTM_FWD_HS=16 / 32): launch time with one
 piece of the per-step chain left out at a time (template parameter ABL, library built with ASR_BUILD_ABLATE=1; the ablated
 kernels compute garbage -- only their duration is looked at).  What a piece costs ON the serial chain is the difference to
 the full kernel; the sum of the pieces against the full step shows how much of the step overlaps.
 
     ASR_BUILD_ABLATE=1 python -m tensorflow_end2end_speech_recognition_amd.build --force     # here
     gpurun -- python scripts/probe_lstm_ablate.py > gpurun_out/ablate.txt                        # on the box
+
+ABL_FPIN=1: first a table of the 16-CU forward form's scheduling-barrier masks; ABL_SKIP_BWD=1: forward table only; ABL_ONLY_FPIN=1: the mask table only.
 """
 import os
 import sys
@@ -67,6 +70,23 @@ def name(bits, names):
 
 
 print('T = %d, B = %d, H = %d, ndir = %d; us per launch (median of 12, min), us per recurrence step' % (T, B, H, ndir))
+print('forward form: ASR_LSTM_FWD_HS=%s, ASR_LSTM_DFLAGS=%s' % (os.environ.get('ASR_LSTM_FWD_HS', '(default)'),
+                                                             os.environ.get('ASR_LSTM_DFLAGS', '0')))
+fwd = lambda: ops.lstm_fwd(xproj, whf, peep, sld, H, ndir, ASR_BF16, 1.0, 50.0)
+if os.environ.get('ABL_FPIN') == '1' and H == 256:
+    # scheduling-barrier masks of the 16-CU forward form (ASR_LSTM_FPIN_FWD, ablate builds only); '' = the committed mask
+    print('\n| FPIN mask | us / launch (median) | min |')
+    print('|---|---|---|')
+    for m in ('', '0', '1', '2', '4', '8', '3', '6', '15', '34', '32'):
+        if m:
+            os.environ['ASR_LSTM_FPIN_FWD'] = m
+        else:
+            os.environ.pop('ASR_LSTM_FPIN_FWD', None)
+        med, mn = timed(fwd)
+        print('| %s | %.1f | %.1f |' % (m or 'committed', med, mn))
+    os.environ.pop('ASR_LSTM_FPIN_FWD', None)
+    if os.environ.get('ABL_ONLY_FPIN') == '1':
+        sys.exit(0)
 for label, env, names, variants, fn in (
         ('forward', 'ASR_LSTM_ABL_FWD', FW, (0, 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 6, 14, 48, 513, 515, 519, 527, 545, 769, 800, 1023) if H == 256
          else (0, 1, 8, 16, 64, 512, 6, 513, 519, 527, 545, 1023),
@@ -74,6 +94,8 @@ for label, env, names, variants, fn in (
         ('BPTT', 'ASR_LSTM_ABL_BWD', BW, (0, 1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 6, 14, 80, 144, 513, 515, 519, 527, 545, 641, 1023) if H == 256
          else (0, 1, 8, 64, 512, 6, 513, 519, 527, 545, 641, 1023),
          lambda: ops.lstm_bwd(dout, gates, cs, whb, peep, sld, H, ndir, ASR_BF16))):
+    if label == 'BPTT' and os.environ.get('ABL_SKIP_BWD') == '1':
+        continue
     base = None
     print('\n| %s ABL | left out | us / launch (median) | min | us / step | delta vs full (us / step) |' % label)
     print('|---|---|---|---|---|---|')

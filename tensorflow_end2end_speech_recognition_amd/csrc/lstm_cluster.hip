@@ -628,6 +628,237 @@ __global__ __launch_bounds__(HSU * 8, 1) void lstm_fwd_cluster8_kernel(
 // per launch at H = 256.  A poll round is then 4 waves x 8 KB = 32 KB per CU through a 64 B/clk L2 port (~500 cycles)
 // instead of 8 KB shared through the LDS (128 B/clk): the staging is what keeps the hop short.  Removed again.)
 
+// ---------------------------------------------------------------- forward, H = 256 on 16 CUs x four waves x 4 units
+// The next halving of the forward form above (HSU = 32 -> 16): a wave owns FOUR units, so its whole step is ONE 16-column
+// MFMA tile -- column n = gate (n >> 2) of unit (n & 3) -- over the eight k-chunks (8 MFMAs instead of 16, 32 VGPRs of W_h
+// instead of 64) and the gate math of ONE (row, unit) pair per lane.  After the MFMAs lane (gate q, unit u, row group rg)
+// holds gate q of rows rg*4 .. rg*4+3; a 4 x 4 transpose over the lanes q = 0..3 of a DPP row (bank-masked row_ror:4/8/12
+// moves: the bank mask picks the destination lanes, so the source register is a constant and nothing is selected with
+// v_cndmask) leaves it with all four gates of (row rg*4 + q, unit u).
+// Same bits as the HSU = 32 EARLY form: same operand roles in the MFMA, and the k-chunks of unit j are accumulated from
+// chunk j / 32 upwards, cyclically -- the order that form's own-slice-early trick produces.  A CU's own 16 units are half a
+// k-chunk, so nothing can be multiplied early here: all eight chunks go behind the poll, ONE barrier per step.
+// Exchange: 4-byte self-tagged words (xw_tag), slice of a CU = [16 rows][16 units] bf16 = 512 bytes = 32 16-byte pieces
+// (row, half).  The 16 slices of a cluster -- the CU's own among them, which therefore needs no LDS write of its own -- are
+// 512 pieces: exactly two 16-byte polls per lane and round, wave w taking the whole slices of CUs 4w .. 4w+3, each piece
+// staged with one ds_write_b128.  A pair of lanes (units u, u^1) publishes its word twice (same address, same value):
+// nothing in the step is exec-masked, and the word must go out as ONE 4-byte store to validate itself.
+// Everything else as above: h image XOR-swizzled and double-buffered by step parity, x rows requested two steps ahead,
+// parked positions, saved activations stored behind the poll loop, bounded spins, zero_next_area.  ABL as above (bit 5
+// leaves out the one barrier; there is no own-slice LDS write to ablate).
+template <int FPIN = 0, int ABL = 0>
+__global__ __launch_bounds__(256, 1) void lstm_fwd_cluster16_kernel(
+    int T_, int B_, int ndir, const f32x4_t* __restrict__ xg, const bf16_t* __restrict__ whp,
+    const float* __restrict__ peep, const int32_t* __restrict__ seq_len, float forget_bias,
+    float cell_clip, cbf16x4_t* __restrict__ gates, bf16_t* __restrict__ hout, float* __restrict__ cs,
+    float* __restrict__ c_final, float* __restrict__ h_final, u64* __restrict__ xch,
+    unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords, int tile0, int ntl) {
+  zero_next_area(znext, zwords);
+  constexpr int H = 256, HSU = 16, G = H / HSU, KS = H / 32, LDH = H + 8;
+  constexpr int SLICE = 16 * (HSU / 2);                     // words one CU publishes per step (slot stride as in the forms above)
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  bf16_t* hs = reinterpret_cast<bf16_t*>(smem);            // [2][16][LDH]
+
+  const ClusterId cid = cluster_id<G>(ndir, tile0, ntl);
+  if (!cid.valid) return;
+  const int g = cid.g, d = cid.d, b0 = cid.tile * 16;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int col = lane & 15, rg = lane >> 4;
+  const int q = col >> 2, u = col & 3;                     // gate of this lane's MFMA column, unit inside the wave
+  const bool odd = (u & 1) != 0;
+  const bool rev = (d == 1);
+  const bf16_t* wp = whp + (size_t)d * H * 4 * H;
+  const unsigned jw = g * HSU + wave * 4 + u;              // global unit of this lane
+  const int row = rg * 4 + q;                              // this lane's batch row
+
+  const int len = seq_len[b0 + row];
+  int tmax = 0;
+  for (int i = 0; i < 16; ++i) tmax = max(tmax, seq_len[b0 + i]);
+  tmax = min(tmax, T_);
+
+  float c = 0.f, hr = 0.f;
+  const float wci = peep ? peep[(d * 3 + 0) * H + jw] : 0.f;
+  const float wcf = peep ? peep[(d * 3 + 1) * H + jw] : 0.f;
+  const float wco = peep ? peep[(d * 3 + 2) * H + jw] : 0.f;
+
+  for (int i = threadIdx.x; i < 2 * 16 * LDH; i += 256) hs[i] = 0;
+  // B fragments out of the standard forward packing (tile = (unit/16)*4 + gate, column unit%16): this lane's column is
+  // (gate q, unit jw); register chunk ks holds k-chunk (ks + jw/32) % 8 -- the accumulation order of the HSU = 32 form
+  bf16x8_t wreg[KS];
+  const int k0 = g >> 1;
+  {
+    const int tile = (jw >> 4) * 4 + q;
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      const int kk = (ks + k0) & (KS - 1);
+      wreg[ks] = *reinterpret_cast<const bf16x8_t*>(wp + (((size_t)tile * KS + kk) * 64 + rg * 16 + (jw & 15)) * 8);
+    }
+  }
+
+  u64* xhdr = xch + (size_t)cid.c * (XHDR + 2 * G * SLICE);
+  u64* xbase = xhdr + XHDR;                                // as words: [2 parity][G][16 rows][8 words]
+  bool timed_out = false;
+  const bool colocated = same_xcd<G>(xhdr, g, timed_out);
+  const bool fast = colocated && !(kflags & 1);            // same decision on every member
+  unsigned spin_limit = (kflags & 2) ? 2000u : SPIN_LIMIT; // after the first timeout the limit drops to 0
+  if ((kflags & 2) && g == G - 1) return;                  // TEST ONLY (ASR_LSTM_DFLAGS bit 6): a member goes missing
+  __syncthreads();
+
+  const unsigned stride = (unsigned)B_ * ndir * H;
+  const unsigned dstep = rev ? 0u - stride : stride;
+  unsigned os = ((unsigned)(b0 + row) * ndir + d) * H + jw;                    // frame s of this (row, unit)
+  unsigned oa = os + (rev ? (unsigned)max(len - 1, 0) * stride : 0u);          // frame of the running step of an active row
+  const unsigned opark = os + (unsigned)max(tmax - 1, 0) * stride;             // parked position (see the form above)
+  const unsigned pofs = (unsigned)(row * 8 + wave * 2 + (u >> 1));             // publish word in the slice
+  unsigned* xw = reinterpret_cast<unsigned*>(xbase);
+  const __amdgpu_buffer_rsrc_t xwrs = __builtin_amdgcn_make_buffer_rsrc(xw, 0, 0x7fffffff, 0x00020000);
+  // poll j of a lane: piece lane % 32 = (row, half) of the slice of CU wave * 4 + j * 2 + lane / 32
+  unsigned xvoff[2], xldst[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int gsrc = wave * 4 + j * 2 + (lane >> 5), pc = lane & 31, prow = pc >> 1;
+    xvoff[j] = (unsigned)(gsrc * SLICE + pc * 4) * 4u;
+    // the image is rotated by the CU's first k-chunk, so that register chunk ks reads LDS chunk ks at a constant offset
+    xldst[j] = ((unsigned)(prow * LDH + ((gsrc * HSU + (pc & 1) * 8 - k0 * 32) & (H - 1))) * 2u) ^ lds_swz(prow);
+  }
+  const unsigned lrd = ((unsigned)(col * LDH + rg * 8) * 2u) ^ lds_swz(col);
+
+  f32x4_t xq[2];                                           // xproj rows of the running step, requested TWO steps ahead
+  xq[0] = xg[(0 < len) ? oa : opark];
+  xq[1] = (tmax > 1) ? xg[(1 < len) ? oa + dstep : opark] : xq[0];
+
+  unsigned nonfin = 0;                                     // OR of every published pair (see the tail of the form above)
+#define C16_FPIN(k) do { if constexpr ((FPIN >> (k)) & 1) __builtin_amdgcn_sched_barrier(0); } while (0)
+#define C16_G(v, QP, Q) v = __builtin_amdgcn_update_dpp(v, __float_as_int(acc[Q]), /* (no bit_cast of a vector element) */ \
+                                                        (QP) == (Q) ? 0xE4 : 0x120 + 4 * (((Q) - (QP)) & 3), 0xF, 1 << (Q), false)
+#define C16_GATE(name, QP) float name; { int v_ = 0; C16_G(v_, QP, 0); C16_G(v_, QP, 1); C16_G(v_, QP, 2); C16_G(v_, QP, 3); \
+                                         name = __builtin_bit_cast(float, v_); }
+
+  auto step = [&](int s, auto PAR) {
+    constexpr int P = decltype(PAR)::value;                // parity of step s
+    C16_FPIN(0);
+    const char* hcur = smem + P * 16 * LDH * 2;
+    char* hnxt = smem + (1 - P) * 16 * LDH * 2;
+    const f32x4_t x0 = xq[P];
+    if (s + 2 < tmax && !(ABL & 64)) xq[P] = xg[(s + 2 < len) ? oa + 2u * dstep : opark];   // lands during the next steps
+    f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+    bf16x8_t afr[KS];                                      // all eight A fragments in flight at once
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      if constexpr ((ABL & 2) != 0) afr[ks] = wreg[ks ^ 1];
+      else afr[ks] = *reinterpret_cast<const bf16x8_t*>(hcur + lrd + ks * 64);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      if constexpr ((ABL & 4) != 0) {                       // keeps the dependence on every fragment, nothing else
+        const xw4_t fb = __builtin_bit_cast(xw4_t, afr[ks]);
+        acc[0] = __uint_as_float(__float_as_uint(acc[0]) ^ (fb[0] & 1u));
+        continue;
+      }
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(afr[ks], wreg[ks], acc, 0, 0, 0);
+    }
+    C16_FPIN(1);
+    // 4 x 4 transpose over the lanes q = 0..3: gate q' of (row rg*4 + q, unit u) is acc[q] of lane (q', u, rg)
+    C16_GATE(pi, 0) C16_GATE(pq, 1) C16_GATE(pf, 2) C16_GATE(po, 3)
+    C16_FPIN(4);                                           // behind the DPP transpose
+    const bool act = s < len;
+    float ig, gg, fg, og, cn, hn;
+    if constexpr ((ABL & 8) != 0) {
+      ig = pi + x0[0]; gg = pq + x0[1]; fg = pf + x0[2]; og = po + x0[3];
+      cn = c;
+      hn = fminf(fmaxf((ig + gg) + (fg + og), -1.f), 1.f);
+    } else {
+      ig = cfsig(pi + x0[0] + wci * c);
+      gg = cftanh(pq + x0[1]);
+      fg = cfsig(pf + x0[2] + forget_bias + wcf * c);
+      cn = gg * ig + c * fg;
+      if (cell_clip > 0.f) cn = fminf(fmaxf(cn, -cell_clip), cell_clip);
+      og = cfsig(po + x0[3] + wco * cn);
+      hn = cftanh(cn) * og;
+    }
+    c = act ? cn : c;
+    hr = act ? hn : hr;
+    C16_FPIN(5);                                           // behind the gate math
+    // publish: both lanes of a pair the (even unit, odd unit) word of their row
+    const unsigned hb = f32_to_bf16(hr);
+    const unsigned nb = (unsigned)__builtin_amdgcn_update_dpp(0, (int)hb, 0xB1, 0xF, 0xF, false);
+    const unsigned pk = odd ? (nb | (hb << 16)) : (hb | (nb << 16));
+    const unsigned etag = xw_tag(s);
+    if constexpr ((ABL & 128) == 0) {
+      unsigned* pw = uoff(xw + (size_t)(P * G + g) * SLICE, pofs);
+      nonfin |= pk;
+      const unsigned tv = (pk & ~XW_MASK) | etag;
+      if (fast) __hip_atomic_store(pw, tv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // plain store, stays in the L2
+      else __hip_atomic_store(pw, tv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    C16_FPIN(6);                                           // behind the publish
+    const unsigned off = act ? oa : os, offg = act ? oa : opark;   // hout position / saved-activation position
+    oa += dstep;
+    os += stride;
+    C16_FPIN(2);
+    {
+      __builtin_amdgcn_sched_barrier(0);
+      constexpr unsigned pbytes = (unsigned)P * G * SLICE * 4u;   // this parity's slices
+      xw4_t v[2];
+      unsigned spins = 0;
+#pragma unroll 1
+      for (;;) {                                           // wave-uniform loop: no exec masking
+        asm volatile("" ::: "memory");                     // every round is a fresh set of loads
+        if constexpr ((ABL & 512) != 0) {
+          v[0] = v[1] = (xw4_t){pk, pk, pk, pk};
+          break;
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j)                         // L1-bypassing (sc1) 16-byte loads
+          v[j] = __builtin_amdgcn_raw_buffer_load_b128(xwrs, xvoff[j], pbytes, 16);
+        unsigned bad = 0;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          v[j] ^= etag;                                    // tag bits clear exactly where the word is this step's
+          bad |= v[j][0] | v[j][1] | v[j][2] | v[j][3];
+        }
+        if (__all((bad & XW_MASK) == 0u)) break;
+        if constexpr ((ABL & 1) != 0) break;                // one round, whatever it carries
+        if (++spins > spin_limit) { timed_out = true; spin_limit = 0; break; }
+      }
+      C16_FPIN(7);                                         // behind the poll loop
+      if constexpr ((ABL & 256) != 0) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) asm volatile("" ::"v"(v[j]));
+      } else {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) *reinterpret_cast<xw4_t*>(hnxt + xldst[j]) = v[j];
+      }
+      C16_FPIN(8);                                         // behind the LDS staging
+    }
+    // saved activations behind the poll loop (loads and stores share one in-order counter, see the form above)
+    if constexpr (!(ABL & 16)) {
+      hout[off] = act ? (bf16_t)hb : (bf16_t)0;
+      gates[offg] = (cbf16x4_t){(__bf16)ig, (__bf16)gg, (__bf16)fg, (__bf16)og};
+      cs[offg] = cn;
+    }
+    C16_FPIN(3);
+    if constexpr (!(ABL & 32)) __syncthreads();
+  };
+  int s = 0;
+  for (; s + 1 < tmax; s += 2) {
+    step(s, std::integral_constant<int, 0>{});
+    step(s + 1, std::integral_constant<int, 1>{});
+  }
+  if (s < tmax) step(s, std::integral_constant<int, 0>{});
+#undef C16_FPIN
+#undef C16_G
+#undef C16_GATE
+
+  if (timed_out) atomicOr(err, 1u);
+  if (nonfin & XW_MASK) atomicOr(err, 4u);                 // a non-finite h must not be laundered by the forced tag bits
+  for (int t = tmax; t < T_; ++t) { hout[os] = 0; os += stride; }   // common padded tail: os points at frame tmax
+  const size_t o = ((size_t)d * B_ + b0 + row) * H + jw;
+  if (c_final) c_final[o] = c;
+  if (h_final) h_final[o] = hr;
+}
+
 // ---------------------------------------------------------------- backward
 // K-partition: CU g owns the gate gradients of its 64 units (k' = unit*4+q in its slice) and the
 // rows k' of W_h^T; each step it multiplies its dG slice by W_h^T[k' slice, all H] -> a partial
@@ -3101,6 +3332,7 @@ static int g_dflags = -1;
 // bit 10 (1024): forward all-gather with 8-byte {step, payload} granules instead of 4-byte self-tagged words (A/B, tests)
 // bit 11 (2048): inverts the default choice of the BPTT reduce-scatter slot layout (consumer-major source pairs, XP) (A/B, tests)
 // bit 12 (4096): fp32 operands on the exact-fp32 MFMA kernels instead of the three-term bf16 split (A/B, tests)
+// bit 13 (8192): inverts the choice between the 16-CU and the 8-CU forward form at H = 256 (A/B, tests)
 // bit 6 (64): TEST ONLY -- the last member of every cluster leaves right after the placement handshake and the
 //             spin limit drops to 2000 polls, so every hand-off times out (tests/test_gpu_ops.py checks that the
 //             error word is raised and surfaces as an exception)
@@ -3229,13 +3461,23 @@ extern "C" int asr_reset_recurrence_path_counts(asr_handle* h) {
 // 64 (H/64 CUs with eight waves; ASR_LSTM_HS=64, ASR_LSTM_FWD_HS / ASR_LSTM_BWD_HS for one pass only, or
 // ASR_LSTM_DFLAGS bit 9 at run time -- the tests run both).  Measured (profiles/r03_cluster_hs32.md): forward
 // 907 -> 866 us and BPTT 953 -> 929 us per launch at H = 256 (T = 778), 1791 -> 1374 and 2354 -> 1833 us at H = 512.
-static int units_per_cu(const char* specific) {
+// The bf16 forward at H = 256 has a third form, 16 units per CU (lstm_fwd_cluster16_kernel: 16 CUs x four waves x 4 units).
+// FWD_HS16_DEFAULT says whether it is the default there; ASR_LSTM_FWD_HS=16 / 32 / 64 picks a form, ASR_LSTM_DFLAGS bit 13
+// inverts the choice between 16 and 32 at run time (tests, A/B).  Every other kernel reads 16 as 32.  Measured
+// (profiles/r10_fwd_cu16.md): forward launch 694 -> 622 us at T = 745, B = 16, headline step 8.63 -> 8.34 ms, same bits.
+static constexpr bool FWD_HS16_DEFAULT = true;
+static int units_per_cu(const char* specific, bool allow16 = false) {
   if (dbg_flags() & 512) return 64;
   const char* e = getenv(specific);
   if (!e) e = getenv("ASR_LSTM_HS");
-  return (e && atoi(e) == 64) ? 64 : 32;
+  const int v = e ? atoi(e) : 0;
+  if (v == 64) return 64;
+  if (!allow16) return 32;
+  const bool cu16 = e ? v == 16 : FWD_HS16_DEFAULT;
+  return (cu16 != ((dbg_flags() & 8192) != 0)) ? 16 : 32;
 }
 static int fwd_units_per_cu() { return units_per_cu("ASR_LSTM_FWD_HS"); }
+static int fwd256_units_per_cu() { return units_per_cu("ASR_LSTM_FWD_HS", true); }
 // forward all-gather word format: 4-byte self-tagged words unless ASR_LSTM_XW=0 or ASR_LSTM_DFLAGS bit 10 (run time, tests)
 static bool fwd_xw_enabled() {
   static const bool on = [] { const char* e = getenv("ASR_LSTM_XW"); return !(e && e[0] == '0'); }();
@@ -3320,6 +3562,55 @@ static bool cluster_fwd_launch(asr_handle* h, int T, int B, int ndir, const floa
   return true;
 }
 
+// H = 256 on clusters of 16 CUs x four waves x 4 units (lstm_fwd_cluster16_kernel).  4-byte exchange words only: with
+// ASR_LSTM_XW=0 / flag bit 10, or the phase timers on, the caller goes on to the 32-unit form.
+static bool cluster_fwd16_launch(asr_handle* h, int T, int B, int ndir, const float* xproj, const void* whp,
+                                 const float* peep, const int32_t* seq_len, float fb, float clip, void* gates,
+                                 void* hout, float* cs, float* cf, float* hf, hipStream_t st, bool grouped) {
+  constexpr int H = 256, HSU = 16, G = H / HSU;
+  static_assert(G <= XHDR, "placement header too small");
+  constexpr size_t cl_bytes = (XHDR + 2 * G * 16 * (HSU / 2)) * sizeof(u64);
+  if (!fwd_xw_enabled() || g_cdbg_host) return false;
+  if ((size_t)T * B * ndir * H >= (1ull << 31) || h->scratch_bytes < XCH_BYTES) return false;
+  const TilePlan plan = cluster_launch_plan(h, G, ndir, B, cl_bytes, grouped);   // every member of a launch must be resident at once
+  if (!plan.n) return false;
+  char* base = (char*)h->scratch + (h->scratch_bytes - XCH_BYTES);
+  // scheduling-barrier mask (FPIN, the points of the forms above), searched over the same eight masks as the 8-CU form; us
+  // per launch at T = 745, B = 16, two directions, two passes (median of 12 launches each): none 621 / 621, {0} 617 / 620,
+  // {1} 626 / 628, {2} 619 / 620, {3} 622 / 623, {0,1} 627 / 625, {1,2} 625 / 624, all four 630 / 628; also {5} 620 / 616 and
+  // the 8-CU form's {1,5} 623 / 622.  The barrier between the MFMAs and the gate math (bit 1), which that form gains 29 us
+  // from, costs this one 4 - 8 us wherever it appears; the masks without it lie within the 5 us the passes differ by.
+  // {0} (nothing moves across the step boundary) is kept: profiles/r10_fwd_cu16.md.
+  auto k = lstm_fwd_cluster16_kernel<1>;
+#ifdef ASR_LSTM_ABLATE
+  // scripts/probe_lstm_ablate.py: ASR_LSTM_FPIN_FWD picks one of the searched masks, ASR_LSTM_ABL_FWD an ablated build
+  if (const char* e = getenv("ASR_LSTM_FPIN_FWD")) {
+    switch (atoi(e)) {
+#define FPINF(n) case n: k = lstm_fwd_cluster16_kernel<n>; break;
+      FPINF(0) FPINF(1) FPINF(2) FPINF(4) FPINF(8) FPINF(3) FPINF(6) FPINF(15) FPINF(34) FPINF(32)
+#undef FPINF
+      default: break;
+    }
+  }
+  if (const char* e = getenv("ASR_LSTM_ABL_FWD")) {
+    switch (atoi(e)) {
+#define ABLF(n) case n: k = lstm_fwd_cluster16_kernel<1, n>; break;
+      ABLF(1) ABLF(2) ABLF(4) ABLF(8) ABLF(16) ABLF(32) ABLF(64) ABLF(128) ABLF(256) ABLF(512)
+      ABLF(513) ABLF(515) ABLF(519) ABLF(527) ABLF(545) ABLF(769) ABLF(1023) ABLF(6) ABLF(14) ABLF(48) ABLF(800)
+#undef ABLF
+      default: break;
+    }
+  }
+#endif
+  const size_t lds = (size_t)2 * 16 * (H + 8) * 2;
+  run_tile_groups(h, base, plan, B, ndir, cl_bytes, st, 0, [&](const XchAreas& xa, int ncl, int t0, int nt) {
+    hipLaunchKernelGGL(k, dim3(cluster_grid(G, ncl)), dim3(256), lds, st, T, B, ndir,
+                       (const f32x4_t*)xproj, (const bf16_t*)whp, peep, seq_len, fb, clip, (cbf16x4_t*)gates,
+                       (bf16_t*)hout, cs, cf, hf, xa.area, (unsigned*)base, kernel_flags(), xa.znext, xa.zwords, t0, nt);
+  });
+  return true;
+}
+
 bool asr_cluster_fwd_try(asr_handle* h, int T, int B, int H, int ndir, const float* xproj,
                          const void* whp, const float* peep, const int32_t* seq_len, float fb,
                          float clip, void* gates, void* hout, float* cs, float* cf, float* hf,
@@ -3329,6 +3620,10 @@ bool asr_cluster_fwd_try(asr_handle* h, int T, int B, int H, int ndir, const flo
   // first every form as ONE launch, in the order of preference; tile groups only when no form fits in one launch
   auto attempt = [&](bool grouped) -> bool {
     if (H == 320) return cluster_fwd_launch<320>(h, T, B, ndir, xproj, whp, peep, seq_len, fb, clip, gates, hout, cs, cf, hf, st, grouped);
+    // H = 256: the 16-CU form when it fits in one launch (a batch of more tiles runs as tile groups of the 32-unit form)
+    if (H == 256 && !grouped && fwd256_units_per_cu() == 16 &&
+        cluster_fwd16_launch(h, T, B, ndir, xproj, whp, peep, seq_len, fb, clip, gates, hout, cs, cf, hf, st, false))
+      return true;
     if (fwd_units_per_cu() == 32) {
       const bool ok = H == 512
           ? cluster_fwd_launch<512, 32>(h, T, B, ndir, xproj, whp, peep, seq_len, fb, clip, gates, hout, cs, cf, hf, st, grouped)
