@@ -56,7 +56,9 @@ def model_kwargs(params):
         logits_temperature=params['logits_temperature'], sigmoid_smoothing=params['sigmoid_smoothing'],
         dtype=params.get('dtype', 'f32'), device=params.get('device', 'cuda:0'),
         subsample_list=params.get('subsample_list'), subsample_type=params.get('subsample_type', 'drop'),
-        label_smoothing_prob=float(params.get('label_smoothing_prob') or 0.0))
+        label_smoothing_prob=float(params.get('label_smoothing_prob') or 0.0),
+        encoder_residual=bool(params.get('encoder_residual', False)),
+        encoder_dense_residual=bool(params.get('encoder_dense_residual', False)))
 
 
 def scheduled_sampling_prob(params, step):
@@ -89,6 +91,10 @@ def run_name(params):
         name += '_temp' + str(params['logits_temperature'])
     if params.get('subsample_list') and any(params['subsample_list']):
         name += '_sub' + params.get('subsample_type', 'drop') + str(sum(bool(f) for f in params['subsample_list']))
+    if params.get('encoder_residual'):
+        name += '_res'
+    elif params.get('encoder_dense_residual'):
+        name += '_dres'
     if params.get('scheduled_sampling_prob'):
         name += '_ss' + str(params['scheduled_sampling_prob'])
     if params.get('label_smoothing_prob'):

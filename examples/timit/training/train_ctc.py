@@ -167,7 +167,9 @@ def build_model(params):
                 clip_grad_norm=params['clip_grad_norm'], clip_activation=params['clip_activation'],
                 num_proj=params['num_proj'], weight_decay=params['weight_decay'],
                 dtype=params.get('dtype', 'bf16'), device=params.get('device', 'cuda:0'),
-                subsample_list=params.get('subsample_list'), subsample_type=params.get('subsample_type', 'drop'))
+                subsample_list=params.get('subsample_list'), subsample_type=params.get('subsample_type', 'drop'),
+                encoder_residual=bool(params.get('encoder_residual', False)),
+                encoder_dense_residual=bool(params.get('encoder_dense_residual', False)))
     # run-directory name, as :338-351
     model.name += '_' + str(params['num_units'])
     model.name += '_' + str(params['num_layers'])
@@ -183,6 +185,10 @@ def build_model(params):
         model.name += '_wd' + str(params['weight_decay'])
     if any(model.subsample_list):
         model.name += '_sub' + model.subsample_type + str(sum(model.subsample_list))
+    if params.get('encoder_residual'):
+        model.name += '_res'
+    elif params.get('encoder_dense_residual'):
+        model.name += '_dres'
     return model
 
 

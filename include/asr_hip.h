@@ -113,6 +113,25 @@ int asr_time_subsample_fwd(asr_handle* h, int dtype, int type, const void* x_tb,
  * t' < len_out[b], zero everywhere else.  dy is never read at t' >= len_out[b]. */
 int asr_time_subsample_bwd(asr_handle* h, int type, const float* dy_tb, const int32_t* len_out, int T, int Bp, int W,
                            float* dx_tb, asr_stream s);
+/* Skip connections between two recurrent layers (later within ABI 5; encoder_residual / encoder_dense_residual of
+ * config/ctc/encoders/residual_blstm_ctc.yml, dense_residual_blstm_ctc.yml, config/attention/encoders/
+ * att_residual_blstm_location.yml, att_dense_residual_blstm_location.yml -- keys none of the reference's code reads; the
+ * semantics are fixed in models/encoders/core/residual.py).  All tensors time-major [T,Bp,W]; seq_len[Bp] is clamped to
+ * [0,T]; at t >= seq_len[b] nothing is loaded and every output is zero.  (keep_prob, seed, offset): the dropout mask
+ * asr_dropout_mask would write for the [T,Bp,W] tensor with those arguments (element e: word e % 4 of the block at
+ * offset + e / 4), formed in the kernel; keep_prob = 1: no dropout.
+ * Forward: out = round_dtype(fl32(fl32(m * h) + skip)) with h, out in `dtype` and skip in skip_dtype (dtype or ASR_F32);
+ * sum_out (nullable, fp32) = fl32(skip + out as stored) -- the running sum of the dense form; it may be `skip` itself when
+ * that is fp32 (updated in place).  T == 0 or Bp == 0: nothing is launched. */
+int asr_residual_fwd(asr_handle* h, int dtype, int skip_dtype, const void* h_tb, const void* skip,
+                     const int32_t* seq_len, int T, int Bp, int W, float keep_prob, uint64_t seed, uint64_t offset,
+                     void* out, float* sum_out, asr_stream s);
+/* Backward (all fp32): g = fl32(dx_raw + carry); dout = fl32(m * g), what the layer's BPTT takes as its already-masked
+ * output gradient; carry_out = g, or fl32(g + carry) with dense != 0 -- the un-masked gradient that travels further
+ * down.  dout may be dx_raw and carry_out may be carry.  dx_raw may be unwritten memory at padded frames. */
+int asr_residual_bwd(asr_handle* h, const float* dx_raw, const float* carry, const int32_t* seq_len, int T, int Bp,
+                     int W, float keep_prob, uint64_t seed, uint64_t offset, int dense, float* dout, float* carry_out,
+                     asr_stream s);
 /* out[c*ld_out + r] = in[r*ld_in + c] for an [rows, cols] matrix in `dtype` (LDS-tiled, both
  * sides coalesced).  The MFMA GEMM wants both operands reduction-contiguous; the k-major ones
  * (W_x as stored by TF: [Din, 4H], models/encoders/core/blstm.py:286-320 via LSTMBlockCell's

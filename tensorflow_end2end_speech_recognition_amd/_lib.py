@@ -187,6 +187,9 @@ SIGNATURES = {
     # time subsampling between recurrent layers (later within ABI 5)
     'asr_time_subsample_fwd': (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'asr_time_subsample_bwd': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    # skip connections between recurrent layers (later within ABI 5)
+    'asr_residual_fwd': (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _f, _u64, _u64, _vp, _vp, _vp]),
+    'asr_residual_bwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _u64, _u64, _i, _vp, _vp, _vp]),
     # scheduled sampling in the training loop, label-smoothed sequence loss (later within ABI 5)
     'asr_att_decoder_fwd_ss': (_i, [_vp, _vp, _vp, _vp]),
     'asr_seq_xent_ls': (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp]),

@@ -23,7 +23,9 @@ FLAGS = ['--offload-arch=%s' % ARCH, '-O3', '-std=c++17', '-fPIC', '-Wno-unused-
 # memory latency on the serial chain); without it the loads stay 8 frames ahead of their use
 # lstm_cluster.hip: MFMA results in VGPRs (the default picks AGPR accumulators for the 4-wave kernels, whose gate math then
 # starts with 12 v_accvgpr_read per step on the serial chain)
-FILE_FLAGS = {'ctc.hip': ['-fno-slp-vectorize'], 'lstm_cluster.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form']}
+# residual.hip: m * h + skip and dx + carry are held bit for bit to a numpy statement that rounds after the multiply
+FILE_FLAGS = {'ctc.hip': ['-fno-slp-vectorize'], 'lstm_cluster.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form'],
+              'residual.hip': ['-ffp-contract=off']}
 # ASR_BUILD_ABLATE=1: the ablated instantiations of the headline recurrence kernels (scripts/probe_lstm_ablate.py); never
 # part of a shipped library -- the default kernels' ISA is identical with and without it
 if os.environ.get('ASR_BUILD_ABLATE') == '1':

@@ -30,6 +30,7 @@ from ..._lib import ASR_BF16, ASR_F32
 from ...utils.evaluation.edit_distance import compute_ler as _ler
 from ...utils.parameter import ParamStore
 from ..ctc.ctc import Placeholder, truncated_normal
+from ..encoders.core.residual import check_residual, load_residual
 from ..encoders.core.subsample import check_subsample, load_subsampled, shift_lengths
 from ..encoders.load_encoder import load as load_encoder
 from ..model_base import ModelBase
@@ -59,7 +60,7 @@ class AttentionSeq2Seq(ModelBase):
                  weight_decay=0.0, time_major=True, sharpening_factor=1.0, logits_temperature=1.0,
                  sigmoid_smoothing=False, name='attention', dtype='f32', device='cuda:0', seed=0,
                  _extra_vars=None, prev_alpha='zeros', subsample_list=None, subsample_type='drop',
-                 label_smoothing_prob=0.0):
+                 label_smoothing_prob=0.0, encoder_residual=False, encoder_dense_residual=False):
         super(AttentionSeq2Seq, self).__init__()
         assert input_size % 3 == 0, 'input_size must be divisible by 3 (+ delta, double delta features).'
         assert splice % 2 == 1, 'splice must be the odd number'
@@ -122,9 +123,20 @@ class AttentionSeq2Seq(ModelBase):
         enc_kw = dict(num_units=encoder_num_units, num_proj=None, num_layers=encoder_num_layers, lstm_impl=lstm_impl,
                       use_peephole=use_peephole, parameter_init=parameter_init, clip_activation=clip_activation_encoder,
                       time_major=True, dtype=self.dtype)
+        # encoder_residual / encoder_dense_residual (extension keywords): skip connections between the encoder's layers
+        # (models/encoders/core/residual.py); both false, or fewer than two layers, builds exactly the plain encoder
+        self.encoder_skip = check_residual(encoder_residual, encoder_dense_residual)
+        if self.encoder_skip is not None:
+            load_residual(encoder_type)
+            if any(self.subsample_list):
+                raise ValueError('skip connections join layers of one frame rate: not with a true subsample_list entry')
+            if encoder_num_layers < 2:
+                self.encoder_skip = None
         if any(self.subsample_list):
             self.encoder = load_subsampled(encoder_type)(subsample_list=self.subsample_list,
                                                          subsample_type=self.subsample_type, **enc_kw)
+        elif self.encoder_skip is not None:
+            self.encoder = load_residual(encoder_type)(dense=self.encoder_skip == 'dense', **enc_kw)
         else:
             self.encoder = load_encoder(encoder_type)(**enc_kw)
         E2 = self.enc_dim = self.encoder.build(st, input_size * splice, rng, scope_prefix='encoder/')

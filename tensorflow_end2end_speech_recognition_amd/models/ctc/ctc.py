@@ -19,6 +19,7 @@ from ..._lib import ASR_BF16, ASR_F32
 from ...utils.io.labels.sparsetensor import dense_to_flat, sparse_to_flat
 from ...utils.evaluation.edit_distance import compute_ler as _ler
 from ...utils.parameter import ParamStore
+from ..encoders.core.residual import check_residual, load_residual
 from ..encoders.core.subsample import check_subsample, load_subsampled, shift_lengths
 from ..encoders.load_encoder import load
 from ..model_base import ModelBase
@@ -70,7 +71,9 @@ class CTC(ModelBase):
     Extra keyword arguments of the HIP build (not in the reference): `dtype` ('f32' exact
     fp32 MFMA path | 'bf16' operands with fp32 accumulate), `device`, `seed`; `subsample_list` / `subsample_type`
     (time subsampling inside the blstm / lstm encoders, models/encoders/core/subsample.py -- the logits then have
-    T >> k frames and decoder() takes output_seq_len(inputs_seq_len); None or all false: the plain encoder).
+    T >> k frames and decoder() takes output_seq_len(inputs_seq_len); None or all false: the plain encoder);
+    `encoder_residual` / `encoder_dense_residual` (skip connections between the layers of the blstm / lstm encoders,
+    models/encoders/core/residual.py; both false: the plain encoder).
     """
     head_scope = 'output'      # variable scope of the output FC (ctc.py:216-224)
 
@@ -78,7 +81,8 @@ class CTC(ModelBase):
                  lstm_impl='LSTMBlockCell', use_peephole=True, splice=1, num_stack=1,
                  parameter_init=0.1, clip_grad_norm=None, clip_activation=None, num_proj=None,
                  weight_decay=0.0, bottleneck_dim=None, time_major=True,
-                 dtype='f32', device='cuda:0', seed=0, subsample_list=None, subsample_type='drop'):
+                 dtype='f32', device='cuda:0', seed=0, subsample_list=None, subsample_type='drop',
+                 encoder_residual=False, encoder_dense_residual=False):
         super(CTC, self).__init__()
         assert input_size % 3 == 0, 'input_size must be divisible by 3 (+ delta, acceleration coefficients).'
         assert splice % 2 == 1, 'splice must be the odd number'
@@ -125,6 +129,13 @@ class CTC(ModelBase):
         self.subsample_type = subsample_type
         if any(self.subsample_list):
             load_subsampled(encoder_type)                # ValueError for the families that have no subsampled form
+        self.encoder_skip = check_residual(encoder_residual, encoder_dense_residual)   # None | 'residual' | 'dense'
+        if self.encoder_skip is not None:
+            load_residual(encoder_type)                  # ValueError for the families that have no skip connections
+            if any(self.subsample_list):
+                raise ValueError('skip connections join layers of one frame rate: not with a true subsample_list entry')
+            if num_layers < 2:
+                self.encoder_skip = None                 # nothing to connect: the plain encoder
 
         self.encoder = self._create_encoder(encoder_type, input_size, splice, num_stack, num_units, num_layers,
                                             lstm_impl, use_peephole, parameter_init, clip_activation)
@@ -150,6 +161,12 @@ class CTC(ModelBase):
                     lstm_impl=lstm_impl, use_peephole=use_peephole, parameter_init=parameter_init,
                     clip_activation=clip_activation, time_major=True, dtype=self._requested_dtype,
                     subsample_list=self.subsample_list, subsample_type=self.subsample_type)
+            if self.encoder_skip is not None:
+                return load_residual(encoder_type)(
+                    num_units=num_units, num_proj=self.num_proj, num_layers=num_layers,
+                    lstm_impl=lstm_impl, use_peephole=use_peephole, parameter_init=parameter_init,
+                    clip_activation=clip_activation, time_major=True, dtype=self._requested_dtype,
+                    dense=self.encoder_skip == 'dense')
             return load(encoder_type)(
                 num_units=num_units, num_proj=self.num_proj, num_layers=num_layers,
                 lstm_impl=lstm_impl, use_peephole=use_peephole, parameter_init=parameter_init,

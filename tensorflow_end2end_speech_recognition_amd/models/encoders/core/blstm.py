@@ -214,14 +214,25 @@ class _RecurrentEncoderBase(object):
             defer = top and self.defer_top_dropout and self.num_layers_sub is None and (mk is None or isinstance(mk, tuple))
             x, final = layer.forward(x, seq_len, self.dtype, keep_prob, is_training, prep=preps[li],
                                      mask_event=ready_m[li], rows=self._rows[0] if self._rows else None,
-                                     defer_mask=defer)
+                                     defer_mask=defer or self._connects(li))
             if defer:
                 self._top_deferred, self._top_drop = True, mk
+            x = self._connect(li, x, mk, seq_len)
             finals.append(final)
             if self.num_layers_sub is not None and li + 1 == self.num_layers_sub:
                 # blstm.py:326-328: outputs_sub IS the tensor the next layer consumes (after the dropout wrapper)
                 self._out_sub_op, self._final_sub_ch = x, final
         return self._finish_call(x, finals, seq_len, B)
+
+    # the two places where the encoders with skip connections (residual.py) differ in the forward loop; the plain
+    # stack has none
+    def _connects(self, li):
+        """Whether a skip connection ends behind layer li (its consumer then applies a dropout descriptor itself)."""
+        return False
+
+    def _connect(self, li, x, mask, seq_len):
+        """What the layer above consumes, from layer li's output x."""
+        return x
 
     def _finish_call(self, x, finals, seq_len, B):
         self.seq_len_padded = seq_len

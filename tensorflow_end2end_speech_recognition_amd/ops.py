@@ -346,6 +346,74 @@ def time_subsample_bwd(dy_tb, len_out, T, kind='drop', out=None):
     return dx
 
 
+def _drop_args(drop):
+    """(keep_prob, seed, offset) of a dropout descriptor; None: no dropout (keep_prob 1)."""
+    if drop is None:
+        return 1.0, 0, 0
+    keep, seed, offset = drop
+    if not 0.0 < float(keep) <= 1.0:
+        raise ValueError('dropout descriptor: keep_prob must be in (0, 1], got %r' % (keep,))
+    return float(keep), int(seed), int(offset)
+
+
+def residual_fwd(h_tb, skip, seq_len, drop=None, sum_out=None, out=None):
+    """A skip connection behind a recurrent layer (asr_residual_fwd; encoder_residual / encoder_dense_residual):
+    out = round(m * h + skip) [T,Bp,W] in h's dtype for the layer's output h (fp32 or bf16), skip in h's dtype or fp32,
+    lengths seq_len [Bp] and drop = (keep_prob, seed, offset) -- the mask dropout_mask(h.shape, ...) would hold -- or
+    None.  sum_out: None, True (a new fp32 tensor) or an fp32 [T,Bp,W] tensor, which may be an fp32 `skip` itself
+    (updated in place), receives skip + out.  Frames t >= seq_len[b] are not read and come back zero.
+    Returns out (`out` or a new tensor), or (out, sum_out) when sum_out was asked for."""
+    h = _h(h_tb)
+    _chk(seq_len, torch.int32, 'seq_len')
+    dtype = dtype_id(h_tb.dtype)
+    if h_tb.dim() != 3 or tuple(skip.shape) != tuple(h_tb.shape) or seq_len.shape[0] != h_tb.shape[1]:
+        raise ValueError('residual_fwd: h %s, skip %s, %d lengths' % (tuple(h_tb.shape), tuple(skip.shape),
+                                                                      seq_len.shape[0]))
+    if skip.dtype != h_tb.dtype and skip.dtype != torch.float32:
+        raise ValueError('residual_fwd: skip must be %s or fp32, got %s' % (h_tb.dtype, skip.dtype))
+    if not skip.is_cuda or not seq_len.is_cuda:
+        raise RuntimeError('HIP path needs a CUDA(ROCm) tensor; there is no CPU fallback')
+    keep, seed, offset = _drop_args(drop)
+    T, Bp, W = h_tb.shape
+    if sum_out is True:
+        sum_out = torch.empty((T, Bp, W), dtype=torch.float32, device=h_tb.device)
+    if sum_out is not None and (tuple(sum_out.shape) != (T, Bp, W) or sum_out.dtype != torch.float32
+                                or not sum_out.is_cuda):
+        raise ValueError('residual_fwd: sum_out must be a device fp32 %s' % ((T, Bp, W),))
+    if out is None:
+        out = torch.empty_like(h_tb, memory_format=torch.contiguous_format)
+    elif tuple(out.shape) != (T, Bp, W) or out.dtype != h_tb.dtype or not out.is_cuda:
+        raise ValueError('residual_fwd: out must be a device %s %s' % (h_tb.dtype, (T, Bp, W)))
+    h.check(h.lib.asr_residual_fwd(h.h, dtype, dtype_id(skip.dtype), _p(h_tb), _p(skip), _p(seq_len), T, Bp, W, keep,
+                                   seed, offset, _p(out), _p(sum_out), _s()), 'asr_residual_fwd')
+    return out if sum_out is None else (out, sum_out)
+
+
+def residual_bwd(dx_raw, carry, seq_len, drop=None, dense=False, dout=None, carry_out=None):
+    """The backward pass at a skip connection (asr_residual_bwd), all fp32 [T,Bp,W]: g = dx_raw + carry, returns
+    (dout = m * g, carry_out = g, or g + carry with dense) -- new tensors, or the ones handed in: `dout` may be dx_raw
+    itself and `carry_out` may be carry itself.  Frames t >= seq_len[b] are not read (dx_raw may be unwritten there) and come back zero in both."""
+    h = _h(dx_raw)
+    _chk(dx_raw, torch.float32, 'dx_raw')
+    _chk(carry, torch.float32, 'carry')
+    _chk(seq_len, torch.int32, 'seq_len')
+    if dx_raw.dim() != 3 or tuple(carry.shape) != tuple(dx_raw.shape) or seq_len.shape[0] != dx_raw.shape[1]:
+        raise ValueError('residual_bwd: dx_raw %s, carry %s, %d lengths' % (tuple(dx_raw.shape), tuple(carry.shape),
+                                                                            seq_len.shape[0]))
+    if not carry.is_cuda or not seq_len.is_cuda:
+        raise RuntimeError('HIP path needs a CUDA(ROCm) tensor; there is no CPU fallback')
+    keep, seed, offset = _drop_args(drop)
+    T, Bp, W = dx_raw.shape
+    for name, t in (('dout', dout), ('carry_out', carry_out)):
+        if t is not None and (tuple(t.shape) != (T, Bp, W) or t.dtype != torch.float32 or not t.is_cuda):
+            raise ValueError('residual_bwd: %s must be a device fp32 %s' % (name, (T, Bp, W)))
+    dout = dout if dout is not None else torch.empty_like(dx_raw, memory_format=torch.contiguous_format)
+    carry_out = carry_out if carry_out is not None else torch.empty_like(carry, memory_format=torch.contiguous_format)
+    h.check(h.lib.asr_residual_bwd(h.h, _p(dx_raw), _p(carry), _p(seq_len), T, Bp, W, keep, seed, offset,
+                                   1 if dense else 0, _p(dout), _p(carry_out), _s()), 'asr_residual_bwd')
+    return dout, carry_out
+
+
 def stack_frames(x_btf, seq_len, num_stack, num_skip):
     """Zero-padded batch [B,T,F] fp32 + seq_len [B] int32 -> ([B, ceil(T/num_skip), F*num_stack], new seq_len)."""
     h = _h(x_btf)
