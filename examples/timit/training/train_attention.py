@@ -95,6 +95,8 @@ def run_name(params):
         name += '_res'
     elif params.get('encoder_dense_residual'):
         name += '_dres'
+    if params.get('decoder_type') == 'gru':
+        name += '_grudec'
     if params.get('scheduled_sampling_prob'):
         name += '_ss' + str(params['scheduled_sampling_prob'])
     if params.get('label_smoothing_prob'):

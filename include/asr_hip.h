@@ -1190,6 +1190,73 @@ int asr_ctc_beam_lm_counts(asr_handle* h, unsigned long long* out3);
 int asr_reset_ctc_beam_lm_counts(asr_handle* h);
 /* work: B*(5*U + 3*T + E2) floats.  dav_cell is consumed (its rows accumulate the query-path gradient in place). */
 int asr_att_decoder_bwd(asr_handle* h, const asr_att_decoder* a, asr_stream s);
+/* ---- GRU decoder cell (later within ABI 5, additive) ---------------------------------------------------------- *
+ * decoder_type 'gru': tf.contrib.rnn.GRUCell as the decoder cell (attention_seq2seq.py:364-365; DEVIATION: the
+ * reference reads self.num_units there, which does not exist -- it is read as decoder_num_units).  With U units,
+ * x = embedding | previous context (Dx columns), Din = Dx + U, and one input row = x | h:
+ *     [r, u] = sigmoid([x, h] W_g + b_g)        W_g [Din,2U] (columns r | u), b_g [2U]
+ *     c      = tanh([x, r*h] W_c + b_c)         W_c [Din,U], b_c [U]
+ *     hn     = u*h + (1-u)*c;  cell_out = hn * out_mask;  h' = live ? hn : h
+ * No peepholes, no forget bias, no cell clip (GRUCell has none).  fp32 weights only.
+ * asr_gru_cell_prep writes the image W3 [(Din+1), 3U] every product below reads: columns [0,2U) = W_g, columns [2U,3U) =
+ * W_c with its U h-rows ZEROED (so x W3 gives the gate pre-activations and the x-part of the candidate's in one product,
+ * and dpre W3^T the whole cell-input gradient but the r*h path), row Din = b_g | b_c.
+ * Forward of one step: gates [B,4U] = r | u | c | r*h is what the backward needs (the candidate's x-part passes through
+ * the c columns between the two phases); h_out [B,U]; cell_out (row stride ld_c >= U); h_out2 / cell_out2 (may be NULL):
+ * the same values into column blocks of wider arrays (row strides ld_h2 / ld_c2).  x rows have stride ldx and hold
+ * x | h_prev, h_prev [B,U] is the same state contiguous.  W_ch = W_c + Dx*U (the h-rows of the candidate kernel, [U,U]).
+ * asr_gru_cell_fwd_ex: any shape, four launches (asr_gemm_act -> gates -> asr_gemm_act -> output); work: B*4U floats.
+ * asr_gru_cell_gemm_fwd: two launches, each a skinny exact-fp32 MFMA product with the cell arithmetic in its epilogue
+ * (A: x W3, sigmoid, r*h; B: (r*h) W_ch, tanh, state update and scatter); asr_gru_cell_gemm_ok states its shapes:
+ * B <= 32, Din % 64 == 0, U % 16 == 0, ldx % 4 == 0 (and 16-byte aligned x, gates).
+ * Rows with live == 0 carry h; rows are independent, so padding rows need only hold finite-or-not initialised memory. */
+int asr_gru_cell_prep(asr_handle* h, const float* W_g, const float* b_g, const float* W_c, const float* b_c, int Din,
+                      int U, float* W3, asr_stream s);
+int asr_gru_cell_gemm_ok(int B, int Din, int U, int ldx);
+int asr_gru_cell_fwd_ex(asr_handle* h, const float* x, int ldx, int Din, const float* W3, const float* W_ch,
+                        const float* h_prev, const float* live, const float* out_mask, int B, int U, float* gates,
+                        float* h_out, float* cell_out, int ld_c, float* h_out2, int ld_h2, float* cell_out2, int ld_c2,
+                        float* work, asr_stream s);
+int asr_gru_cell_gemm_fwd(asr_handle* h, const float* x, int ldx, int Din, const float* W3, const float* W_ch,
+                          const float* h_prev, const float* live, const float* out_mask, int B, int U, float* gates,
+                          float* h_out, float* cell_out, int ld_c, float* h_out2, int ld_h2, float* cell_out2, int ld_c2,
+                          asr_stream s);
+/* Backward of one step.  dcell [B,U]: gradient w.r.t. cell_out; dh_c (+ dh_c2 with row stride ld2, may be NULL): the
+ * carried gradient w.r.t. h'.  With dhn = out_mask*dcell + live*dh_c:
+ *     dc = dhn*(1-u); du = dhn*(h-c); dp = dc*(1-c^2); d_rh = dp W_ch^T; dr = d_rh*h
+ *     dpre [B,3U] = dr*r*(1-r) | du*u*(1-u) | dp
+ *     d_in [B,Din] = dpre W3^T        (x columns: d_x; h columns: dg W_g[h rows]^T)
+ *     dh_prev_carry [B,U] = (1-live)*dh_c + dhn*u + d_rh*r      (the caller adds d_in's h columns)
+ * Launches: elementwise (dp, du, dhn) -> asr_gemm_act (d_rh) -> elementwise (dr, carry) -> asr_gemm_act (d_in); the
+ * mask and the dh_c2 add are folded into the first kernel.  work: 2*B*U floats.  Weight gradients are the caller's,
+ * batched over steps: dW3 = in^T dpre (W_g = columns [0,2U); W_c x-rows = columns [2U,3U) of rows < Dx),
+ * dW_c[h rows] = (r*h)^T dp, biases = column sums. */
+int asr_gru_cell_bwd(asr_handle* h, const float* dcell, const float* dh_c, const float* dh_c2, int ld2,
+                     const float* out_mask, const float* live, const float* gates, const float* h_prev,
+                     const float* W3, const float* W_ch, int B, int Din, int U, float* dpre, float* dh_prev_carry,
+                     float* d_in, int ld_din, float* work, asr_stream s);
+/* The decoder loops with the GRU cell: asr_att_decoder_fwd / _bwd / _infer / _beam with the cell launches replaced by the
+ * ones above and everything else (query FC, attention, head, selection, re-ordering) issued exactly as there.  `a` as for
+ * those calls except: W_cell, b_cell, peep, craw_all, dc0 are not read (NULL allowed); c_all is read only by the beam
+ * loop (asr_att_beam_reorder gathers it: give it zeros [2,R,U]); gates_all [To,B,4U] holds r | u | c | r*h; dpre_all is
+ * [To,B,3U] (asr_gru_cell_bwd's dpre); forget_bias / cell_clip / W_cell_il / W_cell_h are ignored.  g->W3: (Din+1)*3U
+ * floats of work space, written once per call (asr_gru_cell_prep).  The two-launch form runs where
+ * asr_gru_cell_gemm_ok(B, Din, U, Din) and g->fused != 0, the four-launch form everywhere else (a beam's B*W rows). */
+typedef struct asr_att_gru {
+  const float *W_g, *b_g, *W_c, *b_c;           /* [Din,2U], [2U], [Din,U], [U]; rows: embedding | context | h */
+  float *W3;                                    /* work space, (Din+1)*3U floats */
+  int fused;                                    /* 0: always the four-launch form (A/B) */
+} asr_att_gru;
+int asr_att_decoder_fwd_gru(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, asr_stream s);
+int asr_att_decoder_bwd_gru(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, asr_stream s);
+int asr_att_decoder_infer_gru(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, const asr_att_infer* f,
+                              int* steps_issued, asr_stream s);
+int asr_att_decoder_beam_gru(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, const asr_att_infer* f,
+                             const asr_att_beam* m, int* steps_issued, asr_stream s);
+/* GRU decoder steps on this handle since the last reset: {two-launch forward steps, four-launch forward steps,
+ * backward steps} (the loops and the single-step entry points both count). */
+int asr_att_gru_counts(asr_handle* h, unsigned long long* out3);
+int asr_reset_att_gru_counts(asr_handle* h);
 /* out[b, j] = x[b*ldx + j] + y[b*ldy + j], j < W (row blocks of wider arrays; out may alias x) */
 int asr_add_cols(asr_handle* h, const float* x, int ldx, const float* y, int ldy, float* out, int ldo, int B, int W,
                  asr_stream s);

@@ -192,6 +192,21 @@ SIGNATURES = {
     'asr_residual_bwd': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _u64, _u64, _i, _vp, _vp, _vp]),
     # scheduled sampling in the training loop, label-smoothed sequence loss (later within ABI 5)
     'asr_att_decoder_fwd_ss': (_i, [_vp, _vp, _vp, _vp]),
+    # GRU decoder cell (later within ABI 5)
+    'asr_gru_cell_prep': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
+    'asr_gru_cell_gemm_ok': (_i, [_i, _i, _i, _i]),
+    'asr_gru_cell_fwd_ex': (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i,
+                                 _vp, _vp]),
+    'asr_gru_cell_gemm_fwd': (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i,
+                                   _vp]),
+    'asr_gru_cell_bwd': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp,
+                              _vp]),
+    'asr_att_decoder_fwd_gru': (_i, [_vp] * 4),
+    'asr_att_decoder_bwd_gru': (_i, [_vp] * 4),
+    'asr_att_decoder_infer_gru': (_i, [_vp] * 6),
+    'asr_att_decoder_beam_gru': (_i, [_vp] * 7),
+    'asr_att_gru_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
+    'asr_reset_att_gru_counts': (_i, [_vp]),
     'asr_seq_xent_ls': (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp]),
     'asr_add_cols': (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp]),
     'asr_tanh_fwd': (_i, [_vp, _vp, _vp, _sz, _vp]),

@@ -2216,7 +2216,18 @@ extern "C" int asr_add_cols(asr_handle* h, const float* x, int ldx, const float*
   return ASR_OK;
 }
 
-static int dec_check(asr_handle* h, const asr_att_decoder* a, bool bwd) {
+// g != nullptr (the *_gru entry points): the cell is the GRU of gru_decoder.hip -- the LSTM cell's weights, its raw cell
+// state, c and dc0 are not asked for, the GRU block is.  g == nullptr is every call this file has always made.
+static int dec_check(asr_handle* h, const asr_att_decoder* a, bool bwd, const asr_att_gru* g = nullptr) {
+  if (g && a) {
+    asr_att_decoder d = *a;                                // the LSTM-only fields pass the checks below
+    d.W_cell = d.b_cell = g->W_g;
+    d.craw_all = d.c_all = d.gates_all;
+    d.dc0 = d.dh0;
+    d.peep = nullptr;
+    ASR_TRY(asr_gru_dec_check(h, a, g));
+    return dec_check(h, &d, bwd);
+  }
   if (!a || a->To < 1 || a->B < 1 || a->T < 1 || a->U < 1 || a->Em < 0 || a->E2 < 1 || a->A < 1 || !a->W_cell ||
       !a->b_cell || !a->enc || !a->seq_len || !a->live || !a->dec_in || !a->av_in || !a->alpha_all || !a->gates_all ||
       !a->craw_all || !a->c_all || !a->h_all || !a->qz_all || !a->work || (a->att_mode != 0 && a->att_mode != 1) ||
@@ -2282,7 +2293,8 @@ static inline bool dec_cell_gemm_h(const asr_att_decoder* a) {
   return a->W_cell_h && asr_lstm_cell_gemm_ok(a->B, Din, a->U, Din) && a->U % 16 == 0 && ((uintptr_t)a->dec_in) % 16 == 0 &&
          ((uintptr_t)a->W_cell_h) % 16 == 0;
 }
-static int dec_cell_image(asr_handle* h, const asr_att_decoder* a, asr_stream s) {
+static int dec_cell_image(asr_handle* h, const asr_att_decoder* a, asr_stream s, const asr_att_gru* g = nullptr) {
+  if (g) return asr_gru_dec_image(h, a, g, s);
   if (dec_cell_gemm_h(a)) return asr_lstm_cell_gemm_prep_h(h, a->W_cell, a->b_cell, a->Em + a->E2 + a->U, a->U, a->W_cell_h, s);
   if (!dec_cell_gemm(a)) return ASR_OK;
   return asr_lstm_cell_gemm_prep(h, a->W_cell, a->b_cell, a->Em + a->E2 + a->U, a->U, a->W_cell_il, s);
@@ -2291,7 +2303,9 @@ static int dec_cell_image(asr_handle* h, const asr_att_decoder* a, asr_stream s)
 // One forward step of the decoder loop: cell-input GEMM -> cell -> query FC -> energies -> softmax + context.  k indexes
 // the step arrays that carry the recurrence (dec_in, av_in, c / h, alpha, live); ks the saved activations only the
 // backward reads (gates, raw cell, query: the inference loop reuses row 0).
-static int dec_fwd_step(asr_handle* h, const asr_att_decoder* a, int k, int ks, bool more, asr_stream s) {
+// g != nullptr: the cell launches are the GRU's (asr_gru_dec_fwd_step, same scatter targets); everything behind them is shared.
+static int dec_fwd_step(asr_handle* h, const asr_att_decoder* a, int k, int ks, bool more, asr_stream s,
+                        const asr_att_gru* g = nullptr) {
   const int B = a->B, U = a->U, T = a->T, E2 = a->E2, Em = a->Em, A = a->A;
   const int Din = Em + E2 + U, Dav = U + E2;
   float* pre = a->work;                                    // [B,4U]
@@ -2303,7 +2317,9 @@ static int dec_fwd_step(asr_handle* h, const asr_att_decoder* a, int k, int ks, 
   float* av = a->av_in + (size_t)k * B * Dav;
   float* qz = a->qz_all + (size_t)ks * B * A;
   // the cell output (times its dropout mask) lands in av[:, :U]; without a query FC it IS the query
-  if (dec_cell_gemm_h(a)) {  // product + cell as one launch on the bf16 fragment image (dec_cell_image)
+  if (g) {
+    ASR_TRY(asr_gru_dec_fwd_step(h, a, g, k, ks, dnext, qz, s));
+  } else if (dec_cell_gemm_h(a)) {  // product + cell as one launch on the bf16 fragment image (dec_cell_image)
     h->att_counts[ASR_ATT_FWD_CELL_BF16] += 1;
     ASR_TRY(asr_lstm_cell_gemm_fwd_h(h, din, Din, Din, a->W_cell_h, a->c_all + (size_t)k * B * U,
                                      a->h_all + (size_t)k * B * U, a->peep, a->live + (size_t)k * B, B, U, a->forget_bias,
@@ -2349,15 +2365,23 @@ static int dec_fwd_step(asr_handle* h, const asr_att_decoder* a, int k, int ks, 
   return ASR_OK;
 }
 
-extern "C" int asr_att_decoder_fwd(asr_handle* h, const asr_att_decoder* a, asr_stream s) {
+static int dec_fwd_loop(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  ASR_TRY(dec_check(h, a, false));
+  ASR_TRY(dec_check(h, a, false, g));
   const int B = a->B, U = a->U, T = a->T, E2 = a->E2, Em = a->Em, A = a->A;
   const int Din = Em + E2 + U, Dav = U + E2;
-  ASR_TRY(dec_cell_image(h, a, s));
-  for (int k = 0; k < a->To; ++k) ASR_TRY(dec_fwd_step(h, a, k, k, k + 1 < a->To, s));
+  ASR_TRY(dec_cell_image(h, a, s, g));
+  for (int k = 0; k < a->To; ++k) ASR_TRY(dec_fwd_step(h, a, k, k, k + 1 < a->To, s, g));
   (void)B; (void)U; (void)T; (void)E2; (void)Em; (void)A; (void)Din; (void)Dav;
   return ASR_OK;
+}
+extern "C" int asr_att_decoder_fwd(asr_handle* h, const asr_att_decoder* a, asr_stream s) {
+  return dec_fwd_loop(h, a, nullptr, s);
+}
+extern "C" int asr_att_decoder_fwd_gru(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  if (!g) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_fwd_gru: bad arguments");
+  return dec_fwd_loop(h, a, g, s);
 }
 
 // ---------------------------------------------------------------- greedy inference loop, native
@@ -2413,10 +2437,10 @@ __global__ __launch_bounds__(256) void att_infer_select_kernel(const float* __re
 }
 }  // namespace
 
-extern "C" int asr_att_decoder_infer(asr_handle* h, const asr_att_decoder* a, const asr_att_infer* f, int* steps_issued,
-                                     asr_stream s) {
+static int dec_infer_loop(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, const asr_att_infer* f,
+                          int* steps_issued, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  ASR_TRY(dec_check(h, a, false));
+  ASR_TRY(dec_check(h, a, false, g));
   if (!f || !f->W_av || !f->W_out || !f->embedding || !f->live || !f->av_all || !f->logits_all || !f->ids_all ||
       !f->live_count || f->C2 < 1 || f->eos < 0 || f->live != a->live || a->dmask)
     ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_infer: bad arguments");
@@ -2442,7 +2466,7 @@ extern "C" int asr_att_decoder_infer(asr_handle* h, const asr_att_decoder* a, co
         ASR_FAIL(h, ASR_ERR_HIP, "asr_att_decoder_infer: event");
       }
   }
-  int rc = dec_cell_image(h, a, s), k = 0;
+  int rc = dec_cell_image(h, a, s, g), k = 0;
   for (; rc == ASR_OK && k < To; ++k) {
     if (every && k % every == 0 && k > 0) {
       const int c = k / every;                             // this check point; c - 1 was recorded one interval ago
@@ -2458,7 +2482,7 @@ extern "C" int asr_att_decoder_infer(asr_handle* h, const asr_att_decoder* a, co
     }
     const bool more = k + 1 < To;
     // (saved-activation arrays the backward would need are reused every step: index 0)
-    if ((rc = dec_fwd_step(h, a, k, 0, more, s)) != ASR_OK) break;
+    if ((rc = dec_fwd_step(h, a, k, 0, more, s, g)) != ASR_OK) break;
     float* av = f->av_all + (size_t)k * B * U;
     float* lg = f->logits_all + (size_t)k * B * C2;
     if ((rc = asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, B, U, Dav, a->av_in + (size_t)k * B * Dav, Dav, f->W_av, U, av, U, nullptr,
@@ -2475,6 +2499,16 @@ extern "C" int asr_att_decoder_infer(asr_handle* h, const asr_att_decoder* a, co
   ASR_CHECK_LAUNCH(h, "asr_att_decoder_infer");
   if (steps_issued) *steps_issued = k;
   return ASR_OK;
+}
+extern "C" int asr_att_decoder_infer(asr_handle* h, const asr_att_decoder* a, const asr_att_infer* f, int* steps_issued,
+                                     asr_stream s) {
+  return dec_infer_loop(h, a, nullptr, f, steps_issued, s);
+}
+extern "C" int asr_att_decoder_infer_gru(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, const asr_att_infer* f,
+                                         int* steps_issued, asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  if (!g) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_infer_gru: bad arguments");
+  return dec_infer_loop(h, a, g, f, steps_issued, s);
 }
 
 // ---------------------------------------------------------------- scheduled-sampling training loop, native
@@ -2573,14 +2607,18 @@ extern "C" int asr_att_decoder_fwd_ss(asr_handle* h, const asr_att_decoder* a, c
 // the fused rank kernel would leave its `last` block unwritten), asr_lm_beam_reorder at the end of the step.  Only the
 // selection differs between the three searches; the state advance and the re-ordering behind it are shared.  Without lm
 // nothing of this is issued.
+// g != nullptr (asr_att_decoder_beam_gru): the GRU cell in the step; a->c_all is then a block of zeros the re-ordering
+// gathers as it always has.
 static int att_beam_loop(asr_handle* h, const asr_att_decoder* a_, const asr_att_infer* f, const asr_att_beam* m,
-                         const asr_att_beam_ctc* j, const asr_att_lm* lm, int* steps_issued, asr_stream s) {
-  const char* who = lm ? "asr_att_decoder_beam_lm" : j ? "asr_att_decoder_beam_joint" : "asr_att_decoder_beam";
+                         const asr_att_beam_ctc* j, const asr_att_lm* lm, int* steps_issued, asr_stream s,
+                         const asr_att_gru* g = nullptr) {
+  const char* who = g ? "asr_att_decoder_beam_gru" : lm ? "asr_att_decoder_beam_lm" : j ? "asr_att_decoder_beam_joint" : "asr_att_decoder_beam";
   if (!a_ || !m) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "%s: bad arguments", who);
   asr_att_decoder d = *a_;
   if (d.carry_alpha) d.alpha_zero = m->alpha_prev;
   const asr_att_decoder* a = &d;
-  ASR_TRY(dec_check(h, a, false));
+  ASR_TRY(dec_check(h, a, false, g));
+  if (g && !a->c_all) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "%s: c_all (zeros [2,R,U]) is needed by the re-ordering", who);
   if (!f || !f->W_av || !f->W_out || !f->embedding || f->C2 < 1 || f->eos < 0 || f->eos >= f->C2 || a->dmask || m->W < 1 ||
       m->W > 32 || m->W > f->C2 || a->B % m->W != 0 || !m->word || !m->parent || !m->score || !m->log_probs || !m->finished ||
       !m->lengths || !m->av || !m->logits || !m->unfinished || !m->ids || !m->hyp_len || !m->final_score ||
@@ -2616,7 +2654,7 @@ static int att_beam_loop(asr_handle* h, const asr_att_decoder* a_, const asr_att
   float* din1 = a->dec_in + (size_t)R * Din;
   float* c1 = a->c_all + (size_t)R * U;
   float* h1 = a->h_all + (size_t)R * U;
-  int rc = dec_cell_image(h, a, s), k = 0;
+  int rc = dec_cell_image(h, a, s, g), k = 0;
   for (; rc == ASR_OK && k < To; ++k) {
     if (every && k % every == 0 && k > 0) {                // (see asr_att_decoder_infer)
       const int c = k / every;
@@ -2630,7 +2668,7 @@ static int att_beam_loop(asr_handle* h, const asr_att_decoder* a_, const asr_att
       if (hipMemcpyAsync(f->host_live_count + k, m->unfinished + k, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
           hipEventRecord(ev[c % NEV], st) != hipSuccess) { rc = ASR_ERR_HIP; break; }
     }
-    if ((rc = dec_fwd_step(h, a, 0, 0, true, s)) != ASR_OK) break;
+    if ((rc = dec_fwd_step(h, a, 0, 0, true, s, g)) != ASR_OK) break;
     if ((rc = asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, R, U, Dav, a->av_in, Dav, f->W_av, U, m->av, U, nullptr, 0, 0, s)) != ASR_OK) break;
     if ((rc = asr_tanh_fwd(h, m->av, m->av, (size_t)R * U, s)) != ASR_OK) break;
     if ((rc = asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, R, C2, U, m->av, U, f->W_out, C2, m->logits, C2, f->b_out, 0, 0, s)) != ASR_OK) break;
@@ -2702,9 +2740,18 @@ extern "C" int asr_att_decoder_beam_lm(asr_handle* h, const asr_att_decoder* a, 
   return att_beam_loop(h, a, f, m, j, lm, steps_issued, s);
 }
 
-extern "C" int asr_att_decoder_bwd(asr_handle* h, const asr_att_decoder* a, asr_stream s) {
+extern "C" int asr_att_decoder_beam_gru(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, const asr_att_infer* f,
+                                        const asr_att_beam* m, int* steps_issued, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  ASR_TRY(dec_check(h, a, true));
+  if (!g) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_beam_gru: bad arguments");
+  return att_beam_loop(h, a, f, m, nullptr, nullptr, steps_issued, s, g);
+}
+
+// g != nullptr (asr_att_decoder_bwd_gru): the cell backward and the cell-input product of a step are the GRU's
+// (asr_gru_dec_bwd_step); the query-FC backward in front of them is the unfused branch's.
+static int dec_bwd_loop(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  ASR_TRY(dec_check(h, a, true, g));
   const int B = a->B, U = a->U, T = a->T, E2 = a->E2, Em = a->Em, A = a->A, To = a->To;
   const int Din = Em + E2 + U;
   hipStream_t st = (hipStream_t)s;
@@ -2718,7 +2765,8 @@ extern "C" int asr_att_decoder_bwd(asr_handle* h, const asr_att_decoder* a, asr_
     ASR_FAIL(h, ASR_ERR_HIP, "asr_att_decoder_bwd: memset");
   // the bf16 images of W_cell are written again here (one launch per loop): the call does not depend on the forward
   // loop having run with the same work space
-  const bool cell_h = dec_cell_gemm_h(a);
+  const bool cell_h = !g && dec_cell_gemm_h(a);
+  if (g) ASR_TRY(asr_gru_dec_image(h, a, g, s));
   if (cell_h) ASR_TRY(asr_lstm_cell_gemm_prep_h(h, a->W_cell, a->b_cell, Din, U, a->W_cell_h, s));
   int cur = 0;
   const float* dalpha_next = nullptr;
@@ -2760,7 +2808,7 @@ extern "C" int asr_att_decoder_bwd(asr_handle* h, const asr_att_decoder* a, asr_
     const float* dmask = a->dmask ? a->dmask + (size_t)k * B * U : nullptr;
     // query-FC backward + cell backward in ONE launch that also sums the energy backward's chunk partials, when the
     // shapes allow (a query FC over A = 64 / 128 / 256 / 512 columns, U % 16 == 0, 16-byte aligned rows, no carried alpha)
-    const bool fused_q = !a->carry_alpha && a->has_query_fc && (A == 64 || A == 128 || A == 256 || A == 512) && U % DQ_CT == 0 &&
+    const bool fused_q = !g && !a->carry_alpha && a->has_query_fc && (A == 64 || A == 128 || A == 256 || A == 512) && U % DQ_CT == 0 &&
                          a->ld_wq % 4 == 0 && ((uintptr_t)a->W_q) % 16 == 0 && ((uintptr_t)dqz) % 16 == 0 &&
                          (!dv || ((uintptr_t)dv) % 16 == 0);
     h->att_counts[fused_q ? ASR_ATT_BWD_STEP_FUSED_Q : ASR_ATT_BWD_STEP_UNFUSED] += 1;
@@ -2782,6 +2830,11 @@ extern "C" int asr_att_decoder_bwd(asr_handle* h, const asr_att_decoder* a, asr_
         ASR_TRY(asr_gemm_act(h, ASR_F32, ASR_F32, 0, 1, B, U, A, dqz, A, a->W_q, a->ld_wq, dcell, U, nullptr, 1, 0, s));
       else
         ASR_TRY(asr_add_cols(h, dcell, U, dqz, A, dcell, U, B, U, s));
+      if (g) {       // (mask and the h-columns of step k+1's cell-input gradient are folded in as below; dcs is its work space)
+        ASR_TRY(asr_gru_dec_bwd_step(h, a, g, k, dcell, dhc[cur], dh2, dhc[cur ^ 1], dcs[0], s));
+        cur ^= 1;
+        continue;
+      }
       // the cell kernel applies the output dropout mask to dcell and adds the h-columns of step k+1's cell-input
       // gradient to the carried dh itself
       ASR_TRY(cell_bwd_launch(h, dcell, dcs[cur], dhc[cur], a->gates_all + (size_t)k * B * 4 * U,
@@ -2797,9 +2850,19 @@ extern "C" int asr_att_decoder_bwd(asr_handle* h, const asr_att_decoder* a, asr_
     cur ^= 1;
   }
   ASR_TRY(asr_add_cols(h, dhc[cur], U, a->d_in_all + Em + E2, Din, a->dh0, U, B, U, s));
+  if (g) return ASR_OK;                                    // (no cell state, no dc0)
   if (hipMemcpyAsync(a->dc0, dcs[cur], (size_t)B * U * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
     ASR_FAIL(h, ASR_ERR_HIP, "asr_att_decoder_bwd: copy");
   return ASR_OK;
+}
+
+extern "C" int asr_att_decoder_bwd(asr_handle* h, const asr_att_decoder* a, asr_stream s) {
+  return dec_bwd_loop(h, a, nullptr, s);
+}
+extern "C" int asr_att_decoder_bwd_gru(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  if (!g) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_bwd_gru: bad arguments");
+  return dec_bwd_loop(h, a, g, s);
 }
 
 

@@ -45,6 +45,8 @@ struct asr_handle {
   unsigned long long ctc_beam_lm_counts[3];
   // CTC head since the last asr_reset_ctc_head_counts: {asr_ctc_head_fwd launches, asr_ctc_loss_ex calls, asr_ctc_loss calls}
   unsigned long long ctc_head_counts[3];
+  // GRU decoder steps since the last asr_reset_att_gru_counts: {two-launch forward, four-launch forward, backward}
+  unsigned long long att_gru_counts[3];
 };
 
 #define ASR_FAIL(h, code, ...)                                  \
@@ -189,6 +191,16 @@ bool asr_cluster_gru_fwd_try(asr_handle* h, int T, int B, int H, int ndir, const
 bool asr_cluster_gru_bwd_try(asr_handle* h, int T, int B, int H, int ndir, const float* dout, const float* d_h_final,
                              const float* hout, const float* r, const float* u, const float* c, const float* wghT,
                              const float* wchT, const int32_t* seq_len, float* dgate, float* dcand, hipStream_t st);
+
+// the GRU cell's part of a decoder-loop step (gru_decoder.hip; the loops are attention.hip's): argument check, the weight
+// image once per loop call, the cell launches of forward step k (saved activations at row ks; dnext = the next step's
+// input rows or NULL; qz = the step's query rows) and of backward step k (work2: 2*B*U floats)
+int asr_gru_dec_check(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g);
+int asr_gru_dec_image(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, asr_stream s);
+int asr_gru_dec_fwd_step(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, int k, int ks, float* dnext,
+                         float* qz, asr_stream s);
+int asr_gru_dec_bwd_step(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, int k, const float* dcell,
+                         const float* dh_c, const float* dh_c2, float* dh_carry, float* work2, asr_stream s);
 
 static inline int asr_dtype_ok(int dt) { return dt == ASR_F32 || dt == ASR_BF16; }
 static inline size_t asr_dtype_size(int dt) { return dt == ASR_BF16 ? 2 : 4; }

@@ -19,6 +19,16 @@ W_filter/weights therefore receive zero gradient, W_keys of 'location' too (Q6).
 written to express: the previous step's weights go through conv1d([201|200,1,10], SAME) -> W_filter inside the
 energy kernel (csrc/attention.hip asr_att_loc_energy_*), with gradients into `filter`, W_filter and, through the
 previous step's softmax, everything upstream.
+
+decoder_type='gru': the decoder cell is tf.contrib.rnn.GRUCell, the branch the reference has at attention_seq2seq.py:364-365
+(GRUCell(self.num_units); DEVIATION: self.num_units does not exist there -- the branch crashes -- and is read as
+decoder_num_units).  Variables attention_decoder/decoder/gru_cell/{gates,candidate}/{kernel,bias} (rows embedding | context |
+h; gates/bias initialised to one), the bridge's FC is [4H, U] and gives h0 only (GRUCell.state_size is the integer U).
+use_peephole and clip_activation_decoder do not reach a GRU decoder: TF's GRUCell has no peepholes, no forget bias and no
+cell clip.  Everything around the cell (input feeding, attention, attentional vector, impute_finished, output dropout) is
+the LSTM decoder's; the loops are the same native ones around the GRU cell's launches (csrc/gru_decoder.hip), in fp32 on the
+master weights also in a dtype='bf16' model.  Not available with a GRU decoder (each raises ValueError):
+scheduled_sampling_prob > 0, infer(ctc_weight > 0), infer(lm=...).
 """
 import os as _os
 
@@ -76,9 +86,9 @@ class AttentionSeq2Seq(ModelBase):
         self.label_smoothing_prob = float(label_smoothing_prob)
         # carried weights only exist for the two types that have location features
         self.carry_alpha = prev_alpha == 'carry' and attention_type in AL.HAS_FILTER
-        if decoder_type != 'lstm':
-            raise TypeError('decoder_type is "lstm" or "gru".') if decoder_type != 'gru' else \
-                NotImplementedError('GRU decoder (crashes in the reference too, attention_seq2seq.py:364-365)')
+        if decoder_type not in ('lstm', 'gru'):
+            raise TypeError('decoder_type is "lstm" or "gru".')
+        self.gru_decoder = decoder_type == 'gru'
         if encoder_type not in ('blstm',):
             raise NotImplementedError
         self.input_size, self.splice = input_size, splice
@@ -144,14 +154,24 @@ class AttentionSeq2Seq(ModelBase):
         u = lambda *s: rng.uniform(-parameter_init, parameter_init, size=s)
         tn = lambda *s: truncated_normal(rng, parameter_init, s)
         st.declare('output_embedding/W_embedding', (C2, Em), u(C2, Em))
-        st.declare('bridge/fully_connected/weights', (4 * H, 2 * U), tn(4 * H, 2 * U))
-        st.declare('bridge/fully_connected/biases', (2 * U,), np.zeros(2 * U))
+        # the decoder's state: (c, h) of an LSTM cell, h alone of a GRU cell (GRUCell.state_size is the integer U)
+        S = U if self.gru_decoder else 2 * U
+        st.declare('bridge/fully_connected/weights', (4 * H, S), tn(4 * H, S))
+        st.declare('bridge/fully_connected/biases', (S,), np.zeros(S))
         self.dec_in_dim = Em + E2 + U
-        st.declare(D + 'lstm_cell/kernel', (self.dec_in_dim, 4 * U), u(self.dec_in_dim, 4 * U))
-        st.declare(D + 'lstm_cell/bias', (4 * U,), np.zeros(4 * U))
-        if use_peephole:
-            for n in ('w_i_diag', 'w_f_diag', 'w_o_diag'):
-                st.declare(D + 'lstm_cell/' + n, (U,), u(U))
+        if self.gru_decoder:
+            # tf.contrib.rnn.GRUCell (attention_seq2seq.py:364-365; its self.num_units read as decoder_num_units): the
+            # names models/encoders/core/gru.py uses for its cells, gates/bias initialised to one; no peepholes
+            st.declare(D + 'gru_cell/gates/kernel', (self.dec_in_dim, 2 * U), u(self.dec_in_dim, 2 * U))
+            st.declare(D + 'gru_cell/gates/bias', (2 * U,), np.ones(2 * U))
+            st.declare(D + 'gru_cell/candidate/kernel', (self.dec_in_dim, U), u(self.dec_in_dim, U))
+            st.declare(D + 'gru_cell/candidate/bias', (U,), np.zeros(U))
+        else:
+            st.declare(D + 'lstm_cell/kernel', (self.dec_in_dim, 4 * U), u(self.dec_in_dim, 4 * U))
+            st.declare(D + 'lstm_cell/bias', (4 * U,), np.zeros(4 * U))
+            if use_peephole:
+                for n in ('w_i_diag', 'w_f_diag', 'w_o_diag'):
+                    st.declare(D + 'lstm_cell/' + n, (U,), u(U))
         at = attention_type
         self.att_mode = 0 if at in AL.ADDITIVE else 1
         if at == 'luong_dot' and E2 != U:
@@ -202,7 +222,7 @@ class AttentionSeq2Seq(ModelBase):
 
     def _peep(self):
         st = self.store
-        if not self.use_peephole:
+        if not self.use_peephole or self.gru_decoder:
             return None
         return torch.stack([st[D + 'lstm_cell/w_i_diag'], st[D + 'lstm_cell/w_f_diag'],
                             st[D + 'lstm_cell/w_o_diag']]).contiguous()
@@ -255,9 +275,24 @@ class AttentionSeq2Seq(ModelBase):
         class _Enc(object):
             final_state = ((final_c[0], final_h[0]), (final_c[1], final_h[1]))
         U = self.decoder_num_units
+        if self.gru_decoder:                  # the state is h alone: c0 is None
+            br = InitialStateBridge(_Enc, U, self.parameter_init, store=self.store)
+            h0, = br()
+            return br.bridge_input(), None, h0
         br = InitialStateBridge(_Enc, (U, U), self.parameter_init, store=self.store)
         c0, h0 = br()
         return br.bridge_input(), c0, h0
+
+    def _cell_fields(self, peep):
+        """The decoder cell's entries of a loop dict: the LSTM kernel / bias / peepholes, or the GRU block ops.att_decoder_*
+        dispatch on (fp32 master weights also in a bf16-operand model)."""
+        st = self.store
+        if self.gru_decoder:
+            return dict(W_cell=None, b_cell=None, cell_bf16=False, peep=None,
+                        gru=dict(W_g=st[D + 'gru_cell/gates/kernel'], b_g=st[D + 'gru_cell/gates/bias'],
+                                 W_c=st[D + 'gru_cell/candidate/kernel'], b_c=st[D + 'gru_cell/candidate/bias']))
+        return dict(W_cell=self._w_cell(), b_cell=st[D + 'lstm_cell/bias'], cell_bf16=(self.dtype == ASR_BF16),
+                    peep=peep)
 
     def attention_layer(self, time_major_inputs=True):
         """The model's AttentionLayer (attention_seq2seq.py:413-430), bound to its variables."""
@@ -278,6 +313,9 @@ class AttentionSeq2Seq(ModelBase):
         if not 0.0 <= ss_prob <= 1.0:
             raise ValueError('scheduled_sampling_prob must be in [0, 1], got %r' % (scheduled_sampling_prob,))
         sample = is_training and ss_prob > 0.0
+        if self.gru_decoder and ss_prob > 0.0:
+            raise ValueError('scheduled_sampling_prob > 0 is not available with decoder_type="gru" (the sampling loop runs '
+                             'the LSTM decoder only)')
         dev, st = self.device, self.store
         # nothing below may drain the stream (pageable uploads and device read-backs do): the host has to run ahead of the
         # device for the step to be device-bound -- ops.to_device stages through pinned memory, ops.host_ints remembers
@@ -329,7 +367,6 @@ class AttentionSeq2Seq(ModelBase):
         dec_in = torch.empty((To, Bp, Din), dtype=torch.float32, device=dev)
         av_in = torch.empty((To, Bp, U + E2), dtype=torch.float32, device=dev)
         ctx = torch.zeros((Bp, E2), dtype=torch.float32, device=dev)
-        W_cell, b_cell = self._w_cell(), st[D + 'lstm_cell/bias']
         v = st[AT + 'v_a'] if self.att_mode == 0 else None
         alpha_all = torch.empty((To, Bp, T), dtype=torch.float32, device=dev)   # one slab: d_enc GEMMs read it strided
         use_ddrop = is_training and float(keep_prob_decoder) < 1.0
@@ -350,24 +387,25 @@ class AttentionSeq2Seq(ModelBase):
         # where the next one reads) are issued by ONE native call: a host loop over ~9 launches per step is host-bound
         A = self.key_dim                                     # width of keys / query (== U for the luong_* types)
         has_q = self.attention_type in AL.HAS_QUERY_FC
-        c_all = torch.empty((To + 1, Bp, U), dtype=torch.float32, device=dev)
+        gru = self.gru_decoder
+        c_all = None if gru else torch.empty((To + 1, Bp, U), dtype=torch.float32, device=dev)
         h_all = torch.empty((To + 1, Bp, U), dtype=torch.float32, device=dev)
-        c_all[0].copy_(c)
+        if not gru:
+            c_all[0].copy_(c)
         h_all[0].copy_(h)
         loop = dict(To=To, B=Bp, T=T, U=U, Em=Em, E2=E2, A=A, att_mode=self.att_mode, has_query_fc=int(has_q),
                     carry_alpha=int(self.carry_alpha), taps=int(st[AT + 'filter'].shape[0]) if self.carry_alpha else 0,
                     enc_dtype=ops.dtype_id(enc_att.dtype), forget_bias=1.0,
                     cell_clip=float(self.clip_activation_decoder or 0.0), sharpening=float(self.sharpening_factor),
-                    W_cell=W_cell, b_cell=b_cell, cell_bf16=(self.dtype == ASR_BF16), peep=peep,
                     W_q=self._wq() if has_q else None,
                     b_q=st[AT + 'W_filter/biases'] if (has_q and self.attention_type in AL.HAS_FILTER) else None,
                     v=v, keys=keys, enc=enc_att, seq_len=seq_p,
                     filt=st[AT + 'filter'] if self.carry_alpha else None,
                     wfil=st[AT + 'W_filter/weights'] if self.carry_alpha else None, alpha_zero=alpha_zero,
                     live=live_d, dmask=dmask_all, dec_in=dec_in, av_in=av_in, alpha_all=alpha_all, snorm_all=snorm_all,
-                    gates_all=torch.empty((To, Bp, 4 * U), dtype=torch.float32, device=dev),
-                    craw_all=torch.empty((To, Bp, U), dtype=torch.float32, device=dev), c_all=c_all, h_all=h_all,
-                    qz_all=torch.empty((To, Bp, A), dtype=torch.float32, device=dev))
+                    gates_all=torch.empty((To, Bp, 4 * U), dtype=torch.float32, device=dev),     # (GRU: r | u | c | r*h)
+                    craw_all=None if gru else torch.empty((To, Bp, U), dtype=torch.float32, device=dev), c_all=c_all,
+                    h_all=h_all, qz_all=torch.empty((To, Bp, A), dtype=torch.float32, device=dev), **self._cell_fields(peep))
         if sample:
             # one launch for the draws of every step; a non-zero entry feeds the model's prediction (rows that have
             # finished and the padding of the batch tile keep the label's token whatever their draw)
@@ -493,10 +531,13 @@ class AttentionSeq2Seq(ModelBase):
             dkeys = torch.zeros_like(keys)
         elif at == 'luong_dot':
             dkeys = denc
-        dpre_all = torch.empty((To, Bp, 4 * U), dtype=torch.float32, device=dev)
+        gru = self.gru_decoder
+        has_peep = self.use_peephole and not gru
+        # pre-activation gradients of the cell: i | g | f | o of the LSTM, dr | du | dp (gates, candidate) of the GRU
+        dpre_all = torch.empty((To, Bp, (3 if gru else 4) * U), dtype=torch.float32, device=dev)
         dqz_all = torch.empty((To, Bp, A), dtype=torch.float32, device=dev)
         dv_all = torch.empty_like(dqz_all) if self.att_mode == 0 else None
-        dpeep_all = torch.empty((To, Bp, 3 * U), dtype=torch.float32, device=dev) if self.use_peephole else None
+        dpeep_all = torch.empty((To, Bp, 3 * U), dtype=torch.float32, device=dev) if has_peep else None
         cell_out_all = av_in[:, :, :U]
         d_in_all = torch.empty((To, Bp, Em + E2 + U), dtype=torch.float32, device=dev)   # d loss / d cell input
         dctx_all = torch.empty((To, Bp, E2), dtype=torch.float32, device=dev)
@@ -505,7 +546,7 @@ class AttentionSeq2Seq(ModelBase):
             filt, wfil = st[AT + 'filter'], st[AT + 'W_filter/weights']
             dwfil_rows = torch.empty((Bp,) + tuple(wfil.shape), dtype=torch.float32, device=dev)
             dfilt_rows = torch.empty((Bp, filt.shape[0], filt.shape[2]), dtype=torch.float32, device=dev)
-        dc_next = torch.empty((Bp, U), dtype=torch.float32, device=dev)
+        dc_next = None if gru else torch.empty((Bp, U), dtype=torch.float32, device=dev)     # (a GRU has no cell state)
         dh_next = torch.empty((Bp, U), dtype=torch.float32, device=dev)
         # the reverse loop, native as the forward one: per step  d ctx = attentional-vector part + the next step's
         # cell-input part -> softmax / context backward -> energy backward (d_enc += alpha (x) dctx is NOT done per
@@ -537,7 +578,7 @@ class AttentionSeq2Seq(ModelBase):
         elif dk2d is not None:
             ops.gemm(dk2d, self._wk(), transB=True, out=denc.view(T * Bp, E2), accumulate=True)
         # bridge
-        dinit = torch.cat([dc_next, dh_next], dim=1).contiguous()
+        dinit = dh_next if gru else torch.cat([dc_next, dh_next], dim=1).contiguous()
         dbi = ops.gemm(dinit, st['bridge/fully_connected/weights'], transB=True)
         H = self.encoder_num_units
         dcf = torch.stack([dbi[:, :H], dbi[:, 2 * H:3 * H]]).contiguous()
@@ -546,15 +587,30 @@ class AttentionSeq2Seq(ModelBase):
         side_keep = [t for t in (dec_in, dpre_all, dpeep_all, dqz_all, dv_all, dwfil_rows, dfilt_rows, dkeys, enc,
                                  d_in_all, av_in, dinit, tp['bi'], tp['ids'], tp['emb_mask'], dk16, tp['enc_att'])
                      if t is not None]
-        with ops.side_lane(dev, keep=side_keep, lane=1):
-            if b16:     # 84 GFLOP at cfg D: 1.38 ms on the fp32 pipe beside the top encoder layer's BPTT
+        with ops.side_lane(dev, keep=side_keep + ([loop['gates_all']] if gru else []), lane=1):
+            if gru:
+                # fp32 on the master weights, also in a bf16-operand model.  One product for everything the image W3 =
+                # W_g | W_c[x rows] multiplied: dW3 = dec_in^T [dr | du | dp]; the candidate kernel's h-rows saw r*h
+                # (the fourth block of gates_all), not h, so they are a product of their own
+                Dx = Em + E2
+                dp2d = dpre_all.view(To * Bp, 3 * U)
+                dW3 = ops.gemm(dec_in.view(To * Bp, -1), dp2d, transA=True)
+                db3 = ops.colsum(dp2d)
+                st.g(D + 'gru_cell/gates/kernel').copy_(dW3[:, :2 * U])
+                st.g(D + 'gru_cell/gates/bias').copy_(db3[:2 * U])
+                st.g(D + 'gru_cell/candidate/kernel')[:Dx].copy_(dW3[:Dx, 2 * U:])
+                st.g(D + 'gru_cell/candidate/bias').copy_(db3[2 * U:])
+                rh = loop['gates_all'].view(To * Bp, 4 * U)[:, 3 * U:].contiguous()
+                ops.gemm(rh, dp2d[:, 2 * U:].contiguous(), transA=True, out=st.g(D + 'gru_cell/candidate/kernel')[Dx:])
+            elif b16:     # 84 GFLOP at cfg D: 1.38 ms on the fp32 pipe beside the top encoder layer's BPTT
                 ops.gemm(dec_in.view(To * Bp, -1).to(torch.bfloat16), dpre_all.view(To * Bp, 4 * U).to(torch.bfloat16),
                          transA=True, out=st.g(D + 'lstm_cell/kernel'))
             else:
                 ops.gemm(dec_in.view(To * Bp, -1), dpre_all.view(To * Bp, 4 * U), transA=True,
                          out=st.g(D + 'lstm_cell/kernel'))
-            ops.colsum(dpre_all.view(To * Bp, 4 * U), out=st.g(D + 'lstm_cell/bias'))
-            if self.use_peephole:
+            if not gru:
+                ops.colsum(dpre_all.view(To * Bp, 4 * U), out=st.g(D + 'lstm_cell/bias'))
+            if has_peep:
                 dp = ops.colsum(dpeep_all.view(To * Bp, 3 * U))
                 st.g(D + 'lstm_cell/w_i_diag').copy_(dp[:U])
                 st.g(D + 'lstm_cell/w_f_diag').copy_(dp[U:2 * U])
@@ -623,8 +679,9 @@ class AttentionSeq2Seq(ModelBase):
         dec_in[0, :, :Em].copy_(emb0)
         dec_in[0, :, Em:Em + E2].zero_()
         dec_in[0, :, Em + E2:].copy_(h)
-        c_all, h_all = f32(To + 1, Bp, U), f32(To + 1, Bp, U)
-        c_all[0].copy_(c)
+        c_all, h_all = (None if self.gru_decoder else f32(To + 1, Bp, U)), f32(To + 1, Bp, U)
+        if c is not None:
+            c_all[0].copy_(c)
         h_all[0].copy_(h)
         live = torch.zeros((To + 1, Bp), dtype=torch.float32, device=dev)
         live[0, :B] = 1.0                                    # rows B.. are the zero-length padding of the batch tile
@@ -632,8 +689,6 @@ class AttentionSeq2Seq(ModelBase):
                     carry_alpha=int(self.carry_alpha), taps=int(st[AT + 'filter'].shape[0]) if self.carry_alpha else 0,
                     enc_dtype=ops.dtype_id(enc_att.dtype), forget_bias=1.0,
                     cell_clip=float(self.clip_activation_decoder or 0.0), sharpening=float(self.sharpening_factor),
-                    W_cell=self._w_cell(), b_cell=st[D + 'lstm_cell/bias'], cell_bf16=(self.dtype == ASR_BF16),
-                    peep=self._peep(),
                     W_q=self._wq() if has_q else None,
                     b_q=st[AT + 'W_filter/biases'] if (has_q and self.attention_type in AL.HAS_FILTER) else None,
                     v=st[AT + 'v_a'] if self.att_mode == 0 else None, keys=keys, enc=enc_att, seq_len=seq_p,
@@ -642,7 +697,8 @@ class AttentionSeq2Seq(ModelBase):
                     alpha_zero=torch.zeros((Bp, T), dtype=torch.float32, device=dev) if self.carry_alpha else None,
                     live=live, dmask=None, dec_in=dec_in, av_in=f32(To, Bp, U + E2), alpha_all=f32(To, Bp, T),
                     snorm_all=f32(To, Bp) if self.sigmoid_smoothing else None,
-                    gates_all=f32(1, Bp, 4 * U), craw_all=f32(1, Bp, U), c_all=c_all, h_all=h_all, qz_all=f32(1, Bp, A))
+                    gates_all=f32(1, Bp, 4 * U), craw_all=f32(1, Bp, U), c_all=c_all, h_all=h_all, qz_all=f32(1, Bp, A),
+                    **self._cell_fields(self._peep()))
         out = ops.att_decoder_infer(loop, st[D + 'attentional_vector/weights'], st[D + 'output_layer/weights'],
                                     st[D + 'output_layer/biases'], st['output_embedding/W_embedding'], self.eos_index,
                                     n_live=B)
@@ -660,6 +716,8 @@ class AttentionSeq2Seq(ModelBase):
         T, Bp, E2 = enc.shape
         cf, hf = self.encoder._final_ch
         _, c, h = self._bridge(cf, hf, B)
+        if self.gru_decoder:
+            raise ValueError('decoder_type="gru" decodes through the native loops only (native=True)')
         layer = self.attention_layer(time_major_inputs=True)
         cell = LSTMDecoderCell(st, self.decoder_num_units, self.use_peephole, self.clip_activation_decoder,
                                kernel=self._w_cell())
@@ -715,14 +773,15 @@ class AttentionSeq2Seq(ModelBase):
         dec_in[0, :, Em:Em + E2].zero_()
         dec_in[0, :, Em + E2:].copy_(h0)
         c_all, h_all = f32(2, R, U), f32(2, R, U)
-        c_all[0].copy_(c.index_select(0, rows))
+        if c is not None:
+            c_all[0].copy_(c.index_select(0, rows))
+        else:                                 # GRU decoder: no cell state; the re-ordering gathers a block of zeros
+            c_all.zero_()
         h_all[0].copy_(h0)
         loop = dict(To=To, B=R, T=T, U=U, Em=Em, E2=E2, A=A, att_mode=self.att_mode, has_query_fc=int(has_q),
                     carry_alpha=int(self.carry_alpha), taps=int(st[AT + 'filter'].shape[0]) if self.carry_alpha else 0,
                     enc_dtype=ops.dtype_id(enc_att.dtype), forget_bias=1.0,
                     cell_clip=float(self.clip_activation_decoder or 0.0), sharpening=float(self.sharpening_factor),
-                    W_cell=self._w_cell(), b_cell=st[D + 'lstm_cell/bias'], cell_bf16=(self.dtype == ASR_BF16),
-                    peep=self._peep(),
                     W_q=self._wq() if has_q else None,
                     b_q=st[AT + 'W_filter/biases'] if (has_q and self.attention_type in AL.HAS_FILTER) else None,
                     v=st[AT + 'v_a'] if self.att_mode == 0 else None, keys=keys, enc=enc_att,
@@ -732,7 +791,8 @@ class AttentionSeq2Seq(ModelBase):
                     live=torch.ones((R,), dtype=torch.float32, device=dev), dmask=None, dec_in=dec_in,
                     av_in=f32(1, R, U + E2), alpha_all=f32(1, R, T),
                     snorm_all=f32(1, R) if self.sigmoid_smoothing else None,
-                    gates_all=f32(1, R, 4 * U), craw_all=f32(1, R, U), c_all=c_all, h_all=h_all, qz_all=f32(1, R, A))
+                    gates_all=f32(1, R, 4 * U), craw_all=f32(1, R, U), c_all=c_all, h_all=h_all, qz_all=f32(1, R, A),
+                    **self._cell_fields(self._peep()))
         head = (st[D + 'attentional_vector/weights'], st[D + 'output_layer/weights'], st[D + 'output_layer/biases'],
                 st['output_embedding/W_embedding'], self.eos_index)
         if lm_weight:
@@ -792,6 +852,14 @@ class AttentionSeq2Seq(ModelBase):
         lm, lm_weight (EXTENSION): shallow fusion with an RNNLM (models/lm) over the same classes on the same device --
         lm_weight > 0 needs lm, has the native form only and runs the beam search on fused scores at any beam width (1 is
         a width-1 fused search), alone or together with ctc_weight; lm None or lm_weight 0 is everything above, untouched."""
+        if self.gru_decoder and ctc_weight:
+            raise ValueError('ctc_weight > 0 is not available with decoder_type="gru" (the joint search runs the LSTM '
+                             'decoder only)')
+        if self.gru_decoder and not native:
+            raise ValueError('decoder_type="gru" decodes through the native loops only (native=True)')
+        if self.gru_decoder and (lm is not None or lm_weight):
+            raise ValueError('lm / lm_weight are not available with decoder_type="gru" (the LM-fused search runs the LSTM '
+                             'decoder only)')
         lam = check_ctc_weight(ctc_weight)
         mu = self._check_lm(lm, lm_weight)
         if lam != 0.0 and not self._has_ctc_head:

@@ -2067,6 +2067,8 @@ def _cell_gemm_image(h, a):
     product and LSTM cell are one launch (asr_lstm_cell_gemm_fwd).  a['cell_bf16'] (bf16-operand models): the bf16 images
     instead (asr_lstm_cell_gemm_*_h: forward product + cell, backward product)."""
     Din = a['Em'] + a['E2'] + a['U']
+    if a.get('gru') is not None:          # the GRU cell has its own image (_att_gru_struct)
+        return
     if not (FUSED_CELL_GEMM and h.lib.asr_lstm_cell_gemm_ok(int(a['B']), Din, int(a['U']), Din)):
         return
     if a.get('cell_bf16') and BF16_CELL_WEIGHTS and a['U'] % 16 == 0:
@@ -2085,6 +2087,10 @@ def att_decoder_fwd(a):
         a['work'] = _f32((a['B'] * (5 * a['U'] + a['T'] + a['E2']),), a['dec_in'].device)
     _cell_gemm_image(h, a)
     st = _att_decoder_struct(a)
+    if a.get('gru') is not None:          # decoder_type 'gru': the same loop around the GRU cell's launches
+        g = _att_gru_struct(a)
+        h.check(h.lib.asr_att_decoder_fwd_gru(h.h, C.byref(st), C.byref(g), _s()), 'asr_att_decoder_fwd_gru')
+        return
     h.check(h.lib.asr_att_decoder_fwd(h.h, C.byref(st), _s()), 'asr_att_decoder_fwd')
 
 
@@ -2146,6 +2152,10 @@ def att_decoder_bwd(a):
     a['work'] = _f32((a['B'] * (5 * a['U'] + 3 * a['T'] + a['E2']),), a['dec_in'].device)
     _cell_gemm_image(h, a)
     st = _att_decoder_struct(a)
+    if a.get('gru') is not None:          # dpre_all is [To,B,3U] = dr | du | dp there, dc0 is not written
+        g = _att_gru_struct(a)
+        h.check(h.lib.asr_att_decoder_bwd_gru(h.h, C.byref(st), C.byref(g), _s()), 'asr_att_decoder_bwd_gru')
+        return
     h.check(h.lib.asr_att_decoder_bwd(h.h, C.byref(st), _s()), 'asr_att_decoder_bwd')
 
 
@@ -2182,7 +2192,12 @@ def att_decoder_infer(a, W_av, W_out, b_out, embedding, eos, n_live, check_every
     f.C2, f.eos, f.check_every = int(C2), int(eos), int(check_every or 0)
     f.host_live_count = host.data_ptr() if host is not None else None
     issued = C.c_int(0)
-    h.check(h.lib.asr_att_decoder_infer(h.h, C.byref(st), C.byref(f), C.byref(issued), _s()), 'asr_att_decoder_infer')
+    if a.get('gru') is not None:
+        g = _att_gru_struct(a)
+        h.check(h.lib.asr_att_decoder_infer_gru(h.h, C.byref(st), C.byref(g), C.byref(f), C.byref(issued), _s()),
+                'asr_att_decoder_infer_gru')
+    else:
+        h.check(h.lib.asr_att_decoder_infer(h.h, C.byref(st), C.byref(f), C.byref(issued), _s()), 'asr_att_decoder_infer')
     out['steps_issued'] = issued.value
     out['_host'] = host                      # keeps the pinned words alive until the caller has synchronised
     return out
@@ -2337,7 +2352,13 @@ def att_decoder_beam(a, W_av, W_out, b_out, embedding, eos, beam_width, length_p
     h, st, f, m, out, scratch, host = _beam_loop_call('att_decoder_beam', a, W_av, W_out, b_out, embedding, eos, W,
                                                       length_penalty_weight, check_every)
     issued = C.c_int(0)
-    h.check(h.lib.asr_att_decoder_beam(h.h, C.byref(st), C.byref(f), C.byref(m), C.byref(issued), _s()), 'asr_att_decoder_beam')
+    if a.get('gru') is not None:          # (c_all: zeros [2,R,U], gathered by the re-ordering as ever)
+        g = _att_gru_struct(a)
+        h.check(h.lib.asr_att_decoder_beam_gru(h.h, C.byref(st), C.byref(g), C.byref(f), C.byref(m), C.byref(issued), _s()),
+                'asr_att_decoder_beam_gru')
+    else:
+        h.check(h.lib.asr_att_decoder_beam(h.h, C.byref(st), C.byref(f), C.byref(m), C.byref(issued), _s()),
+                'asr_att_decoder_beam')
     return _beam_loop_done(out, issued, host, scratch)
 
 
@@ -2596,6 +2617,118 @@ def att_joint_counts(device=0):
 
 def reset_att_joint_counts(device=0):
     _reset_counts3('att_joint_counts', device)
+
+
+# ---------------------------------------------------------------- GRU decoder cell (decoder_type 'gru')
+GRU_CELL_GEMM = os.environ.get('ASR_DEC_GRU_GEMM', '1') != '0'   # A/B: 0 keeps every step on the four-launch form
+
+
+class _AttGru(C.Structure):
+    """struct asr_att_gru (include/asr_hip.h), field for field."""
+    _PTRS = ['W_g', 'b_g', 'W_c', 'b_c', 'W3']
+    _fields_ = [(n, C.c_void_p) for n in _PTRS] + [('fused', C.c_int)]
+
+
+def _att_gru_struct(a):
+    """The GRU block of a loop dict: a['gru'] = dict(W_g [Din,2U], b_g [2U], W_c [Din,U], b_c [U]) and, optional, W3 (the
+    image work space, made here when missing) and fused (False: the four-launch form at every shape)."""
+    gd = a['gru']
+    U, Din = int(a['U']), int(a['Em'] + a['E2'] + a['U'])
+    for n, shape in (('W_g', (Din, 2 * U)), ('b_g', (2 * U,)), ('W_c', (Din, U)), ('b_c', (U,))):
+        t = gd.get(n)
+        if t is None or not t.is_cuda or not t.is_contiguous() or t.dtype != torch.float32 or tuple(t.shape) != shape:
+            raise ValueError('att_decoder (gru): %s must be a contiguous fp32 device tensor of shape %r' % (n, shape))
+    if gd.get('W3') is None:
+        gd['W3'] = _f32(((Din + 1), 3 * U), a['dec_in'].device)
+    g = _AttGru()
+    for n in _AttGru._PTRS:
+        setattr(g, n, gd[n].data_ptr())
+    g.fused = int(bool(gd.get('fused', True)) and GRU_CELL_GEMM)
+    return g
+
+
+def gru_cell_prep(W_g, b_g, W_c, b_c):
+    """The image W3 [(Din + 1), 3U] the GRU cell's products read (asr_gru_cell_prep): W_g | W_c with its h-rows zeroed,
+    bias row last."""
+    h = _h(W_g)
+    Din, U = W_c.shape
+    for t, n in ((W_g, 'W_g'), (b_g, 'b_g'), (W_c, 'W_c'), (b_c, 'b_c')):
+        _chk(t, torch.float32, n)
+    if tuple(W_g.shape) != (Din, 2 * U) or tuple(b_g.shape) != (2 * U,) or tuple(b_c.shape) != (U,) or Din <= U:
+        raise ValueError('gru_cell_prep: W_g [Din,2U], b_g [2U], W_c [Din,U], b_c [U], Din > U')
+    out = _f32((Din + 1, 3 * U), W_g.device)
+    h.check(h.lib.asr_gru_cell_prep(h.h, _p(W_g), _p(b_g), _p(W_c), _p(b_c), Din, U, _p(out), _s()), 'asr_gru_cell_prep')
+    return out
+
+
+def gru_cell_gemm_ok(B, Din, U, ldx=None):
+    """Whether the two-launch form covers the shape (asr_gru_cell_gemm_ok): B <= 32, Din % 64 == 0, U % 16 == 0."""
+    from . import _lib
+    return bool(_lib.load().asr_gru_cell_gemm_ok(int(B), int(Din), int(U), int(Din if ldx is None else ldx)))
+
+
+def gru_cell_fwd(x, W3, W_c, h_prev, live, out_mask=None, fused=False, h_also=None, cell_out_also=None, out=None):
+    """One GRU decoder cell step (asr_gru_cell_fwd_ex, or asr_gru_cell_gemm_fwd when fused): x [B,Din] = input | h_prev (a
+    row block of a wider array is fine), W3 from gru_cell_prep, W_c the candidate kernel itself (its h-rows are read).
+    Returns (gates [B,4U] = r | u | c | r*h, h_out [B,U], cell_out [B,U]); h_also / cell_out_also / cell_out_also2: [B,U]
+    column blocks of wider arrays that receive h_out / cell_out as well.  out: the three result tensors, when the caller
+    brings its own (cell_out may itself be a column block of a wider array: the loops write it into av_in)."""
+    h = _h(x)
+    B, Din = x.shape
+    U = W_c.shape[1]
+    dev = x.device
+    if x.dtype != torch.float32 or x.stride(1) != 1:
+        raise ValueError('gru_cell_fwd: x must be fp32 with unit inner stride')
+    for t, n in ((W3, 'W3'), (W_c, 'W_c'), (h_prev, 'h_prev'), (live, 'live')):
+        _chk(t, torch.float32, n)
+    if tuple(W3.shape) != (Din + 1, 3 * U) or tuple(W_c.shape) != (Din, U) or tuple(h_prev.shape) != (B, U):
+        raise ValueError('gru_cell_fwd: shapes disagree')
+    gates, h_out, cell_out = out if out is not None else (_f32((B, 4 * U), dev), _f32((B, U), dev), _f32((B, U), dev))
+    hp, hld = _col_block(h_also, B, U, 'h_also')
+    cp, cld = _col_block(cell_out_also, B, U, 'cell_out_also')
+    op, old = _col_block(cell_out, B, U, 'cell_out')
+    W_ch = C.c_void_p(W_c.data_ptr() + (Din - U) * U * 4)
+    xp = C.c_void_p(x.data_ptr())
+    if fused:
+        h.check(h.lib.asr_gru_cell_gemm_fwd(h.h, xp, int(x.stride(0)), Din, _p(W3), W_ch, _p(h_prev), _p(live), _p(out_mask),
+                                            B, U, _p(gates), _p(h_out), op, old, hp, hld, cp, cld, _s()),
+                'asr_gru_cell_gemm_fwd')
+    else:
+        work = _f32((B, 4 * U), dev)
+        h.check(h.lib.asr_gru_cell_fwd_ex(h.h, xp, int(x.stride(0)), Din, _p(W3), W_ch, _p(h_prev), _p(live), _p(out_mask),
+                                          B, U, _p(gates), _p(h_out), op, old, hp, hld, cp, cld, _p(work), _s()),
+                'asr_gru_cell_fwd_ex')
+    return gates, h_out, cell_out
+
+
+def gru_cell_bwd(dcell, dh_c, gates, h_prev, W3, W_c, live, out_mask=None, dh_c2=None):
+    """One GRU decoder cell step backwards (asr_gru_cell_bwd).  Returns (dpre [B,3U] = dr | du | dp pre-activation
+    gradients, dh_prev_carry [B,U] -- WITHOUT d_in's h-columns --, d_in [B,Din])."""
+    h = _h(dcell)
+    B, U = dcell.shape
+    Din = W_c.shape[0]
+    dev = dcell.device
+    for t, n in ((dcell, 'dcell'), (dh_c, 'dh_c'), (gates, 'gates'), (h_prev, 'h_prev'), (W3, 'W3'), (W_c, 'W_c'), (live, 'live')):
+        _chk(t, torch.float32, n)
+    p2, ld2 = _col_block(dh_c2, B, U, 'dh_c2')
+    dpre, carry, d_in, work = _f32((B, 3 * U), dev), _f32((B, U), dev), _f32((B, Din), dev), _f32((2, B, U), dev)
+    W_ch = C.c_void_p(W_c.data_ptr() + (Din - U) * U * 4)
+    h.check(h.lib.asr_gru_cell_bwd(h.h, _p(dcell), _p(dh_c), p2, ld2, _p(out_mask), _p(live), _p(gates), _p(h_prev), _p(W3),
+                                   W_ch, B, Din, U, _p(dpre), _p(carry), _p(d_in), Din, _p(work), _s()), 'asr_gru_cell_bwd')
+    return dpre, carry, d_in
+
+
+_ATT_GRU_KEYS = ('fwd_fused', 'fwd_general', 'bwd')
+
+
+def att_gru_counts(device=0):
+    """GRU decoder steps on `device` since the last reset, summed over its handles (asr_att_gru_counts): two-launch forward
+    steps, four-launch forward steps, backward steps.  Host counters: no device work, no synchronisation."""
+    return _counts3('att_gru_counts', _ATT_GRU_KEYS, device)
+
+
+def reset_att_gru_counts(device=0):
+    _reset_counts3('att_gru_counts', device)
 
 
 # ---------------------------------------------------------------- shallow fusion with an RNN language model (an extension)
