@@ -1257,6 +1257,74 @@ int asr_att_decoder_beam_gru(asr_handle* h, const asr_att_decoder* a, const asr_
  * backward steps} (the loops and the single-step entry points both count). */
 int asr_att_gru_counts(asr_handle* h, unsigned long long* out3);
 int asr_reset_att_gru_counts(asr_handle* h);
+/* ---- multi-layer LSTM decoder (later within ABI 5, additive) ---------------------------------------------------- *
+ * decoder_num_layers = L > 1: the decoder cell is MultiRNNCell of L LSTMBlockCell(U), each in a DropoutWrapper(output
+ * keep).  Layer 0 is the cell of asr_att_decoder (input row embedding | previous context | its own previous h); upper
+ * layer l = 1 .. L-1 reads x_l = [ o_{l-1} | h_{l,k-1} ] (2U wide), o_l = mask_l * h_l; the top layer's o_{L-1} is the
+ * decoder's cell output (query, av_in[:, :U]).  A row with live == 0 keeps the state of every layer.  Everything behind
+ * the cell -- query FC, energies, softmax + context, the fused attention step, the heads, the selections -- is the
+ * code of the one-layer calls.  The upper layers run in fp32 on the weights given here, also where layer 0 streams bf16
+ * images.  One asr_att_stack_layer per upper layer, up[l-1] for layer l; step arrays as asr_att_decoder's:
+ *   W [2U,4U] (rows o_{l-1} then h; gate-major columns i, ci, f, o), b [4U], peep [3,U] or NULL, dmask [To,B,U] or NULL;
+ *   in [To,B,2U]: the saved input rows -- columns [0,U) written by the layer below at the same step, columns [U,2U) by the
+ *     layer itself at the step before; the caller fills in[0][:, U:] with the layer's initial h;
+ *   c, h [To+1,B,U] (row 0: the initial state); gates [To,B,4U], craw [To,B,U];
+ *   W_il: optional (2U+1)*4U floats of work space -- where asr_lstm_cell_gemm_ok(B, 2U, U, 2U) holds the loop writes the
+ *     layer's interleaved image there once per call and its step is ONE launch (asr_lstm_cell_gemm_fwd), elsewhere (and
+ *     without it) asr_gemm_act + asr_lstm_cell_fwd_ex;
+ *   backward only: dpre [To,B,4U], d_hin [To,B,U] (the h-columns of the step's dpre W^T: what the layer's step before
+ *     adds to its carried dh), dpeep [To,B,3U] or NULL (needed with peep), dc0, dh0 [B,U] (out: gradient w.r.t. the
+ *     layer's initial state).
+ * work (backward only): (L-1)*4*B*U + B*U floats -- per upper layer the carried dc / dh, two buffers each (ping-pong),
+ * and one [B,U] block of the generic form.
+ * Inference (asr_att_decoder_infer_stack): in / c / h as in training (To = max_decode_length), gates / craw ONE step.
+ * Beam (asr_att_decoder_beam_stack): in [2,R,2U], c / h [2,R,U] -- block 0 is what a step reads (the caller fills c, h
+ * and in[:, U:] with the initial state, each utterance's row W times), block 1 receives the step's outputs and
+ * asr_att_stack_reorder gathers it back by parent; gates / craw one step.
+ * Backward of step k (asr_att_decoder_bwd_stack): the top layer's cell backward takes the place of the one-layer
+ * loop's (fused with the query FC where that loop fuses it); then for l = L-2 .. 0
+ *     dx = dpre_{l+1}[k] W_{l+1}^T [B,2U];  d_hin_{l+1}[k] = dx[:, U:];  cell backward of layer l on  mask_l * dx[:, :U]
+ *     (+ carried dc_l, carried dh_l + d_hin_l[k+1]; layer 0: the h-columns of d_in_all[k+1])   ->   dpre_l[k]
+ * as ONE launch (exact-fp32 MFMA product, the cell in its epilogue) where asr_att_stack_bwd_ok(B, U) holds -- B <= 32,
+ * U % 16 == 0 -- and `fused` != 0, and as asr_gemm_act x 2 (the two column halves) + the plain cell backward launch at
+ * every other shape.  Layer 0's own d_in product follows as ever.  cell_clip is straight-through at every layer.  Weight
+ * gradients are the caller's, batched over the steps: dW_l = in_l^T dpre_l, db_l = column sums, peepholes from dpeep.
+ * Not with scheduled sampling, the joint or the LM-fused search (those loops run one layer). */
+#define ASR_ATT_STACK_MAX 7                     /* upper layers: decoder_num_layers <= 8 */
+typedef struct asr_att_stack_layer {
+  const float *W, *b, *peep, *dmask;
+  float *in, *c, *h, *gates, *craw, *W_il;
+  float *dpre, *d_hin, *dpeep, *dc0, *dh0;      /* backward only */
+} asr_att_stack_layer;
+typedef struct asr_att_stack {
+  int L;                                        /* decoder_num_layers, 2 .. ASR_ATT_STACK_MAX + 1 */
+  int fused;                                    /* 0: the generic backward form at every shape (A/B) */
+  asr_att_stack_layer up[ASR_ATT_STACK_MAX];    /* up[l-1]: layer l */
+  float *work;                                  /* backward only */
+} asr_att_stack;
+int asr_att_decoder_fwd_stack(asr_handle* h, const asr_att_decoder* a, const asr_att_stack* k, asr_stream s);
+int asr_att_decoder_bwd_stack(asr_handle* h, const asr_att_decoder* a, const asr_att_stack* k, asr_stream s);
+int asr_att_decoder_infer_stack(asr_handle* h, const asr_att_decoder* a, const asr_att_stack* k, const asr_att_infer* f,
+                                int* steps_issued, asr_stream s);
+int asr_att_decoder_beam_stack(asr_handle* h, const asr_att_decoder* a, const asr_att_stack* k, const asr_att_infer* f,
+                               const asr_att_beam* m, int* steps_issued, asr_stream s);
+/* One launch: for every upper layer, row r = b*W + w of block 0 of c, h [2,R,U] and of columns [U,2U) of in [2,R,2U]
+ * becomes row b*W + parent[r] of block 1 (out of place).  parent [B,W], each in [0, W). */
+int asr_att_stack_reorder(asr_handle* h, const asr_att_stack* k, const int32_t* parent, int B, int W, int U, asr_stream s);
+/* The backward of one lower layer at one step, on its own: dx [B,2U] = dpre_up [B,4U] W_up^T ([2U,4U]), d_hin_up [B,U] =
+ * dx[:, U:], and the cell backward (operands as asr_lstm_cell_bwd's, plus dh_next2 with row stride ld2 and use_mask, both
+ * may be NULL) on dx[:, :U].  fused != 0 and asr_att_stack_bwd_ok(B, U) (and 16-byte aligned dpre_up, W_up): the one-launch
+ * form; else the generic one (work: B*U floats). */
+int asr_att_stack_bwd_ok(int B, int U);
+int asr_att_stack_bwd_step(asr_handle* h, const float* dpre_up, const float* W_up, int B, int U, const float* dc_next,
+                           const float* dh_next, const float* dh_next2, int ld2, const float* gates, const float* c_raw,
+                           const float* c_prev, const float* peep, const float* live, const float* use_mask, float* dpre,
+                           float* dc_prev, float* dh_prev_carry, float* dpeep_rows, float* d_hin_up, float* work, int fused,
+                           asr_stream s);
+/* Upper-layer steps on this handle since the last reset: {forward on the image (one launch), forward as product + cell
+ * (two launches), backward fused (one launch), backward generic}. */
+int asr_att_stack_counts(asr_handle* h, unsigned long long* out4);
+int asr_reset_att_stack_counts(asr_handle* h);
 /* out[b, j] = x[b*ldx + j] + y[b*ldy + j], j < W (row blocks of wider arrays; out may alias x) */
 int asr_add_cols(asr_handle* h, const float* x, int ldx, const float* y, int ldy, float* out, int ldo, int B, int W,
                  asr_stream s);

@@ -207,6 +207,17 @@ SIGNATURES = {
     'asr_att_decoder_beam_gru': (_i, [_vp] * 7),
     'asr_att_gru_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
     'asr_reset_att_gru_counts': (_i, [_vp]),
+    # multi-layer LSTM decoder (later within ABI 5)
+    'asr_att_decoder_fwd_stack': (_i, [_vp] * 4),
+    'asr_att_decoder_bwd_stack': (_i, [_vp] * 4),
+    'asr_att_decoder_infer_stack': (_i, [_vp] * 6),
+    'asr_att_decoder_beam_stack': (_i, [_vp] * 7),
+    'asr_att_stack_reorder': (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    'asr_att_stack_bwd_ok': (_i, [_i, _i]),
+    'asr_att_stack_bwd_step': (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _vp, _vp, _vp, _i, _vp]),
+    'asr_att_stack_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
+    'asr_reset_att_stack_counts': (_i, [_vp]),
     'asr_seq_xent_ls': (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp]),
     'asr_add_cols': (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp]),
     'asr_tanh_fwd': (_i, [_vp, _vp, _vp, _sz, _vp]),

@@ -12,6 +12,7 @@
 // parts (keys, query, cell input projection, attentional vector, output layer and all their
 // gradients) run on asr_gemm, batched over all decoder steps wherever the recurrence allows.
 #include "common.h"
+#include "lstm_cell_bwd.h"
 #include <math.h>
 
 namespace {
@@ -90,20 +91,14 @@ __global__ void cell_bwd_kernel(const float* __restrict__ dh_out_use, const floa
   const float wci = peep ? peep[j] : 0.f, wcf = peep ? peep[U + j] : 0.f, wco = peep ? peep[2 * U + j] : 0.f;
   const float c = c_raw[idx], cp = c_prev[idx];
   const float dh = (use_mask ? dh_out_use[idx] * use_mask[idx] : dh_out_use[idx]) + dhn;
-  const float tc = tanhf(c);
-  const float d_o = dh * tc * o * (1.f - o);
-  const float dct = dc_next[idx] + dh * o * (1.f - tc * tc) + d_o * wco;
-  const float dc = (clip > 0.f && fabsf(c) >= clip) ? 0.f : dct;
-  const float d_g = dc * i * (1.f - g * g);
-  const float d_i = dc * g * i * (1.f - i);
-  const float d_f = dc * cp * f * (1.f - f);
-  dp[j] = d_i; dp[U + j] = d_g; dp[2 * U + j] = d_f; dp[3 * U + j] = d_o;
-  dc_prev[idx] = dc * f + d_i * wci + d_f * wcf;
+  const CellBwdElem r = lstm_cell_bwd_elem(dh, dc_next[idx], i, g, f, o, c, cp, wci, wcf, wco, clip);   // (lstm_cell_bwd.h)
+  dp[j] = r.d_i; dp[U + j] = r.d_g; dp[2 * U + j] = r.d_f; dp[3 * U + j] = r.d_o;
+  dc_prev[idx] = r.dc_prev;
   dh_prev_carry[idx] = 0.f;   // h_prev enters only through the input projection (dpre W^T)
   if (dpeep_rows) {
-    dpeep_rows[(size_t)b * 3 * U + j] = d_i * cp;
-    dpeep_rows[(size_t)b * 3 * U + U + j] = d_f * cp;
-    dpeep_rows[(size_t)b * 3 * U + 2 * U + j] = d_o * c;
+    dpeep_rows[(size_t)b * 3 * U + j] = r.d_i * cp;
+    dpeep_rows[(size_t)b * 3 * U + U + j] = r.d_f * cp;
+    dpeep_rows[(size_t)b * 3 * U + 2 * U + j] = r.d_o * c;
   }
 }
 
@@ -1611,12 +1606,7 @@ namespace {
 // One workgroup = 16 utterances x 16 units; wave w multiplies the 64-wide slice w of A (A <= 512), its A fragment
 // being the SUM of the chunk partials read straight from the energy kernel's scratch; the tiles meet in LDS in a fixed
 // order.  Column-tile 0 also writes dqz / dv_rows (the weight gradients after the loop need them).
-struct CellBwdArgs {
-  const float *dc_next, *dh_next, *dh_next2, *gates, *c_raw, *c_prev, *peep, *live, *use_mask;
-  float *dpre, *dc_prev, *dh_prev_carry, *dpeep_rows;
-  int ld2;
-  float clip;
-};
+// (CellBwdArgs: lstm_cell_bwd.h)
 // NTL MFMA column tiles (16 NTL units) per workgroup.  Measured on the cfg D shard (A = 128, U = 512, 25 chunks): NTL = 1
 // (34 workgroups x 2 row groups) 54.3 ms for the reverse pass, NTL = 4 (10 x 2) 55.4, the three separate launches 55.0.
 constexpr int DQ_NTL = 1, DQ_CT = 16 * DQ_NTL;
@@ -1759,22 +1749,16 @@ __global__ __launch_bounds__(512) void att_dq_cell_bwd_kernel(const float* __res
       }
       continue;
     }
-    const float gi = e_g[h2][0], gg = e_g[h2][1], gf = e_g[h2][2], go = e_g[h2][3];
     const float dh = dcell * e_mask[h2] + e_dhn[h2];
-    const float tc = tanhf(e_cr[h2]);
-    const float d_o = dh * tc * go * (1.f - go);
-    const float dct = e_dcn[h2] + dh * go * (1.f - tc * tc) + d_o * e_w[h2][2];
-    const float dc = (c.clip > 0.f && fabsf(e_cr[h2]) >= c.clip) ? 0.f : dct;     // a clamped state passes nothing back
-    const float d_g = dc * gi * (1.f - gg * gg);
-    const float d_i = dc * gg * gi * (1.f - gi);
-    const float d_f = dc * e_cp[h2] * gf * (1.f - gf);
-    dp[j] = d_i; dp[U + j] = d_g; dp[2 * U + j] = d_f; dp[3 * U + j] = d_o;
-    c.dc_prev[bu] = dc * gf + d_i * e_w[h2][0] + d_f * e_w[h2][1];
+    const CellBwdElem r = lstm_cell_bwd_elem(dh, e_dcn[h2], e_g[h2][0], e_g[h2][1], e_g[h2][2], e_g[h2][3], e_cr[h2],
+                                             e_cp[h2], e_w[h2][0], e_w[h2][1], e_w[h2][2], c.clip);
+    dp[j] = r.d_i; dp[U + j] = r.d_g; dp[2 * U + j] = r.d_f; dp[3 * U + j] = r.d_o;
+    c.dc_prev[bu] = r.dc_prev;
     c.dh_prev_carry[bu] = 0.f;
     if (c.dpeep_rows) {
-      c.dpeep_rows[(size_t)b * 3 * U + j] = d_i * e_cp[h2];
-      c.dpeep_rows[(size_t)b * 3 * U + U + j] = d_f * e_cp[h2];
-      c.dpeep_rows[(size_t)b * 3 * U + 2 * U + j] = d_o * e_cr[h2];
+      c.dpeep_rows[(size_t)b * 3 * U + j] = r.d_i * e_cp[h2];
+      c.dpeep_rows[(size_t)b * 3 * U + U + j] = r.d_f * e_cp[h2];
+      c.dpeep_rows[(size_t)b * 3 * U + 2 * U + j] = r.d_o * e_cr[h2];
     }
   }
 }
@@ -1815,6 +1799,10 @@ static int cell_bwd_launch(asr_handle* h, const float* dh_use, const float* dc_n
                      dh_next2, ld2, use_mask, clip);
   ASR_CHECK_LAUNCH(h, "asr_lstm_cell_bwd");
   return ASR_OK;
+}
+int asr_lstm_cell_bwd_args(asr_handle* h, const float* dh_use, const CellBwdArgs& c, int B, int U, asr_stream s) {
+  return cell_bwd_launch(h, dh_use, c.dc_next, c.dh_next, c.gates, c.c_raw, c.c_prev, c.peep, c.live, B, U, c.dpre, c.dc_prev,
+                         c.dh_prev_carry, c.dpeep_rows, c.dh_next2, c.ld2, c.use_mask, c.clip, s);
 }
 extern "C" int asr_lstm_cell_bwd(asr_handle* h, const float* dh_use, const float* dc_next, const float* dh_next,
                                  const float* gates, const float* c_raw, const float* c_prev, const float* peep,
@@ -2218,7 +2206,14 @@ extern "C" int asr_add_cols(asr_handle* h, const float* x, int ldx, const float*
 
 // g != nullptr (the *_gru entry points): the cell is the GRU of gru_decoder.hip -- the LSTM cell's weights, its raw cell
 // state, c and dc0 are not asked for, the GRU block is.  g == nullptr is every call this file has always made.
-static int dec_check(asr_handle* h, const asr_att_decoder* a, bool bwd, const asr_att_gru* g = nullptr) {
+// sk != nullptr (the *_stack entry points): upper LSTM layers above the cell (dec_stack.hip), checked there.
+static int dec_check(asr_handle* h, const asr_att_decoder* a, bool bwd, const asr_att_gru* g = nullptr,
+                     const asr_att_stack* sk = nullptr) {
+  if (sk && a) {
+    if (g) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder: a stack runs LSTM cells only");
+    ASR_TRY(asr_stack_dec_check(h, a, sk, bwd));
+    return dec_check(h, a, bwd);
+  }
   if (g && a) {
     asr_att_decoder d = *a;                                // the LSTM-only fields pass the checks below
     d.W_cell = d.b_cell = g->W_g;
@@ -2293,7 +2288,9 @@ static inline bool dec_cell_gemm_h(const asr_att_decoder* a) {
   return a->W_cell_h && asr_lstm_cell_gemm_ok(a->B, Din, a->U, Din) && a->U % 16 == 0 && ((uintptr_t)a->dec_in) % 16 == 0 &&
          ((uintptr_t)a->W_cell_h) % 16 == 0;
 }
-static int dec_cell_image(asr_handle* h, const asr_att_decoder* a, asr_stream s, const asr_att_gru* g = nullptr) {
+static int dec_cell_image(asr_handle* h, const asr_att_decoder* a, asr_stream s, const asr_att_gru* g = nullptr,
+                          const asr_att_stack* sk = nullptr) {
+  if (sk) ASR_TRY(asr_stack_dec_image(h, a, sk, s));       // (the upper layers' images; layer 0's below, as ever)
   if (g) return asr_gru_dec_image(h, a, g, s);
   if (dec_cell_gemm_h(a)) return asr_lstm_cell_gemm_prep_h(h, a->W_cell, a->b_cell, a->Em + a->E2 + a->U, a->U, a->W_cell_h, s);
   if (!dec_cell_gemm(a)) return ASR_OK;
@@ -2304,8 +2301,10 @@ static int dec_cell_image(asr_handle* h, const asr_att_decoder* a, asr_stream s,
 // the step arrays that carry the recurrence (dec_in, av_in, c / h, alpha, live); ks the saved activations only the
 // backward reads (gates, raw cell, query: the inference loop reuses row 0).
 // g != nullptr: the cell launches are the GRU's (asr_gru_dec_fwd_step, same scatter targets); everything behind them is shared.
+// sk != nullptr: layer 0's masked output goes to the input row of layer 1 instead of av / the query, and the upper layers'
+// cell launches follow it (asr_stack_dec_fwd_step: the top layer writes av[:, :U] and the query).
 static int dec_fwd_step(asr_handle* h, const asr_att_decoder* a, int k, int ks, bool more, asr_stream s,
-                        const asr_att_gru* g = nullptr) {
+                        const asr_att_gru* g = nullptr, const asr_att_stack* sk = nullptr) {
   const int B = a->B, U = a->U, T = a->T, E2 = a->E2, Em = a->Em, A = a->A;
   const int Din = Em + E2 + U, Dav = U + E2;
   float* pre = a->work;                                    // [B,4U]
@@ -2317,6 +2316,9 @@ static int dec_fwd_step(asr_handle* h, const asr_att_decoder* a, int k, int ks, 
   float* av = a->av_in + (size_t)k * B * Dav;
   float* qz = a->qz_all + (size_t)ks * B * A;
   // the cell output (times its dropout mask) lands in av[:, :U]; without a query FC it IS the query
+  float* q0 = (a->has_query_fc || sk) ? nullptr : qz;
+  float* out0 = sk ? sk->up[0].in + (size_t)k * B * 2 * U : av;
+  const int ld0 = sk ? 2 * U : Dav;
   if (g) {
     ASR_TRY(asr_gru_dec_fwd_step(h, a, g, k, ks, dnext, qz, s));
   } else if (dec_cell_gemm_h(a)) {  // product + cell as one launch on the bf16 fragment image (dec_cell_image)
@@ -2325,16 +2327,16 @@ static int dec_fwd_step(asr_handle* h, const asr_att_decoder* a, int k, int ks, 
                                      a->h_all + (size_t)k * B * U, a->peep, a->live + (size_t)k * B, B, U, a->forget_bias,
                                      a->cell_clip, a->gates_all + (size_t)ks * B * 4 * U, a->craw_all + (size_t)ks * B * U,
                                      a->c_all + (size_t)(k + 1) * B * U, a->h_all + (size_t)(k + 1) * B * U, hraw,
-                                     a->dmask ? a->dmask + (size_t)k * B * U : nullptr, a->has_query_fc ? nullptr : qz,
-                                     dnext ? dnext + Em + E2 : nullptr, Din, av, Dav, s));
+                                     a->dmask ? a->dmask + (size_t)k * B * U : nullptr, q0,
+                                     dnext ? dnext + Em + E2 : nullptr, Din, out0, ld0, s));
   } else if (dec_cell_gemm(a)) {    // ... on the fp32 interleaved weight image
     h->att_counts[ASR_ATT_FWD_CELL_F32IMG] += 1;
     ASR_TRY(asr_lstm_cell_gemm_fwd(h, din, Din, Din, a->W_cell_il, a->b_cell ? 1 : 0, a->c_all + (size_t)k * B * U,
                                    a->h_all + (size_t)k * B * U, a->peep, a->live + (size_t)k * B, B, U, a->forget_bias,
                                    a->cell_clip, a->gates_all + (size_t)ks * B * 4 * U, a->craw_all + (size_t)ks * B * U,
                                    a->c_all + (size_t)(k + 1) * B * U, a->h_all + (size_t)(k + 1) * B * U, hraw,
-                                   a->dmask ? a->dmask + (size_t)k * B * U : nullptr, a->has_query_fc ? nullptr : qz,
-                                   dnext ? dnext + Em + E2 : nullptr, Din, av, Dav, s));
+                                   a->dmask ? a->dmask + (size_t)k * B * U : nullptr, q0,
+                                   dnext ? dnext + Em + E2 : nullptr, Din, out0, ld0, s));
   } else {
     h->att_counts[ASR_ATT_FWD_CELL_GEMM] += 1;
     ASR_TRY(asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, B, 4 * U, Din, din, Din, a->W_cell, 4 * U, pre, 4 * U, a->b_cell, 0, 0, s));
@@ -2342,9 +2344,10 @@ static int dec_fwd_step(asr_handle* h, const asr_att_decoder* a, int k, int ks, 
                                  a->live + (size_t)k * B, B, U, a->forget_bias, a->cell_clip,
                                  a->gates_all + (size_t)ks * B * 4 * U, a->craw_all + (size_t)ks * B * U,
                                  a->c_all + (size_t)(k + 1) * B * U, a->h_all + (size_t)(k + 1) * B * U, hraw,
-                                 a->dmask ? a->dmask + (size_t)k * B * U : nullptr, a->has_query_fc ? nullptr : qz,
-                                 dnext ? dnext + Em + E2 : nullptr, Din, av, Dav, s));
+                                 a->dmask ? a->dmask + (size_t)k * B * U : nullptr, q0,
+                                 dnext ? dnext + Em + E2 : nullptr, Din, out0, ld0, s));
   }
+  if (sk) ASR_TRY(asr_stack_dec_fwd_step(h, a, sk, k, ks, more, a->has_query_fc ? nullptr : qz, s));
   if (a->has_query_fc)
     ASR_TRY(asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, B, A, U, av, Dav, a->W_q, a->ld_wq, qz, A, a->b_q, 0, 0, s));
   if (att_fused_step(h, a, qz, a->alpha_all + (size_t)k * B * T, ctx, av + U, Dav, dnext ? dnext + Em : nullptr, Din, s)) {
@@ -2365,13 +2368,14 @@ static int dec_fwd_step(asr_handle* h, const asr_att_decoder* a, int k, int ks, 
   return ASR_OK;
 }
 
-static int dec_fwd_loop(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, asr_stream s) {
+static int dec_fwd_loop(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, asr_stream s,
+                        const asr_att_stack* sk = nullptr) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  ASR_TRY(dec_check(h, a, false, g));
+  ASR_TRY(dec_check(h, a, false, g, sk));
   const int B = a->B, U = a->U, T = a->T, E2 = a->E2, Em = a->Em, A = a->A;
   const int Din = Em + E2 + U, Dav = U + E2;
-  ASR_TRY(dec_cell_image(h, a, s, g));
-  for (int k = 0; k < a->To; ++k) ASR_TRY(dec_fwd_step(h, a, k, k, k + 1 < a->To, s, g));
+  ASR_TRY(dec_cell_image(h, a, s, g, sk));
+  for (int k = 0; k < a->To; ++k) ASR_TRY(dec_fwd_step(h, a, k, k, k + 1 < a->To, s, g, sk));
   (void)B; (void)U; (void)T; (void)E2; (void)Em; (void)A; (void)Din; (void)Dav;
   return ASR_OK;
 }
@@ -2382,6 +2386,11 @@ extern "C" int asr_att_decoder_fwd_gru(asr_handle* h, const asr_att_decoder* a, 
   if (!h) return ASR_ERR_INVALID_ARG;
   if (!g) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_fwd_gru: bad arguments");
   return dec_fwd_loop(h, a, g, s);
+}
+extern "C" int asr_att_decoder_fwd_stack(asr_handle* h, const asr_att_decoder* a, const asr_att_stack* sk, asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  if (!sk) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_fwd_stack: bad arguments");
+  return dec_fwd_loop(h, a, nullptr, s, sk);
 }
 
 // ---------------------------------------------------------------- greedy inference loop, native
@@ -2438,9 +2447,9 @@ __global__ __launch_bounds__(256) void att_infer_select_kernel(const float* __re
 }  // namespace
 
 static int dec_infer_loop(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, const asr_att_infer* f,
-                          int* steps_issued, asr_stream s) {
+                          int* steps_issued, asr_stream s, const asr_att_stack* sk = nullptr) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  ASR_TRY(dec_check(h, a, false, g));
+  ASR_TRY(dec_check(h, a, false, g, sk));
   if (!f || !f->W_av || !f->W_out || !f->embedding || !f->live || !f->av_all || !f->logits_all || !f->ids_all ||
       !f->live_count || f->C2 < 1 || f->eos < 0 || f->live != a->live || a->dmask)
     ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_infer: bad arguments");
@@ -2466,7 +2475,7 @@ static int dec_infer_loop(asr_handle* h, const asr_att_decoder* a, const asr_att
         ASR_FAIL(h, ASR_ERR_HIP, "asr_att_decoder_infer: event");
       }
   }
-  int rc = dec_cell_image(h, a, s, g), k = 0;
+  int rc = dec_cell_image(h, a, s, g, sk), k = 0;
   for (; rc == ASR_OK && k < To; ++k) {
     if (every && k % every == 0 && k > 0) {
       const int c = k / every;                             // this check point; c - 1 was recorded one interval ago
@@ -2482,7 +2491,7 @@ static int dec_infer_loop(asr_handle* h, const asr_att_decoder* a, const asr_att
     }
     const bool more = k + 1 < To;
     // (saved-activation arrays the backward would need are reused every step: index 0)
-    if ((rc = dec_fwd_step(h, a, k, 0, more, s, g)) != ASR_OK) break;
+    if ((rc = dec_fwd_step(h, a, k, 0, more, s, g, sk)) != ASR_OK) break;
     float* av = f->av_all + (size_t)k * B * U;
     float* lg = f->logits_all + (size_t)k * B * C2;
     if ((rc = asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, B, U, Dav, a->av_in + (size_t)k * B * Dav, Dav, f->W_av, U, av, U, nullptr,
@@ -2509,6 +2518,12 @@ extern "C" int asr_att_decoder_infer_gru(asr_handle* h, const asr_att_decoder* a
   if (!h) return ASR_ERR_INVALID_ARG;
   if (!g) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_infer_gru: bad arguments");
   return dec_infer_loop(h, a, g, f, steps_issued, s);
+}
+extern "C" int asr_att_decoder_infer_stack(asr_handle* h, const asr_att_decoder* a, const asr_att_stack* sk,
+                                           const asr_att_infer* f, int* steps_issued, asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  if (!sk) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_infer_stack: bad arguments");
+  return dec_infer_loop(h, a, nullptr, f, steps_issued, s, sk);
 }
 
 // ---------------------------------------------------------------- scheduled-sampling training loop, native
@@ -2611,13 +2626,13 @@ extern "C" int asr_att_decoder_fwd_ss(asr_handle* h, const asr_att_decoder* a, c
 // gathers as it always has.
 static int att_beam_loop(asr_handle* h, const asr_att_decoder* a_, const asr_att_infer* f, const asr_att_beam* m,
                          const asr_att_beam_ctc* j, const asr_att_lm* lm, int* steps_issued, asr_stream s,
-                         const asr_att_gru* g = nullptr) {
-  const char* who = g ? "asr_att_decoder_beam_gru" : lm ? "asr_att_decoder_beam_lm" : j ? "asr_att_decoder_beam_joint" : "asr_att_decoder_beam";
+                         const asr_att_gru* g = nullptr, const asr_att_stack* sk = nullptr) {
+  const char* who = sk ? "asr_att_decoder_beam_stack" : g ? "asr_att_decoder_beam_gru" : lm ? "asr_att_decoder_beam_lm" : j ? "asr_att_decoder_beam_joint" : "asr_att_decoder_beam";
   if (!a_ || !m) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "%s: bad arguments", who);
   asr_att_decoder d = *a_;
   if (d.carry_alpha) d.alpha_zero = m->alpha_prev;
   const asr_att_decoder* a = &d;
-  ASR_TRY(dec_check(h, a, false, g));
+  ASR_TRY(dec_check(h, a, false, g, sk));
   if (g && !a->c_all) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "%s: c_all (zeros [2,R,U]) is needed by the re-ordering", who);
   if (!f || !f->W_av || !f->W_out || !f->embedding || f->C2 < 1 || f->eos < 0 || f->eos >= f->C2 || a->dmask || m->W < 1 ||
       m->W > 32 || m->W > f->C2 || a->B % m->W != 0 || !m->word || !m->parent || !m->score || !m->log_probs || !m->finished ||
@@ -2654,7 +2669,7 @@ static int att_beam_loop(asr_handle* h, const asr_att_decoder* a_, const asr_att
   float* din1 = a->dec_in + (size_t)R * Din;
   float* c1 = a->c_all + (size_t)R * U;
   float* h1 = a->h_all + (size_t)R * U;
-  int rc = dec_cell_image(h, a, s, g), k = 0;
+  int rc = dec_cell_image(h, a, s, g, sk), k = 0;
   for (; rc == ASR_OK && k < To; ++k) {
     if (every && k % every == 0 && k > 0) {                // (see asr_att_decoder_infer)
       const int c = k / every;
@@ -2668,7 +2683,7 @@ static int att_beam_loop(asr_handle* h, const asr_att_decoder* a_, const asr_att
       if (hipMemcpyAsync(f->host_live_count + k, m->unfinished + k, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
           hipEventRecord(ev[c % NEV], st) != hipSuccess) { rc = ASR_ERR_HIP; break; }
     }
-    if ((rc = dec_fwd_step(h, a, 0, 0, true, s, g)) != ASR_OK) break;
+    if ((rc = dec_fwd_step(h, a, 0, 0, true, s, g, sk)) != ASR_OK) break;
     if ((rc = asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, R, U, Dav, a->av_in, Dav, f->W_av, U, m->av, U, nullptr, 0, 0, s)) != ASR_OK) break;
     if ((rc = asr_tanh_fwd(h, m->av, m->av, (size_t)R * U, s)) != ASR_OK) break;
     if ((rc = asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, R, C2, U, m->av, U, f->W_out, C2, m->logits, C2, f->b_out, 0, 0, s)) != ASR_OK) break;
@@ -2705,6 +2720,7 @@ static int att_beam_loop(asr_handle* h, const asr_att_decoder* a_, const asr_att
     if ((rc = asr_att_beam_reorder(h, m->parent + o, m->word + o, Bu, W, U, Em, E2, a->carry_alpha ? T : 0, C2, c1, h1, din1,
                                    a->carry_alpha ? a->alpha_all : nullptr, f->embedding, a->c_all, a->h_all, a->dec_in,
                                    a->carry_alpha ? m->alpha_prev : nullptr, s)) != ASR_OK) break;
+    if (sk && (rc = asr_att_stack_reorder(h, sk, m->parent + o, Bu, W, U, s)) != ASR_OK) break;   // the upper layers' rows
     if (lm) {
       const size_t lblk = (size_t)lm->L * R * lm->H;       // block 1 (the step's new state) -> block 0
       if ((rc = asr_lm_beam_reorder(h, m->parent + o, m->word + o, Bu, W, lm->L, lm->H, lm->Em_lm, C2, lm->c + lblk,
@@ -2746,12 +2762,22 @@ extern "C" int asr_att_decoder_beam_gru(asr_handle* h, const asr_att_decoder* a,
   if (!g) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_beam_gru: bad arguments");
   return att_beam_loop(h, a, f, m, nullptr, nullptr, steps_issued, s, g);
 }
+extern "C" int asr_att_decoder_beam_stack(asr_handle* h, const asr_att_decoder* a, const asr_att_stack* sk,
+                                          const asr_att_infer* f, const asr_att_beam* m, int* steps_issued, asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  if (!sk) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_beam_stack: bad arguments");
+  return att_beam_loop(h, a, f, m, nullptr, nullptr, steps_issued, s, nullptr, sk);
+}
 
 // g != nullptr (asr_att_decoder_bwd_gru): the cell backward and the cell-input product of a step are the GRU's
 // (asr_gru_dec_bwd_step); the query-FC backward in front of them is the unfused branch's.
-static int dec_bwd_loop(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, asr_stream s) {
+// sk != nullptr (asr_att_decoder_bwd_stack): the cell backward of a step is the TOP layer's; behind it, per lower layer,
+// the dx product of the layer above with that layer's cell backward (asr_stack_dec_bwd_lower), down to layer 0, whose
+// own cell-input product follows as ever.
+static int dec_bwd_loop(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, asr_stream s,
+                        const asr_att_stack* sk = nullptr) {
   if (!h) return ASR_ERR_INVALID_ARG;
-  ASR_TRY(dec_check(h, a, true, g));
+  ASR_TRY(dec_check(h, a, true, g, sk));
   const int B = a->B, U = a->U, T = a->T, E2 = a->E2, Em = a->Em, A = a->A, To = a->To;
   const int Din = Em + E2 + U;
   hipStream_t st = (hipStream_t)s;
@@ -2767,6 +2793,7 @@ static int dec_bwd_loop(asr_handle* h, const asr_att_decoder* a, const asr_att_g
   // loop having run with the same work space
   const bool cell_h = !g && dec_cell_gemm_h(a);
   if (g) ASR_TRY(asr_gru_dec_image(h, a, g, s));
+  if (sk) ASR_TRY(asr_stack_dec_bwd_begin(h, a, sk, s));
   if (cell_h) ASR_TRY(asr_lstm_cell_gemm_prep_h(h, a->W_cell, a->b_cell, Din, U, a->W_cell_h, s));
   int cur = 0;
   const float* dalpha_next = nullptr;
@@ -2812,16 +2839,17 @@ static int dec_bwd_loop(asr_handle* h, const asr_att_decoder* a, const asr_att_g
                          a->ld_wq % 4 == 0 && ((uintptr_t)a->W_q) % 16 == 0 && ((uintptr_t)dqz) % 16 == 0 &&
                          (!dv || ((uintptr_t)dv) % 16 == 0);
     h->att_counts[fused_q ? ASR_ATT_BWD_STEP_FUSED_Q : ASR_ATT_BWD_STEP_UNFUSED] += 1;
+    // layer 0's cell backward (the only one without a stack)
+    const CellBwdArgs ca0 = {dcs[cur], dhc[cur], dh2, a->gates_all + (size_t)k * B * 4 * U, a->craw_all + (size_t)k * B * U,
+                             a->c_all + (size_t)k * B * U, a->peep, a->live + (size_t)k * B, dmask,
+                             dpre, dcs[cur ^ 1], dhc[cur ^ 1], dpeep, Din, 0.f};   // (clip: see the unfused call below)
     if (fused_q) {
       const float* part = nullptr;
       int nchq = 0;
       ASR_TRY(energy_bwd_launch(h, denergy, a->keys, qz, a->v, T, B, A, a->att_mode, a->dkeys, dqz, dv, a->seq_len, fp, s,
                                 &part, &nchq));
-      CellBwdArgs ca = {dcs[cur], dhc[cur], dh2, a->gates_all + (size_t)k * B * 4 * U, a->craw_all + (size_t)k * B * U,
-                        a->c_all + (size_t)k * B * U, a->peep, a->live + (size_t)k * B, dmask,
-                        dpre, dcs[cur ^ 1], dhc[cur ^ 1], dpeep, Din, 0.f};   // (clip: see the unfused call below)
       hipLaunchKernelGGL(att_dq_cell_bwd_kernel, dim3(U / DQ_CT + 2, (B + 15) / 16), dim3(512), 0, st, part, nchq, B, A, U,
-                         a->W_q, a->ld_wq, dcell, dqz, dv, ca);
+                         a->W_q, a->ld_wq, dcell, dqz, dv, sk ? asr_stack_cell_args(a, sk, sk->L - 1, k, cur) : ca0);
       ASR_CHECK_LAUNCH(h, "asr_att_decoder_bwd");
     } else {
       if (!a->carry_alpha)
@@ -2837,12 +2865,13 @@ static int dec_bwd_loop(asr_handle* h, const asr_att_decoder* a, const asr_att_g
       }
       // the cell kernel applies the output dropout mask to dcell and adds the h-columns of step k+1's cell-input
       // gradient to the carried dh itself
-      ASR_TRY(cell_bwd_launch(h, dcell, dcs[cur], dhc[cur], a->gates_all + (size_t)k * B * 4 * U,
-                              a->craw_all + (size_t)k * B * U, a->c_all + (size_t)k * B * U, a->peep,
-                              a->live + (size_t)k * B, B, U, dpre, dcs[cur ^ 1], dhc[cur ^ 1], dpeep, dh2, Din, dmask,
-                              0.f, s));   // the decoder cell is tf.contrib.rnn.LSTMBlockCell (attention_seq2seq.py:354-365),
-                                          // whose gradient op ignores cell_clip: the clamp is straight-through here
+      // (clip 0: the decoder cell is tf.contrib.rnn.LSTMBlockCell (attention_seq2seq.py:354-365), whose gradient op
+      // ignores cell_clip: the clamp is straight-through here)
+      ASR_TRY(asr_lstm_cell_bwd_args(h, dcell, sk ? asr_stack_cell_args(a, sk, sk->L - 1, k, cur) : ca0, B, U, s));
     }
+    if (sk)                                // down the stack: dx of layer l + 1 and the cell backward of layer l, l = L-2 .. 0
+      for (int l = sk->L - 2; l >= 0; --l)
+        ASR_TRY(asr_stack_dec_bwd_lower(h, a, sk, l, k, l ? asr_stack_cell_args(a, sk, l, k, cur) : ca0, s));
     float* d_in = a->d_in_all + (size_t)k * B * Din;
     h->att_counts[cell_h ? ASR_ATT_BWD_CELL_BF16 : ASR_ATT_BWD_CELL_GEMM] += 1;
     if (cell_h) ASR_TRY(asr_lstm_cell_gemm_bwd_h(h, dpre, B, Din, U, a->W_cell_h, d_in, Din, s));   // bf16 weight rows
@@ -2850,6 +2879,7 @@ static int dec_bwd_loop(asr_handle* h, const asr_att_decoder* a, const asr_att_g
     cur ^= 1;
   }
   ASR_TRY(asr_add_cols(h, dhc[cur], U, a->d_in_all + Em + E2, Din, a->dh0, U, B, U, s));
+  if (sk) ASR_TRY(asr_stack_dec_bwd_end(h, a, sk, cur, s));
   if (g) return ASR_OK;                                    // (no cell state, no dc0)
   if (hipMemcpyAsync(a->dc0, dcs[cur], (size_t)B * U * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
     ASR_FAIL(h, ASR_ERR_HIP, "asr_att_decoder_bwd: copy");
@@ -2863,6 +2893,11 @@ extern "C" int asr_att_decoder_bwd_gru(asr_handle* h, const asr_att_decoder* a, 
   if (!h) return ASR_ERR_INVALID_ARG;
   if (!g) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_bwd_gru: bad arguments");
   return dec_bwd_loop(h, a, g, s);
+}
+extern "C" int asr_att_decoder_bwd_stack(asr_handle* h, const asr_att_decoder* a, const asr_att_stack* sk, asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  if (!sk) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_bwd_stack: bad arguments");
+  return dec_bwd_loop(h, a, nullptr, s, sk);
 }
 
 

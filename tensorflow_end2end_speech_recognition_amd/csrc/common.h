@@ -47,6 +47,9 @@ struct asr_handle {
   unsigned long long ctc_head_counts[3];
   // GRU decoder steps since the last asr_reset_att_gru_counts: {two-launch forward, four-launch forward, backward}
   unsigned long long att_gru_counts[3];
+  // upper layers of a decoder stack since the last asr_reset_att_stack_counts: {forward on the image, forward as product +
+  // cell, backward fused, backward generic}
+  unsigned long long att_stack_counts[4];
 };
 
 #define ASR_FAIL(h, code, ...)                                  \
@@ -201,6 +204,17 @@ int asr_gru_dec_fwd_step(asr_handle* h, const asr_att_decoder* a, const asr_att_
                          float* qz, asr_stream s);
 int asr_gru_dec_bwd_step(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, int k, const float* dcell,
                          const float* dh_c, const float* dh_c2, float* dh_carry, float* work2, asr_stream s);
+
+// the upper layers of a multi-layer LSTM decoder (dec_stack.hip; the loops are attention.hip's): argument check, the
+// layers' weight images once per loop call, the upper layers' cell launches of forward step k (layer 0 has written
+// up[0].in[k][:, :U]; saved activations at row ks; `more`: the next step's h-columns are written; qz: the step's query rows
+// when there is no query FC, else NULL), and the per-loop parts of the backward (zeroed carries; dc0 / dh0 at the end)
+int asr_stack_dec_check(asr_handle* h, const asr_att_decoder* a, const asr_att_stack* k, bool bwd);
+int asr_stack_dec_image(asr_handle* h, const asr_att_decoder* a, const asr_att_stack* k, asr_stream s);
+int asr_stack_dec_fwd_step(asr_handle* h, const asr_att_decoder* a, const asr_att_stack* sk, int k, int ks, bool more,
+                           float* qz, asr_stream s);
+int asr_stack_dec_bwd_begin(asr_handle* h, const asr_att_decoder* a, const asr_att_stack* sk, asr_stream s);
+int asr_stack_dec_bwd_end(asr_handle* h, const asr_att_decoder* a, const asr_att_stack* sk, int cur, asr_stream s);
 
 static inline int asr_dtype_ok(int dt) { return dt == ASR_F32 || dt == ASR_BF16; }
 static inline size_t asr_dtype_size(int dt) { return dt == ASR_BF16 ? 2 : 4; }

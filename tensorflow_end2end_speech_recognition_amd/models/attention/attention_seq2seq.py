@@ -29,6 +29,18 @@ cell clip.  Everything around the cell (input feeding, attention, attentional ve
 the LSTM decoder's; the loops are the same native ones around the GRU cell's launches (csrc/gru_decoder.hip), in fp32 on the
 master weights also in a dtype='bf16' model.  Not available with a GRU decoder (each raises ValueError):
 scheduled_sampling_prob > 0, infer(ctc_weight > 0), infer(lm=...).
+
+decoder_num_layers = L > 1 (decoder_type='lstm'; the reference takes the argument, stores it as `decdoder_num_layers` and
+builds one layer whatever it says): the decoder cell is MultiRNNCell of L LSTMBlockCell(decoder_num_units, forget_bias 1,
+clip_cell=clip_activation_decoder, use_peephole), each in a DropoutWrapper(output_keep_prob=keep_prob_decoder) -- the
+convention of the reference's encoders (models/encoders/core/lstm.py:147).  Layer 0 is today's cell (input embedding |
+previous context | its own h); layer l >= 1 reads [ o_{l-1} | h_{l,k-1} ] and has attention_decoder/decoder/lstm_cell_<l>/
+{kernel [2U,4U], bias [4U], w_{i,f,o}_diag [U]}; the top layer's masked output is the decoder's cell output.  The bridge's one
+FC is [4H, 2 U L] and splits into c_0, h_0, c_1, h_1, ... (nest.flatten of the state, bridge.py:136-151).  The native loops
+take the upper layers as a `stack` block (csrc/dec_stack.hip); they run in fp32 on the master weights also in a
+dtype='bf16' model (layer 0 keeps its bf16 weight images).  L = 1 is the model as it has always been: same variables, same
+entry points, same bits.  Not available with L > 1 (each raises ValueError): decoder_type='gru',
+scheduled_sampling_prob > 0, infer(ctc_weight > 0), infer(lm=...).
 """
 import os as _os
 
@@ -47,7 +59,7 @@ from ..model_base import ModelBase
 from .bridge import InitialStateBridge
 from .decoders import attention_layer as AL
 from .decoders.attention_decoder import (AttentionDecoder, AttentionDecoderOutput, GreedyEmbeddingHelper,  # noqa: F401
-                                         LSTMDecoderCell, TrainingHelper)
+                                         LSTMDecoderCell, StackedLSTMDecoderCell, TrainingHelper)
 from .decoders.attention_layer import AttentionLayer
 from .decoders.beam_search.ctc_prefix_score import check_ctc_weight
 from .decoders.beam_search.lm_fusion import check_lm_weight
@@ -89,6 +101,10 @@ class AttentionSeq2Seq(ModelBase):
         if decoder_type not in ('lstm', 'gru'):
             raise TypeError('decoder_type is "lstm" or "gru".')
         self.gru_decoder = decoder_type == 'gru'
+        if int(decoder_num_layers) != decoder_num_layers or not 1 <= int(decoder_num_layers) <= 8:
+            raise ValueError('decoder_num_layers must be an integer in [1, 8], got %r' % (decoder_num_layers,))
+        if self.gru_decoder and int(decoder_num_layers) > 1:
+            raise ValueError('decoder_num_layers > 1 is not available with decoder_type="gru" (the stack runs LSTM cells only)')
         if encoder_type not in ('blstm',):
             raise NotImplementedError
         self.input_size, self.splice = input_size, splice
@@ -99,7 +115,8 @@ class AttentionSeq2Seq(ModelBase):
         self.attention_type, self.attention_dim = attention_type, attention_dim
         self.sharpening_factor, self.sigmoid_smoothing = sharpening_factor, sigmoid_smoothing
         self.decoder_type, self.decoder_num_units = decoder_type, decoder_num_units
-        self.decdoder_num_layers = decoder_num_layers
+        self.decdoder_num_layers = decoder_num_layers        # (the reference's spelling, kept)
+        self.decoder_num_layers = int(decoder_num_layers)
         self.embedding_dim = embedding_dim
         self.num_classes = num_classes + 2
         self.sos_index, self.eos_index = sos_index, eos_index
@@ -123,6 +140,7 @@ class AttentionSeq2Seq(ModelBase):
         self.device = torch.device(device)
         self.seed = seed
         self._calls = 0
+        self._init_up = []                    # (c0, h0) of the upper decoder layers, set by _bridge
 
         rng = np.random.RandomState(seed)
         st = self.store = ParamStore(self.device)
@@ -155,7 +173,7 @@ class AttentionSeq2Seq(ModelBase):
         tn = lambda *s: truncated_normal(rng, parameter_init, s)
         st.declare('output_embedding/W_embedding', (C2, Em), u(C2, Em))
         # the decoder's state: (c, h) of an LSTM cell, h alone of a GRU cell (GRUCell.state_size is the integer U)
-        S = U if self.gru_decoder else 2 * U
+        S = U if self.gru_decoder else 2 * U * self.decoder_num_layers
         st.declare('bridge/fully_connected/weights', (4 * H, S), tn(4 * H, S))
         st.declare('bridge/fully_connected/biases', (S,), np.zeros(S))
         self.dec_in_dim = Em + E2 + U
@@ -172,6 +190,14 @@ class AttentionSeq2Seq(ModelBase):
             if use_peephole:
                 for n in ('w_i_diag', 'w_f_diag', 'w_o_diag'):
                     st.declare(D + 'lstm_cell/' + n, (U,), u(U))
+            # upper layers of a stack (decoder_num_layers > 1), directly behind layer 0: rows o_{l-1} then h
+            for l in range(1, self.decoder_num_layers):
+                cell = D + 'lstm_cell_%d/' % l
+                st.declare(cell + 'kernel', (2 * U, 4 * U), u(2 * U, 4 * U))
+                st.declare(cell + 'bias', (4 * U,), np.zeros(4 * U))
+                if use_peephole:
+                    for n in ('w_i_diag', 'w_f_diag', 'w_o_diag'):
+                        st.declare(cell + n, (U,), u(U))
         at = attention_type
         self.att_mode = 0 if at in AL.ADDITIVE else 1
         if at == 'luong_dot' and E2 != U:
@@ -227,6 +253,36 @@ class AttentionSeq2Seq(ModelBase):
         return torch.stack([st[D + 'lstm_cell/w_i_diag'], st[D + 'lstm_cell/w_f_diag'],
                             st[D + 'lstm_cell/w_o_diag']]).contiguous()
 
+    def _peep_up(self, l):
+        st, cell = self.store, D + 'lstm_cell_%d/' % l
+        if not self.use_peephole:
+            return None
+        return torch.stack([st[cell + 'w_i_diag'], st[cell + 'w_f_diag'], st[cell + 'w_o_diag']]).contiguous()
+
+    def _stack_layers(self, init_up, n_in, n_state, R, dev, steps, dmask_up=None, rows=None):
+        """The `stack` block of a loop dict (ops._att_stack_struct) for the upper layers 1 .. L-1, or None at L = 1.  init_up:
+        [(c0, h0)] per upper layer; in is n_in and c / h are n_state row blocks of R rows with the initial state in block 0
+        (rows: gather the initial state's rows first -- the beam's tiling); gates / craw `steps` long; dmask_up
+        [(L-1),To,R,U] or None."""
+        if self.decoder_num_layers == 1:
+            return None
+        st, U = self.store, self.decoder_num_units
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)          # noqa: E731
+        layers = []
+        for l in range(1, self.decoder_num_layers):
+            cell = D + 'lstm_cell_%d/' % l
+            c0, h0 = init_up[l - 1]
+            if rows is not None:
+                c0, h0 = c0.index_select(0, rows), h0.index_select(0, rows)
+            x, c, h = f32(n_in, R, 2 * U), f32(n_state, R, U), f32(n_state, R, U)
+            c[0].copy_(c0)
+            h[0].copy_(h0)
+            x[0, :, U:].copy_(h0)
+            layers.append({'W': st[cell + 'kernel'], 'b': st[cell + 'bias'], 'peep': self._peep_up(l),
+                           'dmask': dmask_up[l - 1] if dmask_up is not None else None, 'in': x, 'c': c, 'h': h,
+                           'gates': f32(steps, R, 4 * U), 'craw': f32(steps, R, U)})
+        return dict(layers=layers)
+
     # key / query projection matrices (and their gradient views); luong_concat slices W_concat
     def _wk(self, grad=False):
         st = self.store
@@ -279,9 +335,10 @@ class AttentionSeq2Seq(ModelBase):
             br = InitialStateBridge(_Enc, U, self.parameter_init, store=self.store)
             h0, = br()
             return br.bridge_input(), None, h0
-        br = InitialStateBridge(_Enc, (U, U), self.parameter_init, store=self.store)
-        c0, h0 = br()
-        return br.bridge_input(), c0, h0
+        br = InitialStateBridge(_Enc, (U, U) * self.decoder_num_layers, self.parameter_init, store=self.store)
+        flat = br()                           # c_0, h_0, c_1, h_1, ... (nest.flatten of the state, bridge.py:136-151)
+        self._init_up = [(flat[2 * l], flat[2 * l + 1]) for l in range(1, self.decoder_num_layers)]
+        return br.bridge_input(), flat[0], flat[1]
 
     def _cell_fields(self, peep):
         """The decoder cell's entries of a loop dict: the LSTM kernel / bias / peepholes, or the GRU block ops.att_decoder_*
@@ -316,6 +373,9 @@ class AttentionSeq2Seq(ModelBase):
         if self.gru_decoder and ss_prob > 0.0:
             raise ValueError('scheduled_sampling_prob > 0 is not available with decoder_type="gru" (the sampling loop runs '
                              'the LSTM decoder only)')
+        if self.decoder_num_layers > 1 and ss_prob > 0.0:
+            raise ValueError('scheduled_sampling_prob > 0 is not available with decoder_num_layers > 1 (the sampling loop '
+                             'runs a one-layer decoder only)')
         dev, st = self.device, self.store
         # nothing below may drain the stream (pageable uploads and device read-backs do): the host has to run ahead of the
         # device for the step to be device-bound -- ops.to_device stages through pinned memory, ops.host_ints remembers
@@ -378,6 +438,11 @@ class AttentionSeq2Seq(ModelBase):
         if use_ddrop:                                            # one launch for the masks of every step
             self._calls += 1
             dmask_all = ops.dropout_mask((To, Bp, U), keep_prob_decoder, self.seed + 2, self._calls << 40, dev)
+        dmask_up = None
+        if use_ddrop and self.decoder_num_layers > 1:            # the upper layers' DropoutWrappers: a second draw
+            self._calls += 1
+            dmask_up = ops.dropout_mask((self.decoder_num_layers - 1, To, Bp, U), keep_prob_decoder, self.seed + 2,
+                                        self._calls << 40, dev)
         # sigmoid smoothing (attention_layer.py:92-96): the per-step normaliser is kept for the backward
         snorm_all = torch.empty((To, Bp), dtype=torch.float32, device=dev) if self.sigmoid_smoothing else None
         alpha_zero = torch.zeros((Bp, T), dtype=torch.float32, device=dev) if self.carry_alpha else None
@@ -406,6 +471,9 @@ class AttentionSeq2Seq(ModelBase):
                     gates_all=torch.empty((To, Bp, 4 * U), dtype=torch.float32, device=dev),     # (GRU: r | u | c | r*h)
                     craw_all=None if gru else torch.empty((To, Bp, U), dtype=torch.float32, device=dev), c_all=c_all,
                     h_all=h_all, qz_all=torch.empty((To, Bp, A), dtype=torch.float32, device=dev), **self._cell_fields(peep))
+        stack = self._stack_layers(self._init_up, To, To + 1, Bp, dev, To, dmask_up)
+        if stack is not None:
+            loop['stack'] = stack
         if sample:
             # one launch for the draws of every step; a non-zero entry feeds the model's prediction (rows that have
             # finished and the padding of the batch tile keep the label's token whatever their draw)
@@ -555,6 +623,13 @@ class AttentionSeq2Seq(ModelBase):
         loop.update(dav_cell=dav_cell, dav_ctx=dav_ctx, dctx_all=dctx_all, dpre_all=dpre_all, dqz_all=dqz_all,
                     dv_all=dv_all, dpeep_all=dpeep_all, d_in_all=d_in_all, dkeys=dkeys, dwfil_rows=dwfil_rows,
                     dfilt_rows=dfilt_rows, dc0=dc_next, dh0=dh_next)
+        ups = loop['stack']['layers'] if loop.get('stack') is not None else []
+        for ld in ups:                        # the upper layers' gradient arrays (ops._att_stack_struct)
+            ld.update(dpre=torch.empty((To, Bp, 4 * U), dtype=torch.float32, device=dev),
+                      d_hin=torch.empty((To, Bp, U), dtype=torch.float32, device=dev),
+                      dpeep=torch.empty((To, Bp, 3 * U), dtype=torch.float32, device=dev) if has_peep else None,
+                      dc0=torch.empty((Bp, U), dtype=torch.float32, device=dev),
+                      dh0=torch.empty((Bp, U), dtype=torch.float32, device=dev))
         ops.att_decoder_bwd(loop)
         # ---- d_enc[:, b, :] += alpha_b^T [T, To] . dctx_b [To, 2H]   (context path of all steps at once)
         alpha_all = tp['alpha_all']
@@ -578,7 +653,8 @@ class AttentionSeq2Seq(ModelBase):
         elif dk2d is not None:
             ops.gemm(dk2d, self._wk(), transB=True, out=denc.view(T * Bp, E2), accumulate=True)
         # bridge
-        dinit = dh_next if gru else torch.cat([dc_next, dh_next], dim=1).contiguous()
+        dinit = dh_next if gru else torch.cat([dc_next, dh_next] + [t for ld in ups for t in (ld['dc0'], ld['dh0'])],
+                                              dim=1).contiguous()
         dbi = ops.gemm(dinit, st['bridge/fully_connected/weights'], transB=True)
         H = self.encoder_num_units
         dcf = torch.stack([dbi[:, :H], dbi[:, 2 * H:3 * H]]).contiguous()
@@ -587,6 +663,7 @@ class AttentionSeq2Seq(ModelBase):
         side_keep = [t for t in (dec_in, dpre_all, dpeep_all, dqz_all, dv_all, dwfil_rows, dfilt_rows, dkeys, enc,
                                  d_in_all, av_in, dinit, tp['bi'], tp['ids'], tp['emb_mask'], dk16, tp['enc_att'])
                      if t is not None]
+        side_keep += [t for ld in ups for t in (ld['in'], ld['dpre'], ld['dpeep']) if t is not None]
         with ops.side_lane(dev, keep=side_keep + ([loop['gates_all']] if gru else []), lane=1):
             if gru:
                 # fp32 on the master weights, also in a bf16-operand model.  One product for everything the image W3 =
@@ -615,6 +692,16 @@ class AttentionSeq2Seq(ModelBase):
                 st.g(D + 'lstm_cell/w_i_diag').copy_(dp[:U])
                 st.g(D + 'lstm_cell/w_f_diag').copy_(dp[U:2 * U])
                 st.g(D + 'lstm_cell/w_o_diag').copy_(dp[2 * U:])
+            for l, ld in enumerate(ups, 1):   # the upper layers: fp32 on the master weights, one product over all steps
+                cell = D + 'lstm_cell_%d/' % l
+                dp2d = ld['dpre'].view(To * Bp, 4 * U)
+                ops.gemm(ld['in'].view(To * Bp, 2 * U), dp2d, transA=True, out=st.g(cell + 'kernel'))
+                ops.colsum(dp2d, out=st.g(cell + 'bias'))
+                if has_peep:
+                    dp = ops.colsum(ld['dpeep'].view(To * Bp, 3 * U))
+                    st.g(cell + 'w_i_diag').copy_(dp[:U])
+                    st.g(cell + 'w_f_diag').copy_(dp[U:2 * U])
+                    st.g(cell + 'w_o_diag').copy_(dp[2 * U:])
             if at in AL.HAS_QUERY_FC:
                 ops.gemm(cell_out_all.reshape(To * Bp, U), dq2d, transA=True, out=self._wq(grad=True))
             if at in AL.HAS_FILTER:
@@ -699,6 +786,9 @@ class AttentionSeq2Seq(ModelBase):
                     snorm_all=f32(To, Bp) if self.sigmoid_smoothing else None,
                     gates_all=f32(1, Bp, 4 * U), craw_all=f32(1, Bp, U), c_all=c_all, h_all=h_all, qz_all=f32(1, Bp, A),
                     **self._cell_fields(self._peep()))
+        stack = self._stack_layers(self._init_up, To, To + 1, Bp, dev, 1)
+        if stack is not None:
+            loop['stack'] = stack
         out = ops.att_decoder_infer(loop, st[D + 'attentional_vector/weights'], st[D + 'output_layer/weights'],
                                     st[D + 'output_layer/biases'], st['output_embedding/W_embedding'], self.eos_index,
                                     n_live=B)
@@ -721,12 +811,18 @@ class AttentionSeq2Seq(ModelBase):
         layer = self.attention_layer(time_major_inputs=True)
         cell = LSTMDecoderCell(st, self.decoder_num_units, self.use_peephole, self.clip_activation_decoder,
                                kernel=self._w_cell())
+        state = (c, h)
+        if self.decoder_num_layers > 1:       # MultiRNNCell: layer 0 above, then lstm_cell_1 ..; state c_0, h_0, c_1, h_1, ...
+            cell = StackedLSTMDecoderCell([cell] + [
+                LSTMDecoderCell(st, self.decoder_num_units, self.use_peephole, self.clip_activation_decoder,
+                                scope='lstm_cell_%d/' % l) for l in range(1, self.decoder_num_layers)])
+            state = (c, h) + tuple(t for ch in self._init_up for t in ch)
         decoder = AttentionDecoder(cell, self.parameter_init, self.max_decode_length, self.num_classes, enc, seq_p, layer,
                                    time_major=False, mode='infer', store=st)
         decoder.live_rows = torch.arange(Bp, device=dev) < B      # rows B.. are the zero-length padding of the batch tile
         helper = GreedyEmbeddingHelper(st['output_embedding/W_embedding'],
                                        torch.full((Bp,), self.sos_index, dtype=torch.int32, device=dev), self.eos_index)
-        outputs, _ = decoder((c, h), helper)
+        outputs, _ = decoder(state, helper)
         return outputs.predicted_ids[:B]
 
     def _decode_beam(self, inputs, isl, beam_width, length_penalty_weight=0.0, ctc_weight=0.0, lm=None, lm_weight=0.0):
@@ -793,6 +889,9 @@ class AttentionSeq2Seq(ModelBase):
                     snorm_all=f32(1, R) if self.sigmoid_smoothing else None,
                     gates_all=f32(1, R, 4 * U), craw_all=f32(1, R, U), c_all=c_all, h_all=h_all, qz_all=f32(1, R, A),
                     **self._cell_fields(self._peep()))
+        stack = self._stack_layers(self._init_up, 2, 2, R, dev, 1, rows=rows)
+        if stack is not None:
+            loop['stack'] = stack
         head = (st[D + 'attentional_vector/weights'], st[D + 'output_layer/weights'], st[D + 'output_layer/biases'],
                 st['output_embedding/W_embedding'], self.eos_index)
         if lm_weight:
@@ -860,6 +959,12 @@ class AttentionSeq2Seq(ModelBase):
         if self.gru_decoder and (lm is not None or lm_weight):
             raise ValueError('lm / lm_weight are not available with decoder_type="gru" (the LM-fused search runs the LSTM '
                              'decoder only)')
+        if self.decoder_num_layers > 1 and ctc_weight:
+            raise ValueError('ctc_weight > 0 is not available with decoder_num_layers > 1 (the joint search runs a one-layer '
+                             'decoder only)')
+        if self.decoder_num_layers > 1 and (lm is not None or lm_weight):
+            raise ValueError('lm / lm_weight are not available with decoder_num_layers > 1 (the LM-fused search runs a '
+                             'one-layer decoder only)')
         lam = check_ctc_weight(ctc_weight)
         mu = self._check_lm(lm, lm_weight)
         if lam != 0.0 and not self._has_ctc_head:

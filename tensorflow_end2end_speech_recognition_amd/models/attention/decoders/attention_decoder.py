@@ -36,17 +36,19 @@ class LSTMDecoderCell(object):
     """tf.contrib.rnn.LSTMBlockCell of the decoder (attention_seq2seq.py:353-363): (c, h) state, peepholes, cell clip,
     forget_bias 1; variables attention_decoder/decoder/lstm_cell/{kernel,bias,w_*_diag} of `store`."""
 
-    def __init__(self, store, num_units, use_peephole=True, cell_clip=None, forget_bias=1.0, kernel=None):
+    def __init__(self, store, num_units, use_peephole=True, cell_clip=None, forget_bias=1.0, kernel=None,
+                 scope='lstm_cell/'):
         """kernel: the tensor to multiply with instead of the stored variable (a bf16-operand model hands in the kernel
-        rounded to bf16, AttentionSeq2Seq._w_cell)."""
+        rounded to bf16, AttentionSeq2Seq._w_cell).  scope: 'lstm_cell_<l>/' for layer l >= 1 of a stack."""
         self.store, self.num_units = store, num_units
         self.kernel = kernel
+        self.scope = D_SCOPE + scope
         self.output_size = num_units
         self.cell_clip, self.forget_bias = float(cell_clip or 0.0), forget_bias
         self.peep = None
         if use_peephole:
-            self.peep = torch.stack([store[D_SCOPE + 'lstm_cell/w_i_diag'], store[D_SCOPE + 'lstm_cell/w_f_diag'],
-                                     store[D_SCOPE + 'lstm_cell/w_o_diag']]).contiguous()
+            self.peep = torch.stack([store[self.scope + 'w_i_diag'], store[self.scope + 'w_f_diag'],
+                                     store[self.scope + 'w_o_diag']]).contiguous()
 
     def __call__(self, inputs, state, live=None):
         """inputs [B, E + 2H + U]: the reference concatenates [inputs, h] inside the cell; here the caller's buffer
@@ -56,10 +58,31 @@ class LSTMDecoderCell(object):
         c, h = state
         if live is None:
             live = torch.ones((inputs.shape[0],), dtype=torch.float32, device=inputs.device)
-        W = self.kernel if self.kernel is not None else st[D_SCOPE + 'lstm_cell/kernel']
-        pre = ops.gemm(inputs, W, bias=st[D_SCOPE + 'lstm_cell/bias'])
+        W = self.kernel if self.kernel is not None else st[self.scope + 'kernel']
+        pre = ops.gemm(inputs, W, bias=st[self.scope + 'bias'])
         _, _, c_new, h_new, h_raw = ops.lstm_cell_fwd(pre, c, h, self.peep, live, self.forget_bias, self.cell_clip)
         return h_raw, (c_new, h_new)
+
+
+class StackedLSTMDecoderCell(object):
+    """tf.contrib.rnn.MultiRNNCell of LSTMDecoderCells (decoder_num_layers > 1): cells[0] reads the decoder's input buffer
+    (its last U columns carry h_0), cells[l] reads [ output of cells[l-1] | h_l ].  The state is the flat tuple c_0, h_0,
+    c_1, h_1, ... (so that state[1] is layer 0's h, which AttentionDecoder.step feeds back); the output is the top layer's.
+    No dropout: this is the inference surface."""
+
+    def __init__(self, cells):
+        self.cells = list(cells)
+        self.store, self.num_units = cells[0].store, cells[0].num_units
+        self.output_size = self.num_units
+
+    def __call__(self, inputs, state, live=None):
+        out, (c, h) = self.cells[0](inputs, (state[0], state[1]), live=live)
+        new = [c, h]
+        for l, cell in enumerate(self.cells[1:], 1):
+            out, (c, h) = cell(torch.cat([out, state[2 * l + 1]], dim=1).contiguous(), (state[2 * l], state[2 * l + 1]),
+                               live=live)
+            new += [c, h]
+        return out, tuple(new)
 
 
 class TrainingHelper(object):

@@ -2091,6 +2091,10 @@ def att_decoder_fwd(a):
         g = _att_gru_struct(a)
         h.check(h.lib.asr_att_decoder_fwd_gru(h.h, C.byref(st), C.byref(g), _s()), 'asr_att_decoder_fwd_gru')
         return
+    if a.get('stack') is not None:        # decoder_num_layers > 1: the same loop with the upper layers' cell launches
+        k = _att_stack_struct(a)
+        h.check(h.lib.asr_att_decoder_fwd_stack(h.h, C.byref(st), C.byref(k), _s()), 'asr_att_decoder_fwd_stack')
+        return
     h.check(h.lib.asr_att_decoder_fwd(h.h, C.byref(st), _s()), 'asr_att_decoder_fwd')
 
 
@@ -2156,6 +2160,10 @@ def att_decoder_bwd(a):
         g = _att_gru_struct(a)
         h.check(h.lib.asr_att_decoder_bwd_gru(h.h, C.byref(st), C.byref(g), _s()), 'asr_att_decoder_bwd_gru')
         return
+    if a.get('stack') is not None:        # the upper layers' dpre / d_hin / dpeep / dc0 / dh0 are in the stack block
+        k = _att_stack_struct(a, bwd=True)
+        h.check(h.lib.asr_att_decoder_bwd_stack(h.h, C.byref(st), C.byref(k), _s()), 'asr_att_decoder_bwd_stack')
+        return
     h.check(h.lib.asr_att_decoder_bwd(h.h, C.byref(st), _s()), 'asr_att_decoder_bwd')
 
 
@@ -2196,6 +2204,10 @@ def att_decoder_infer(a, W_av, W_out, b_out, embedding, eos, n_live, check_every
         g = _att_gru_struct(a)
         h.check(h.lib.asr_att_decoder_infer_gru(h.h, C.byref(st), C.byref(g), C.byref(f), C.byref(issued), _s()),
                 'asr_att_decoder_infer_gru')
+    elif a.get('stack') is not None:
+        k = _att_stack_struct(a)
+        h.check(h.lib.asr_att_decoder_infer_stack(h.h, C.byref(st), C.byref(k), C.byref(f), C.byref(issued), _s()),
+                'asr_att_decoder_infer_stack')
     else:
         h.check(h.lib.asr_att_decoder_infer(h.h, C.byref(st), C.byref(f), C.byref(issued), _s()), 'asr_att_decoder_infer')
     out['steps_issued'] = issued.value
@@ -2356,6 +2368,10 @@ def att_decoder_beam(a, W_av, W_out, b_out, embedding, eos, beam_width, length_p
         g = _att_gru_struct(a)
         h.check(h.lib.asr_att_decoder_beam_gru(h.h, C.byref(st), C.byref(g), C.byref(f), C.byref(m), C.byref(issued), _s()),
                 'asr_att_decoder_beam_gru')
+    elif a.get('stack') is not None:      # (upper layers: in [2,R,2U], c / h [2,R,U], re-ordered by asr_att_stack_reorder)
+        k = _att_stack_struct(a)
+        h.check(h.lib.asr_att_decoder_beam_stack(h.h, C.byref(st), C.byref(k), C.byref(f), C.byref(m), C.byref(issued), _s()),
+                'asr_att_decoder_beam_stack')
     else:
         h.check(h.lib.asr_att_decoder_beam(h.h, C.byref(st), C.byref(f), C.byref(m), C.byref(issued), _s()),
                 'asr_att_decoder_beam')
@@ -2729,6 +2745,134 @@ def att_gru_counts(device=0):
 
 def reset_att_gru_counts(device=0):
     _reset_counts3('att_gru_counts', device)
+
+
+# ---------------------------------------------------------------- multi-layer LSTM decoder (decoder_num_layers > 1)
+STACK_BWD_FUSED = os.environ.get('ASR_DEC_STACK_FUSED', '1') != '0'   # A/B: 0 keeps every backward step on the generic form
+ATT_STACK_MAX = 7                                                     # upper layers (ASR_ATT_STACK_MAX)
+
+
+class _AttStackLayer(C.Structure):
+    """struct asr_att_stack_layer (include/asr_hip.h), field for field."""
+    _PTRS = ['W', 'b', 'peep', 'dmask', 'in', 'c', 'h', 'gates', 'craw', 'W_il', 'dpre', 'd_hin', 'dpeep', 'dc0', 'dh0']
+    _fields_ = [(n, C.c_void_p) for n in _PTRS]
+
+
+class _AttStack(C.Structure):
+    """struct asr_att_stack (include/asr_hip.h), field for field."""
+    _fields_ = [('L', C.c_int), ('fused', C.c_int), ('up', _AttStackLayer * ATT_STACK_MAX), ('work', C.c_void_p)]
+
+
+def _att_stack_struct(a, bwd=False):
+    """The stack block of a loop dict: a['stack'] = dict(layers=[one dict per upper layer, layer 1 first, with the fields of
+    asr_att_stack_layer as contiguous fp32 device tensors or None], fused (optional; False: the generic backward form at
+    every shape), work (made here for the backward when missing)).  W_il, the work space of a layer's interleaved image,
+    is made here where the one-launch forward covers the shape."""
+    sd = a['stack']
+    layers = sd['layers']
+    U, B, To = int(a['U']), int(a['B']), int(a['To'])
+    if not 1 <= len(layers) <= ATT_STACK_MAX:
+        raise ValueError('att_decoder (stack): 1 .. %d upper layers, got %d' % (ATT_STACK_MAX, len(layers)))
+    dev = a['dec_in'].device
+    h = _h(a['dec_in'])
+    need = ['W', 'b', 'in', 'c', 'h', 'gates', 'craw'] + (['dpre', 'd_hin', 'dc0', 'dh0'] if bwd else [])
+    k = _AttStack()
+    k.L = len(layers) + 1
+    k.fused = int(bool(sd.get('fused', True)) and STACK_BWD_FUSED)
+    for i, ld in enumerate(layers):
+        if tuple(ld['W'].shape) != (2 * U, 4 * U) or tuple(ld['b'].shape) != (4 * U,):
+            raise ValueError('att_decoder (stack): layer %d: W [2U,4U], b [4U]' % (i + 1))
+        if bwd and ld.get('peep') is not None and ld.get('dpeep') is None:
+            raise ValueError('att_decoder (stack): layer %d: dpeep is needed with peepholes' % (i + 1))
+        if ld.get('W_il') is None and FUSED_CELL_GEMM and h.lib.asr_lstm_cell_gemm_ok(B, 2 * U, U, 2 * U):
+            ld['W_il'] = _f32(((2 * U + 1) * 4 * U,), dev)
+        for n in _AttStackLayer._PTRS:
+            t = ld.get(n)
+            if t is None:
+                if n in need:
+                    raise ValueError('att_decoder (stack): layer %d: %s is missing' % (i + 1, n))
+                continue
+            if not t.is_cuda or not t.is_contiguous() or t.dtype != torch.float32:
+                raise ValueError('att_decoder (stack): layer %d: %s must be a contiguous fp32 device tensor' % (i + 1, n))
+            setattr(k.up[i], n, t.data_ptr())
+    if bwd:
+        if sd.get('work') is None:
+            sd['work'] = _f32((len(layers) * 4 * B * U + B * U,), dev)
+        k.work = sd['work'].data_ptr()
+    return k
+
+
+def att_stack_bwd_ok(B, U):
+    """Whether the one-launch backward of a lower layer (dx product + cell backward) covers the shape
+    (asr_att_stack_bwd_ok): B <= 32, U % 16 == 0."""
+    from . import _lib
+    return bool(_lib.load().asr_att_stack_bwd_ok(int(B), int(U)))
+
+
+def att_stack_bwd_step(dpre_up, W_up, dc_next, dh_next, gates, c_raw, c_prev, live, peep=None, use_mask=None, dh_next2=None,
+                       fused=True, want_dpeep=None):
+    """The backward of one lower layer of a decoder stack at one step (asr_att_stack_bwd_step): dx = dpre_up [B,4U] W_up^T
+    ([2U,4U]); the cell backward on dx[:, :U] * use_mask with the carried dc_next / dh_next (+ dh_next2 [B,U]).  Returns
+    (dpre [B,4U], dc_prev, dh_prev_carry, d_hin_up = dx[:, U:], dpeep_rows [B,3U] or None), every output prefilled with
+    NaN.  fused: the one-launch form where att_stack_bwd_ok."""
+    h = _h(dpre_up)
+    B, U = dc_next.shape
+    dev = dpre_up.device
+    for t, n in ((dpre_up, 'dpre_up'), (W_up, 'W_up'), (dc_next, 'dc_next'), (dh_next, 'dh_next'), (gates, 'gates'),
+                 (c_raw, 'c_raw'), (c_prev, 'c_prev'), (live, 'live')):
+        _chk(t, torch.float32, n)
+    if tuple(dpre_up.shape) != (B, 4 * U) or tuple(W_up.shape) != (2 * U, 4 * U) or tuple(gates.shape) != (B, 4 * U):
+        raise ValueError('att_stack_bwd_step: shapes disagree')
+    nan = lambda *shape: torch.full(shape, float('nan'), dtype=torch.float32, device=dev)   # noqa: E731
+    dpre, dc_prev, carry, d_hin = nan(B, 4 * U), nan(B, U), nan(B, U), nan(B, U)
+    want = (peep is not None) if want_dpeep is None else want_dpeep
+    dpeep = nan(B, 3 * U) if want else None
+    work = _f32((B, U), dev)
+    p2, ld2 = _col_block(dh_next2, B, U, 'dh_next2')
+    h.check(h.lib.asr_att_stack_bwd_step(h.h, _p(dpre_up), _p(W_up), B, U, _p(dc_next), _p(dh_next), p2, ld2, _p(gates),
+                                         _p(c_raw), _p(c_prev), _p(peep), _p(live), _p(use_mask), _p(dpre), _p(dc_prev),
+                                         _p(carry), _p(dpeep), _p(d_hin), _p(work), int(bool(fused) and STACK_BWD_FUSED),
+                                         _s()), 'asr_att_stack_bwd_step')
+    return dpre, dc_prev, carry, d_hin, dpeep
+
+
+def att_stack_reorder(parent, c, h, in_):
+    """Beam re-ordering of a stack's upper layers in one launch (asr_att_stack_reorder): c / h: lists of [2,R,U], in_: list of
+    [2,R,2U]; parent [B,W] int32.  Block 0 row b*W + w (of in_: its columns [U,2U)) becomes block 1 row b*W + parent[b,w]."""
+    hd = _h(c[0])
+    B, W = parent.shape
+    U = c[0].shape[2]
+    _chk(parent, torch.int32, 'parent')
+    k = _AttStack()
+    k.L = len(c) + 1
+    for i, (ci, hi, xi) in enumerate(zip(c, h, in_)):
+        for t, shape, n in ((ci, (2, B * W, U), 'c'), (hi, (2, B * W, U), 'h'), (xi, (2, B * W, 2 * U), 'in')):
+            _chk(t, torch.float32, n)
+            if tuple(t.shape) != shape:
+                raise ValueError('att_stack_reorder: %s must be %r' % (n, shape))
+        k.up[i].c, k.up[i].h = ci.data_ptr(), hi.data_ptr()
+        setattr(k.up[i], 'in', xi.data_ptr())
+    hd.check(hd.lib.asr_att_stack_reorder(hd.h, C.byref(k), _p(parent), B, W, U, _s()), 'asr_att_stack_reorder')
+
+
+_ATT_STACK_KEYS = ('fwd_image', 'fwd_two_launch', 'bwd_fused', 'bwd_generic')
+
+
+def att_stack_counts(device=0):
+    """Upper-layer steps of decoder stacks on `device` since the last reset, summed over its handles
+    (asr_att_stack_counts): forward on the image (one launch), forward as product + cell, backward fused, backward generic.
+    Host counters: no device work, no synchronisation."""
+    tot = [0] * 4
+    for h in _device_handles(device):
+        out = (C.c_ulonglong * 4)()
+        h.check(h.lib.asr_att_stack_counts(h.h, out), 'asr_att_stack_counts')
+        tot = [x + int(y) for x, y in zip(tot, out)]
+    return dict(zip(_ATT_STACK_KEYS, tot))
+
+
+def reset_att_stack_counts(device=0):
+    for h in _device_handles(device):
+        h.check(h.lib.asr_reset_att_stack_counts(h.h), 'asr_reset_att_stack_counts')
 
 
 # ---------------------------------------------------------------- shallow fusion with an RNN language model (an extension)
