@@ -206,7 +206,7 @@ int asr_gemm_rows(asr_handle* h, int dtype, int transA, int transB, int M, int N
                   const void* B, int ldb, float* C, int ldc, const float* bias, int accumulate, int act,
                   const float* mul, int ldmul, float keep_prob, uint64_t seed, uint64_t offset, const int32_t* rows,
                   int num_rows, asr_stream s);
-/* What the asr_gemm_rows calls on this handle ran since the last reset (host integers bumped at launch time: no device
+/* What the GEMM calls on this handle ran since the last reset (host integers bumped at launch time: no device
  * work, no synchronisation); out[i], i < min(n, ASR_GEMMP_N), in the order of the enum, the rest of `out` zeroed. */
 enum {
   ASR_GEMMP_ROWS_128 = 0,         /* listed-row launches of the 128 x 128 NT kernel */
@@ -216,6 +216,22 @@ enum {
   ASR_GEMMP_TN_FRAMES_GENERIC,    /* asr_gemm_tn_frames calls on the generic kernel (shape outside the lean TN path) */
   ASR_GEMMP_HEAD_BWD_LEAN,        /* asr_ctc_head_bwd calls on the lean NT kernels (listed rows where a list is given) */
   ASR_GEMMP_HEAD_BWD_FULL,        /* asr_ctc_head_bwd calls that ran the full generic product */
+  /* The kernel a FULL product ended in: one of the next ten per product that asr_gemm / asr_gemm_act / asr_gemm_mul /
+   * asr_gemm_drop ran.  The calls counted above that fall to the full product (ROWS_FULL, TN_FRAMES_GENERIC,
+   * HEAD_BWD_FULL) run it through the same code and bump one of these as well; the listed-row launches, the lean
+   * tn-frames launches and the lean head-bwd launches do not. */
+  ASR_GEMMP_SKINNY_NN16,          /* skinny fp32 kernel (M <= 32), B row-major, 16 columns per workgroup */
+  ASR_GEMMP_SKINNY_NN32,          /* the same, 32 columns per workgroup */
+  ASR_GEMMP_SKINNY_NT16,          /* skinny fp32 kernel, B^T rows, 16 columns per workgroup */
+  ASR_GEMMP_SKINNY_NT32,          /* the same, 32 columns per workgroup (N >= 6144) */
+  ASR_GEMMP_NT128,                /* lean bf16 NT kernel, 128 x 128 tiles */
+  ASR_GEMMP_NT256,                /* lean bf16 NT kernel, 256 x 256 tiles */
+  ASR_GEMMP_TN_LEAN,              /* lean bf16 TN kernel + split-K reducer */
+  ASR_GEMMP_GENERIC128,           /* generic kernel, 128 x 128 tiles */
+  ASR_GEMMP_GENERIC64,            /* generic kernel, 64 x 64 tiles, one pass over K */
+  ASR_GEMMP_GENERIC64_SPLITK,     /* generic kernel, 64 x 64 tiles, split-K slabs + reducer */
+  ASR_GEMMP_MUL_PASS,             /* asr_gemm_mul calls whose multiplier ran as a second pass (mul_rows_kernel) */
+  ASR_GEMMP_DROP_PASS,            /* asr_gemm_drop calls whose dropout ran as a second pass (asr_dropout_apply) */
   ASR_GEMMP_N
 };
 int asr_gemm_path_counts(asr_handle* h, unsigned long long* out, int n);

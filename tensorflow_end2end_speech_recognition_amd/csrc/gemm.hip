@@ -658,12 +658,12 @@ static void launch_gemm_nt_rows128(int nrows, int N, int K, const void* A, int l
 
 // rows / nrows (asr_gemm_rows, fp32 output): the product of the `nrows` (>= 1) listed rows only.  Whether the lean path
 // applies is judged on the full M, as for the full product; which of the two kernels runs, on the listed count.
-// counts: the handle's gemm_counts (listed-row launches by kernel).
+// counts: the handle's gemm_counts (listed-row launches by kernel).  used_big: set to whether the 256 x 256 kernel ran.
 template <typename TO>
 bool try_gemm_nt_bf16(int transA, int transB, int M, int N, int K, const void* A, int lda, const void* B,
                       int ldb, void* C, int ldc, const float* bias, int accumulate, hipStream_t st, int act,
                       const float* mul, int ldm, GemmDrop drop = GemmDrop{1.f, 0, 0, 0}, const int32_t* rows = nullptr,
-                      int nrows = 0, unsigned long long* counts = nullptr) {
+                      int nrows = 0, unsigned long long* counts = nullptr, bool* used_big = nullptr) {
   if (transA || !transB || K % 64 != 0 || N % 128 != 0 || M < 1024) return false;
   if (drop.use && sizeof(TO) != 4) return false;
   if (mul && (sizeof(TO) != 4 || ldm % 4 != 0 || ((uintptr_t)mul) % 16 != 0)) return false;
@@ -677,6 +677,7 @@ bool try_gemm_nt_bf16(int transA, int transB, int M, int N, int K, const void* A
   const int Mk = rows ? nrows : M;                          // rows the launch computes
   const long tiles256 = (long)(N / 256) * ((Mk + 255) / 256);
   const bool use_big = big && fits32 && N % 256 == 0 && (big == 2 ? Mk >= 2048 : tiles256 >= 512);
+  if (used_big) *used_big = use_big;
   if constexpr (sizeof(TO) == 4) {
     if (rows) {
       if (use_big)
@@ -933,11 +934,12 @@ __global__ __launch_bounds__(64 * SK_WAVES) void gemm_skinny_f32_kernel(int M, i
   }
 }
 
-static bool try_gemm_skinny_f32(int transA, int transB, int M, int N, int K, const void* A, int lda, const void* B,
-                                int ldb, void* C, int ldc, const float* bias, int accumulate, hipStream_t st, int act) {
-  if (transA || M < 1 || M > 32 || K % 64 != 0 || N % 16 != 0 || K < 64) return false;
-  if (lda % 4 != 0 || ((uintptr_t)A) % 16 != 0 || ((uintptr_t)B) % 16 != 0) return false;
-  if (transB && ldb % 4 != 0) return false;
+// Returns the ASR_GEMMP_SKINNY_* counter of the instantiation it launched, -1 where the skinny path does not apply.
+static int try_gemm_skinny_f32(int transA, int transB, int M, int N, int K, const void* A, int lda, const void* B,
+                               int ldb, void* C, int ldc, const float* bias, int accumulate, hipStream_t st, int act) {
+  if (transA || M < 1 || M > 32 || K % 64 != 0 || N % 16 != 0 || K < 64) return -1;
+  if (lda % 4 != 0 || ((uintptr_t)A) % 16 != 0 || ((uintptr_t)B) % 16 != 0) return -1;
+  if (transB && ldb % 4 != 0) return -1;
   // full 128-byte lines of a row-major B need 32 columns per workgroup; B^T rows are contiguous in k, so the narrow
   // tile (twice the workgroups) is used until the launch is wide enough anyway
   const bool wide = (N % 32 == 0) && (!transB || N >= 32 * 192);
@@ -951,7 +953,7 @@ static bool try_gemm_skinny_f32(int transA, int transB, int M, int N, int K, con
     if (wide) ASR_SKINNY(false, 2); else ASR_SKINNY(false, 1);
   }
 #undef ASR_SKINNY
-  return true;
+  return transB ? (wide ? ASR_GEMMP_SKINNY_NT32 : ASR_GEMMP_SKINNY_NT16) : (wide ? ASR_GEMMP_SKINNY_NN32 : ASR_GEMMP_SKINNY_NN16);
 }
 
 // ---------------------------------------------------------------- lean TN kernel (bf16)
@@ -1202,16 +1204,27 @@ int launch_gemm(asr_handle* h, int transA, int transB, int M, int N, int K, cons
                 hipStream_t st, int act, const float* mul = nullptr, int ldm = 0, bool* mul_done = nullptr,
                 GemmDrop drop = GemmDrop{1.f, 0, 0, 0}, TnFrames fv = TnFrames{nullptr, 1, 0}) {
   constexpr int VEC = GT<T>::VEC, BK = GT<T>::BK;
+  // every return below bumps the ASR_GEMMP_* counter of the kernel the product ended in (host integers on the handle)
   if constexpr (sizeof(T) == 4 && sizeof(TO) == 4) {
-    if (try_gemm_skinny_f32(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, st, act)) return 0;
+    const int sk = try_gemm_skinny_f32(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, st, act);
+    if (sk >= 0) {
+      h->gemm_counts[sk] += 1;
+      return 0;
+    }
   }
   if constexpr (sizeof(T) == 2) {
-    if (try_gemm_nt_bf16<TO>(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, st, act, mul, ldm, drop)) {
+    bool used_big = false;
+    if (try_gemm_nt_bf16<TO>(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, st, act, mul, ldm, drop,
+                             nullptr, 0, nullptr, &used_big)) {
       if (mul_done) *mul_done = true;
+      h->gemm_counts[used_big ? ASR_GEMMP_NT256 : ASR_GEMMP_NT128] += 1;
       return 0;
     }
     // reduction-major operands (X^T dG): lean TN kernel, always through split-K slabs
-    if (try_gemm_tn_bf16<TO>(h, transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, st, act, fv)) return 0;
+    if (try_gemm_tn_bf16<TO>(h, transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, st, act, fv)) {
+      h->gemm_counts[ASR_GEMMP_TN_LEAN] += 1;
+      return 0;
+    }
   }
   const int aa = (((uintptr_t)A) % 16 == 0) && (lda % VEC == 0);
   const int ba = (((uintptr_t)B) % 16 == 0) && (ldb % VEC == 0);
@@ -1227,6 +1240,7 @@ int launch_gemm(asr_handle* h, int transA, int transB, int M, int N, int K, cons
       (void)hipFuncSetAttribute((const void*)gemm_kernel<T, TO, 128, 128, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       (void)hipFuncSetAttribute((const void*)gemm_kernel<T, TO, 128, 128, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
+    h->gemm_counts[ASR_GEMMP_GENERIC128] += 1;
     return launch_layout<T, TO, 128, 128>(transA, transB, grid, lds, st, M, N, K, (const T*)A, lda,
                                           (const T*)B, ldb, (TO*)C, ldc, bias, accumulate, aa, ba, K, nullptr, act, fv);
   }
@@ -1245,6 +1259,7 @@ int launch_gemm(asr_handle* h, int transA, int transB, int M, int N, int K, cons
   size_t lds = (size_t)2 * (64 + 64) * (BK + VEC) * sizeof(T);
   if (S <= 1) {
     dim3 grid((N + 63) / 64, (M + 63) / 64);
+    h->gemm_counts[ASR_GEMMP_GENERIC64] += 1;
     return launch_layout<T, TO, 64, 64>(transA, transB, grid, lds, st, M, N, K, (const T*)A, lda,
                                         (const T*)B, ldb, (TO*)C, ldc, bias, accumulate, aa, ba, K, nullptr, act, fv);
   }
@@ -1253,6 +1268,7 @@ int launch_gemm(asr_handle* h, int transA, int transB, int M, int N, int K, cons
   S = (K + kchunk - 1) / kchunk;
   dim3 grid((N + 63) / 64, (M + 63) / 64, S);
   float* partial = (float*)h->scratch;
+  h->gemm_counts[ASR_GEMMP_GENERIC64_SPLITK] += 1;
   launch_layout<T, TO, 64, 64>(transA, transB, grid, lds, st, M, N, K, (const T*)A, lda, (const T*)B, ldb,
                                (TO*)C, ldc, nullptr, 0, aa, ba, kchunk, partial, 0, fv);
   const size_t total = (size_t)M * N;
@@ -1367,6 +1383,7 @@ extern "C" int asr_gemm_mul(asr_handle* h, int dtype, int transA, int transB, in
     int blocks = (int)((total + 255) / 256);
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(mul_rows_kernel, dim3(blocks), dim3(256), 0, st, C, ldc, mul, ldmul, M, N);
+    h->gemm_counts[ASR_GEMMP_MUL_PASS] += 1;
     ASR_CHECK_LAUNCH(h, "asr_gemm_mul(multiply)");
   }
   return ASR_OK;
@@ -1393,7 +1410,10 @@ extern "C" int asr_gemm_drop(asr_handle* h, int dtype, int transA, int transB, i
   else
     launch_gemm<bf16_t, float>(h, transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, st, act, nullptr, 0, &fused, drop);
   ASR_CHECK_LAUNCH(h, "asr_gemm_drop");
-  if (!fused) return asr_dropout_apply(h, ASR_F32, C, C, (size_t)M * N, keep_prob, seed, offset, s);
+  if (!fused) {
+    h->gemm_counts[ASR_GEMMP_DROP_PASS] += 1;
+    return asr_dropout_apply(h, ASR_F32, C, C, (size_t)M * N, keep_prob, seed, offset, s);
+  }
   return ASR_OK;
 }
 

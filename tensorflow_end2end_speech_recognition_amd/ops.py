@@ -1580,6 +1580,9 @@ def reset_conv_path_counts(device=0):
 _GEMM_PATH_KEYS = ('rows_128', 'rows_256', 'rows_full')
 _TN_PATH_KEYS = ('tn_frames', 'tn_frames_generic')
 _HEAD_BWD_KEYS = ('head_bwd_lean', 'head_bwd_full')   # behind those    # behind the listed-row counters in the ASR_GEMMP_* enum
+# behind those: the kernel a full product ended in, and the second passes of gemm(mul=...) / gemm(drop=...)
+_GEMM_KERNEL_KEYS = ('skinny_nn16', 'skinny_nn32', 'skinny_nt16', 'skinny_nt32', 'nt128', 'nt256', 'tn_lean', 'generic128',
+                     'generic64', 'generic64_splitk', 'mul_pass', 'drop_pass')
 
 
 def gemm_path_counts(device=0):
@@ -1618,6 +1621,21 @@ def ctc_head_bwd_counts(device=0):
         h.check(h.lib.asr_gemm_path_counts(h.h, out, n), 'asr_gemm_path_counts')
         tot = [a + int(b) for a, b in zip(tot, out)]
     return dict(zip(_HEAD_BWD_KEYS, tot[n0:]))
+
+
+def gemm_kernel_counts(device=0):
+    """The kernel each full product on `device` ended in since the last reset_gemm_path_counts (gemm() without rows, and
+    the listed-row / tn-frames / head-bwd calls that fell to the full product): the four skinny fp32 forms, the lean NT
+    kernels by tile size, the lean TN kernel, the generic kernel by tile size and split-K; and the calls whose multiplier
+    (mul_pass) or dropout (drop_pass) ran as a second pass instead of in an epilogue."""
+    n0 = len(_GEMM_PATH_KEYS) + len(_TN_PATH_KEYS) + len(_HEAD_BWD_KEYS)
+    n = n0 + len(_GEMM_KERNEL_KEYS)
+    tot = [0] * n
+    for h in _device_handles(device):
+        out = (C.c_ulonglong * n)()
+        h.check(h.lib.asr_gemm_path_counts(h.h, out, n), 'asr_gemm_path_counts')
+        tot = [a + int(b) for a, b in zip(tot, out)]
+    return dict(zip(_GEMM_KERNEL_KEYS, tot[n0:]))
 
 
 def reset_gemm_path_counts(device=0):
