@@ -169,7 +169,8 @@ def build_model(params):
                 dtype=params.get('dtype', 'bf16'), device=params.get('device', 'cuda:0'),
                 subsample_list=params.get('subsample_list'), subsample_type=params.get('subsample_type', 'drop'),
                 encoder_residual=bool(params.get('encoder_residual', False)),
-                encoder_dense_residual=bool(params.get('encoder_dense_residual', False)))
+                encoder_dense_residual=bool(params.get('encoder_dense_residual', False)),
+                label_smoothing_prob=float(params.get('label_smoothing_prob') or 0.0))
     # run-directory name, as :338-351
     model.name += '_' + str(params['num_units'])
     model.name += '_' + str(params['num_layers'])
@@ -189,6 +190,8 @@ def build_model(params):
         model.name += '_res'
     elif params.get('encoder_dense_residual'):
         model.name += '_dres'
+    if params.get('label_smoothing_prob'):
+        model.name += '_ls' + str(params['label_smoothing_prob'])
     return model
 
 

@@ -69,14 +69,23 @@ def do_train(model, params):
                          'CER' if is_char else 'PER')
 
 
+def joint_run_name(params):
+    name = run_name(params) + '_lambda' + str(params['lambda_weight'])
+    if params.get('ctc_label_smoothing_prob'):
+        name += '_ctcls' + str(params['ctc_label_smoothing_prob'])
+    return name
+
+
 def main(config_path, model_save_path, log_to_file=True):
     with open(config_path, 'r') as f:
         params = yaml.safe_load(f)['param']
     if params['label_type'] not in NUM_CLASSES:
         raise TypeError
     params['num_classes'] = NUM_CLASSES[params['label_type']]
-    model = JointCTCAttention(lambda_weight=params['lambda_weight'], **model_kwargs(params))
-    model.name = run_name(params) + '_lambda' + str(params['lambda_weight'])
+    model = JointCTCAttention(lambda_weight=params['lambda_weight'],
+                              ctc_label_smoothing_prob=float(params.get('ctc_label_smoothing_prob') or 0.0),
+                              **model_kwargs(params))
+    model.name = joint_run_name(params)
     model.save_path = new_run_directory(join(model_save_path, 'joint_ctc_attention', params['label_type'], model.name),
                                         config_path)
     result = run_with_log(lambda: do_train(model, params), model.save_path, log_to_file)

@@ -68,6 +68,18 @@ def do_train(model, params):
     return training_loop(model, params, train_data, dev_data, train_step, monitor, evaluate, 'CER')
 
 
+def run_name_suffix(params):
+    """What follows the model's own name in the run directory's name."""
+    name = '_' + str(params['num_units']) + '_main' + str(params['num_layers_main'])
+    name += '_sub' + str(params['num_layers_sub']) + '_' + params['optimizer']
+    name += '_lr' + str(params['learning_rate']) + '_w' + str(params['main_task_weight'])
+    if params['dropout'] != 0:
+        name += '_drop' + str(params['dropout'])
+    if params.get('label_smoothing_prob'):
+        name += '_ls' + str(params['label_smoothing_prob'])
+    return name
+
+
 def main(config_path, model_save_path, log_to_file=True):
     with open(config_path, 'r') as f:
         params = yaml.safe_load(f)['param']
@@ -81,12 +93,9 @@ def main(config_path, model_save_path, log_to_file=True):
                          parameter_init=params['weight_init'], clip_grad_norm=params['clip_grad_norm'],
                          clip_activation=params['clip_activation'], num_proj=params['num_proj'],
                          weight_decay=params['weight_decay'], dtype=params.get('dtype', 'bf16'),
-                         device=params.get('device', 'cuda:0'))
-    model.name += '_' + str(params['num_units']) + '_main' + str(params['num_layers_main'])
-    model.name += '_sub' + str(params['num_layers_sub']) + '_' + params['optimizer']
-    model.name += '_lr' + str(params['learning_rate']) + '_w' + str(params['main_task_weight'])
-    if params['dropout'] != 0:
-        model.name += '_drop' + str(params['dropout'])
+                         device=params.get('device', 'cuda:0'),
+                         label_smoothing_prob=float(params.get('label_smoothing_prob') or 0.0))
+    model.name += run_name_suffix(params)
     model.save_path = new_run_directory(
         join(model_save_path, 'ctc', params['label_type_main'] + '_' + params['label_type_sub'], model.name),
         config_path)

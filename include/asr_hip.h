@@ -679,6 +679,27 @@ int asr_ctc_loss_ex(asr_handle* h, const float* logits, int T, int B, int C,
                     const int32_t* seq_len, int max_label_len, float grad_scale,
                     float* loss, float* grad, int32_t* num_infeasible,
                     void* workspace, size_t workspace_bytes, int lse_done, void* grad_bf16, int Kp, asr_stream s);
+/* EXTENSION (not in the reference: its blstm_ctc_ls.yml sets label_smoothing_prob, none of its code reads the key): label
+ * smoothing of a CTC head towards the uniform distribution over all C classes, blank included.  asr_ctc_loss_ex's
+ * arguments plus smoothing = eps in (0, 1) (else ASR_ERR_INVALID_ARG) and kl [B]:
+ *   loss[b] = the UNSMOOTHED CTC loss, the bits of asr_ctc_loss on the same inputs for every eps
+ *   kl[b]   = sum_{t < min(seq_len[b], T)} KL(uniform || softmax(logits[t,b,:])) = sum_t (lse - mean_k x_k - ln C)
+ *   grad    = grad_scale * (softmax - (1 - eps) * occupation - eps / C): the gradient of (1 - eps) loss[b] + eps kl[b],
+ *             written by the gradient kernel in its one pass over the row (grad_bf16: the image of THESE values)
+ * The caller forms (1 - eps) loss + eps kl.  Infeasible utterances and seq_len[b] == 0 give loss 0, kl 0, grad 0; frames
+ * t >= seq_len[b] are never read (grad and image rows 0).  Logits must be finite (a -inf logit makes KL infinite).
+ * grad may be NULL (kl is still produced).  Row terms are formed in fp64 and reduced per utterance in a fixed order: the
+ * same bits on every call.  workspace: asr_ctc_ls_workspace_bytes -- the layout of asr_ctc_workspace_bytes is a prefix of
+ * it, so asr_ctc_head_fwd on such a workspace followed by lse_done = 1 here is the smoothed head in three launches.
+ * asr_ctc_ls_counts: {calls, calls with lse_done, calls without grad} since the last reset. */
+size_t asr_ctc_ls_workspace_bytes(int T, int B, int max_label_len);
+int asr_ctc_loss_ls(asr_handle* h, const float* logits, int T, int B, int C,
+                    const int32_t* labels_flat, const int32_t* label_offsets,
+                    const int32_t* seq_len, int max_label_len, float grad_scale, float smoothing,
+                    float* loss, float* kl, float* grad, int32_t* num_infeasible,
+                    void* workspace, size_t workspace_bytes, int lse_done, void* grad_bf16, int Kp, asr_stream s);
+int asr_ctc_ls_counts(asr_handle* h, unsigned long long* out3);
+int asr_reset_ctc_ls_counts(asr_handle* h);
 /* The output layer of a CTC model and the first CTC launch in ONE kernel (bf16 operands, E % 64 == 0, C <= 64):
  *   x_op   = dropout(hout)               [T*B, E] bf16, asr_dropout_apply(keep_prob, seed, offset) bit for bit, every row
  *                                        (keep_prob == 0: no dropout, x_op is not written and may be NULL -- hout IS the operand)

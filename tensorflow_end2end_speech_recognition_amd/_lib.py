@@ -117,6 +117,11 @@ SIGNATURES = {
     'asr_ctc_workspace_bytes': (_sz, [_i, _i, _i]),
     'asr_ctc_loss': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     'asr_ctc_loss_ex': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _sz, _i, _vp, _i, _vp]),
+    'asr_ctc_ls_workspace_bytes': (_sz, [_i, _i, _i]),
+    'asr_ctc_loss_ls': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp, _i,
+                             _vp]),
+    'asr_ctc_ls_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
+    'asr_reset_ctc_ls_counts': (_i, [_vp]),
     'asr_ctc_head_ok': (_i, [_i, _i, _i]),
     'asr_ctc_head_prep': (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     'asr_ctc_head_fwd': (_i, [_vp, _vp, _i, _i, _i, _f, _u64, _u64, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp,

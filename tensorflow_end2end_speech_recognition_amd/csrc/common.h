@@ -45,6 +45,8 @@ struct asr_handle {
   unsigned long long ctc_beam_lm_counts[3];
   // CTC head since the last asr_reset_ctc_head_counts: {asr_ctc_head_fwd launches, asr_ctc_loss_ex calls, asr_ctc_loss calls}
   unsigned long long ctc_head_counts[3];
+  // asr_ctc_loss_ls since the last asr_reset_ctc_ls_counts: {calls, calls with lse_done, calls without a gradient}
+  unsigned long long ctc_ls_counts[3];
   // GRU decoder steps since the last asr_reset_att_gru_counts: {two-launch forward, four-launch forward, backward}
   unsigned long long att_gru_counts[3];
   // upper layers of a decoder stack since the last asr_reset_att_stack_counts: {forward on the image, forward as product +

@@ -26,6 +26,9 @@
 //   3.  grad         ctc_grad_kernel<true> also stores the bf16 operand image [T*B, Kp] of what it writes (zero columns
 //                    behind C): no cast pass; d(encoder output) is then the lean NT product image x Wp^T on valid frames
 //                    with the top layer's dropout in its epilogue (models/ctc/ctc.py)
+// Label smoothing of the head (asr_ctc_loss_ls, an extension) stays inside launch 3 -- ctc_grad_kernel<IMG, true> writes
+// softmax - (1 - eps) occupation - eps / C and the row's KL term -- plus one small launch that sums the KL terms per utterance
+// (3b); launch 2 is untouched, so the loss it returns is the plain one.
 // Headline step (5 x 256, B = 16, T = 745, C = 39): 270 -> 221 us between the two recurrences
 // (profiles/r09_ctc_head_tn_frames.md).  Other shapes, fp32 models and asr_ctc_loss keep launches 1, 2, 3.
 #include "common.h"
@@ -441,14 +444,19 @@ __global__ __launch_bounds__(64 * NW) void ctc_alpha_beta_kernel(
 // IMG: every value written to grad also goes, rounded as asr_cast_from_f32 rounds it, to the bf16 image gimg [T*B, Kp]
 // (Kp >= C a multiple of 64, columns C .. Kp-1 zero in every row): the operand of the products that consume dlogits,
 // without a cast pass over grad.
-template <bool IMG>
+// LS (asr_ctc_loss_ls, an EXTENSION: label smoothing towards the uniform distribution over all C classes): the row's value
+// becomes softmax - om * occupation - eC (om = 1 - eps, eC = eps / C), and lane 0 leaves the row's term of
+// KL(uniform || softmax) = lse - mean_k x_k - ln C in klrow[t * B + b] (fp64; rows of padded frames and of infeasible
+// utterances are not written and ctc_kl_finish_kernel does not read them).  LS = false reads none of om, eC, klrow.
+template <bool IMG, bool LS = false>
 __global__ __launch_bounds__(256) void ctc_grad_kernel(
     const float* __restrict__ logits, const double* __restrict__ lse, int T, int B, int C,
     const int32_t* __restrict__ labels_flat, const int32_t* __restrict__ label_offsets,
     const int32_t* __restrict__ seq_len, int SW, int SP, const MantExp* __restrict__ yext,
     const MantExp* __restrict__ alpha_ws, const MantExp* __restrict__ beta_ws,
     const int32_t* __restrict__ rank_ws, const double* __restrict__ ll_ws, float grad_scale,
-    float* __restrict__ grad, bf16_t* __restrict__ gimg, int Kp) {
+    float* __restrict__ grad, bf16_t* __restrict__ gimg, int Kp, float om = 1.f, float eC = 0.f,
+    double* __restrict__ klrow = nullptr) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   // Per wave: gam[SW] (state occupations), acc[(SW-1)/2] (occupation of a class, kept at the position of its FIRST
@@ -520,6 +528,25 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(
     __builtin_amdgcn_wave_barrier();
   }
   // classes that are not labels (and not blank): softmax only; every address below is written exactly once
+  if constexpr (LS) {                                      // (the same three kinds of class, smoothed)
+    double sx = 0.0;                                       // the row sum of the KL term rides on the pass over the classes
+    for (int k = lane; k < C; k += 64) {
+      const double x = (double)row[k];
+      sx += x;
+      if (k == blank) put(k, ((float)exp(x - z) - om * blank_sum - eC) * grad_scale);
+      else if (!((bits[k >> 5] >> (k & 31)) & 1u)) put(k, ((float)exp(x - z) - eC) * grad_scale);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sx += __shfl_xor(sx, o, 64);
+    if (lane == 0) klrow[(size_t)t * B + b] = z - sx / (double)C - log((double)C);
+    for (int i = lane; i < L; i += 64) {
+      if ((rk[i] & 0xffff) == 0) {
+        const int k = lab[i];
+        put(k, ((float)exp((double)row[k] - z) - om * acc[i] - eC) * grad_scale);
+      }
+    }
+    return;
+  }
   for (int k = lane; k < C; k += 64) {
     if (k == blank) put(k, ((float)exp((double)row[k] - z) - blank_sum) * grad_scale);
     else if (!((bits[k >> 5] >> (k & 31)) & 1u)) put(k, (float)exp((double)row[k] - z) * grad_scale);
@@ -530,6 +557,48 @@ __global__ __launch_bounds__(256) void ctc_grad_kernel(
       put(k, ((float)exp((double)row[k] - z) - acc[i]) * grad_scale);
     }
   }
+}
+
+// ---- 3b. label smoothing: the KL term per utterance ---------------------------------------------------------------------
+// The row terms of a call WITHOUT a gradient (want_grad = False: dev-style calls of the op itself): one wave per valid
+// (t, b) row, the sum ctc_grad_kernel<.., true> forms, in the same order -> the same bits.
+__global__ __launch_bounds__(256) void ctc_kl_rows_kernel(const float* __restrict__ logits, const double* __restrict__ lse,
+                                                          int T, int B, int C, const int32_t* __restrict__ seq_len,
+                                                          double* __restrict__ klrow) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= T * B) return;
+  const int t = r / B, b = r - t * B;
+  if (t >= min(seq_len[b], T)) return;                       // frames past the utterance are never read
+  const float* row = logits + (size_t)r * C;
+  double sx = 0.0;
+  for (int k = lane; k < C; k += 64) sx += (double)row[k];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sx += __shfl_xor(sx, o, 64);
+  if (lane == 0) klrow[r] = lse[r] - sx / (double)C - log((double)C);
+}
+
+// kl[b] = sum over the utterance's frames of klrow, one workgroup per utterance: thread i adds frames i, i + 256, ... in
+// ascending order, then a fixed tree over the 256 partial sums -- no atomics, the same bits on every call.  Infeasible and
+// empty utterances get 0 (their rows were never written).
+__global__ __launch_bounds__(256) void ctc_kl_finish_kernel(const double* __restrict__ klrow, int T, int B,
+                                                            const int32_t* __restrict__ seq_len,
+                                                            const double* __restrict__ ll_ws, float* __restrict__ kl) {
+  __shared__ double part[256];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int Tb = min(seq_len[b], T);
+  const bool ok = Tb > 0 && ll_ws[b] > DNEG_INF;
+  double s = 0.0;
+  if (ok)
+    for (int t = tid; t < Tb; t += 256) s += klrow[(size_t)t * B + b];
+  part[tid] = s;
+  __syncthreads();
+#pragma unroll
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) part[tid] += part[tid + o];
+    __syncthreads();
+  }
+  if (tid == 0) kl[b] = ok ? (float)part[0] : 0.f;
 }
 
 // ---- greedy decode -------------------------------------------------------------
@@ -630,6 +699,11 @@ inline CtcWs ctc_ws_layout(int T, int B, int Lmax) {
   w.total = o;
   return w;
 }
+// asr_ctc_loss_ls: the plain layout (what asr_ctc_head_fwd writes stays a prefix) and behind it the KL row terms [T*B] fp64
+inline size_t ctc_ls_ws_total(int T, int B, int Lmax) {
+  return ctc_ws_layout(T, B, Lmax).total + ((size_t)T * B * 8 + 255) / 256 * 256;
+}
+struct CtcLs { float smoothing; float* kl; };
 
 }  // namespace
 
@@ -638,12 +712,19 @@ extern "C" size_t asr_ctc_workspace_bytes(int T, int B, int max_label_len) {
   return ctc_ws_layout(T, B, max_label_len).total;
 }
 
-// lse_done: kernel 1 has already run on this workspace (asr_ctc_head_fwd); gimg / Kp: the bf16 image of grad (or NULL)
+extern "C" size_t asr_ctc_ls_workspace_bytes(int T, int B, int max_label_len) {
+  if (T < 0 || B < 0 || max_label_len < 0) return 0;
+  return ctc_ls_ws_total(T, B, max_label_len);
+}
+
+// lse_done: kernel 1 has already run on this workspace (asr_ctc_head_fwd); gimg / Kp: the bf16 image of grad (or NULL);
+// ls: asr_ctc_loss_ls only (NULL: the plain loss, which reads nothing of it)
 static int ctc_loss_impl(asr_handle* h, const float* logits, int T, int B, int C,
                          const int32_t* labels_flat, const int32_t* label_offsets,
                          const int32_t* seq_len, int max_label_len, float grad_scale, float* loss,
                          float* grad, int32_t* num_infeasible, void* workspace,
-                         size_t workspace_bytes, int lse_done, void* gimg, int Kp, asr_stream s) {
+                         size_t workspace_bytes, int lse_done, void* gimg, int Kp, asr_stream s,
+                         const CtcLs* ls = nullptr) {
   if (!h) return ASR_ERR_INVALID_ARG;
   if (!logits || !label_offsets || !seq_len || !loss || T <= 0 || B <= 0 || C < 2 ||
       max_label_len < 0 || (max_label_len > 0 && !labels_flat))
@@ -653,6 +734,9 @@ static int ctc_loss_impl(asr_handle* h, const float* logits, int T, int B, int C
   if (!w.K) ASR_FAIL(h, ASR_ERR_UNSUPPORTED, "asr_ctc_loss: label length %d > %d", max_label_len, (64 * 32 - 1) / 2);
   if (!workspace || workspace_bytes < w.total)
     ASR_FAIL(h, ASR_ERR_WORKSPACE, "asr_ctc_loss: workspace %zu < %zu bytes", workspace_bytes, w.total);
+  if (ls && workspace_bytes < ctc_ls_ws_total(T, B, max_label_len))
+    ASR_FAIL(h, ASR_ERR_WORKSPACE, "asr_ctc_loss_ls: workspace %zu < %zu bytes (asr_ctc_ls_workspace_bytes)", workspace_bytes,
+             ctc_ls_ws_total(T, B, max_label_len));
   char* ws = (char*)workspace;
   double* lse = (double*)(ws + w.lse);
   MantExp* yext = (MantExp*)(ws + w.yext);
@@ -703,7 +787,20 @@ static int ctc_loss_impl(asr_handle* h, const float* logits, int T, int B, int C
     const size_t lds_g = (size_t)4 * (SW + (SW - 1) / 2 + (C + 31) / 32) * sizeof(float);
     if (lds_g > 160 * 1024)
       ASR_FAIL(h, ASR_ERR_UNSUPPORTED, "asr_ctc_loss: C=%d, Lmax=%d need %zu B of LDS", C, max_label_len, lds_g);
-    if (gimg) {
+    if (ls) {
+      double* klrow = (double*)(ws + w.total);
+      const float om = 1.f - ls->smoothing, eC = ls->smoothing / (float)C;
+#define ASR_GRAD_LS(IMG_, GI_, KP_)                                                                                          \
+  do {                                                                                                                       \
+    (void)hipFuncSetAttribute((const void*)ctc_grad_kernel<IMG_, true>, hipFuncAttributeMaxDynamicSharedMemorySize,          \
+                              (int)lds_g);                                                                                   \
+    hipLaunchKernelGGL((ctc_grad_kernel<IMG_, true>), dim3((T + 3) / 4, B), dim3(256), lds_g, st, logits, lse, T, B, C,      \
+                       labels_flat, label_offsets, seq_len, SW, SP, yext, alpha, beta, rank, ll, grad_scale, grad, GI_, KP_, \
+                       om, eC, klrow);                                                                                       \
+  } while (0)
+      if (gimg) ASR_GRAD_LS(true, (bf16_t*)gimg, Kp); else ASR_GRAD_LS(false, (bf16_t*)nullptr, 0);
+#undef ASR_GRAD_LS
+    } else if (gimg) {
       (void)hipFuncSetAttribute((const void*)ctc_grad_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g);
       hipLaunchKernelGGL(ctc_grad_kernel<true>, dim3((T + 3) / 4, B), dim3(256), lds_g, st, logits, lse, T, B, C,
                          labels_flat, label_offsets, seq_len, SW, SP, yext, alpha, beta, rank, ll, grad_scale, grad,
@@ -715,6 +812,15 @@ static int ctc_loss_impl(asr_handle* h, const float* logits, int T, int B, int C
                          (bf16_t*)nullptr, 0);
     }
     ASR_CHECK_LAUNCH(h, "asr_ctc_loss(grad)");
+  }
+  if (ls) {
+    double* klrow = (double*)(ws + w.total);
+    if (!grad) {
+      hipLaunchKernelGGL(ctc_kl_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, logits, lse, T, B, C, seq_len, klrow);
+      ASR_CHECK_LAUNCH(h, "asr_ctc_loss_ls(kl_rows)");
+    }
+    hipLaunchKernelGGL(ctc_kl_finish_kernel, dim3(B), dim3(256), 0, st, klrow, T, B, seq_len, ll, ls->kl);
+    ASR_CHECK_LAUNCH(h, "asr_ctc_loss_ls(kl_finish)");
   }
   return ASR_OK;
 }
@@ -740,6 +846,29 @@ extern "C" int asr_ctc_loss_ex(asr_handle* h, const float* logits, int T, int B,
   h->ctc_head_counts[1] += 1;
   return ctc_loss_impl(h, logits, T, B, C, labels_flat, label_offsets, seq_len, max_label_len, grad_scale, loss, grad,
                        num_infeasible, workspace, workspace_bytes, lse_done, grad_bf16, Kp, s);
+}
+
+// asr_ctc_loss_ex's arguments plus the smoothing eps in (0, 1) and kl [B]: loss stays the UNSMOOTHED CTC loss (the recursion
+// launch is the plain one), grad = grad_scale (softmax - (1 - eps) occupation - eps / C), kl[b] = sum_t KL(uniform || softmax).
+// Launches: [row_lse] alpha_beta grad kl_finish with a gradient (one more than asr_ctc_loss_ex), [row_lse] alpha_beta kl_rows
+// kl_finish without.
+extern "C" int asr_ctc_loss_ls(asr_handle* h, const float* logits, int T, int B, int C, const int32_t* labels_flat,
+                               const int32_t* label_offsets, const int32_t* seq_len, int max_label_len, float grad_scale,
+                               float smoothing, float* loss, float* kl, float* grad, int32_t* num_infeasible,
+                               void* workspace, size_t workspace_bytes, int lse_done, void* grad_bf16, int Kp,
+                               asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  if (!(smoothing > 0.f && smoothing < 1.f))
+    ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_ctc_loss_ls: smoothing = %g outside (0, 1)", (double)smoothing);
+  if (!kl) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_ctc_loss_ls: kl is NULL");
+  if (grad_bf16 && (!grad || Kp < C || Kp % 64 != 0))
+    ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_ctc_loss_ls: the bf16 image needs grad and Kp = %d >= C = %d, Kp %% 64 == 0", Kp, C);
+  h->ctc_ls_counts[0] += 1;
+  if (lse_done) h->ctc_ls_counts[1] += 1;
+  if (!grad) h->ctc_ls_counts[2] += 1;
+  const CtcLs ls = {smoothing, kl};
+  return ctc_loss_impl(h, logits, T, B, C, labels_flat, label_offsets, seq_len, max_label_len, grad_scale, loss, grad,
+                       num_infeasible, workspace, workspace_bytes, lse_done, grad_bf16, Kp, s, &ls);
 }
 
 // today's logits product of the shape runs asr_gemm's generic kernel in ONE pass over K (no split-K slabs), whose
@@ -800,6 +929,7 @@ extern "C" int asr_ctc_head_fwd(asr_handle* h, const void* hout, int T, int B, i
 }
 
 ASR_DEFINE_COUNTS3(ctc_head_counts)
+ASR_DEFINE_COUNTS3(ctc_ls_counts)
 
 extern "C" int asr_ctc_greedy_decode(asr_handle* h, const float* logits, int T, int B, int C,
                                      const int32_t* seq_len, int blank, int32_t* out_labels,

@@ -11,6 +11,9 @@ clip_activation_decoder=50, weight_decay=0.0, time_major=True, sharpening_factor
 class as literals (:133-137) -- whatever the recipe passed (examples/timit/training/train_joint_ctc_attention.py:382-386
 passes all of them from the config) is ignored.  REPRODUCED by default, with a warning when a passed value differs from
 the literal; `honour_ctor_args=True` (extension keyword) uses the caller's values instead.
+`ctc_label_smoothing_prob` (extension keyword): label smoothing of the CTC head as CTC(label_smoothing_prob=...) applies it
+(ops.ctc_loss_ls, training steps only; lambda scales the whole smoothed term); `label_smoothing_prob` keeps meaning the
+attention targets only.
 """
 import warnings
 
@@ -36,8 +39,11 @@ class JointCTCAttention(AttentionSeq2Seq):
                  lstm_impl='LSTMBlockCell', use_peephole=True, splice=1, parameter_init=0.1,
                  clip_grad_norm=5.0, clip_activation_encoder=50, clip_activation_decoder=50,
                  weight_decay=0.0, time_major=True, sharpening_factor=1.0, logits_temperature=1.0,
-                 name='joint_ctc_attention', honour_ctor_args=False, **kw):
+                 name='joint_ctc_attention', honour_ctor_args=False, ctc_label_smoothing_prob=0.0, **kw):
         assert 0 <= lambda_weight <= 1, 'lambda_weight must be in [0, 1]'
+        if not 0.0 <= float(ctc_label_smoothing_prob) < 1.0:
+            raise ValueError('ctc_label_smoothing_prob must be in [0, 1), got %r' % (ctc_label_smoothing_prob,))
+        self.ctc_label_smoothing_prob = float(ctc_label_smoothing_prob)
         if not honour_ctor_args:                      # Q15: joint_ctc_attention.py:133-137
             passed = dict(clip_activation_decoder=clip_activation_decoder, weight_decay=weight_decay,
                           time_major=time_major, sharpening_factor=sharpening_factor,
@@ -91,6 +97,10 @@ class JointCTCAttention(AttentionSeq2Seq):
         # pinned staging + asynchronous copies: a pageable upload would drain the stream (ops.to_device)
         flat_d = ops.to_device(flat if len(flat) else np.zeros(1, np.int32), torch.int32, dev)
         off_d = ops.to_device(offsets, torch.int32, dev)
+        eps = self.ctc_label_smoothing_prob if is_training else 0.0
+        if eps > 0.0:
+            losses, kl, grad, _, ninf = ops.ctc_loss_ls(logits, flat_d, off_d, seq_p, max_len, eps, grad_scale=lam / B)
+            return logits, losses, grad, ninf, flat_d, off_d, (eps, kl)
         losses, grad, ninf = ops.ctc_loss(logits, flat_d, off_d, seq_p, max_len, grad_scale=lam / B,
                                           want_grad=is_training)
         return logits, losses, grad, ninf, flat_d, off_d
@@ -128,6 +138,9 @@ class JointCTCAttention(AttentionSeq2Seq):
         # must not wait for the forward pass every step; the error surfaces at most ops.DeferredCheck.DEPTH (4) arm() calls late, in steady state <= 3 steps), at once otherwise
         ops.defer_zero_check(ninf, _not_enough_time, blocking=grad is None)
         self.ctc_losses = losses[:B]
+        if len(pending) > 6:                                       # the smoothed training objective of _ctc_head_launch
+            eps, kl = pending[6]
+            return logits[:, :B], ((1.0 - eps) * losses + eps * kl)[:B].mean(), dict(dlogits=grad)
         return logits[:, :B], losses[:B].mean(), dict(dlogits=grad)
 
     def _ctc_head_backward(self, tape, enc, denc, accumulate=True):

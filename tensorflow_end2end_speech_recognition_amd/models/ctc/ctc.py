@@ -73,7 +73,10 @@ class CTC(ModelBase):
     (time subsampling inside the blstm / lstm encoders, models/encoders/core/subsample.py -- the logits then have
     T >> k frames and decoder() takes output_seq_len(inputs_seq_len); None or all false: the plain encoder);
     `encoder_residual` / `encoder_dense_residual` (skip connections between the layers of the blstm / lstm encoders,
-    models/encoders/core/residual.py; both false: the plain encoder).
+    models/encoders/core/residual.py; both false: the plain encoder); `label_smoothing_prob` (eps in [0, 1): the training
+    loss of an utterance becomes (1 - eps) * ctc + eps * sum_t KL(uniform || softmax(logits_t)) over all classes, blank
+    included, through ops.ctc_loss_ls -- a key of the reference's blstm_ctc_ls.yml that none of its code reads; dev losses
+    (is_training=False) and self.ctc_losses stay the plain CTC loss; 0: today's calls).
     """
     head_scope = 'output'      # variable scope of the output FC (ctc.py:216-224)
 
@@ -82,8 +85,11 @@ class CTC(ModelBase):
                  parameter_init=0.1, clip_grad_norm=None, clip_activation=None, num_proj=None,
                  weight_decay=0.0, bottleneck_dim=None, time_major=True,
                  dtype='f32', device='cuda:0', seed=0, subsample_list=None, subsample_type='drop',
-                 encoder_residual=False, encoder_dense_residual=False):
+                 encoder_residual=False, encoder_dense_residual=False, label_smoothing_prob=0.0):
         super(CTC, self).__init__()
+        if not 0.0 <= float(label_smoothing_prob) < 1.0:
+            raise ValueError('label_smoothing_prob must be in [0, 1), got %r' % (label_smoothing_prob,))
+        self.label_smoothing_prob = float(label_smoothing_prob)
         assert input_size % 3 == 0, 'input_size must be divisible by 3 (+ delta, acceleration coefficients).'
         assert splice % 2 == 1, 'splice must be the odd number'
         if clip_grad_norm is not None:
@@ -244,7 +250,8 @@ class CTC(ModelBase):
                 raise RuntimeError('CTC head: the encoder deferred its top dropout for a head that does not apply it')
             # x_op is the top layer's output BEFORE dropout: one launch forms the dropped operand, the logits and what
             # the first CTC kernel would leave in the workspace
-            ws = ops.ctc_workspace(T, Bp, head['max_len'], x_op.device)
+            ws = (ops.ctc_ls_workspace if self.label_smoothing_prob > 0.0 else ops.ctc_workspace)(
+                T, Bp, head['max_len'], x_op.device)
             x_op, logits, ninf = ops.ctc_head_fwd(x_op, enc._top_drop, self._head_imgs[0],
                                                   self.store[self.head_scope + '/biases'], Cc, head['flat'], head['off'],
                                                   enc.seq_len_padded, head['max_len'], ws)
@@ -331,14 +338,24 @@ class CTC(ModelBase):
         if softmax_temperature != 1:
             ctc_in = ops.scale_(logits.clone(), inv_temp)
         hs, img = self._head_state, None
-        if hs is not None:
+        eps = self.label_smoothing_prob if is_training else 0.0
+        kl = None
+        if eps > 0.0:
+            # the smoothed objective: the gradient kernel writes d((1 - eps) ctc + eps kl), ctc_losses stay the plain ones
+            fused = dict(ws=hs['ws'], ninf=hs['ninf'], lse_done=hs['lse_done'], want_image=True) if hs is not None else {}
+            ctc_losses, kl, grad, img, ninf = ops.ctc_loss_ls(ctc_in, flat_d, off_d, self.encoder.seq_len_padded, max_len,
+                                                              eps, grad_scale=inv_temp / B, **fused)
+        elif hs is not None:
             ctc_losses, grad, img, ninf = ops.ctc_loss_ex(ctc_in, flat_d, off_d, self.encoder.seq_len_padded, max_len,
                                                           grad_scale=inv_temp / B, ws=hs['ws'], ninf=hs['ninf'],
                                                           lse_done=hs['lse_done'])
         else:
             ctc_losses, grad, ninf = ops.ctc_loss(ctc_in, flat_d, off_d, self.encoder.seq_len_padded,
                                                   max_len, grad_scale=inv_temp / B, want_grad=is_training)
-        ctc_loss = ctc_losses[:B].mean()                                   # ctc.py:298
+        if kl is not None:
+            ctc_loss = ((1.0 - eps) * ctc_losses + eps * kl)[:B].mean()
+        else:
+            ctc_loss = ctc_losses[:B].mean()                               # ctc.py:298
         total_loss = ctc_loss
         if self.weight_decay > 0:
             l2 = torch.zeros((), dtype=torch.float32, device=dev)

@@ -97,12 +97,22 @@ class MultitaskCTC(CTC):
         fm, om, lm = self._upload_labels(labels_main, B, Bp)
         fs, os_, ls = self._upload_labels(labels_sub, B, Bp)
         # the task weights and the 1/B of the batch mean are folded into the CTC gradient (:258-276)
-        losses_m, grad_m, ninf_m = ops.ctc_loss(logits_main, fm, om, seq_p, lm,
-                                                grad_scale=self.main_task_weight / B, want_grad=is_training)
-        losses_s, grad_s, ninf_s = ops.ctc_loss(logits_sub, fs, os_, seq_p, ls,
-                                                grad_scale=self.sub_task_weight / B, want_grad=is_training)
-        self.ctc_loss_main = losses_m[:B].mean()
-        self.ctc_loss_sub = losses_s[:B].mean()
+        eps = self.label_smoothing_prob if is_training else 0.0
+        if eps > 0.0:
+            # label_smoothing_prob (extension keyword, CTC's): both heads, inside the task weights
+            losses_m, kl_m, grad_m, _, ninf_m = ops.ctc_loss_ls(logits_main, fm, om, seq_p, lm, eps,
+                                                                grad_scale=self.main_task_weight / B)
+            losses_s, kl_s, grad_s, _, ninf_s = ops.ctc_loss_ls(logits_sub, fs, os_, seq_p, ls, eps,
+                                                                grad_scale=self.sub_task_weight / B)
+            self.ctc_loss_main = ((1.0 - eps) * losses_m + eps * kl_m)[:B].mean()
+            self.ctc_loss_sub = ((1.0 - eps) * losses_s + eps * kl_s)[:B].mean()
+        else:
+            losses_m, grad_m, ninf_m = ops.ctc_loss(logits_main, fm, om, seq_p, lm,
+                                                    grad_scale=self.main_task_weight / B, want_grad=is_training)
+            losses_s, grad_s, ninf_s = ops.ctc_loss(logits_sub, fs, os_, seq_p, ls,
+                                                    grad_scale=self.sub_task_weight / B, want_grad=is_training)
+            self.ctc_loss_main = losses_m[:B].mean()
+            self.ctc_loss_sub = losses_s[:B].mean()
         total_loss = self.ctc_loss_main * self.main_task_weight + self.ctc_loss_sub * self.sub_task_weight
         if self.weight_decay > 0:
             l2 = torch.zeros((), dtype=torch.float32, device=dev)

@@ -1792,6 +1792,62 @@ def reset_ctc_head_counts(device=0):
     _reset_counts3('ctc_head_counts', device)
 
 
+def ctc_ls_workspace(T, B, max_label_len, device):
+    """The workspace of ctc_loss_ls (asr_ctc_ls_workspace_bytes): ctc_workspace's layout and behind it the KL row terms,
+    so ctc_head_fwd can fill it for ctc_loss_ls(lse_done=True)."""
+    nbytes = _lib.load().asr_ctc_ls_workspace_bytes(int(T), int(B), int(max_label_len))
+    return torch.empty((nbytes,), dtype=torch.uint8, device=device)
+
+
+def ctc_loss_ls(logits, labels_flat, label_offsets, seq_len, max_label_len, smoothing, grad_scale=1.0, ws=None, ninf=None,
+                lse_done=False, want_grad=True, want_image=False):
+    """EXTENSION: CTC loss with label smoothing towards the uniform distribution over all classes (asr_ctc_loss_ls).
+    Returns (loss [B] -- the UNSMOOTHED CTC loss, ctc_loss's bits --, kl [B] = sum_t KL(uniform || softmax(logits[t,b])),
+    grad [T,B,C] = grad_scale * d((1 - smoothing) loss + smoothing kl) / d logits or None, its bf16 image [T*B, Kp] or None,
+    num_infeasible).  0 < smoothing < 1; finite logits; ws: ctc_ls_workspace (needed with lse_done, after ctc_head_fwd)."""
+    eps = float(smoothing)
+    if not 0.0 < eps < 1.0:
+        raise ValueError('ctc_loss_ls: smoothing must be in (0, 1), got %r' % (smoothing,))
+    if want_image and not want_grad:
+        raise ValueError('ctc_loss_ls: the image is the image of the gradient (want_grad)')
+    h = _h(logits)
+    _chk(logits, torch.float32, 'logits')
+    _chk(labels_flat, torch.int32, 'labels_flat')
+    _chk(label_offsets, torch.int32, 'label_offsets')
+    _chk(seq_len, torch.int32, 'seq_len')
+    T, B, Cc = logits.shape
+    dev = logits.device
+    if ws is None:
+        if lse_done:
+            raise ValueError('ctc_loss_ls: lse_done needs the workspace of ctc_head_fwd (ctc_ls_workspace)')
+        ws = ctc_ls_workspace(T, B, max_label_len, dev)
+    if ninf is None:
+        ninf = torch.empty((1,), dtype=torch.int32, device=dev)
+    loss = torch.empty((B,), dtype=torch.float32, device=dev)
+    kl = torch.empty((B,), dtype=torch.float32, device=dev)
+    grad = torch.empty_like(logits) if want_grad else None
+    Kp = (Cc + 63) // 64 * 64
+    img = torch.empty((T * B, Kp), dtype=torch.bfloat16, device=dev) if want_image else None
+    h.check(h.lib.asr_ctc_loss_ls(h.h, _p(logits), T, B, Cc, _p(labels_flat), _p(label_offsets), _p(seq_len),
+                                  int(max_label_len), float(grad_scale), eps, _p(loss), _p(kl), _p(grad), _p(ninf),
+                                  _p(ws), ws.numel(), 1 if lse_done else 0, _p(img), Kp if want_image else 0, _s()),
+            'asr_ctc_loss_ls')
+    return loss, kl, grad, img, ninf
+
+
+_CTC_LS_KEYS = ('calls', 'lse_done', 'no_grad')
+
+
+def ctc_ls_counts(device=0):
+    """ctc_loss_ls calls on `device` since the last reset (asr_ctc_ls_counts): all, those that continued from
+    ctc_head_fwd's workspace, those without a gradient.  Host counters: no device work, no synchronisation."""
+    return _counts3('ctc_ls_counts', _CTC_LS_KEYS, device)
+
+
+def reset_ctc_ls_counts(device=0):
+    _reset_counts3('ctc_ls_counts', device)
+
+
 def ctc_greedy_decode(logits, seq_len, blank=None):
     h = _h(logits)
     _chk(logits, torch.float32, 'logits')
