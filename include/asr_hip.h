@@ -544,6 +544,12 @@ int asr_cluster_tile_groups(int G, int ndir, int tiles, int cu_budget, int* firs
  * measured). */
 int asr_recurrence_path_counts(asr_handle* h, unsigned long long* out6);
 int asr_reset_recurrence_path_counts(asr_handle* h);
+/* The form each asr_gru_fwd / asr_gru_bwd call on this handle ended in since the last reset (host integers like the ones
+ * above, one bumped per call where the form is chosen): out6 = {forward on clusters, forward persistent on one CU per
+ * (direction, tile), forward launched per step, and the same three for the backward}.  The counters above are left as
+ * they are: both single-CU forms count there as one single-CU call. */
+int asr_gru_kernel_counts(asr_handle* h, unsigned long long* out6);
+int asr_reset_gru_kernel_counts(asr_handle* h);
 /* Which kernels the attention decoder calls on this handle launched since the last reset (host integers bumped at
  * launch time like the recurrence counters above: no device work, no synchronisation, no effect on any launch).
  * out[i], i < min(n, ASR_ATT_PATH_N), in the order of the enum below; entries of `out` past ASR_ATT_PATH_N are zeroed.

@@ -29,6 +29,9 @@ struct asr_handle {
   // recurrence launches since the last asr_reset_recurrence_path_counts (plain host counters bumped at launch time):
   // {cluster launches, single-CU calls, calls split into more than one tile group} of the LSTM, then of the GRU
   unsigned long long rec_counts[6];
+  // asr_gru_fwd / asr_gru_bwd calls since the last asr_reset_gru_kernel_counts by the form they ended in:
+  // {fwd cluster, fwd persistent, fwd per step, bwd cluster, bwd persistent, bwd per step}
+  unsigned long long gru_counts[6];
   // attention-decoder launches since the last asr_reset_att_path_counts, indexed by the ASR_ATT_* enum of asr_hip.h
   unsigned long long att_counts[ASR_ATT_PATH_N];
   // beam search launches since the last asr_reset_att_beam_counts: {select, reorder, backtrace}

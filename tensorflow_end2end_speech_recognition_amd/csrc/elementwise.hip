@@ -17,6 +17,7 @@
 // still 5 (additive): asr_gemm_rows (the NT products on listed rows), asr_gemm_path_counts / asr_reset_gemm_path_counts.
 // still 5 (additive): asr_time_subsample_fwd / asr_time_subsample_bwd (subsample.hip).
 // still 5 (additive): asr_residual_fwd / asr_residual_bwd (residual.hip).
+// still 5 (additive): asr_gru_kernel_counts / asr_reset_gru_kernel_counts (the form a GRU recurrence call ended in).
 extern "C" int asr_abi_version(void) { return 5; }
 
 extern "C" int asr_create(asr_handle** out, int device) { return asr_create_ex(out, device, (size_t)192 << 20); }

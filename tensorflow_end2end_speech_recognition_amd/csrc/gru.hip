@@ -473,8 +473,9 @@ __global__ __launch_bounds__(GP_THREADS, 1) void gru_bwd_persistent_kernel(
 
 }  // namespace
 
-// The persistent kernels apply when the LDS images fit one CU (H <= 512 forward, H <= 480 backward) and the packed
-// weights fit the handle's scratch; ASR_GRU_PERSISTENT=0 keeps the launch-per-step form (A/B, and the tests run both).
+// The persistent kernels apply when the LDS images fit one CU's 160 KiB (forward 192 (H + 4) bytes: every H <= 512;
+// backward 64 (5 H + 16) bytes: H <= 496, so H = 512 runs its backward per step) and the packed weights fit the handle's
+// scratch; ASR_GRU_PERSISTENT=0 keeps the launch-per-step form (A/B, and the tests run both).
 static int g_gru_persistent = -1;
 extern "C" int asr_debug_set_gru_persistent(int on) { g_gru_persistent = on ? 1 : 0; return 0; }
 static bool gru_persistent_ok(asr_handle* h, int H, int ndir, size_t lds) {
@@ -508,11 +509,13 @@ extern "C" int asr_gru_fwd(asr_handle* h, int T, int B, int H, int ndir, const f
   // H = 128 / 256: clusters of H / 32 CUs with the recurrent blocks in registers (lstm_cluster.hip), final state in hs[0]
   if (gru_cluster_allowed() &&
       asr_cluster_gru_fwd_try(h, T, B, H, ndir, xg, xc, wgh, wch, seq_len, r, u, c, rh, hout, hs[0], st)) {
+    h->gru_counts[0] += 1;
     ASR_CHECK_LAUNCH(h, "asr_gru_fwd(cluster)");
     return ASR_OK;
   }
   h->rec_counts[4] += 1;   // single-CU path, persistent or launch-per-step (asr_recurrence_path_counts)
   if (gru_persistent_ok(h, H, ndir, (size_t)3 * 16 * (H + 4) * sizeof(float))) {
+    h->gru_counts[1] += 1;
     // frames [tmax, T) of the output are beyond every utterance: zero
     if (T > tmax && hipMemsetAsync(hout + (size_t)tmax * B * ndir * H, 0, (size_t)(T - tmax) * B * ndir * H * sizeof(float), st) != hipSuccess)
       ASR_FAIL(h, ASR_ERR_HIP, "asr_gru_fwd: memset");
@@ -528,6 +531,7 @@ extern "C" int asr_gru_fwd(asr_handle* h, int T, int B, int H, int ndir, const f
     ASR_CHECK_LAUNCH(h, "asr_gru_fwd");
     return ASR_OK;
   }
+  h->gru_counts[2] += 1;
   if (hipMemsetAsync(hs[0], 0, sn * sizeof(float), st) != hipSuccess) ASR_FAIL(h, ASR_ERR_HIP, "asr_gru_fwd: memset");
   // frames [tmax, T) of the output are beyond every utterance: zero
   if (T > tmax && hipMemsetAsync(hout + (size_t)tmax * B * ndir * H, 0, (size_t)(T - tmax) * B * ndir * H * sizeof(float), st) != hipSuccess)
@@ -568,6 +572,7 @@ extern "C" int asr_gru_bwd(asr_handle* h, int T, int B, int H, int ndir, const f
   // H = 128 / 256: clusters of H / 32 CUs (lstm_cluster.hip)
   if (gru_cluster_allowed() &&
       asr_cluster_gru_bwd_try(h, T, B, H, ndir, dout, d_h_final, hout, r, u, c, wghT, wchT, seq_len, dgate, dcand, st)) {
+    h->gru_counts[3] += 1;
     ASR_CHECK_LAUNCH(h, "asr_gru_bwd(cluster)");
     return ASR_OK;
   }
@@ -580,6 +585,7 @@ extern "C" int asr_gru_bwd(asr_handle* h, int T, int B, int H, int ndir, const f
   }
   const size_t lds_p = (size_t)16 * (3 * (H + 4) + 2 * H + 4) * sizeof(float);
   if (gru_persistent_ok(h, H, ndir, lds_p)) {
+    h->gru_counts[4] += 1;
     float* wgT_pk = (float*)h->scratch;                    // [ndir][H/16][2H/16][64][4]  (K = 2H, N = H)
     float* wcT_pk = wgT_pk + (size_t)ndir * 2 * H * H;     // [ndir][H/16][H/16][64][4]
     hipLaunchKernelGGL(gru_pack_kernel, dim3(256), dim3(256), 0, st, wghT, 2 * H, H, H, wgT_pk, ndir, (size_t)2 * H * H,
@@ -591,6 +597,7 @@ extern "C" int asr_gru_bwd(asr_handle* h, int T, int B, int H, int ndir, const f
     ASR_CHECK_LAUNCH(h, "asr_gru_bwd");
     return ASR_OK;
   }
+  h->gru_counts[5] += 1;
   const int eb = (int)((sn + 255) / 256 < 1024 ? (sn + 255) / 256 : 1024);
   const size_t lds1 = (size_t)16 * (H + 1) * sizeof(float);
   for (int step = tmax - 1; step >= 0; --step) {
@@ -602,5 +609,17 @@ extern "C" int asr_gru_bwd(asr_handle* h, int T, int B, int H, int ndir, const f
                        wghT, dh_acc, seq_len, dh_rec);
   }
   ASR_CHECK_LAUNCH(h, "asr_gru_bwd");
+  return ASR_OK;
+}
+
+// the form each asr_gru_fwd / asr_gru_bwd call on this handle ended in (host integers bumped where the form is chosen)
+extern "C" int asr_gru_kernel_counts(asr_handle* h, unsigned long long* out6) {
+  if (!h || !out6) return ASR_ERR_INVALID_ARG;
+  for (int i = 0; i < 6; ++i) out6[i] = h->gru_counts[i];
+  return ASR_OK;
+}
+extern "C" int asr_reset_gru_kernel_counts(asr_handle* h) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  for (int i = 0; i < 6; ++i) h->gru_counts[i] = 0;
   return ASR_OK;
 }

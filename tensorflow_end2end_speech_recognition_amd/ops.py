@@ -1519,6 +1519,26 @@ def reset_recurrence_path_counts(device=0):
         h.check(h.lib.asr_reset_recurrence_path_counts(h.h), 'asr_reset_recurrence_path_counts')
 
 
+_GRU_KERNEL_KEYS = ('fwd_cluster', 'fwd_persistent', 'fwd_per_step', 'bwd_cluster', 'bwd_persistent', 'bwd_per_step')
+
+
+def gru_kernel_counts(device=0):
+    """The form each gru_fwd / gru_bwd call on `device` ended in since the last reset_gru_kernel_counts, summed over its
+    handles (asr_gru_kernel_counts): clusters, the persistent single-CU kernel, or the launch-per-step kernels.  Host
+    counters: no device work, no synchronisation."""
+    tot = [0] * 6
+    for h in _device_handles(device):
+        out = (C.c_ulonglong * 6)()
+        h.check(h.lib.asr_gru_kernel_counts(h.h, out), 'asr_gru_kernel_counts')
+        tot = [a + int(b) for a, b in zip(tot, out)]
+    return dict(zip(_GRU_KERNEL_KEYS, tot))
+
+
+def reset_gru_kernel_counts(device=0):
+    for h in _device_handles(device):
+        h.check(h.lib.asr_reset_gru_kernel_counts(h.h), 'asr_reset_gru_kernel_counts')
+
+
 # the ASR_ATT_* enum of include/asr_hip.h, in its order
 _ATT_PATH_KEYS = ('fwd_step_fused', 'fwd_step_4launch', 'fwd_cell_bf16', 'fwd_cell_f32img', 'fwd_cell_gemm',
                   'bwd_step_fused_q', 'bwd_step_unfused', 'bwd_cell_bf16', 'bwd_cell_gemm', 'bwd_softmax_folded',
