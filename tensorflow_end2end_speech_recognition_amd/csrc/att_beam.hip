@@ -3,7 +3,7 @@
 // scores and / or a language model's (the att_select_candidates_kernel / att_select_rank_kernel pair: joint CTC /
 // attention search, Watanabe et al. 2017, Hori et al. 2017, and shallow LM fusion; float64 statements in
 // beam_search/ctc_prefix_score.py and beam_search/lm_fusion.py) --, the re-ordering of what the next step reads, and the
-// back-trace.  The loops that issue them are asr_att_decoder_beam{,_joint,_lm} (attention.hip, next to the greedy loop
+// back-trace.  The loops that issue them are asr_att_decoder_beam{,_joint,_lm} (dec_loop.hip, next to the greedy loop
 // whose per-step code they share); the prefix scorer is ctc_prefix.hip, the language model lm_fusion.hip.
 #include "common.h"
 #include <math.h>

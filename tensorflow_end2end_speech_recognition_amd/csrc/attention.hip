@@ -11,8 +11,10 @@
 // (B*T*A*4 B) and the context pass reads the encoder outputs once (B*T*E*4 B).  The GEMM-shaped
 // parts (keys, query, cell input projection, attentional vector, output layer and all their
 // gradients) run on asr_gemm, batched over all decoder steps wherever the recurrence allows.
+// Kernels, launchers and single-op entry points; the loops over all decoder steps are dec_loop.hip's (att_launch.h).
 #include "common.h"
-#include "lstm_cell_bwd.h"
+#include "att_launch.h"
+#include "argmax_first.h"
 #include <math.h>
 
 namespace {
@@ -192,15 +194,6 @@ __global__ void att_energy_bwd_reduce_kernel(const float* __restrict__ part, int
   else dv_rows[(size_t)b * A + j - A] = s;
 }
 
-struct SoftmaxBwdFold {        // see att_energy_bwd_vec_kernel
-  const float* da;             // [B,T] d loss / d alpha  (NULL: not folded)
-  const float* alpha;          // [B,T]
-  const float* dotp;           // [ndot,B] partial sums of alpha . dalpha
-  const float* norm;           // [B] sigmoid-smoothing normaliser or NULL
-  int ndot;
-  float sharp;
-};
-
 // The same two kernels for A % 4 == 0, A <= 512 (every configuration of the reference): a frame is handled by LPF lanes
 // holding float4 slices of qz / v in registers (LPF = 16, 32 or 64 -> 4, 2 or 1 frames per wave and trip), tanh from
 // the hardware exp2 / rcp, the per-frame sum by DPP adds, and -- backward -- the sums over frames in registers instead
@@ -345,12 +338,6 @@ __global__ __launch_bounds__(256) void att_energy_bwd_vec_kernel(const float* __
     const int w = a >= A, c = a - w * A;
     o[a] = (red[0][w][c] + red[1][w][c]) + (red[2][w][c] + red[3][w][c]);
   }
-}
-// 0: not applicable, else LPF * 4 + NV  (A % 4 == 0, A <= 512, 16-byte aligned operands)
-static inline int energy_vec_shape(int A, const void* keys, const void* qz, const void* v, const void* dkeys) {
-  if (A % 4 != 0 || A > 512 || ((uintptr_t)keys | (uintptr_t)qz | (uintptr_t)v | (uintptr_t)dkeys) % 16 != 0) return 0;
-  const int nvec = A / 4;
-  return nvec <= 16 ? 16 * 4 + 1 : nvec <= 32 ? 32 * 4 + 1 : nvec <= 64 ? 64 * 4 + 1 : 64 * 4 + 2;
 }
 
 // asr_att_path_counts: the counter of a lane shape behind `first` (..._L16, _L32, _L64[, _L64X2], _GENERAL); `general`
@@ -1572,20 +1559,10 @@ __global__ __launch_bounds__(256) void argmax_rows_kernel(const float* __restric
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  const float* p = x + (size_t)row * Cc;
-  float best = -INFINITY;
-  int bi = 0x7fffffff;
-  for (int k = lane; k < Cc; k += 64) {
-    const float v = p[k];
-    if (v > best || (v == best && k < bi)) { best = v; bi = k; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-  }
-  if (lane == 0) out[row] = bi == 0x7fffffff ? 0 : bi;
+  float best;
+  int bi;
+  argmax_first_wave(x + (size_t)row * Cc, Cc, lane, 64, best, bi);   // one wave per row
+  if (lane == 0) out[row] = argmax_first_id(bi);
 }
 
 inline int gridn(size_t n) {
@@ -1607,9 +1584,8 @@ namespace {
 // being the SUM of the chunk partials read straight from the energy kernel's scratch; the tiles meet in LDS in a fixed
 // order.  Column-tile 0 also writes dqz / dv_rows (the weight gradients after the loop need them).
 // (CellBwdArgs: lstm_cell_bwd.h)
-// NTL MFMA column tiles (16 NTL units) per workgroup.  Measured on the cfg D shard (A = 128, U = 512, 25 chunks): NTL = 1
+// DQ_NTL (att_launch.h) MFMA column tiles (16 NTL units) per workgroup.  Measured on the cfg D shard (A = 128, U = 512, 25 chunks): NTL = 1
 // (34 workgroups x 2 row groups) 54.3 ms for the reverse pass, NTL = 4 (10 x 2) 55.4, the three separate launches 55.0.
-constexpr int DQ_NTL = 1, DQ_CT = 16 * DQ_NTL;
 __global__ __launch_bounds__(512) void att_dq_cell_bwd_kernel(const float* __restrict__ part, int nch, int B, int A, int U,
                                                               const float* __restrict__ Wq, int ldw,
                                                               const float* __restrict__ dcell_in,
@@ -1764,6 +1740,14 @@ __global__ __launch_bounds__(512) void att_dq_cell_bwd_kernel(const float* __res
 }
 }  // namespace
 
+int att_dq_cell_bwd_launch(asr_handle* h, const float* part, int nch, int B, int A, int U, const float* Wq, int ldw,
+                           const float* dcell, float* dqz, float* dv, const CellBwdArgs& c, asr_stream s) {
+  hipLaunchKernelGGL(att_dq_cell_bwd_kernel, dim3(U / DQ_CT + 2, (B + 15) / 16), dim3(512), 0, (hipStream_t)s, part, nch, B,
+                     A, U, Wq, ldw, dcell, dqz, dv, c);
+  ASR_CHECK_LAUNCH(h, "asr_att_decoder_bwd");
+  return ASR_OK;
+}
+
 extern "C" int asr_lstm_cell_fwd_ex(asr_handle* h, const float* pre, const float* c_prev, const float* h_prev,
                                     const float* peep, const float* live, int B, int U, float forget_bias,
                                     float cell_clip, float* gates, float* c_raw, float* c_out, float* h_out,
@@ -1819,7 +1803,7 @@ extern "C" int asr_lstm_cell_bwd_ex(asr_handle* h, const float* dh_use, const fl
                          dh_prev_carry, dpeep_rows, nullptr, 0, nullptr, cell_clip, s);
 }
 
-static int energy_fwd_launch(asr_handle* h, const float* keys, const float* qz, const float* v, int T, int B, int A,
+int energy_fwd_launch(asr_handle* h, const float* keys, const float* qz, const float* v, int T, int B, int A,
                              int mode, float* energy, const int32_t* seq_len, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
   ASR_NEED(qz && energy && T > 0 && B > 0 && A > 0 && (mode == 0 ? v != nullptr : keys != nullptr),
@@ -1847,16 +1831,10 @@ extern "C" int asr_att_energy_fwd(asr_handle* h, const float* keys, const float*
   return energy_fwd_launch(h, keys, qz, v, T, B, A, mode, energy, nullptr, s);
 }
 
-static inline float* att_scratch(asr_handle* h, size_t bytes) {
-  return (bytes <= h->scratch_bytes - ASR_XCH_BYTES) ? (float*)h->scratch : nullptr;
-}
-
-static int energy_bwd_launch(asr_handle* h, const float* denergy, const float* keys, const float* qz, const float* v,
+int energy_bwd_launch(asr_handle* h, const float* denergy, const float* keys, const float* qz, const float* v,
                              int T, int B, int A, int mode, float* dkeys, float* dqz, float* dv_rows,
-                             const int32_t* seq_len, const SoftmaxBwdFold* fold, asr_stream s,
-                             const float** part_out = nullptr, int* nch_out = nullptr) {
-  // part_out / nch_out: the caller sums the chunk partials itself (att_dq_cell_bwd_kernel does it on its operand
-  // load) -- no reduction launch here, dqz / dv_rows are not written
+                             const int32_t* seq_len, const SoftmaxBwdFold* fold, asr_stream s, const float** part_out,
+                             int* nch_out) {
   if (!h) return ASR_ERR_INVALID_ARG;
   const int shape = energy_vec_shape(A, keys, qz, v, dkeys);
   ASR_NEED((denergy || (fold && fold->da && shape)) && qz && dqz && T > 0 && B > 0 && A > 0,
@@ -1903,7 +1881,7 @@ extern "C" int asr_att_energy_bwd(asr_handle* h, const float* denergy, const flo
   return energy_bwd_launch(h, denergy, keys, qz, v, T, B, A, mode, dkeys, dqz, dv_rows, nullptr, nullptr, s);
 }
 
-static int loc_energy_fwd_launch(asr_handle* h, const float* alpha_prev, const float* filt, const float* wfil,
+int loc_energy_fwd_launch(asr_handle* h, const float* alpha_prev, const float* filt, const float* wfil,
                                  const float* keys, const float* qz, const float* v, int T, int B, int A, int taps,
                                  float* energy, const int32_t* seq_len, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
@@ -1935,7 +1913,7 @@ extern "C" int asr_att_loc_energy_fwd(asr_handle* h, const float* alpha_prev, co
   return loc_energy_fwd_launch(h, alpha_prev, filt, wfil, keys, qz, v, T, B, A, taps, energy, nullptr, s);
 }
 
-static int loc_energy_bwd_launch(asr_handle* h, const float* denergy, const float* alpha_prev, const float* filt,
+int loc_energy_bwd_launch(asr_handle* h, const float* denergy, const float* alpha_prev, const float* filt,
                                  const float* wfil, const float* keys, const float* qz, const float* v, int T, int B,
                                  int A, int taps, float* dkeys, float* dqz, float* dv_rows, float* dwfil_rows,
                                  float* dfilt_rows, float* dalpha_prev, int accumulate, const int32_t* seq_len,
@@ -2059,11 +2037,7 @@ bool dalpha_vec_launch(const float* da_, const float* db_, int ldb, float* dout,
 }
 }  // namespace
 
-// dctx = dctx_a (+ dctx_b with row stride ldb, may be NULL); the sum goes to dctx_out when that is given.
-// fold (may be NULL): the caller's energy backward can take the softmax backward in (vectorised kernels on both sides,
-// no carried-alpha gradient); when that applies, *fold is filled, denergy is NOT written and no softmax backward
-// kernel is launched -- otherwise fold->da is left NULL and denergy holds the result as usual.
-static int softmax_ctx_bwd_launch(asr_handle* h, const float* dctx_a, const float* dctx_b, int ldb, float* dctx_out,
+int softmax_ctx_bwd_launch(asr_handle* h, const float* dctx_a, const float* dctx_b, int ldb, float* dctx_out,
                                   const float* alpha, const int32_t* seq_len, float sharpening, const void* enc,
                                   int enc_dtype, int T, int B, int E, float* denergy, float* denc,
                                   const float* sigmoid_norm, const float* dalpha_extra, SoftmaxBwdFold* fold,
@@ -2193,7 +2167,6 @@ extern "C" int asr_argmax_rows(asr_handle* h, const float* x, int rows, int C, i
   return ASR_OK;
 }
 
-// ---------------------------------------------------------------- the decoder loop, native
 extern "C" int asr_add_cols(asr_handle* h, const float* x, int ldx, const float* y, int ldy, float* out, int ldo, int B,
                             int W, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
@@ -2204,42 +2177,8 @@ extern "C" int asr_add_cols(asr_handle* h, const float* x, int ldx, const float*
   return ASR_OK;
 }
 
-// g != nullptr (the *_gru entry points): the cell is the GRU of gru_decoder.hip -- the LSTM cell's weights, its raw cell
-// state, c and dc0 are not asked for, the GRU block is.  g == nullptr is every call this file has always made.
-// sk != nullptr (the *_stack entry points): upper LSTM layers above the cell (dec_stack.hip), checked there.
-static int dec_check(asr_handle* h, const asr_att_decoder* a, bool bwd, const asr_att_gru* g = nullptr,
-                     const asr_att_stack* sk = nullptr) {
-  if (sk && a) {
-    if (g) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder: a stack runs LSTM cells only");
-    ASR_TRY(asr_stack_dec_check(h, a, sk, bwd));
-    return dec_check(h, a, bwd);
-  }
-  if (g && a) {
-    asr_att_decoder d = *a;                                // the LSTM-only fields pass the checks below
-    d.W_cell = d.b_cell = g->W_g;
-    d.craw_all = d.c_all = d.gates_all;
-    d.dc0 = d.dh0;
-    d.peep = nullptr;
-    ASR_TRY(asr_gru_dec_check(h, a, g));
-    return dec_check(h, &d, bwd);
-  }
-  if (!a || a->To < 1 || a->B < 1 || a->T < 1 || a->U < 1 || a->Em < 0 || a->E2 < 1 || a->A < 1 || !a->W_cell ||
-      !a->b_cell || !a->enc || !a->seq_len || !a->live || !a->dec_in || !a->av_in || !a->alpha_all || !a->gates_all ||
-      !a->craw_all || !a->c_all || !a->h_all || !a->qz_all || !a->work || (a->att_mode != 0 && a->att_mode != 1) ||
-      (a->has_query_fc && !a->W_q) || (!a->has_query_fc && a->A != a->U) || (a->att_mode == 0 && !a->v) ||
-      (a->att_mode == 1 && !a->keys) || (a->carry_alpha && (!a->filt || !a->wfil || !a->alpha_zero || a->taps < 1)))
-    ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder: bad arguments");
-  if (bwd && (!a->dav_cell || !a->dav_ctx || !a->dctx_all || !a->dpre_all || !a->dqz_all || !a->d_in_all || !a->dc0 ||
-              !a->dh0 || (a->att_mode == 0 && !a->dv_all) || (a->peep && !a->dpeep_all) ||
-              (a->carry_alpha && (!a->dwfil_rows || !a->dfilt_rows))))
-    ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_bwd: bad arguments");
-  return ASR_OK;
-}
-
-// energies + softmax + context of one decoder step as two launches (att_fused_fwd_kernel + combine); false = the shape is
-// not covered (the caller takes the four-launch path).  ASR_ATT_FUSED=0 switches it off (A/B).
-static bool att_fused_step(asr_handle* h, const asr_att_decoder* a, const float* qz, float* alpha, float* ctx, float* ctx2,
-                           int ld2, float* ctx3, int ld3, asr_stream s) {
+bool att_fused_step(asr_handle* h, const asr_att_decoder* a, const float* qz, float* alpha, float* ctx, float* ctx2,
+                    int ld2, float* ctx3, int ld3, asr_stream s) {
   static const bool on = [] { const char* e = getenv("ASR_ATT_FUSED"); return !(e && e[0] == '0'); }();
   const int B = a->B, T = a->T, E = a->E2, A = a->A;
   if (!on || a->carry_alpha || a->snorm_all || E % 256 != 0 || T > 64 * ATT_CH || ((uintptr_t)a->enc) % 16 != 0) return false;
@@ -2275,631 +2214,6 @@ static bool att_fused_step(asr_handle* h, const asr_att_decoder* a, const float*
                      ctx, ctx2, ld2, ctx3, ld3, alpha);
   return true;
 }
-
-// The fused cell launch of a step (asr_lstm_cell_gemm_fwd) needs the caller's work space for the interleaved weight image
-static inline bool dec_cell_gemm(const asr_att_decoder* a) {
-  const int Din = a->Em + a->E2 + a->U;
-  return a->W_cell_il && asr_lstm_cell_gemm_ok(a->B, Din, a->U, Din) && ((uintptr_t)a->dec_in) % 16 == 0 &&
-         ((uintptr_t)a->W_cell_il) % 16 == 0;
-}
-// ... or for the bf16 weight images (both loops)
-static inline bool dec_cell_gemm_h(const asr_att_decoder* a) {
-  const int Din = a->Em + a->E2 + a->U;
-  return a->W_cell_h && asr_lstm_cell_gemm_ok(a->B, Din, a->U, Din) && a->U % 16 == 0 && ((uintptr_t)a->dec_in) % 16 == 0 &&
-         ((uintptr_t)a->W_cell_h) % 16 == 0;
-}
-static int dec_cell_image(asr_handle* h, const asr_att_decoder* a, asr_stream s, const asr_att_gru* g = nullptr,
-                          const asr_att_stack* sk = nullptr) {
-  if (sk) ASR_TRY(asr_stack_dec_image(h, a, sk, s));       // (the upper layers' images; layer 0's below, as ever)
-  if (g) return asr_gru_dec_image(h, a, g, s);
-  if (dec_cell_gemm_h(a)) return asr_lstm_cell_gemm_prep_h(h, a->W_cell, a->b_cell, a->Em + a->E2 + a->U, a->U, a->W_cell_h, s);
-  if (!dec_cell_gemm(a)) return ASR_OK;
-  return asr_lstm_cell_gemm_prep(h, a->W_cell, a->b_cell, a->Em + a->E2 + a->U, a->U, a->W_cell_il, s);
-}
-
-// One forward step of the decoder loop: cell-input GEMM -> cell -> query FC -> energies -> softmax + context.  k indexes
-// the step arrays that carry the recurrence (dec_in, av_in, c / h, alpha, live); ks the saved activations only the
-// backward reads (gates, raw cell, query: the inference loop reuses row 0).
-// g != nullptr: the cell launches are the GRU's (asr_gru_dec_fwd_step, same scatter targets); everything behind them is shared.
-// sk != nullptr: layer 0's masked output goes to the input row of layer 1 instead of av / the query, and the upper layers'
-// cell launches follow it (asr_stack_dec_fwd_step: the top layer writes av[:, :U] and the query).
-static int dec_fwd_step(asr_handle* h, const asr_att_decoder* a, int k, int ks, bool more, asr_stream s,
-                        const asr_att_gru* g = nullptr, const asr_att_stack* sk = nullptr) {
-  const int B = a->B, U = a->U, T = a->T, E2 = a->E2, Em = a->Em, A = a->A;
-  const int Din = Em + E2 + U, Dav = U + E2;
-  float* pre = a->work;                                    // [B,4U]
-  float* hraw = pre + (size_t)B * 4 * U;                   // [B,U]
-  float* energy = hraw + (size_t)B * U;                    // [B,T]
-  float* ctx = energy + (size_t)B * T;                     // [B,E2]
-  float* din = a->dec_in + (size_t)k * B * Din;
-  float* dnext = more ? din + (size_t)B * Din : nullptr;
-  float* av = a->av_in + (size_t)k * B * Dav;
-  float* qz = a->qz_all + (size_t)ks * B * A;
-  // the cell output (times its dropout mask) lands in av[:, :U]; without a query FC it IS the query
-  float* q0 = (a->has_query_fc || sk) ? nullptr : qz;
-  float* out0 = sk ? sk->up[0].in + (size_t)k * B * 2 * U : av;
-  const int ld0 = sk ? 2 * U : Dav;
-  if (g) {
-    ASR_TRY(asr_gru_dec_fwd_step(h, a, g, k, ks, dnext, qz, s));
-  } else if (dec_cell_gemm_h(a)) {  // product + cell as one launch on the bf16 fragment image (dec_cell_image)
-    h->att_counts[ASR_ATT_FWD_CELL_BF16] += 1;
-    ASR_TRY(asr_lstm_cell_gemm_fwd_h(h, din, Din, Din, a->W_cell_h, a->c_all + (size_t)k * B * U,
-                                     a->h_all + (size_t)k * B * U, a->peep, a->live + (size_t)k * B, B, U, a->forget_bias,
-                                     a->cell_clip, a->gates_all + (size_t)ks * B * 4 * U, a->craw_all + (size_t)ks * B * U,
-                                     a->c_all + (size_t)(k + 1) * B * U, a->h_all + (size_t)(k + 1) * B * U, hraw,
-                                     a->dmask ? a->dmask + (size_t)k * B * U : nullptr, q0,
-                                     dnext ? dnext + Em + E2 : nullptr, Din, out0, ld0, s));
-  } else if (dec_cell_gemm(a)) {    // ... on the fp32 interleaved weight image
-    h->att_counts[ASR_ATT_FWD_CELL_F32IMG] += 1;
-    ASR_TRY(asr_lstm_cell_gemm_fwd(h, din, Din, Din, a->W_cell_il, a->b_cell ? 1 : 0, a->c_all + (size_t)k * B * U,
-                                   a->h_all + (size_t)k * B * U, a->peep, a->live + (size_t)k * B, B, U, a->forget_bias,
-                                   a->cell_clip, a->gates_all + (size_t)ks * B * 4 * U, a->craw_all + (size_t)ks * B * U,
-                                   a->c_all + (size_t)(k + 1) * B * U, a->h_all + (size_t)(k + 1) * B * U, hraw,
-                                   a->dmask ? a->dmask + (size_t)k * B * U : nullptr, q0,
-                                   dnext ? dnext + Em + E2 : nullptr, Din, out0, ld0, s));
-  } else {
-    h->att_counts[ASR_ATT_FWD_CELL_GEMM] += 1;
-    ASR_TRY(asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, B, 4 * U, Din, din, Din, a->W_cell, 4 * U, pre, 4 * U, a->b_cell, 0, 0, s));
-    ASR_TRY(asr_lstm_cell_fwd_ex(h, pre, a->c_all + (size_t)k * B * U, a->h_all + (size_t)k * B * U, a->peep,
-                                 a->live + (size_t)k * B, B, U, a->forget_bias, a->cell_clip,
-                                 a->gates_all + (size_t)ks * B * 4 * U, a->craw_all + (size_t)ks * B * U,
-                                 a->c_all + (size_t)(k + 1) * B * U, a->h_all + (size_t)(k + 1) * B * U, hraw,
-                                 a->dmask ? a->dmask + (size_t)k * B * U : nullptr, q0,
-                                 dnext ? dnext + Em + E2 : nullptr, Din, out0, ld0, s));
-  }
-  if (sk) ASR_TRY(asr_stack_dec_fwd_step(h, a, sk, k, ks, more, a->has_query_fc ? nullptr : qz, s));
-  if (a->has_query_fc)
-    ASR_TRY(asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, B, A, U, av, Dav, a->W_q, a->ld_wq, qz, A, a->b_q, 0, 0, s));
-  if (att_fused_step(h, a, qz, a->alpha_all + (size_t)k * B * T, ctx, av + U, Dav, dnext ? dnext + Em : nullptr, Din, s)) {
-    h->att_counts[ASR_ATT_FWD_STEP_FUSED] += 1;
-    ASR_CHECK_LAUNCH(h, "asr_att_decoder_fwd(fused step)");
-    return ASR_OK;
-  }
-  h->att_counts[ASR_ATT_FWD_STEP_4LAUNCH] += 1;
-  if (a->carry_alpha)
-    ASR_TRY(loc_energy_fwd_launch(h, k > 0 ? a->alpha_all + (size_t)(k - 1) * B * T : a->alpha_zero, a->filt, a->wfil,
-                                  a->keys, qz, a->v, T, B, A, a->taps, energy, a->seq_len, s));
-  else
-    ASR_TRY(energy_fwd_launch(h, a->keys, qz, a->v, T, B, A, a->att_mode, energy, a->seq_len, s));
-  ASR_TRY(asr_att_softmax_ctx_fwd_ex(h, energy, a->seq_len, a->sharpening, a->enc, a->enc_dtype, T, B, E2,
-                                     a->alpha_all + (size_t)k * B * T, ctx,
-                                     a->snorm_all ? a->snorm_all + (size_t)k * B : nullptr, av + U, Dav,
-                                     dnext ? dnext + Em : nullptr, Din, s));
-  return ASR_OK;
-}
-
-static int dec_fwd_loop(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, asr_stream s,
-                        const asr_att_stack* sk = nullptr) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  ASR_TRY(dec_check(h, a, false, g, sk));
-  const int B = a->B, U = a->U, T = a->T, E2 = a->E2, Em = a->Em, A = a->A;
-  const int Din = Em + E2 + U, Dav = U + E2;
-  ASR_TRY(dec_cell_image(h, a, s, g, sk));
-  for (int k = 0; k < a->To; ++k) ASR_TRY(dec_fwd_step(h, a, k, k, k + 1 < a->To, s, g, sk));
-  (void)B; (void)U; (void)T; (void)E2; (void)Em; (void)A; (void)Din; (void)Dav;
-  return ASR_OK;
-}
-extern "C" int asr_att_decoder_fwd(asr_handle* h, const asr_att_decoder* a, asr_stream s) {
-  return dec_fwd_loop(h, a, nullptr, s);
-}
-extern "C" int asr_att_decoder_fwd_gru(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, asr_stream s) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  if (!g) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_fwd_gru: bad arguments");
-  return dec_fwd_loop(h, a, g, s);
-}
-extern "C" int asr_att_decoder_fwd_stack(asr_handle* h, const asr_att_decoder* a, const asr_att_stack* sk, asr_stream s) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  if (!sk) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_fwd_stack: bad arguments");
-  return dec_fwd_loop(h, a, nullptr, s, sk);
-}
-
-// ---------------------------------------------------------------- greedy inference loop, native
-namespace {
-// One workgroup per batch row, behind the output layer of decoder step k: id = argmax(logits) (first maximum wins, as
-// asr_argmax_rows), emitted id = id for a row that was live at the start of the step and 0 otherwise (impute_finished),
-// live[k+1] = live[k] && id != eos, live_count[k+1] += live[k+1]; the NEXT step's input row gets the embedding of id
-// (whatever the row's state: GreedyEmbeddingHelper.next_inputs does not look at `finished`) and its context columns
-// are zeroed for rows that had finished before this step (dynamic_decode zeroes next_inputs' attention part with the
-// imputed outputs, dynamic_decoder.py:172-190).
-__global__ __launch_bounds__(256) void att_infer_select_kernel(const float* __restrict__ logits, int C2, int eos,
-                                                               const float* __restrict__ live_k, float* __restrict__ live_n,
-                                                               int32_t* __restrict__ count_n, int32_t* __restrict__ ids,
-                                                               const float* __restrict__ emb, int Em, float* __restrict__ dnext,
-                                                               int Din, int E2) {
-  __shared__ float sv[4];
-  __shared__ int si[4];
-  const int b = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const float* p = logits + (size_t)b * C2;
-  float best = -INFINITY;
-  int bi = 0x7fffffff;
-  for (int k = threadIdx.x; k < C2; k += 256) {
-    const float v = p[k];
-    if (v > best || (v == best && k < bi)) { best = v; bi = k; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-  }
-  if (lane == 0) { sv[w] = best; si[w] = bi; }
-  __syncthreads();
-  best = sv[0]; bi = si[0];
-#pragma unroll
-  for (int i = 1; i < 4; ++i)
-    if (sv[i] > best || (sv[i] == best && si[i] < bi)) { best = sv[i]; bi = si[i]; }
-  const int id = bi == 0x7fffffff ? 0 : bi;
-  const float lv = live_k[b];
-  if (threadIdx.x == 0) {
-    ids[b] = lv != 0.f ? id : 0;
-    const float ln = (lv != 0.f && id != eos) ? 1.f : 0.f;
-    live_n[b] = ln;
-    if (ln != 0.f) atomicAdd(count_n, 1);
-  }
-  if (dnext) {
-    float* d = dnext + (size_t)b * Din;
-    const float* e = emb + (size_t)id * Em;
-    for (int j = threadIdx.x; j < Em; j += 256) d[j] = e[j];
-    if (lv == 0.f)
-      for (int j = threadIdx.x; j < E2; j += 256) d[Em + j] = 0.f;
-  }
-}
-}  // namespace
-
-static int dec_infer_loop(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, const asr_att_infer* f,
-                          int* steps_issued, asr_stream s, const asr_att_stack* sk = nullptr) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  ASR_TRY(dec_check(h, a, false, g, sk));
-  if (!f || !f->W_av || !f->W_out || !f->embedding || !f->live || !f->av_all || !f->logits_all || !f->ids_all ||
-      !f->live_count || f->C2 < 1 || f->eos < 0 || f->live != a->live || a->dmask)
-    ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_infer: bad arguments");
-  const int B = a->B, U = a->U, E2 = a->E2, Em = a->Em, To = a->To, C2 = f->C2;
-  const int Din = Em + E2 + U, Dav = U + E2;
-  hipStream_t st = (hipStream_t)s;
-  if (hipMemsetAsync(f->live_count + 1, 0, (size_t)To * sizeof(int32_t), st) != hipSuccess)
-    ASR_FAIL(h, ASR_ERR_HIP, "asr_att_decoder_infer: memset");
-  // early exit without draining the pipeline: every `check_every` steps the count of live rows at that step is copied to
-  // the caller's pinned words behind the step's kernels.  A check point looks at the newest copy that has ALREADY landed
-  // and, so that the host cannot run arbitrarily far past the end of the decode (it enqueues a step in a fraction of the
-  // time the device takes to run one), waits for the copy of two check points ago: the issue loop stays 2 .. 3 intervals
-  // ahead of the device, never idle, and at most that many surplus steps are enqueued.  The result does not depend on how
-  // many were: a step with no live row changes nothing but its own (imputed: zero) outputs, and the caller trims at the
-  // first such step.
-  constexpr int NEV = 3;
-  hipEvent_t ev[NEV] = {nullptr, nullptr, nullptr};
-  const int every = (f->host_live_count && f->check_every > 0) ? f->check_every : 0;
-  if (every) {
-    for (int i = 0; i < NEV; ++i)
-      if (hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) != hipSuccess) {
-        for (int j = 0; j < i; ++j) (void)hipEventDestroy(ev[j]);          // the ones already made
-        ASR_FAIL(h, ASR_ERR_HIP, "asr_att_decoder_infer: event");
-      }
-  }
-  int rc = dec_cell_image(h, a, s, g, sk), k = 0;
-  for (; rc == ASR_OK && k < To; ++k) {
-    if (every && k % every == 0 && k > 0) {
-      const int c = k / every;                             // this check point; c - 1 was recorded one interval ago
-      bool done = false;
-      if (c >= 3) {
-        (void)hipEventSynchronize(ev[(c - 2) % NEV]);
-        done = f->host_live_count[(c - 2) * every] == 0;
-      }
-      if (!done && c >= 2 && hipEventQuery(ev[(c - 1) % NEV]) == hipSuccess) done = f->host_live_count[(c - 1) * every] == 0;
-      if (done) break;
-      if (hipMemcpyAsync(f->host_live_count + k, f->live_count + k, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-          hipEventRecord(ev[c % NEV], st) != hipSuccess) { rc = ASR_ERR_HIP; break; }
-    }
-    const bool more = k + 1 < To;
-    // (saved-activation arrays the backward would need are reused every step: index 0)
-    if ((rc = dec_fwd_step(h, a, k, 0, more, s, g, sk)) != ASR_OK) break;
-    float* av = f->av_all + (size_t)k * B * U;
-    float* lg = f->logits_all + (size_t)k * B * C2;
-    if ((rc = asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, B, U, Dav, a->av_in + (size_t)k * B * Dav, Dav, f->W_av, U, av, U, nullptr,
-                           0, 0, s)) != ASR_OK) break;
-    if ((rc = asr_tanh_fwd(h, av, av, (size_t)B * U, s)) != ASR_OK) break;
-    if ((rc = asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, B, C2, U, av, U, f->W_out, C2, lg, C2, f->b_out, 0, 0, s)) != ASR_OK) break;
-    hipLaunchKernelGGL(att_infer_select_kernel, dim3(B), dim3(256), 0, st, lg, C2, f->eos, f->live + (size_t)k * B,
-                       f->live + (size_t)(k + 1) * B, f->live_count + k + 1, f->ids_all + (size_t)k * B, f->embedding, Em,
-                       more ? a->dec_in + (size_t)(k + 1) * B * Din : nullptr, Din, E2);
-  }
-  if (every)
-    for (int i = 0; i < NEV; ++i) (void)hipEventDestroy(ev[i]);
-  if (rc != ASR_OK) ASR_FAIL(h, rc, "asr_att_decoder_infer: step %d failed", k);
-  ASR_CHECK_LAUNCH(h, "asr_att_decoder_infer");
-  if (steps_issued) *steps_issued = k;
-  return ASR_OK;
-}
-extern "C" int asr_att_decoder_infer(asr_handle* h, const asr_att_decoder* a, const asr_att_infer* f, int* steps_issued,
-                                     asr_stream s) {
-  return dec_infer_loop(h, a, nullptr, f, steps_issued, s);
-}
-extern "C" int asr_att_decoder_infer_gru(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, const asr_att_infer* f,
-                                         int* steps_issued, asr_stream s) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  if (!g) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_infer_gru: bad arguments");
-  return dec_infer_loop(h, a, g, f, steps_issued, s);
-}
-extern "C" int asr_att_decoder_infer_stack(asr_handle* h, const asr_att_decoder* a, const asr_att_stack* sk,
-                                           const asr_att_infer* f, int* steps_issued, asr_stream s) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  if (!sk) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_infer_stack: bad arguments");
-  return dec_infer_loop(h, a, nullptr, f, steps_issued, s, sk);
-}
-
-// ---------------------------------------------------------------- scheduled-sampling training loop, native
-namespace {
-// One workgroup per batch row, behind the output layer of decoder step k; every pointer is the row block of step k + 1
-// except `logits` (step k).  The token step k + 1 is fed: the argmax of step k's raw logits (first maximum wins, the
-// reduction of att_infer_select_kernel) where the row's draw is set and the row is still live at k + 1, the teacher's
-// token otherwise -- the reduction runs only when it is used (the test is uniform over the workgroup).  The fed id goes
-// to ids_n and its embedding, times the row's embedding-dropout mask, into the Em embedding columns of the next input row;
-// the context and h columns of that row are the loop's.
-__global__ __launch_bounds__(256) void att_ss_select_kernel(const float* __restrict__ logits, int C2,
-                                                            const float* __restrict__ draw_n, const float* __restrict__ live_n,
-                                                            const int32_t* __restrict__ teacher_n, int32_t* __restrict__ ids_n,
-                                                            const float* __restrict__ emb, int Em,
-                                                            const float* __restrict__ mask_n, float* __restrict__ dnext,
-                                                            int Din) {
-  __shared__ float sv[4];
-  __shared__ int si[4];
-  const int b = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int id = teacher_n[b];
-  if (draw_n[b] != 0.f && live_n[b] != 0.f) {
-    const float* p = logits + (size_t)b * C2;
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int k = threadIdx.x; k < C2; k += 256) {
-      const float v = p[k];
-      if (v > best || (v == best && k < bi)) { best = v; bi = k; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(best, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-    }
-    if (lane == 0) { sv[w] = best; si[w] = bi; }
-    __syncthreads();
-    best = sv[0]; bi = si[0];
-#pragma unroll
-    for (int i = 1; i < 4; ++i)
-      if (sv[i] > best || (sv[i] == best && si[i] < bi)) { best = sv[i]; bi = si[i]; }
-    id = bi == 0x7fffffff ? 0 : bi;
-  }
-  if (threadIdx.x == 0) ids_n[b] = id;
-  float* d = dnext + (size_t)b * Din;
-  const float* e = emb + (size_t)id * Em;
-  if (mask_n) {
-    const float* mk = mask_n + (size_t)b * Em;
-    for (int j = threadIdx.x; j < Em; j += 256) d[j] = e[j] * mk[j];
-  } else {
-    for (int j = threadIdx.x; j < Em; j += 256) d[j] = e[j];
-  }
-}
-}  // namespace
-
-extern "C" int asr_att_decoder_fwd_ss(asr_handle* h, const asr_att_decoder* a, const asr_att_decoder_ss* f, asr_stream s) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  ASR_TRY(dec_check(h, a, false));
-  if (!f || !f->W_av || !f->W_out || !f->embedding || !f->teacher_ids || !f->draw || !f->av_all || !f->logits_all ||
-      !f->ids_fed || f->C2 < 1 || a->Em < 1)
-    ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_fwd_ss: bad arguments");
-  const int B = a->B, U = a->U, E2 = a->E2, Em = a->Em, To = a->To, C2 = f->C2;
-  const int Din = Em + E2 + U, Dav = U + E2;
-  hipStream_t st = (hipStream_t)s;
-  ASR_TRY(dec_cell_image(h, a, s));
-  for (int k = 0; k < To; ++k) {
-    const bool more = k + 1 < To;
-    ASR_TRY(dec_fwd_step(h, a, k, k, more, s));
-    // the head of the step, as asr_att_decoder_infer issues it
-    float* av = f->av_all + (size_t)k * B * U;
-    float* lg = f->logits_all + (size_t)k * B * C2;
-    ASR_TRY(asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, B, U, Dav, a->av_in + (size_t)k * B * Dav, Dav, f->W_av, U, av, U, nullptr,
-                         0, 0, s));
-    ASR_TRY(asr_tanh_fwd(h, av, av, (size_t)B * U, s));
-    ASR_TRY(asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, B, C2, U, av, U, f->W_out, C2, lg, C2, f->b_out, 0, 0, s));
-    if (!more) break;
-    const size_t n = (size_t)(k + 1) * B;
-    hipLaunchKernelGGL(att_ss_select_kernel, dim3(B), dim3(256), 0, st, lg, C2, f->draw + n, a->live + n, f->teacher_ids + n,
-                       f->ids_fed + n, f->embedding, Em, f->emb_mask ? f->emb_mask + n * Em : nullptr,
-                       a->dec_in + n * Din, Din);
-  }
-  ASR_CHECK_LAUNCH(h, "asr_att_decoder_fwd_ss");
-  return ASR_OK;
-}
-
-// ---------------------------------------------------------------- beam search loop, native
-// BeamSearchDecoder.step under dynamic_decode (beam_search/beam_search_decoder.py:173-231) and finalize (:125-150).  The
-// loop carries one step of state: block 0 of dec_in / c_all / h_all is what a step reads, block 1 takes its raw
-// outputs, and the reorder kernel gathers block 1 back into block 0 by parent -- so every step is dec_fwd_step at
-// k = 0 with a next row, the very launches asr_att_decoder_infer issues, and the carried attention weights are the
-// `alpha_zero` of that step.  Early exit: the scheme of asr_att_decoder_infer on the count of unfinished slots.
-// j != nullptr: the joint CTC / attention search (asr_att_decoder_beam_joint) -- the selection is
-// asr_att_beam_select_joint on the prefix state of block k & 1 of j->r / j->last, and asr_ctc_prefix_advance writes the
-// other block from the parents'.  Without j the calls are those this loop has always issued.
-// lm != nullptr: shallow fusion with a language model (asr_att_decoder_beam_lm, lm_fusion.hip) -- asr_lm_step behind the
-// head, asr_att_beam_select_fused as the selection (with or without j; a j whose ctc_weight is not in (0, 1] is refused:
-// the fused rank kernel would leave its `last` block unwritten), asr_lm_beam_reorder at the end of the step.  Only the
-// selection differs between the three searches; the state advance and the re-ordering behind it are shared.  Without lm
-// nothing of this is issued.
-// g != nullptr (asr_att_decoder_beam_gru): the GRU cell in the step; a->c_all is then a block of zeros the re-ordering
-// gathers as it always has.
-static int att_beam_loop(asr_handle* h, const asr_att_decoder* a_, const asr_att_infer* f, const asr_att_beam* m,
-                         const asr_att_beam_ctc* j, const asr_att_lm* lm, int* steps_issued, asr_stream s,
-                         const asr_att_gru* g = nullptr, const asr_att_stack* sk = nullptr) {
-  const char* who = sk ? "asr_att_decoder_beam_stack" : g ? "asr_att_decoder_beam_gru" : lm ? "asr_att_decoder_beam_lm" : j ? "asr_att_decoder_beam_joint" : "asr_att_decoder_beam";
-  if (!a_ || !m) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "%s: bad arguments", who);
-  asr_att_decoder d = *a_;
-  if (d.carry_alpha) d.alpha_zero = m->alpha_prev;
-  const asr_att_decoder* a = &d;
-  ASR_TRY(dec_check(h, a, false, g, sk));
-  if (g && !a->c_all) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "%s: c_all (zeros [2,R,U]) is needed by the re-ordering", who);
-  if (!f || !f->W_av || !f->W_out || !f->embedding || f->C2 < 1 || f->eos < 0 || f->eos >= f->C2 || a->dmask || m->W < 1 ||
-      m->W > 32 || m->W > f->C2 || a->B % m->W != 0 || !m->word || !m->parent || !m->score || !m->log_probs || !m->finished ||
-      !m->lengths || !m->av || !m->logits || !m->unfinished || !m->ids || !m->hyp_len || !m->final_score ||
-      (a->carry_alpha && !m->alpha_prev))
-    ASR_FAIL(h, ASR_ERR_INVALID_ARG, "%s: bad arguments", who);
-  const int R = a->B, W = m->W, Bu = R / W, U = a->U, E2 = a->E2, Em = a->Em, To = a->To, C2 = f->C2, T = a->T;
-  const int Din = Em + E2 + U, Dav = U + E2;
-  hipStream_t st = (hipStream_t)s;
-  if (lm) {
-    if (lm->R != R || lm->C2 != C2 || f->eos != C2 - 1 || C2 < 3 || W > C2 - 1 || !lm->lm_score || !lm->cand ||
-        !lm->cand_total || !lm->cand_lm || !(lm->lm_weight > 0.f) || (j && !(j->ctc_weight > 0.f && j->ctc_weight <= 1.f)))
-      ASR_FAIL(h, ASR_ERR_INVALID_ARG, "%s: bad arguments (the language model part)", who);
-    ASR_TRY(asr_lm_prep(h, lm, s));
-  }
-  if (j) {
-    if (!j->y || !j->seq_len || !j->r || !j->last || !j->ctc_score || !j->cand || !j->cand_total || !j->psi ||
-        C2 != j->n_labels + 2 || f->eos != j->n_labels + 1)
-      ASR_FAIL(h, ASR_ERR_INVALID_ARG, "%s: bad arguments (the CTC part)", who);
-    ASR_TRY(asr_ctc_prefix_init(h, j->y, j->seq_len, Bu, W, T, j->By, j->Cc, j->blank, j->r, j->last, j->ctc_score, s));
-  }
-  if (hipMemsetAsync(m->unfinished, 0, (size_t)(To + 1) * sizeof(int32_t), st) != hipSuccess)
-    ASR_FAIL(h, ASR_ERR_HIP, "%s: memset", who);
-  constexpr int NEV = 3;
-  hipEvent_t ev[NEV] = {nullptr, nullptr, nullptr};
-  const int every = (f->host_live_count && f->check_every > 0) ? f->check_every : 0;
-  if (every) {
-    for (int i = 0; i < NEV; ++i)
-      if (hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) != hipSuccess) {
-        for (int e = 0; e < i; ++e) (void)hipEventDestroy(ev[e]);
-        ASR_FAIL(h, ASR_ERR_HIP, "%s: event", who);
-      }
-  }
-  float* din1 = a->dec_in + (size_t)R * Din;
-  float* c1 = a->c_all + (size_t)R * U;
-  float* h1 = a->h_all + (size_t)R * U;
-  int rc = dec_cell_image(h, a, s, g, sk), k = 0;
-  for (; rc == ASR_OK && k < To; ++k) {
-    if (every && k % every == 0 && k > 0) {                // (see asr_att_decoder_infer)
-      const int c = k / every;
-      bool done = false;
-      if (c >= 3) {
-        (void)hipEventSynchronize(ev[(c - 2) % NEV]);
-        done = f->host_live_count[(c - 2) * every] == 0;
-      }
-      if (!done && c >= 2 && hipEventQuery(ev[(c - 1) % NEV]) == hipSuccess) done = f->host_live_count[(c - 1) * every] == 0;
-      if (done) break;
-      if (hipMemcpyAsync(f->host_live_count + k, m->unfinished + k, sizeof(int32_t), hipMemcpyDeviceToHost, st) != hipSuccess ||
-          hipEventRecord(ev[c % NEV], st) != hipSuccess) { rc = ASR_ERR_HIP; break; }
-    }
-    if ((rc = dec_fwd_step(h, a, 0, 0, true, s, g, sk)) != ASR_OK) break;
-    if ((rc = asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, R, U, Dav, a->av_in, Dav, f->W_av, U, m->av, U, nullptr, 0, 0, s)) != ASR_OK) break;
-    if ((rc = asr_tanh_fwd(h, m->av, m->av, (size_t)R * U, s)) != ASR_OK) break;
-    if ((rc = asr_gemm_act(h, ASR_F32, ASR_F32, 0, 0, R, C2, U, m->av, U, f->W_out, C2, m->logits, C2, f->b_out, 0, 0, s)) != ASR_OK) break;
-    const size_t o = (size_t)k * R;
-    // the prefix state of this step and the next (j): blocks k & 1 and (k + 1) & 1
-    const size_t rblk = (size_t)R * 2 * T;
-    float* r_cur = j ? j->r + (size_t)(k & 1) * rblk : nullptr;
-    float* r_nxt = j ? j->r + (size_t)((k + 1) & 1) * rblk : nullptr;
-    int32_t* last_cur = j ? j->last + (size_t)(k & 1) * R : nullptr;
-    int32_t* last_nxt = j ? j->last + (size_t)((k + 1) & 1) * R : nullptr;
-    // the selection: fused with the language model's step in front of it, joint, or attention alone
-    if (lm) {
-      if ((rc = asr_lm_step(h, lm, s)) != ASR_OK) break;
-      if ((rc = asr_att_beam_select_fused(h, m->logits, lm->lm_logits, Bu, W, C2 - 2, m->length_penalty_weight,
-                                          j ? j->ctc_weight : 0.f, lm->lm_weight, k == 0, j ? j->y : nullptr,
-                                          j ? j->seq_len : nullptr, T, j ? j->By : 0, j ? j->Cc : 0, j ? j->blank : 0, r_cur,
-                                          m->log_probs, m->finished, m->lengths, last_cur, j ? j->ctc_score : nullptr,
-                                          lm->lm_score, lm->cand, lm->cand_total, lm->cand_lm, j ? j->psi : nullptr,
-                                          m->word + o, m->parent + o, m->score + o, m->log_probs, m->finished, m->lengths,
-                                          last_nxt, j ? j->ctc_score : nullptr, lm->lm_score, m->unfinished + k + 1,
-                                          s)) != ASR_OK) break;
-    } else if (j) {
-      if ((rc = asr_att_beam_select_joint(h, m->logits, Bu, W, j->n_labels, m->length_penalty_weight, j->ctc_weight, k == 0,
-                                          j->y, j->seq_len, T, j->By, j->Cc, j->blank, r_cur, m->log_probs, m->finished,
-                                          m->lengths, last_cur, j->ctc_score, j->cand, j->cand_total, j->psi, m->word + o,
-                                          m->parent + o, m->score + o, m->log_probs, m->finished, m->lengths, last_nxt,
-                                          j->ctc_score, m->unfinished + k + 1, s)) != ASR_OK) break;
-    } else if ((rc = asr_att_beam_select(h, m->logits, Bu, W, C2, f->eos, m->length_penalty_weight, k == 0, m->log_probs,
-                                         m->finished, m->lengths, m->word + o, m->parent + o, m->score + o, m->log_probs,
-                                         m->finished, m->lengths, m->unfinished + k + 1, s)) != ASR_OK) break;
-    // what the next step reads: the prefix state of the winners (j), the decoder's rows, the language model's rows (lm)
-    if (j && (rc = asr_ctc_prefix_advance(h, j->y, j->seq_len, Bu, W, T, j->By, j->Cc, j->blank, j->n_labels, r_cur, last_cur,
-                                          m->parent + o, m->word + o, r_nxt, s)) != ASR_OK) break;
-    if ((rc = asr_att_beam_reorder(h, m->parent + o, m->word + o, Bu, W, U, Em, E2, a->carry_alpha ? T : 0, C2, c1, h1, din1,
-                                   a->carry_alpha ? a->alpha_all : nullptr, f->embedding, a->c_all, a->h_all, a->dec_in,
-                                   a->carry_alpha ? m->alpha_prev : nullptr, s)) != ASR_OK) break;
-    if (sk && (rc = asr_att_stack_reorder(h, sk, m->parent + o, Bu, W, U, s)) != ASR_OK) break;   // the upper layers' rows
-    if (lm) {
-      const size_t lblk = (size_t)lm->L * R * lm->H;       // block 1 (the step's new state) -> block 0
-      if ((rc = asr_lm_beam_reorder(h, m->parent + o, m->word + o, Bu, W, lm->L, lm->H, lm->Em_lm, C2, lm->c + lblk,
-                                    lm->h + lblk, lm->emb, lm->c, lm->h, lm->in, s)) != ASR_OK) break;
-    }
-  }
-  if (every)
-    for (int i = 0; i < NEV; ++i) (void)hipEventDestroy(ev[i]);
-  if (rc != ASR_OK) return rc;                             // (the failing call has set the message)
-  if (k < 1) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "%s: no step issued", who);
-  ASR_TRY(asr_att_beam_backtrace(h, m->word, m->parent, m->score, k, To, Bu, W, f->eos, m->ids, m->hyp_len, m->final_score, s));
-  if (steps_issued) *steps_issued = k;
-  return ASR_OK;
-}
-
-extern "C" int asr_att_decoder_beam(asr_handle* h, const asr_att_decoder* a, const asr_att_infer* f, const asr_att_beam* m,
-                                    int* steps_issued, asr_stream s) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  return att_beam_loop(h, a, f, m, nullptr, nullptr, steps_issued, s);
-}
-
-extern "C" int asr_att_decoder_beam_joint(asr_handle* h, const asr_att_decoder* a, const asr_att_infer* f, const asr_att_beam* m,
-                                          const asr_att_beam_ctc* j, int* steps_issued, asr_stream s) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  if (!j) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_beam_joint: bad arguments");
-  return att_beam_loop(h, a, f, m, j, nullptr, steps_issued, s);
-}
-
-extern "C" int asr_att_decoder_beam_lm(asr_handle* h, const asr_att_decoder* a, const asr_att_infer* f, const asr_att_beam* m,
-                                       const asr_att_beam_ctc* j, const asr_att_lm* lm, int* steps_issued, asr_stream s) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  if (!lm) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_beam_lm: bad arguments");
-  return att_beam_loop(h, a, f, m, j, lm, steps_issued, s);
-}
-
-extern "C" int asr_att_decoder_beam_gru(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, const asr_att_infer* f,
-                                        const asr_att_beam* m, int* steps_issued, asr_stream s) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  if (!g) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_beam_gru: bad arguments");
-  return att_beam_loop(h, a, f, m, nullptr, nullptr, steps_issued, s, g);
-}
-extern "C" int asr_att_decoder_beam_stack(asr_handle* h, const asr_att_decoder* a, const asr_att_stack* sk,
-                                          const asr_att_infer* f, const asr_att_beam* m, int* steps_issued, asr_stream s) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  if (!sk) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_beam_stack: bad arguments");
-  return att_beam_loop(h, a, f, m, nullptr, nullptr, steps_issued, s, nullptr, sk);
-}
-
-// g != nullptr (asr_att_decoder_bwd_gru): the cell backward and the cell-input product of a step are the GRU's
-// (asr_gru_dec_bwd_step); the query-FC backward in front of them is the unfused branch's.
-// sk != nullptr (asr_att_decoder_bwd_stack): the cell backward of a step is the TOP layer's; behind it, per lower layer,
-// the dx product of the layer above with that layer's cell backward (asr_stack_dec_bwd_lower), down to layer 0, whose
-// own cell-input product follows as ever.
-static int dec_bwd_loop(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, asr_stream s,
-                        const asr_att_stack* sk = nullptr) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  ASR_TRY(dec_check(h, a, true, g, sk));
-  const int B = a->B, U = a->U, T = a->T, E2 = a->E2, Em = a->Em, A = a->A, To = a->To;
-  const int Din = Em + E2 + U;
-  hipStream_t st = (hipStream_t)s;
-  // work: dc / carried-dh state (two buffers each, ping-pong), denergy, dalpha_prev x2
-  float* dcs[2] = {a->work, a->work + (size_t)B * U};
-  float* dhc[2] = {a->work + (size_t)2 * B * U, a->work + (size_t)3 * B * U};
-  float* dalp[2] = {a->work + (size_t)4 * B * U, a->work + (size_t)4 * B * U + (size_t)B * T};
-  float* denergy = dalp[1] + (size_t)B * T;
-  if (hipMemsetAsync(dcs[0], 0, (size_t)B * U * sizeof(float), st) != hipSuccess ||
-      hipMemsetAsync(dhc[0], 0, (size_t)B * U * sizeof(float), st) != hipSuccess)
-    ASR_FAIL(h, ASR_ERR_HIP, "asr_att_decoder_bwd: memset");
-  // the bf16 images of W_cell are written again here (one launch per loop): the call does not depend on the forward
-  // loop having run with the same work space
-  const bool cell_h = !g && dec_cell_gemm_h(a);
-  if (g) ASR_TRY(asr_gru_dec_image(h, a, g, s));
-  if (sk) ASR_TRY(asr_stack_dec_bwd_begin(h, a, sk, s));
-  if (cell_h) ASR_TRY(asr_lstm_cell_gemm_prep_h(h, a->W_cell, a->b_cell, Din, U, a->W_cell_h, s));
-  int cur = 0;
-  const float* dalpha_next = nullptr;
-  for (int k = To - 1; k >= 0; --k) {
-    // d loss / d ctx_k = attentional-vector part + the context columns of step k+1's cell-input gradient; the sum is
-    // formed inside the d-alpha kernel (and kept in dctx_all for the d_enc contraction after the loop)
-    float* dctx = a->dctx_all + (size_t)k * B * E2;
-    const float* dav_ctx = a->dav_ctx + (size_t)k * B * E2;
-    const float* d_in_next = (k + 1 < To) ? a->d_in_all + (size_t)(k + 1) * B * Din : nullptr;
-    const float* alpha_k = a->alpha_all + (size_t)k * B * T;
-    const float* qz = a->qz_all + (size_t)k * B * A;
-    float* dqz = a->dqz_all + (size_t)k * B * A;
-    float* dv = a->dv_all ? a->dv_all + (size_t)k * B * A : nullptr;
-    // the softmax backward is folded into the energy backward when both sides run their vectorised kernels
-    SoftmaxBwdFold fold = {nullptr, nullptr, nullptr, nullptr, 0, 0.f};
-    SoftmaxBwdFold* fp = (!a->carry_alpha && energy_vec_shape(A, a->keys, qz, a->v, a->dkeys)) ? &fold : nullptr;
-    const float* snorm = a->snorm_all ? a->snorm_all + (size_t)k * B : nullptr;
-    if (d_in_next) {
-      ASR_TRY(softmax_ctx_bwd_launch(h, dav_ctx, d_in_next + Em, Din, dctx, alpha_k, a->seq_len, a->sharpening, a->enc,
-                                     a->enc_dtype, T, B, E2, denergy, nullptr, snorm, dalpha_next, fp, s));
-    } else {
-      if (hipMemcpyAsync(dctx, dav_ctx, (size_t)B * E2 * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
-        ASR_FAIL(h, ASR_ERR_HIP, "asr_att_decoder_bwd: copy");
-      ASR_TRY(softmax_ctx_bwd_launch(h, dctx, nullptr, 0, nullptr, alpha_k, a->seq_len, a->sharpening, a->enc,
-                                     a->enc_dtype, T, B, E2, denergy, nullptr, snorm, dalpha_next, fp, s));
-    }
-    h->att_counts[(fp && fp->da) ? ASR_ATT_BWD_SOFTMAX_FOLDED : ASR_ATT_BWD_SOFTMAX_SEPARATE] += 1;
-    if (a->carry_alpha) {
-      float* dap = dalp[k & 1];
-      ASR_TRY(loc_energy_bwd_launch(h, denergy, k > 0 ? a->alpha_all + (size_t)(k - 1) * B * T : a->alpha_zero, a->filt,
-                                    a->wfil, a->keys, qz, a->v, T, B, A, a->taps, a->dkeys, dqz, dv, a->dwfil_rows,
-                                    a->dfilt_rows, dap, k != To - 1, a->seq_len, s));
-      dalpha_next = dap;
-    }
-    float* dcell = const_cast<float*>(a->dav_cell) + (size_t)k * B * U;
-    float* dpre = a->dpre_all + (size_t)k * B * 4 * U;
-    float* dpeep = a->dpeep_all ? a->dpeep_all + (size_t)k * B * 3 * U : nullptr;
-    const float* dh2 = d_in_next ? d_in_next + Em + E2 : nullptr;
-    const float* dmask = a->dmask ? a->dmask + (size_t)k * B * U : nullptr;
-    // query-FC backward + cell backward in ONE launch that also sums the energy backward's chunk partials, when the
-    // shapes allow (a query FC over A = 64 / 128 / 256 / 512 columns, U % 16 == 0, 16-byte aligned rows, no carried alpha)
-    const bool fused_q = !g && !a->carry_alpha && a->has_query_fc && (A == 64 || A == 128 || A == 256 || A == 512) && U % DQ_CT == 0 &&
-                         a->ld_wq % 4 == 0 && ((uintptr_t)a->W_q) % 16 == 0 && ((uintptr_t)dqz) % 16 == 0 &&
-                         (!dv || ((uintptr_t)dv) % 16 == 0);
-    h->att_counts[fused_q ? ASR_ATT_BWD_STEP_FUSED_Q : ASR_ATT_BWD_STEP_UNFUSED] += 1;
-    // layer 0's cell backward (the only one without a stack)
-    const CellBwdArgs ca0 = {dcs[cur], dhc[cur], dh2, a->gates_all + (size_t)k * B * 4 * U, a->craw_all + (size_t)k * B * U,
-                             a->c_all + (size_t)k * B * U, a->peep, a->live + (size_t)k * B, dmask,
-                             dpre, dcs[cur ^ 1], dhc[cur ^ 1], dpeep, Din, 0.f};   // (clip: see the unfused call below)
-    if (fused_q) {
-      const float* part = nullptr;
-      int nchq = 0;
-      ASR_TRY(energy_bwd_launch(h, denergy, a->keys, qz, a->v, T, B, A, a->att_mode, a->dkeys, dqz, dv, a->seq_len, fp, s,
-                                &part, &nchq));
-      hipLaunchKernelGGL(att_dq_cell_bwd_kernel, dim3(U / DQ_CT + 2, (B + 15) / 16), dim3(512), 0, st, part, nchq, B, A, U,
-                         a->W_q, a->ld_wq, dcell, dqz, dv, sk ? asr_stack_cell_args(a, sk, sk->L - 1, k, cur) : ca0);
-      ASR_CHECK_LAUNCH(h, "asr_att_decoder_bwd");
-    } else {
-      if (!a->carry_alpha)
-        ASR_TRY(energy_bwd_launch(h, denergy, a->keys, qz, a->v, T, B, A, a->att_mode, a->dkeys, dqz, dv, a->seq_len, fp, s));
-      if (a->has_query_fc)
-        ASR_TRY(asr_gemm_act(h, ASR_F32, ASR_F32, 0, 1, B, U, A, dqz, A, a->W_q, a->ld_wq, dcell, U, nullptr, 1, 0, s));
-      else
-        ASR_TRY(asr_add_cols(h, dcell, U, dqz, A, dcell, U, B, U, s));
-      if (g) {       // (mask and the h-columns of step k+1's cell-input gradient are folded in as below; dcs is its work space)
-        ASR_TRY(asr_gru_dec_bwd_step(h, a, g, k, dcell, dhc[cur], dh2, dhc[cur ^ 1], dcs[0], s));
-        cur ^= 1;
-        continue;
-      }
-      // the cell kernel applies the output dropout mask to dcell and adds the h-columns of step k+1's cell-input
-      // gradient to the carried dh itself
-      // (clip 0: the decoder cell is tf.contrib.rnn.LSTMBlockCell (attention_seq2seq.py:354-365), whose gradient op
-      // ignores cell_clip: the clamp is straight-through here)
-      ASR_TRY(asr_lstm_cell_bwd_args(h, dcell, sk ? asr_stack_cell_args(a, sk, sk->L - 1, k, cur) : ca0, B, U, s));
-    }
-    if (sk)                                // down the stack: dx of layer l + 1 and the cell backward of layer l, l = L-2 .. 0
-      for (int l = sk->L - 2; l >= 0; --l)
-        ASR_TRY(asr_stack_dec_bwd_lower(h, a, sk, l, k, l ? asr_stack_cell_args(a, sk, l, k, cur) : ca0, s));
-    float* d_in = a->d_in_all + (size_t)k * B * Din;
-    h->att_counts[cell_h ? ASR_ATT_BWD_CELL_BF16 : ASR_ATT_BWD_CELL_GEMM] += 1;
-    if (cell_h) ASR_TRY(asr_lstm_cell_gemm_bwd_h(h, dpre, B, Din, U, a->W_cell_h, d_in, Din, s));   // bf16 weight rows
-    else ASR_TRY(asr_gemm_act(h, ASR_F32, ASR_F32, 0, 1, B, Din, 4 * U, dpre, 4 * U, a->W_cell, 4 * U, d_in, Din, nullptr, 0, 0, s));
-    cur ^= 1;
-  }
-  ASR_TRY(asr_add_cols(h, dhc[cur], U, a->d_in_all + Em + E2, Din, a->dh0, U, B, U, s));
-  if (sk) ASR_TRY(asr_stack_dec_bwd_end(h, a, sk, cur, s));
-  if (g) return ASR_OK;                                    // (no cell state, no dc0)
-  if (hipMemcpyAsync(a->dc0, dcs[cur], (size_t)B * U * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
-    ASR_FAIL(h, ASR_ERR_HIP, "asr_att_decoder_bwd: copy");
-  return ASR_OK;
-}
-
-extern "C" int asr_att_decoder_bwd(asr_handle* h, const asr_att_decoder* a, asr_stream s) {
-  return dec_bwd_loop(h, a, nullptr, s);
-}
-extern "C" int asr_att_decoder_bwd_gru(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, asr_stream s) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  if (!g) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_bwd_gru: bad arguments");
-  return dec_bwd_loop(h, a, g, s);
-}
-extern "C" int asr_att_decoder_bwd_stack(asr_handle* h, const asr_att_decoder* a, const asr_att_stack* sk, asr_stream s) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  if (!sk) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_bwd_stack: bad arguments");
-  return dec_bwd_loop(h, a, nullptr, s, sk);
-}
-
 
 extern "C" int asr_att_path_counts(asr_handle* h, unsigned long long* out, int n) {
   if (!h || !out || n < 0) return ASR_ERR_INVALID_ARG;

@@ -200,7 +200,7 @@ bool asr_cluster_gru_bwd_try(asr_handle* h, int T, int B, int H, int ndir, const
                              const float* hout, const float* r, const float* u, const float* c, const float* wghT,
                              const float* wchT, const int32_t* seq_len, float* dgate, float* dcand, hipStream_t st);
 
-// the GRU cell's part of a decoder-loop step (gru_decoder.hip; the loops are attention.hip's): argument check, the weight
+// the GRU cell's part of a decoder-loop step (gru_decoder.hip; the loops are dec_loop.hip's): argument check, the weight
 // image once per loop call, the cell launches of forward step k (saved activations at row ks; dnext = the next step's
 // input rows or NULL; qz = the step's query rows) and of backward step k (work2: 2*B*U floats)
 int asr_gru_dec_check(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g);
@@ -210,7 +210,7 @@ int asr_gru_dec_fwd_step(asr_handle* h, const asr_att_decoder* a, const asr_att_
 int asr_gru_dec_bwd_step(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g, int k, const float* dcell,
                          const float* dh_c, const float* dh_c2, float* dh_carry, float* work2, asr_stream s);
 
-// the upper layers of a multi-layer LSTM decoder (dec_stack.hip; the loops are attention.hip's): argument check, the
+// the upper layers of a multi-layer LSTM decoder (dec_stack.hip; the loops are dec_loop.hip's): argument check, the
 // layers' weight images once per loop call, the upper layers' cell launches of forward step k (layer 0 has written
 // up[0].in[k][:, :U]; saved activations at row ks; `more`: the next step's h-columns are written; qz: the step's query rows
 // when there is no query FC, else NULL), and the per-loop parts of the backward (zeroed carries; dc0 / dh0 at the end)

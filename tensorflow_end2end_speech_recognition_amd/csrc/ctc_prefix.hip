@@ -2,7 +2,7 @@
 // prefix scores of the candidates of a beam search step and the state they are computed from.  The selection by fused
 // score that runs it between its two kernels is asr_att_beam_select_joint / _fused (att_beam.hip).  The float64 statement
 // is models/attention/decoders/beam_search/ctc_prefix_score.py; the loops that issue these are asr_att_decoder_beam_joint
-// and asr_att_decoder_beam_lm (attention.hip).
+// and asr_att_decoder_beam_lm (dec_loop.hip).
 //
 // Vocabularies: attention classes C2 = N + 2 (labels, <SOS> = N, <EOS> = N + 1); CTC classes Cc = N + 1 (blank = N by
 // default).  y [T, By, Cc] are log-posteriors (asr_log_softmax_rows of the CTC head's logits); device row r = b*W + w reads

@@ -1,5 +1,5 @@
 // Multi-layer LSTM decoder of the attention models (decoder_num_layers = L > 1): MultiRNNCell of L LSTMBlockCell(U), each
-// in a DropoutWrapper(output_keep_prob).  Layer 0 is the decoder cell the loops of attention.hip have always run; this
+// in a DropoutWrapper(output_keep_prob).  Layer 0 is the decoder cell the loops of dec_loop.hip have always run; this
 // file holds what the upper layers l = 1 .. L-1 add to a step (x_l = [ o_{l-1} | h_{l,k-1} ], 2U wide):
 //   forward    one cell launch per upper layer with the existing kernels -- asr_lstm_cell_gemm_fwd on the layer's
 //              interleaved image where asr_lstm_cell_gemm_ok(B, 2U, U, 2U), asr_gemm_act + asr_lstm_cell_fwd_ex elsewhere
@@ -8,7 +8,7 @@
 //              dx[:, :U], as ONE launch (stack_dx_cell_bwd_kernel) at B <= 32, U % 16 == 0, 16-byte aligned operands,
 //              and as asr_gemm_act x 2 + the plain cell backward launch at every other shape;
 //   beam       stack_reorder_kernel: every upper layer's c / h rows and carried h-columns gathered by parent, one launch.
-// The loops themselves (and layer 0, the query FC, the attention, the heads) are attention.hip's.
+// The loops themselves (and layer 0, the query FC, the attention, the heads) are dec_loop.hip's.
 #include "common.h"
 #include "lstm_cell_bwd.h"
 #include <math.h>
@@ -228,7 +228,7 @@ extern "C" int asr_reset_att_stack_counts(asr_handle* h) {
   return ASR_OK;
 }
 
-// ---------------------------------------------------------------- the upper layers' part of the loops of attention.hip
+// ---------------------------------------------------------------- the upper layers' part of the loops of dec_loop.hip
 int asr_stack_dec_check(asr_handle* h, const asr_att_decoder* a, const asr_att_stack* sk, bool bwd) {
   if (!a || !sk || sk->L < 2 || sk->L > ASR_ATT_STACK_MAX + 1)
     ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder (stack): L must be 2 .. %d", ASR_ATT_STACK_MAX + 1);

@@ -321,7 +321,7 @@ extern "C" int asr_gru_cell_bwd(asr_handle* h, const float* dcell, const float* 
 
 ASR_DEFINE_COUNTS3(att_gru_counts)
 
-// ---------------------------------------------------------------- the cell part of a decoder-loop step (attention.hip)
+// ---------------------------------------------------------------- the cell part of a decoder-loop step (dec_loop.hip)
 int asr_gru_dec_check(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g) {
   if (!g || !g->W_g || !g->b_g || !g->W_c || !g->b_c || !g->W3 || ((uintptr_t)g->W3) % 16 != 0)
     ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_att_decoder_*_gru: bad arguments (the GRU part)");

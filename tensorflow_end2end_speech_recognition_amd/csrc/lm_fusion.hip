@@ -3,7 +3,7 @@
 // models/ctc/decoders/beam_search_decoder.py:132): the language model -- one LM step on the beam's rows and the re-ordering of
 // the LM state.  The selection over the attention, LM and (for joint models) CTC prefix scores is asr_att_beam_select_fused
 // (att_beam.hip).  The float64 statement is models/attention/decoders/beam_search/lm_fusion.py; the loop that issues these
-// is asr_att_decoder_beam_lm (attention.hip, the beam search loop).  The LM step has no recurrence kernel of its own: it
+// is asr_att_decoder_beam_lm (dec_loop.hip, the beam search loop).  The LM step has no recurrence kernel of its own: it
 // runs the decoder cell's entries.
 #include "common.h"
 #include <math.h>

@@ -1,6 +1,6 @@
 // The backward of one LSTMBlockCell element of the attention decoder, shared by every kernel that runs it: the plain
-// launch and the fused query-FC + cell kernel of attention.hip, and the dx + cell kernel of a decoder stack
-// (dec_stack.hip).  One statement of the arithmetic, so that the three agree bit for bit.
+// launch and the fused query-FC + cell kernel of attention.hip (the backward loop of dec_loop.hip issues both), and the
+// dx + cell kernel of a decoder stack (dec_stack.hip).  One statement of the arithmetic, so that the three agree bit for bit.
 #pragma once
 #include "common.h"
 

@@ -351,6 +351,33 @@ class AttentionSeq2Seq(ModelBase):
         return dict(W_cell=self._w_cell(), b_cell=st[D + 'lstm_cell/bias'], cell_bf16=(self.dtype == ASR_BF16),
                     peep=peep)
 
+    def _loop_dict(self, rows, To, saved, keys, enc_att, seq_len, alpha_zero, live, dmask, dec_in, av_in, alpha_all,
+                   snorm_all, c_all, h_all, craw=True, peep=None):
+        """The dict the ops.att_decoder_* loops take, with what every loop shares filled in here: shape and mode ints, the
+        attention layer's weights and filter, the encoder side, the cell.  The caller brings what differs: `rows` device
+        rows, To steps, the step arrays (To deep to train and to decode greedily, one carried step for the beam), live, the
+        masks, alpha_zero, and `saved`, the depth of what only a backward reads (gates, raw cell state -- craw=False: none,
+        the GRU's training pass --, query).  peep: the caller's copy of self._peep()."""
+        st, U = self.store, self.decoder_num_units
+        A = self.key_dim                                     # width of keys / query (== U for the luong_* types)
+        T, _, E2 = enc_att.shape
+        has_q = self.attention_type in AL.HAS_QUERY_FC
+        f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=self.device)   # noqa: E731
+        return dict(To=To, B=rows, T=T, U=U, Em=self.embedding_dim, E2=E2, A=A, att_mode=self.att_mode,
+                    has_query_fc=int(has_q), carry_alpha=int(self.carry_alpha),
+                    taps=int(st[AT + 'filter'].shape[0]) if self.carry_alpha else 0,
+                    enc_dtype=ops.dtype_id(enc_att.dtype), forget_bias=1.0,
+                    cell_clip=float(self.clip_activation_decoder or 0.0), sharpening=float(self.sharpening_factor),
+                    W_q=self._wq() if has_q else None,
+                    b_q=st[AT + 'W_filter/biases'] if (has_q and self.attention_type in AL.HAS_FILTER) else None,
+                    v=st[AT + 'v_a'] if self.att_mode == 0 else None, keys=keys, enc=enc_att, seq_len=seq_len,
+                    filt=st[AT + 'filter'] if self.carry_alpha else None,
+                    wfil=st[AT + 'W_filter/weights'] if self.carry_alpha else None, alpha_zero=alpha_zero,
+                    live=live, dmask=dmask, dec_in=dec_in, av_in=av_in, alpha_all=alpha_all, snorm_all=snorm_all,
+                    gates_all=f32(saved, rows, 4 * U),                                           # (GRU: r | u | c | r*h)
+                    craw_all=f32(saved, rows, U) if craw else None, c_all=c_all, h_all=h_all, qz_all=f32(saved, rows, A),
+                    **self._cell_fields(self._peep() if peep is None else peep))
+
     def attention_layer(self, time_major_inputs=True):
         """The model's AttentionLayer (attention_seq2seq.py:413-430), bound to its variables."""
         return AttentionLayer(self.attention_type, self.attention_dim, self.parameter_init, self.sharpening_factor,
@@ -427,7 +454,6 @@ class AttentionSeq2Seq(ModelBase):
         dec_in = torch.empty((To, Bp, Din), dtype=torch.float32, device=dev)
         av_in = torch.empty((To, Bp, U + E2), dtype=torch.float32, device=dev)
         ctx = torch.zeros((Bp, E2), dtype=torch.float32, device=dev)
-        v = st[AT + 'v_a'] if self.att_mode == 0 else None
         alpha_all = torch.empty((To, Bp, T), dtype=torch.float32, device=dev)   # one slab: d_enc GEMMs read it strided
         use_ddrop = is_training and float(keep_prob_decoder) < 1.0
         if sample:         # the loop embeds what it feeds; row 0 is always the label's (<SOS>)
@@ -450,27 +476,14 @@ class AttentionSeq2Seq(ModelBase):
         dec_in[0, :, Em + E2:].copy_(h)
         # the To decoder steps (cell-input GEMM -> cell -> query FC -> energies -> softmax + context, each kernel writing
         # where the next one reads) are issued by ONE native call: a host loop over ~9 launches per step is host-bound
-        A = self.key_dim                                     # width of keys / query (== U for the luong_* types)
-        has_q = self.attention_type in AL.HAS_QUERY_FC
         gru = self.gru_decoder
         c_all = None if gru else torch.empty((To + 1, Bp, U), dtype=torch.float32, device=dev)
         h_all = torch.empty((To + 1, Bp, U), dtype=torch.float32, device=dev)
         if not gru:
             c_all[0].copy_(c)
         h_all[0].copy_(h)
-        loop = dict(To=To, B=Bp, T=T, U=U, Em=Em, E2=E2, A=A, att_mode=self.att_mode, has_query_fc=int(has_q),
-                    carry_alpha=int(self.carry_alpha), taps=int(st[AT + 'filter'].shape[0]) if self.carry_alpha else 0,
-                    enc_dtype=ops.dtype_id(enc_att.dtype), forget_bias=1.0,
-                    cell_clip=float(self.clip_activation_decoder or 0.0), sharpening=float(self.sharpening_factor),
-                    W_q=self._wq() if has_q else None,
-                    b_q=st[AT + 'W_filter/biases'] if (has_q and self.attention_type in AL.HAS_FILTER) else None,
-                    v=v, keys=keys, enc=enc_att, seq_len=seq_p,
-                    filt=st[AT + 'filter'] if self.carry_alpha else None,
-                    wfil=st[AT + 'W_filter/weights'] if self.carry_alpha else None, alpha_zero=alpha_zero,
-                    live=live_d, dmask=dmask_all, dec_in=dec_in, av_in=av_in, alpha_all=alpha_all, snorm_all=snorm_all,
-                    gates_all=torch.empty((To, Bp, 4 * U), dtype=torch.float32, device=dev),     # (GRU: r | u | c | r*h)
-                    craw_all=None if gru else torch.empty((To, Bp, U), dtype=torch.float32, device=dev), c_all=c_all,
-                    h_all=h_all, qz_all=torch.empty((To, Bp, A), dtype=torch.float32, device=dev), **self._cell_fields(peep))
+        loop = self._loop_dict(Bp, To, To, keys, enc_att, seq_p, alpha_zero, live_d, dmask_all, dec_in, av_in, alpha_all,
+                               snorm_all, c_all, h_all, craw=not gru, peep=peep)
         stack = self._stack_layers(self._init_up, To, To + 1, Bp, dev, To, dmask_up)
         if stack is not None:
             loop['stack'] = stack
@@ -754,11 +767,10 @@ class AttentionSeq2Seq(ModelBase):
         T, Bp, E2 = enc.shape
         cf, hf = self.encoder._final_ch
         _, c, h = self._bridge(cf, hf, B)
-        U, Em, A = self.decoder_num_units, self.embedding_dim, self.key_dim
+        U, Em = self.decoder_num_units, self.embedding_dim
         To, Din = int(self.max_decode_length), self.dec_in_dim
         keys = self._keys(enc)
         enc_att = self.encoder._out_op.contiguous() if self.dtype == ASR_BF16 else enc
-        has_q = self.attention_type in AL.HAS_QUERY_FC
         f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)          # noqa: E731
         dec_in = f32(To, Bp, Din)
         emb0 = ops.embedding_gather(st['output_embedding/W_embedding'],
@@ -772,20 +784,10 @@ class AttentionSeq2Seq(ModelBase):
         h_all[0].copy_(h)
         live = torch.zeros((To + 1, Bp), dtype=torch.float32, device=dev)
         live[0, :B] = 1.0                                    # rows B.. are the zero-length padding of the batch tile
-        loop = dict(To=To, B=Bp, T=T, U=U, Em=Em, E2=E2, A=A, att_mode=self.att_mode, has_query_fc=int(has_q),
-                    carry_alpha=int(self.carry_alpha), taps=int(st[AT + 'filter'].shape[0]) if self.carry_alpha else 0,
-                    enc_dtype=ops.dtype_id(enc_att.dtype), forget_bias=1.0,
-                    cell_clip=float(self.clip_activation_decoder or 0.0), sharpening=float(self.sharpening_factor),
-                    W_q=self._wq() if has_q else None,
-                    b_q=st[AT + 'W_filter/biases'] if (has_q and self.attention_type in AL.HAS_FILTER) else None,
-                    v=st[AT + 'v_a'] if self.att_mode == 0 else None, keys=keys, enc=enc_att, seq_len=seq_p,
-                    filt=st[AT + 'filter'] if self.carry_alpha else None,
-                    wfil=st[AT + 'W_filter/weights'] if self.carry_alpha else None,
-                    alpha_zero=torch.zeros((Bp, T), dtype=torch.float32, device=dev) if self.carry_alpha else None,
-                    live=live, dmask=None, dec_in=dec_in, av_in=f32(To, Bp, U + E2), alpha_all=f32(To, Bp, T),
-                    snorm_all=f32(To, Bp) if self.sigmoid_smoothing else None,
-                    gates_all=f32(1, Bp, 4 * U), craw_all=f32(1, Bp, U), c_all=c_all, h_all=h_all, qz_all=f32(1, Bp, A),
-                    **self._cell_fields(self._peep()))
+        loop = self._loop_dict(Bp, To, 1, keys, enc_att, seq_p,
+                               torch.zeros((Bp, T), dtype=torch.float32, device=dev) if self.carry_alpha else None,
+                               live, None, dec_in, f32(To, Bp, U + E2), f32(To, Bp, T),
+                               f32(To, Bp) if self.sigmoid_smoothing else None, c_all, h_all)
         stack = self._stack_layers(self._init_up, To, To + 1, Bp, dev, 1)
         if stack is not None:
             loop['stack'] = stack
@@ -852,14 +854,13 @@ class AttentionSeq2Seq(ModelBase):
         T, Bp, E2 = enc.shape
         cf, hf = self.encoder._final_ch
         _, c, h = self._bridge(cf, hf, B)
-        U, Em, A = self.decoder_num_units, self.embedding_dim, self.key_dim
+        U, Em = self.decoder_num_units, self.embedding_dim
         To, Din = int(self.max_decode_length), self.dec_in_dim
         R = B * W
         rows = torch.arange(B, device=dev).repeat_interleave(W)          # device row b*W + w reads utterance b
         keys = self._keys(enc)
         keys = keys.index_select(1, rows).contiguous() if keys is not None else None
         enc_att = (self.encoder._out_op if self.dtype == ASR_BF16 else enc).index_select(1, rows).contiguous()
-        has_q = self.attention_type in AL.HAS_QUERY_FC
         f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)          # noqa: E731
         dec_in = f32(2, R, Din)
         emb0 = ops.embedding_gather(st['output_embedding/W_embedding'],
@@ -874,21 +875,9 @@ class AttentionSeq2Seq(ModelBase):
         else:                                 # GRU decoder: no cell state; the re-ordering gathers a block of zeros
             c_all.zero_()
         h_all[0].copy_(h0)
-        loop = dict(To=To, B=R, T=T, U=U, Em=Em, E2=E2, A=A, att_mode=self.att_mode, has_query_fc=int(has_q),
-                    carry_alpha=int(self.carry_alpha), taps=int(st[AT + 'filter'].shape[0]) if self.carry_alpha else 0,
-                    enc_dtype=ops.dtype_id(enc_att.dtype), forget_bias=1.0,
-                    cell_clip=float(self.clip_activation_decoder or 0.0), sharpening=float(self.sharpening_factor),
-                    W_q=self._wq() if has_q else None,
-                    b_q=st[AT + 'W_filter/biases'] if (has_q and self.attention_type in AL.HAS_FILTER) else None,
-                    v=st[AT + 'v_a'] if self.att_mode == 0 else None, keys=keys, enc=enc_att,
-                    seq_len=seq_p.index_select(0, rows).contiguous(),
-                    filt=st[AT + 'filter'] if self.carry_alpha else None,
-                    wfil=st[AT + 'W_filter/weights'] if self.carry_alpha else None, alpha_zero=None,
-                    live=torch.ones((R,), dtype=torch.float32, device=dev), dmask=None, dec_in=dec_in,
-                    av_in=f32(1, R, U + E2), alpha_all=f32(1, R, T),
-                    snorm_all=f32(1, R) if self.sigmoid_smoothing else None,
-                    gates_all=f32(1, R, 4 * U), craw_all=f32(1, R, U), c_all=c_all, h_all=h_all, qz_all=f32(1, R, A),
-                    **self._cell_fields(self._peep()))
+        loop = self._loop_dict(R, To, 1, keys, enc_att, seq_p.index_select(0, rows).contiguous(), None,
+                               torch.ones((R,), dtype=torch.float32, device=dev), None, dec_in, f32(1, R, U + E2),
+                               f32(1, R, T), f32(1, R) if self.sigmoid_smoothing else None, c_all, h_all)
         stack = self._stack_layers(self._init_up, 2, 2, R, dev, 1, rows=rows)
         if stack is not None:
             loop['stack'] = stack

@@ -2173,23 +2173,31 @@ def _cell_gemm_image(h, a):
         a['W_cell_il'] = _f32(((Din + 1) * 4 * a['U'],), a['dec_in'].device)
 
 
+def _dec_work_floats(a, bwd):
+    """Floats of a loop's work space (forward: pre-activations, raw h, energies, context; backward: 2 x dc, dh, d-alpha)."""
+    return a['B'] * (5 * a['U'] + (3 if bwd else 1) * a['T'] + a['E2'])
+
+
+def _dec_loop_call(h, base_name, a, st, *extra, bwd=False):
+    """Call loop entry point `base_name` for the cell of `a`: + '_gru' with the GRU block, + '_stack' with the upper layers'
+    block, else as it is.  st: the filled asr_att_decoder; extra: the arguments between the cell block and the stream."""
+    if a.get('gru') is not None:
+        name, blocks = base_name + '_gru', (C.byref(st), C.byref(_att_gru_struct(a)))
+    elif a.get('stack') is not None:
+        name, blocks = base_name + '_stack', (C.byref(st), C.byref(_att_stack_struct(a, bwd=bwd)))
+    else:
+        name, blocks = base_name, (C.byref(st),)
+    h.check(getattr(h.lib, name)(h.h, *blocks, *extra, _s()), name)
+
+
 def att_decoder_fwd(a):
     """All To steps of the attention decoder's forward pass from one call (asr_att_decoder_fwd).  `a`: dict of the
     struct's fields (ints / floats / cuda tensors or None); the per-step arrays are filled in place."""
     h = _h(a['dec_in'])
     if a.get('work') is None:
-        a['work'] = _f32((a['B'] * (5 * a['U'] + a['T'] + a['E2']),), a['dec_in'].device)
+        a['work'] = _f32((_dec_work_floats(a, False),), a['dec_in'].device)
     _cell_gemm_image(h, a)
-    st = _att_decoder_struct(a)
-    if a.get('gru') is not None:          # decoder_type 'gru': the same loop around the GRU cell's launches
-        g = _att_gru_struct(a)
-        h.check(h.lib.asr_att_decoder_fwd_gru(h.h, C.byref(st), C.byref(g), _s()), 'asr_att_decoder_fwd_gru')
-        return
-    if a.get('stack') is not None:        # decoder_num_layers > 1: the same loop with the upper layers' cell launches
-        k = _att_stack_struct(a)
-        h.check(h.lib.asr_att_decoder_fwd_stack(h.h, C.byref(st), C.byref(k), _s()), 'asr_att_decoder_fwd_stack')
-        return
-    h.check(h.lib.asr_att_decoder_fwd(h.h, C.byref(st), _s()), 'asr_att_decoder_fwd')
+    _dec_loop_call(h, 'asr_att_decoder_fwd', a, _att_decoder_struct(a))
 
 
 class _AttDecoderSS(C.Structure):
@@ -2218,7 +2226,7 @@ def att_decoder_fwd_ss(a, W_av, W_out, b_out, embedding, teacher_ids, draw, emb_
             (b_out is not None and tuple(b_out.shape) != (C2,)):
         raise ValueError('att_decoder_fwd_ss: W_av [U+E2,U], W_out [U,C2], b_out [C2], embedding [C2,Em]')
     if a.get('work') is None:
-        a['work'] = _f32((B * (5 * U + a['T'] + a['E2']),), dev)
+        a['work'] = _f32((_dec_work_floats(a, False),), dev)
     _cell_gemm_image(h, a)
     if out is not None:
         av, logits, ids_fed = out
@@ -2247,18 +2255,11 @@ def att_decoder_bwd(a):
     """The reverse loop (asr_att_decoder_bwd): fills dctx_all, dpre_all, dqz_all, dv_all, dpeep_all, d_in_all, dc0, dh0
     (and adds into dkeys / the filter gradients)."""
     h = _h(a['dec_in'])
-    a['work'] = _f32((a['B'] * (5 * a['U'] + 3 * a['T'] + a['E2']),), a['dec_in'].device)
+    a['work'] = _f32((_dec_work_floats(a, True),), a['dec_in'].device)
     _cell_gemm_image(h, a)
-    st = _att_decoder_struct(a)
-    if a.get('gru') is not None:          # dpre_all is [To,B,3U] = dr | du | dp there, dc0 is not written
-        g = _att_gru_struct(a)
-        h.check(h.lib.asr_att_decoder_bwd_gru(h.h, C.byref(st), C.byref(g), _s()), 'asr_att_decoder_bwd_gru')
-        return
-    if a.get('stack') is not None:        # the upper layers' dpre / d_hin / dpeep / dc0 / dh0 are in the stack block
-        k = _att_stack_struct(a, bwd=True)
-        h.check(h.lib.asr_att_decoder_bwd_stack(h.h, C.byref(st), C.byref(k), _s()), 'asr_att_decoder_bwd_stack')
-        return
-    h.check(h.lib.asr_att_decoder_bwd(h.h, C.byref(st), _s()), 'asr_att_decoder_bwd')
+    # (GRU: dpre_all is [To,B,3U] = dr | du | dp and dc0 is not written; stack: the upper layers' dpre / d_hin / dpeep /
+    # dc0 / dh0 are in the stack block)
+    _dec_loop_call(h, 'asr_att_decoder_bwd', a, _att_decoder_struct(a), bwd=True)
 
 
 class _AttInfer(C.Structure):
@@ -2266,6 +2267,20 @@ class _AttInfer(C.Structure):
     _fields_ = [('W_av', C.c_void_p), ('W_out', C.c_void_p), ('b_out', C.c_void_p), ('embedding', C.c_void_p),
                 ('C2', C.c_int), ('eos', C.c_int), ('live', C.c_void_p), ('av_all', C.c_void_p), ('logits_all', C.c_void_p),
                 ('ids_all', C.c_void_p), ('live_count', C.c_void_p), ('host_live_count', C.c_void_p), ('check_every', C.c_int)]
+
+
+def _att_infer_struct(what, To, C2, eos, check_every, **tensors):
+    """struct asr_att_infer for a decode loop of at most To steps, with the pinned words its early exit reads (None with
+    check_every 0; the caller keeps them alive until it has synchronised)."""
+    host = torch.ones((To + 1,), dtype=torch.int32).pin_memory() if check_every else None
+    f = _AttInfer()
+    for n, t in tensors.items():
+        if t is not None and (not t.is_cuda or not t.is_contiguous()):
+            raise ValueError('%s: %s must be a contiguous device tensor' % (what, n))
+        setattr(f, n, t.data_ptr() if t is not None else None)
+    f.C2, f.eos, f.check_every = int(C2), int(eos), int(check_every or 0)
+    f.host_live_count = host.data_ptr() if host is not None else None
+    return f, host
 
 
 def att_decoder_infer(a, W_av, W_out, b_out, embedding, eos, n_live, check_every=8):
@@ -2278,32 +2293,17 @@ def att_decoder_infer(a, W_av, W_out, b_out, embedding, eos, n_live, check_every
     To, B, U = a['To'], a['B'], a['U']
     C2 = W_out.shape[1]
     if a.get('work') is None:
-        a['work'] = _f32((B * (5 * U + a['T'] + a['E2']),), dev)
+        a['work'] = _f32((_dec_work_floats(a, False),), dev)
     _cell_gemm_image(h, a)
     out = dict(ids=torch.empty((To, B), dtype=torch.int32, device=dev), logits=_f32((To, B, C2), dev), av=_f32((To, B, U), dev),
                live=a['live'], live_count=torch.empty((To + 1,), dtype=torch.int32, device=dev))
     out['live_count'][:1].fill_(int(n_live))
-    host = torch.ones((To + 1,), dtype=torch.int32).pin_memory() if check_every else None
     st = _att_decoder_struct(a)
-    f = _AttInfer()
-    for n, t in (('W_av', W_av), ('W_out', W_out), ('b_out', b_out), ('embedding', embedding), ('live', a['live']),
-                 ('av_all', out['av']), ('logits_all', out['logits']), ('ids_all', out['ids']), ('live_count', out['live_count'])):
-        if t is not None and (not t.is_cuda or not t.is_contiguous()):
-            raise ValueError('att_decoder_infer: %s must be a contiguous device tensor' % n)
-        setattr(f, n, t.data_ptr() if t is not None else None)
-    f.C2, f.eos, f.check_every = int(C2), int(eos), int(check_every or 0)
-    f.host_live_count = host.data_ptr() if host is not None else None
+    f, host = _att_infer_struct('att_decoder_infer', To, C2, eos, check_every, W_av=W_av, W_out=W_out, b_out=b_out,
+                                embedding=embedding, live=a['live'], av_all=out['av'], logits_all=out['logits'],
+                                ids_all=out['ids'], live_count=out['live_count'])
     issued = C.c_int(0)
-    if a.get('gru') is not None:
-        g = _att_gru_struct(a)
-        h.check(h.lib.asr_att_decoder_infer_gru(h.h, C.byref(st), C.byref(g), C.byref(f), C.byref(issued), _s()),
-                'asr_att_decoder_infer_gru')
-    elif a.get('stack') is not None:
-        k = _att_stack_struct(a)
-        h.check(h.lib.asr_att_decoder_infer_stack(h.h, C.byref(st), C.byref(k), C.byref(f), C.byref(issued), _s()),
-                'asr_att_decoder_infer_stack')
-    else:
-        h.check(h.lib.asr_att_decoder_infer(h.h, C.byref(st), C.byref(f), C.byref(issued), _s()), 'asr_att_decoder_infer')
+    _dec_loop_call(h, 'asr_att_decoder_infer', a, st, C.byref(f), C.byref(issued))
     out['steps_issued'] = issued.value
     out['_host'] = host                      # keeps the pinned words alive until the caller has synchronised
     return out
@@ -2408,7 +2408,7 @@ def _beam_loop_call(what, a, W_av, W_out, b_out, embedding, eos, W, length_penal
         raise ValueError('%s: %d rows are not a multiple of beam_width %d' % (what, R, W))
     B = R // W
     if a.get('work') is None:
-        a['work'] = _f32((R * (5 * U + a['T'] + a['E2']),), dev)
+        a['work'] = _f32((_dec_work_floats(a, False),), dev)
     _cell_gemm_image(h, a)
     out = dict(word=_i32((To, B, W), dev), parent=_i32((To, B, W), dev), score=_f32((To, B, W), dev),
                log_probs=torch.zeros((B, W), dtype=torch.float32, device=dev),
@@ -2421,15 +2421,8 @@ def _beam_loop_call(what, a, W_av, W_out, b_out, embedding, eos, W, length_penal
     scratch.update(extra_scratch or {})
     if a.get('carry_alpha') and a.get('alpha_zero') is None:
         a['alpha_zero'] = scratch['alpha_prev']
-    host = torch.ones((To + 1,), dtype=torch.int32).pin_memory() if check_every else None
     st = _att_decoder_struct(a)
-    f = _AttInfer()
-    for n, t in (('W_av', W_av), ('W_out', W_out), ('b_out', b_out), ('embedding', embedding)):
-        if t is not None and (not t.is_cuda or not t.is_contiguous()):
-            raise ValueError('%s: %s must be a contiguous device tensor' % (what, n))
-        setattr(f, n, t.data_ptr() if t is not None else None)
-    f.C2, f.eos, f.check_every = int(C2), int(eos), int(check_every or 0)
-    f.host_live_count = host.data_ptr() if host is not None else None
+    f, host = _att_infer_struct(what, To, C2, eos, check_every, W_av=W_av, W_out=W_out, b_out=b_out, embedding=embedding)
     m = _AttBeam()
     m.W = W
     m.length_penalty_weight = 0.0 if length_penalty_weight is None else float(length_penalty_weight)
@@ -2458,17 +2451,9 @@ def att_decoder_beam(a, W_av, W_out, b_out, embedding, eos, beam_width, length_p
     h, st, f, m, out, scratch, host = _beam_loop_call('att_decoder_beam', a, W_av, W_out, b_out, embedding, eos, W,
                                                       length_penalty_weight, check_every)
     issued = C.c_int(0)
-    if a.get('gru') is not None:          # (c_all: zeros [2,R,U], gathered by the re-ordering as ever)
-        g = _att_gru_struct(a)
-        h.check(h.lib.asr_att_decoder_beam_gru(h.h, C.byref(st), C.byref(g), C.byref(f), C.byref(m), C.byref(issued), _s()),
-                'asr_att_decoder_beam_gru')
-    elif a.get('stack') is not None:      # (upper layers: in [2,R,2U], c / h [2,R,U], re-ordered by asr_att_stack_reorder)
-        k = _att_stack_struct(a)
-        h.check(h.lib.asr_att_decoder_beam_stack(h.h, C.byref(st), C.byref(k), C.byref(f), C.byref(m), C.byref(issued), _s()),
-                'asr_att_decoder_beam_stack')
-    else:
-        h.check(h.lib.asr_att_decoder_beam(h.h, C.byref(st), C.byref(f), C.byref(m), C.byref(issued), _s()),
-                'asr_att_decoder_beam')
+    # (GRU: c_all is zeros [2,R,U], gathered by the re-ordering as ever; stack: the upper layers' in [2,R,2U] and c / h
+    # [2,R,U] are re-ordered by asr_att_stack_reorder)
+    _dec_loop_call(h, 'asr_att_decoder_beam', a, st, C.byref(f), C.byref(m), C.byref(issued))
     return _beam_loop_done(out, issued, host, scratch)
 
 

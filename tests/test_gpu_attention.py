@@ -882,6 +882,78 @@ def test_native_inference_loop_at_the_fused_cell_widths(cuda, cell_bf16):
     assert ops.check_async_errors(0) == 0
 
 
+def test_first_maximum_of_tied_logits_in_the_loops_and_argmax_rows(cuda):
+    """The one first-maximum argmax behind asr_argmax_rows, the greedy loop's selection and the scheduled-sampling loop's:
+    on logits that tie EXACTLY at the row maximum, all three give numpy's answer (the first index) on the very logits the
+    loops returned -- no tolerance.  C2 = 300 > 256, so a thread of the 256-wide scan meets a second column (261 = 5 + 256).
+    Row 0 ties at columns 5, 70 and 261 (-> 5), row 1 at 261 and 299 (-> 261), row 2 has its maximum at 261 alone.
+    How the ties come about: columns 5 and 70 of the output layer are duplicates, 261 and 299 differ from them (and from
+    each other) only in the weights of the attentional units 0 and 1, and those units are exactly 0 for row 0 / row 1:
+    their only input is a context column in which that row's encoder frames are zero, tanh(0) = 0, and a product with an
+    exact zero adds nothing to a column's sum.  (Four identical columns would tie in every row alike and could not tell
+    the rows apart.)  The ties are asserted before anything is concluded from them.  <EOS> is none of these columns and
+    far below them, so every row stays live for all four steps."""
+    from tensorflow_end2end_speech_recognition_amd import ops
+    rng = np.random.RandomState(11)
+    B, T, U, E2, Em, A, To, C2 = 3, 8, 16, 16, 8, 16, 4, 300
+    Din, eos = Em + E2 + U, 298
+    f = lambda *s, sc=1.0: torch.tensor(rng.randn(*s) * sc, dtype=torch.float32)
+    seq_len = torch.tensor([8, 5, 1], dtype=torch.int32)
+    enc = f(T, B, E2, sc=0.5)
+    enc[:, :, 0] = torch.tensor([0.0, 1.0, 1.0])             # row 0: context column 0 is zero -> attentional unit 0 is
+    enc[:, :, 1] = torch.tensor([1.0, 0.0, 1.0])             # row 1: context column 1                  -> unit 1
+    enc[:, :, 2] = 1.0                                       # every row: unit 2 is tanh(2 x 1), the tied columns' lead
+    enc = enc * (torch.arange(T).view(T, 1, 1) < seq_len.view(1, B, 1))
+    W_av = f(U + E2, U, sc=0.15)
+    W_av[:, :3] = 0.0
+    W_av[U, 0] = W_av[U + 1, 1] = W_av[U + 2, 2] = 2.0
+    W_out, b_out = f(U, C2, sc=0.05), f(C2, sc=0.05)
+    for col, (x, y) in {5: (0.0, 1.0), 70: (0.0, 1.0), 261: (1.0, 1.0), 299: (1.0, 0.0)}.items():
+        W_out[:, col] = W_out[:, 5]
+        W_out[0, col], W_out[1, col], W_out[2, col] = x, y, 5.0
+        b_out[col] = b_out[5]
+    b_out[eos] = -10.0
+    emb = f(C2, Em, sc=0.5)
+
+    def loop_dict(n_live_rows):
+        a = dict(To=To, B=B, T=T, U=U, Em=Em, E2=E2, A=A, att_mode=0, has_query_fc=1, carry_alpha=0, taps=0, enc_dtype=0,
+                 forget_bias=1.0, cell_clip=3.0, sharpening=1.5, W_cell=f(Din, 4 * U, sc=0.08), b_cell=f(4 * U, sc=0.1),
+                 peep=f(3, U, sc=0.1), W_q=f(U, A, sc=0.1), v=f(A, sc=0.5), keys=f(T, B, A, sc=0.5), enc=enc, seq_len=seq_len,
+                 live=torch.ones(n_live_rows, B), dec_in=torch.zeros(To, B, Din), av_in=torch.zeros(To, B, U + E2),
+                 alpha_all=torch.zeros(To, B, T), gates_all=torch.zeros(To, B, 4 * U), craw_all=torch.zeros(To, B, U),
+                 c_all=torch.zeros(To + 1, B, U), h_all=torch.zeros(To + 1, B, U), qz_all=torch.zeros(To, B, A))
+        a['c_all'][0], a['h_all'][0] = f(B, U, sc=0.3), f(B, U, sc=0.3)
+        a['dec_in'][0, :, :Em] = emb[7]
+        a['dec_in'][0, :, Em + E2:] = a['h_all'][0]
+        return {k: (v.to(cuda) if torch.is_tensor(v) else v) for k, v in a.items()}
+
+    def first_maxima(logits):
+        """numpy's argmax of the loop's own logits [To,B,C2], after checking that the ties are there."""
+        lg = logits.cpu().numpy()
+        for k in range(To):
+            top = lg[k].max(axis=1)
+            assert [sorted(np.flatnonzero(lg[k, b] == top[b]).tolist()) for b in range(B)] == [[5, 70, 261], [261, 299], [261]]
+        want = lg.argmax(axis=2)
+        assert (want == np.array([5, 261, 261])).all()
+        assert np.array_equal(ops.argmax_rows(logits.view(To * B, C2)).cpu().numpy().reshape(To, B), want)
+        return want
+
+    head = [t.to(cuda) for t in (W_av, W_out, b_out, emb)]
+    a = loop_dict(To + 1)
+    a['live'][1:] = 0.0                                      # (the loop writes rows 1 ..)
+    got = ops.att_decoder_infer(a, *head, eos, B, check_every=0)
+    torch.cuda.synchronize()
+    want = first_maxima(got['logits'])
+    assert bool((got['live'][:To] == 1.0).all()) and got['steps_issued'] == To
+    assert np.array_equal(got['ids'].cpu().numpy(), want)
+    teacher = torch.full((To, B), 7, dtype=torch.int32, device=cuda)
+    _, logits, ids_fed = ops.att_decoder_fwd_ss(loop_dict(To), *head, teacher, torch.ones(To, B, device=cuda), None)
+    torch.cuda.synchronize()
+    want = first_maxima(logits)
+    assert np.array_equal(ids_fed.cpu().numpy()[1:], want[:To - 1])
+    assert ops.check_async_errors(0) == 0
+
+
 @pytest.mark.parametrize('att,prev,sig', [('bahdanau_content', 'zeros', False), ('location', 'carry', False),
                                           ('hybrid', 'carry', True), ('luong_dot', 'zeros', False),
                                           ('luong_concat', 'zeros', False)])

@@ -1,5 +1,5 @@
-"""GPU: scheduled sampling and label smoothing for the attention decoder (csrc/attention.hip: asr_att_decoder_fwd_ss with
-att_ss_select_kernel, asr_seq_xent_ls) -- the selection rule at the kernel's edges, the loop against asr_att_decoder_fwd
+"""GPU: scheduled sampling and label smoothing for the attention decoder (csrc/dec_loop.hip: asr_att_decoder_fwd_ss with
+att_ss_select_kernel; csrc/attention.hip: asr_seq_xent_ls) -- the selection rule at the kernel's edges, the loop against asr_att_decoder_fwd
 (no draw set) and asr_att_decoder_infer (every draw set), the models against the float64 statement of the whole loss
 (tests/_cpu_ops_att_ss.py), the draws, the smoothed cross-entropy against float64, and repeatability.
 
