@@ -550,6 +550,31 @@ int asr_reset_recurrence_path_counts(asr_handle* h);
  * they are: both single-CU forms count there as one single-CU call. */
 int asr_gru_kernel_counts(asr_handle* h, unsigned long long* out6);
 int asr_reset_gru_kernel_counts(asr_handle* h);
+/* The same for the LSTM recurrence: the form each asr_lstm_fwd / asr_lstm_bwd(_ex) call on this handle ended in since the
+ * last reset.  One counter is bumped per call where the form is chosen (a call that runs as several tile groups counts
+ * once); out[i], i < min(n, ASR_LSTM_KERNEL_N), in the order of the enum below, the rest of `out` zeroed.  The template
+ * choices inside a form (EARLY, exchange word format, slot layout, CLIPZ, write-through) are not counted: the flags of
+ * asr_debug_set_lstm_flags set them directly.  asr_recurrence_path_counts is left as it is. */
+enum {
+  ASR_LSTM_FWD_BF16_CU16 = 0,     /* bf16, H = 256 on clusters of 16 CUs (lstm_fwd_cluster16_kernel) */
+  ASR_LSTM_FWD_BF16_HS32,         /* bf16 clusters, 32 units per CU (H = 256, 512) */
+  ASR_LSTM_FWD_BF16_HS64,         /* bf16 clusters, 64 units per CU (H = 256, 320, 512) */
+  ASR_LSTM_FWD_F32_SPLIT,         /* fp32 as three bf16 terms, 32 units per CU (lstm_fwd_cluster_f32s_kernel; H = 128, 256) */
+  ASR_LSTM_FWD_F32_HS32,          /* exact fp32 clusters, 32 units per CU (H = 128, 256, 320, 512) */
+  ASR_LSTM_FWD_F32_HS64,          /* exact fp32 clusters, 64 units per CU (H = 128) */
+  ASR_LSTM_FWD_SINGLE_BF16,       /* lstm_fwd_kernel<bf16>, one CU per (direction, tile) */
+  ASR_LSTM_FWD_SINGLE_F32,        /* lstm_fwd_kernel<float> */
+  ASR_LSTM_BWD_BF16_HS32,         /* bf16 BPTT clusters, 32 units per CU (H = 256, 512) */
+  ASR_LSTM_BWD_BF16_HS64,         /* bf16 BPTT clusters, 64 units per CU (H = 256, 320, 512) */
+  ASR_LSTM_BWD_F32_SPLIT,         /* lstm_bwd_cluster_f32s_kernel (H = 128, 256) */
+  ASR_LSTM_BWD_F32_HS32,          /* lstm_bwd_cluster_f32_kernel, 32 units per CU (H = 128, 256, 320, 512) */
+  ASR_LSTM_BWD_F32_HS64,          /* lstm_bwd_cluster8_f32_kernel, 64 units per CU (H = 128) */
+  ASR_LSTM_BWD_SINGLE_BF16,       /* lstm_bwd_kernel<bf16> */
+  ASR_LSTM_BWD_SINGLE_F32,        /* lstm_bwd_kernel<float> */
+  ASR_LSTM_KERNEL_N
+};
+int asr_lstm_kernel_counts(asr_handle* h, unsigned long long* out, int n);
+int asr_reset_lstm_kernel_counts(asr_handle* h);
 /* Which kernels the attention decoder calls on this handle launched since the last reset (host integers bumped at
  * launch time like the recurrence counters above: no device work, no synchronisation, no effect on any launch).
  * out[i], i < min(n, ASR_ATT_PATH_N), in the order of the enum below; entries of `out` past ASR_ATT_PATH_N are zeroed.

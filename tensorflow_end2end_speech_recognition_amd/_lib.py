@@ -105,6 +105,8 @@ SIGNATURES = {
     'asr_reset_recurrence_path_counts': (_i, [_vp]),
     'asr_gru_kernel_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
     'asr_reset_gru_kernel_counts': (_i, [_vp]),
+    'asr_lstm_kernel_counts': (_i, [_vp, C.POINTER(C.c_ulonglong), _i]),
+    'asr_reset_lstm_kernel_counts': (_i, [_vp]),
     'asr_att_path_counts': (_i, [_vp, C.POINTER(C.c_ulonglong), _i]),
     'asr_reset_att_path_counts': (_i, [_vp]),
     'asr_conv_path_counts': (_i, [_vp, C.POINTER(C.c_ulonglong), _i]),

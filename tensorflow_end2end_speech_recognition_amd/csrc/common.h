@@ -32,6 +32,9 @@ struct asr_handle {
   // asr_gru_fwd / asr_gru_bwd calls since the last asr_reset_gru_kernel_counts by the form they ended in:
   // {fwd cluster, fwd persistent, fwd per step, bwd cluster, bwd persistent, bwd per step}
   unsigned long long gru_counts[6];
+  // asr_lstm_fwd / asr_lstm_bwd(_ex) calls since the last asr_reset_lstm_kernel_counts by the form they ended in, indexed by
+  // the ASR_LSTM_* enum of asr_hip.h (bumped where the form is chosen: lstm_cluster.hip for the clusters, lstm.hip else)
+  unsigned long long lstm_counts[ASR_LSTM_KERNEL_N];
   // attention-decoder launches since the last asr_reset_att_path_counts, indexed by the ASR_ATT_* enum of asr_hip.h
   unsigned long long att_counts[ASR_ATT_PATH_N];
   // beam search launches since the last asr_reset_att_beam_counts: {select, reorder, backtrace}

@@ -18,6 +18,7 @@
 // still 5 (additive): asr_time_subsample_fwd / asr_time_subsample_bwd (subsample.hip).
 // still 5 (additive): asr_residual_fwd / asr_residual_bwd (residual.hip).
 // still 5 (additive): asr_gru_kernel_counts / asr_reset_gru_kernel_counts (the form a GRU recurrence call ended in).
+// still 5 (additive): asr_lstm_kernel_counts / asr_reset_lstm_kernel_counts (the same for the LSTM recurrence, fifteen forms).
 extern "C" int asr_abi_version(void) { return 5; }
 
 extern "C" int asr_create(asr_handle** out, int device) { return asr_create_ex(out, device, (size_t)192 << 20); }

@@ -887,7 +887,9 @@ extern "C" int asr_lstm_fwd(asr_handle* h, int dtype, int T, int B, int H, int n
     ASR_FAIL(h, ASR_ERR_UNSUPPORTED, "asr_lstm_fwd: T*B*ndir*H exceeds 32-bit element offsets");
   if (T == 0) return ASR_OK;
   hipStream_t st = (hipStream_t)s;
-  // multi-CU form (W_h slices LDS-resident, per-step h all-gather between 4 CUs): lstm_cluster.hip
+  // multi-CU forms (W_h slices resident per CU, per-step h all-gather inside a cluster): lstm_cluster.hip.  bf16: H = 256
+  // (16 / 8 / 4 CUs), 320 (5), 512 (16 / 8); fp32: H = 128, 256, 320, 512 on H/32 CUs, 128 also on 2.  Every other width,
+  // and any shape no cluster form has the CUs or the exchange area for, runs on the single-CU kernels below.
   if (dtype == ASR_BF16 && asr_cluster_fwd_try(h, T, B, H, ndir, xproj, wh_packed, peep, seq_len, forget_bias,
                                                cell_clip, gates, hout, cs, c_final, h_final, st)) {
     ASR_CHECK_LAUNCH(h, "asr_lstm_fwd(cluster)");
@@ -906,6 +908,7 @@ extern "C" int asr_lstm_fwd(asr_handle* h, int dtype, int T, int B, int H, int n
                                                  cell_clip, gates, hout, cs, c_final, h_final, st)));
   }
   h->rec_counts[1] += 1;   // single-CU path (asr_recurrence_path_counts)
+  h->lstm_counts[dtype == ASR_F32 ? ASR_LSTM_FWD_SINGLE_F32 : ASR_LSTM_FWD_SINGLE_BF16] += 1;   // asr_lstm_kernel_counts
   ASR_CHECK_LAUNCH(h, "asr_lstm_fwd");
   return ASR_OK;
 }
@@ -946,7 +949,10 @@ static int lstm_bwd_impl(asr_handle* h, int dtype, int T, int B, int H, int ndir
     ASR_H_DISPATCH(H, T, (launch_bwd<bf16_t, HH>(T, B, ndir, dhout, gates, cs, wh_packed_bwd, peep, seq_len,
                                                  d_c_final, d_h_final, dgates, part, clipz, st)));
   }
-  if (!launched) h->rec_counts[1] += 1;   // single-CU path (asr_recurrence_path_counts)
+  if (!launched) {
+    h->rec_counts[1] += 1;   // single-CU path (asr_recurrence_path_counts)
+    h->lstm_counts[dtype == ASR_F32 ? ASR_LSTM_BWD_SINGLE_F32 : ASR_LSTM_BWD_SINGLE_BF16] += 1;   // asr_lstm_kernel_counts
+  }
   ASR_CHECK_LAUNCH(h, "asr_lstm_bwd");
   if (dpeep && !single_tile) {
     const int n = ndir * 7 * H;

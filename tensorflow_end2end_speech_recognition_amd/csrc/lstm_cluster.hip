@@ -173,7 +173,9 @@ __device__ __forceinline__ float dpp_ror8_into(float old, float src) {
 // exchange-buffer parity is a compile-time constant (loop unrolled by two), every address is an
 // incrementally advanced register, the phase timers (DBG) are a template parameter, nothing in
 // the loop is exec-masked.
-// EARLY (default at H = 256; ASR_LSTM_DFLAGS bit 5 inverts the default): the k-chunks of this CU's OWN slice of h -- which
+// Served widths (asr_cluster_fwd_try): HSU = 64 at H = 256, 320, 512 (H = 320 has no other form), HSU = 32 at H = 256, 512.
+// EARLY (default at H = 256, H = 320 and wherever HSU = 32, i.e. everywhere but H = 512 on 64 units per CU;
+// ASR_LSTM_DFLAGS bit 5 inverts the default): the k-chunks of this CU's OWN slice of h -- which
 // never leave the CU -- are multiplied for step s+1 right after they are written, i.e. before the wave starts polling
 // for the peers' slices, so that part of the LDS-read + MFMA phase runs under the L2 hop.  The chunk order in the
 // registers is rotated by the CU index so that the own chunks are always register chunks 0 .. KO-1.
@@ -1395,7 +1397,12 @@ __global__ __launch_bounds__(HSU * 8, 1) void lstm_bwd_cluster8_kernel(
   }
 }
 
-// ---------------------------------------------------------------- fp32 operands (exact fp32 MFMA path), H = 128
+// ---------------------------------------------------------------- fp32 operands (exact fp32 MFMA path)
+// (Written for H = 128 on two CUs, as told below.  Served today, cluster_fwd_f32_attempt / cluster_bwd_f32_attempt: the
+// forward kernel at 32 units per CU for H = 128, 256, 320, 512 -- at 128 and 256 only when the three-term split is off or
+// T >= 65536 -- and at 64 units per CU for H = 128 alone; the BPTT of 64 units per CU, lstm_bwd_cluster8_f32_kernel, for
+// H = 128 alone; lstm_bwd_cluster_f32_kernel at 32 units per CU for all four widths.  With 64 units per CU requested
+// (ASR_LSTM_HS=64 / flag bit 9) the fp32 widths above 128 have no cluster form and run on the single-CU kernels.)
 // BASELINE configs[0] (2 x 128 BLSTM-CTC, fp32) ran on the single-CU kernels of lstm.hip at 5.1 / 6.7 us per
 // recurrence step: with fp32 operands the step is bound by the CU's fp32 matrix rate (v_mfma_f32_16x16x4_f32:
 // 256 flop/clk/CU; h W_h of one step = 2.1 Mflop = 8.2 k cycles), not by streaming W_h.  The same cluster scheme
@@ -3328,7 +3335,8 @@ static int g_dflags = -1;
 // bit 5 (32): invert the default choice of the EARLY forward variant (A/B measurements)
 // bit 7 (128): BPTT kernel requests the next iteration's saved activations ahead of the poll loop (the old place; A/B)
 // bit 8 (256): fp32 BPTT kernel without the priority of the published tile's MFMAs (A/B)
-// bit 9 (512): H = 256 / 512 clusters of H/64 CUs x eight waves instead of H/32 CUs x four waves
+// bit 9 (512): clusters of H/64 CUs x eight waves instead of H/32 CUs x four waves: bf16 H = 256 / 512 (H = 320 has only
+//              that form), fp32 H = 128; fp32 H = 256 / 320 / 512 have no such form and fall to the single-CU kernels
 // bit 10 (1024): forward all-gather with 8-byte {step, payload} granules instead of 4-byte self-tagged words (A/B, tests)
 // bit 11 (2048): inverts the default choice of the BPTT reduce-scatter slot layout (consumer-major source pairs, XP) (A/B, tests)
 // bit 12 (4096): fp32 operands on the exact-fp32 MFMA kernels instead of the three-term bf16 split (A/B, tests)
@@ -3454,6 +3462,18 @@ extern "C" int asr_reset_recurrence_path_counts(asr_handle* h) {
   for (int i = 0; i < 6; ++i) h->rec_counts[i] = 0;
   return ASR_OK;
 }
+// the form each asr_lstm_fwd / asr_lstm_bwd(_ex) call on this handle ended in (host integers bumped where the form is
+// chosen: the cluster launchers below, asr_lstm_fwd / lstm_bwd_impl for the single-CU kernels)
+extern "C" int asr_lstm_kernel_counts(asr_handle* h, unsigned long long* out, int n) {
+  if (!h || !out || n < 0) return ASR_ERR_INVALID_ARG;
+  for (int i = 0; i < n; ++i) out[i] = i < ASR_LSTM_KERNEL_N ? h->lstm_counts[i] : 0ull;
+  return ASR_OK;
+}
+extern "C" int asr_reset_lstm_kernel_counts(asr_handle* h) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  for (int i = 0; i < ASR_LSTM_KERNEL_N; ++i) h->lstm_counts[i] = 0;
+  return ASR_OK;
+}
 
 // ASR_LSTM_FWD_HS=32: forward recurrence on clusters of H/32 CUs with four waves each (one per SIMD) instead of H/64
 // CUs with eight (A/B switch)
@@ -3559,6 +3579,7 @@ static bool cluster_fwd_launch(asr_handle* h, int T, int B, int ndir, const floa
                        (const f32x4_t*)xproj, (const bf16_t*)whp, peep, seq_len, fb, clip, (cbf16x4_t*)gates,
                        (bf16_t*)hout, cs, cf, hf, xa.area, (unsigned*)base, kernel_flags(), xa.znext, xa.zwords, t0, nt);
   });
+  h->lstm_counts[HSU == 32 ? ASR_LSTM_FWD_BF16_HS32 : ASR_LSTM_FWD_BF16_HS64] += 1;   // asr_lstm_kernel_counts
   return true;
 }
 
@@ -3608,6 +3629,7 @@ static bool cluster_fwd16_launch(asr_handle* h, int T, int B, int ndir, const fl
                        (const f32x4_t*)xproj, (const bf16_t*)whp, peep, seq_len, fb, clip, (cbf16x4_t*)gates,
                        (bf16_t*)hout, cs, cf, hf, xa.area, (unsigned*)base, kernel_flags(), xa.znext, xa.zwords, t0, nt);
   });
+  h->lstm_counts[ASR_LSTM_FWD_BF16_CU16] += 1;   // asr_lstm_kernel_counts
   return true;
 }
 
@@ -3685,6 +3707,7 @@ static bool cluster_bwd_launch(asr_handle* h, int T, int B, int ndir, const floa
                        (cbf16x4_t*)dgates, dpeep_part, xa.area, (unsigned*)base, kernel_flags(), xa.znext, xa.zwords,
                        h->bptt_clip, t0, nt);
   });
+  h->lstm_counts[HSU == 32 ? ASR_LSTM_BWD_BF16_HS32 : ASR_LSTM_BWD_BF16_HS64] += 1;   // asr_lstm_kernel_counts
   return true;
 }
 
@@ -3711,7 +3734,8 @@ bool asr_cluster_bwd_try(asr_handle* h, int T, int B, int H, int ndir, const flo
   return attempt(false) || attempt(true);
 }
 
-// fp32 operands: H = 128 on two CUs per (direction, tile).  ASR_LSTM_CLUSTER_F32=0 keeps the single-CU kernels (A/B).
+// fp32 operands (H = 128 / 256 / 320 / 512, see cluster_fwd_f32_attempt) and the GRU clusters: ASR_LSTM_CLUSTER_F32=0 keeps
+// the single-CU kernels (A/B).
 static bool cluster_f32_enabled() {
   static const bool on = [] { const char* e = getenv("ASR_LSTM_CLUSTER_F32"); return !(e && e[0] == '0'); }();
   return on && cluster_enabled();
@@ -3747,6 +3771,7 @@ static bool cluster_fwd_f32_launch(asr_handle* h, int T, int B, int ndir, const 
                            (const float*)whp, peep, seq_len, fb, clip, (f32x4_t*)gates, (float*)hout, cs, cf, hf, xa.area,
                            (unsigned*)base, kernel_flags(), xa.znext, xa.zwords, t0, nt);
       });
+      h->lstm_counts[ASR_LSTM_FWD_F32_SPLIT] += 1;   // asr_lstm_kernel_counts
       return true;
     }
   }
@@ -3759,6 +3784,7 @@ static bool cluster_fwd_f32_launch(asr_handle* h, int T, int B, int ndir, const 
                        (const float*)whp, peep, seq_len, fb, clip, (f32x4_t*)gates, (float*)hout, cs, cf, hf, xa.area,
                        (unsigned*)base, kernel_flags(), xa.znext, xa.zwords, t0, nt);
   });
+  h->lstm_counts[HSU == 32 ? ASR_LSTM_FWD_F32_HS32 : ASR_LSTM_FWD_F32_HS64] += 1;   // asr_lstm_kernel_counts
   return true;
 }
 
@@ -3815,6 +3841,7 @@ static bool cluster_bwd_f32_launch(asr_handle* h, int T, int B, int ndir, const 
                            (f32x4_t*)dgates, dpeep_part, xa.area, (unsigned*)base, kernel_flags(), xa.znext, xa.zwords,
                            h->bptt_clip, t0, nt);
       });
+      h->lstm_counts[ASR_LSTM_BWD_F32_SPLIT] += 1;   // asr_lstm_kernel_counts
       return true;
     }
   }
@@ -3824,6 +3851,8 @@ static bool cluster_bwd_f32_launch(asr_handle* h, int T, int B, int ndir, const 
                        dhout, (const f32x4_t*)gates, cs, (const float*)whpb, peep, seq_len, dcf, dhf, (f32x4_t*)dgates,
                        dpeep_part, xa.area, (unsigned*)base, kernel_flags(), xa.znext, xa.zwords, h->bptt_clip, t0, nt);
   });
+  static_assert(HSU == 32, "the 64-unit fp32 BPTT is lstm_bwd_cluster8_f32_kernel (cluster_bwd_f32_attempt)");
+  h->lstm_counts[ASR_LSTM_BWD_F32_HS32] += 1;   // asr_lstm_kernel_counts
   return true;
 }
 
@@ -3908,6 +3937,7 @@ static bool cluster_bwd_f32_attempt(asr_handle* h, int T, int B, int H, int ndir
                        dhout, (const f32x4_t*)gates, cs, (const float*)whpb, peep, seq_len, dcf, dhf, (f32x4_t*)dgates,
                        dpeep_part, xa.area, (unsigned*)base, kernel_flags(), xa.znext, xa.zwords, h->bptt_clip, t0, nt);
   });
+  h->lstm_counts[ASR_LSTM_BWD_F32_HS64] += 1;   // asr_lstm_kernel_counts
   return true;
 }
 #undef ASR_F32_ARGS_B

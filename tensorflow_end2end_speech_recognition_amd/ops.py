@@ -1197,9 +1197,10 @@ def lstm_fwd(xproj, wh_packed, peep, seq_len, H, ndir, dtype, forget_bias=1.0, c
 
 
 def lstm_bwd(dhout, gates, cs, wh_packed_bwd, peep, seq_len, H, ndir, dtype, d_c_final=None,
-             d_h_final=None, want_dpeep=True, clip_no_grad=0.0):
-    """clip_no_grad > 0 (fp32 only): the forward's cell_clip, for a cell whose clamp passes no gradient (LSTMCell's
-    tf.clip_by_value; LSTMBlockCell's clip is straight-through: 0)."""
+             d_h_final=None, want_dpeep=True, clip_no_grad=0.0, dpeep_workspace=None):
+    """clip_no_grad > 0: the forward's cell_clip, for a cell whose clamp passes no gradient (LSTMCell's
+    tf.clip_by_value; LSTMBlockCell's clip is straight-through: 0).  dpeep_workspace (tests): a caller's fp32 tensor of
+    (B/16)*ndir*7*H elements for the per-tile partials [tile, ndir, 7, H] (written for B > 16 only)."""
     h = _h(dhout)
     _chk(dhout, torch.float32, 'dhout')
     T, B, _ = dhout.shape
@@ -1208,7 +1209,11 @@ def lstm_bwd(dhout, gates, cs, wh_packed_bwd, peep, seq_len, H, ndir, dtype, d_c
     dpeep = ws = None
     if want_dpeep:
         dpeep = torch.empty((ndir, 7, H), dtype=torch.float32, device=dev)   # 3 peephole + 4 bias rows
-        ws = torch.empty(((B // 16) * ndir * 7 * H,), dtype=torch.float32, device=dev)
+        ws = dpeep_workspace
+        if ws is None:
+            ws = torch.empty(((B // 16) * ndir * 7 * H,), dtype=torch.float32, device=dev)
+        elif ws.dtype != torch.float32 or ws.numel() < (B // 16) * ndir * 7 * H or not ws.is_contiguous():
+            raise ValueError('lstm_bwd: dpeep_workspace must be contiguous fp32 with (B/16)*ndir*7*H elements')
     h.check(h.lib.asr_lstm_bwd_ex(h.h, dtype, T, B, H, ndir, _p(dhout), _p(gates), _p(cs),
                                   _p(wh_packed_bwd), _p(peep), _p(seq_len), _p(d_c_final), _p(d_h_final),
                                   float(clip_no_grad or 0.0), _p(dgates), _p(dpeep), _p(ws), _s()), 'asr_lstm_bwd')
@@ -1537,6 +1542,32 @@ def gru_kernel_counts(device=0):
 def reset_gru_kernel_counts(device=0):
     for h in _device_handles(device):
         h.check(h.lib.asr_reset_gru_kernel_counts(h.h), 'asr_reset_gru_kernel_counts')
+
+
+# the ASR_LSTM_* enum of include/asr_hip.h, in its order
+_LSTM_KERNEL_KEYS = ('fwd_bf16_cu16', 'fwd_bf16_hs32', 'fwd_bf16_hs64', 'fwd_f32_split', 'fwd_f32_hs32', 'fwd_f32_hs64',
+                     'fwd_single_bf16', 'fwd_single_f32',
+                     'bwd_bf16_hs32', 'bwd_bf16_hs64', 'bwd_f32_split', 'bwd_f32_hs32', 'bwd_f32_hs64',
+                     'bwd_single_bf16', 'bwd_single_f32')
+
+
+def lstm_kernel_counts(device=0):
+    """The form each lstm_fwd / lstm_bwd call on `device` ended in since the last reset_lstm_kernel_counts, summed over its
+    handles (asr_lstm_kernel_counts): the bf16 clusters of 16 / 32 / 64 units per CU, the fp32 three-term split, the exact
+    fp32 clusters of 32 / 64 units per CU, or the single-CU kernels, forward and backward.  One count per call, however
+    many tile groups it ran as.  Host counters: no device work, no synchronisation."""
+    n = len(_LSTM_KERNEL_KEYS)
+    tot = [0] * n
+    for h in _device_handles(device):
+        out = (C.c_ulonglong * n)()
+        h.check(h.lib.asr_lstm_kernel_counts(h.h, out, n), 'asr_lstm_kernel_counts')
+        tot = [a + int(b) for a, b in zip(tot, out)]
+    return dict(zip(_LSTM_KERNEL_KEYS, tot))
+
+
+def reset_lstm_kernel_counts(device=0):
+    for h in _device_handles(device):
+        h.check(h.lib.asr_reset_lstm_kernel_counts(h.h), 'asr_reset_lstm_kernel_counts')
 
 
 # the ASR_ATT_* enum of include/asr_hip.h, in its order
