@@ -206,7 +206,7 @@ def build_model(params, device):
                 clip_grad_norm=params['clip_grad_norm'], clip_activation=params['clip_activation'],
                 num_proj=params['num_proj'], weight_decay=params['weight_decay'],
                 bottleneck_dim=params.get('bottleneck_dim'), dtype=params.get('dtype', 'bf16'), device=device,
-                seed=params.get('seed', 0))
+                seed=params.get('seed', 0), weight_noise_std=float(params.get('weight_noise_std') or 0.0))
     model.name += '_' + str(params['num_units']) + '_' + str(params['num_layers']) + '_' + params['optimizer']
     model.name += '_lr' + str(params['learning_rate'])
     if params['num_proj'] not in (0, None):
@@ -219,6 +219,8 @@ def build_model(params, device):
         model.name += '_wd' + str(params['weight_decay'])
     if params.get('bottleneck_dim') not in (0, None):
         model.name += '_bottle' + str(params['bottleneck_dim'])
+    if params.get('weight_noise_std') and float(params['weight_noise_std']) > 0:
+        model.name += '_wn' + str(params['weight_noise_std'])
     return model
 
 

@@ -58,7 +58,8 @@ def model_kwargs(params):
         subsample_list=params.get('subsample_list'), subsample_type=params.get('subsample_type', 'drop'),
         label_smoothing_prob=float(params.get('label_smoothing_prob') or 0.0),
         encoder_residual=bool(params.get('encoder_residual', False)),
-        encoder_dense_residual=bool(params.get('encoder_dense_residual', False)))
+        encoder_dense_residual=bool(params.get('encoder_dense_residual', False)),
+        weight_noise_std=float(params.get('weight_noise_std') or 0.0))
 
 
 def scheduled_sampling_prob(params, step):
@@ -101,6 +102,8 @@ def run_name(params):
         name += '_ss' + str(params['scheduled_sampling_prob'])
     if params.get('label_smoothing_prob'):
         name += '_ls' + str(params['label_smoothing_prob'])
+    if params.get('weight_noise_std') and float(params['weight_noise_std']) > 0:
+        name += '_wn' + str(params['weight_noise_std'])
     return name
 
 

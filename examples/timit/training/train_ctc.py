@@ -170,7 +170,8 @@ def build_model(params):
                 subsample_list=params.get('subsample_list'), subsample_type=params.get('subsample_type', 'drop'),
                 encoder_residual=bool(params.get('encoder_residual', False)),
                 encoder_dense_residual=bool(params.get('encoder_dense_residual', False)),
-                label_smoothing_prob=float(params.get('label_smoothing_prob') or 0.0))
+                label_smoothing_prob=float(params.get('label_smoothing_prob') or 0.0),
+                weight_noise_std=float(params.get('weight_noise_std') or 0.0))
     # run-directory name, as :338-351
     model.name += '_' + str(params['num_units'])
     model.name += '_' + str(params['num_layers'])
@@ -192,6 +193,8 @@ def build_model(params):
         model.name += '_dres'
     if params.get('label_smoothing_prob'):
         model.name += '_ls' + str(params['label_smoothing_prob'])
+    if params.get('weight_noise_std') and float(params['weight_noise_std']) > 0:
+        model.name += '_wn' + str(params['weight_noise_std'])
     return model
 
 

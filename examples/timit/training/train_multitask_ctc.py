@@ -77,6 +77,8 @@ def run_name_suffix(params):
         name += '_drop' + str(params['dropout'])
     if params.get('label_smoothing_prob'):
         name += '_ls' + str(params['label_smoothing_prob'])
+    if params.get('weight_noise_std') and float(params['weight_noise_std']) > 0:
+        name += '_wn' + str(params['weight_noise_std'])
     return name
 
 
@@ -94,7 +96,8 @@ def main(config_path, model_save_path, log_to_file=True):
                          clip_activation=params['clip_activation'], num_proj=params['num_proj'],
                          weight_decay=params['weight_decay'], dtype=params.get('dtype', 'bf16'),
                          device=params.get('device', 'cuda:0'),
-                         label_smoothing_prob=float(params.get('label_smoothing_prob') or 0.0))
+                         label_smoothing_prob=float(params.get('label_smoothing_prob') or 0.0),
+                         weight_noise_std=float(params.get('weight_noise_std') or 0.0))
     model.name += run_name_suffix(params)
     model.save_path = new_run_directory(
         join(model_save_path, 'ctc', params['label_type_main'] + '_' + params['label_type_sub'], model.name),

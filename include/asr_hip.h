@@ -132,6 +132,24 @@ int asr_residual_fwd(asr_handle* h, int dtype, int skip_dtype, const void* h_tb,
 int asr_residual_bwd(asr_handle* h, const float* dx_raw, const float* carry, const int32_t* seq_len, int T, int Bp,
                      int W, float keep_prob, uint64_t seed, uint64_t offset, int dense, float* dout, float* carry_out,
                      asr_stream s);
+/* EXTENSION (later within ABI 5; weight_noise_std of config/ctc/regularization/blstm_ctc_weight_noise.yml (1e-5),
+ * config/attention/regularization/att_blstm_location_weight_noise.yml and att_baseline.yml (1e-9) -- keys none of the
+ * reference's code reads; Graves 2011 / 2013): Gaussian noise on a flat fp32 weight buffer for one training step, in one
+ * pass:  backup[i] = w[i];  w[i] = fl32(w[i] + fl32(std * z[i])),  i < n.
+ * z: Philox4x32-10 (the generator of asr_dropout_mask), block of counter {lo, hi, 0, 0} of offset + (i >> 2) under
+ * key = seed; element 4q + j takes the word pair (c0, c1) for j = 0, 1 and (c2, c3) for j = 2, 3:
+ *   u_a = ((c_even >> 8) + 1) 2^-24 in (0, 1],  u_b = (c_odd >> 8) 2^-24,  r = sqrt(-2 ln u_a),
+ *   z = r cos(2 pi u_b) for even j, r sin(2 pi u_b) for odd j;  |z| <= 5.768.
+ * ln / sin / cos are the accurate device-library forms: z is within 1e-5 of that statement in float64.  A slice that
+ * starts at a multiple of 4 elements, called with offset + start / 4, gets the bits of the same elements of a whole-buffer
+ * call.  std >= 0 and finite (else ASR_ERR_INVALID_ARG); std == 0 takes the backup and leaves w bit for bit.  backup must
+ * not overlap w.  16-byte accesses where both pointers are 16-byte aligned, element by element otherwise and for the
+ * n % 4 tail.  The clean weights come back by copying backup over w on the same stream; there is no entry point for it.
+ * asr_weight_noise_counts: {calls, elements, calls on the 16-byte path} since the last reset. */
+int asr_weight_noise_perturb(asr_handle* h, float* w, float* backup, size_t n, float std, uint64_t seed,
+                             uint64_t offset, asr_stream s);
+int asr_weight_noise_counts(asr_handle* h, unsigned long long* out3);
+int asr_reset_weight_noise_counts(asr_handle* h);
 /* out[c*ld_out + r] = in[r*ld_in + c] for an [rows, cols] matrix in `dtype` (LDS-tiled, both
  * sides coalesced).  The MFMA GEMM wants both operands reduction-contiguous; the k-major ones
  * (W_x as stored by TF: [Din, 4H], models/encoders/core/blstm.py:286-320 via LSTMBlockCell's

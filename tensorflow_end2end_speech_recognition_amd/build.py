@@ -24,8 +24,9 @@ FLAGS = ['--offload-arch=%s' % ARCH, '-O3', '-std=c++17', '-fPIC', '-Wno-unused-
 # lstm_cluster.hip: MFMA results in VGPRs (the default picks AGPR accumulators for the 4-wave kernels, whose gate math then
 # starts with 12 v_accvgpr_read per step on the serial chain)
 # residual.hip: m * h + skip and dx + carry are held bit for bit to a numpy statement that rounds after the multiply
+# weight_noise.hip: w + std * z likewise (a slice of the buffer must get the bits of the whole-buffer call on every path)
 FILE_FLAGS = {'ctc.hip': ['-fno-slp-vectorize'], 'lstm_cluster.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form'],
-              'residual.hip': ['-ffp-contract=off']}
+              'residual.hip': ['-ffp-contract=off'], 'weight_noise.hip': ['-ffp-contract=off']}
 # ASR_BUILD_ABLATE=1: the ablated instantiations of the headline recurrence kernels (scripts/probe_lstm_ablate.py); never
 # part of a shipped library -- the default kernels' ISA is identical with and without it
 if os.environ.get('ASR_BUILD_ABLATE') == '1':

@@ -58,6 +58,8 @@ struct asr_handle {
   // upper layers of a decoder stack since the last asr_reset_att_stack_counts: {forward on the image, forward as product +
   // cell, backward fused, backward generic}
   unsigned long long att_stack_counts[4];
+  // asr_weight_noise_perturb since the last asr_reset_weight_noise_counts: {calls, elements, calls on the 16-byte path}
+  unsigned long long weight_noise_counts[3];
 };
 
 #define ASR_FAIL(h, code, ...)                                  \
@@ -153,10 +155,9 @@ __device__ __forceinline__ float fast_tanhf(float x) {
   return 1.f - 2.f * __builtin_amdgcn_rcpf(e + 1.f);
 }
 
-// Philox4x32-10 block -> the four dropout multipliers of elements 4 ctr' .. 4 ctr' + 3 (ctr = offset + element / 4);
-// the generator of asr_dropout_mask (elementwise.hip), for the kernels that form the mask in their epilogue.
-__device__ __forceinline__ void asr_dropout_words(uint64_t ctr, uint64_t seed, float keep, float inv, float m[4]) {
-  uint32_t c[4] = {(uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u};
+// Philox4x32-10: the block of counter {lo, hi, 0, 0} of ctr under key = seed
+__device__ __forceinline__ void asr_philox_block(uint64_t ctr, uint64_t seed, uint32_t c[4]) {
+  c[0] = (uint32_t)ctr; c[1] = (uint32_t)(ctr >> 32); c[2] = 0u; c[3] = 0u;
   uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
 #pragma unroll
   for (int r = 0; r < 10; ++r) {
@@ -169,8 +170,35 @@ __device__ __forceinline__ void asr_dropout_words(uint64_t ctr, uint64_t seed, f
     c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
     k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
   }
+}
+
+// Philox block -> the four dropout multipliers of elements 4 ctr' .. 4 ctr' + 3 (ctr = offset + element / 4);
+// the generator of asr_dropout_mask (elementwise.hip), for the kernels that form the mask in their epilogue.
+__device__ __forceinline__ void asr_dropout_words(uint64_t ctr, uint64_t seed, float keep, float inv, float m[4]) {
+  uint32_t c[4];
+  asr_philox_block(ctr, seed, c);
 #pragma unroll
   for (int j = 0; j < 4; ++j) m[j] = ((c[j] >> 8) * (1.0f / 16777216.0f) < keep) ? inv : 0.f;
+}
+
+// Philox block -> four standard normal values for elements 4 ctr' .. 4 ctr' + 3 (ctr = offset + element / 4), Box-Muller on
+// the word pairs (c0, c1) and (c2, c3): u_a = ((c_even >> 8) + 1) 2^-24 in (0, 1], u_b = (c_odd >> 8) 2^-24 in [0, 1),
+// r = sqrt(-2 ln u_a), z_even = r cos(2 pi u_b), z_odd = r sin(2 pi u_b); |z| <= sqrt(48 ln 2) = 5.768.  The generator of
+// asr_weight_noise_perturb (weight_noise.hip), for kernels that form the same noise in an epilogue.  Accurate library ln /
+// sin / cos (2 u_b is exact, sincospif reduces its argument exactly): within 1e-5 of the float64 statement.
+__device__ __forceinline__ void asr_normal_words(uint64_t ctr, uint64_t seed, float z[4]) {
+  uint32_t c[4];
+  asr_philox_block(ctr, seed, c);
+#pragma unroll
+  for (int j = 0; j < 4; j += 2) {
+    const float ua = (float)((c[j] >> 8) + 1u) * (1.0f / 16777216.0f);
+    const float ub = (float)(c[j + 1] >> 8) * (1.0f / 16777216.0f);
+    const float r = sqrtf(-2.f * logf(ua));
+    float sn, cs;
+    sincospif(2.f * ub, &sn, &cs);
+    z[j] = r * cs;
+    z[j + 1] = r * sn;
+  }
 }
 
 // top ASR_XCH_BYTES of the scratch: granule exchange + error word of the multi-CU LSTM kernels

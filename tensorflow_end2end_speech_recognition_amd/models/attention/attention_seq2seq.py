@@ -82,8 +82,13 @@ class AttentionSeq2Seq(ModelBase):
                  weight_decay=0.0, time_major=True, sharpening_factor=1.0, logits_temperature=1.0,
                  sigmoid_smoothing=False, name='attention', dtype='f32', device='cuda:0', seed=0,
                  _extra_vars=None, prev_alpha='zeros', subsample_list=None, subsample_type='drop',
-                 label_smoothing_prob=0.0, encoder_residual=False, encoder_dense_residual=False):
+                 label_smoothing_prob=0.0, encoder_residual=False, encoder_dense_residual=False, weight_noise_std=0.0):
         super(AttentionSeq2Seq, self).__init__()
+        # weight_noise_std (extension keyword; a key of the reference's att_blstm_location_weight_noise.yml and
+        # att_baseline.yml that none of its code reads): Gaussian noise on every trainable variable for the forward and
+        # backward pass of each training step, the update on the clean weights (ModelBase._noise_begin has the rules);
+        # dev passes, infer and decode never see noise; 0: today's model, call for call
+        self._set_weight_noise(weight_noise_std)
         assert input_size % 3 == 0, 'input_size must be divisible by 3 (+ delta, double delta features).'
         assert splice % 2 == 1, 'splice must be the odd number'
         assert clip_grad_norm > 0, 'clip_grad_norm must be larger than 0.'
@@ -404,6 +409,10 @@ class AttentionSeq2Seq(ModelBase):
             raise ValueError('scheduled_sampling_prob > 0 is not available with decoder_num_layers > 1 (the sampling loop '
                              'runs a one-layer decoder only)')
         dev, st = self.device, self.store
+        if is_training:
+            self._noise_begin()
+        else:
+            self._noise_guard()
         # nothing below may drain the stream (pageable uploads and device read-backs do): the host has to run ahead of the
         # device for the step to be device-bound -- ops.to_device stages through pinned memory, ops.host_ints remembers
         # the host copy of a device vector it has seen
@@ -524,7 +533,7 @@ class AttentionSeq2Seq(ModelBase):
             total = (1.0 - lam) * seq_loss + lam * ctc_mean
         if self.weight_decay > 0:
             l2 = torch.zeros((), dtype=torch.float32, device=dev)
-            ops.weight_decay(None, st.flat, st.plan, st.decay_mask, self.weight_decay, l2_out=l2)
+            ops.weight_decay(None, st.clean, st.plan, st.decay_mask, self.weight_decay, l2_out=l2)
             total = total + l2
         self.sequence_loss = seq_loss
         logits_bm = logits2d.view(To, Bp, C2)[:, :B].transpose(0, 1)        # [B,To,C2] (batch-major)
@@ -557,6 +566,7 @@ class AttentionSeq2Seq(ModelBase):
 
     # ------------------------------------------------------------------ backward
     def _backward(self):
+        self._noise_tape()
         if self._tape is None:
             raise RuntimeError('train()/compute_gradients() needs a preceding compute_loss(is_training=True)')
         tp, st, dev = self._tape, self.store, self.device
@@ -743,8 +753,9 @@ class AttentionSeq2Seq(ModelBase):
             self._ctc_head_backward(tp['ctc'], enc, denc, accumulate=True)
         self.encoder.backward(denc, d_final=(dcf, dhf))
         ops.join_side(dev)
+        self._noise_end()
         if self.weight_decay > 0:
-            ops.weight_decay(st.grad, st.flat, st.plan, st.decay_mask, self.weight_decay)
+            ops.weight_decay(st.grad, st.clean, st.plan, st.decay_mask, self.weight_decay)
         self._tape = None
 
     def _ctc_head_backward(self, *a):
@@ -761,6 +772,7 @@ class AttentionSeq2Seq(ModelBase):
         reference-shaped form and as the oracle of the native one (ids identical, tests/test_gpu_attention.py)."""
         if not native:
             return self._decode_infer_class_surface(inputs, isl)
+        self._noise_guard()        # (also the lazy decoder_outputs_infer of a training compute_loss, read before train())
         st, dev = self.store, self.device
         B = inputs.shape[0]
         enc, seq_p = self._encode(inputs, isl, 1.0, False)
@@ -802,6 +814,7 @@ class AttentionSeq2Seq(ModelBase):
 
     def _decode_infer_class_surface(self, inputs, isl):
         """The reference-shaped inference path: AttentionDecoder.step under dynamic_decode (one device sync per token)."""
+        self._noise_guard()
         st, dev = self.store, self.device
         B = inputs.shape[0]
         enc, seq_p = self._encode(inputs, isl, 1.0, False)
@@ -848,6 +861,7 @@ class AttentionSeq2Seq(ModelBase):
         the step loop, and _beam_raw also keeps lm_score [B,W]."""
         # (joint / fused: <SOS> never scores)
         W = check_beam_width(beam_width, self.num_classes - (1 if (ctc_weight or lm_weight) else 0))
+        self._noise_guard()
         st, dev = self.store, self.device
         B = inputs.shape[0]
         enc, seq_p = self._encode(inputs, isl, 1.0, False)

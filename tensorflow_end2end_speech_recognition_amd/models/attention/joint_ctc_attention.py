@@ -13,7 +13,8 @@ passes all of them from the config) is ignored.  REPRODUCED by default, with a w
 the literal; `honour_ctor_args=True` (extension keyword) uses the caller's values instead.
 `ctc_label_smoothing_prob` (extension keyword): label smoothing of the CTC head as CTC(label_smoothing_prob=...) applies it
 (ops.ctc_loss_ls, training steps only; lambda scales the whole smoothed term); `label_smoothing_prob` keeps meaning the
-attention targets only.
+attention targets only.  `weight_noise_std` (extension keyword of AttentionSeq2Seq) passes through: the noise covers the
+CTC head's variables too, they live in the same flat buffer.
 """
 import warnings
 

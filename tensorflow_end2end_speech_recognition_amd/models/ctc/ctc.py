@@ -76,7 +76,10 @@ class CTC(ModelBase):
     models/encoders/core/residual.py; both false: the plain encoder); `label_smoothing_prob` (eps in [0, 1): the training
     loss of an utterance becomes (1 - eps) * ctc + eps * sum_t KL(uniform || softmax(logits_t)) over all classes, blank
     included, through ops.ctc_loss_ls -- a key of the reference's blstm_ctc_ls.yml that none of its code reads; dev losses
-    (is_training=False) and self.ctc_losses stay the plain CTC loss; 0: today's calls).
+    (is_training=False) and self.ctc_losses stay the plain CTC loss; 0: today's calls); `weight_noise_std` (sigma >= 0:
+    Gaussian noise on every trainable variable for the forward and backward pass of each training step, the update on
+    the clean weights -- ModelBase._noise_begin has the rules; a key of the reference's blstm_ctc_weight_noise.yml that
+    none of its code reads; dev passes never see noise; 0: today's model, call for call).
     """
     head_scope = 'output'      # variable scope of the output FC (ctc.py:216-224)
 
@@ -85,8 +88,9 @@ class CTC(ModelBase):
                  parameter_init=0.1, clip_grad_norm=None, clip_activation=None, num_proj=None,
                  weight_decay=0.0, bottleneck_dim=None, time_major=True,
                  dtype='f32', device='cuda:0', seed=0, subsample_list=None, subsample_type='drop',
-                 encoder_residual=False, encoder_dense_residual=False, label_smoothing_prob=0.0):
+                 encoder_residual=False, encoder_dense_residual=False, label_smoothing_prob=0.0, weight_noise_std=0.0):
         super(CTC, self).__init__()
+        self._set_weight_noise(weight_noise_std)
         if not 0.0 <= float(label_smoothing_prob) < 1.0:
             raise ValueError('label_smoothing_prob must be in [0, 1), got %r' % (label_smoothing_prob,))
         self.label_smoothing_prob = float(label_smoothing_prob)
@@ -316,6 +320,10 @@ class CTC(ModelBase):
         list2sparsetensor or a dense [B,Lmax] array padded -1; inputs_seq_len [B].
         Returns (total_loss 0-dim cuda tensor, logits [T,B,num_classes])."""
         dev = self.device
+        if is_training:
+            self._noise_begin()
+        else:
+            self._noise_guard()
         # host-side view of the lengths for encoders that plan on the host (VGG valid-frame packing, GRU tmax): taken
         # from what the caller handed over, never by reading a device copy back (that would drain the stream each step)
         self.encoder._lens_host = ops.host_ints(inputs_seq_len)
@@ -359,7 +367,7 @@ class CTC(ModelBase):
         total_loss = ctc_loss
         if self.weight_decay > 0:
             l2 = torch.zeros((), dtype=torch.float32, device=dev)
-            ops.weight_decay(None, self.store.flat, self.store.plan, self.store.decay_mask,
+            ops.weight_decay(None, self.store.clean, self.store.plan, self.store.decay_mask,
                              self.weight_decay, l2_out=l2)
             total_loss = ctc_loss + l2                                      # ctc.py:280-302
         self.ctc_losses = ctc_losses[:B]
@@ -375,6 +383,7 @@ class CTC(ModelBase):
 
     # ------------------------------------------------------------------ backward
     def _backward(self):
+        self._noise_tape()
         if self._tape is None:
             raise RuntimeError('train()/compute_gradients() needs a preceding compute_loss(is_training=True)')
         tape, st = self._tape, self.store
@@ -399,8 +408,9 @@ class CTC(ModelBase):
                 ops.colsum(dl2d, out=st.g(self.head_scope + '/biases'))
             ops.ctc_head_bwd(img, self._head_imgs[1], denc, drop=mask, **listed)
             self.encoder.backward(denc.view(T, Bp, E), top_masked=mask is not None, **self._encoder_backward_extra())
+            self._noise_end()
             if self.weight_decay > 0:
-                ops.weight_decay(st.grad, st.flat, st.plan, st.decay_mask, self.weight_decay)
+                ops.weight_decay(st.grad, st.clean, st.plan, st.decay_mask, self.weight_decay)
             self._tape = None
             return
         dl_op = ops.cast_from_f32(dl2d, ASR_BF16) if self.dtype == ASR_BF16 else dl2d
@@ -419,8 +429,9 @@ class CTC(ModelBase):
             E = Ee
             self._bn = None
         self.encoder.backward(denc.view(T, Bp, E), **self._encoder_backward_extra())
+        self._noise_end()
         if self.weight_decay > 0:
-            ops.weight_decay(st.grad, st.flat, st.plan, st.decay_mask, self.weight_decay)
+            ops.weight_decay(st.grad, st.clean, st.plan, st.decay_mask, self.weight_decay)
         self._tape = None
 
     @staticmethod

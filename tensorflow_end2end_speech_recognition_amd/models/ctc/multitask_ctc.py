@@ -87,6 +87,10 @@ class MultitaskCTC(CTC):
                      is_training=True):
         """:227-312.  Returns (total_loss, logits_main [T,B,C_main], logits_sub [T,B,C_sub])."""
         dev = self.device
+        if is_training:
+            self._noise_begin()            # weight_noise_std (extension keyword, CTC's)
+        else:
+            self._noise_guard()
         self.encoder._lens_host = ops.host_ints(inputs_seq_len)
         inputs = ops.to_device(inputs, torch.float32, dev)
         inputs_seq_len = ops.to_device(inputs_seq_len, torch.int32, dev)
@@ -116,7 +120,7 @@ class MultitaskCTC(CTC):
         total_loss = self.ctc_loss_main * self.main_task_weight + self.ctc_loss_sub * self.sub_task_weight
         if self.weight_decay > 0:
             l2 = torch.zeros((), dtype=torch.float32, device=dev)
-            ops.weight_decay(None, self.store.flat, self.store.plan, self.store.decay_mask,
+            ops.weight_decay(None, self.store.clean, self.store.plan, self.store.decay_mask,
                              self.weight_decay, l2_out=l2)
             total_loss = total_loss + l2                                     # :240-247
         self.ctc_losses, self.ctc_losses_sub = losses_m[:B], losses_s[:B]

@@ -44,8 +44,11 @@ class Optimizer(object):
 
     def apply_gradients(self, grads_and_vars=None, global_step=None, learning_rate=None):
         lr = self.learning_rate if learning_rate is None else learning_rate
-        self.global_step += 1
         st = self.store
+        if st.perturbed:
+            raise RuntimeError('apply_gradients: the weights still carry weight noise (compute_gradients of the model that '
+                               'perturbed them restores the clean ones); an update must not land on noisy weights')
+        self.global_step += 1
         ops.optimizer_step(self.opt_id, st.flat, st.grad, self.slot0, self.slot1, lr, self.global_step)
         st.mark_dirty()
         if st.flat.is_cuda:
@@ -59,11 +62,55 @@ class Optimizer(object):
 
 
 class ModelBase(object):
+    # Gaussian weight noise (extension keyword weight_noise_std of CTC / AttentionSeq2Seq; 0: none of it runs)
+    weight_noise_std = 0.0
+    _noise_calls = 0
 
     def __init__(self, *args, **kwargs):
         self.optimizer = None
         self.clip_grad_norm = None
         self.store = None
+
+    # ---- weight noise (the rules: _noise_begin)
+    def _set_weight_noise(self, std):
+        std = float(std or 0.0)
+        if not 0.0 <= std < float('inf'):
+            raise ValueError('weight_noise_std must be finite and >= 0, got %r' % (std,))
+        self.weight_noise_std = std
+
+    def _noise_begin(self):
+        """Top of a training compute_loss.  Weight noise (Graves 2011): at every training step zero-mean Gaussian noise of
+        standard deviation weight_noise_std is added to ALL trainable variables (store.flat, biases and peepholes included)
+        for the forward and the backward pass, and the update goes to the clean weights.  Step k (the k-th training
+        compute_loss, from 1) draws ops.weight_noise_perturb(seed = model.seed + 7, offset = k << 40).  The perturbed
+        weights live from here to the end of this model's _backward(), which puts the clean bits back BEFORE the
+        weight-decay gradient, the clip, the data-parallel mean and the optimizer; weight decay (both terms) and
+        store.state_dict() read the clean weights (store.clean) throughout.  Any other use of the weights in between -- a
+        dev compute_loss, infer / decode, load_state_dict, a second training compute_loss -- first restores the clean
+        weights and drops the tape, so a later train() raises.
+        Data parallel: ranks build the model with one seed and so draw the same noise; a rank with an empty shard makes no
+        compute_loss and so no perturbation that step, which is harmless because every replica applies the identical
+        update to identical clean weights."""
+        if self.weight_noise_std > 0.0:
+            self._noise_guard()
+            self._noise_calls += 1
+            self.store.perturb(self.weight_noise_std, self.seed + 7, self._noise_calls << 40)
+
+    def _noise_end(self):
+        """In _backward(), behind the last product on the perturbed weights and before the weight-decay gradient."""
+        if self.store.perturbed:
+            self.store.restore()
+
+    def _noise_guard(self):
+        """Every other entry that reads the weights: a perturbation still live ends here, and with it its tape."""
+        if self.store.perturbed:
+            self.store.restore()
+            self._tape = None
+
+    def _noise_tape(self):
+        """Top of _backward(): the tape of a forward whose perturbation is gone (load_state_dict) is no tape."""
+        if self.weight_noise_std > 0.0 and not self.store.perturbed:
+            self._tape = None
 
     def _build(self, *args, **kwargs):
         """Construct model graph."""

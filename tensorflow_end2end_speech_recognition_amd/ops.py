@@ -3398,6 +3398,38 @@ def weight_decay(flat_grads, flat_params, plan, decay_mask, wd, l2_out=None):
             'asr_weight_decay')
 
 
+def weight_noise_perturb(flat, backup, std, seed, offset):
+    """EXTENSION: Gaussian weight noise for one training step (asr_weight_noise_perturb), in place and in one pass:
+    backup[i] = flat[i], flat[i] += std * z[i] with z the standard normal values of the Philox blocks offset + i / 4 under
+    key `seed` (the statement: include/asr_hip.h).  flat / backup: contiguous fp32 of one size that do not overlap; a view
+    that starts at a multiple of 4 elements, with offset + start / 4, gets the bits of those elements of a whole-buffer
+    call.  std >= 0 (0: the backup alone).  The clean weights come back with flat.copy_(backup)."""
+    sd = float(std)
+    if not (0.0 <= sd < float('inf')):
+        raise ValueError('weight_noise_perturb: std must be finite and >= 0, got %r' % (std,))
+    _chk(flat, torch.float32, 'flat')
+    _chk(backup, torch.float32, 'backup')
+    if backup.numel() != flat.numel():
+        raise ValueError('weight_noise_perturb: backup has %d elements, flat %d' % (backup.numel(), flat.numel()))
+    h = _h(flat)
+    h.check(h.lib.asr_weight_noise_perturb(h.h, _p(flat), _p(backup), flat.numel(), sd, int(seed), int(offset), _s()),
+            'asr_weight_noise_perturb')
+    return flat
+
+
+_WEIGHT_NOISE_KEYS = ('calls', 'elements', 'vec_calls')
+
+
+def weight_noise_counts(device=0):
+    """weight_noise_perturb calls on `device` since the last reset (asr_weight_noise_counts): calls, elements, calls that
+    ran the 16-byte kernel.  Host counters: no device work, no synchronisation."""
+    return _counts3('weight_noise_counts', _WEIGHT_NOISE_KEYS, device)
+
+
+def reset_weight_noise_counts(device=0):
+    _reset_counts3('weight_noise_counts', device)
+
+
 def optimizer_step(opt_id, params, grads, slot0, slot1, lr, step):
     h = _h(params)
     h.check(h.lib.asr_optimizer_step(h.h, int(opt_id), _p(params), _p(grads), _p(slot0), _p(slot1),

@@ -31,6 +31,8 @@ class ParamStore(object):
         self.finalized = False
         self._shadow = None
         self._shadow_dirty = True
+        self._backup = None    # the clean weights while a weight-noise perturbation is live (allocated on first use)
+        self.perturbed = False
 
     # -- declaration (like tf.get_variable at graph-build time)
     def declare(self, name, shape, init):
@@ -109,10 +111,45 @@ class ParamStore(object):
             self._shadow_dirty = False
         return self._shadow
 
+    # -- Gaussian weight noise (weight_noise_std of CTC / AttentionSeq2Seq; the lifetime rules: ModelBase._noise_begin)
+    def perturb(self, std, seed, offset):
+        """flat += std * z for one training step (ops.weight_noise_perturb, one pass that also saves the clean weights),
+        on the current stream and therefore before any side lane the forward forks for weight images."""
+        if self.perturbed:
+            raise RuntimeError('ParamStore.perturb: the previous perturbation was not restored')
+        if self._backup is None:
+            self._backup = torch.empty_like(self.flat)
+        ops.weight_noise_perturb(self.flat, self._backup, std, seed, offset)
+        self.perturbed = True
+        self.mark_dirty()
+
+    def restore(self):
+        """The clean weights back, bit for bit (a copy of the backup, not a subtraction); a no-op when not perturbed.
+        Ordered behind every reader of the perturbed weights: the side lanes a backward pass left open are joined."""
+        if not self.perturbed:
+            return
+        ops.join_side(self.flat.device)
+        self.flat.copy_(self._backup)
+        self.perturbed = False
+        self.mark_dirty()
+
+    @property
+    def clean(self):
+        """The flat buffer of the weights without noise: what weight decay and checkpoints read."""
+        return self._backup if self.perturbed else self.flat
+
     def state_dict(self):
+        if self.perturbed:
+            out = {}
+            for n in self.names:
+                v = self.views[n]
+                st = v.storage_offset()
+                out[n] = self._backup[st:st + v.numel()].view(v.shape).clone()
+            return out
         return {n: self.views[n].detach().clone() for n in self.names}
 
     def load_state_dict(self, sd):
+        self.restore()
         for n in self.names:
             self.views[n].copy_(sd[n].to(self.flat.device).view(self.views[n].shape))
         self.mark_dirty()
