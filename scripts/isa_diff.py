@@ -5,23 +5,34 @@ normalised).  Used to prove that an experimental template variant behind a defau
 between files, leaves the kernels' code untouched, so it can be committed without a GPU run.
 
     python scripts/isa_diff.py <rev_a> <rev_b> [file.hip ...] [--b file.hip ...] [--rename old=new ...] [--work dir]
-    e.g.  isa_diff.py HEAD~1 HEAD                                   (the default file)
+    e.g.  isa_diff.py HEAD~1 HEAD                                   (the default files: the cluster recurrence family)
           isa_diff.py HEAD~1 . csrc/gemm.hip --b csrc/gemm.hip csrc/conv.hip --rename conv3x5_nt_kernel=conv_nt_kernel
+(file paths from the repository root).  Every file is compiled with the flags that build.py OF ITS OWN TREE gives it -- FLAGS
+and the file's FILE_FLAGS entry, ASR_BUILD_ABLATE=1 in the environment included -- so a file that exists only on side b
+takes tree b's flags and the verdict is about the code each tree ships.
 Kernels are matched by demangled name over ALL files of a side (they may move between files), with
 `(anonymous namespace)::` dropped and the --rename substitutions (re.sub) applied to side a's names.  Template arguments appended
 with a default (kernel<256, false> -> kernel<256, false, false>) are matched by trying the old name with `, false` appended
 to the argument list.  --work keeps the trees and their assembly in a directory (and reuses what is there).  Kernels that differ are listed with their registers, scratch and LDS on both sides."""
 import os
 import re
+import runpy
 import subprocess
 import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DEFAULT = 'tensorflow_end2end_speech_recognition_amd/csrc/lstm_cluster.hip'
-FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wno-unused-value', '--cuda-device-only', '-S']
+CSRC = 'tensorflow_end2end_speech_recognition_amd/csrc/'
+DEFAULT = [CSRC + f for f in ('lstm_cluster.hip', 'lstm_cluster_f32.hip', 'gru_cluster.hip', 'cluster_host.hip')]
 CXXFILT = 'c++filt'
 RES = ('.vgpr_count', '.agpr_count', '.sgpr_count', '.private_segment_fixed_size', '.group_segment_fixed_size')
+
+
+def build_flags(tree, rel):
+    """What build.py of the SAME tree compiles `rel` with (FLAGS + its FILE_FLAGS entry, ASR_BUILD_ABLATE included), so that
+    the verdict is about the code that ships; only the switches that stop at device assembly are added."""
+    build = runpy.run_path(os.path.join(tree, os.path.dirname(os.path.dirname(rel)), 'build.py'))
+    return build['FLAGS'] + build['FILE_FLAGS'].get(os.path.basename(rel), []) + ['--cuda-device-only', '-S']
 
 
 def asm_of(rev, rels, tmp, tag):
@@ -29,7 +40,8 @@ def asm_of(rev, rels, tmp, tag):
     tree = os.path.join(tmp, tag)
     fresh = not os.path.isdir(tree)
     os.makedirs(tree, exist_ok=True)
-    dirs = sorted({'include'} | {os.path.dirname(r) for r in rels})
+    dirs = sorted({'include'} | {os.path.dirname(r) for r in rels} |
+                  {os.path.join(os.path.dirname(os.path.dirname(r)), 'build.py') for r in rels})
     if not fresh:
         pass
     elif os.path.isdir(rev):
@@ -41,8 +53,8 @@ def asm_of(rev, rels, tmp, tag):
     for i, rel in enumerate(rels):
         out = os.path.join(tree, 'out%d.s' % i)
         if not os.path.exists(out):
-            subprocess.run(['/opt/rocm/bin/hipcc'] + FLAGS + ['-I', os.path.join(tree, 'include'), '-o', out,
-                                                             os.path.join(tree, rel)], check=True, capture_output=True)
+            subprocess.run(['/opt/rocm/bin/hipcc'] + build_flags(tree, rel) + ['-I', os.path.join(tree, 'include'), '-o', out,
+                                                                               os.path.join(tree, rel)], check=True, capture_output=True)
         txt = open(out).read()
         res = resources(txt)
         for name, body in functions(txt).items():
@@ -105,7 +117,7 @@ def main():
             dest = work
         else:
             dest.append(a)
-    files_a = files_a or [DEFAULT]
+    files_a = files_a or DEFAULT
     files_b = files_b or files_a
     renames = [tuple(r.split('=', 1)) for r in renames]
     with tempfile.TemporaryDirectory() as tmp:

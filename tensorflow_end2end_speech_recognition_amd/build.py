@@ -21,14 +21,18 @@ FLAGS = ['--offload-arch=%s' % ARCH, '-O3', '-std=c++17', '-fPIC', '-Wno-unused-
 # ctc.hip: the SLP vectoriser pairs the per-state multiplies of the single-wave recursion into v_pk_mul_f32 and then
 # re-packs freshly loaded emission registers right behind their global_load (s_waitcnt vmcnt(0) every frame: the whole
 # memory latency on the serial chain); without it the loads stay 8 frames ahead of their use
-# lstm_cluster.hip: MFMA results in VGPRs (the default picks AGPR accumulators for the 4-wave kernels, whose gate math then
-# starts with 12 v_accvgpr_read per step on the serial chain)
+# the units that hold cluster recurrence kernels (CLUSTER_UNITS): MFMA results in VGPRs (the default picks AGPR accumulators
+# for the 4-wave kernels, whose gate math then starts with 12 v_accvgpr_read per step on the serial chain); every kernel of
+# the family was tuned under it, so a new unit of the family takes it too
 # residual.hip: m * h + skip and dx + carry are held bit for bit to a numpy statement that rounds after the multiply
 # weight_noise.hip: w + std * z likewise (a slice of the buffer must get the bits of the whole-buffer call on every path)
-FILE_FLAGS = {'ctc.hip': ['-fno-slp-vectorize'], 'lstm_cluster.hip': ['-mllvm', '-amdgpu-mfma-vgpr-form'],
-              'residual.hip': ['-ffp-contract=off'], 'weight_noise.hip': ['-ffp-contract=off']}
-# ASR_BUILD_ABLATE=1: the ablated instantiations of the headline recurrence kernels (scripts/probe_lstm_ablate.py); never
-# part of a shipped library -- the default kernels' ISA is identical with and without it
+CLUSTER_UNITS = ('lstm_cluster.hip', 'lstm_cluster_f32.hip', 'gru_cluster.hip')
+FILE_FLAGS = {'ctc.hip': ['-fno-slp-vectorize'], 'residual.hip': ['-ffp-contract=off'],
+              'weight_noise.hip': ['-ffp-contract=off']}
+FILE_FLAGS.update({u: ['-mllvm', '-amdgpu-mfma-vgpr-form'] for u in CLUSTER_UNITS})
+# ASR_BUILD_ABLATE=1: the ablated instantiations of the headline recurrence kernels (scripts/probe_lstm_ablate.py), all of
+# them bf16 kernels of lstm_cluster.hip; never part of a shipped library -- the default kernels' ISA is identical with and
+# without it
 if os.environ.get('ASR_BUILD_ABLATE') == '1':
     FILE_FLAGS['lstm_cluster.hip'] = FILE_FLAGS['lstm_cluster.hip'] + ['-DASR_LSTM_ABLATE']
 

@@ -15,7 +15,7 @@ struct asr_handle {
   // split-K slabs of asr_gemm.  Calls on one handle are single-stream by contract.
   void* scratch;
   size_t scratch_bytes;
-  // exchange areas of the multi-CU LSTM kernels (lstm_cluster.hip): bytes of each area that hold stale tags, and the
+  // exchange areas of the cluster recurrences (xch_take, cluster_host.hip): bytes of each area that hold stale tags, and the
   // area the next launch runs on
   size_t xch_dirty[2];
   int xch_next;
@@ -33,7 +33,7 @@ struct asr_handle {
   // {fwd cluster, fwd persistent, fwd per step, bwd cluster, bwd persistent, bwd per step}
   unsigned long long gru_counts[6];
   // asr_lstm_fwd / asr_lstm_bwd(_ex) calls since the last asr_reset_lstm_kernel_counts by the form they ended in, indexed by
-  // the ASR_LSTM_* enum of asr_hip.h (bumped where the form is chosen: lstm_cluster.hip for the clusters, lstm.hip else)
+  // the ASR_LSTM_* enum of asr_hip.h (bumped where the form is chosen: lstm_cluster.hip / lstm_cluster_f32.hip for the clusters, lstm.hip else)
   unsigned long long lstm_counts[ASR_LSTM_KERNEL_N];
   // attention-decoder launches since the last asr_reset_att_path_counts, indexed by the ASR_ATT_* enum of asr_hip.h
   unsigned long long att_counts[ASR_ATT_PATH_N];
@@ -204,6 +204,7 @@ __device__ __forceinline__ void asr_normal_words(uint64_t ctr, uint64_t seed, fl
 // top ASR_XCH_BYTES of the scratch: granule exchange + error word of the multi-CU LSTM kernels
 // (64 MB: two areas; the BPTT kernel's H = 512 clusters of 16 CUs take 1 MB of slots each, 16 clusters at B = 128)
 static constexpr size_t ASR_XCH_BYTES = (size_t)64 << 20;
+// bf16 operands (lstm_cluster.hip); false = not applicable, nothing launched
 bool asr_cluster_fwd_try(asr_handle* h, int T, int B, int H, int ndir, const float* xproj,
                          const void* whp, const float* peep, const int32_t* seq_len, float fb,
                          float clip, void* gates, void* hout, float* cs, float* cf, float* hf,
@@ -212,7 +213,7 @@ bool asr_cluster_bwd_try(asr_handle* h, int T, int B, int H, int ndir, const flo
                          const void* gates, const float* cs, const void* whpb, const float* peep,
                          const int32_t* seq_len, const float* dcf, const float* dhf, void* dgates,
                          float* dpeep_part, hipStream_t st);
-// fp32 operands (H = 128 on two CUs per direction); same contract: false = not applicable, nothing launched
+// fp32 operands (lstm_cluster_f32.hip); same contract
 bool asr_cluster_fwd_f32_try(asr_handle* h, int T, int B, int H, int ndir, const float* xproj,
                              const void* whp, const float* peep, const int32_t* seq_len, float fb,
                              float clip, void* gates, void* hout, float* cs, float* cf, float* hf,
@@ -222,7 +223,7 @@ bool asr_cluster_bwd_f32_try(asr_handle* h, int T, int B, int H, int ndir, const
                              const int32_t* seq_len, const float* dcf, const float* dhf, void* dgates,
                              float* dpeep_part, hipStream_t st);
 
-// GRU forward on clusters (lstm_cluster.hip: the exchange machinery lives there); false = not applicable
+// GRU forward / backward on clusters (gru_cluster.hip); false = not applicable
 bool asr_cluster_gru_fwd_try(asr_handle* h, int T, int B, int H, int ndir, const float* xg, const float* xc,
                              const float* wgh, const float* wch, const int32_t* seq_len, float* r, float* u, float* c,
                              float* rh, float* hout, float* h_final, hipStream_t st);

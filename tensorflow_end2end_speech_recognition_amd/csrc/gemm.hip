@@ -278,7 +278,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(int M, int N, int K, const T*
 
 // LDS images [rows][64 + 8 bf16] read as MFMA fragments with ds_read_b128 (16 lanes = 16 rows of one 16-byte k-slot): the
 // hardware serves a wave in lane groups that pair rows 0-3, 12-15 of k-slot q with rows 4-11 of k-slot q ^ 1
-// (lstm_cluster.hip, lds_swz), so with plain padding those two sets collide on the 16 sixteen-byte bank groups --
+// (cluster_xch.h, lds_swz), so with plain padding those two sets collide on the 16 sixteen-byte bank groups --
 // SQ_LDS_BANK_CONFLICT on 11-13 % of the CU cycles of these kernels (profiles/r03_pmc_util.md).  Swapping the two halves of
 // every 32 bytes OF A ROW for rows 4-11 (mod 16), by writers and readers alike, makes every group hit 16 distinct slots
 // (row stride 9 slots: 9 r + q mod 16 is a permutation of the 16 rows).

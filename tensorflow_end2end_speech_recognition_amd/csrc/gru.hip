@@ -506,7 +506,7 @@ extern "C" int asr_gru_fwd(asr_handle* h, int T, int B, int H, int ndir, const f
   (void)hipFuncSetAttribute((const void*)gru_cand_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   const size_t sn = (size_t)ndir * B * H;
   float* hs[2] = {hstate2, hstate2 + sn};
-  // H = 128 / 256: clusters of H / 32 CUs with the recurrent blocks in registers (lstm_cluster.hip), final state in hs[0]
+  // H = 128 / 256: clusters of H / 32 CUs with the recurrent blocks in registers (gru_cluster.hip), final state in hs[0]
   if (gru_cluster_allowed() &&
       asr_cluster_gru_fwd_try(h, T, B, H, ndir, xg, xc, wgh, wch, seq_len, r, u, c, rh, hout, hs[0], st)) {
     h->gru_counts[0] += 1;
@@ -569,7 +569,7 @@ extern "C" int asr_gru_bwd(asr_handle* h, int T, int B, int H, int ndir, const f
   if (hipMemsetAsync(dgate, 0, (size_t)T * B * ndir * 2 * H * sizeof(float), st) != hipSuccess ||
       hipMemsetAsync(dcand, 0, (size_t)T * B * ndir * H * sizeof(float), st) != hipSuccess)
     ASR_FAIL(h, ASR_ERR_HIP, "asr_gru_bwd: memset");
-  // H = 128 / 256: clusters of H / 32 CUs (lstm_cluster.hip)
+  // H = 128 / 256: clusters of H / 32 CUs (gru_cluster.hip)
   if (gru_cluster_allowed() &&
       asr_cluster_gru_bwd_try(h, T, B, H, ndir, dout, d_h_final, hout, r, u, c, wghT, wchT, seq_len, dgate, dcand, st)) {
     h->gru_counts[3] += 1;

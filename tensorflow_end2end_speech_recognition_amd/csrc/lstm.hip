@@ -887,7 +887,7 @@ extern "C" int asr_lstm_fwd(asr_handle* h, int dtype, int T, int B, int H, int n
     ASR_FAIL(h, ASR_ERR_UNSUPPORTED, "asr_lstm_fwd: T*B*ndir*H exceeds 32-bit element offsets");
   if (T == 0) return ASR_OK;
   hipStream_t st = (hipStream_t)s;
-  // multi-CU forms (W_h slices resident per CU, per-step h all-gather inside a cluster): lstm_cluster.hip.  bf16: H = 256
+  // multi-CU forms (W_h slices resident per CU, per-step h all-gather inside a cluster): lstm_cluster.hip (bf16), lstm_cluster_f32.hip.  bf16: H = 256
   // (16 / 8 / 4 CUs), 320 (5), 512 (16 / 8); fp32: H = 128, 256, 320, 512 on H/32 CUs, 128 also on 2.  Every other width,
   // and any shape no cluster form has the CUs or the exchange area for, runs on the single-CU kernels below.
   if (dtype == ASR_BF16 && asr_cluster_fwd_try(h, T, B, H, ndir, xproj, wh_packed, peep, seq_len, forget_bias,
@@ -972,7 +972,7 @@ extern "C" int asr_lstm_bwd_ex(asr_handle* h, int dtype, int T, int B, int H, in
                                float* dpeep, float* dpeep_workspace, asr_stream s) {
   if (!h) return ASR_ERR_INVALID_ARG;
   if (!(clip_no_grad >= 0.f)) ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_lstm_bwd_ex: clip_no_grad must be >= 0");
-  h->bptt_clip = clip_no_grad;   // the cluster launchers (lstm_cluster.hip) read it
+  h->bptt_clip = clip_no_grad;   // the cluster launchers (lstm_cluster.hip, lstm_cluster_f32.hip) read it
   const int rc = lstm_bwd_impl(h, dtype, T, B, H, ndir, dhout, gates, cs, wh_packed_bwd, peep, seq_len, d_c_final,
                                d_h_final, clip_no_grad, dgates, dpeep, dpeep_workspace, s);
   h->bptt_clip = 0.f;

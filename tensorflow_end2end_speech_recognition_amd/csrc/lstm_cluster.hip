@@ -15,74 +15,15 @@
 // timeout the workgroup raises the error word and keeps going (garbage, but no hang).
 //
 // Same semantics / data layouts as lstm.hip (gates interleaved [T,B,dir,H,4], etc.).
-#include "common.h"
+//
+// This unit: the bf16 kernels (fp32 operands: lstm_cluster_f32.hip, GRU: gru_cluster.hip).  What all three share is
+// cluster_xch.h on the device and cluster_launch.h on the host, every switch and counter defined once in cluster_host.hip.
+#include "cluster_launch.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace {
-
-typedef unsigned long long u64;
-typedef __attribute__((ext_vector_type(4))) __bf16 cbf16x4_t;
-
-constexpr int HS = 64;                 // units per CU
-constexpr unsigned SPIN_LIMIT = 4000000u;
-
-__device__ __forceinline__ float cfsig(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float cftanh(float x) {
-  return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x));
-}
-__device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
-  typedef __attribute__((ext_vector_type(2))) __bf16 bf2;
-  return __builtin_bit_cast(unsigned, (bf2){(__bf16)lo, (__bf16)hi});
-}
-__device__ __forceinline__ void gstore(u64* p, unsigned epoch, unsigned payload) {
-  __hip_atomic_store(p, ((u64)epoch << 32) | payload, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ u64 gload(const u64* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 __device__ unsigned long long* g_cdbg = nullptr;   // debug phase timers (env ASR_LSTM_DBG=1)
-
-// 16-byte exchange store of self-tagged words.  Same-XCD cluster: plain store (stays in the shared
-// L2); otherwise sc1 (write-through), as the agent-scope atomics lower to.  Inline asm pins the store
-// in program order (a plain C++ store could legally sink below the spin loop that follows).
-__device__ __forceinline__ void xstore16(f32x4_t* ubase, unsigned voff, f32x4_t v, bool fast) {
-  // uniform base in SGPRs + 32-bit per-lane byte offset: no 64-bit pointer registers per slot
-  // (s_nop 4 in front: a base restored from a spill lane by v_readlane is a VALU-written SGPR, which a VMEM address may
-  // only use 5 wait states later -- the compiler cannot see that hazard inside the block; see the XP publish)
-  if (fast) asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2\n\ts_nop 1" ::"v"(voff), "v"(v), "s"(ubase) : "memory");
-  else asm volatile("s_nop 4\n\tglobal_store_dwordx4 %0, %1, %2 sc1\n\ts_nop 1" ::"v"(voff), "v"(v), "s"(ubase) : "memory");
-}
-// ---- forward exchange with 4-byte SELF-TAGGED words (XW) ----
-// h = o * tanh(c) lies in [-1, 1], so the top exponent bit of its bf16 form (bit 14) is always 0: the two free bits of a
-// packed {bf16, bf16} word (bits 14 and 30) carry a 2-bit step tag and the DATA IS THE FLAG at 4-byte granularity -- no
-// separate tag word (half of every polled byte in the 8-byte {tag, payload} granules), tear-proof for any load / store
-// width because every 4-byte word validates itself.  tag(s) = ((s >> 1) + 1) & 3 for the slot of parity s & 1: 1 on the
-// first write into the zeroed area, a different value on each of the next three writes to the same word (a consumer is
-// never more than one write behind, see the poll).  The publisher FORCES the two bits, so a NaN (exponent all ones)
-// cannot forge a tag and stall the cluster.
-constexpr unsigned XW_MASK = 0x40004000u;
-__device__ __forceinline__ unsigned xw_tag(int s) {
-  const unsigned t = (((unsigned)s >> 1) + 1u) & 3u;
-  return ((t & 1u) << 14) | ((t & 2u) << 29);
-}
-typedef __attribute__((ext_vector_type(4))) unsigned xw4_t;
-// uniform base + per-lane element offset (lets the backend use the SGPR-base addressing mode)
-template <typename T>
-__device__ __forceinline__ T* uoff(T* ubase, unsigned elem) {
-  return ubase + elem;   // plain pointer arithmetic: an integer round trip would demote it to a flat pointer
-}
-
-// The exchange area is double-buffered ACROSS launches: launch n runs on area n % 2 and, as its first act, zeroes the
-// part of the other area the previous launch dirtied (all workgroups of the grid help: < 3 stores per thread), so the
-// next launch finds clean tags without a memset launch in front of every recurrence kernel (10 per training step,
-// each ~6 us on the critical path).  The host side tracks the dirty extent of both areas (asr_handle::xch_dirty).
-__device__ __forceinline__ void zero_next_area(u64* __restrict__ znext, unsigned zwords) {
-  const unsigned nthreads = gridDim.x * blockDim.x;
-  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < zwords; i += nthreads) znext[i] = 0;
-}
-
 // ---------------------------------------------------------------- forward, 8 waves
 // Same cluster / exchange as above with TWO waves per SIMD: the 4-wave form spends ~2.2k of its
 // 5.2k cycles/step in the gate math of 4 (row, unit) pairs per lane with nothing to hide the
@@ -90,84 +31,6 @@ __device__ __forceinline__ void zero_next_area(u64* __restrict__ znext, unsigned
 // tile 1 = [f x 8 | o x 8]; after the MFMAs lanes n and n^8 swap halves over DPP row_ror:8 so each
 // lane ends up with all four gates of TWO (row, unit) pairs; the second wave of the SIMD fills
 // the other's stalls.  LDS A-fragment reads double (8 waves x 8 KB) but hide behind the MFMAs.
-constexpr int CT8 = 512;
-// LDS images [16 rows][...] read as MFMA A fragments with ds_read_b128: row stride = 33 x 16 B.  The
-// hardware services a wave in lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31}, ... (rows 0-3,12-15
-// of k-block q together with rows 4-11 of k-block q^1), so a plain row-major image always has one
-// 2-way bank conflict per group; swapping the two 16-byte halves of every 32 B for rows 4-11 makes
-// each group hit 16 distinct 16-byte slots.  Byte offset XOR applied by writers and readers alike.
-__device__ __forceinline__ unsigned lds_swz(int row) { return (((row + 4) >> 3) & 1) ? 16u : 0u; }
-
-__device__ __forceinline__ float dpp_ror8(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x128, 0xF, 0xF, false));
-}
-__device__ __forceinline__ float dpp_xor1(float v) {   // quad_perm [1,0,3,2]
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, false));
-}
-
-// ---------------------------------------------------------------- cluster placement
-// Cluster c = tile * ndir + dir.  Block b of the 1-D grid: XCD slot x = b % 8, q = b / 8,
-// member g = q % G, round = q / G, cluster c = round * 8 + x.  grid = 8 * G * ceil(nclusters / 8).
-// A launch covers the TILE RANGE [tile0, tile0 + ntl) of the batch (one launch: tile0 = 0, ntl = B / 16; a batch that needs
-// more clusters than the chip has CUs for runs as several launches over consecutive ranges, see cluster_tile_plan).  c is
-// LOCAL to the launch (tile - tile0) * ndir + dir: it picks the cluster's exchange slots and placement header -- handed out
-// per launch -- and decides `valid`.  `tile` is the GLOBAL tile: everything in memory (B stays the batch stride of every
-// tensor; seq_len, the final states, the per-tile peephole / bias partials) is indexed with it.
-struct ClusterId { int c, g, d, tile; bool valid; };
-template <int G>
-__device__ __forceinline__ ClusterId cluster_id(int ndir, int tile0, int ntl) {
-  const int b = blockIdx.x, x = b & 7, q = b >> 3;
-  ClusterId r;
-  r.g = q % G;
-  r.c = (q / G) * 8 + x;
-  r.valid = r.c < ndir * ntl;
-  r.d = r.c % ndir;
-  r.tile = tile0 + r.c / ndir;
-  return r;
-}
-static inline unsigned cluster_grid(int G, int nclusters) { return 8u * G * ((nclusters + 7) / 8); }
-
-constexpr int XHDR = 16;                  // header granules per cluster (XCC ids of the members)
-constexpr unsigned XCC_EPOCH = 0x80000001u;
-
-// Every member publishes the XCC (= XCD) id it runs on with the placement-independent granule
-// protocol and reads all G of them: true iff the whole cluster shares one XCD, hence one L2.
-// Same inputs -> same answer on every member.
-template <int G>
-__device__ __forceinline__ bool same_xcd(u64* hdr, int g, bool& timed_out) {
-  const unsigned mine = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xFu;   // HW_REG_XCC_ID[3:0]
-  if (threadIdx.x == 0) gstore(hdr + g, XCC_EPOCH, mine);
-  bool same = true;
-#pragma unroll
-  for (int i = 0; i < G; ++i) {
-    u64 v = gload(hdr + i);
-    unsigned spins = 0;
-    while ((unsigned)(v >> 32) != XCC_EPOCH) {
-      if (++spins > SPIN_LIMIT) { timed_out = true; break; }
-      v = gload(hdr + i);
-    }
-    same = same && ((unsigned)v == mine);
-  }
-  return same;
-}
-// Granule publish.  Same-XCD cluster: a PLAIN 8-byte store stays in the shared L2, where the
-// consumers' L1-bypassing (sc1) polls find it after ~an L2 round trip; an sc1 store would drop the
-// line from L2 and make every poll a fabric round trip (MI355X_MICROARCH.md, store-flavour row).
-// Otherwise: the write-through agent-scope store, correct for any placement.
-__device__ __forceinline__ void gpublish(u64* p, unsigned epoch, unsigned payload, bool fast) {
-  const u64 v = ((u64)epoch << 32) | payload;
-  if (fast) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // plain store, no wait
-  else __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// masked DPP: lanes whose bank (lane & 15) >> 2 is in `BANKS` take `src` of lane (i + 8) % 16 of
-// their row, the others keep `old` -- the halves swap without any v_cndmask
-template <int BANKS>
-__device__ __forceinline__ float dpp_ror8_into(float old, float src) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old),
-                                                                 __builtin_bit_cast(int, src), 0x128, 0xF, BANKS, false));
-}
-
 // The kernel is instruction-issue bound (a wave issues ~1 instruction per 4 cycles; measured
 // 435 instructions/step -> 3.5k cycles), so the step body is written for instruction count:
 // exchange-buffer parity is a compile-time constant (loop unrolled by two), every address is an
@@ -1397,1928 +1260,6 @@ __global__ __launch_bounds__(HSU * 8, 1) void lstm_bwd_cluster8_kernel(
   }
 }
 
-// ---------------------------------------------------------------- fp32 operands (exact fp32 MFMA path)
-// (Written for H = 128 on two CUs, as told below.  Served today, cluster_fwd_f32_attempt / cluster_bwd_f32_attempt: the
-// forward kernel at 32 units per CU for H = 128, 256, 320, 512 -- at 128 and 256 only when the three-term split is off or
-// T >= 65536 -- and at 64 units per CU for H = 128 alone; the BPTT of 64 units per CU, lstm_bwd_cluster8_f32_kernel, for
-// H = 128 alone; lstm_bwd_cluster_f32_kernel at 32 units per CU for all four widths.  With 64 units per CU requested
-// (ASR_LSTM_HS=64 / flag bit 9) the fp32 widths above 128 have no cluster form and run on the single-CU kernels.)
-// BASELINE configs[0] (2 x 128 BLSTM-CTC, fp32) ran on the single-CU kernels of lstm.hip at 5.1 / 6.7 us per
-// recurrence step: with fp32 operands the step is bound by the CU's fp32 matrix rate (v_mfma_f32_16x16x4_f32:
-// 256 flop/clk/CU; h W_h of one step = 2.1 Mflop = 8.2 k cycles), not by streaming W_h.  The same cluster scheme
-// halves that: G = H/64 = 2 CUs per (direction, tile), 64 units per CU, and the byte layouts of the bf16 H = 256
-// form carry over unchanged (a row of h is 128 fp32 = 512 B, a fragment 16 B per lane, 8 fragments per tile, W_h
-// slice in 64 VGPRs per wave).  What differs: four K = 4 MFMAs per fragment, one {tag, fp32} granule per (row,
-// unit) pair in the all-gather (two per lane) instead of one {tag, 2 x bf16}, saved activations in fp32.
-__device__ __forceinline__ void mma_f32x2(const f32x4_t& a, const f32x4_t& b0, const f32x4_t& b1, f32x4_t& c0,
-                                          f32x4_t& c1) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b0[e], c0, 0, 0, 0);
-    c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b1[e], c1, 0, 0, 0);
-  }
-}
-__device__ __forceinline__ f32x4_t mma_f32(const f32x4_t& a, const f32x4_t& b, f32x4_t c) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b[e], c, 0, 0, 0);
-  return c;
-}
-
-// EARLY: as in the bf16 kernel, the fragments of the CU's OWN slice of h (half of K with two CUs) are multiplied for
-// step s+1 right after they are written, before the wave starts polling for the peer's half.
-// HSU = units per CU: 64 (eight waves) or 32 (four waves, one per SIMD: twice the CUs, each wave alone on its SIMD's fp32
-// matrix pipe -- the step is bound by that pipe: 2 waves x 64 K=4 MFMAs x 32 cycles per SIMD in the 8-wave form).
-template <int H, bool EARLY, int HSU = 64>
-__global__ __launch_bounds__(HSU * 8, 1) void lstm_fwd_cluster8_f32_kernel(
-    int T_, int B_, int ndir, const f32x4_t* __restrict__ xg, const float* __restrict__ whp,
-    const float* __restrict__ peep, const int32_t* __restrict__ seq_len, float forget_bias,
-    float cell_clip, f32x4_t* __restrict__ gates, float* __restrict__ hout, float* __restrict__ cs,
-    float* __restrict__ c_final, float* __restrict__ h_final, u64* __restrict__ xch,
-    unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords, int tile0, int ntl) {
-  zero_next_area(znext, zwords);
-  constexpr int G = H / HSU;
-  constexpr int CTW = HSU * 8;
-  constexpr int KS = H / 16;                               // fragments of k = 16 (four K = 4 MFMAs each)
-  constexpr int LDH = H + 4;                               // floats: 33 x 16 B at H = 128, like the bf16 image
-  constexpr int SLICE = 16 * HSU;                           // granules one CU publishes per step
-  constexpr int KO = HSU / 16;                              // fragments of one CU's own slice
-  // fragment index modulo KS (a mask where KS is a power of two; H = 320 has 20 fragments: x < 2 KS there)
-  auto krotf = [](int x) -> int { return ((KS & (KS - 1)) == 0) ? (x & (KS - 1)) : (x >= KS ? x - KS : x); };
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* hs = reinterpret_cast<float*>(smem);              // [2][16][LDH]
-
-  const ClusterId cid = cluster_id<G>(ndir, tile0, ntl);
-  if (!cid.valid) return;
-  const int g = cid.g, d = cid.d, b0 = cid.tile * 16;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int col = lane & 15, rg = lane >> 4;
-  const bool lo = col < 8;
-  const bool rev = (d == 1);
-  const float* wp = whp + (size_t)d * H * 4 * H;
-  const int ul = wave * 8 + (col & 7);                     // unit inside this CU's slice
-  const unsigned jw = g * HSU + ul;                         // global unit of this lane
-  const int rbase = rg * 4 + (lo ? 0 : 2);                 // first of this lane's two batch rows
-
-  int len[2];
-  int tmax = 0;
-#pragma unroll
-  for (int r = 0; r < 2; ++r) len[r] = seq_len[b0 + rbase + r];
-  for (int i = 0; i < 16; ++i) tmax = max(tmax, seq_len[b0 + i]);
-  tmax = min(tmax, T_);
-
-  float c[2] = {0.f, 0.f}, hr[2] = {0.f, 0.f};
-  const float wci = peep ? peep[(d * 3 + 0) * H + jw] : 0.f;
-  const float wcf = peep ? peep[(d * 3 + 1) * H + jw] : 0.f;
-  const float wco = peep ? peep[(d * 3 + 2) * H + jw] : 0.f;
-
-  for (int i = threadIdx.x; i < 2 * 16 * LDH; i += CTW) hs[i] = 0.f;
-  // B fragments out of the standard forward packing (lstm.hip prep: tile = (unit/16)*4 + gate, fragment ks, lane
-  // (n, rg) holds k = ks*16 + rg*4 + e): this lane's column of tile p is (gate p*2 + (col>>3), unit jw)
-  f32x4_t wreg[2][KS];
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    const int tile = (jw >> 4) * 4 + p * 2 + (col >> 3);
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const int kk = EARLY ? krotf(ks + g * KO) : ks;            // EARLY: register fragment ks holds k-fragment kk
-      wreg[p][ks] = *reinterpret_cast<const f32x4_t*>(wp + (((size_t)tile * KS + kk) * 64 + rg * 16 + (jw & 15)) * 4);
-    }
-  }
-
-  u64* xhdr = xch + (size_t)cid.c * (XHDR + 2 * G * SLICE);
-  u64* xbase = xhdr + XHDR;                                // [2 parity][G][8 waves][16 rows][8 units]
-  bool timed_out = false;
-  const bool colocated = same_xcd<G>(xhdr, g, timed_out);
-  const bool fast = colocated && !(kflags & 1);
-  unsigned spin_limit = (kflags & 2) ? 2000u : SPIN_LIMIT;
-  if ((kflags & 2) && g == G - 1) return;                  // TEST ONLY: a member goes missing
-  __syncthreads();
-
-  const unsigned stride = (unsigned)B_ * ndir * H;
-  const unsigned dstep = rev ? 0u - stride : stride;
-  unsigned oa[2], os[2];
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    os[r] = ((unsigned)(b0 + rbase + r) * ndir + d) * H + jw;
-    oa[r] = os[r] + (rev ? (unsigned)max(len[r] - 1, 0) * stride : 0u);
-  }
-  // granule i of a wave's 128: row i >> 3, unit i & 7.  A lane publishes its two (row, unit) pairs and polls
-  // granules lane and 64 + lane of wave `wave` of every peer.
-  const unsigned pofs = (unsigned)(wave * 128 + rbase * 8 + (col & 7));
-  const unsigned lofs = (unsigned)(wave * 128 + lane);
-  unsigned ldst[G - 1][2];                                 // byte offsets inside one h buffer
-  auto slice = [&](int P, int gg) -> u64* { return xbase + ((size_t)P * G + gg) * SLICE; };
-#pragma unroll
-  for (int k = 0; k < G - 1; ++k) {
-    const int gsrc = k + (k >= g ? 1 : 0);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int row = j * 8 + (lane >> 3);
-      ldst[k][j] = ((unsigned)(row * LDH + gsrc * HSU + wave * 8 + (lane & 7)) * 4u) ^ lds_swz(row);
-    }
-  }
-  unsigned lown[2];
-#pragma unroll
-  for (int r = 0; r < 2; ++r) lown[r] = ((unsigned)((rbase + r) * LDH + g * HSU + ul) * 4u) ^ lds_swz(rbase + r);
-  const unsigned lrd = ((unsigned)(col * LDH + rg * 4) * 4u) ^ lds_swz(col);
-
-  f32x4_t xq[2][2];                                        // x projection rows, requested two steps ahead
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    xq[0][r] = xg[(0 < len[r]) ? oa[r] : os[r]];
-    xq[1][r] = (tmax > 1) ? xg[(1 < len[r]) ? oa[r] + dstep : os[r] + stride] : xq[0][r];
-  }
-  f32x4_t accn0 = {0.f, 0.f, 0.f, 0.f}, accn1 = {0.f, 0.f, 0.f, 0.f};   // EARLY: own-slice part of the next step
-
-  auto step = [&](int s, auto PAR) {
-    constexpr int P = decltype(PAR)::value;
-    const char* hcur = smem + P * 16 * LDH * 4;
-    char* hnxt = smem + (1 - P) * 16 * LDH * 4;
-    const f32x4_t x0 = xq[P][0], x1 = xq[P][1];
-    if (s + 2 < tmax) {
-#pragma unroll
-      for (int r = 0; r < 2; ++r)
-        xq[P][r] = xg[(s + 2 < len[r]) ? oa[r] + 2u * dstep : os[r] + 2u * stride];
-    }
-    f32x4_t acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (EARLY) { acc0 = accn0; acc1 = accn1; }    // own-slice fragments: done at the end of the last step
-    {
-      constexpr int K0 = EARLY ? KO : 0;
-      if constexpr (KS <= 16) {
-        f32x4_t afr[KS];
-#pragma unroll
-        for (int ks = K0; ks < KS; ++ks)
-          afr[ks] = *reinterpret_cast<const f32x4_t*>(hcur + lrd + (EARLY ? krotf(ks + g * KO) : ks) * 64);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int ks = K0; ks < KS; ++ks) mma_f32x2(afr[ks], wreg[0][ks], wreg[1][ks], acc0, acc1);
-      } else {                                             // H >= 320: the weights hold 160+ registers; A in runs of 8
-#pragma unroll
-        for (int kb = K0; kb < KS; kb += 8) {
-          f32x4_t afr[8];
-#pragma unroll
-          for (int ks = 0; ks < 8; ++ks)
-            if (kb + ks < KS)
-              afr[ks] = *reinterpret_cast<const f32x4_t*>(hcur + lrd + (EARLY ? krotf(kb + ks + g * KO) : kb + ks) * 64);
-#pragma unroll
-          for (int ks = 0; ks < 8; ++ks)
-            if (kb + ks < KS) mma_f32x2(afr[ks], wreg[0][kb + ks], wreg[1][kb + ks], acc0, acc1);
-        }
-      }
-    }
-    float pi[2], pq[2], pf[2], po[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      pi[r] = dpp_ror8_into<0xC>(acc0[r], acc0[2 + r]);
-      pq[r] = dpp_ror8_into<0x3>(acc0[2 + r], acc0[r]);
-      pf[r] = dpp_ror8_into<0xC>(acc1[r], acc1[2 + r]);
-      po[r] = dpp_ror8_into<0x3>(acc1[2 + r], acc1[r]);
-    }
-    const unsigned epoch = (unsigned)s + 1u;
-    bool act[2];
-    float ig[2], gg[2], fg[2], og[2], cn[2], hn[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) act[r] = s < len[r];
-    const f32x4_t xr[2] = {x0, x1};
-#pragma unroll
-    for (int r = 0; r < 2; ++r) ig[r] = cfsig(pi[r] + xr[r][0] + wci * c[r]);
-#pragma unroll
-    for (int r = 0; r < 2; ++r) gg[r] = cftanh(pq[r] + xr[r][1]);
-#pragma unroll
-    for (int r = 0; r < 2; ++r) fg[r] = cfsig(pf[r] + xr[r][2] + forget_bias + wcf * c[r]);
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      cn[r] = gg[r] * ig[r] + c[r] * fg[r];
-      if (cell_clip > 0.f) cn[r] = fminf(fmaxf(cn[r], -cell_clip), cell_clip);
-    }
-#pragma unroll
-    for (int r = 0; r < 2; ++r) og[r] = cfsig(po[r] + xr[r][3] + wco * cn[r]);
-#pragma unroll
-    for (int r = 0; r < 2; ++r) hn[r] = cftanh(cn[r]) * og[r];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      c[r] = act[r] ? cn[r] : c[r];
-      hr[r] = act[r] ? hn[r] : hr[r];
-    }
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      gpublish(uoff(slice(P, g), pofs + 8u * r), epoch, __float_as_uint(hr[r]), fast);
-      *reinterpret_cast<float*>(hnxt + lown[r]) = hr[r];
-    }
-    unsigned offs[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      offs[r] = act[r] ? oa[r] : os[r];
-      oa[r] += dstep;
-      os[r] += stride;
-    }
-    if constexpr (EARLY) {
-      if (s + 1 < tmax) {                                  // block-uniform
-        __syncthreads();                                   // the CU's own slice of h(s) is complete in hnxt
-        f32x4_t ao[KO];
-#pragma unroll
-        for (int k = 0; k < KO; ++k) ao[k] = *reinterpret_cast<const f32x4_t*>(hnxt + lrd + krotf(k + g * KO) * 64);
-        accn0 = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-        accn1 = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < KO; ++k) mma_f32x2(ao[k], wreg[0][k], wreg[1][k], accn0, accn1);
-      }
-    }
-    {
-      u64 v[G - 1][2];
-#pragma unroll
-      for (int k = 0; k < G - 1; ++k)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) v[k][j] = gload(uoff(slice(P, k + (k >= g ? 1 : 0)), lofs + 64u * j));
-      unsigned spins = 0;
-#pragma unroll 1
-      for (;;) {                                           // wave-uniform loop: no exec masking
-        bool ok = true;
-#pragma unroll
-        for (int k = 0; k < G - 1; ++k)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) ok = ok && ((unsigned)(v[k][j] >> 32) == epoch);
-        if (__all(ok)) break;
-        if (++spins > spin_limit) { timed_out = true; spin_limit = 0; break; }
-#pragma unroll
-        for (int k = 0; k < G - 1; ++k)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) v[k][j] = gload(uoff(slice(P, k + (k >= g ? 1 : 0)), lofs + 64u * j));
-      }
-#pragma unroll
-      for (int k = 0; k < G - 1; ++k)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) *reinterpret_cast<unsigned*>(hnxt + ldst[k][j]) = (unsigned)v[k][j];
-    }
-    // saved activations behind the poll loop (loads and stores share the wave's in-order counter); rows past their
-    // length write frame s of the padding (hout: zeros; gates / cs: never read there)
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      hout[offs[r]] = act[r] ? hr[r] : 0.f;
-      gates[offs[r]] = (f32x4_t){ig[r], gg[r], fg[r], og[r]};
-      cs[offs[r]] = cn[r];
-    }
-    __syncthreads();
-  };
-  int s = 0;
-  for (; s + 1 < tmax; s += 2) {
-    step(s, std::integral_constant<int, 0>{});
-    step(s + 1, std::integral_constant<int, 1>{});
-  }
-  if (s < tmax) step(s, std::integral_constant<int, 0>{});
-
-  if (timed_out) atomicOr(err, 1u);
-  for (int t = tmax; t < T_; ++t)
-#pragma unroll
-    for (int r = 0; r < 2; ++r) { hout[os[r]] = 0.f; os[r] += stride; }
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const size_t o = ((size_t)d * B_ + b0 + rbase + r) * H + jw;
-    if (c_final) c_final[o] = c[r];
-    if (h_final) h_final[o] = hr[r];
-  }
-}
-
-// ---------------------------------------------------------------- fp32 operands on the bf16 matrix pipe (round 5)
-// The fp32 cluster kernels above are bound by v_mfma_f32_16x16x4_f32: 32 cycles per SIMD for K = 4, i.e. 256 cycles per
-// K = 32 against 17 for one v_mfma_f32_16x16x32_bf16 (MI355X_MICROARCH.md) -- 2 048 of the ~4 000 cycles of a step at
-// H = 128.  An fp32 value IS the sum of three bf16 values (hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid): 3 x 8
-// significand bits; both subtractions are exact in fp32), so x.w = sum of the nine term products, of which the six with
-// weight >= 2^-16 are kept: lo.hi + hi.lo + mid.mid + mid.hi + hi.mid + hi.hi -- every product of two bf16 values is exact
-// in the MFMA's fp32 accumulator; the dropped terms (mid.lo, lo.mid, lo.lo) are below 2^-24 of the result.  6 bf16 MFMAs x 17
-// cycles = 102 per K = 32: the matrix phase of a step drops from 2 048 to ~820 cycles.  W_h is split once per launch into
-// registers; h (forward) / the gate gradients (BPTT) are split by the lane that writes them into three bf16 LDS images.
-// Same exchange, same saved activations, same lane <-> (row, unit) mapping as the fp32 kernels above; results differ from
-// theirs by accumulation rounding only (fp32 parity bounds unchanged, tests/test_gpu_ops.py).  ASR_LSTM_F32_SPLIT=0 keeps
-// the exact-fp32 MFMA kernels.
-__device__ __forceinline__ void split3(float x, unsigned short (&t)[3]) {
-  const __bf16 h = (__bf16)x;
-  const float r1 = x - (float)h;
-  const __bf16 m = (__bf16)r1;
-  const float r2 = r1 - (float)m;
-  t[0] = __builtin_bit_cast(unsigned short, h);
-  t[1] = __builtin_bit_cast(unsigned short, m);
-  t[2] = __builtin_bit_cast(unsigned short, (__bf16)r2);
-}
-// one K = 32 chunk of a 16 x 16 tile: a[term], b[term] bf16 fragments; smallest terms first
-__device__ __forceinline__ f32x4_t mma_s3(const bf16x8_t (&a)[3], const bf16x8_t (&b)[3], f32x4_t c) {
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], b[0], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[2], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[1], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], b[0], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[1], c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], b[0], c, 0, 0, 0);
-  return c;
-}
-// B fragment of chunk c (k = 32 c + 8 rg + j, j < 8) of one 16-column tile out of an fp32 fragment packing
-// [frag16][64 lanes][4] (lane (n, rg') holds k = 16 frag16 + 4 rg' + e): two 16-byte loads, split into three bf16 terms
-__device__ __forceinline__ void load_split_frag(const float* tile_base, int c, int rg, int n, bf16x8_t (&out)[3]) {
-  const float* p = tile_base + (((size_t)(2 * c + (rg >> 1)) * 64 + ((rg & 1) * 2) * 16 + n) * 4);
-  const f32x4_t v0 = *reinterpret_cast<const f32x4_t*>(p);
-  const f32x4_t v1 = *reinterpret_cast<const f32x4_t*>(p + 16 * 4);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    unsigned short t[3];
-    split3(j < 4 ? v0[j] : v1[j - 4], t);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) out[k][j] = (short)t[k];
-  }
-}
-
-template <int H, bool EARLY, int HSU = 32>
-__global__ __launch_bounds__(HSU * 8, 1) void lstm_fwd_cluster_f32s_kernel(
-    int T_, int B_, int ndir, const f32x4_t* __restrict__ xg, const float* __restrict__ whp,
-    const float* __restrict__ peep, const int32_t* __restrict__ seq_len, float forget_bias,
-    float cell_clip, f32x4_t* __restrict__ gates, float* __restrict__ hout, float* __restrict__ cs,
-    float* __restrict__ c_final, float* __restrict__ h_final, u64* __restrict__ xch,
-    unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords, int tile0, int ntl) {
-  zero_next_area(znext, zwords);
-  constexpr int G = H / HSU;
-  constexpr int CTW = HSU * 8;
-  static_assert(HSU == 32 && (H & (H - 1)) == 0, "four waves per CU, power-of-two width");
-  constexpr int KS = H / 32;                               // chunks of k = 32 (six bf16 MFMAs each per tile)
-  constexpr int KS16 = H / 16;                             // fragments of the fp32 weight packing
-  constexpr int LDH = H + 8;                               // bf16 elements per image row: 17 / 33 x 16 B
-  constexpr int PLB = 16 * LDH * 2;                        // bytes of one term image
-  constexpr int SLICE = 16 * HSU;                           // granules one CU publishes per step
-  constexpr int KO = HSU / 32;                              // chunks of one CU's own slice
-  auto krotf = [](int x) -> int { return x & (KS - 1); };
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  unsigned short* hs = reinterpret_cast<unsigned short*>(smem);   // [2 parity][3 terms][16][LDH]
-
-  const ClusterId cid = cluster_id<G>(ndir, tile0, ntl);
-  if (!cid.valid) return;
-  const int g = cid.g, d = cid.d, b0 = cid.tile * 16;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int col = lane & 15, rg = lane >> 4;
-  const bool lo = col < 8;
-  const bool rev = (d == 1);
-  const float* wp = whp + (size_t)d * H * 4 * H;
-  const int ul = wave * 8 + (col & 7);                     // unit inside this CU's slice
-  const unsigned jw = g * HSU + ul;                         // global unit of this lane
-  const int rbase = rg * 4 + (lo ? 0 : 2);                 // first of this lane's two batch rows
-
-  int len[2];
-  int tmax = 0;
-#pragma unroll
-  for (int r = 0; r < 2; ++r) len[r] = seq_len[b0 + rbase + r];
-  for (int i = 0; i < 16; ++i) tmax = max(tmax, seq_len[b0 + i]);
-  tmax = min(tmax, T_);
-
-  float c[2] = {0.f, 0.f}, hr[2] = {0.f, 0.f};
-  const float wci = peep ? peep[(d * 3 + 0) * H + jw] : 0.f;
-  const float wcf = peep ? peep[(d * 3 + 1) * H + jw] : 0.f;
-  const float wco = peep ? peep[(d * 3 + 2) * H + jw] : 0.f;
-
-  for (int i = threadIdx.x; i < 2 * 3 * 16 * LDH; i += CTW) hs[i] = 0;
-  // B fragments out of the standard fp32 forward packing (lstm.hip prep: tile = (unit/16)*4 + gate, fragment of k = 16, lane
-  // (n, rg) holds k = 16 frag + 4 rg + e), re-cut into k = 32 chunks and split: this lane's column of tile p is
-  // (gate p*2 + (col>>3), unit jw)
-  bf16x8_t wreg[2][KS][3];
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    const int tile = (jw >> 4) * 4 + p * 2 + (col >> 3);
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const int kk = EARLY ? krotf(ks + g * KO) : ks;            // EARLY: register chunk ks holds k-chunk kk
-      load_split_frag(wp + (size_t)tile * KS16 * 256, kk, rg, (int)(jw & 15), wreg[p][ks]);
-    }
-  }
-
-  u64* xhdr = xch + (size_t)cid.c * (XHDR + 2 * G * SLICE);
-  u64* xbase = xhdr + XHDR;                                // [2 parity][G][8 waves][16 rows][8 units]
-  bool timed_out = false;
-  const bool colocated = same_xcd<G>(xhdr, g, timed_out);
-  const bool fast = colocated && !(kflags & 1);
-  unsigned spin_limit = (kflags & 2) ? 2000u : SPIN_LIMIT;
-  if ((kflags & 2) && g == G - 1) return;                  // TEST ONLY: a member goes missing
-  __syncthreads();
-
-  const unsigned stride = (unsigned)B_ * ndir * H;
-  const unsigned dstep = rev ? 0u - stride : stride;
-  unsigned oa[2], os[2];
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    os[r] = ((unsigned)(b0 + rbase + r) * ndir + d) * H + jw;
-    oa[r] = os[r] + (rev ? (unsigned)max(len[r] - 1, 0) * stride : 0u);
-  }
-  // granule i of a wave's 128: row i >> 3, unit i & 7.  A lane publishes its two (row, unit) pairs and polls
-  // granules lane and 64 + lane of wave `wave` of every peer.
-  const unsigned pofs = (unsigned)(wave * 128 + rbase * 8 + (col & 7));
-  const unsigned lofs = (unsigned)(wave * 128 + lane);
-  unsigned ldst[G - 1][2];                                 // byte offsets inside one h buffer
-  auto slice = [&](int P, int gg) -> u64* { return xbase + ((size_t)P * G + gg) * SLICE; };
-#pragma unroll
-  for (int k = 0; k < G - 1; ++k) {
-    const int gsrc = k + (k >= g ? 1 : 0);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int row = j * 8 + (lane >> 3);
-      ldst[k][j] = ((unsigned)(row * LDH + gsrc * HSU + wave * 8 + (lane & 7)) * 2u) ^ lds_swz(row);
-    }
-  }
-  unsigned lown[2];
-#pragma unroll
-  for (int r = 0; r < 2; ++r) lown[r] = ((unsigned)((rbase + r) * LDH + g * HSU + ul) * 2u) ^ lds_swz(rbase + r);
-  const unsigned lrd = ((unsigned)(col * LDH + rg * 8) * 2u) ^ lds_swz(col);
-  // The all-gather carries the TERMS: granule = {hi | mid << 16, lo | tag16 << 16} (one 8-byte store / load per (row, unit)
-  // pair as in the fp32 kernels, tag = (step + 1) & 0xffff: T_ < 65536, checked by the launcher) -- a value is split once, by
-  // the lane that produced it, and a consumer stages what it polled with three 2-byte LDS stores and no arithmetic.
-  auto put3w = [&](char* img, unsigned off, unsigned w0, unsigned w1) {
-    *reinterpret_cast<unsigned short*>(img + off) = (unsigned short)w0;
-    *reinterpret_cast<unsigned short*>(img + PLB + off) = (unsigned short)(w0 >> 16);
-    *reinterpret_cast<unsigned short*>(img + 2 * PLB + off) = (unsigned short)w1;
-  };
-
-  // rows past their length: saved activations never read, x-projection rows not used -> ONE parked position per row (its
-  // frame tmax - 1) that stays in the L2 instead of streaming the padded part of the batch through HBM (see the bf16 kernel)
-  unsigned opark[2];
-#pragma unroll
-  for (int r = 0; r < 2; ++r) opark[r] = os[r] + (unsigned)max(tmax - 1, 0) * stride;
-  f32x4_t xq[2][2];                                        // x projection rows, requested two steps ahead
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    xq[0][r] = xg[(0 < len[r]) ? oa[r] : opark[r]];
-    xq[1][r] = (tmax > 1) ? xg[(1 < len[r]) ? oa[r] + dstep : opark[r]] : xq[0][r];
-  }
-  f32x4_t accn0 = {0.f, 0.f, 0.f, 0.f}, accn1 = {0.f, 0.f, 0.f, 0.f};   // EARLY: own-slice part of the next step
-
-  auto step = [&](int s, auto PAR) {
-    constexpr int P = decltype(PAR)::value;
-    const char* hcur = smem + P * 3 * PLB;
-    char* hnxt = smem + (1 - P) * 3 * PLB;
-    const f32x4_t x0 = xq[P][0], x1 = xq[P][1];
-    if (s + 2 < tmax) {
-#pragma unroll
-      for (int r = 0; r < 2; ++r)
-        xq[P][r] = xg[(s + 2 < len[r]) ? oa[r] + 2u * dstep : opark[r]];
-    }
-    f32x4_t acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (EARLY) { acc0 = accn0; acc1 = accn1; }    // own-slice fragments: done at the end of the last step
-    {
-      constexpr int K0 = EARLY ? KO : 0;
-      bf16x8_t afr[KS][3];
-#pragma unroll
-      for (int ks = K0; ks < KS; ++ks)
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-          afr[ks][k] = *reinterpret_cast<const bf16x8_t*>(hcur + k * PLB + lrd + (EARLY ? krotf(ks + g * KO) : ks) * 64);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int ks = K0; ks < KS; ++ks) {
-        acc0 = mma_s3(afr[ks], wreg[0][ks], acc0);
-        acc1 = mma_s3(afr[ks], wreg[1][ks], acc1);
-      }
-    }
-    float pi[2], pq[2], pf[2], po[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      pi[r] = dpp_ror8_into<0xC>(acc0[r], acc0[2 + r]);
-      pq[r] = dpp_ror8_into<0x3>(acc0[2 + r], acc0[r]);
-      pf[r] = dpp_ror8_into<0xC>(acc1[r], acc1[2 + r]);
-      po[r] = dpp_ror8_into<0x3>(acc1[2 + r], acc1[r]);
-    }
-    const unsigned epoch = (unsigned)s + 1u;
-    bool act[2];
-    float ig[2], gg[2], fg[2], og[2], cn[2], hn[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) act[r] = s < len[r];
-    const f32x4_t xr[2] = {x0, x1};
-#pragma unroll
-    for (int r = 0; r < 2; ++r) ig[r] = cfsig(pi[r] + xr[r][0] + wci * c[r]);
-#pragma unroll
-    for (int r = 0; r < 2; ++r) gg[r] = cftanh(pq[r] + xr[r][1]);
-#pragma unroll
-    for (int r = 0; r < 2; ++r) fg[r] = cfsig(pf[r] + xr[r][2] + forget_bias + wcf * c[r]);
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      cn[r] = gg[r] * ig[r] + c[r] * fg[r];
-      if (cell_clip > 0.f) cn[r] = fminf(fmaxf(cn[r], -cell_clip), cell_clip);
-    }
-#pragma unroll
-    for (int r = 0; r < 2; ++r) og[r] = cfsig(po[r] + xr[r][3] + wco * cn[r]);
-#pragma unroll
-    for (int r = 0; r < 2; ++r) hn[r] = cftanh(cn[r]) * og[r];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      c[r] = act[r] ? cn[r] : c[r];
-      hr[r] = act[r] ? hn[r] : hr[r];
-    }
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      unsigned short t3[3];
-      split3(hr[r], t3);
-      const unsigned w0 = (unsigned)t3[0] | ((unsigned)t3[1] << 16);
-      gpublish(uoff(slice(P, g), pofs + 8u * r), ((unsigned)t3[2]) | (epoch << 16), w0, fast);
-      put3w(hnxt, lown[r], w0, (unsigned)t3[2]);
-    }
-    unsigned offs[2], offgs[2];                            // hout position / saved-activation position
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      offs[r] = act[r] ? oa[r] : os[r];
-      offgs[r] = act[r] ? oa[r] : opark[r];
-      oa[r] += dstep;
-      os[r] += stride;
-    }
-    if constexpr (EARLY) {
-      if (s + 1 < tmax) {                                  // block-uniform
-        __syncthreads();                                   // the CU's own slice of h(s) is complete in hnxt
-        bf16x8_t ao[KO][3];
-#pragma unroll
-        for (int k = 0; k < KO; ++k)
-#pragma unroll
-          for (int q = 0; q < 3; ++q)
-            ao[k][q] = *reinterpret_cast<const bf16x8_t*>(hnxt + q * PLB + lrd + krotf(k + g * KO) * 64);
-        accn0 = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-        accn1 = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < KO; ++k) {
-          accn0 = mma_s3(ao[k], wreg[0][k], accn0);
-          accn1 = mma_s3(ao[k], wreg[1][k], accn1);
-        }
-      }
-    }
-    {
-      u64 v[G - 1][2];
-#pragma unroll
-      for (int k = 0; k < G - 1; ++k)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) v[k][j] = gload(uoff(slice(P, k + (k >= g ? 1 : 0)), lofs + 64u * j));
-      unsigned spins = 0;
-#pragma unroll 1
-      for (;;) {                                           // wave-uniform loop: no exec masking
-        bool ok = true;
-#pragma unroll
-        for (int k = 0; k < G - 1; ++k)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) ok = ok && ((unsigned)(v[k][j] >> 48) == (epoch & 0xffffu));
-        if (__all(ok)) break;
-        if (++spins > spin_limit) { timed_out = true; spin_limit = 0; break; }
-#pragma unroll
-        for (int k = 0; k < G - 1; ++k)
-#pragma unroll
-          for (int j = 0; j < 2; ++j) v[k][j] = gload(uoff(slice(P, k + (k >= g ? 1 : 0)), lofs + 64u * j));
-      }
-#pragma unroll
-      for (int k = 0; k < G - 1; ++k)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) put3w(hnxt, ldst[k][j], (unsigned)v[k][j], (unsigned)(v[k][j] >> 32));
-    }
-    // saved activations behind the poll loop (loads and stores share the wave's in-order counter); rows past their
-    // length write frame s of the padding (hout: zeros; gates / cs: never read there)
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      hout[offs[r]] = act[r] ? hr[r] : 0.f;
-      gates[offgs[r]] = (f32x4_t){ig[r], gg[r], fg[r], og[r]};
-      cs[offgs[r]] = cn[r];
-    }
-    __syncthreads();
-  };
-  int s = 0;
-  for (; s + 1 < tmax; s += 2) {
-    step(s, std::integral_constant<int, 0>{});
-    step(s + 1, std::integral_constant<int, 1>{});
-  }
-  if (s < tmax) step(s, std::integral_constant<int, 0>{});
-
-  if (timed_out) atomicOr(err, 1u);
-  for (int t = tmax; t < T_; ++t)
-#pragma unroll
-    for (int r = 0; r < 2; ++r) { hout[os[r]] = 0.f; os[r] += stride; }
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const size_t o = ((size_t)d * B_ + b0 + rbase + r) * H + jw;
-    if (c_final) c_final[o] = c[r];
-    if (h_final) h_final[o] = hr[r];
-  }
-}
-
-// ---------------------------------------------------------------- GRU forward on a cluster (round 6)
-// tf.contrib.rnn.GRUCell (models/encoders/core/gru.py:58-76):  [r | u] = sigmoid(xg + h W_gh),  c = tanh(xc + (r * h) W_ch),
-// h' = u h + (1 - u) c -- TWO dependent products per step, so two all-gathers: r * h between them, h' behind the second.
-// The single-CU persistent kernel (gru.hip) streams both recurrent blocks from L2 every step and multiplies on the fp32 MFMA:
-// 11.7 us of matrix work + the weight trips per step at H = 256.  Here the cluster machinery of lstm_fwd_cluster_f32s_kernel:
-// H / 32 CUs per (direction, 16-utterance tile), four waves x 8 units, the CU's slices of W_gh ([H] x [r | u of its units])
-// and W_ch as three-bf16-term fragments in registers for the whole launch, h and r * h as three-term LDS images, both
-// exchanges in 8-byte self-tagged granules {hi | mid << 16, lo | tag << 16}.  Phase 1 is one 16-column tile per wave
-// ([r x 8 | u x 8], halves swapped over DPP as in the LSTM kernels), phase 2 one tile whose upper eight columns repeat the
-// lower ones (a 16-column MFMA for 8 units: the lanes col >= 8 read rows 2, 3 of the same unit from their own copy).
-// Saved activations r, u, c, r * h at the frame a row worked on; rows past their length store nothing but hout's zero
-// and keep h (their x loads are parked on a valid frame).  Same fp32-level arithmetic as the f32s LSTM kernels (six exact bf16 products per k = 32 chunk).
-template <int H>
-__global__ __launch_bounds__(256, 1) void gru_fwd_cluster_kernel(
-    int T_, int B_, int ndir, const float* __restrict__ xg, const float* __restrict__ xc, const float* __restrict__ wgh,
-    const float* __restrict__ wch, const int32_t* __restrict__ seq_len, float* __restrict__ r_out, float* __restrict__ u_out,
-    float* __restrict__ c_out, float* __restrict__ rh_out, float* __restrict__ hout, float* __restrict__ h_final,
-    u64* __restrict__ xch, unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords, int tile0, int ntl) {
-  zero_next_area(znext, zwords);
-  constexpr int HSU = 32, G = H / HSU;
-  constexpr int KS = H / 32;
-  constexpr int LDH = H + 8;                               // bf16 elements per image row
-  constexpr int PLB = 16 * LDH * 2;                        // bytes of one term image
-  constexpr int SLICE = 16 * HSU;                           // granules one CU publishes per exchange and step
-  extern __shared__ __attribute__((aligned(16))) char smem[];   // [h parity 0][h parity 1][r * h], three term images each
-
-  const ClusterId cid = cluster_id<G>(ndir, tile0, ntl);
-  if (!cid.valid) return;
-  const int g = cid.g, d = cid.d, b0 = cid.tile * 16;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int col = lane & 15, rg = lane >> 4;
-  const bool lo = col < 8;
-  const bool rev = (d == 1);
-  const int ul = wave * 8 + (col & 7);                     // unit inside this CU's slice
-  const unsigned jw = g * HSU + ul;                         // global unit of this lane
-  const int rbase = rg * 4 + (lo ? 0 : 2);                 // first of this lane's two batch rows
-
-  int len[2];
-  int tmax = 0;
-#pragma unroll
-  for (int r = 0; r < 2; ++r) len[r] = min(max(seq_len[b0 + rbase + r], 0), T_);
-  for (int i = 0; i < 16; ++i) tmax = max(tmax, seq_len[b0 + i]);
-  tmax = min(tmax, T_);
-
-  for (int i = threadIdx.x; i < 3 * 3 * 16 * LDH; i += 256) reinterpret_cast<unsigned short*>(smem)[i] = 0;
-  // B fragments straight from the row-major recurrent blocks: lane (column col, k-group rg) of chunk ks holds
-  // W[32 ks + 8 rg + j][column], j < 8, split into three bf16 terms.  Phase 1: column = gate (col >> 3) of unit jw;
-  // phase 2: unit jw (both halves of the tile).
-  bf16x8_t w1[KS][3], w2[KS][3];
-  {
-    const float* wg = wgh + (size_t)d * H * 2 * H + (size_t)(col >> 3) * H + jw;
-    const float* wc = wch + (size_t)d * H * H + jw;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int k = 32 * ks + 8 * rg + j;
-        unsigned short t1[3], t2[3];
-        split3(wg[(size_t)k * 2 * H], t1);
-        split3(wc[(size_t)k * H], t2);
-#pragma unroll
-        for (int q = 0; q < 3; ++q) { w1[ks][q][j] = (short)t1[q]; w2[ks][q][j] = (short)t2[q]; }
-      }
-  }
-
-  u64* xhdr = xch + (size_t)cid.c * (XHDR + 4 * G * SLICE);
-  u64* xa = xhdr + XHDR;                                   // r * h: [2 parity][G][SLICE]
-  u64* xb = xa + 2 * G * SLICE;                            // h':    [2 parity][G][SLICE]
-  bool timed_out = false;
-  const bool colocated = same_xcd<G>(xhdr, g, timed_out);
-  const bool fast = colocated && !(kflags & 1);
-  unsigned spin_limit = (kflags & 2) ? 2000u : SPIN_LIMIT;
-  if ((kflags & 2) && g == G - 1) return;                  // TEST ONLY: a member goes missing
-  __syncthreads();
-
-  const unsigned stride = (unsigned)B_ * ndir * H;
-  const unsigned dstep = rev ? 0u - stride : stride;
-  unsigned oa[2], os[2], os0[2];
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    os[r] = ((unsigned)(b0 + rbase + r) * ndir + d) * H + jw;
-    os0[r] = os[r];
-    oa[r] = os[r] + (rev ? (unsigned)max(len[r] - 1, 0) * stride : 0u);
-  }
-  const unsigned pofs = (unsigned)(wave * 128 + rbase * 8 + (col & 7));
-  const unsigned lofs = (unsigned)(wave * 128 + lane);
-  unsigned ldst[G - 1][2];
-#pragma unroll
-  for (int k = 0; k < G - 1; ++k) {
-    const int gsrc = k + (k >= g ? 1 : 0);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int row = j * 8 + (lane >> 3);
-      ldst[k][j] = ((unsigned)(row * LDH + gsrc * HSU + wave * 8 + (lane & 7)) * 2u) ^ lds_swz(row);
-    }
-  }
-  unsigned lown[2];
-#pragma unroll
-  for (int r = 0; r < 2; ++r) lown[r] = ((unsigned)((rbase + r) * LDH + g * HSU + ul) * 2u) ^ lds_swz(rbase + r);
-  const unsigned lrd = ((unsigned)(col * LDH + rg * 8) * 2u) ^ lds_swz(col);
-  auto put3w = [&](char* img, unsigned off, unsigned w0, unsigned w1v) {
-    *reinterpret_cast<unsigned short*>(img + off) = (unsigned short)w0;
-    *reinterpret_cast<unsigned short*>(img + PLB + off) = (unsigned short)(w0 >> 16);
-    *reinterpret_cast<unsigned short*>(img + 2 * PLB + off) = (unsigned short)w1v;
-  };
-  auto product = [&](const char* img, const bf16x8_t (&w)[KS][3]) -> f32x4_t {
-    bf16x8_t afr[KS][3];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-      for (int q = 0; q < 3; ++q) afr[ks][q] = *reinterpret_cast<const bf16x8_t*>(img + q * PLB + lrd + ks * 64);
-    f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) acc = mma_s3(afr[ks], w[ks], acc);
-    return acc;
-  };
-  // publish this lane's two (row, unit) values into slice g of `area`, stage them into `img`; then collect the peers' slices
-  auto exchange = [&](u64* area, int P, unsigned epoch, const float (&val)[2], char* img) {
-    u64* mine = area + ((size_t)P * G + g) * SLICE;
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      unsigned short t3[3];
-      split3(val[r], t3);
-      const unsigned w0 = (unsigned)t3[0] | ((unsigned)t3[1] << 16);
-      gpublish(uoff(mine, pofs + 8u * r), ((unsigned)t3[2]) | (epoch << 16), w0, fast);
-      put3w(img, lown[r], w0, (unsigned)t3[2]);
-    }
-    u64 v[G - 1][2];
-#pragma unroll
-    for (int k = 0; k < G - 1; ++k)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) v[k][j] = gload(uoff(area + ((size_t)P * G + k + (k >= g ? 1 : 0)) * SLICE, lofs + 64u * j));
-    unsigned spins = 0;
-#pragma unroll 1
-    for (;;) {                                             // wave-uniform loop: no exec masking
-      bool ok = true;
-#pragma unroll
-      for (int k = 0; k < G - 1; ++k)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) ok = ok && ((unsigned)(v[k][j] >> 48) == (epoch & 0xffffu));
-      if (__all(ok)) break;
-      if (++spins > spin_limit) { timed_out = true; spin_limit = 0; break; }
-#pragma unroll
-      for (int k = 0; k < G - 1; ++k)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) v[k][j] = gload(uoff(area + ((size_t)P * G + k + (k >= g ? 1 : 0)) * SLICE, lofs + 64u * j));
-    }
-#pragma unroll
-    for (int k = 0; k < G - 1; ++k)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) put3w(img, ldst[k][j], (unsigned)v[k][j], (unsigned)(v[k][j] >> 32));
-  };
-
-  float hr[2] = {0.f, 0.f};
-  char* rhimg = smem + 2 * 3 * PLB;
-  // x-projections of a step, requested one step ahead (a row past its length: the parked frame, unused)
-  float nxr[2], nxu[2], nxc[2];
-  auto xfetch = [&](int s) {
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const bool a = s < len[r];
-      const int fr = a ? (rev ? len[r] - 1 - s : s) : max(tmax - 1, 0);
-      const unsigned o = os0[r] + (unsigned)fr * stride;
-      const unsigned og = (o - jw) * 2u + jw;              // the same (frame, row, direction) in the [.., 2H] gate tensor
-      nxr[r] = xg[og];
-      nxu[r] = xg[og + H];
-      nxc[r] = xc[o];
-    }
-  };
-  xfetch(0);
-  for (int s = 0; s < tmax; ++s) {
-    const int P = s & 1;
-    const char* hcur = smem + P * 3 * PLB;
-    char* hnxt = smem + (1 - P) * 3 * PLB;
-    const unsigned epoch = (unsigned)s + 1u;
-    bool act[2];
-    float xr[2], xu[2], xcv[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      act[r] = s < len[r];
-      xr[r] = nxr[r]; xu[r] = nxu[r]; xcv[r] = nxc[r];
-    }
-    if (s + 1 < tmax) xfetch(s + 1);                       // block-uniform
-    // ---- phase 1: [r | u] = sigmoid(xg + h W_gh)
-    const f32x4_t a1 = product(hcur, w1);
-    float rv[2], uv[2], rhv[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const float pr = dpp_ror8_into<0xC>(a1[r], a1[2 + r]);
-      const float pu = dpp_ror8_into<0x3>(a1[2 + r], a1[r]);
-      rv[r] = cfsig(pr + xr[r]);
-      uv[r] = cfsig(pu + xu[r]);
-      rhv[r] = rv[r] * hr[r];
-    }
-    exchange(xa, P, epoch, rhv, rhimg);
-    __syncthreads();                                       // r * h complete in LDS
-    // ---- phase 2: c = tanh(xc + (r h) W_ch), h' = u h + (1 - u) c
-    const f32x4_t a2 = product(rhimg, w2);
-    float cv[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const float pc = lo ? a2[r] : a2[2 + r];
-      cv[r] = cftanh(pc + xcv[r]);
-      const float hn = uv[r] * hr[r] + (1.f - uv[r]) * cv[r];
-      hr[r] = act[r] ? hn : hr[r];
-    }
-    exchange(xb, P, epoch, hr, hnxt);
-    // saved activations behind the poll loop; a row past its length writes a zero into frame s of hout's padding and
-    // nothing else (r * h is contracted over ALL T * B rows by the weight-gradient GEMM: the caller's zeros must stay)
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      hout[act[r] ? oa[r] : os[r]] = act[r] ? hr[r] : 0.f;
-      if (act[r]) {
-        const unsigned o = oa[r];
-        r_out[o] = rv[r];
-        u_out[o] = uv[r];
-        c_out[o] = cv[r];
-        rh_out[o] = rhv[r];
-      }
-      oa[r] += dstep;
-      os[r] += stride;
-    }
-    __syncthreads();                                       // h' complete in LDS; r * h free again
-  }
-  if (timed_out) atomicOr(err, 1u);
-  for (int t = tmax; t < T_; ++t)
-#pragma unroll
-    for (int r = 0; r < 2; ++r) { hout[os[r]] = 0.f; os[r] += stride; }
-#pragma unroll
-  for (int r = 0; r < 2; ++r) h_final[((size_t)d * B_ + b0 + rbase + r) * H + jw] = hr[r];
-}
-
-// GRU backward through time on the same clusters, as two ALL-GATHERS per step (not the LSTM BPTT's reduce-scatter of fp32
-// partials): a CU owns the dh of its 32 units, so it needs every unit's pre-activation gradients and the rows of W^T that
-// lead to its units --
-//     dh = dout[frame] + dh_rec;  du_pre = dh (hp - c) u (1 - u);  dc_pre = dh (1 - u)(1 - c^2);  acc = dh u      (own units)
-//     gather dc_pre, du_pre;      d(rh) = dc_pre W_c^T [own units];  dr_pre = d(rh) hp r (1 - r);  acc += d(rh) r
-//     gather dr_pre;              dh_rec' = acc + [dr_pre | du_pre] W_g^T [own units]
-// with W_c^T / W_g^T columns of the CU's units as three-term fragments in registers (three sets), the gathered gradients
-// as three-term LDS images (dc_pre and du_pre double-buffered by step parity: two barriers per step), saved activations and
-// dout requested one step ahead.  dgate / dcand are written for active rows only (the caller zeroes them).
-template <int H>
-__global__ __launch_bounds__(256, 1) void gru_bwd_cluster_kernel(
-    int T_, int B_, int ndir, const float* __restrict__ dout, const float* __restrict__ d_h_final,
-    const float* __restrict__ hout, const float* __restrict__ r_in, const float* __restrict__ u_in,
-    const float* __restrict__ c_in, const float* __restrict__ wghT, const float* __restrict__ wchT,
-    const int32_t* __restrict__ seq_len, float* __restrict__ dgate, float* __restrict__ dcand, u64* __restrict__ xch,
-    unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords, int tile0, int ntl) {
-  zero_next_area(znext, zwords);
-  constexpr int HSU = 32, G = H / HSU;
-  constexpr int KS = H / 32;
-  constexpr int LDH = H + 8;
-  constexpr int PLB = 16 * LDH * 2;
-  constexpr int IMG = 3 * PLB;                             // one gathered vector: three term images
-  constexpr int SLICE = 16 * HSU;
-  extern __shared__ __attribute__((aligned(16))) char smem[];   // [dc_pre P0][dc_pre P1][du_pre P0][du_pre P1][dr_pre]
-
-  const ClusterId cid = cluster_id<G>(ndir, tile0, ntl);
-  if (!cid.valid) return;
-  const int g = cid.g, d = cid.d, b0 = cid.tile * 16;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int col = lane & 15, rg = lane >> 4;
-  const bool lo = col < 8;
-  const bool rev = (d == 1);
-  const int ul = wave * 8 + (col & 7);
-  const unsigned jw = g * HSU + ul;
-  const int rbase = rg * 4 + (lo ? 0 : 2);
-
-  int len[2];
-  int tmax = 0;
-#pragma unroll
-  for (int r = 0; r < 2; ++r) len[r] = min(max(seq_len[b0 + rbase + r], 0), T_);
-  for (int i = 0; i < 16; ++i) tmax = max(tmax, seq_len[b0 + i]);
-  tmax = min(tmax, T_);
-
-  for (int i = threadIdx.x; i < 5 * 3 * 16 * LDH; i += 256) reinterpret_cast<unsigned short*>(smem)[i] = 0;
-  // B fragments: lane (column = unit jw, both halves of the tile; k-group rg) of chunk ks holds W^T[32 ks + 8 rg + j][jw]
-  bf16x8_t wc[KS][3], wr[KS][3], wu[KS][3];
-  {
-    const float* pc = wchT + (size_t)d * H * H + jw;
-    const float* pg = wghT + (size_t)d * 2 * H * H + jw;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int k = 32 * ks + 8 * rg + j;
-        unsigned short t1[3], t2[3], t3[3];
-        split3(pc[(size_t)k * H], t1);
-        split3(pg[(size_t)k * H], t2);
-        split3(pg[(size_t)(H + k) * H], t3);
-#pragma unroll
-        for (int q = 0; q < 3; ++q) { wc[ks][q][j] = (short)t1[q]; wr[ks][q][j] = (short)t2[q]; wu[ks][q][j] = (short)t3[q]; }
-      }
-  }
-
-  u64* xhdr = xch + (size_t)cid.c * (XHDR + 6 * G * SLICE);
-  u64* xc_ = xhdr + XHDR;                                  // dc_pre: [2 parity][G][SLICE]
-  u64* xu_ = xc_ + 2 * G * SLICE;                          // du_pre
-  u64* xr_ = xu_ + 2 * G * SLICE;                          // dr_pre
-  bool timed_out = false;
-  const bool colocated = same_xcd<G>(xhdr, g, timed_out);
-  const bool fast = colocated && !(kflags & 1);
-  unsigned spin_limit = (kflags & 2) ? 2000u : SPIN_LIMIT;
-  if ((kflags & 2) && g == G - 1) return;                  // TEST ONLY: a member goes missing
-  __syncthreads();
-
-  const unsigned stride = (unsigned)B_ * ndir * H;
-  unsigned ob[2];                                          // frame 0 of this lane's (row, direction, unit)
-#pragma unroll
-  for (int r = 0; r < 2; ++r) ob[r] = ((unsigned)(b0 + rbase + r) * ndir + d) * H + jw;
-  const unsigned pofs = (unsigned)(wave * 128 + rbase * 8 + (col & 7));
-  const unsigned lofs = (unsigned)(wave * 128 + lane);
-  unsigned ldst[G - 1][2];
-#pragma unroll
-  for (int k = 0; k < G - 1; ++k) {
-    const int gsrc = k + (k >= g ? 1 : 0);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int row = j * 8 + (lane >> 3);
-      ldst[k][j] = ((unsigned)(row * LDH + gsrc * HSU + wave * 8 + (lane & 7)) * 2u) ^ lds_swz(row);
-    }
-  }
-  unsigned lown[2];
-#pragma unroll
-  for (int r = 0; r < 2; ++r) lown[r] = ((unsigned)((rbase + r) * LDH + g * HSU + ul) * 2u) ^ lds_swz(rbase + r);
-  const unsigned lrd = ((unsigned)(col * LDH + rg * 8) * 2u) ^ lds_swz(col);
-  auto put3w = [&](char* img, unsigned off, unsigned w0, unsigned w1v) {
-    *reinterpret_cast<unsigned short*>(img + off) = (unsigned short)w0;
-    *reinterpret_cast<unsigned short*>(img + PLB + off) = (unsigned short)(w0 >> 16);
-    *reinterpret_cast<unsigned short*>(img + 2 * PLB + off) = (unsigned short)w1v;
-  };
-  auto product = [&](const char* img, const bf16x8_t (&w)[KS][3], f32x4_t acc) -> f32x4_t {
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      bf16x8_t afr[3];
-#pragma unroll
-      for (int q = 0; q < 3; ++q) afr[q] = *reinterpret_cast<const bf16x8_t*>(img + q * PLB + lrd + ks * 64);
-      acc = mma_s3(afr, w[ks], acc);
-    }
-    return acc;
-  };
-  auto publish = [&](u64* area, int P, unsigned epoch, const float (&val)[2], char* img) {
-    u64* mine = area + ((size_t)P * G + g) * SLICE;
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      unsigned short t3[3];
-      split3(val[r], t3);
-      const unsigned w0 = (unsigned)t3[0] | ((unsigned)t3[1] << 16);
-      gpublish(uoff(mine, pofs + 8u * r), ((unsigned)t3[2]) | (epoch << 16), w0, fast);
-      put3w(img, lown[r], w0, (unsigned)t3[2]);
-    }
-  };
-  auto collect = [&](u64* area, int P, unsigned epoch, char* img) {
-    u64 v[G - 1][2];
-#pragma unroll
-    for (int k = 0; k < G - 1; ++k)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) v[k][j] = gload(uoff(area + ((size_t)P * G + k + (k >= g ? 1 : 0)) * SLICE, lofs + 64u * j));
-    unsigned spins = 0;
-#pragma unroll 1
-    for (;;) {                                             // wave-uniform loop: no exec masking
-      bool ok = true;
-#pragma unroll
-      for (int k = 0; k < G - 1; ++k)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) ok = ok && ((unsigned)(v[k][j] >> 48) == (epoch & 0xffffu));
-      if (__all(ok)) break;
-      if (++spins > spin_limit) { timed_out = true; spin_limit = 0; break; }
-#pragma unroll
-      for (int k = 0; k < G - 1; ++k)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) v[k][j] = gload(uoff(area + ((size_t)P * G + k + (k >= g ? 1 : 0)) * SLICE, lofs + 64u * j));
-    }
-#pragma unroll
-    for (int k = 0; k < G - 1; ++k)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) put3w(img, ldst[k][j], (unsigned)v[k][j], (unsigned)(v[k][j] >> 32));
-  };
-
-  // saved activations + dout of step s, requested one step ahead (rows past their length: a valid position, unused)
-  struct Saved { float dout, u, c, r, hp; };
-  auto fetch = [&](int s, Saved (&sv)[2]) {
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const bool act = s >= 0 && s < len[r];
-      const int fr = act ? (rev ? len[r] - 1 - s : s) : 0;
-      const int fp = act ? (rev ? len[r] - s : s - 1) : 0;   // the frame of the previous step's h (s > 0)
-      const unsigned o = ob[r] + (unsigned)fr * stride;
-      sv[r].dout = dout[o];
-      sv[r].u = u_in[o];
-      sv[r].c = c_in[o];
-      sv[r].r = r_in[o];
-      sv[r].hp = (act && s > 0) ? hout[ob[r] + (unsigned)fp * stride] : 0.f;
-    }
-  };
-
-  float dhc[2];                                            // dh_rec of this lane's two (row, unit) pairs
-#pragma unroll
-  for (int r = 0; r < 2; ++r) dhc[r] = d_h_final ? d_h_final[((size_t)d * B_ + b0 + rbase + r) * H + jw] : 0.f;
-  char* drimg = smem + 4 * IMG;
-  Saved cur[2], nxt[2];
-  fetch(tmax - 1, cur);
-  unsigned epoch = 0;
-  for (int s = tmax - 1; s >= 0; --s) {
-    ++epoch;
-    const int P = (int)(epoch & 1u);
-    char* dcimg = smem + P * IMG;
-    char* duimg = smem + (2 + P) * IMG;
-    fetch(s - 1, nxt);
-    bool act[2];
-    float dcp[2], dup[2], da[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      act[r] = s < len[r];
-      const float dh = cur[r].dout + dhc[r];
-      const float u = cur[r].u, c = cur[r].c;
-      dup[r] = act[r] ? dh * (cur[r].hp - c) * u * (1.f - u) : 0.f;
-      dcp[r] = act[r] ? dh * (1.f - u) * (1.f - c * c) : 0.f;
-      da[r] = act[r] ? dh * u : dhc[r];
-    }
-    publish(xc_, P, epoch, dcp, dcimg);
-    publish(xu_, P, epoch, dup, duimg);
-    collect(xc_, P, epoch, dcimg);
-    collect(xu_, P, epoch, duimg);
-    __syncthreads();                                       // dc_pre, du_pre complete in LDS
-    // ---- d(rh) = dc_pre W_c^T for the own units
-    const f32x4_t a1 = product(dcimg, wc, (f32x4_t){0.f, 0.f, 0.f, 0.f});
-    float drp[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const float drh = lo ? a1[r] : a1[2 + r];
-      const float rr = cur[r].r;
-      drp[r] = act[r] ? drh * cur[r].hp * rr * (1.f - rr) : 0.f;
-      da[r] += act[r] ? drh * rr : 0.f;
-    }
-    publish(xr_, P, epoch, drp, drimg);
-    // the du_pre half of the second product does not wait for dr_pre: its multiplies run under the poll
-    f32x4_t a2 = product(duimg, wu, (f32x4_t){0.f, 0.f, 0.f, 0.f});
-    collect(xr_, P, epoch, drimg);
-    // gradients of the pre-activations, behind the poll loop (active rows only: the caller zeroed the tensors)
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-      if (act[r]) {
-        const int fr = rev ? len[r] - 1 - s : s;
-        const unsigned o = ob[r] + (unsigned)fr * stride;
-        dcand[o] = dcp[r];
-        const unsigned og = (o - jw) * 2u + jw;
-        dgate[og] = drp[r];
-        dgate[og + H] = dup[r];
-      }
-    __syncthreads();                                       // dr_pre complete in LDS
-    // ---- dh_rec' = acc + [dr_pre | du_pre] W_g^T for the own units
-    a2 = product(drimg, wr, a2);
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      dhc[r] = da[r] + (lo ? a2[r] : a2[2 + r]);
-      cur[r] = nxt[r];
-    }
-  }
-  if (timed_out) atomicOr(err, 2u);
-}
-
-// BPTT, fp32 operands: the H = 512 arrangement of the bf16 kernel (each tile computed ONCE: the hh = 0 waves take the
-// four own-unit tiles and hand rows 2,3 to their hh = 1 partners through LDS, the hh = 1 waves take the four tiles of
-// the peer's units and publish them) -- 64 K = 4 MFMAs per wave and step instead of the 128 + 64 of the redundant form.
-template <int H>
-__global__ __launch_bounds__(CT8, 1) void lstm_bwd_cluster8_f32_kernel(
-    int T_, int B_, int ndir, const float* __restrict__ dhout, const f32x4_t* __restrict__ gates,
-    const float* __restrict__ cs, const float* __restrict__ whpb, const float* __restrict__ peep,
-    const int32_t* __restrict__ seq_len, const float* __restrict__ d_c_final,
-    const float* __restrict__ d_h_final, f32x4_t* __restrict__ dgates, float* __restrict__ dpeep_part,
-    u64* __restrict__ xch, unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords, float clipz, int tile0, int ntl) {
-  static_assert(H / HS == 2, "one foreign tile per hh = 1 wave: two CUs per direction");
-  zero_next_area(znext, zwords);
-  constexpr int G = H / HS;
-  constexpr int KC = 4 * HS / 16;            // fragments of this CU's slice of k' (16)
-  constexpr int KSF = 4 * H / 16;            // fragments of the full packing
-  constexpr int LDG = 4 * HS + 4;            // floats: 65 x 16 B per row
-  constexpr size_t CL_U64 = XHDR + (size_t)2 * G * G * 4 * 64 * 2;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int DGB = 16 * LDG * 4;                        // bytes per dG image
-
-  const ClusterId cid = cluster_id<G>(ndir, tile0, ntl);
-  if (!cid.valid) return;
-  const int g = cid.g, d = cid.d, b0 = cid.tile * 16;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int col = lane & 15, rg = lane >> 4;
-  const int hh = wave >> 2, wt = wave & 3;
-  const bool rev = (d == 1);
-  const float* wp = whpb + (size_t)d * H * 4 * H;
-  const int ul = wt * 16 + col;
-  const unsigned jw = g * HS + ul;
-  const int rbase = rg * 4 + hh * 2;
-
-  int len[2];
-  int tmax = 0;
-#pragma unroll
-  for (int r = 0; r < 2; ++r) len[r] = seq_len[b0 + rbase + r];
-  for (int i = 0; i < 16; ++i) tmax = max(tmax, seq_len[b0 + i]);
-  tmax = min(tmax, T_);
-
-  const float wci = peep ? peep[(d * 3 + 0) * H + jw] : 0.f;
-  const float wcf = peep ? peep[(d * 3 + 1) * H + jw] : 0.f;
-  const float wco = peep ? peep[(d * 3 + 2) * H + jw] : 0.f;
-
-  const unsigned stride = (unsigned)B_ * ndir * H;
-  const unsigned dstep = rev ? stride : 0u - stride;
-  unsigned oa[2], os[2];
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const unsigned base = ((unsigned)(b0 + rbase + r) * ndir + d) * H + jw;
-    os[r] = base + (unsigned)(tmax - 1) * stride;
-    oa[r] = base + (unsigned)(rev ? len[r] - tmax : tmax - 1) * stride;
-  }
-  {
-    const f32x4_t gzero = {0.f, 0.f, 0.f, 0.f};
-    for (int t = tmax; t < T_; ++t)
-#pragma unroll
-      for (int r = 0; r < 2; ++r) dgates[os[r] + (unsigned)(t - tmax + 1) * stride] = gzero;
-  }
-
-  float dhr[2], dcr[2], cc[2];
-  float sums[7] = {0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const size_t o = ((size_t)d * B_ + b0 + rbase + r) * H + jw;
-    dhr[r] = d_h_final ? d_h_final[o] : 0.f;
-    dcr[r] = d_c_final ? d_c_final[o] : 0.f;
-    cc[r] = (tmax > 0 && tmax - 1 < len[r]) ? cs[oa[r]] : 0.f;
-  }
-  // this wave's tile of W_h^T (rows k' of the CU's slice): hh = 0 the own-unit tile 4g + wt, hh = 1 tile wt of the peer
-  const int peer = 1 - g;
-  const int nt = (hh == 0 ? g : peer) * 4 + wt;
-  f32x4_t wf[KC];
-#pragma unroll
-  for (int kc = 0; kc < KC; ++kc)
-    wf[kc] = *reinterpret_cast<const f32x4_t*>(wp + (((size_t)nt * KSF + g * KC + kc) * 64 + lane) * 4);
-  float* ownx = reinterpret_cast<float*>(smem + 2 * DGB);  // [2 parity][4 tiles][64 lanes] x (row 2, row 3)
-
-  u64* xhdr = xch + (size_t)cid.c * CL_U64;
-  bool timed_out = false;
-  const bool fast = same_xcd<G>(xhdr, g, timed_out) && !(kflags & 1);
-  unsigned spin_limit = (kflags & 2) ? 2000u : SPIN_LIMIT;
-  if ((kflags & 2) && g == G - 1) return;                  // TEST ONLY: a member goes missing
-  f32x4_t* xs = reinterpret_cast<f32x4_t*>(xhdr + XHDR);   // [2][G dst][G src][4][64] x 16 B
-  auto uslot = [&](int par, int dst, int src_, int tile) -> f32x4_t* {
-    return xs + ((((size_t)par * G + dst) * G + src_) * 4 + tile) * 64;
-  };
-  const unsigned voff16 = (unsigned)lane * 16u;
-  const unsigned pofs = (unsigned)lane * 2u + hh;          // u64 index of this lane's two rows in a slot
-  const unsigned lwr[2] = {((unsigned)(rbase * LDG + ul * 4) * 4u) ^ lds_swz(rbase),
-                           ((unsigned)((rbase + 1) * LDG + ul * 4) * 4u) ^ lds_swz(rbase + 1)};
-  const unsigned lrd = ((unsigned)(col * LDG + rg * 4) * 4u) ^ lds_swz(col);
-
-  f32x4_t pg[2];
-  float pcp[2], pdh[2];
-  auto prefetch = [&](int s_) {                            // oa/os already hold iteration s_
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const bool act = s_ < len[r];
-      const bool ldp = (s_ > 0) && (s_ - 1 < len[r]);
-      const unsigned offl = act ? oa[r] : os[r];
-      const unsigned offn = ldp ? oa[r] + dstep : os[r];
-      pg[r] = gates[offl];
-      pcp[r] = cs[offn];
-      pdh[r] = dhout[offl];
-    }
-  };
-  if (tmax > 0) prefetch(tmax - 1);
-  __syncthreads();
-
-  auto step = [&](int s, auto PAR) {
-    constexpr int P = decltype(PAR)::value;                // parity of THIS iteration's publish
-    const int it = tmax - 1 - s;
-    // ---- 1. poll for the partial the peer published at the previous iteration (parity 1-P)
-    u64 pv = 0;
-    if (it > 0) pv = gload(uoff(reinterpret_cast<const u64*>(uslot(1 - P, g, peer, wt)), pofs));
-    // ---- 2. everything that does not need dh
-    bool act[2], ldp[2];
-    float gi[2], gq[2], gf[2], go[2], cprev[2], a_o[2], b_c[2], c_g[2], c_i[2], c_f[2];
-    unsigned off[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      act[r] = s < len[r];
-      ldp[r] = (s > 0) && (s - 1 < len[r]);
-      off[r] = act[r] ? oa[r] : os[r];
-      gi[r] = pg[r][0]; gq[r] = pg[r][1]; gf[r] = pg[r][2]; go[r] = pg[r][3];
-      cprev[r] = (act[r] && s > 0) ? pcp[r] : 0.f;
-    }
-    float tc[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) tc[r] = cftanh(cc[r]);
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      a_o[r] = tc[r] * go[r] * (1.f - go[r]);
-      b_c[r] = go[r] * (1.f - tc[r] * tc[r]);
-      c_g[r] = gi[r] * (1.f - gq[r] * gq[r]);
-      c_i[r] = gq[r] * gi[r] * (1.f - gi[r]);
-      c_f[r] = cprev[r] * gf[r] * (1.f - gf[r]);
-    }
-    const float pdhv[2] = {pdh[0], pdh[1]}, pcpv[2] = {pcp[0], pcp[1]}, curv[2] = {cc[0], cc[1]};
-#pragma unroll
-    for (int r = 0; r < 2; ++r) { oa[r] += dstep; os[r] -= stride; }
-    // ---- 3. finish the poll: both words must carry the previous iteration's tag
-    if (it > 0) {
-      const unsigned want = (((unsigned)(it - 1) >> 1) + 1u) & 1u;
-      const u64 wmask = 0x0000000100000001ull, wtag = want ? wmask : 0ull;
-      unsigned spins = 0;
-#pragma unroll 1
-      for (;;) {
-        if (__all((pv & wmask) == wtag)) break;
-        if (++spins > spin_limit) { timed_out = true; spin_limit = 0; break; }
-        pv = gload(uoff(reinterpret_cast<const u64*>(uslot(1 - P, g, peer, wt)), pofs));
-      }
-      dhr[0] += __uint_as_float((unsigned)pv & ~1u);
-      dhr[1] += __uint_as_float((unsigned)(pv >> 32) & ~1u);
-    }
-    // next iteration's saved activations: requested BEHIND the poll loop (see the bf16 kernel)
-    if (s > 0) prefetch(s - 1);
-    // ---- 4. gate gradients of the own pairs
-    float zi[2], zg[2], zf[2], zo[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const float dh = pdhv[r] + dhr[r];
-      const float d_o = dh * a_o[r];
-      const float dct = dcr[r] + dh * b_c[r] + d_o * wco;
-      const float dc = (clipz > 0.f && fabsf(curv[r]) >= clipz) ? 0.f : dct;   // asr_lstm_bwd_ex
-      const float d_g = dc * c_g[r], d_i = dc * c_i[r], d_f = dc * c_f[r];
-      dcr[r] = act[r] ? (dc * gf[r] + d_i * wci + d_f * wcf) : dcr[r];
-      dhr[r] = act[r] ? 0.f : dhr[r];
-      zi[r] = act[r] ? d_i : 0.f; zg[r] = act[r] ? d_g : 0.f;
-      zf[r] = act[r] ? d_f : 0.f; zo[r] = act[r] ? d_o : 0.f;
-      cc[r] = ldp[r] ? pcpv[r] : 0.f;
-      const f32x4_t pk = {zi[r], zg[r], zf[r], zo[r]};
-      *reinterpret_cast<f32x4_t*>(smem + P * DGB + lwr[r]) = pk;
-      dgates[off[r]] = pk;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      sums[0] += zi[r] * cprev[r]; sums[1] += zf[r] * cprev[r]; sums[2] += zo[r] * curv[r];
-      sums[3] += zi[r]; sums[4] += zg[r]; sums[5] += zf[r]; sums[6] += zo[r];
-    }
-    // ---- 5. partial dh_prev of this wave's tile from the own dG slice
-    if (s > 0) {
-      f32x4_t ac = {0.f, 0.f, 0.f, 0.f};
-      // the tile the peer waits for outranks its SIMD sibling's own-unit tile (nobody waits for that one before the
-      // next step's gate math): it is published after ~half of the SIMD's MFMA time instead of all of it
-      if (hh == 1 && !(kflags & 8)) __builtin_amdgcn_s_setprio(2);
-#pragma unroll
-      for (int kb = 0; kb < KC; kb += 8) {
-        f32x4_t afr[8];
-#pragma unroll
-        for (int kc = 0; kc < 8; ++kc) afr[kc] = *reinterpret_cast<const f32x4_t*>(smem + P * DGB + lrd + (kb + kc) * 64);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int kc = 0; kc < 8; ++kc) ac = mma_f32(afr[kc], wf[kb + kc], ac);
-      }
-      if (hh == 1) {                                       // the peer's units: publish, every word tagged
-        const unsigned tag = (((unsigned)it >> 1) + 1u) & 1u;
-        f32x4_t o;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) o[i] = __uint_as_float((__float_as_uint(ac[i]) & ~1u) | tag);
-        xstore16(uslot(P, peer, g, wt), voff16, o, fast);
-        __builtin_amdgcn_s_setprio(0);
-      } else {                                             // own units: rows 0,1 stay, rows 2,3 -> partner wave
-        dhr[0] += ac[0];
-        dhr[1] += ac[1];
-        float* o = ownx + ((P * 4 + wt) * 64 + lane) * 2;
-        o[0] = ac[2];
-        o[1] = ac[3];
-      }
-    }
-    __syncthreads();                                       // hand-over visible before the partner's next step
-    if (s > 0 && hh == 1) {
-      const float* o = ownx + ((P * 4 + wt) * 64 + lane) * 2;
-      dhr[0] += o[0];
-      dhr[1] += o[1];
-    }
-  };
-  int s = tmax - 1;
-  for (; s >= 1; s -= 2) {
-    step(s, std::integral_constant<int, 0>{});
-    step(s - 1, std::integral_constant<int, 1>{});
-  }
-  if (s == 0) step(0, std::integral_constant<int, 0>{});
-
-  if (timed_out) atomicOr(err, 2u);
-  if (dpeep_part) {
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-      sums[k] += __shfl_xor(sums[k], 16, 64);
-      sums[k] += __shfl_xor(sums[k], 32, 64);
-    }
-    __syncthreads();
-    float* red = reinterpret_cast<float*>(smem);           // [7][HS]
-    if (hh == 1 && rg == 0) {
-#pragma unroll
-      for (int k = 0; k < 7; ++k) red[k * HS + ul] = sums[k];
-    }
-    __syncthreads();
-    if (hh == 0 && rg == 0) {
-      float* p = dpeep_part + ((size_t)cid.tile * ndir + d) * 7 * H;
-#pragma unroll
-      for (int k = 0; k < 7; ++k) p[k * H + jw] = sums[k] + red[k * HS + ul];
-    }
-  }
-}
-
-// BPTT, fp32 operands, GENERAL form: clusters of G = H / HSU CUs (any even G), four waves per CU at HSU = 32 (one per SIMD:
-// the fp32 step is bound by the SIMD's matrix pipe -- 32 cycles per K = 4 MFMA -- so a wave alone on its SIMD is what pays).
-// Tile deal as in the bf16 kernel's each-tile-once arrangement: a CU owns TPC = HSU / 16 unit tiles and multiplies its dG
-// slice by W_h^T for ALL H / 16 tiles; the TPC own + TPC (G - 1) foreign tiles are dealt G / 2 per wave -- an hh = 0 wave
-// takes its own-unit tile (rows 2,3 handed to the hh = 1 partner through LDS) and G/2 - 1 foreign ones, an hh = 1 wave
-// G / 2 foreign ones; foreign partials go out as 16-byte stores of self-tagged fp32 words, the chains of a wave's
-// foreign tiles advance together and the stores follow in one run.  H = 128 runs on four CUs (the two-CU kernel above:
-// 2011 us per launch at T = 778), H = 256 / 320 / 512 -- which had no fp32 cluster kernel -- on 8 / 10 / 16.
-template <int H, int HSU>
-__global__ __launch_bounds__(HSU * 8, 1) void lstm_bwd_cluster_f32_kernel(
-    int T_, int B_, int ndir, const float* __restrict__ dhout, const f32x4_t* __restrict__ gates,
-    const float* __restrict__ cs, const float* __restrict__ whpb, const float* __restrict__ peep,
-    const int32_t* __restrict__ seq_len, const float* __restrict__ d_c_final,
-    const float* __restrict__ d_h_final, f32x4_t* __restrict__ dgates, float* __restrict__ dpeep_part,
-    u64* __restrict__ xch, unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords, float clipz, int tile0, int ntl) {
-  zero_next_area(znext, zwords);
-  constexpr int G = H / HSU;
-  static_assert(G % 2 == 0 && G >= 2 && G <= XHDR, "even number of CUs per cluster");
-  constexpr int TPC = HSU / 16, NWAVES = 2 * TPC;
-  constexpr int KC = 4 * HSU / 16;           // fragments (k = 16) of this CU's slice of k'
-  constexpr int KSF = 4 * H / 16;            // fragments of the full packing
-  constexpr int LDG = 4 * HSU + 4;           // floats per row of the dG image
-  constexpr int NF = G / 2;                  // tile slots per wave
-  constexpr size_t CL_U64 = XHDR + (size_t)2 * G * G * TPC * 64 * 2;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int DGB = 16 * LDG * 4;                        // bytes per dG image
-
-  const ClusterId cid = cluster_id<G>(ndir, tile0, ntl);
-  if (!cid.valid) return;
-  const int g = cid.g, d = cid.d, b0 = cid.tile * 16;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int col = lane & 15, rg = lane >> 4;
-  const int hh = wave / TPC, wt = wave % TPC;
-  const bool rev = (d == 1);
-  const float* wp = whpb + (size_t)d * H * 4 * H;
-  const int ul = wt * 16 + col;
-  const unsigned jw = g * HSU + ul;
-  const int rbase = rg * 4 + hh * 2;
-
-  int len[2];
-  int tmax = 0;
-#pragma unroll
-  for (int r = 0; r < 2; ++r) len[r] = seq_len[b0 + rbase + r];
-  for (int i = 0; i < 16; ++i) tmax = max(tmax, seq_len[b0 + i]);
-  tmax = min(tmax, T_);
-
-  const float wci = peep ? peep[(d * 3 + 0) * H + jw] : 0.f;
-  const float wcf = peep ? peep[(d * 3 + 1) * H + jw] : 0.f;
-  const float wco = peep ? peep[(d * 3 + 2) * H + jw] : 0.f;
-
-  const unsigned stride = (unsigned)B_ * ndir * H;
-  const unsigned dstep = rev ? stride : 0u - stride;
-  unsigned oa[2], os[2];
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const unsigned base = ((unsigned)(b0 + rbase + r) * ndir + d) * H + jw;
-    os[r] = base + (unsigned)(tmax - 1) * stride;
-    oa[r] = base + (unsigned)(rev ? len[r] - tmax : tmax - 1) * stride;
-  }
-  {
-    const f32x4_t gzero = {0.f, 0.f, 0.f, 0.f};
-    for (int t = tmax; t < T_; ++t)
-#pragma unroll
-      for (int r = 0; r < 2; ++r) dgates[os[r] + (unsigned)(t - tmax + 1) * stride] = gzero;
-  }
-
-  float dhr[2], dcr[2], cc[2];
-  float sums[7] = {0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const size_t o = ((size_t)d * B_ + b0 + rbase + r) * H + jw;
-    dhr[r] = d_h_final ? d_h_final[o] : 0.f;
-    dcr[r] = d_c_final ? d_c_final[o] : 0.f;
-    cc[r] = (tmax > 0 && tmax - 1 < len[r]) ? cs[oa[r]] : 0.f;
-  }
-  // tile slots: i < NF - 1: foreign tile f = wave + NWAVES i;  slot NF - 1: hh = 0 the own tile, hh = 1 foreign tile
-  // f = NWAVES (NF - 1) + wt.  Foreign index f -> destination CU (f / TPC, skipping g), its tile f % TPC.
-  auto ftile = [&](int f) { const int q = f / TPC; return ((q + (q >= g ? 1 : 0)) * TPC) | (f % TPC); };
-  int nt_f[NF];
-#pragma unroll
-  for (int i = 0; i < NF; ++i)
-    nt_f[i] = (i < NF - 1) ? ftile(wave + NWAVES * i) : (hh == 1 ? ftile(NWAVES * (NF - 1) + wt) : g * TPC + wt);
-  f32x4_t wf[NF][KC];
-#pragma unroll
-  for (int i = 0; i < NF; ++i)
-#pragma unroll
-    for (int kc = 0; kc < KC; ++kc)
-      wf[i][kc] = *reinterpret_cast<const f32x4_t*>(wp + (((size_t)nt_f[i] * KSF + g * KC + kc) * 64 + lane) * 4);
-  float* ownx = reinterpret_cast<float*>(smem + 2 * DGB);  // [2 parity][TPC tiles][64 lanes] x (row 2, row 3)
-
-  u64* xhdr = xch + (size_t)cid.c * CL_U64;
-  bool timed_out = false;
-  const bool fast = same_xcd<G>(xhdr, g, timed_out) && !(kflags & 1);
-  unsigned spin_limit = (kflags & 2) ? 2000u : SPIN_LIMIT;
-  if ((kflags & 2) && g == G - 1) return;                  // TEST ONLY: a member goes missing
-  f32x4_t* xs = reinterpret_cast<f32x4_t*>(xhdr + XHDR);   // [2][G dst][G src][TPC][64] x 16 B
-  auto uslot = [&](int par, int dst, int src_, int tile) -> f32x4_t* {
-    return xs + ((((size_t)par * G + dst) * G + src_) * TPC + tile) * 64;
-  };
-  const unsigned voff16 = (unsigned)lane * 16u;
-  const unsigned pofs = (unsigned)lane * 2u + hh;          // u64 index of this lane's two rows in a slot
-  const unsigned lwr[2] = {((unsigned)(rbase * LDG + ul * 4) * 4u) ^ lds_swz(rbase),
-                           ((unsigned)((rbase + 1) * LDG + ul * 4) * 4u) ^ lds_swz(rbase + 1)};
-  const unsigned lrd = ((unsigned)(col * LDG + rg * 4) * 4u) ^ lds_swz(col);
-
-  f32x4_t pg[2];
-  float pcp[2], pdh[2];
-  if (tmax > 0) {
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const int s_ = tmax - 1;
-      const bool act = s_ < len[r];
-      const bool ldp = (s_ > 0) && (s_ - 1 < len[r]);
-      pg[r] = gates[act ? oa[r] : os[r]];
-      pcp[r] = cs[ldp ? oa[r] + dstep : os[r]];
-      pdh[r] = dhout[act ? oa[r] : os[r]];
-    }
-  }
-  __syncthreads();
-
-  auto step = [&](int s, auto PAR) {
-    // step boundary pinned (see the bf16 BPTT kernel): neutral at H = 128 / 256, 7.6 -> 4.4 ms per launch at H = 512, B = 32
-    __builtin_amdgcn_sched_barrier(0);
-    constexpr int P = decltype(PAR)::value;                // parity of THIS iteration's publish
-    const int it = tmax - 1 - s;
-    // ---- 1. polls for the partials the peers published at the previous iteration (parity 1-P)
-    u64 pv[G - 1];
-    if (it > 0) {
-#pragma unroll
-      for (int k = 0; k < G - 1; ++k)
-        pv[k] = gload(uoff(reinterpret_cast<const u64*>(uslot(1 - P, g, k + (k >= g ? 1 : 0), wt)), pofs));
-    }
-    // ---- 2. everything that does not need dh
-    bool act[2], ldp[2];
-    float gi[2], gq[2], gf[2], go[2], cprev[2], a_o[2], b_c[2], c_g[2], c_i[2], c_f[2];
-    unsigned off[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      act[r] = s < len[r];
-      ldp[r] = (s > 0) && (s - 1 < len[r]);
-      off[r] = act[r] ? oa[r] : os[r];
-      gi[r] = pg[r][0]; gq[r] = pg[r][1]; gf[r] = pg[r][2]; go[r] = pg[r][3];
-      cprev[r] = (act[r] && s > 0) ? pcp[r] : 0.f;
-    }
-    float tc[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) tc[r] = cftanh(cc[r]);
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      a_o[r] = tc[r] * go[r] * (1.f - go[r]);
-      b_c[r] = go[r] * (1.f - tc[r] * tc[r]);
-      c_g[r] = gi[r] * (1.f - gq[r] * gq[r]);
-      c_i[r] = gq[r] * gi[r] * (1.f - gi[r]);
-      c_f[r] = cprev[r] * gf[r] * (1.f - gf[r]);
-    }
-    float pdh0 = pdh[0], pdh1 = pdh[1], pcp0 = pcp[0], pcp1 = pcp[1];
-    const float cur0 = cc[0], cur1 = cc[1];
-    // everything that reads the values fetched one iteration ago is pinned here, ahead of the next fetch (see the bf16 kernel)
-    asm volatile("" : "+v"(pdh0), "+v"(pdh1), "+v"(pcp0), "+v"(pcp1), "+v"(cprev[0]), "+v"(cprev[1]));
-    asm volatile("" : "+v"(c_g[0]), "+v"(c_g[1]), "+v"(c_i[0]), "+v"(c_i[1]), "+v"(c_f[0]), "+v"(c_f[1]));
-    asm volatile("" : "+v"(a_o[0]), "+v"(a_o[1]), "+v"(b_c[0]), "+v"(b_c[1]), "+v"(gf[0]), "+v"(gf[1]));
-#pragma unroll
-    for (int r = 0; r < 2; ++r) { oa[r] += dstep; os[r] -= stride; }
-    // ---- 3. finish the polls: every word must carry the previous iteration's tag
-    if (it > 0) {
-      const unsigned want = (((unsigned)(it - 1) >> 1) + 1u) & 1u;
-      const u64 wmask = 0x0000000100000001ull, wtag = want ? wmask : 0ull;
-      unsigned spins = 0;
-#pragma unroll 1
-      for (;;) {
-        bool ok = true;
-#pragma unroll
-        for (int k = 0; k < G - 1; ++k) ok = ok && ((pv[k] & wmask) == wtag);
-        if (__all(ok)) break;
-        if (++spins > spin_limit) { timed_out = true; spin_limit = 0; break; }
-#pragma unroll
-        for (int k = 0; k < G - 1; ++k)
-          pv[k] = gload(uoff(reinterpret_cast<const u64*>(uslot(1 - P, g, k + (k >= g ? 1 : 0), wt)), pofs));
-      }
-      float add0 = 0.f, add1 = 0.f;
-#pragma unroll
-      for (int k = 0; k < G - 1; ++k) {                     // fixed order
-        add0 += __uint_as_float((unsigned)pv[k] & ~1u);
-        add1 += __uint_as_float((unsigned)(pv[k] >> 32) & ~1u);
-      }
-      dhr[0] += add0;
-      dhr[1] += add1;
-    }
-    // next iteration's saved activations: unconditional (the last iteration re-fetches its own rows) and pinned BEHIND
-    // the poll loop by a compiler barrier
-    {
-      asm volatile("" ::: "memory");
-      const bool more = s > 0;
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        const bool actn = s - 1 < len[r];
-        const bool ldpn = (s - 1 > 0) && (s - 2 < len[r]);
-        const unsigned offl = more ? (actn ? oa[r] : os[r]) : off[r];
-        const unsigned offn = more ? (ldpn ? oa[r] + dstep : os[r]) : off[r];
-        pg[r] = gates[offl];
-        pcp[r] = cs[offn];
-        pdh[r] = dhout[offl];
-      }
-    }
-    // ---- 4. gate gradients of the own pairs
-    const float pdhv[2] = {pdh0, pdh1}, pcpv[2] = {pcp0, pcp1}, curv[2] = {cur0, cur1};
-    float zi[2], zg[2], zf[2], zo[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const float dh = pdhv[r] + dhr[r];
-      const float d_o = dh * a_o[r];
-      const float dct = dcr[r] + dh * b_c[r] + d_o * wco;
-      const float dc = (clipz > 0.f && fabsf(curv[r]) >= clipz) ? 0.f : dct;   // asr_lstm_bwd_ex
-      const float d_g = dc * c_g[r], d_i = dc * c_i[r], d_f = dc * c_f[r];
-      dcr[r] = act[r] ? (dc * gf[r] + d_i * wci + d_f * wcf) : dcr[r];
-      dhr[r] = act[r] ? 0.f : dhr[r];
-      zi[r] = act[r] ? d_i : 0.f; zg[r] = act[r] ? d_g : 0.f;
-      zf[r] = act[r] ? d_f : 0.f; zo[r] = act[r] ? d_o : 0.f;
-      cc[r] = ldp[r] ? pcpv[r] : 0.f;
-      const f32x4_t pk = {zi[r], zg[r], zf[r], zo[r]};
-      *reinterpret_cast<f32x4_t*>(smem + P * DGB + lwr[r]) = pk;
-      dgates[off[r]] = pk;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      sums[0] += zi[r] * cprev[r]; sums[1] += zf[r] * cprev[r]; sums[2] += zo[r] * curv[r];
-      sums[3] += zi[r]; sums[4] += zg[r]; sums[5] += zf[r]; sums[6] += zo[r];
-    }
-    // ---- 5. partial dh_prev of this wave's tiles from the own dG slice
-    if (s > 0) {
-      f32x4_t afr[KC];
-#pragma unroll
-      for (int kc = 0; kc < KC; ++kc) afr[kc] = *reinterpret_cast<const f32x4_t*>(smem + P * DGB + lrd + kc * 64);
-      __builtin_amdgcn_sched_barrier(0);
-      f32x4_t ac[NF];
-#pragma unroll
-      for (int i = 0; i < NF; ++i) ac[i] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int kc = 0; kc < KC; ++kc)
-#pragma unroll
-        for (int i = 0; i < NF; ++i) ac[i] = mma_f32(afr[kc], wf[i][kc], ac[i]);
-      const unsigned tag = (((unsigned)it >> 1) + 1u) & 1u;
-      auto tagged = [&](const f32x4_t& a) {
-        f32x4_t o;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) o[i] = __uint_as_float((__float_as_uint(a[i]) & ~1u) | tag);
-        return o;
-      };
-      if (fast) {
-#pragma unroll
-        for (int i = 0; i < NF; ++i)
-          if (i < NF - 1 || hh == 1) xstore16(uslot(P, nt_f[i] / TPC, g, nt_f[i] % TPC), voff16, tagged(ac[i]), true);
-      } else {
-#pragma unroll
-        for (int i = 0; i < NF; ++i)
-          if (i < NF - 1 || hh == 1) xstore16(uslot(P, nt_f[i] / TPC, g, nt_f[i] % TPC), voff16, tagged(ac[i]), false);
-      }
-      if (hh == 0) {                                       // own units: rows 0,1 stay, rows 2,3 -> partner wave
-        dhr[0] += ac[NF - 1][0];
-        dhr[1] += ac[NF - 1][1];
-        float* o = ownx + ((P * TPC + wt) * 64 + lane) * 2;
-        o[0] = ac[NF - 1][2];
-        o[1] = ac[NF - 1][3];
-      }
-    }
-    __syncthreads();                                       // hand-over visible before the partner's next step
-    if (s > 0 && hh == 1) {
-      const float* o = ownx + ((P * TPC + wt) * 64 + lane) * 2;
-      dhr[0] += o[0];
-      dhr[1] += o[1];
-    }
-  };
-  int s = tmax - 1;
-  for (; s >= 1; s -= 2) {
-    step(s, std::integral_constant<int, 0>{});
-    step(s - 1, std::integral_constant<int, 1>{});
-  }
-  if (s == 0) step(0, std::integral_constant<int, 0>{});
-
-  if (timed_out) atomicOr(err, 2u);
-  if (dpeep_part) {
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-      sums[k] += __shfl_xor(sums[k], 16, 64);
-      sums[k] += __shfl_xor(sums[k], 32, 64);
-    }
-    __syncthreads();
-    float* red = reinterpret_cast<float*>(smem);           // [7][HSU]
-    if (hh == 1 && rg == 0) {
-#pragma unroll
-      for (int k = 0; k < 7; ++k) red[k * HSU + ul] = sums[k];
-    }
-    __syncthreads();
-    if (hh == 0 && rg == 0) {
-      float* p = dpeep_part + ((size_t)cid.tile * ndir + d) * 7 * H;
-#pragma unroll
-      for (int k = 0; k < 7; ++k) p[k * H + jw] = sums[k] + red[k * HSU + ul];
-    }
-  }
-}
-
-// BPTT of the fp32-operand clusters on the bf16 matrix pipe (three-term split, see lstm_fwd_cluster_f32s_kernel)
-template <int H, int HSU>
-__global__ __launch_bounds__(HSU * 8, 1) void lstm_bwd_cluster_f32s_kernel(
-    int T_, int B_, int ndir, const float* __restrict__ dhout, const f32x4_t* __restrict__ gates,
-    const float* __restrict__ cs, const float* __restrict__ whpb, const float* __restrict__ peep,
-    const int32_t* __restrict__ seq_len, const float* __restrict__ d_c_final,
-    const float* __restrict__ d_h_final, f32x4_t* __restrict__ dgates, float* __restrict__ dpeep_part,
-    u64* __restrict__ xch, unsigned* __restrict__ err, int kflags, u64* __restrict__ znext, unsigned zwords, float clipz, int tile0, int ntl) {
-  zero_next_area(znext, zwords);
-  constexpr int G = H / HSU;
-  static_assert(G % 2 == 0 && G >= 2 && G <= XHDR, "even number of CUs per cluster");
-  constexpr int TPC = HSU / 16, NWAVES = 2 * TPC;
-  constexpr int KC = 4 * HSU / 32;           // chunks (k = 32) of this CU's slice of k'
-  constexpr int KC16 = 4 * HSU / 16;         // ... in fragments of the fp32 weight packing
-  constexpr int KSF = 4 * H / 16;            // fragments of the full packing
-  constexpr int LDG = 4 * HSU + 8;           // bf16 elements per row of a dG term image (17 x 16 B)
-  constexpr int NF = G / 2;                  // tile slots per wave
-  constexpr size_t CL_U64 = XHDR + (size_t)2 * G * G * TPC * 64 * 2;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  constexpr int PLB = 16 * LDG * 2;                        // bytes of one term image
-  constexpr int DGB = 3 * PLB;                             // bytes per dG image (three bf16 terms)
-
-  const ClusterId cid = cluster_id<G>(ndir, tile0, ntl);
-  if (!cid.valid) return;
-  const int g = cid.g, d = cid.d, b0 = cid.tile * 16;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int col = lane & 15, rg = lane >> 4;
-  const int hh = wave / TPC, wt = wave % TPC;
-  const bool rev = (d == 1);
-  const float* wp = whpb + (size_t)d * H * 4 * H;
-  const int ul = wt * 16 + col;
-  const unsigned jw = g * HSU + ul;
-  const int rbase = rg * 4 + hh * 2;
-
-  int len[2];
-  int tmax = 0;
-#pragma unroll
-  for (int r = 0; r < 2; ++r) len[r] = seq_len[b0 + rbase + r];
-  for (int i = 0; i < 16; ++i) tmax = max(tmax, seq_len[b0 + i]);
-  tmax = min(tmax, T_);
-
-  const float wci = peep ? peep[(d * 3 + 0) * H + jw] : 0.f;
-  const float wcf = peep ? peep[(d * 3 + 1) * H + jw] : 0.f;
-  const float wco = peep ? peep[(d * 3 + 2) * H + jw] : 0.f;
-
-  const unsigned stride = (unsigned)B_ * ndir * H;
-  const unsigned dstep = rev ? stride : 0u - stride;
-  unsigned oa[2], os[2];
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const unsigned base = ((unsigned)(b0 + rbase + r) * ndir + d) * H + jw;
-    os[r] = base + (unsigned)(tmax - 1) * stride;
-    oa[r] = base + (unsigned)(rev ? len[r] - tmax : tmax - 1) * stride;
-  }
-  // inactive rows read nothing that is used: their fetches go to one parked position per row (frame tmax - 1)
-  const unsigned opark[2] = {os[0], os[1]};
-  {
-    const f32x4_t gzero = {0.f, 0.f, 0.f, 0.f};
-    for (int t = tmax; t < T_; ++t)
-#pragma unroll
-      for (int r = 0; r < 2; ++r) dgates[os[r] + (unsigned)(t - tmax + 1) * stride] = gzero;
-  }
-
-  float dhr[2], dcr[2], cc[2];
-  float sums[7] = {0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-  for (int r = 0; r < 2; ++r) {
-    const size_t o = ((size_t)d * B_ + b0 + rbase + r) * H + jw;
-    dhr[r] = d_h_final ? d_h_final[o] : 0.f;
-    dcr[r] = d_c_final ? d_c_final[o] : 0.f;
-    cc[r] = (tmax > 0 && tmax - 1 < len[r]) ? cs[oa[r]] : 0.f;
-  }
-  // tile slots: i < NF - 1: foreign tile f = wave + NWAVES i;  slot NF - 1: hh = 0 the own tile, hh = 1 foreign tile
-  // f = NWAVES (NF - 1) + wt.  Foreign index f -> destination CU (f / TPC, skipping g), its tile f % TPC.
-  auto ftile = [&](int f) { const int q = f / TPC; return ((q + (q >= g ? 1 : 0)) * TPC) | (f % TPC); };
-  int nt_f[NF];
-#pragma unroll
-  for (int i = 0; i < NF; ++i)
-    nt_f[i] = (i < NF - 1) ? ftile(wave + NWAVES * i) : (hh == 1 ? ftile(NWAVES * (NF - 1) + wt) : g * TPC + wt);
-  bf16x8_t wf[NF][KC][3];                  // W_h^T fragments, re-cut into k = 32 chunks and split into three bf16 terms
-#pragma unroll
-  for (int i = 0; i < NF; ++i)
-#pragma unroll
-    for (int kc = 0; kc < KC; ++kc)
-      load_split_frag(wp + ((size_t)nt_f[i] * KSF + g * KC16) * 256, kc, rg, col, wf[i][kc]);
-  float* ownx = reinterpret_cast<float*>(smem + 2 * DGB);  // [2 parity][TPC tiles][64 lanes] x (row 2, row 3)
-
-  u64* xhdr = xch + (size_t)cid.c * CL_U64;
-  bool timed_out = false;
-  const bool fast = same_xcd<G>(xhdr, g, timed_out) && !(kflags & 1);
-  unsigned spin_limit = (kflags & 2) ? 2000u : SPIN_LIMIT;
-  if ((kflags & 2) && g == G - 1) return;                  // TEST ONLY: a member goes missing
-  f32x4_t* xs = reinterpret_cast<f32x4_t*>(xhdr + XHDR);   // [2][G dst][G src][TPC][64] x 16 B
-  auto uslot = [&](int par, int dst, int src_, int tile) -> f32x4_t* {
-    return xs + ((((size_t)par * G + dst) * G + src_) * TPC + tile) * 64;
-  };
-  const unsigned voff16 = (unsigned)lane * 16u;
-  const unsigned pofs = (unsigned)lane * 2u + hh;          // u64 index of this lane's two rows in a slot
-  const unsigned lwr[2] = {((unsigned)(rbase * LDG + ul * 4) * 2u) ^ lds_swz(rbase),
-                           ((unsigned)((rbase + 1) * LDG + ul * 4) * 2u) ^ lds_swz(rbase + 1)};
-  const unsigned lrd = ((unsigned)(col * LDG + rg * 8) * 2u) ^ lds_swz(col);
-
-  f32x4_t pg[2];
-  float pcp[2], pdh[2];
-  if (tmax > 0) {
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const int s_ = tmax - 1;
-      const bool act = s_ < len[r];
-      const bool ldp = (s_ > 0) && (s_ - 1 < len[r]);
-      pg[r] = gates[act ? oa[r] : opark[r]];
-      pcp[r] = cs[ldp ? oa[r] + dstep : opark[r]];
-      pdh[r] = dhout[act ? oa[r] : opark[r]];
-    }
-  }
-  __syncthreads();
-
-  auto step = [&](int s, auto PAR) {
-    // step boundary pinned (see the bf16 BPTT kernel): neutral at H = 128 / 256, 7.6 -> 4.4 ms per launch at H = 512, B = 32
-    __builtin_amdgcn_sched_barrier(0);
-    constexpr int P = decltype(PAR)::value;                // parity of THIS iteration's publish
-    const int it = tmax - 1 - s;
-    // ---- 1. polls for the partials the peers published at the previous iteration (parity 1-P)
-    u64 pv[G - 1];
-    if (it > 0) {
-#pragma unroll
-      for (int k = 0; k < G - 1; ++k)
-        pv[k] = gload(uoff(reinterpret_cast<const u64*>(uslot(1 - P, g, k + (k >= g ? 1 : 0), wt)), pofs));
-    }
-    // ---- 2. everything that does not need dh
-    bool act[2], ldp[2];
-    float gi[2], gq[2], gf[2], go[2], cprev[2], a_o[2], b_c[2], c_g[2], c_i[2], c_f[2];
-    unsigned off[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      act[r] = s < len[r];
-      ldp[r] = (s > 0) && (s - 1 < len[r]);
-      off[r] = act[r] ? oa[r] : os[r];
-      gi[r] = pg[r][0]; gq[r] = pg[r][1]; gf[r] = pg[r][2]; go[r] = pg[r][3];
-      cprev[r] = (act[r] && s > 0) ? pcp[r] : 0.f;
-    }
-    float tc[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) tc[r] = cftanh(cc[r]);
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      a_o[r] = tc[r] * go[r] * (1.f - go[r]);
-      b_c[r] = go[r] * (1.f - tc[r] * tc[r]);
-      c_g[r] = gi[r] * (1.f - gq[r] * gq[r]);
-      c_i[r] = gq[r] * gi[r] * (1.f - gi[r]);
-      c_f[r] = cprev[r] * gf[r] * (1.f - gf[r]);
-    }
-    float pdh0 = pdh[0], pdh1 = pdh[1], pcp0 = pcp[0], pcp1 = pcp[1];
-    const float cur0 = cc[0], cur1 = cc[1];
-    // everything that reads the values fetched one iteration ago is pinned here, ahead of the next fetch (see the bf16 kernel)
-    asm volatile("" : "+v"(pdh0), "+v"(pdh1), "+v"(pcp0), "+v"(pcp1), "+v"(cprev[0]), "+v"(cprev[1]));
-    asm volatile("" : "+v"(c_g[0]), "+v"(c_g[1]), "+v"(c_i[0]), "+v"(c_i[1]), "+v"(c_f[0]), "+v"(c_f[1]));
-    asm volatile("" : "+v"(a_o[0]), "+v"(a_o[1]), "+v"(b_c[0]), "+v"(b_c[1]), "+v"(gf[0]), "+v"(gf[1]));
-#pragma unroll
-    for (int r = 0; r < 2; ++r) { oa[r] += dstep; os[r] -= stride; }
-    // ---- 3. finish the polls: every word must carry the previous iteration's tag
-    if (it > 0) {
-      const unsigned want = (((unsigned)(it - 1) >> 1) + 1u) & 1u;
-      const u64 wmask = 0x0000000100000001ull, wtag = want ? wmask : 0ull;
-      unsigned spins = 0;
-#pragma unroll 1
-      for (;;) {
-        bool ok = true;
-#pragma unroll
-        for (int k = 0; k < G - 1; ++k) ok = ok && ((pv[k] & wmask) == wtag);
-        if (__all(ok)) break;
-        if (++spins > spin_limit) { timed_out = true; spin_limit = 0; break; }
-#pragma unroll
-        for (int k = 0; k < G - 1; ++k)
-          pv[k] = gload(uoff(reinterpret_cast<const u64*>(uslot(1 - P, g, k + (k >= g ? 1 : 0), wt)), pofs));
-      }
-      float add0 = 0.f, add1 = 0.f;
-#pragma unroll
-      for (int k = 0; k < G - 1; ++k) {                     // fixed order
-        add0 += __uint_as_float((unsigned)pv[k] & ~1u);
-        add1 += __uint_as_float((unsigned)(pv[k] >> 32) & ~1u);
-      }
-      dhr[0] += add0;
-      dhr[1] += add1;
-    }
-    // next iteration's saved activations: unconditional (the last iteration re-fetches its own rows) and pinned BEHIND
-    // the poll loop by a compiler barrier
-    {
-      asm volatile("" ::: "memory");
-      const bool more = s > 0;
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        const bool actn = s - 1 < len[r];
-        const bool ldpn = (s - 1 > 0) && (s - 2 < len[r]);
-        const unsigned offl = more ? (actn ? oa[r] : opark[r]) : off[r];
-        const unsigned offn = more ? (ldpn ? oa[r] + dstep : opark[r]) : off[r];
-        pg[r] = gates[offl];
-        pcp[r] = cs[offn];
-        pdh[r] = dhout[offl];
-      }
-    }
-    // ---- 4. gate gradients of the own pairs
-    const float pdhv[2] = {pdh0, pdh1}, pcpv[2] = {pcp0, pcp1}, curv[2] = {cur0, cur1};
-    float zi[2], zg[2], zf[2], zo[2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      const float dh = pdhv[r] + dhr[r];
-      const float d_o = dh * a_o[r];
-      const float dct = dcr[r] + dh * b_c[r] + d_o * wco;
-      const float dc = (clipz > 0.f && fabsf(curv[r]) >= clipz) ? 0.f : dct;   // asr_lstm_bwd_ex
-      const float d_g = dc * c_g[r], d_i = dc * c_i[r], d_f = dc * c_f[r];
-      dcr[r] = act[r] ? (dc * gf[r] + d_i * wci + d_f * wcf) : dcr[r];
-      dhr[r] = act[r] ? 0.f : dhr[r];
-      zi[r] = act[r] ? d_i : 0.f; zg[r] = act[r] ? d_g : 0.f;
-      zf[r] = act[r] ? d_f : 0.f; zo[r] = act[r] ? d_o : 0.f;
-      cc[r] = ldp[r] ? pcpv[r] : 0.f;
-      const f32x4_t pk = {zi[r], zg[r], zf[r], zo[r]};
-      typedef __attribute__((ext_vector_type(4))) unsigned short us4_t;
-      us4_t tq[3];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        unsigned short t[3];
-        split3(pk[q], t);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) tq[k][q] = t[k];
-      }
-#pragma unroll
-      for (int k = 0; k < 3; ++k) *reinterpret_cast<us4_t*>(smem + P * DGB + k * PLB + lwr[r]) = tq[k];
-      dgates[off[r]] = pk;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-      sums[0] += zi[r] * cprev[r]; sums[1] += zf[r] * cprev[r]; sums[2] += zo[r] * curv[r];
-      sums[3] += zi[r]; sums[4] += zg[r]; sums[5] += zf[r]; sums[6] += zo[r];
-    }
-    // ---- 5. partial dh_prev of this wave's tiles from the own dG slice
-    if (s > 0) {
-      bf16x8_t afr[KC][3];
-#pragma unroll
-      for (int kc = 0; kc < KC; ++kc)
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-          afr[kc][k] = *reinterpret_cast<const bf16x8_t*>(smem + P * DGB + k * PLB + lrd + kc * 64);
-      __builtin_amdgcn_sched_barrier(0);
-      f32x4_t ac[NF];
-#pragma unroll
-      for (int i = 0; i < NF; ++i) ac[i] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int kc = 0; kc < KC; ++kc)
-#pragma unroll
-        for (int i = 0; i < NF; ++i) ac[i] = mma_s3(afr[kc], wf[i][kc], ac[i]);
-      const unsigned tag = (((unsigned)it >> 1) + 1u) & 1u;
-      auto tagged = [&](const f32x4_t& a) {
-        f32x4_t o;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) o[i] = __uint_as_float((__float_as_uint(a[i]) & ~1u) | tag);
-        return o;
-      };
-      if (fast) {
-#pragma unroll
-        for (int i = 0; i < NF; ++i)
-          if (i < NF - 1 || hh == 1) xstore16(uslot(P, nt_f[i] / TPC, g, nt_f[i] % TPC), voff16, tagged(ac[i]), true);
-      } else {
-#pragma unroll
-        for (int i = 0; i < NF; ++i)
-          if (i < NF - 1 || hh == 1) xstore16(uslot(P, nt_f[i] / TPC, g, nt_f[i] % TPC), voff16, tagged(ac[i]), false);
-      }
-      if (hh == 0) {                                       // own units: rows 0,1 stay, rows 2,3 -> partner wave
-        dhr[0] += ac[NF - 1][0];
-        dhr[1] += ac[NF - 1][1];
-        float* o = ownx + ((P * TPC + wt) * 64 + lane) * 2;
-        o[0] = ac[NF - 1][2];
-        o[1] = ac[NF - 1][3];
-      }
-    }
-    __syncthreads();                                       // hand-over visible before the partner's next step
-    if (s > 0 && hh == 1) {
-      const float* o = ownx + ((P * TPC + wt) * 64 + lane) * 2;
-      dhr[0] += o[0];
-      dhr[1] += o[1];
-    }
-  };
-  int s = tmax - 1;
-  for (; s >= 1; s -= 2) {
-    step(s, std::integral_constant<int, 0>{});
-    step(s - 1, std::integral_constant<int, 1>{});
-  }
-  if (s == 0) step(0, std::integral_constant<int, 0>{});
-
-  if (timed_out) atomicOr(err, 2u);
-  if (dpeep_part) {
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-      sums[k] += __shfl_xor(sums[k], 16, 64);
-      sums[k] += __shfl_xor(sums[k], 32, 64);
-    }
-    __syncthreads();
-    float* red = reinterpret_cast<float*>(smem);           // [7][HSU]
-    if (hh == 1 && rg == 0) {
-#pragma unroll
-      for (int k = 0; k < 7; ++k) red[k * HSU + ul] = sums[k];
-    }
-    __syncthreads();
-    if (hh == 0 && rg == 0) {
-      float* p = dpeep_part + ((size_t)cid.tile * ndir + d) * 7 * H;
-#pragma unroll
-      for (int k = 0; k < 7; ++k) p[k * H + jw] = sums[k] + red[k * HSU + ul];
-    }
-  }
-}
-
 static unsigned long long* g_cdbg_host = nullptr;
 static void cdbg_setup() {
   static bool done = false;
@@ -3330,191 +1271,7 @@ static void cdbg_setup() {
   (void)hipMemset(g_cdbg_host, 0, 1280 * sizeof(unsigned long long));
   (void)hipMemcpyToSymbol(HIP_SYMBOL(g_cdbg), &g_cdbg_host, sizeof(g_cdbg_host));
 }
-static int g_dflags = -1;
-// bit 4 (16): force the placement-independent write-through exchange
-// bit 5 (32): invert the default choice of the EARLY forward variant (A/B measurements)
-// bit 7 (128): BPTT kernel requests the next iteration's saved activations ahead of the poll loop (the old place; A/B)
-// bit 8 (256): fp32 BPTT kernel without the priority of the published tile's MFMAs (A/B)
-// bit 9 (512): clusters of H/64 CUs x eight waves instead of H/32 CUs x four waves: bf16 H = 256 / 512 (H = 320 has only
-//              that form), fp32 H = 128; fp32 H = 256 / 320 / 512 have no such form and fall to the single-CU kernels
-// bit 10 (1024): forward all-gather with 8-byte {step, payload} granules instead of 4-byte self-tagged words (A/B, tests)
-// bit 11 (2048): inverts the default choice of the BPTT reduce-scatter slot layout (consumer-major source pairs, XP) (A/B, tests)
-// bit 12 (4096): fp32 operands on the exact-fp32 MFMA kernels instead of the three-term bf16 split (A/B, tests)
-// bit 13 (8192): inverts the choice between the 16-CU and the 8-CU forward form at H = 256 (A/B, tests)
-// bit 6 (64): TEST ONLY -- the last member of every cluster leaves right after the placement handshake and the
-//             spin limit drops to 2000 polls, so every hand-off times out (tests/test_gpu_ops.py checks that the
-//             error word is raised and surfaces as an exception)
-static int dbg_flags() {
-  if (g_dflags < 0) { const char* e = getenv("ASR_LSTM_DFLAGS"); g_dflags = e ? atoi(e) : 0; }
-  return g_dflags;
-}
-static int kernel_flags() {
-  return ((dbg_flags() & 16) ? 1 : 0) | ((dbg_flags() & 64) ? 2 : 0) | ((dbg_flags() & 128) ? 4 : 0) |
-         ((dbg_flags() & 256) ? 8 : 0);
-}
-static bool cluster_enabled() {
-  static const bool on = [] { const char* e = getenv("ASR_LSTM_CLUSTER"); return !(e && e[0] == '0'); }();
-  return on;
-}
-// H = 320 (the width of most of the reference's recipes): five CUs per (direction, tile).  ASR_LSTM_CLUSTER_320=0
-// keeps the single-CU kernels for that width (A/B).
-static bool cluster_320_enabled() {
-  static const bool on = [] { const char* e = getenv("ASR_LSTM_CLUSTER_320"); return !(e && e[0] == '0'); }();
-  return on;
-}
 }  // namespace
-
-static constexpr size_t XCH_BYTES = ASR_XCH_BYTES;
-static constexpr size_t XCH_HALF = ((XCH_BYTES - 256) / 2) & ~(size_t)255;   // one of the two exchange areas
-
-// The area this launch runs on (clean by construction; the memset is the fallback for a handle whose bookkeeping was
-// reset) and the stretch of the other one it has to zero for its successor (zero_next_area).
-struct XchAreas { u64* area; u64* znext; unsigned zwords; };
-static XchAreas xch_take(asr_handle* h, char* base, size_t need, hipStream_t st) {
-  const int a = h->xch_next & 1, o = a ^ 1;
-  char* area = base + 256 + (size_t)a * XCH_HALF;
-  char* other = base + 256 + (size_t)o * XCH_HALF;
-  if (h->xch_dirty[a]) {
-    (void)hipMemsetAsync(area, 0, h->xch_dirty[a], st);
-    h->xch_dirty[a] = 0;
-  }
-  XchAreas x;
-  x.area = (u64*)area;
-  x.znext = (u64*)other;
-  x.zwords = (unsigned)(h->xch_dirty[o] / sizeof(u64));
-  h->xch_dirty[o] = 0;
-  h->xch_dirty[a] = (need + 7) & ~(size_t)7;
-  h->xch_next = o;
-  return x;
-}
-
-// ---------------------------------------------------------------- tile groups
-// Every member of a launch must be resident at once (one workgroup per CU), so a launch holds at most
-// 8 * floor(budget / (8 G)) clusters.  A batch with more (tile, direction) pairs runs as consecutive launches over tile
-// ranges: clusters never talk to each other, so the ranges are independent and each launch is the same kernel with a
-// first tile.  The plan is the minimal number of groups: full groups of `per` tiles and one partial group at the end.
-struct TilePlan { int per, n; };   // tiles per full group, number of groups (0: not even one tile fits)
-static TilePlan cluster_tile_plan(int G, int ndir, int tiles, int budget) {
-  TilePlan p = {0, 0};
-  if (G < 1 || ndir < 1 || ndir > 8 || tiles < 1 || budget < 1) return p;
-  const int per = (budget / (8 * G)) * 8 / ndir;          // largest m with cluster_grid(G, m * ndir) <= budget
-  if (per < 1) return p;
-  p.per = per < tiles ? per : tiles;
-  p.n = (tiles + p.per - 1) / p.per;
-  return p;
-}
-extern "C" int asr_cluster_tile_groups(int G, int ndir, int tiles, int cu_budget, int* first_tile, int* ntiles,
-                                       int max_groups) {
-  if (G < 1 || (ndir != 1 && ndir != 2) || tiles < 1 || cu_budget < 1 || max_groups < 0) return ASR_ERR_INVALID_ARG;
-  const TilePlan p = cluster_tile_plan(G, ndir, tiles, cu_budget);
-  for (int i = 0; i < p.n && i < max_groups; ++i) {
-    if (first_tile) first_tile[i] = i * p.per;
-    if (ntiles) ntiles[i] = (i + 1 < p.n) ? p.per : tiles - i * p.per;
-  }
-  return p.n;
-}
-// TEST ONLY: co-resident workgroups a cluster launch may use; 0 = the device's CU count.  Clamped to the CU count where it
-// is used -- a grid larger than the chip would leave members spinning on peers that are not resident.  Process-wide and
-// NOT thread-safe (a plain int every handle reads at launch time, like g_dflags): set it while no recurrence call runs.
-static int g_cu_budget = 0;
-extern "C" int asr_debug_set_cluster_cu_budget(int n) { g_cu_budget = n; return 0; }
-static int cluster_cu_budget(const asr_handle* h) {
-  return (g_cu_budget <= 0 || g_cu_budget > h->num_cu) ? h->num_cu : g_cu_budget;
-}
-// The plan of one launcher call: `grouped` false = exactly one launch or nothing (the shapes that fit keep their form and
-// their single launch), true = any number of groups.  cl_bytes = exchange bytes per cluster: every group's slots must fit
-// in one exchange area, so a grouped plan also shrinks its groups to what the area holds (a shape whose one launch fits the
-// CUs but not the area is split too).
-static TilePlan cluster_launch_plan(const asr_handle* h, int G, int ndir, int B, size_t cl_bytes, bool grouped) {
-  const int tiles = B / 16;
-  TilePlan p = cluster_tile_plan(G, ndir, tiles, cluster_cu_budget(h));
-  const size_t area_tiles = XCH_HALF / ((size_t)ndir * cl_bytes);   // tiles whose clusters one area has slots for
-  if (p.n && (size_t)p.per > area_tiles) {
-    p.per = (int)area_tiles;
-    p.n = p.per ? (tiles + p.per - 1) / p.per : 0;
-  }
-  if (p.n != 1 && !grouped) p.n = 0;
-  return p;
-}
-// host counters of the path a recurrence call took (asr_recurrence_path_counts); kind 0 = LSTM, 1 = GRU
-static void count_cluster_launches(asr_handle* h, int kind, int groups) {
-  h->rec_counts[3 * kind + 0] += (unsigned long long)groups;
-  if (groups > 1) h->rec_counts[3 * kind + 2] += 1;
-}
-// Runs launch(xa, ncl, t0, nt) once per tile group of the plan on `st`: an exchange area per launch (xch_take: each launch
-// zeroes what its predecessor dirtied), ncl = clusters of the group, [t0, t0 + nt) its tiles.  kind as above.
-template <typename F>
-static void run_tile_groups(asr_handle* h, char* base, const TilePlan& plan, int B, int ndir, size_t cl_bytes,
-                            hipStream_t st, int kind, F launch) {
-  for (int t0 = 0; t0 < B / 16; t0 += plan.per) {
-    const int nt = min(plan.per, B / 16 - t0), ncl = nt * ndir;
-    launch(xch_take(h, base, ncl * cl_bytes, st), ncl, t0, nt);
-  }
-  count_cluster_launches(h, kind, plan.n);
-}
-extern "C" int asr_recurrence_path_counts(asr_handle* h, unsigned long long* out6) {
-  if (!h || !out6) return ASR_ERR_INVALID_ARG;
-  for (int i = 0; i < 6; ++i) out6[i] = h->rec_counts[i];
-  return ASR_OK;
-}
-extern "C" int asr_reset_recurrence_path_counts(asr_handle* h) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  for (int i = 0; i < 6; ++i) h->rec_counts[i] = 0;
-  return ASR_OK;
-}
-// the form each asr_lstm_fwd / asr_lstm_bwd(_ex) call on this handle ended in (host integers bumped where the form is
-// chosen: the cluster launchers below, asr_lstm_fwd / lstm_bwd_impl for the single-CU kernels)
-extern "C" int asr_lstm_kernel_counts(asr_handle* h, unsigned long long* out, int n) {
-  if (!h || !out || n < 0) return ASR_ERR_INVALID_ARG;
-  for (int i = 0; i < n; ++i) out[i] = i < ASR_LSTM_KERNEL_N ? h->lstm_counts[i] : 0ull;
-  return ASR_OK;
-}
-extern "C" int asr_reset_lstm_kernel_counts(asr_handle* h) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  for (int i = 0; i < ASR_LSTM_KERNEL_N; ++i) h->lstm_counts[i] = 0;
-  return ASR_OK;
-}
-
-// ASR_LSTM_FWD_HS=32: forward recurrence on clusters of H/32 CUs with four waves each (one per SIMD) instead of H/64
-// CUs with eight (A/B switch)
-// Units per CU of the H = 256 / 512 clusters: 32 (default since round 3: H/32 CUs with four waves each, one per SIMD) or
-// 64 (H/64 CUs with eight waves; ASR_LSTM_HS=64, ASR_LSTM_FWD_HS / ASR_LSTM_BWD_HS for one pass only, or
-// ASR_LSTM_DFLAGS bit 9 at run time -- the tests run both).  Measured (profiles/r03_cluster_hs32.md): forward
-// 907 -> 866 us and BPTT 953 -> 929 us per launch at H = 256 (T = 778), 1791 -> 1374 and 2354 -> 1833 us at H = 512.
-// The bf16 forward at H = 256 has a third form, 16 units per CU (lstm_fwd_cluster16_kernel: 16 CUs x four waves x 4 units).
-// FWD_HS16_DEFAULT says whether it is the default there; ASR_LSTM_FWD_HS=16 / 32 / 64 picks a form, ASR_LSTM_DFLAGS bit 13
-// inverts the choice between 16 and 32 at run time (tests, A/B).  Every other kernel reads 16 as 32.  Measured
-// (profiles/r10_fwd_cu16.md): forward launch 694 -> 622 us at T = 745, B = 16, headline step 8.63 -> 8.34 ms, same bits.
-static constexpr bool FWD_HS16_DEFAULT = true;
-static int units_per_cu(const char* specific, bool allow16 = false) {
-  if (dbg_flags() & 512) return 64;
-  const char* e = getenv(specific);
-  if (!e) e = getenv("ASR_LSTM_HS");
-  const int v = e ? atoi(e) : 0;
-  if (v == 64) return 64;
-  if (!allow16) return 32;
-  const bool cu16 = e ? v == 16 : FWD_HS16_DEFAULT;
-  return (cu16 != ((dbg_flags() & 8192) != 0)) ? 16 : 32;
-}
-static int fwd_units_per_cu() { return units_per_cu("ASR_LSTM_FWD_HS"); }
-static int fwd256_units_per_cu() { return units_per_cu("ASR_LSTM_FWD_HS", true); }
-// forward all-gather word format: 4-byte self-tagged words unless ASR_LSTM_XW=0 or ASR_LSTM_DFLAGS bit 10 (run time, tests)
-static bool fwd_xw_enabled() {
-  static const bool on = [] { const char* e = getenv("ASR_LSTM_XW"); return !(e && e[0] == '0'); }();
-  return on && !(dbg_flags() & 1024);
-}
-static int bwd_units_per_cu() { return units_per_cu("ASR_LSTM_BWD_HS"); }
-// BPTT reduce-scatter slot layout: consumer-major source pairs (XP) or one 16-byte slot per (source, tile).  Measured
-// (round 4, us per BPTT launch, T = 778): H = 320 on five CUs x eight waves 1107 -> 1064 with XP, but H = 256 on eight CUs x
-// four waves 851 -> 940 and H = 512 on sixteen 1520 -> 1790: with one wave per SIMD the doubled store count of the
-// producers (two 8-byte stores per tile instead of one 16-byte store) sits on the chain between the MFMAs and the peers'
-// polls and costs more than the halved poll count saves.  Default: XP only on the eight-wave clusters (units per CU 64);
-// ASR_LSTM_XP=1 / 0 forces it on / off everywhere, ASR_LSTM_DFLAGS bit 11 inverts the choice at run time (tests, A/B).
-static bool bwd_xp_enabled(int hsu) {
-  static const int env = [] { const char* e = getenv("ASR_LSTM_XP"); return e ? (e[0] == '0' ? 0 : 1) : -1; }();
-  const bool def = env >= 0 ? env == 1 : hsu == 64;
-  return def != ((dbg_flags() & 2048) != 0);
-}
 
 template <int H, int HSU = 64>
 static bool cluster_fwd_launch(asr_handle* h, int T, int B, int ndir, const float* xproj, const void* whp,
@@ -3523,10 +1280,8 @@ static bool cluster_fwd_launch(asr_handle* h, int T, int B, int ndir, const floa
   constexpr int G = H / HSU;
   static_assert(G <= XHDR, "placement header too small");
   constexpr size_t cl_bytes = (XHDR + 2 * G * 16 * (HSU / 2)) * sizeof(u64);
-  if ((size_t)T * B * ndir * H >= (1ull << 31) || h->scratch_bytes < XCH_BYTES) return false;
-  const TilePlan plan = cluster_launch_plan(h, G, ndir, B, cl_bytes, grouped);   // every member of a launch must be resident at once
-  if (!plan.n) return false;
-  char* base = (char*)h->scratch + (h->scratch_bytes - XCH_BYTES);
+  const ClusterCall cc = cluster_call(h, G, ndir, B, (size_t)T * B * ndir * H, cl_bytes, grouped);
+  if (!cc.plan.n) return false;
   // EARLY (own-slice k-chunks multiplied under the L2 hop): measured at H = 256 (round 2, cfg B): 970 -> 938 us per
   // launch, at H = 320: 1069 -> 969; default at both.  ASR_LSTM_DFLAGS bit 5 (32) inverts the default for A/B measurements.
   const bool early = (H == 256 || H == 320 || HSU == 32) != ((dbg_flags() & 32) != 0);   // H = 320: 1069 -> 969 us per launch
@@ -3574,10 +1329,10 @@ static bool cluster_fwd_launch(asr_handle* h, int T, int B, int ndir, const floa
   // (padding the LDS request past half a CU so that two 4-wave members can never share one was measured: no
   // difference, 866.7 vs 867.6 us -- the dispatcher spreads the members over the CUs by itself)
   const size_t lds = (size_t)2 * 16 * (H + 8) * 2;
-  run_tile_groups(h, base, plan, B, ndir, cl_bytes, st, 0, [&](const XchAreas& xa, int ncl, int t0, int nt) {
+  run_tile_groups(h, cc, B, ndir, cl_bytes, st, 0, [&](const XchAreas& xa, int ncl, int t0, int nt) {
     hipLaunchKernelGGL(k, dim3(cluster_grid(G, ncl)), dim3(HSU * 8), lds, st, T, B, ndir,
                        (const f32x4_t*)xproj, (const bf16_t*)whp, peep, seq_len, fb, clip, (cbf16x4_t*)gates,
-                       (bf16_t*)hout, cs, cf, hf, xa.area, (unsigned*)base, kernel_flags(), xa.znext, xa.zwords, t0, nt);
+                       (bf16_t*)hout, cs, cf, hf, xa.area, (unsigned*)cc.base, kernel_flags(), xa.znext, xa.zwords, t0, nt);
   });
   h->lstm_counts[HSU == 32 ? ASR_LSTM_FWD_BF16_HS32 : ASR_LSTM_FWD_BF16_HS64] += 1;   // asr_lstm_kernel_counts
   return true;
@@ -3592,10 +1347,8 @@ static bool cluster_fwd16_launch(asr_handle* h, int T, int B, int ndir, const fl
   static_assert(G <= XHDR, "placement header too small");
   constexpr size_t cl_bytes = (XHDR + 2 * G * 16 * (HSU / 2)) * sizeof(u64);
   if (!fwd_xw_enabled() || g_cdbg_host) return false;
-  if ((size_t)T * B * ndir * H >= (1ull << 31) || h->scratch_bytes < XCH_BYTES) return false;
-  const TilePlan plan = cluster_launch_plan(h, G, ndir, B, cl_bytes, grouped);   // every member of a launch must be resident at once
-  if (!plan.n) return false;
-  char* base = (char*)h->scratch + (h->scratch_bytes - XCH_BYTES);
+  const ClusterCall cc = cluster_call(h, G, ndir, B, (size_t)T * B * ndir * H, cl_bytes, grouped);
+  if (!cc.plan.n) return false;
   // scheduling-barrier mask (FPIN, the points of the forms above), searched over the same eight masks as the 8-CU form; us
   // per launch at T = 745, B = 16, two directions, two passes (median of 12 launches each): none 621 / 621, {0} 617 / 620,
   // {1} 626 / 628, {2} 619 / 620, {3} 622 / 623, {0,1} 627 / 625, {1,2} 625 / 624, all four 630 / 628; also {5} 620 / 616 and
@@ -3624,10 +1377,10 @@ static bool cluster_fwd16_launch(asr_handle* h, int T, int B, int ndir, const fl
   }
 #endif
   const size_t lds = (size_t)2 * 16 * (H + 8) * 2;
-  run_tile_groups(h, base, plan, B, ndir, cl_bytes, st, 0, [&](const XchAreas& xa, int ncl, int t0, int nt) {
+  run_tile_groups(h, cc, B, ndir, cl_bytes, st, 0, [&](const XchAreas& xa, int ncl, int t0, int nt) {
     hipLaunchKernelGGL(k, dim3(cluster_grid(G, ncl)), dim3(256), lds, st, T, B, ndir,
                        (const f32x4_t*)xproj, (const bf16_t*)whp, peep, seq_len, fb, clip, (cbf16x4_t*)gates,
-                       (bf16_t*)hout, cs, cf, hf, xa.area, (unsigned*)base, kernel_flags(), xa.znext, xa.zwords, t0, nt);
+                       (bf16_t*)hout, cs, cf, hf, xa.area, (unsigned*)cc.base, kernel_flags(), xa.znext, xa.zwords, t0, nt);
   });
   h->lstm_counts[ASR_LSTM_FWD_BF16_CU16] += 1;   // asr_lstm_kernel_counts
   return true;
@@ -3639,8 +1392,7 @@ bool asr_cluster_fwd_try(asr_handle* h, int T, int B, int H, int ndir, const flo
                          hipStream_t st) {
   if (!cluster_enabled() || (H != 256 && H != 512 && !(H == 320 && cluster_320_enabled()))) return false;
   cdbg_setup();
-  // first every form as ONE launch, in the order of preference; tile groups only when no form fits in one launch
-  auto attempt = [&](bool grouped) -> bool {
+  return one_launch_else_groups([&](bool grouped) -> bool {
     if (H == 320) return cluster_fwd_launch<320>(h, T, B, ndir, xproj, whp, peep, seq_len, fb, clip, gates, hout, cs, cf, hf, st, grouped);
     // H = 256: the 16-CU form when it fits in one launch (a batch of more tiles runs as tile groups of the 32-unit form)
     if (H == 256 && !grouped && fwd256_units_per_cu() == 16 &&
@@ -3654,8 +1406,7 @@ bool asr_cluster_fwd_try(asr_handle* h, int T, int B, int H, int ndir, const flo
     }
     return H == 512 ? cluster_fwd_launch<512>(h, T, B, ndir, xproj, whp, peep, seq_len, fb, clip, gates, hout, cs, cf, hf, st, grouped)
                     : cluster_fwd_launch<256>(h, T, B, ndir, xproj, whp, peep, seq_len, fb, clip, gates, hout, cs, cf, hf, st, grouped);
-  };
-  return attempt(false) || attempt(true);
+  });
 }
 
 template <int H, int HSU = 64>
@@ -3666,10 +1417,8 @@ static bool cluster_bwd_launch(asr_handle* h, int T, int B, int ndir, const floa
   constexpr int G = H / HSU;
   static_assert(G <= XHDR, "placement header too small");
   constexpr size_t cl_bytes = (XHDR + (size_t)2 * G * G * (HSU / 16) * 64 * 2) * sizeof(u64);
-  if ((size_t)T * B * ndir * H >= (1ull << 31) || h->scratch_bytes < XCH_BYTES) return false;
-  const TilePlan plan = cluster_launch_plan(h, G, ndir, B, cl_bytes, grouped);   // every member of a launch must be resident at once
-  if (!plan.n) return false;
-  char* base = (char*)h->scratch + (h->scratch_bytes - XCH_BYTES);
+  const ClusterCall cc = cluster_call(h, G, ndir, B, (size_t)T * B * ndir * H, cl_bytes, grouped);
+  if (!cc.plan.n) return false;
   // two dG images; the H = 512 form adds the own-tile hand-over buffer behind them
   const size_t lds = (size_t)2 * 16 * (4 * HSU + 8) * 2 + ((G == 8 && HSU == 64) ? 2 * 4 * 64 * 8 : 0);
   // reduce-scatter slots in the consumer-major paired layout (default) or one 16-byte slot per (source, tile) (ASR_LSTM_XP=0)
@@ -3701,10 +1450,10 @@ static bool cluster_bwd_launch(asr_handle* h, int T, int B, int ndir, const floa
     }
   }
 #endif
-  run_tile_groups(h, base, plan, B, ndir, cl_bytes, st, 0, [&](const XchAreas& xa, int ncl, int t0, int nt) {
+  run_tile_groups(h, cc, B, ndir, cl_bytes, st, 0, [&](const XchAreas& xa, int ncl, int t0, int nt) {
     hipLaunchKernelGGL(k, dim3(cluster_grid(G, ncl)), dim3(HSU * 8), lds, st, T, B, ndir, dhout,
                        (const cbf16x4_t*)gates, cs, (const bf16_t*)whpb, peep, seq_len, dcf, dhf,
-                       (cbf16x4_t*)dgates, dpeep_part, xa.area, (unsigned*)base, kernel_flags(), xa.znext, xa.zwords,
+                       (cbf16x4_t*)dgates, dpeep_part, xa.area, (unsigned*)cc.base, kernel_flags(), xa.znext, xa.zwords,
                        h->bptt_clip, t0, nt);
   });
   h->lstm_counts[HSU == 32 ? ASR_LSTM_BWD_BF16_HS32 : ASR_LSTM_BWD_BF16_HS64] += 1;   // asr_lstm_kernel_counts
@@ -3717,8 +1466,7 @@ bool asr_cluster_bwd_try(asr_handle* h, int T, int B, int H, int ndir, const flo
                          float* dpeep_part, hipStream_t st) {
   if (!cluster_enabled() || (H != 256 && H != 512 && !(H == 320 && cluster_320_enabled()))) return false;
   cdbg_setup();
-  // first every form as ONE launch, in the order of preference; tile groups only when no form fits in one launch
-  auto attempt = [&](bool grouped) -> bool {
+  return one_launch_else_groups([&](bool grouped) -> bool {
     if (H == 320)
       return cluster_bwd_launch<320>(h, T, B, ndir, dhout, gates, cs, whpb, peep, seq_len, dcf, dhf, dgates, dpeep_part, st, grouped);
     if (bwd_units_per_cu() == 32) {
@@ -3730,317 +1478,10 @@ bool asr_cluster_bwd_try(asr_handle* h, int T, int B, int H, int ndir, const flo
     }
     return H == 512 ? cluster_bwd_launch<512>(h, T, B, ndir, dhout, gates, cs, whpb, peep, seq_len, dcf, dhf, dgates, dpeep_part, st, grouped)
                     : cluster_bwd_launch<256>(h, T, B, ndir, dhout, gates, cs, whpb, peep, seq_len, dcf, dhf, dgates, dpeep_part, st, grouped);
-  };
-  return attempt(false) || attempt(true);
-}
-
-// fp32 operands (H = 128 / 256 / 320 / 512, see cluster_fwd_f32_attempt) and the GRU clusters: ASR_LSTM_CLUSTER_F32=0 keeps
-// the single-CU kernels (A/B).
-static bool cluster_f32_enabled() {
-  static const bool on = [] { const char* e = getenv("ASR_LSTM_CLUSTER_F32"); return !(e && e[0] == '0'); }();
-  return on && cluster_enabled();
-}
-
-// fp32 operands as three bf16 terms on the bf16 matrix pipe (H = 128 / 256, four waves per CU); ASR_LSTM_F32_SPLIT=0 or
-// ASR_LSTM_DFLAGS bit 12 (run time, tests) keeps the exact-fp32 MFMA kernels
-static bool cluster_f32_split_enabled() {
-  static const bool on = [] { const char* e = getenv("ASR_LSTM_F32_SPLIT"); return !(e && e[0] == '0'); }();
-  return on && !(dbg_flags() & 4096);
-}
-
-template <int HH, int HSU>
-static bool cluster_fwd_f32_launch(asr_handle* h, int T, int B, int ndir, const float* xproj, const void* whp,
-                                   const float* peep, const int32_t* seq_len, float fb, float clip, void* gates,
-                                   void* hout, float* cs, float* cf, float* hf, hipStream_t st, bool grouped) {
-  constexpr int G = HH / HSU;
-  static_assert(G <= XHDR, "placement header too small");
-  constexpr size_t cl_bytes = (XHDR + 2 * G * 16 * HSU) * sizeof(u64);
-  if ((size_t)T * B * ndir * HH >= (1ull << 31) || h->scratch_bytes < XCH_BYTES) return false;
-  const TilePlan plan = cluster_launch_plan(h, G, ndir, B, cl_bytes, grouped);
-  if (!plan.n) return false;
-  char* base = (char*)h->scratch + (h->scratch_bytes - XCH_BYTES);
-  // EARLY own-slice products by default, except H = 512 where their extra live accumulators push the 256 weight
-  // registers into scratch (measured 5.93 vs 5.36 ms per 778-step launch); ASR_LSTM_DFLAGS bit 5 inverts (A/B)
-  const bool early = ((dbg_flags() & 32) == 0) != (HH >= 512);
-  if constexpr (HSU == 32 && (HH == 128 || HH == 256)) {
-    if (cluster_f32_split_enabled() && T < 65536) {   // round 5: the same recurrence on the bf16 matrix pipe (three-term split; 16-bit step tags)
-      auto ks = early ? lstm_fwd_cluster_f32s_kernel<HH, true, HSU> : lstm_fwd_cluster_f32s_kernel<HH, false, HSU>;
-      const size_t lds_s = (size_t)2 * 3 * 16 * (HH + 8) * 2;
-      run_tile_groups(h, base, plan, B, ndir, cl_bytes, st, 0, [&](const XchAreas& xa, int ncl, int t0, int nt) {
-        hipLaunchKernelGGL(ks, dim3(cluster_grid(G, ncl)), dim3(HSU * 8), lds_s, st, T, B, ndir, (const f32x4_t*)xproj,
-                           (const float*)whp, peep, seq_len, fb, clip, (f32x4_t*)gates, (float*)hout, cs, cf, hf, xa.area,
-                           (unsigned*)base, kernel_flags(), xa.znext, xa.zwords, t0, nt);
-      });
-      h->lstm_counts[ASR_LSTM_FWD_F32_SPLIT] += 1;   // asr_lstm_kernel_counts
-      return true;
-    }
-  }
-  auto k = early ? lstm_fwd_cluster8_f32_kernel<HH, true, HSU> : lstm_fwd_cluster8_f32_kernel<HH, false, HSU>;
-  const size_t lds = (size_t)2 * 16 * (HH + 4) * 4;
-  if (lds > ((size_t)64 << 10))
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  run_tile_groups(h, base, plan, B, ndir, cl_bytes, st, 0, [&](const XchAreas& xa, int ncl, int t0, int nt) {
-    hipLaunchKernelGGL(k, dim3(cluster_grid(G, ncl)), dim3(HSU * 8), lds, st, T, B, ndir, (const f32x4_t*)xproj,
-                       (const float*)whp, peep, seq_len, fb, clip, (f32x4_t*)gates, (float*)hout, cs, cf, hf, xa.area,
-                       (unsigned*)base, kernel_flags(), xa.znext, xa.zwords, t0, nt);
   });
-  h->lstm_counts[HSU == 32 ? ASR_LSTM_FWD_F32_HS32 : ASR_LSTM_FWD_F32_HS64] += 1;   // asr_lstm_kernel_counts
-  return true;
 }
 
-// fp32 operands: H = 128 / 256 / 320 / 512 on clusters of H/32 CUs x four waves (default), H = 128 also on two CUs x eight
-// waves (ASR_LSTM_HS=64 / flag bit 9).  ASR_LSTM_CLUSTER_F32=0 keeps the single-CU kernels (A/B);
-// ASR_LSTM_CLUSTER_F32_WIDE=0 keeps them for H > 128 only.
-static bool cluster_f32_wide_enabled() {
-  static const bool on = [] { const char* e = getenv("ASR_LSTM_CLUSTER_F32_WIDE"); return !(e && e[0] == '0'); }();
-  return on;
-}
-#define ASR_F32_ARGS_F h, T, B, ndir, xproj, whp, peep, seq_len, fb, clip, gates, hout, cs, cf, hf, st, grouped
-static bool cluster_fwd_f32_attempt(asr_handle* h, int T, int B, int H, int ndir, const float* xproj,
-                             const void* whp, const float* peep, const int32_t* seq_len, float fb,
-                             float clip, void* gates, void* hout, float* cs, float* cf, float* hf,
-                             hipStream_t st, bool grouped) {
-  if (!cluster_f32_enabled()) return false;
-  if (fwd_units_per_cu() == 32) {
-    if (H == 128) return cluster_fwd_f32_launch<128, 32>(ASR_F32_ARGS_F);
-    if (!cluster_f32_wide_enabled()) return false;
-    if (H == 256) return cluster_fwd_f32_launch<256, 32>(ASR_F32_ARGS_F);
-    if (H == 320) return cluster_fwd_f32_launch<320, 32>(ASR_F32_ARGS_F);
-    if (H == 512) return cluster_fwd_f32_launch<512, 32>(ASR_F32_ARGS_F);
-    return false;
-  }
-  return H == 128 ? cluster_fwd_f32_launch<128, 64>(ASR_F32_ARGS_F) : false;
-}
-#undef ASR_F32_ARGS_F
-bool asr_cluster_fwd_f32_try(asr_handle* h, int T, int B, int H, int ndir, const float* xproj,
-                             const void* whp, const float* peep, const int32_t* seq_len, float fb,
-                             float clip, void* gates, void* hout, float* cs, float* cf, float* hf,
-                             hipStream_t st) {
-  // one launch where it fits, tile groups otherwise
-  return cluster_fwd_f32_attempt(h, T, B, H, ndir, xproj, whp, peep, seq_len, fb, clip, gates, hout, cs, cf, hf, st, false) ||
-         cluster_fwd_f32_attempt(h, T, B, H, ndir, xproj, whp, peep, seq_len, fb, clip, gates, hout, cs, cf, hf, st, true);
-}
-
-template <int HH, int HSU>
-static bool cluster_bwd_f32_launch(asr_handle* h, int T, int B, int ndir, const float* dhout, const void* gates,
-                                   const float* cs, const void* whpb, const float* peep, const int32_t* seq_len,
-                                   const float* dcf, const float* dhf, void* dgates, float* dpeep_part, hipStream_t st,
-                                   bool grouped) {
-  constexpr int G = HH / HSU, TPC = HSU / 16;
-  constexpr size_t cl_bytes = (XHDR + (size_t)2 * G * G * TPC * 64 * 2) * sizeof(u64);
-  if ((size_t)T * B * ndir * HH >= (1ull << 31) || h->scratch_bytes < XCH_BYTES) return false;
-  const TilePlan plan = cluster_launch_plan(h, G, ndir, B, cl_bytes, grouped);
-  if (!plan.n) return false;
-  char* base = (char*)h->scratch + (h->scratch_bytes - XCH_BYTES);
-  if constexpr (HSU == 32 && (HH == 128 || HH == 256)) {
-    if (cluster_f32_split_enabled()) {
-      const size_t lds_s = (size_t)2 * 3 * 16 * (4 * HSU + 8) * 2 + (size_t)2 * TPC * 64 * 8;   // two x three term images + hand-over
-      run_tile_groups(h, base, plan, B, ndir, cl_bytes, st, 0, [&](const XchAreas& xa, int ncl, int t0, int nt) {
-        hipLaunchKernelGGL((lstm_bwd_cluster_f32s_kernel<HH, HSU>), dim3(cluster_grid(G, ncl)), dim3(HSU * 8), lds_s, st, T,
-                           B, ndir, dhout, (const f32x4_t*)gates, cs, (const float*)whpb, peep, seq_len, dcf, dhf,
-                           (f32x4_t*)dgates, dpeep_part, xa.area, (unsigned*)base, kernel_flags(), xa.znext, xa.zwords,
-                           h->bptt_clip, t0, nt);
-      });
-      h->lstm_counts[ASR_LSTM_BWD_F32_SPLIT] += 1;   // asr_lstm_kernel_counts
-      return true;
-    }
-  }
-  const size_t lds = (size_t)2 * 16 * (4 * HSU + 4) * 4 + (size_t)2 * TPC * 64 * 8;   // two dG images + the hand-over buffer
-  run_tile_groups(h, base, plan, B, ndir, cl_bytes, st, 0, [&](const XchAreas& xa, int ncl, int t0, int nt) {
-    hipLaunchKernelGGL((lstm_bwd_cluster_f32_kernel<HH, HSU>), dim3(cluster_grid(G, ncl)), dim3(HSU * 8), lds, st, T, B, ndir,
-                       dhout, (const f32x4_t*)gates, cs, (const float*)whpb, peep, seq_len, dcf, dhf, (f32x4_t*)dgates,
-                       dpeep_part, xa.area, (unsigned*)base, kernel_flags(), xa.znext, xa.zwords, h->bptt_clip, t0, nt);
-  });
-  static_assert(HSU == 32, "the 64-unit fp32 BPTT is lstm_bwd_cluster8_f32_kernel (cluster_bwd_f32_attempt)");
-  h->lstm_counts[ASR_LSTM_BWD_F32_HS32] += 1;   // asr_lstm_kernel_counts
-  return true;
-}
-
-// GRU forward on clusters of H / 32 CUs (H = 64 / 128 / 256 / 320; B a multiple of 16).  ASR_GRU_CLUSTER=0 keeps the single-CU
-// persistent kernel (A/B, and the tests run both).  false = not applicable, nothing launched.
-bool asr_cluster_gru_fwd_try(asr_handle* h, int T, int B, int H, int ndir, const float* xg, const float* xc,
-                             const float* wgh, const float* wch, const int32_t* seq_len, float* r, float* u, float* c,
-                             float* rh, float* hout, float* h_final, hipStream_t st) {
-  const char* env_c = getenv("ASR_GRU_CLUSTER");          // (read per call: the A-B test flips it inside one process)
-  if ((env_c && env_c[0] == '0') || !cluster_f32_enabled() || (H != 64 && H != 128 && H != 256 && H != 320) || T < 1 || T >= 65536) return false;
-  const int G = H / 32;
-  const size_t cl_bytes = (XHDR + (size_t)4 * G * 16 * 32) * sizeof(u64);
-  if ((size_t)T * B * ndir * 2 * H >= (1ull << 31) || h->scratch_bytes < XCH_BYTES) return false;
-  const TilePlan plan = cluster_launch_plan(h, G, ndir, B, cl_bytes, true);   // one launch where it fits, tile groups otherwise
-  if (!plan.n) return false;
-  char* base = (char*)h->scratch + (h->scratch_bytes - XCH_BYTES);
-  const size_t lds = (size_t)3 * 3 * 16 * (H + 8) * 2;
-#define ASR_GRU_CL(HH)                                                                                              \
-  do {                                                                                                              \
-    (void)hipFuncSetAttribute((const void*)gru_fwd_cluster_kernel<HH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    run_tile_groups(h, base, plan, B, ndir, cl_bytes, st, 1, [&](const XchAreas& xa, int ncl, int t0, int nt) {      \
-      hipLaunchKernelGGL(gru_fwd_cluster_kernel<HH>, dim3(cluster_grid(HH / 32, ncl)), dim3(256), lds, st, T, B, ndir, xg, xc, \
-                         wgh, wch, seq_len, r, u, c, rh, hout, h_final, xa.area, (unsigned*)base, kernel_flags(), xa.znext, \
-                         xa.zwords, t0, nt);                                                                         \
-    });                                                                                                             \
-  } while (0)
-  if (H == 64) ASR_GRU_CL(64); else if (H == 128) ASR_GRU_CL(128); else if (H == 256) ASR_GRU_CL(256); else ASR_GRU_CL(320);
-#undef ASR_GRU_CL
-  return true;
-}
-
-bool asr_cluster_gru_bwd_try(asr_handle* h, int T, int B, int H, int ndir, const float* dout, const float* d_h_final,
-                             const float* hout, const float* r, const float* u, const float* c, const float* wghT,
-                             const float* wchT, const int32_t* seq_len, float* dgate, float* dcand, hipStream_t st) {
-  const char* env_c = getenv("ASR_GRU_CLUSTER");          // (read per call: the A-B test flips it inside one process)
-  if ((env_c && env_c[0] == '0') || !cluster_f32_enabled() || (H != 64 && H != 128 && H != 256 && H != 320) || T < 1 || T >= 65536) return false;
-  const int G = H / 32;
-  const size_t cl_bytes = (XHDR + (size_t)6 * G * 16 * 32) * sizeof(u64);
-  if ((size_t)T * B * ndir * 2 * H >= (1ull << 31) || h->scratch_bytes < XCH_BYTES) return false;
-  const TilePlan plan = cluster_launch_plan(h, G, ndir, B, cl_bytes, true);   // one launch where it fits, tile groups otherwise
-  if (!plan.n) return false;
-  char* base = (char*)h->scratch + (h->scratch_bytes - XCH_BYTES);
-  const size_t lds = (size_t)5 * 3 * 16 * (H + 8) * 2;
-#define ASR_GRU_CLB(HH)                                                                                             \
-  do {                                                                                                              \
-    (void)hipFuncSetAttribute((const void*)gru_bwd_cluster_kernel<HH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    run_tile_groups(h, base, plan, B, ndir, cl_bytes, st, 1, [&](const XchAreas& xa, int ncl, int t0, int nt) {      \
-      hipLaunchKernelGGL(gru_bwd_cluster_kernel<HH>, dim3(cluster_grid(HH / 32, ncl)), dim3(256), lds, st, T, B, ndir, dout, \
-                         d_h_final, hout, r, u, c, wghT, wchT, seq_len, dgate, dcand, xa.area, (unsigned*)base,       \
-                         kernel_flags(), xa.znext, xa.zwords, t0, nt);                                               \
-    });                                                                                                             \
-  } while (0)
-  if (H == 64) ASR_GRU_CLB(64); else if (H == 128) ASR_GRU_CLB(128); else if (H == 256) ASR_GRU_CLB(256); else ASR_GRU_CLB(320);
-#undef ASR_GRU_CLB
-  return true;
-}
-
-#define ASR_F32_ARGS_B h, T, B, ndir, dhout, gates, cs, whpb, peep, seq_len, dcf, dhf, dgates, dpeep_part, st, grouped
-static bool cluster_bwd_f32_attempt(asr_handle* h, int T, int B, int H, int ndir, const float* dhout,
-                             const void* gates, const float* cs, const void* whpb, const float* peep,
-                             const int32_t* seq_len, const float* dcf, const float* dhf, void* dgates,
-                             float* dpeep_part, hipStream_t st, bool grouped) {
-  if (!cluster_f32_enabled()) return false;
-  if (bwd_units_per_cu() == 32) {
-    if (H == 128) return cluster_bwd_f32_launch<128, 32>(ASR_F32_ARGS_B);
-    if (!cluster_f32_wide_enabled()) return false;
-    if (H == 256) return cluster_bwd_f32_launch<256, 32>(ASR_F32_ARGS_B);
-    if (H == 320) return cluster_bwd_f32_launch<320, 32>(ASR_F32_ARGS_B);
-    if (H == 512) return cluster_bwd_f32_launch<512, 32>(ASR_F32_ARGS_B);
-    return false;
-  }
-  constexpr int HH = 128, G = HH / HS;
-  if (H != HH) return false;
-  constexpr size_t cl_bytes = (XHDR + (size_t)2 * G * G * 4 * 64 * 2) * sizeof(u64);
-  if ((size_t)T * B * ndir * H >= (1ull << 31) || h->scratch_bytes < XCH_BYTES) return false;
-  const TilePlan plan = cluster_launch_plan(h, G, ndir, B, cl_bytes, grouped);
-  if (!plan.n) return false;
-  char* base = (char*)h->scratch + (h->scratch_bytes - XCH_BYTES);
-  const size_t lds = (size_t)2 * 16 * (4 * HS + 4) * 4 + 2 * 4 * 64 * 8;   // two dG images + the hand-over buffer
-  run_tile_groups(h, base, plan, B, ndir, cl_bytes, st, 0, [&](const XchAreas& xa, int ncl, int t0, int nt) {
-    hipLaunchKernelGGL(lstm_bwd_cluster8_f32_kernel<HH>, dim3(cluster_grid(G, ncl)), dim3(CT8), lds, st, T, B, ndir,
-                       dhout, (const f32x4_t*)gates, cs, (const float*)whpb, peep, seq_len, dcf, dhf, (f32x4_t*)dgates,
-                       dpeep_part, xa.area, (unsigned*)base, kernel_flags(), xa.znext, xa.zwords, h->bptt_clip, t0, nt);
-  });
-  h->lstm_counts[ASR_LSTM_BWD_F32_HS64] += 1;   // asr_lstm_kernel_counts
-  return true;
-}
-#undef ASR_F32_ARGS_B
-bool asr_cluster_bwd_f32_try(asr_handle* h, int T, int B, int H, int ndir, const float* dhout,
-                             const void* gates, const float* cs, const void* whpb, const float* peep,
-                             const int32_t* seq_len, const float* dcf, const float* dhf, void* dgates,
-                             float* dpeep_part, hipStream_t st) {
-  // one launch where it fits, tile groups otherwise
-  return cluster_bwd_f32_attempt(h, T, B, H, ndir, dhout, gates, cs, whpb, peep, seq_len, dcf, dhf, dgates, dpeep_part, st, false) ||
-         cluster_bwd_f32_attempt(h, T, B, H, ndir, dhout, gates, cs, whpb, peep, seq_len, dcf, dhf, dgates, dpeep_part, st, true);
-}
-
-// ---------------------------------------------------------------- debug: 16-byte exchange words, tear probe
-// Would a lane's 16-byte store be seen whole by a 16-byte load of another CU?  The clusters' exchange uses 8-byte granules
-// (one 64-bit store / load per lane: single-copy atomic by construction) or per-word tags; a 16-byte self-tagged word would
-// halve the poll instructions but is only correct if the four dwords of one
-// global_store_dwordx4 never appear torn.  Workgroup 0 writes {i, i, i, i} for i = 1 .. iters into one word per lane
-// (plain stores when `wt` is 0, as a co-located cluster does, write-through sc1 stores otherwise); workgroup `peer`
-// (8: same XCD as workgroup 0, 1: another XCD) polls the same words with L1-bypassing 16-byte loads and counts the loads
-// whose four dwords differ.  out[3 lane .. + 2] = {loads, torn loads, distinct values seen}.
-namespace {
-__global__ __launch_bounds__(64) void tear_probe_kernel(unsigned* __restrict__ buf, unsigned iters, int peer, int wt,
-                                                        unsigned long long* __restrict__ out) {
-  typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
-  const int lane = threadIdx.x;
-  u32x4_t* word = reinterpret_cast<u32x4_t*>(buf) + lane;
-  if (blockIdx.x == 0) {
-    for (unsigned i = 1; i <= iters; ++i) {
-      const u32x4_t v = {i, i, i, i};
-      if (wt) asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(word), "v"(v) : "memory");
-      else asm volatile("global_store_dwordx4 %0, %1, off" ::"v"(word), "v"(v) : "memory");
-      if ((i & 63u) == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // bounded queue, stores in order
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    return;
-  }
-  if ((int)blockIdx.x != peer) return;
-  unsigned long long loads = 0, torn = 0, seen = 0;
-  unsigned last = 0;
-  for (unsigned long long spin = 0; spin < (1ull << 24); ++spin) {          // bounded: ~15 s even if nothing ever arrives
-    u32x4_t v;
-    asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(word) : "memory");
-    ++loads;
-    if (!(v[0] == v[1] && v[1] == v[2] && v[2] == v[3])) ++torn;
-    if (v[0] != last) { ++seen; last = v[0]; }
-    if (__all(v[0] >= iters && v[1] >= iters && v[2] >= iters && v[3] >= iters)) break;
-  }
-  out[3 * lane + 0] = loads;
-  out[3 * lane + 1] = torn;
-  out[3 * lane + 2] = seen;
-}
-}  // namespace
-extern "C" int asr_debug_tear_probe(asr_handle* h, unsigned* buf, unsigned iters, int peer, int write_through,
-                                    unsigned long long* out, asr_stream s) {
-  if (!h || !buf || !out || iters < 1 || (peer != 1 && peer != 8) || ((uintptr_t)buf) % 16 != 0) return ASR_ERR_INVALID_ARG;
-  if (hipMemsetAsync(buf, 0, 64 * 16, (hipStream_t)s) != hipSuccess) return ASR_ERR_HIP;
-  hipLaunchKernelGGL(tear_probe_kernel, dim3(9), dim3(64), 0, (hipStream_t)s, buf, iters, peer, write_through, out);
-  ASR_CHECK_LAUNCH(h, "asr_debug_tear_probe");
-  return ASR_OK;
-}
-
-extern "C" int asr_debug_set_lstm_flags(int flags) { g_dflags = flags; return 0; }
-
-// Asynchronous read of the sticky error word: one 4-byte device->host copy on `st`, no synchronisation.
-extern "C" int asr_peek_async_errors(asr_handle* h, unsigned* host_flags, asr_stream s) {
-  hipStream_t st = (hipStream_t)s;
-  if (!h || !host_flags) return ASR_ERR_INVALID_ARG;
-  if (h->scratch_bytes < XCH_BYTES) { *host_flags = 0; return ASR_OK; }
-  char* base = (char*)h->scratch + (h->scratch_bytes - XCH_BYTES);
-  if (hipMemcpyAsync(host_flags, base, sizeof(unsigned), hipMemcpyDeviceToHost, st) != hipSuccess)
-    ASR_FAIL(h, ASR_ERR_HIP, "asr_peek_async_errors: copy failed");
-  return ASR_OK;
-}
-// Clears the sticky error word (after it has been reported) -- and, since a launch whose hand-off timed out leaves its
-// exchange area in a state no later launch was written for (members that gave up at different steps, a header of a cluster
-// that never completed its placement handshake), puts BOTH exchange areas and their bookkeeping back to what a fresh handle
-// has: everything zero, nothing owed.  64 MiB of memset on the error path only.
-extern "C" int asr_clear_async_errors(asr_handle* h, asr_stream s) {
-  hipStream_t st = (hipStream_t)s;
-  if (!h) return ASR_ERR_INVALID_ARG;
-  if (h->scratch_bytes < XCH_BYTES) return ASR_OK;
-  char* base = (char*)h->scratch + (h->scratch_bytes - XCH_BYTES);
-  if (hipMemsetAsync(base, 0, XCH_BYTES, st) != hipSuccess) ASR_FAIL(h, ASR_ERR_HIP, "asr_clear_async_errors");
-  h->xch_dirty[0] = h->xch_dirty[1] = 0;
-  h->xch_next = 0;
-  return ASR_OK;
-}
 extern "C" int asr_debug_cluster_cycles(unsigned long long* out, int n) {
   if (!g_cdbg_host || n > 1280) return -1;
   return hipMemcpy(out, g_cdbg_host, n * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess ? 0 : -3;
-}
-
-// Synchronises the device and returns the sticky error word of the cluster kernels
-// (bit 0: forward hand-off timed out, bit 1: backward); 0 = fine.
-extern "C" int asr_check_async_errors(asr_handle* h, unsigned* flags_out) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  unsigned v = 0;
-  char* base = (char*)h->scratch + (h->scratch_bytes - XCH_BYTES);
-  if (hipDeviceSynchronize() != hipSuccess ||
-      hipMemcpy(&v, base, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess)
-    ASR_FAIL(h, ASR_ERR_HIP, "asr_check_async_errors: device error");
-  if (flags_out) *flags_out = v;
-  if (v & 3u) ASR_FAIL(h, ASR_ERR_HIP, "LSTM cluster hand-off timed out (flags 0x%x)", v);
-  if (v) ASR_FAIL(h, ASR_ERR_HIP, "LSTM recurrence produced a non-finite hidden state (flags 0x%x)", v);
-  return ASR_OK;
 }

@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE of tests/test_gpu_gru_variants.py and tests/test_gru_variants_host.py: the GRU recurrence of
-csrc/gru.hip and of the two GRU cluster kernels of csrc/lstm_cluster.hip, as
+csrc/gru.hip and of the two GRU cluster kernels of csrc/gru_cluster.hip, as
 
   * a plain reference (gru_reference): the recurrence of models/encoders/core/gru.py on hoisted x-projections, written
     with explicit per-frame loops and hand-written backward formulas in numpy -- float64 for the reference, float32 for
@@ -27,8 +27,8 @@ import functools
 import numpy as np
 
 XCH_BYTES = 64 << 20                      # csrc/common.h: ASR_XCH_BYTES
-XCH_HALF = ((XCH_BYTES - 256) // 2) & ~255  # csrc/lstm_cluster.hip: one of the two exchange areas
-XHDR = 16                                 # csrc/lstm_cluster.hip: header granules per cluster
+XCH_HALF = ((XCH_BYTES - 256) // 2) & ~255  # csrc/cluster_launch.h: one of the two exchange areas
+XHDR = 16                                 # csrc/cluster_xch.h: header granules per cluster
 LDS_LIMIT = 160 * 1024
 ROOM = (192 << 20) - XCH_BYTES            # scratch below the exchange area of a handle with asr_create's 192 MiB arena
 CLUSTER_WIDTHS = (64, 128, 256, 320)

@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE of tests/test_gpu_lstm_variants.py and tests/test_lstm_variants_host.py: the LSTM recurrence of
-csrc/lstm.hip (single-CU kernels) and csrc/lstm_cluster.hip (the cluster forms), as
+csrc/lstm.hip (single-CU kernels) and csrc/lstm_cluster.hip / csrc/lstm_cluster_f32.hip (the cluster forms), as
 
   * a plain reference (lstm_forward / lstm_backward): LSTMBlockCell under dynamic_rnn on hoisted x-projections, written
     with explicit per-frame loops and hand-written BPTT in numpy -- float64 for the reference, float32 for the yardstick
@@ -7,7 +7,7 @@ csrc/lstm.hip (single-CU kernels) and csrc/lstm_cluster.hip (the cluster forms),
     emitted h, the saved gates, dG entering dG W_h^T: the list of oracle/lstm.py).  Written apart from oracle/lstm.py and
     tests/_cpu_ops.py so that the host test can hold them against each other;
   * the dispatch rule (expected_form): every condition of asr_lstm_fwd / lstm_bwd_impl, asr_cluster_fwd_try /
-    asr_cluster_bwd_try, the _f32_ attempts, cluster_launch_plan / cluster_tile_plan, units_per_cu and the forward split's
+    asr_cluster_bwd_try, their _f32_ forms, cluster_launch_plan / cluster_tile_plan, units_per_cu and the forward split's
     T < 65536 restated, so that every device call of the tests can assert the one counter of ops.lstm_kernel_counts it
     must move;
   * the case lists, each case the smallest that reaches its path.
@@ -34,8 +34,8 @@ import functools
 import numpy as np
 
 XCH_BYTES = 64 << 20                        # csrc/common.h: ASR_XCH_BYTES
-XCH_HALF = ((XCH_BYTES - 256) // 2) & ~255  # csrc/lstm_cluster.hip: one of the two exchange areas
-XHDR = 16                                   # csrc/lstm_cluster.hip: header granules per cluster
+XCH_HALF = ((XCH_BYTES - 256) // 2) & ~255  # csrc/cluster_launch.h: one of the two exchange areas
+XHDR = 16                                   # csrc/cluster_xch.h: header granules per cluster
 SCRATCH = 192 << 20                         # asr_create's arena
 LSTM_UNITS = (64, 128, 192, 256, 320, 512)  # ASR_H_DISPATCH
 FORMS = ('bf16_cu16', 'bf16_hs32', 'bf16_hs64', 'f32_split', 'f32_hs32', 'f32_hs64', 'single_bf16', 'single_f32')
@@ -75,7 +75,7 @@ def env_flags(env):
 
 
 def units_per_cu(pass_, flags, env, allow16=False):
-    """units_per_cu of lstm_cluster.hip: 64 with flag bit 9 or ASR_LSTM_{FWD,BWD}_HS / ASR_LSTM_HS = 64, else 32; with
+    """units_per_cu of cluster_host.hip: 64 with flag bit 9 or ASR_LSTM_{FWD,BWD}_HS / ASR_LSTM_HS = 64, else 32; with
     allow16 (the bf16 forward at H = 256) 16 by default or when the variable says 16, inverted by flag bit 13."""
     if flags & F_HS64:
         return 64

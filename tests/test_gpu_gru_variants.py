@@ -1,4 +1,4 @@
-"""The GRU recurrence (csrc/gru.hip and the two GRU cluster kernels of csrc/lstm_cluster.hip) at every form asr_gru_fwd and
+"""The GRU recurrence (csrc/gru.hip and the two GRU cluster kernels of csrc/gru_cluster.hip) at every form asr_gru_fwd and
 asr_gru_bwd can end in -- clusters of H / 32 CUs, the persistent single-CU kernel, the launch-per-step kernels -- each
 device call between a reset of ops.gru_kernel_counts and an assert that exactly the counter the dispatch rule predicts
 (tests/_gru_variants.py::expected_form) moved by one, and every result compared with a float64 reference written apart

@@ -1,4 +1,4 @@
-"""The LSTM recurrence (csrc/lstm.hip, csrc/lstm_cluster.hip) at every form asr_lstm_fwd and asr_lstm_bwd(_ex) can end in
+"""The LSTM recurrence (csrc/lstm.hip, csrc/lstm_cluster*.hip) at every form asr_lstm_fwd and asr_lstm_bwd(_ex) can end in
 -- the bf16 clusters of 16 / 32 / 64 units per CU, the fp32 three-term split, the exact fp32 clusters of 32 / 64 units per
 CU, the single-CU kernels of both dtypes; fifteen counters -- each device call between a reset of ops.lstm_kernel_counts
 and an assert that exactly the counter the dispatch rule predicts (tests/_lstm_variants.py::expected_form) moved by one,

@@ -1,5 +1,5 @@
 """GPU: cluster recurrences in tile groups.  A batch that needs more clusters than the chip has CUs for runs as several
-launches over consecutive tile ranges of the same kernels (csrc/lstm_cluster.hip).  A cluster never talks to another
+launches over consecutive tile ranges of the same kernels (csrc/cluster_launch.h).  A cluster never talks to another
 cluster, so the result must be the one-launch result BIT FOR BIT; asr_debug_set_cluster_cu_budget lowers the number of
 co-resident workgroups a launch may use so that the group loop, a partial last group and every kernel family run at
 B = 80 - 144 instead of B = 272+; the counters of asr_recurrence_path_counts say which path ran."""

@@ -1,4 +1,4 @@
-"""CPU: the plan of the cluster recurrences' tile groups (asr_cluster_tile_groups, csrc/lstm_cluster.hip) -- pure integer
+"""CPU: the plan of the cluster recurrences' tile groups (asr_cluster_tile_groups, csrc/cluster_host.hip) -- pure integer
 arithmetic behind the C ABI, no GPU.  A launch of G workgroups per cluster over m tiles needs 8 G ceil(m ndir / 8)
 co-resident workgroups; a batch that needs more than the budget runs as consecutive launches over tile ranges."""
 import ctypes as C
