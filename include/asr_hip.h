@@ -468,6 +468,20 @@ int asr_lstm_prep_weights(asr_handle* h, int dtype, const float* kernel, const f
 int asr_lstm_prep_layer(asr_handle* h, int dtype, int ndir, const float* const* vars, int Din, int ldk, int H,
                         void* wxT, void* wx_cat, float* bias_cat, void* packed_fwd, void* packed_bwd,
                         float* peep_out, asr_stream s);
+/* asr_lstm_prep_layers: the images of asr_lstm_prep_layer for a whole stack of layers, byte for byte, in ONE launch
+ * (one per 16 layers beyond that).  `layers`: host array of nlayers descriptors, read during the call only (they travel
+ * in the kernel arguments: no device table, no copy on the stream); every field means what the argument of the same
+ * name means to asr_lstm_prep_layer.  All layers share `dtype`.  Nothing is launched if any descriptor is refused. */
+typedef struct asr_lstm_prep_desc {
+  int ndir;
+  const float* const* vars;
+  int Din, ldk, H;
+  void *wxT, *wx_cat;
+  float* bias_cat;
+  void *packed_fwd, *packed_bwd;
+  float* peep_out;
+} asr_lstm_prep_desc;
+int asr_lstm_prep_layers(asr_handle* h, int dtype, int nlayers, const asr_lstm_prep_desc* layers, asr_stream s);
 /* asr_lstm_grad_finish: the way back for one layer's gradients, one launch.  dw_il [ndir][rows = Din+H][4H] fp32 with
  * interleaved columns (output of the weight-gradient GEMMs) and dpeep_dbias [ndir][7][H] (asr_lstm_bwd) are written
  * to grads[ndir*5] = the gradient buffers of the same five variables, in TF's layouts (kernel gate-major). */

@@ -16,6 +16,12 @@ OPTIMIZER_IDS = {'sgd': 0, 'momentum': 1, 'nestrov': 2, 'adagrad': 3, 'adadelta'
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _i64, _u64 = C.c_int64, C.c_uint64
 
+class LstmPrepDesc(C.Structure):
+    """asr_lstm_prep_desc of include/asr_hip.h: one layer of asr_lstm_prep_layers."""
+    _fields_ = [('ndir', _i), ('vars', _vp), ('Din', _i), ('ldk', _i), ('H', _i), ('wxT', _vp), ('wx_cat', _vp),
+                ('bias_cat', _vp), ('packed_fwd', _vp), ('packed_bwd', _vp), ('peep_out', _vp)]
+
+
 # name -> (restype, argtypes); mirrors include/asr_hip.h declaration by declaration
 SIGNATURES = {
     'asr_abi_version': (_i, []),
@@ -86,6 +92,7 @@ SIGNATURES = {
     'asr_softmax_xent_soft': (_i, [_vp, _vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
     'asr_lstm_prep_weights': (_i, [_vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'asr_lstm_prep_layer': (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'asr_lstm_prep_layers': (_i, [_vp, _i, _i, _vp, _vp]),
     'asr_lstm_grad_finish': (_i, [_vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp]),
     'asr_gate_deinterleave': (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _vp]),
     'asr_lstm_fwd': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -193,6 +193,123 @@ __global__ void prep_layer_kernel(PrepVars v, int ndir, int Din, int ldk, int H,
   }
 }
 
+// The same images for a STACK of layers in one launch (asr_lstm_prep_layers), byte for byte: every element is one fp32
+// value converted, so who writes it changes no bit.  The descriptors travel by value in the kernel arguments (no device
+// table, no copy); layer i owns blocks [block0, block0 + ndir * upd) of the grid and a block is ONE unit of one direction:
+//   X (nX = ceil(ldk/32) * H/32)  32 rows of W_x x 32 units x 4 gates through LDS -> the wx_cat rows (256-B runs) and the
+//                                 transposed wxT rows (64-B runs, zeros from Din to ldk); W_x is read once, in 128-B runs
+//                                 (prep_layer_kernel reads it twice, the second time with a stride of 4H floats)
+//   B (nB = H/16 * H/32)          16 rows of W_h x 32 units x 4 gates -> 2048 consecutive elements of packed_bwd
+//   F (nF = (H/32)^2 * 4)         32 rows of W_h x 32 columns of one gate -> two 512-element fragments of packed_fwd
+//   S (the rest)                  256 elements of the bias, then of the peephole block
+// and the index arithmetic per element is shifts and masks (the units are powers of two; H only enters per block).
+constexpr int PREP_MAX_LAYERS = 16;
+struct PrepLayer {
+  PrepVars v;
+  void *wxT, *wx_cat;
+  float* bias_cat;
+  void *pf, *pb;
+  float* peep_out;
+  int ndir, Din, ldk, H;
+  int block0, upd, nX, nB, nF;   // first block; units per direction; of which X, B, F
+};
+struct PrepGroup { PrepLayer l[PREP_MAX_LAYERS]; int n; };
+static_assert(sizeof(PrepGroup) <= 4096, "PrepGroup must fit the kernel argument segment");
+
+template <typename T>
+__global__ __launch_bounds__(256) void prep_layers_kernel(PrepGroup g) {
+  constexpr int KV = LT<T>::KV;
+  constexpr int E = 16 / sizeof(T);
+  static_assert(KV == 4 * E, "a fragment is four row groups of E elements");
+  constexpr int SX = 129, SB = 136, SF = 40;      // LDS row strides (floats) of the three tiles: see the reads below
+  __shared__ float tile[32 * SX];
+  int li = 0;
+  while (li + 1 < g.n && (int)blockIdx.x >= g.l[li + 1].block0) ++li;
+  const PrepLayer& L = g.l[li];
+  const int H = L.H, G = 4 * H, Din = L.Din, ldk = L.ldk, ndir = L.ndir, HT = H / 32;
+  int u = (int)blockIdx.x - L.block0;
+  const int d = u / L.upd;
+  u -= d * L.upd;
+  const float* __restrict__ kernel = L.v.kernel[d];
+  const float* __restrict__ wh = kernel + (size_t)Din * G;
+  const size_t n_wh = (size_t)H * G;
+  const int t = threadIdx.x;
+  if (u < L.nX) {
+    const int r0 = (u / HT) * 32, j0 = (u % HT) * 32;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {                 // rows r0.., per row the four 128-B runs of units j0..j0+31
+      const int e = t + 256 * i, rl = e >> 7, c = e & 127, q = c >> 5, jj = c & 31, r = r0 + rl;
+      tile[rl * SX + jj * 4 + q] = r < Din ? kernel[(size_t)r * G + q * H + j0 + jj] : 0.f;
+    }
+    __syncthreads();
+    T* __restrict__ wx_cat = (T*)L.wx_cat;
+    T* __restrict__ wxT = (T*)L.wxT;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {                 // wx_cat: row r, interleaved columns j0*4 .. +127
+      const int e = t + 256 * i, rl = e >> 7, cpl = e & 127, r = r0 + rl;
+      if (r < Din) wx_cat[(size_t)r * ndir * G + (size_t)d * G + j0 * 4 + cpl] = Elem<T>::from_f32(tile[rl * SX + cpl]);
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {                 // wxT: row cp, columns r0 .. +31 (odd stride: two lanes per bank)
+      const int e = t + 256 * i, cpl = e >> 5, rl = e & 31, r = r0 + rl;
+      if (r < ldk) wxT[((size_t)d * G + j0 * 4 + cpl) * ldk + r] = Elem<T>::from_f32(tile[rl * SX + cpl]);
+    }
+    return;
+  }
+  u -= L.nX;
+  if (u < L.nB) {
+    // packed_bwd of row block ub: element ((ks*64 + rg*16 + n)*E + e) holds Wh[ub*16 + n][k'] with k' = ks*KV + rg*E + e
+    // = j*4 + q, i.e. ascending k' in digits (ks, rg, e): units j0..j0+31 are k' = 4*j0 .. +127, 2048 consecutive elements
+    const int ub = u / HT, j0 = (u % HT) * 32;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int e = t + 256 * i, n = e >> 7, c = e & 127, q = c >> 5, jj = c & 31;
+      tile[n * SB + jj * 4 + q] = wh[(size_t)(ub * 16 + n) * G + q * H + j0 + jj];
+    }
+    __syncthreads();
+    T* __restrict__ pb = (T*)L.pb + (size_t)d * n_wh + (size_t)ub * 16 * G + (size_t)64 * j0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {                  // (stride 136 = 8 mod 64: n*8 + e are distinct banks within a wave)
+      const int o = t + 256 * i, e = o % E, n = (o / E) & 15, rg = (o / (16 * E)) & 3, ksl = o / (64 * E);
+      pb[o] = Elem<T>::from_f32(tile[n * SB + ksl * KV + rg * E + e]);
+    }
+    return;
+  }
+  u -= L.nB;
+  if (u < L.nF) {
+    // packed_fwd: fragment (ub*4 + q, ks) holds Wh[ks*KV + rg*E + e][q*H + ub*16 + n] at ((rg*16 + n)*E + e); rows
+    // k0..k0+31 are 32/KV consecutive fragments = 512 consecutive elements, for each of the two 16-column blocks
+    const int k0 = (u / (4 * HT)) * 32, q = (u % (4 * HT)) / HT, u0 = (u % HT) * 32;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int e = t + 256 * i, kl = e >> 5, cl = e & 31;
+      tile[kl * SF + cl] = wh[(size_t)(k0 + kl) * G + q * H + u0 + cl];
+    }
+    __syncthreads();
+    T* __restrict__ pf = (T*)L.pf + (size_t)d * n_wh;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {                  // (stride 40: 40*e mod 64 runs over the multiples of 8, + n < 8)
+      const int o4 = t + 256 * i, ubl = o4 >> 9, o = o4 & 511;
+      const int e = o % E, n = (o / E) & 15, rg = (o / (16 * E)) & 3, ksl = o / (64 * E);
+      const int ub = u0 / 16 + ubl, kl = ksl * KV + rg * E + e;
+      pf[((size_t)(ub * 4 + q) * H + k0) * 16 + o] = Elem<T>::from_f32(tile[kl * SF + ubl * 16 + n]);
+    }
+    return;
+  }
+  u -= L.nF;
+  if (u < G / 256) {
+    const int cp = u * 256 + t;
+    L.bias_cat[(size_t)d * G + cp] = L.v.bias[d][(cp & 3) * H + (cp >> 2)];
+    return;
+  }
+  const int idx = (u - G / 256) * 256 + t;         // only layers with peep_out have units here
+  if (idx < 3 * H) {
+    const int k = idx / H;
+    const float* p = k == 0 ? L.v.peep[d][0] : k == 1 ? L.v.peep[d][1] : L.v.peep[d][2];
+    L.peep_out[(size_t)d * 3 * H + idx] = p[idx - k * H];
+  }
+}
+
 // The inverse trip for the gradients of one layer (both directions, one launch): dW [ndir][Din+H][4H] with interleaved
 // columns (what the weight-gradient GEMMs write) -> kernel gradient in TF's gate-major layout; rows 3..6 of
 // dpeep [ndir][7][H] (bias gradient by gate, accumulated inside the BPTT kernel) -> bias gradient; rows 0..2 -> the
@@ -850,6 +967,57 @@ extern "C" int asr_lstm_prep_layer(asr_handle* h, int dtype, int ndir, const flo
     hipLaunchKernelGGL(prep_layer_kernel<bf16_t>, dim3(blocks), dim3(256), 0, (hipStream_t)s, v, ndir, Din, ldk, H,
                        (bf16_t*)wxT, (bf16_t*)wx_cat, bias_cat, (bf16_t*)packed_fwd, (bf16_t*)packed_bwd, peep_out);
   ASR_CHECK_LAUNCH(h, "asr_lstm_prep_layer");
+  return ASR_OK;
+}
+
+extern "C" int asr_lstm_prep_layers(asr_handle* h, int dtype, int nlayers, const asr_lstm_prep_desc* layers,
+                                    asr_stream s) {
+  if (!h) return ASR_ERR_INVALID_ARG;
+  if (!asr_dtype_ok(dtype) || nlayers < 0 || (nlayers && !layers))
+    ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_lstm_prep_layers: bad args");
+  for (int i = 0; i < nlayers; ++i) {   // everything is checked before anything is launched
+    const asr_lstm_prep_desc& L = layers[i];
+    if ((L.ndir != 1 && L.ndir != 2) || !L.vars || !L.wxT || !L.wx_cat || !L.bias_cat || !L.packed_fwd ||
+        !L.packed_bwd || L.Din <= 0 || L.ldk < L.Din || L.H <= 0 || L.H % 64)
+      ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_lstm_prep_layers: layer %d: H=%d must be a multiple of 64, ldk=%d >= Din=%d", i,
+               L.H, L.ldk, L.Din);
+    for (int d = 0; d < L.ndir; ++d) {
+      if (!L.vars[d * 5] || !L.vars[d * 5 + 1])
+        ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_lstm_prep_layers: kernel / bias of layer %d, direction %d missing", i, d);
+      if (L.peep_out && (!L.vars[d * 5 + 2] || !L.vars[d * 5 + 3] || !L.vars[d * 5 + 4]))
+        ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_lstm_prep_layers: peep_out given but a peephole vector of layer %d, direction %d is missing", i, d);
+    }
+  }
+  for (int i0 = 0; i0 < nlayers; i0 += PREP_MAX_LAYERS) {   // one launch for up to PREP_MAX_LAYERS layers
+    PrepGroup g;
+    memset(&g, 0, sizeof(g));
+    g.n = nlayers - i0 < PREP_MAX_LAYERS ? nlayers - i0 : PREP_MAX_LAYERS;
+    long long blocks = 0;
+    for (int i = 0; i < g.n; ++i) {
+      const asr_lstm_prep_desc& L = layers[i0 + i];
+      PrepLayer& P = g.l[i];
+      for (int d = 0; d < L.ndir; ++d) {
+        P.v.kernel[d] = L.vars[d * 5 + 0];
+        P.v.bias[d] = L.vars[d * 5 + 1];
+        for (int k = 0; k < 3; ++k) P.v.peep[d][k] = L.vars[d * 5 + 2 + k];
+      }
+      P.wxT = L.wxT, P.wx_cat = L.wx_cat, P.bias_cat = L.bias_cat, P.pf = L.packed_fwd, P.pb = L.packed_bwd;
+      P.peep_out = L.peep_out;
+      P.ndir = L.ndir, P.Din = L.Din, P.ldk = L.ldk, P.H = L.H;
+      const long long HT = L.H / 32;
+      const long long nX = ((long long)L.ldk + 31) / 32 * HT, nB = (L.H / 16) * HT, nF = HT * HT * 4;
+      const long long upd = nX + nB + nF + 4 * L.H / 256 + (L.peep_out ? (3 * L.H + 255) / 256 : 0);
+      if (blocks + L.ndir * upd > 0x7fffffffLL)
+        ASR_FAIL(h, ASR_ERR_INVALID_ARG, "asr_lstm_prep_layers: layer %d: too many units for one grid", i0 + i);
+      P.block0 = (int)blocks, P.upd = (int)upd, P.nX = (int)nX, P.nB = (int)nB, P.nF = (int)nF;
+      blocks += L.ndir * upd;
+    }
+    if (dtype == ASR_F32)
+      hipLaunchKernelGGL(prep_layers_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)s, g);
+    else
+      hipLaunchKernelGGL(prep_layers_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)s, g);
+    ASR_CHECK_LAUNCH(h, "asr_lstm_prep_layers");
+  }
   return ASR_OK;
 }
 

@@ -155,7 +155,8 @@ class CTC(ModelBase):
         self.store = ParamStore(self.device)
         enc_dim = self.encoder.build(self.store, input_size * num_stack * splice, rng)
         self._enc_dim = enc_dim
-        self._head_imgs = None                           # (Wt, Wp) of ops.ctc_head_prep, refreshed per step
+        self._head_imgs = None                           # (Wt, Wp) of ops.ctc_head_prep, refreshed per weight version
+        self._head_key = None                            # store.image_key() the head images were built from
         self._head_state = None
         self._declare_heads(rng, enc_dim, parameter_init)
         self.store.finalize()
@@ -284,9 +285,15 @@ class CTC(ModelBase):
 
     def _refresh_head_shadow(self):
         """Operand-dtype copies of the head weights (cast per variable on first use after an update), and beside them
-        the images of the fused head launches (once per step, on the encoder's side stream)."""
+        the images of the fused head launches (once per weight version behind the encoder's grouped weight-image launch,
+        or once per call on its side stream)."""
         if getattr(self, '_want_head_imgs', False):
-            ops.ctc_head_prep(self.store[self.head_scope + '/weights'], out=self._head_imgs)
+            # an encoder that keeps its weight images per weight version (weight_images) calls this on the main stream
+            # at every call: the head images then live under the same key; any other encoder gets them per call
+            key = self.store.image_key() if getattr(self.encoder, 'weight_images', False) else None
+            if key is None or key != self._head_key:
+                ops.ctc_head_prep(self.store[self.head_scope + '/weights'], out=self._head_imgs)
+                self._head_key = key
         sh = self.store.shadow(self.dtype)
         if sh is not self.store:
             for n in self.store.names:

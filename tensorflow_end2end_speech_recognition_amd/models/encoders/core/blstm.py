@@ -39,6 +39,10 @@ WARM_BPTT = _os.environ.get('ASR_WARM_BPTT', '1') != '0'    # A-B switch of the 
 # queue and the pipelines serialise (70.6 / 81.1 / 47.8).  (The dropout masks of the two forms differ: a mask is indexed
 # by the element's position in ITS part's tensor.)
 ENC_HALVES = _os.environ.get('ASR_ENC_HALVES', '0') == '1'
+# the layers' weight images are kept per weight version and rebuilt in one grouped launch on the main stream
+# (_cached_preps).  ASR_WEIGHT_IMAGES=0 (or encoder.weight_images = False): one launch per layer and call on
+# the side lane, beside the first recurrence (A-B).
+WEIGHT_IMAGES = _os.environ.get('ASR_WEIGHT_IMAGES', '1') != '0'
 PIPE_LANE = 6
 
 # tf.contrib.rnn.LSTMStateTuple: what the reference's encoders hand back as final state (.c, .h)
@@ -93,6 +97,8 @@ class _RecurrentEncoderBase(object):
         self.layers_b = None           # twin layer objects (same variables, own tape) of the second pipeline
         self._split = 0                # rows of the first part in the last __call__ (0: one pipeline)
         self._rows = None              # per pipeline (int32 device vector, count): valid frames of the last __call__
+        self.weight_images = WEIGHT_IMAGES   # keep the layers' weight images per weight version (see WEIGHT_IMAGES)
+        self._images, self._image_key = None, None
 
     # variables are created at graph-build time in the reference; here when the input size is known
     def build(self, store, input_dim, rng, scope_prefix=''):
@@ -165,28 +171,12 @@ class _RecurrentEncoderBase(object):
         def rs_of(li):
             return (rng_state[0], rng_state[1] + li * (1 << 32)) if rng_state is not None else None
 
-        # side stream, in this order: the weight images of every layer (one launch and one event each: the first
-        # layer's GEMM waits for ~10 us of side work, not for the masks), whatever else the model wants refreshed once
-        # per step (side_extra: the operand-dtype shadow of the head weights), then the dropout masks (one event each)
-        preps, ready_w, ready_m = [], [], []
-        with ops.side_lane(inputs.device):
-            # with two layers or more, side_extra goes in front of the LAST layer's marker: the main stream waits for
-            # that one anyway (before the second layer), so the caller needs no wait of its own in front of the head
-            fold = self.side_extra is not None and len(self.layers) >= 2
-            self.side_extra_event = None
-            for li, layer in enumerate(self.layers):
-                preps.append(layer.prepare(inputs.device, self.dtype, Tt, Bp, 1.0, False, None, None,
-                                           ldk=ldk0 if li == 0 else None))
-                if fold and li + 1 == len(self.layers):
-                    self.side_extra()
-                ready_w.append(ops.stream_event())
-            if self.side_extra is not None and not fold:
-                self.side_extra()
-                self.side_extra_event = ops.stream_event()   # the caller waits for it before using what it refreshed
-            for li, layer in enumerate(self.layers):
-                dm = drop_masks[li] if drop_masks is not None else None
-                preps[li]['mask'] = layer.make_mask(inputs.device, Tt, Bp, keep_prob, is_training, rs_of(li), dm)
-                ready_m.append(ops.stream_event())
+        if self.weight_images:
+            preps, ready_w, ready_m = self._cached_preps(inputs.device, ldk0, Tt, Bp, keep_prob, is_training, rs_of,
+                                                         drop_masks)
+        else:
+            preps, ready_w, ready_m = self._side_preps(inputs.device, ldk0, Tt, Bp, keep_prob, is_training, rs_of,
+                                                       drop_masks)
         self._split = self._split_rows(Bp) if drop_masks is None else 0
         self._top_deferred, self._top_drop = False, None
         # the valid frames of each pipeline's [T, B] layout (rnn_util.VALID_ROWS): built on the host, uploaded once per
@@ -223,6 +213,59 @@ class _RecurrentEncoderBase(object):
                 # blstm.py:326-328: outputs_sub IS the tensor the next layer consumes (after the dropout wrapper)
                 self._out_sub_op, self._final_sub_ch = x, final
         return self._finish_call(x, finals, seq_len, B)
+
+    def _cached_preps(self, device, ldk0, Tt, Bp, keep_prob, is_training, rs_of, drop_masks):
+        """The weight images of every layer, kept while the variables are what they were built from.  The key is the
+        store's (ParamStore.image_key: in-place torch writes and native writers), the operand dtype and the bottom
+        layer's row width; a stale key costs ONE grouped launch (ops.lstm_prep_layers) on the main stream, in front of
+        the first projection GEMM -- nothing runs beside the first recurrence, and no event is recorded or waited for.
+        A rebuild allocates new images: a tape that still holds the old ones keeps what its forward pass used.
+        side_extra (the model's head images) follows on the main stream; the model keys it the same way."""
+        key = self.store.image_key() + (self.dtype, ldk0)
+        if key != self._image_key:
+            self._images = ops.lstm_prep_layers(
+                [dict(variables=layer._vars(self.store.__getitem__), din=layer.din, H=layer.H, dtype=self.dtype,
+                      ldk=ldk0 if li == 0 else None) for li, layer in enumerate(self.layers)])
+            self._image_key = key
+        self.side_extra_event = None
+        if self.side_extra is not None:
+            self.side_extra()
+        preps, ready_m = [], []
+        for li, layer in enumerate(self.layers):
+            dm = drop_masks[li] if drop_masks is not None else None
+            w = dict(self._images[li])
+            w['mask'] = layer.make_mask(device, Tt, Bp, keep_prob, is_training, rs_of(li), dm)
+            preps.append(w)
+            # a mask tensor comes from the caller: its consumers are ordered behind this point of the main stream
+            ready_m.append(ops.stream_event() if torch.is_tensor(w['mask']) and w['mask'].is_cuda else None)
+        return preps, [None] * len(self.layers), ready_m
+
+    def _side_preps(self, device, ldk0, Tt, Bp, keep_prob, is_training, rs_of, drop_masks):
+        """weight_images off (ASR_WEIGHT_IMAGES=0): the images of every layer rebuilt per call, one launch per layer on
+        the side lane."""
+        # side stream, in this order: the weight images of every layer (one launch and one event each: the first
+        # layer's GEMM waits for ~10 us of side work, not for the masks), whatever else the model wants refreshed once
+        # per step (side_extra: the operand-dtype shadow of the head weights), then the dropout masks (one event each)
+        preps, ready_w, ready_m = [], [], []
+        with ops.side_lane(device):
+            # with two layers or more, side_extra goes in front of the LAST layer's marker: the main stream waits for
+            # that one anyway (before the second layer), so the caller needs no wait of its own in front of the head
+            fold = self.side_extra is not None and len(self.layers) >= 2
+            self.side_extra_event = None
+            for li, layer in enumerate(self.layers):
+                preps.append(layer.prepare(device, self.dtype, Tt, Bp, 1.0, False, None, None,
+                                           ldk=ldk0 if li == 0 else None))
+                if fold and li + 1 == len(self.layers):
+                    self.side_extra()
+                ready_w.append(ops.stream_event())
+            if self.side_extra is not None and not fold:
+                self.side_extra()
+                self.side_extra_event = ops.stream_event()   # the caller waits for it before using what it refreshed
+            for li, layer in enumerate(self.layers):
+                dm = drop_masks[li] if drop_masks is not None else None
+                preps[li]['mask'] = layer.make_mask(device, Tt, Bp, keep_prob, is_training, rs_of(li), dm)
+                ready_m.append(ops.stream_event())
+        return preps, ready_w, ready_m
 
     # the two places where the encoders with skip connections (residual.py) differ in the forward loop; the plain
     # stack has none

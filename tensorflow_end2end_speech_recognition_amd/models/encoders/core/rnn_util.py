@@ -126,8 +126,9 @@ class LSTMLayer(object):
         """Everything of a layer's forward that does not depend on its input: operand-dtype weight
         images (W_x transposed + zero-padded to the input's row width `ldk` for the GEMM's fast path, W_x
         with both directions side by side for dx, W_h in MFMA fragment order for both passes, the
-        peephole block: ONE launch) and the dropout mask.  The encoder issues this for every layer on
-        the side stream at the start of the step, under the first recurrence kernels."""
+        peephole block: ONE launch) and the dropout mask.  The per-call path: forward(prep=None), and the
+        blstm / lstm encoders with weight_images off, which issue it for every layer on the side stream at
+        the start of the step (by default they keep the images per weight version: blstm._cached_preps)."""
         w = ops.lstm_prep_layer(self._vars(self.store.__getitem__), self.din, self.H, dtype, ldk=ldk)
         w['mask'] = self.make_mask(device, T, B, keep_prob, is_training, rng_state, drop_mask)
         return w

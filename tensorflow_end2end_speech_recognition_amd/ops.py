@@ -1130,12 +1130,9 @@ def _ptr_table(rows):
     return (C.c_void_p * len(flat))(*flat)
 
 
-def lstm_prep_layer(variables, din, H, dtype, ldk=None):
-    """variables: per direction (kernel [Din+H,4H], bias [4H], w_i_diag, w_f_diag, w_o_diag [H] or None) fp32 views.
-    One launch -> dict(wxT [ndir*4H, ldk], wx_cat [Din, ndir*4H], bias [ndir*4H] fp32, whf / whb [ndir, H*4H] packed
-    W_h, peep [ndir,3,H] fp32 or None) in the operand dtype (include/asr_hip.h asr_lstm_prep_layer)."""
+def _prep_layer_args(variables, din, H, dtype, ldk, out=None):
+    """The checks of lstm_prep_layer and its six images (allocated here, or `out` when the caller owns them)."""
     k0 = variables[0][0]
-    h = _h(k0)
     ndir = len(variables)
     ldk = din if ldk is None else int(ldk)
     for v in variables:
@@ -1144,16 +1141,116 @@ def lstm_prep_layer(variables, din, H, dtype, ldk=None):
             raise ValueError('kernel must be [Din+H,4H]')
     has_peep = len(variables[0]) >= 5 and variables[0][2] is not None
     dev, tdt = k0.device, TORCH_DTYPE[dtype]
-    out = dict(wxT=torch.empty((ndir * 4 * H, ldk), dtype=tdt, device=dev),
-               wx_cat=torch.empty((din, ndir * 4 * H), dtype=tdt, device=dev),
-               bias=torch.empty((ndir * 4 * H,), dtype=torch.float32, device=dev),
-               whf=torch.empty((ndir, H * 4 * H), dtype=tdt, device=dev),
-               whb=torch.empty((ndir, H * 4 * H), dtype=tdt, device=dev),
-               peep=torch.empty((ndir, 3, H), dtype=torch.float32, device=dev) if has_peep else None)
+    shapes = dict(wxT=((ndir * 4 * H, ldk), tdt), wx_cat=((din, ndir * 4 * H), tdt),
+                  bias=((ndir * 4 * H,), torch.float32), whf=((ndir, H * 4 * H), tdt), whb=((ndir, H * 4 * H), tdt),
+                  peep=((ndir, 3, H), torch.float32))
+    if out is None:
+        out = dict((k, torch.empty(sh, dtype=dt, device=dev)) for k, (sh, dt) in shapes.items())
+        if not has_peep:
+            out['peep'] = None
+    else:
+        for k, (sh, dt) in shapes.items():
+            t = out.get(k)
+            if k == 'peep' and not has_peep:
+                if t is not None:
+                    raise ValueError('lstm_prep_layers: out has a peephole image for a layer without peepholes')
+                continue
+            if t is None or tuple(t.shape) != sh or t.dtype != dt or t.device != dev or not t.is_contiguous():
+                raise ValueError('lstm_prep_layers: out[%r] must be a contiguous %s tensor of shape %s on %s'
+                                 % (k, dt, sh, dev))
+    return ndir, ldk, out
+
+
+def lstm_prep_layer(variables, din, H, dtype, ldk=None):
+    """variables: per direction (kernel [Din+H,4H], bias [4H], w_i_diag, w_f_diag, w_o_diag [H] or None) fp32 views.
+    One launch -> dict(wxT [ndir*4H, ldk], wx_cat [Din, ndir*4H], bias [ndir*4H] fp32, whf / whb [ndir, H*4H] packed
+    W_h, peep [ndir,3,H] fp32 or None) in the operand dtype (include/asr_hip.h asr_lstm_prep_layer)."""
+    h = _h(variables[0][0])
+    ndir, ldk, out = _prep_layer_args(variables, din, H, dtype, ldk)
     h.check(h.lib.asr_lstm_prep_layer(h.h, dtype, ndir, _ptr_table(variables), din, ldk, H, _p(out['wxT']),
                                       _p(out['wx_cat']), _p(out['bias']), _p(out['whf']), _p(out['whb']),
                                       _p(out['peep']), _s()), 'asr_lstm_prep_layer')
+    _count_prep(variables[0][0].device, per_layer=1)
     return out
+
+
+_lstm_prep_layer_native = lstm_prep_layer
+_prep_counts = {}      # device index (-1: host) -> [grouped, per_layer]
+
+
+def _prep_key(device):
+    if isinstance(device, torch.device):
+        return (device.index or 0) if device.type == 'cuda' else -1
+    return -1 if device in ('cpu', None) else int(device)
+
+
+def _count_prep(device, grouped=0, per_layer=0):
+    c = _prep_counts.setdefault(_prep_key(device), [0, 0])
+    c[0] += grouped
+    c[1] += per_layer
+
+
+def prep_counts(device=0):
+    """Weight-image launches on `device` ('cpu': the per-layer stand-ins of a host run) since the last
+    reset_prep_counts: `grouped` = asr_lstm_prep_layers launches (one per lstm_prep_layers call of up to 16 layers),
+    `per_layer` = asr_lstm_prep_layer launches.  Host counters: no device work, no synchronisation."""
+    c = _prep_counts.get(_prep_key(device), (0, 0))
+    return dict(grouped=int(c[0]), per_layer=int(c[1]))
+
+
+def reset_prep_counts(device=0):
+    _prep_counts.pop(_prep_key(device), None)
+
+
+def lstm_prep_layers(specs, out=None):
+    """lstm_prep_layer for a stack of layers in ONE launch (include/asr_hip.h asr_lstm_prep_layers).  specs: per layer a
+    dict(variables, din, H, dtype, ldk=None) -- the arguments of lstm_prep_layer; one dtype for all.  Returns the list
+    of dicts lstm_prep_layer would return, byte for byte; out (a list of such dicts): caller-owned images to write into.
+    Non-CUDA tensors (host runs that put stand-ins into this module): lstm_prep_layer once per layer, looked up in the
+    module at call time."""
+    specs = list(specs)
+    if out is not None and len(out) != len(specs):
+        raise ValueError('lstm_prep_layers: %d output dicts for %d layers' % (len(out), len(specs)))
+    if not specs:
+        return []
+    k0 = specs[0]['variables'][0][0]
+    if not k0.is_cuda:
+        per_layer = globals()['lstm_prep_layer']
+        if per_layer is _lstm_prep_layer_native:
+            _h(k0)      # raises: the device path has no CPU fallback
+        res = []
+        for i, sp in enumerate(specs):
+            w = per_layer(sp['variables'], sp['din'], sp['H'], sp['dtype'], ldk=sp.get('ldk'))
+            _count_prep(k0.device, per_layer=1)
+            if out is not None:
+                for k, t in w.items():
+                    if t is not None:
+                        out[i][k].copy_(t)
+                w = out[i]
+            res.append(w)
+        return res
+    h = _h(k0)
+    dtype = specs[0]['dtype']
+    descs = (_lib.LstmPrepDesc * len(specs))()
+    res, tables = [], []
+    for i, sp in enumerate(specs):
+        if sp['dtype'] != dtype:
+            raise ValueError('lstm_prep_layers: one operand dtype for all layers')
+        if sp['variables'][0][0].device != k0.device:
+            raise ValueError('lstm_prep_layers: all layers on one device')
+        ndir, ldk, o = _prep_layer_args(sp['variables'], sp['din'], sp['H'], dtype, sp.get('ldk'),
+                                        out[i] if out is not None else None)
+        tab = _ptr_table(sp['variables'])
+        tables.append(tab)
+        d = descs[i]
+        d.ndir, d.vars, d.Din, d.ldk, d.H = ndir, C.addressof(tab), sp['din'], ldk, sp['H']
+        d.wxT, d.wx_cat, d.bias_cat = o['wxT'].data_ptr(), o['wx_cat'].data_ptr(), o['bias'].data_ptr()
+        d.packed_fwd, d.packed_bwd = o['whf'].data_ptr(), o['whb'].data_ptr()
+        d.peep_out = o['peep'].data_ptr() if o.get('peep') is not None else None
+        res.append(o)
+    h.check(h.lib.asr_lstm_prep_layers(h.h, dtype, len(specs), C.addressof(descs), _s()), 'asr_lstm_prep_layers')
+    _count_prep(k0.device, grouped=(len(specs) + 15) // 16)
+    return res
 
 
 def lstm_grad_finish(grads, dw_il, dpeep, H):

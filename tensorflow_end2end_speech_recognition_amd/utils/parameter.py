@@ -33,6 +33,7 @@ class ParamStore(object):
         self._shadow_dirty = True
         self._backup = None    # the clean weights while a weight-noise perturbation is live (allocated on first use)
         self.perturbed = False
+        self.epoch = 0         # native writes to flat so far (mark_dirty): torch's version counter does not see those
 
     # -- declaration (like tf.get_variable at graph-build time)
     def declare(self, name, shape, init):
@@ -96,7 +97,16 @@ class ParamStore(object):
         return int(sum(int(np.prod(s[1])) if len(s[1]) else 1 for s in self._specs))
 
     def mark_dirty(self):
+        """Every native writer of flat calls this (the optimizer, broadcast_parameters, perturb / restore,
+        load_state_dict)."""
         self._shadow_dirty = True
+        self.epoch += 1
+
+    def image_key(self):
+        """Changes whenever the variables may have: flat's version counter covers in-place torch writes through flat or
+        any view of it, the epoch the native writers.  What is derived from the variables alone (the encoders' weight
+        images, the CTC head's) is kept under this key."""
+        return (self.flat._version, self.epoch)
 
     # -- bf16 shadow of the weights for the MFMA operand path: per variable, refreshed on first use after an update
     # (a step of the 5x256 CTC model touches one shadow variable, the 128 KB output matrix -- casting the whole 28 MB
