@@ -31,6 +31,7 @@ if ROOT not in sys.path:
 from examples.librispeech.data.load_dataset_ctc import Dataset                                              # noqa: E402
 from examples.librispeech.metrics.ctc import do_eval_cer, do_eval_wer                                       # noqa: E402
 from examples.timit.metrics.mapping_files import write_mapping_files                                        # noqa: E402
+from examples.timit.training._common import input_augment_kwargs, input_augment_tag                         # noqa: E402
 from tensorflow_end2end_speech_recognition_amd.models.ctc.ctc import CTC                                    # noqa: E402
 from tensorflow_end2end_speech_recognition_amd.utils.io.labels.sparsetensor import list2sparsetensor        # noqa: E402
 from tensorflow_end2end_speech_recognition_amd.utils.parameter import count_total_parameters                # noqa: E402
@@ -206,7 +207,8 @@ def build_model(params, device):
                 clip_grad_norm=params['clip_grad_norm'], clip_activation=params['clip_activation'],
                 num_proj=params['num_proj'], weight_decay=params['weight_decay'],
                 bottleneck_dim=params.get('bottleneck_dim'), dtype=params.get('dtype', 'bf16'), device=device,
-                seed=params.get('seed', 0), weight_noise_std=float(params.get('weight_noise_std') or 0.0))
+                seed=params.get('seed', 0), weight_noise_std=float(params.get('weight_noise_std') or 0.0),
+                **input_augment_kwargs(params))
     model.name += '_' + str(params['num_units']) + '_' + str(params['num_layers']) + '_' + params['optimizer']
     model.name += '_lr' + str(params['learning_rate'])
     if params['num_proj'] not in (0, None):
@@ -221,6 +223,7 @@ def build_model(params, device):
         model.name += '_bottle' + str(params['bottleneck_dim'])
     if params.get('weight_noise_std') and float(params['weight_noise_std']) > 0:
         model.name += '_wn' + str(params['weight_noise_std'])
+    model.name += input_augment_tag(params)
     return model
 
 

@@ -14,6 +14,37 @@ from tensorflow_end2end_speech_recognition_amd.utils.training.learning_rate_cont
 NUM_CLASSES = {'phone61': 61, 'phone48': 48, 'phone39': 39, 'character': 28, 'character_capital_divide': 72}
 
 
+def input_augment_kwargs(params):
+    """The on-device input augmentation keys of a recipe (all optional; absent, null or 0: off) as the keywords of CTC /
+    MultitaskCTC / AttentionSeq2Seq / JointCTCAttention."""
+    kw = dict(input_noise_std=float(params.get('input_noise_std') or 0.0),
+              freq_mask_num=int(params.get('freq_mask_num') or 0), freq_mask_width=int(params.get('freq_mask_width') or 0),
+              time_mask_num=int(params.get('time_mask_num') or 0), time_mask_width=int(params.get('time_mask_width') or 0))
+    if params.get('time_mask_ratio') is not None:
+        kw['time_mask_ratio'] = float(params['time_mask_ratio'])
+    if params.get('input_channels'):
+        kw['input_channels'] = int(params['input_channels'])
+    return kw
+
+
+def input_augment_tag(params):
+    """Run-name tag of those keys, empty unless one is set: `_in<std>` for the noise, `_sa<nf>x<F>_<nt>x<T>` for the masks
+    (`_r<ratio>` behind it when time_mask_ratio is below 1)."""
+    kw = input_augment_kwargs(params)
+    tag = ''
+    if kw['input_noise_std'] > 0:
+        tag += '_in' + str(params['input_noise_std'])
+    fm = kw['freq_mask_num'] > 0 and kw['freq_mask_width'] > 0
+    tm = kw['time_mask_num'] > 0 and kw['time_mask_width'] > 0
+    if fm or tm:
+        f = (kw['freq_mask_num'], kw['freq_mask_width']) if fm else (0, 0)
+        t = (kw['time_mask_num'], kw['time_mask_width']) if tm else (0, 0)
+        tag += '_sa%dx%d_%dx%d' % (f + t)
+        if tm and kw.get('time_mask_ratio', 1.0) < 1.0:
+            tag += '_r' + str(params['time_mask_ratio'])
+    return tag
+
+
 def new_run_directory(base, config_path):
     """Never reuse a directory that holds a finished (complete.txt) or started (config.yml) run."""
     path, index = base, 0

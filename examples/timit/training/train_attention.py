@@ -20,6 +20,7 @@ from examples.timit.data.load_dataset_attention import Dataset                  
 from examples.timit.metrics.attention import do_eval_per, do_eval_cer                                       # noqa: E402
 from examples.timit.metrics.mapping_files import write_mapping_files                                        # noqa: E402
 from examples.timit.training._common import NUM_CLASSES, new_run_directory, run_with_log, training_loop      # noqa: E402
+from examples.timit.training._common import input_augment_kwargs, input_augment_tag                          # noqa: E402
 from tensorflow_end2end_speech_recognition_amd.models.attention.attention_seq2seq import AttentionSeq2Seq   # noqa: E402
 
 
@@ -59,7 +60,7 @@ def model_kwargs(params):
         label_smoothing_prob=float(params.get('label_smoothing_prob') or 0.0),
         encoder_residual=bool(params.get('encoder_residual', False)),
         encoder_dense_residual=bool(params.get('encoder_dense_residual', False)),
-        weight_noise_std=float(params.get('weight_noise_std') or 0.0))
+        weight_noise_std=float(params.get('weight_noise_std') or 0.0), **input_augment_kwargs(params))
 
 
 def scheduled_sampling_prob(params, step):
@@ -104,6 +105,7 @@ def run_name(params):
         name += '_ls' + str(params['label_smoothing_prob'])
     if params.get('weight_noise_std') and float(params['weight_noise_std']) > 0:
         name += '_wn' + str(params['weight_noise_std'])
+    name += input_augment_tag(params)
     return name
 
 

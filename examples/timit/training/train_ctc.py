@@ -28,6 +28,7 @@ if ROOT not in sys.path:
 from examples.timit.data.load_dataset_ctc import Dataset                                                    # noqa: E402
 from examples.timit.metrics.ctc import do_eval_per, do_eval_cer                                            # noqa: E402
 from examples.timit.metrics.mapping_files import write_mapping_files                                       # noqa: E402
+from examples.timit.training._common import input_augment_kwargs, input_augment_tag                        # noqa: E402
 from tensorflow_end2end_speech_recognition_amd.models.ctc.ctc import CTC                                    # noqa: E402
 from tensorflow_end2end_speech_recognition_amd.utils.io.labels.sparsetensor import list2sparsetensor        # noqa: E402
 from tensorflow_end2end_speech_recognition_amd.utils.parameter import count_total_parameters                # noqa: E402
@@ -171,7 +172,7 @@ def build_model(params):
                 encoder_residual=bool(params.get('encoder_residual', False)),
                 encoder_dense_residual=bool(params.get('encoder_dense_residual', False)),
                 label_smoothing_prob=float(params.get('label_smoothing_prob') or 0.0),
-                weight_noise_std=float(params.get('weight_noise_std') or 0.0))
+                weight_noise_std=float(params.get('weight_noise_std') or 0.0), **input_augment_kwargs(params))
     # run-directory name, as :338-351
     model.name += '_' + str(params['num_units'])
     model.name += '_' + str(params['num_layers'])
@@ -195,6 +196,7 @@ def build_model(params):
         model.name += '_ls' + str(params['label_smoothing_prob'])
     if params.get('weight_noise_std') and float(params['weight_noise_std']) > 0:
         model.name += '_wn' + str(params['weight_noise_std'])
+    model.name += input_augment_tag(params)
     return model
 
 

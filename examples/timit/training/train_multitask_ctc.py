@@ -16,6 +16,7 @@ from examples.timit.data.load_dataset_multitask_ctc import Dataset              
 from examples.timit.metrics.ctc import do_eval_per, do_eval_cer                                              # noqa: E402
 from examples.timit.metrics.mapping_files import write_mapping_files                                         # noqa: E402
 from examples.timit.training._common import NUM_CLASSES, new_run_directory, run_with_log, training_loop       # noqa: E402
+from examples.timit.training._common import input_augment_kwargs, input_augment_tag                           # noqa: E402
 from tensorflow_end2end_speech_recognition_amd.models.ctc.multitask_ctc import MultitaskCTC                  # noqa: E402
 from tensorflow_end2end_speech_recognition_amd.utils.io.labels.sparsetensor import list2sparsetensor         # noqa: E402
 
@@ -79,6 +80,7 @@ def run_name_suffix(params):
         name += '_ls' + str(params['label_smoothing_prob'])
     if params.get('weight_noise_std') and float(params['weight_noise_std']) > 0:
         name += '_wn' + str(params['weight_noise_std'])
+    name += input_augment_tag(params)
     return name
 
 
@@ -97,7 +99,7 @@ def main(config_path, model_save_path, log_to_file=True):
                          weight_decay=params['weight_decay'], dtype=params.get('dtype', 'bf16'),
                          device=params.get('device', 'cuda:0'),
                          label_smoothing_prob=float(params.get('label_smoothing_prob') or 0.0),
-                         weight_noise_std=float(params.get('weight_noise_std') or 0.0))
+                         weight_noise_std=float(params.get('weight_noise_std') or 0.0), **input_augment_kwargs(params))
     model.name += run_name_suffix(params)
     model.save_path = new_run_directory(
         join(model_save_path, 'ctc', params['label_type_main'] + '_' + params['label_type_sub'], model.name),

@@ -150,6 +150,35 @@ int asr_weight_noise_perturb(asr_handle* h, float* w, float* backup, size_t n, f
                              uint64_t offset, asr_stream s);
 int asr_weight_noise_counts(asr_handle* h, unsigned long long* out3);
 int asr_reset_weight_noise_counts(asr_handle* h);
+/* EXTENSION (later within ABI 5; the reference declares _add_noise_to_inputs(inputs, stddev=0.075) at
+ * models/model_base.py:40-55 with its body commented out; frequency / time masking: Park et al. 2019): input augmentation
+ * of one training step in one pass over the batch-major features, x, y [B,T,F] fp32 contiguous, y must not overlap x (x is
+ * never written), seq_len [B] int32 on the device, len_b = clamp(seq_len[b], 0, T).  For element i = (b T + t) F + f:
+ *   1. t >= len_b (padded frame): y[i] gets the bits of x[i] -- no noise, no mask, a NaN is copied as it is.
+ *   2. v = x[i]; with noise_std > 0: v = fl32(x[i] + fl32(noise_std * z_i)), z_i = word (i & 3) of the standard normal
+ *      values of block offset + (i >> 2) under key = seed (the generator of asr_weight_noise_perturb, above); at
+ *      noise_std == 0 nothing is added (-0.0 stays -0.0).
+ *   3. masks: slot = one Philox4x32-10 block c = block(offset + 2^39 + 16 b + slot) under key = seed; frequency masks
+ *      take slots 0 .. n_fmask-1, time masks slots 8 .. 8+n_tmask-1; mulhi(u, n) = (uint64(u) n) >> 32.
+ *      frequency: Fcap = min(fmask_width, n_ch), fw = mulhi(c0, Fcap + 1), fs = mulhi(c1, n_ch - fw + 1); covers
+ *        fs <= (f mod n_ch) < fs + fw -- the same band in every group of n_ch columns (static / delta / double-delta,
+ *        stacked and spliced copies: columns are copies x 3 groups x n_ch);
+ *      time: Tcap = min(tmask_width, (int)floorf(tmask_ratio * (float)len_b)) in fp32, tw = mulhi(c0, Tcap + 1),
+ *        ts = mulhi(c1, len_b - tw + 1); covers ts <= t < ts + tw.
+ *      A covered element becomes mask_value exactly, every other y[i] = v.
+ * Counters used: noise offset + [0, 2^39), mask slots offset + 2^39 + [0, 16 B): calls at offset = k << 40 do not collide.
+ * ASR_ERR_INVALID_ARG unless 1 <= n_ch <= F and F % n_ch == 0, 0 <= n_fmask, n_tmask <= 8, both widths >= 0,
+ * 0 <= tmask_ratio <= 1, noise_std finite and >= 0, mask_value finite, B T F < 2^41.  One launch; 16-byte accesses for a
+ * group of four flat elements where both pointers are 16-byte aligned and the group lies inside one utterance's valid (or
+ * padded) frames, element by element otherwise; noise and masks all off: a device-to-device copy.
+ * asr_input_augment_counts: {calls, elements, calls on the 16-byte path} since the last reset.
+ * Call site: ModelBase._augment_inputs (a TRAINING compute_loss of CTC / MultitaskCTC / AttentionSeq2Seq /
+ * JointCTCAttention, behind the upload of the inputs and lengths and in front of _build). */
+int asr_input_augment(asr_handle* h, const float* x, float* y, const int32_t* seq_len, int B, int T, int F, int n_ch,
+                      float noise_std, int n_fmask, int fmask_width, int n_tmask, int tmask_width, float tmask_ratio,
+                      float mask_value, uint64_t seed, uint64_t offset, asr_stream s);
+int asr_input_augment_counts(asr_handle* h, unsigned long long* out3);
+int asr_reset_input_augment_counts(asr_handle* h);
 /* out[c*ld_out + r] = in[r*ld_in + c] for an [rows, cols] matrix in `dtype` (LDS-tiled, both
  * sides coalesced).  The MFMA GEMM wants both operands reduction-contiguous; the k-major ones
  * (W_x as stored by TF: [Din, 4H], models/encoders/core/blstm.py:286-320 via LSTMBlockCell's

@@ -247,6 +247,9 @@ SIGNATURES = {
     'asr_weight_noise_perturb': (_i, [_vp, _vp, _vp, _sz, _f, _u64, _u64, _vp]),
     'asr_weight_noise_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
     'asr_reset_weight_noise_counts': (_i, [_vp]),
+    'asr_input_augment': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _i, _i, _f, _f, _u64, _u64, _vp]),
+    'asr_input_augment_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
+    'asr_reset_input_augment_counts': (_i, [_vp]),
     'asr_weight_decay': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp]),
     'asr_optimizer_step': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _f, _i64, _vp]),
     'asr_scale': (_i, [_vp, _vp, _sz, _f, _vp]),

@@ -26,9 +26,10 @@ FLAGS = ['--offload-arch=%s' % ARCH, '-O3', '-std=c++17', '-fPIC', '-Wno-unused-
 # the family was tuned under it, so a new unit of the family takes it too
 # residual.hip: m * h + skip and dx + carry are held bit for bit to a numpy statement that rounds after the multiply
 # weight_noise.hip: w + std * z likewise (a slice of the buffer must get the bits of the whole-buffer call on every path)
+# input_augment.hip: x + std * z likewise (the 16-byte and the element path must give the same bits)
 CLUSTER_UNITS = ('lstm_cluster.hip', 'lstm_cluster_f32.hip', 'gru_cluster.hip')
 FILE_FLAGS = {'ctc.hip': ['-fno-slp-vectorize'], 'residual.hip': ['-ffp-contract=off'],
-              'weight_noise.hip': ['-ffp-contract=off']}
+              'weight_noise.hip': ['-ffp-contract=off'], 'input_augment.hip': ['-ffp-contract=off']}
 FILE_FLAGS.update({u: ['-mllvm', '-amdgpu-mfma-vgpr-form'] for u in CLUSTER_UNITS})
 # ASR_BUILD_ABLATE=1: the ablated instantiations of the headline recurrence kernels (scripts/probe_lstm_ablate.py), all of
 # them bf16 kernels of lstm_cluster.hip; never part of a shipped library -- the default kernels' ISA is identical with and

@@ -60,6 +60,8 @@ struct asr_handle {
   unsigned long long att_stack_counts[4];
   // asr_weight_noise_perturb since the last asr_reset_weight_noise_counts: {calls, elements, calls on the 16-byte path}
   unsigned long long weight_noise_counts[3];
+  // asr_input_augment since the last asr_reset_input_augment_counts: {calls, elements, calls on the 16-byte path}
+  unsigned long long input_augment_counts[3];
 };
 
 #define ASR_FAIL(h, code, ...)                                  \

@@ -82,8 +82,16 @@ class AttentionSeq2Seq(ModelBase):
                  weight_decay=0.0, time_major=True, sharpening_factor=1.0, logits_temperature=1.0,
                  sigmoid_smoothing=False, name='attention', dtype='f32', device='cuda:0', seed=0,
                  _extra_vars=None, prev_alpha='zeros', subsample_list=None, subsample_type='drop',
-                 label_smoothing_prob=0.0, encoder_residual=False, encoder_dense_residual=False, weight_noise_std=0.0):
+                 label_smoothing_prob=0.0, encoder_residual=False, encoder_dense_residual=False, weight_noise_std=0.0,
+                 input_noise_std=0.0, freq_mask_num=0, freq_mask_width=0, time_mask_num=0, time_mask_width=0,
+                 time_mask_ratio=1.0, input_channels=None):
         super(AttentionSeq2Seq, self).__init__()
+        # input_noise_std, freq_mask_*, time_mask_*, input_channels (extension keywords): Gaussian noise on the input
+        # features and frequency / time masks (Park et al. 2019) for each training compute_loss, drawn on the device
+        # (ModelBase._augment_inputs has the rules); dev passes, infer and decode see the clean inputs; the lazy
+        # decoder_outputs_infer of a training forward decodes the augmented ones; all defaults: today's model
+        self._set_input_augment(input_size, input_noise_std, freq_mask_num, freq_mask_width, time_mask_num, time_mask_width,
+                                time_mask_ratio, input_channels)
         # weight_noise_std (extension keyword; a key of the reference's att_blstm_location_weight_noise.yml and
         # att_baseline.yml that none of its code reads): Gaussian noise on every trainable variable for the forward and
         # backward pass of each training step, the update on the clean weights (ModelBase._noise_begin has the rules);
@@ -419,6 +427,8 @@ class AttentionSeq2Seq(ModelBase):
         self.encoder._lens_host = ops.host_ints(inputs_seq_len)
         inputs = ops.to_device(inputs, torch.float32, dev)
         isl = ops.to_device(inputs_seq_len, torch.int32, dev)
+        if is_training:
+            inputs = self._augment_inputs(inputs, isl)
         labels_np = (ops.host_ints(labels) if torch.is_tensor(labels) else np.asarray(labels)).astype(np.int64)
         lsl_np = (ops.host_ints(labels_seq_len) if torch.is_tensor(labels_seq_len) else np.asarray(labels_seq_len)).astype(np.int64)
         B = inputs.shape[0]

@@ -14,7 +14,8 @@ the literal; `honour_ctor_args=True` (extension keyword) uses the caller's value
 `ctc_label_smoothing_prob` (extension keyword): label smoothing of the CTC head as CTC(label_smoothing_prob=...) applies it
 (ops.ctc_loss_ls, training steps only; lambda scales the whole smoothed term); `label_smoothing_prob` keeps meaning the
 attention targets only.  `weight_noise_std` (extension keyword of AttentionSeq2Seq) passes through: the noise covers the
-CTC head's variables too, they live in the same flat buffer.
+CTC head's variables too, they live in the same flat buffer.  The input augmentation keywords (`input_noise_std`,
+`freq_mask_*`, `time_mask_*`, `input_channels`) pass through as well: both heads read the one augmented encoder input.
 """
 import warnings
 

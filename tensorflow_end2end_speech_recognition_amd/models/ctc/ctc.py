@@ -79,7 +79,12 @@ class CTC(ModelBase):
     (is_training=False) and self.ctc_losses stay the plain CTC loss; 0: today's calls); `weight_noise_std` (sigma >= 0:
     Gaussian noise on every trainable variable for the forward and backward pass of each training step, the update on
     the clean weights -- ModelBase._noise_begin has the rules; a key of the reference's blstm_ctc_weight_noise.yml that
-    none of its code reads; dev passes never see noise; 0: today's model, call for call).
+    none of its code reads; dev passes never see noise; 0: today's model, call for call); `input_noise_std`,
+    `freq_mask_num` / `freq_mask_width`, `time_mask_num` / `time_mask_width` / `time_mask_ratio`, `input_channels`
+    (Gaussian noise on the input features and frequency / time masks, Park et al. 2019, drawn on the device for every
+    training compute_loss -- ModelBase._augment_inputs has the rules; `input_channels` is the number of base channels a
+    frequency band repeats over, default input_size // 3; dev passes, infer and decode see the clean inputs; all
+    defaults: today's model, call for call).
     """
     head_scope = 'output'      # variable scope of the output FC (ctc.py:216-224)
 
@@ -88,9 +93,12 @@ class CTC(ModelBase):
                  parameter_init=0.1, clip_grad_norm=None, clip_activation=None, num_proj=None,
                  weight_decay=0.0, bottleneck_dim=None, time_major=True,
                  dtype='f32', device='cuda:0', seed=0, subsample_list=None, subsample_type='drop',
-                 encoder_residual=False, encoder_dense_residual=False, label_smoothing_prob=0.0, weight_noise_std=0.0):
+                 encoder_residual=False, encoder_dense_residual=False, label_smoothing_prob=0.0, weight_noise_std=0.0, input_noise_std=0.0, freq_mask_num=0,
+                 freq_mask_width=0, time_mask_num=0, time_mask_width=0, time_mask_ratio=1.0, input_channels=None):
         super(CTC, self).__init__()
         self._set_weight_noise(weight_noise_std)
+        self._set_input_augment(input_size, input_noise_std, freq_mask_num, freq_mask_width,
+                                time_mask_num, time_mask_width, time_mask_ratio, input_channels)
         if not 0.0 <= float(label_smoothing_prob) < 1.0:
             raise ValueError('label_smoothing_prob must be in [0, 1), got %r' % (label_smoothing_prob,))
         self.label_smoothing_prob = float(label_smoothing_prob)
@@ -345,6 +353,8 @@ class CTC(ModelBase):
         # output FC and the CTC kernels
         inputs_seq_len, off_d, flat_d = ops.upload_ints(
             dev, [inputs_seq_len, offsets, flat if len(flat) else np.zeros(1, np.int32)])
+        if is_training:
+            inputs = self._augment_inputs(inputs, inputs_seq_len)
         head = dict(flat=flat_d, off=off_d, max_len=max_len) if (is_training and softmax_temperature == 1) else None
         logits = self._build(inputs, inputs_seq_len, keep_prob, is_training, head=head)
         T, Bp, C = logits.shape

@@ -94,6 +94,8 @@ class MultitaskCTC(CTC):
         self.encoder._lens_host = ops.host_ints(inputs_seq_len)
         inputs = ops.to_device(inputs, torch.float32, dev)
         inputs_seq_len = ops.to_device(inputs_seq_len, torch.int32, dev)
+        if is_training:
+            inputs = self._augment_inputs(inputs, inputs_seq_len)   # input_noise_std / *_mask_* (extension keywords, CTC's)
         B = inputs.shape[0]
         logits_main, logits_sub = self._build(inputs, inputs_seq_len, keep_prob, is_training)
         Bp = logits_main.shape[1]

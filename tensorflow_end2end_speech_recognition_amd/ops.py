@@ -3527,6 +3527,50 @@ def reset_weight_noise_counts(device=0):
     _reset_counts3('weight_noise_counts', device)
 
 
+def input_augment(x, seq_len, n_ch, noise_std=0.0, freq_masks=(0, 0), time_masks=(0, 0, 1.0), mask_value=0.0, seed=0,
+                  offset=0, out=None):
+    """EXTENSION: input augmentation of one training step (asr_input_augment), one pass, x untouched: y = x with Gaussian
+    noise of `noise_std` on every valid element, `freq_masks = (number, max width)` bands of the `n_ch` base channels
+    (the same band in every group of n_ch columns) and `time_masks = (number, max width, max share of the utterance)`
+    runs of frames per utterance set to `mask_value`; padded frames (t >= seq_len[b]) keep x's bits.  x [B,T,F] fp32
+    contiguous, seq_len [B] int32 on the device; noise blocks offset + i / 4 and mask slots offset + 2^39 + 16 b + slot
+    under key `seed` (the statement: include/asr_hip.h).  `out`: a [B,T,F] fp32 tensor that does not overlap x (default:
+    a fresh one).  Everything off: a device copy.  Returns y."""
+    _chk(x, torch.float32, 'x')
+    if x.dim() != 3:
+        raise ValueError('input_augment: x must be [B,T,F], got %s' % (tuple(x.shape),))
+    B, T, F = x.shape
+    h = _h(x)
+    seq_len = to_device(seq_len, torch.int32, x.device)
+    if seq_len.numel() != B:
+        raise ValueError('input_augment: seq_len has %d entries for a batch of %d' % (seq_len.numel(), B))
+    if out is None:
+        out = torch.empty_like(x, memory_format=torch.contiguous_format)
+    _chk(out, torch.float32, 'out')
+    if tuple(out.shape) != tuple(x.shape):
+        raise ValueError('input_augment: out is %s, x %s' % (tuple(out.shape), tuple(x.shape)))
+    nf, fw = freq_masks
+    nt, tw, tr = time_masks
+    h.check(h.lib.asr_input_augment(h.h, _p(x), _p(out), _p(seq_len), B, T, F, int(n_ch), float(noise_std), int(nf),
+                                    int(fw), int(nt), int(tw), float(tr), float(mask_value),
+                                    int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, _s()),
+            'asr_input_augment')
+    return out
+
+
+_INPUT_AUGMENT_KEYS = ('calls', 'elements', 'vec_calls')
+
+
+def input_augment_counts(device=0):
+    """input_augment calls on `device` since the last reset (asr_input_augment_counts): calls, elements, calls that ran
+    the 16-byte kernel.  Host counters: no device work, no synchronisation."""
+    return _counts3('input_augment_counts', _INPUT_AUGMENT_KEYS, device)
+
+
+def reset_input_augment_counts(device=0):
+    _reset_counts3('input_augment_counts', device)
+
+
 def optimizer_step(opt_id, params, grads, slot0, slot1, lr, step):
     h = _h(params)
     h.check(h.lib.asr_optimizer_step(h.h, int(opt_id), _p(params), _p(grads), _p(slot0), _p(slot1),
