@@ -6,6 +6,8 @@ module raises.  torch is used only to own device memory / streams.
 import ctypes as C
 import os
 
+from . import _counters
+
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, 'libasr_hip.so')
 
@@ -108,18 +110,6 @@ SIGNATURES = {
     'asr_debug_set_lstm_flags': (_i, [_i]),
     'asr_debug_set_gru_persistent': (_i, [_i]),
     'asr_cluster_tile_groups': (_i, [_i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _i]),
-    'asr_recurrence_path_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
-    'asr_reset_recurrence_path_counts': (_i, [_vp]),
-    'asr_gru_kernel_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
-    'asr_reset_gru_kernel_counts': (_i, [_vp]),
-    'asr_lstm_kernel_counts': (_i, [_vp, C.POINTER(C.c_ulonglong), _i]),
-    'asr_reset_lstm_kernel_counts': (_i, [_vp]),
-    'asr_att_path_counts': (_i, [_vp, C.POINTER(C.c_ulonglong), _i]),
-    'asr_reset_att_path_counts': (_i, [_vp]),
-    'asr_conv_path_counts': (_i, [_vp, C.POINTER(C.c_ulonglong), _i]),
-    'asr_reset_conv_path_counts': (_i, [_vp]),
-    'asr_gemm_path_counts': (_i, [_vp, C.POINTER(C.c_ulonglong), _i]),
-    'asr_reset_gemm_path_counts': (_i, [_vp]),
     'asr_gemm_tn_frames': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _i, _vp]),
     'asr_debug_set_cluster_cu_budget': (_i, [_i]),
     'asr_debug_placement': (_i, [_vp, _vp, _i, _i, _vp]),
@@ -131,15 +121,11 @@ SIGNATURES = {
     'asr_ctc_ls_workspace_bytes': (_sz, [_i, _i, _i]),
     'asr_ctc_loss_ls': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _sz, _i, _vp, _i,
                              _vp]),
-    'asr_ctc_ls_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
-    'asr_reset_ctc_ls_counts': (_i, [_vp]),
     'asr_ctc_head_ok': (_i, [_i, _i, _i]),
     'asr_ctc_head_prep': (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     'asr_ctc_head_fwd': (_i, [_vp, _vp, _i, _i, _i, _f, _u64, _u64, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp,
                               _sz, _vp]),
     'asr_ctc_head_bwd': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _f, _u64, _u64, _vp, _i, _vp]),
-    'asr_ctc_head_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
-    'asr_reset_ctc_head_counts': (_i, [_vp]),
     'asr_ctc_greedy_decode': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     'asr_ctc_beam_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'asr_ctc_beam_decode': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -174,8 +160,6 @@ SIGNATURES = {
     'asr_att_beam_reorder': (_i, [_vp, _vp, _vp] + [_i] * 7 + [_vp] * 9 + [_vp]),
     'asr_att_beam_backtrace': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     'asr_att_decoder_beam': (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
-    'asr_att_beam_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
-    'asr_reset_att_beam_counts': (_i, [_vp]),
     # joint CTC / attention beam search (later within ABI 5)
     'asr_log_softmax_rows': (_i, [_vp, _vp, _vp, _sz, _i, _vp]),
     'asr_ctc_prefix_init': (_i, [_vp, _vp, _vp] + [_i] * 6 + [_vp] * 3 + [_vp]),
@@ -183,23 +167,17 @@ SIGNATURES = {
     'asr_ctc_prefix_advance': (_i, [_vp, _vp, _vp] + [_i] * 7 + [_vp] * 5 + [_vp]),
     'asr_att_beam_select_joint': (_i, [_vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _vp, _i, _i, _i, _i] + [_vp] * 18 + [_vp]),
     'asr_att_decoder_beam_joint': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'asr_att_joint_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
-    'asr_reset_att_joint_counts': (_i, [_vp]),
     # shallow fusion with an RNN language model in the beam search (later within ABI 5)
     'asr_lm_prep': (_i, [_vp, _vp, _vp]),
     'asr_lm_step': (_i, [_vp, _vp, _vp]),
     'asr_att_beam_select_fused': (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _i, _vp, _vp, _i, _i, _i, _i] + [_vp] * 21 + [_vp]),
     'asr_lm_beam_reorder': (_i, [_vp, _vp, _vp] + [_i] * 6 + [_vp] * 6 + [_vp]),
     'asr_att_decoder_beam_lm': (_i, [_vp] * 8),
-    'asr_att_lm_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
-    'asr_reset_att_lm_counts': (_i, [_vp]),
     # CTC prefix beam search with LM fusion (later within ABI 5)
     'asr_ctc_beam_lm_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
     'asr_ctc_beam_lm_frame': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, C.c_double, C.c_double, _vp, _i] + [_vp] * 7 +
                               [_sz, _vp]),
     'asr_ctc_beam_decode_lm': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _i, C.c_double, C.c_double, _vp] + [_vp] * 5 + [_sz, _vp]),
-    'asr_ctc_beam_lm_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
-    'asr_reset_ctc_beam_lm_counts': (_i, [_vp]),
     # time subsampling between recurrent layers (later within ABI 5)
     'asr_time_subsample_fwd': (_i, [_vp, _i, _i, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     'asr_time_subsample_bwd': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
@@ -221,8 +199,6 @@ SIGNATURES = {
     'asr_att_decoder_bwd_gru': (_i, [_vp] * 4),
     'asr_att_decoder_infer_gru': (_i, [_vp] * 6),
     'asr_att_decoder_beam_gru': (_i, [_vp] * 7),
-    'asr_att_gru_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
-    'asr_reset_att_gru_counts': (_i, [_vp]),
     # multi-layer LSTM decoder (later within ABI 5)
     'asr_att_decoder_fwd_stack': (_i, [_vp] * 4),
     'asr_att_decoder_bwd_stack': (_i, [_vp] * 4),
@@ -232,8 +208,6 @@ SIGNATURES = {
     'asr_att_stack_bwd_ok': (_i, [_i, _i]),
     'asr_att_stack_bwd_step': (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _vp, _i, _vp]),
-    'asr_att_stack_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
-    'asr_reset_att_stack_counts': (_i, [_vp]),
     'asr_seq_xent_ls': (_i, [_vp, _vp, _vp, _vp, _i, _i, _f, _f, _f, _vp, _vp, _vp]),
     'asr_add_cols': (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp]),
     'asr_tanh_fwd': (_i, [_vp, _vp, _vp, _sz, _vp]),
@@ -245,11 +219,7 @@ SIGNATURES = {
     'asr_clip_plan': (_i, [_vp, _vp, _i, _vp]),
     'asr_clip_by_norm_multi': (_i, [_vp, _vp, _vp, _vp, _i, _i64, _f, _vp, _vp]),
     'asr_weight_noise_perturb': (_i, [_vp, _vp, _vp, _sz, _f, _u64, _u64, _vp]),
-    'asr_weight_noise_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
-    'asr_reset_weight_noise_counts': (_i, [_vp]),
     'asr_input_augment': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _i, _i, _f, _f, _u64, _u64, _vp]),
-    'asr_input_augment_counts': (_i, [_vp, C.POINTER(C.c_ulonglong)]),
-    'asr_reset_input_augment_counts': (_i, [_vp]),
     'asr_weight_decay': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp]),
     'asr_optimizer_step': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _f, _i64, _vp]),
     'asr_scale': (_i, [_vp, _vp, _sz, _f, _vp]),
@@ -260,6 +230,10 @@ SIGNATURES = {
     'asr_comm_info': (_i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     'asr_allreduce_mean': (_i, [_vp, _vp, _sz, _vp]),
 }
+# the launch counters: asr_<family>(h, out[, n]) and asr_reset_<family>(h) of every row of _counters.FAMILIES
+for _fam in _counters.FAMILIES.values():
+    SIGNATURES[_fam.getter] = (_i, [_vp, C.POINTER(C.c_ulonglong)] + ([_i] if _fam.sized else []))
+    SIGNATURES[_fam.reset] = (_i, [_vp])
 
 _lib = None
 

@@ -456,7 +456,7 @@ extern "C" int asr_att_beam_backtrace(asr_handle* h, const int32_t* word, const 
   return ASR_OK;
 }
 
-ASR_DEFINE_COUNTS3(att_beam_counts)
+ASR_DEFINE_COUNTS(att_beam_counts, att_beam_counts)
 
 // What asr_att_beam_select_joint (ctc, !lm) and asr_att_beam_select_fused (lm, ctc iff ctc_weight > 0) do once their
 // arguments are checked: candidates, the prefix scorer on them with CTC, rank.  `who`: the entry point's launch labels.

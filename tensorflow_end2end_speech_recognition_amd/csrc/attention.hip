@@ -2215,13 +2215,4 @@ bool att_fused_step(asr_handle* h, const asr_att_decoder* a, const float* qz, fl
   return true;
 }
 
-extern "C" int asr_att_path_counts(asr_handle* h, unsigned long long* out, int n) {
-  if (!h || !out || n < 0) return ASR_ERR_INVALID_ARG;
-  for (int i = 0; i < n; ++i) out[i] = i < ASR_ATT_PATH_N ? h->att_counts[i] : 0ull;
-  return ASR_OK;
-}
-extern "C" int asr_reset_att_path_counts(asr_handle* h) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  for (int i = 0; i < ASR_ATT_PATH_N; ++i) h->att_counts[i] = 0;
-  return ASR_OK;
-}
+ASR_DEFINE_COUNTS_N(att_path_counts, att_counts)

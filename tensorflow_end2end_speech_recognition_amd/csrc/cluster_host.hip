@@ -110,28 +110,10 @@ void count_cluster_launches(asr_handle* h, int kind, int groups) {
   h->rec_counts[3 * kind + 0] += (unsigned long long)groups;
   if (groups > 1) h->rec_counts[3 * kind + 2] += 1;
 }
-extern "C" int asr_recurrence_path_counts(asr_handle* h, unsigned long long* out6) {
-  if (!h || !out6) return ASR_ERR_INVALID_ARG;
-  for (int i = 0; i < 6; ++i) out6[i] = h->rec_counts[i];
-  return ASR_OK;
-}
-extern "C" int asr_reset_recurrence_path_counts(asr_handle* h) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  for (int i = 0; i < 6; ++i) h->rec_counts[i] = 0;
-  return ASR_OK;
-}
+ASR_DEFINE_COUNTS(recurrence_path_counts, rec_counts)
 // the form each asr_lstm_fwd / asr_lstm_bwd(_ex) call on this handle ended in (host integers bumped where the form is
 // chosen: the cluster launchers of lstm_cluster.hip and lstm_cluster_f32.hip, asr_lstm_fwd / lstm_bwd_impl for the single-CU kernels)
-extern "C" int asr_lstm_kernel_counts(asr_handle* h, unsigned long long* out, int n) {
-  if (!h || !out || n < 0) return ASR_ERR_INVALID_ARG;
-  for (int i = 0; i < n; ++i) out[i] = i < ASR_LSTM_KERNEL_N ? h->lstm_counts[i] : 0ull;
-  return ASR_OK;
-}
-extern "C" int asr_reset_lstm_kernel_counts(asr_handle* h) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  for (int i = 0; i < ASR_LSTM_KERNEL_N; ++i) h->lstm_counts[i] = 0;
-  return ASR_OK;
-}
+ASR_DEFINE_COUNTS_N(lstm_kernel_counts, lstm_counts)
 
 // Units per CU of the H = 256 / 512 clusters: 32 (default since round 3: H/32 CUs with four waves each, one per SIMD) or
 // 64 (H/64 CUs with eight waves; ASR_LSTM_HS=64, ASR_LSTM_FWD_HS / ASR_LSTM_BWD_HS for one pass only, or

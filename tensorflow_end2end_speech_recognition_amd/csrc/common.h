@@ -80,18 +80,32 @@ struct asr_handle {
 #define ASR_NEED(cond, ...) do { if (!(cond)) ASR_FAIL(h, ASR_ERR_INVALID_ARG, __VA_ARGS__); } while (0)
 #define ASR_TRY(call) do { const int rc_ = (call); if (rc_ != ASR_OK) return rc_; } while (0)
 
-// getter and reset of one of the handle's three-word launch counters: asr_<field>(h, out3), asr_reset_<field>(h)
-#define ASR_DEFINE_COUNTS3(field)                                              \
-  extern "C" int asr_##field(asr_handle* h, unsigned long long* out3) {        \
-    if (!h || !out3) return ASR_ERR_INVALID_ARG;                               \
-    for (int i = 0; i < 3; ++i) out3[i] = h->field[i];                         \
-    return ASR_OK;                                                             \
-  }                                                                            \
-  extern "C" int asr_reset_##field(asr_handle* h) {                            \
+// getter and reset of one of the handle's launch-counter arrays, by export name and handle field; one line in the file that
+// bumps the field.  The field's own size is the word count.
+#define ASR_COUNTS_WORDS_(field) ((int)(sizeof(h->field) / sizeof(h->field[0])))
+#define ASR_DEFINE_COUNTS_RESET_(name, field)                                  \
+  extern "C" int asr_reset_##name(asr_handle* h) {                             \
     if (!h) return ASR_ERR_INVALID_ARG;                                        \
-    for (int i = 0; i < 3; ++i) h->field[i] = 0;                               \
+    for (int i = 0; i < ASR_COUNTS_WORDS_(field); ++i) h->field[i] = 0;        \
     return ASR_OK;                                                             \
   }
+// fixed form: asr_<name>(h, out) writes every word of the field (3, 4 or 6; the header names the parameter out<N>)
+#define ASR_DEFINE_COUNTS(name, field)                                         \
+  extern "C" int asr_##name(asr_handle* h, unsigned long long* out) {          \
+    if (!h || !out) return ASR_ERR_INVALID_ARG;                                \
+    for (int i = 0; i < ASR_COUNTS_WORDS_(field); ++i) out[i] = h->field[i];   \
+    return ASR_OK;                                                             \
+  }                                                                            \
+  ASR_DEFINE_COUNTS_RESET_(name, field)
+// sized form (fields indexed by an enum of asr_hip.h that may grow): asr_<name>(h, out, n) writes n words, zeros past the
+// field's end, fewer than the field has when n is smaller; n < 0 is ASR_ERR_INVALID_ARG
+#define ASR_DEFINE_COUNTS_N(name, field)                                                       \
+  extern "C" int asr_##name(asr_handle* h, unsigned long long* out, int n) {                   \
+    if (!h || !out || n < 0) return ASR_ERR_INVALID_ARG;                                       \
+    for (int i = 0; i < n; ++i) out[i] = i < ASR_COUNTS_WORDS_(field) ? h->field[i] : 0ull;    \
+    return ASR_OK;                                                                             \
+  }                                                                                            \
+  ASR_DEFINE_COUNTS_RESET_(name, field)
 
 typedef uint16_t bf16_t;  // raw bf16 bits
 

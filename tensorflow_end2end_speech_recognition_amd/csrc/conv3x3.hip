@@ -942,13 +942,4 @@ extern "C" int asr_conv3x3_bwd_weight_bias(asr_handle* h, const void* x, const v
   return conv3x3_bwd_weight_impl(h, x, dy, Nimg, H, W, Cin, Cout, dw, dbias, 0, s);
 }
 
-extern "C" int asr_conv_path_counts(asr_handle* h, unsigned long long* out, int n) {
-  if (!h || !out || n < 0) return ASR_ERR_INVALID_ARG;
-  for (int i = 0; i < n; ++i) out[i] = i < ASR_CONVP_N ? h->conv_counts[i] : 0ull;
-  return ASR_OK;
-}
-extern "C" int asr_reset_conv_path_counts(asr_handle* h) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  for (int i = 0; i < ASR_CONVP_N; ++i) h->conv_counts[i] = 0;
-  return ASR_OK;
-}
+ASR_DEFINE_COUNTS_N(conv_path_counts, conv_counts)

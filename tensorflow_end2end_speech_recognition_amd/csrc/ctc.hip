@@ -928,8 +928,8 @@ extern "C" int asr_ctc_head_fwd(asr_handle* h, const void* hout, int T, int B, i
   return ASR_OK;
 }
 
-ASR_DEFINE_COUNTS3(ctc_head_counts)
-ASR_DEFINE_COUNTS3(ctc_ls_counts)
+ASR_DEFINE_COUNTS(ctc_head_counts, ctc_head_counts)
+ASR_DEFINE_COUNTS(ctc_ls_counts, ctc_ls_counts)
 
 extern "C" int asr_ctc_greedy_decode(asr_handle* h, const float* logits, int T, int B, int C,
                                      const int32_t* seq_len, int blank, int32_t* out_labels,

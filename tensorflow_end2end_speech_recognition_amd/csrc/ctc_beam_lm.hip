@@ -543,4 +543,4 @@ extern "C" int asr_ctc_beam_decode_lm(asr_handle* h, const float* logits, int T,
   return ASR_OK;
 }
 
-ASR_DEFINE_COUNTS3(ctc_beam_lm_counts)
+ASR_DEFINE_COUNTS(ctc_beam_lm_counts, ctc_beam_lm_counts)

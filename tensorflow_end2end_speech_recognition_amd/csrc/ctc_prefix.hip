@@ -259,4 +259,4 @@ extern "C" int asr_ctc_prefix_advance(asr_handle* h, const float* y, const int32
   return ASR_OK;
 }
 
-ASR_DEFINE_COUNTS3(att_joint_counts)
+ASR_DEFINE_COUNTS(att_joint_counts, att_joint_counts)

@@ -217,16 +217,7 @@ extern "C" int asr_att_stack_reorder(asr_handle* h, const asr_att_stack* sk, con
   return ASR_OK;
 }
 
-extern "C" int asr_att_stack_counts(asr_handle* h, unsigned long long* out4) {
-  if (!h || !out4) return ASR_ERR_INVALID_ARG;
-  for (int i = 0; i < 4; ++i) out4[i] = h->att_stack_counts[i];
-  return ASR_OK;
-}
-extern "C" int asr_reset_att_stack_counts(asr_handle* h) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  for (int i = 0; i < 4; ++i) h->att_stack_counts[i] = 0;
-  return ASR_OK;
-}
+ASR_DEFINE_COUNTS(att_stack_counts, att_stack_counts)
 
 // ---------------------------------------------------------------- the upper layers' part of the loops of dec_loop.hip
 int asr_stack_dec_check(asr_handle* h, const asr_att_decoder* a, const asr_att_stack* sk, bool bwd) {

@@ -1502,16 +1502,7 @@ extern "C" int asr_ctc_head_bwd(asr_handle* h, int M, int E, int Kp, const void*
   return asr_gemm_act(h, ASR_BF16, ASR_F32, 0, 1, M, E, Kp, dl, Kp, Wp, Kp, denc, E, nullptr, 0, 0, s);
 }
 
-extern "C" int asr_gemm_path_counts(asr_handle* h, unsigned long long* out, int n) {
-  if (!h || !out || n < 0) return ASR_ERR_INVALID_ARG;
-  for (int i = 0; i < n; ++i) out[i] = i < ASR_GEMMP_N ? h->gemm_counts[i] : 0ull;
-  return ASR_OK;
-}
-extern "C" int asr_reset_gemm_path_counts(asr_handle* h) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  for (int i = 0; i < ASR_GEMMP_N; ++i) h->gemm_counts[i] = 0;
-  return ASR_OK;
-}
+ASR_DEFINE_COUNTS_N(gemm_path_counts, gemm_counts)
 
 // ---------------------------------------------------------------- decoder cell: product + LSTM cell in one launch
 extern "C" int asr_lstm_cell_gemm_prep(asr_handle* h, const float* W, const float* bias, int K, int U, float* W_il,

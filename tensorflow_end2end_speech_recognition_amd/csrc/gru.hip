@@ -613,13 +613,4 @@ extern "C" int asr_gru_bwd(asr_handle* h, int T, int B, int H, int ndir, const f
 }
 
 // the form each asr_gru_fwd / asr_gru_bwd call on this handle ended in (host integers bumped where the form is chosen)
-extern "C" int asr_gru_kernel_counts(asr_handle* h, unsigned long long* out6) {
-  if (!h || !out6) return ASR_ERR_INVALID_ARG;
-  for (int i = 0; i < 6; ++i) out6[i] = h->gru_counts[i];
-  return ASR_OK;
-}
-extern "C" int asr_reset_gru_kernel_counts(asr_handle* h) {
-  if (!h) return ASR_ERR_INVALID_ARG;
-  for (int i = 0; i < 6; ++i) h->gru_counts[i] = 0;
-  return ASR_OK;
-}
+ASR_DEFINE_COUNTS(gru_kernel_counts, gru_counts)

@@ -319,7 +319,7 @@ extern "C" int asr_gru_cell_bwd(asr_handle* h, const float* dcell, const float* 
   return ASR_OK;
 }
 
-ASR_DEFINE_COUNTS3(att_gru_counts)
+ASR_DEFINE_COUNTS(att_gru_counts, att_gru_counts)
 
 // ---------------------------------------------------------------- the cell part of a decoder-loop step (dec_loop.hip)
 int asr_gru_dec_check(asr_handle* h, const asr_att_decoder* a, const asr_att_gru* g) {

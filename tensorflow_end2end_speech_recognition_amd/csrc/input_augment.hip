@@ -202,4 +202,4 @@ extern "C" int asr_input_augment(asr_handle* h, const float* x, float* y, const 
   return ASR_OK;
 }
 
-ASR_DEFINE_COUNTS3(input_augment_counts)
+ASR_DEFINE_COUNTS(input_augment_counts, input_augment_counts)

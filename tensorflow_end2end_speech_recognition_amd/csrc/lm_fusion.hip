@@ -126,4 +126,4 @@ extern "C" int asr_lm_beam_reorder(asr_handle* h, const int32_t* parent, const i
   return ASR_OK;
 }
 
-ASR_DEFINE_COUNTS3(att_lm_counts)
+ASR_DEFINE_COUNTS(att_lm_counts, att_lm_counts)

@@ -81,4 +81,4 @@ extern "C" int asr_weight_noise_perturb(asr_handle* h, float* w, float* backup, 
   return ASR_OK;
 }
 
-ASR_DEFINE_COUNTS3(weight_noise_counts)
+ASR_DEFINE_COUNTS(weight_noise_counts, weight_noise_counts)

@@ -12,7 +12,7 @@ import time as _time
 import numpy as np
 import torch
 
-from . import _lib
+from . import _counters, _lib
 from ._lib import ASR_BF16, ASR_F32
 
 TORCH_DTYPE = {ASR_F32: torch.float32, ASR_BF16: torch.bfloat16}
@@ -1583,6 +1583,16 @@ def debug_set_lstm_flags(flags):
     _lib.load().asr_debug_set_lstm_flags(int(flags))
 
 
+def debug_set_gru_persistent(on):
+    """asr_debug_set_gru_persistent: 1 = one persistent launch per GRU layer call (default), 0 = launch per step."""
+    _lib.load().asr_debug_set_gru_persistent(int(bool(on)))
+
+
+def debug_set_cluster_cu_budget(n):
+    """TEST ONLY: co-resident workgroups a cluster launch may use (0 = the device's CU count; never more than that)."""
+    _lib.load().asr_debug_set_cluster_cu_budget(int(n))
+
+
 def cluster_tile_groups(G, ndir, tiles, cu_budget):
     """asr_cluster_tile_groups: the [(first_tile, ntiles), ...] launches of a cluster recurrence with G workgroups per
     cluster over `tiles` 16-utterance tiles when at most cu_budget workgroups are resident at once; [] = no plan.
@@ -1595,213 +1605,76 @@ def cluster_tile_groups(G, ndir, tiles, cu_budget):
     return [(first[i], cnt[i]) for i in range(n)]
 
 
-_PATH_KEYS = ('lstm_cluster', 'lstm_single_cu', 'lstm_split_calls', 'gru_cluster', 'gru_single_cu', 'gru_split_calls')
-
-
+# ---------------------------------------------------------------- launch counters
+# Every native kernel family counts on its handle which path its calls took (plain host integers: no device work, no
+# synchronisation).  _counters holds the table of families, keys and public views; the views are built here.
 def _device_handles(device):
     dev = device.index or 0 if isinstance(device, torch.device) else int(device)
     _lib.handle(dev)
     return [h for (d, _lane), h in list(_lib._handles.items()) if d == dev]
 
 
-def recurrence_path_counts(device=0):
-    """Which path the recurrence calls on `device` took since the last reset, summed over its handles: cluster launches
-    (one per tile group), single-CU calls, and calls that were split into more than one tile group, for LSTM and GRU.
-    Host counters: no device work, no synchronisation."""
-    tot = [0] * 6
-    for h in _device_handles(device):
-        out = (C.c_ulonglong * 6)()
-        h.check(h.lib.asr_recurrence_path_counts(h.h, out), 'asr_recurrence_path_counts')
-        tot = [a + int(b) for a, b in zip(tot, out)]
-    return dict(zip(_PATH_KEYS, tot))
-
-
-def reset_recurrence_path_counts(device=0):
-    for h in _device_handles(device):
-        h.check(h.lib.asr_reset_recurrence_path_counts(h.h), 'asr_reset_recurrence_path_counts')
-
-
-_GRU_KERNEL_KEYS = ('fwd_cluster', 'fwd_persistent', 'fwd_per_step', 'bwd_cluster', 'bwd_persistent', 'bwd_per_step')
-
-
-def gru_kernel_counts(device=0):
-    """The form each gru_fwd / gru_bwd call on `device` ended in since the last reset_gru_kernel_counts, summed over its
-    handles (asr_gru_kernel_counts): clusters, the persistent single-CU kernel, or the launch-per-step kernels.  Host
-    counters: no device work, no synchronisation."""
-    tot = [0] * 6
-    for h in _device_handles(device):
-        out = (C.c_ulonglong * 6)()
-        h.check(h.lib.asr_gru_kernel_counts(h.h, out), 'asr_gru_kernel_counts')
-        tot = [a + int(b) for a, b in zip(tot, out)]
-    return dict(zip(_GRU_KERNEL_KEYS, tot))
-
-
-def reset_gru_kernel_counts(device=0):
-    for h in _device_handles(device):
-        h.check(h.lib.asr_reset_gru_kernel_counts(h.h), 'asr_reset_gru_kernel_counts')
-
-
-# the ASR_LSTM_* enum of include/asr_hip.h, in its order
-_LSTM_KERNEL_KEYS = ('fwd_bf16_cu16', 'fwd_bf16_hs32', 'fwd_bf16_hs64', 'fwd_f32_split', 'fwd_f32_hs32', 'fwd_f32_hs64',
-                     'fwd_single_bf16', 'fwd_single_f32',
-                     'bwd_bf16_hs32', 'bwd_bf16_hs64', 'bwd_f32_split', 'bwd_f32_hs32', 'bwd_f32_hs64',
-                     'bwd_single_bf16', 'bwd_single_f32')
-
-
-def lstm_kernel_counts(device=0):
-    """The form each lstm_fwd / lstm_bwd call on `device` ended in since the last reset_lstm_kernel_counts, summed over its
-    handles (asr_lstm_kernel_counts): the bf16 clusters of 16 / 32 / 64 units per CU, the fp32 three-term split, the exact
-    fp32 clusters of 32 / 64 units per CU, or the single-CU kernels, forward and backward.  One count per call, however
-    many tile groups it ran as.  Host counters: no device work, no synchronisation."""
-    n = len(_LSTM_KERNEL_KEYS)
+def _read_counts(family, device):
+    """The words of _counters.FAMILIES[family], summed over the handles of `device`: one native call per handle."""
+    fam = _counters.FAMILIES[family]
+    n = len(fam.keys)
     tot = [0] * n
     for h in _device_handles(device):
         out = (C.c_ulonglong * n)()
-        h.check(h.lib.asr_lstm_kernel_counts(h.h, out, n), 'asr_lstm_kernel_counts')
+        get = getattr(h.lib, fam.getter)
+        h.check(get(h.h, out, n) if fam.sized else get(h.h, out), fam.getter)
         tot = [a + int(b) for a, b in zip(tot, out)]
-    return dict(zip(_LSTM_KERNEL_KEYS, tot))
+    return tot
 
 
-def reset_lstm_kernel_counts(device=0):
+def _reset_counts(family, device):
+    fam = _counters.FAMILIES[family]
     for h in _device_handles(device):
-        h.check(h.lib.asr_reset_lstm_kernel_counts(h.h), 'asr_reset_lstm_kernel_counts')
+        h.check(getattr(h.lib, fam.reset)(h.h), fam.reset)
 
 
-# the ASR_ATT_* enum of include/asr_hip.h, in its order
-_ATT_PATH_KEYS = ('fwd_step_fused', 'fwd_step_4launch', 'fwd_cell_bf16', 'fwd_cell_f32img', 'fwd_cell_gemm',
-                  'bwd_step_fused_q', 'bwd_step_unfused', 'bwd_cell_bf16', 'bwd_cell_gemm', 'bwd_softmax_folded',
-                  'bwd_softmax_separate',
-                  'energy_fwd_16', 'energy_fwd_32', 'energy_fwd_64', 'energy_fwd_64x2', 'energy_fwd_general',
-                  'energy_bwd_16', 'energy_bwd_32', 'energy_bwd_64', 'energy_bwd_64x2', 'energy_bwd_general',
-                  'loc_fwd_16', 'loc_fwd_32', 'loc_fwd_64', 'loc_fwd_general',
-                  'loc_bwd_16', 'loc_bwd_32', 'loc_bwd_64', 'loc_bwd_general',
-                  'fused_fwd_16', 'fused_fwd_32', 'fused_fwd_64', 'fused_fwd_64x2')
+def _counter_fns(name):
+    """(counts, reset) of the public view `name` of _counters.VIEWS, each taking (device=0): counts returns the view's keys
+    in table order; reset zeroes the view's whole family, and is None for a view that shares another view's reset."""
+    view = _counters.VIEWS[name]
+    end = view.offset + len(view.keys)
+
+    def counts(device=0):
+        return dict(zip(view.keys, _read_counts(view.family, device)[view.offset:end]))
+
+    def reset(device=0):
+        _reset_counts(view.family, device)
+
+    counts.__name__ = counts.__qualname__ = view.name
+    counts.__doc__ = view.doc
+    if view.reset is None:
+        return counts, None
+    reset.__name__ = reset.__qualname__ = view.reset
+    return counts, reset
 
 
-def att_path_counts(device=0):
-    """Which kernels the attention decoder calls on `device` launched since the last reset, summed over its handles
-    (asr_att_path_counts): decoder-loop steps by path (forward step, forward cell, backward step, backward cell product,
-    softmax backward) and energy / location / fused-step launches by lane shape.  Host counters: no device work, no
-    synchronisation."""
-    n = len(_ATT_PATH_KEYS)
-    tot = [0] * n
-    for h in _device_handles(device):
-        out = (C.c_ulonglong * n)()
-        h.check(h.lib.asr_att_path_counts(h.h, out, n), 'asr_att_path_counts')
-        tot = [a + int(b) for a, b in zip(tot, out)]
-    return dict(zip(_ATT_PATH_KEYS, tot))
-
-
-def reset_att_path_counts(device=0):
-    for h in _device_handles(device):
-        h.check(h.lib.asr_reset_att_path_counts(h.h), 'asr_reset_att_path_counts')
-
-
-# the ASR_CONVP_* enum of include/asr_hip.h, in its order
-_CONV_PATH_KEYS = ('img', 'tiled', 'pair_64_64', 'pair_64_128', 'pair_128_128', 'pair_128_64', 'pair_other',
-                   'maxv_2', 'maxv_4', 'maxv_8', 'maxv_14', 'maxv_16', 'act_0', 'act_1', 'act_2', 'act_3', 'act_4',
-                   'nbuf_1', 'nbuf_2', 'stream', 'w8', 'tiled_bn128', 'tiled_bn64',
-                   'wgrad_img_64_small', 'wgrad_img_64_large', 'wgrad_img_128', 'split', 'bias_in_kernel',
-                   'reduce_vec', 'reduce_scalar', 'wgrad_tr_128', 'wgrad_tr_64', 'wgrad_colpix')
-
-
-def conv_path_counts(device=0):
-    """Which kernel instantiations the conv3x3_* calls on `device` launched since the last reset, summed over its handles
-    (asr_conv_path_counts): forward / data-gradient launches by form (img / tiled), channel pair of the product, and for
-    the image-resident kernel MAXV, compile-time ACT, LDS buffers, stream / w8; weight-gradient calls by form, split,
-    bias_in_kernel and reduce kernel.  Host counters: no device work, no synchronisation."""
-    n = len(_CONV_PATH_KEYS)
-    tot = [0] * n
-    for h in _device_handles(device):
-        out = (C.c_ulonglong * n)()
-        h.check(h.lib.asr_conv_path_counts(h.h, out, n), 'asr_conv_path_counts')
-        tot = [a + int(b) for a, b in zip(tot, out)]
-    return dict(zip(_CONV_PATH_KEYS, tot))
-
-
-def reset_conv_path_counts(device=0):
-    for h in _device_handles(device):
-        h.check(h.lib.asr_reset_conv_path_counts(h.h), 'asr_reset_conv_path_counts')
-
-
-# the ASR_GEMMP_* enum of include/asr_hip.h, in its order
-_GEMM_PATH_KEYS = ('rows_128', 'rows_256', 'rows_full')
-_TN_PATH_KEYS = ('tn_frames', 'tn_frames_generic')
-_HEAD_BWD_KEYS = ('head_bwd_lean', 'head_bwd_full')   # behind those    # behind the listed-row counters in the ASR_GEMMP_* enum
-# behind those: the kernel a full product ended in, and the second passes of gemm(mul=...) / gemm(drop=...)
-_GEMM_KERNEL_KEYS = ('skinny_nn16', 'skinny_nn32', 'skinny_nt16', 'skinny_nt32', 'nt128', 'nt256', 'tn_lean', 'generic128',
-                     'generic64', 'generic64_splitk', 'mul_pass', 'drop_pass')
-
-
-def gemm_path_counts(device=0):
-    """What the listed-row products (gemm(..., rows=...)) on `device` ran since the last reset, summed over its handles
-    (asr_gemm_path_counts): listed-row launches of the 128 x 128 and of the 256 x 256 NT kernel, and calls that ignored
-    their list and ran the full product.  Host counters: no device work, no synchronisation."""
-    n = len(_GEMM_PATH_KEYS)
-    tot = [0] * n
-    for h in _device_handles(device):
-        out = (C.c_ulonglong * n)()
-        h.check(h.lib.asr_gemm_path_counts(h.h, out, n), 'asr_gemm_path_counts')
-        tot = [a + int(b) for a, b in zip(tot, out)]
-    return dict(zip(_GEMM_PATH_KEYS, tot))
-
-
-def tn_frames_path_counts(device=0):
-    """What the gemm_tn_frames calls on `device` ran since the last reset_gemm_path_counts: calls on the lean TN kernel
-    and calls on the generic kernel (shape outside the lean TN path); neither loads the rows of padded frames."""
-    n0, n = len(_GEMM_PATH_KEYS), len(_GEMM_PATH_KEYS) + len(_TN_PATH_KEYS)
-    tot = [0] * n
-    for h in _device_handles(device):
-        out = (C.c_ulonglong * n)()
-        h.check(h.lib.asr_gemm_path_counts(h.h, out, n), 'asr_gemm_path_counts')
-        tot = [a + int(b) for a, b in zip(tot, out)]
-    return dict(zip(_TN_PATH_KEYS, tot[n0:]))
-
-
-def ctc_head_bwd_counts(device=0):
-    """What the ctc_head_bwd calls on `device` ran since the last reset_gemm_path_counts: calls on the lean NT kernels
-    (on the listed rows where a list was given) and calls that ran the full generic product."""
-    n0 = len(_GEMM_PATH_KEYS) + len(_TN_PATH_KEYS)
-    n = n0 + len(_HEAD_BWD_KEYS)
-    tot = [0] * n
-    for h in _device_handles(device):
-        out = (C.c_ulonglong * n)()
-        h.check(h.lib.asr_gemm_path_counts(h.h, out, n), 'asr_gemm_path_counts')
-        tot = [a + int(b) for a, b in zip(tot, out)]
-    return dict(zip(_HEAD_BWD_KEYS, tot[n0:]))
-
-
-def gemm_kernel_counts(device=0):
-    """The kernel each full product on `device` ended in since the last reset_gemm_path_counts (gemm() without rows, and
-    the listed-row / tn-frames / head-bwd calls that fell to the full product): the four skinny fp32 forms, the lean NT
-    kernels by tile size, the lean TN kernel, the generic kernel by tile size and split-K; and the calls whose multiplier
-    (mul_pass) or dropout (drop_pass) ran as a second pass instead of in an epilogue."""
-    n0 = len(_GEMM_PATH_KEYS) + len(_TN_PATH_KEYS) + len(_HEAD_BWD_KEYS)
-    n = n0 + len(_GEMM_KERNEL_KEYS)
-    tot = [0] * n
-    for h in _device_handles(device):
-        out = (C.c_ulonglong * n)()
-        h.check(h.lib.asr_gemm_path_counts(h.h, out, n), 'asr_gemm_path_counts')
-        tot = [a + int(b) for a, b in zip(tot, out)]
-    return dict(zip(_GEMM_KERNEL_KEYS, tot[n0:]))
-
-
-def reset_gemm_path_counts(device=0):
-    for h in _device_handles(device):
-        h.check(h.lib.asr_reset_gemm_path_counts(h.h), 'asr_reset_gemm_path_counts')
-
-
-def debug_set_cluster_cu_budget(n):
-    """TEST ONLY: co-resident workgroups a cluster launch may use (0 = the device's CU count; never more than that)."""
-    _lib.load().asr_debug_set_cluster_cu_budget(int(n))
+recurrence_path_counts, reset_recurrence_path_counts = _counter_fns('recurrence_path_counts')
+gru_kernel_counts, reset_gru_kernel_counts = _counter_fns('gru_kernel_counts')
+lstm_kernel_counts, reset_lstm_kernel_counts = _counter_fns('lstm_kernel_counts')
+att_path_counts, reset_att_path_counts = _counter_fns('att_path_counts')
+conv_path_counts, reset_conv_path_counts = _counter_fns('conv_path_counts')
+gemm_path_counts, reset_gemm_path_counts = _counter_fns('gemm_path_counts')
+tn_frames_path_counts = _counter_fns('tn_frames_path_counts')[0]       # these three: reset_gemm_path_counts
+ctc_head_bwd_counts = _counter_fns('ctc_head_bwd_counts')[0]
+gemm_kernel_counts = _counter_fns('gemm_kernel_counts')[0]
+ctc_head_counts, reset_ctc_head_counts = _counter_fns('ctc_head_counts')
+ctc_ls_counts, reset_ctc_ls_counts = _counter_fns('ctc_ls_counts')
+att_beam_counts, reset_att_beam_counts = _counter_fns('att_beam_counts')
+att_joint_counts, reset_att_joint_counts = _counter_fns('att_joint_counts')
+att_gru_counts, reset_att_gru_counts = _counter_fns('att_gru_counts')
+att_stack_counts, reset_att_stack_counts = _counter_fns('att_stack_counts')
+att_lm_counts, reset_att_lm_counts = _counter_fns('att_lm_counts')
+ctc_beam_lm_counts, reset_ctc_beam_lm_counts = _counter_fns('ctc_beam_lm_counts')
+weight_noise_counts, reset_weight_noise_counts = _counter_fns('weight_noise_counts')
+input_augment_counts, reset_input_augment_counts = _counter_fns('input_augment_counts')
 
 
 # ---------------------------------------------------------------- CTC
-def debug_set_gru_persistent(on):
-    """asr_debug_set_gru_persistent: 1 = one persistent launch per GRU layer call (default), 0 = launch per step."""
-    _lib.load().asr_debug_set_gru_persistent(int(bool(on)))
-
-
 def ctc_loss(logits, labels_flat, label_offsets, seq_len, max_label_len, grad_scale=1.0,
              want_grad=True):
     """logits [T,B,C] fp32; returns (loss [B], grad [T,B,C] or None, num_infeasible [1] int32)."""
@@ -1927,19 +1800,6 @@ def ctc_loss_ex(logits, labels_flat, label_offsets, seq_len, max_label_len, grad
     return loss, grad, img, ninf
 
 
-_CTC_HEAD_KEYS = ('head_fwd', 'loss_ex', 'loss')
-
-
-def ctc_head_counts(device=0):
-    """CTC head calls on `device` since the last reset (asr_ctc_head_counts): fused forward launches (ctc_head_fwd),
-    ctc_loss_ex calls, and calls of the plain ctc_loss.  Host counters: no device work, no synchronisation."""
-    return _counts3('ctc_head_counts', _CTC_HEAD_KEYS, device)
-
-
-def reset_ctc_head_counts(device=0):
-    _reset_counts3('ctc_head_counts', device)
-
-
 def ctc_ls_workspace(T, B, max_label_len, device):
     """The workspace of ctc_loss_ls (asr_ctc_ls_workspace_bytes): ctc_workspace's layout and behind it the KL row terms,
     so ctc_head_fwd can fill it for ctc_loss_ls(lse_done=True)."""
@@ -1981,19 +1841,6 @@ def ctc_loss_ls(logits, labels_flat, label_offsets, seq_len, max_label_len, smoo
                                   _p(ws), ws.numel(), 1 if lse_done else 0, _p(img), Kp if want_image else 0, _s()),
             'asr_ctc_loss_ls')
     return loss, kl, grad, img, ninf
-
-
-_CTC_LS_KEYS = ('calls', 'lse_done', 'no_grad')
-
-
-def ctc_ls_counts(device=0):
-    """ctc_loss_ls calls on `device` since the last reset (asr_ctc_ls_counts): all, those that continued from
-    ctc_head_fwd's workspace, those without a gradient.  Host counters: no device work, no synchronisation."""
-    return _counts3('ctc_ls_counts', _CTC_LS_KEYS, device)
-
-
-def reset_ctc_ls_counts(device=0):
-    _reset_counts3('ctc_ls_counts', device)
 
 
 def ctc_greedy_decode(logits, seq_len, blank=None):
@@ -2585,34 +2432,6 @@ def att_decoder_beam(a, W_av, W_out, b_out, embedding, eos, beam_width, length_p
     return _beam_loop_done(out, issued, host, scratch)
 
 
-def _counts3(name, keys, device):
-    """A handle's three launch counters asr_<name>, summed over the handles of `device`, under `keys`."""
-    tot = [0] * 3
-    for h in _device_handles(device):
-        out = (C.c_ulonglong * 3)()
-        h.check(getattr(h.lib, 'asr_' + name)(h.h, out), 'asr_' + name)
-        tot = [x + int(y) for x, y in zip(tot, out)]
-    return dict(zip(keys, tot))
-
-
-def _reset_counts3(name, device):
-    for h in _device_handles(device):
-        h.check(getattr(h.lib, 'asr_reset_' + name)(h.h), 'asr_reset_' + name)
-
-
-_ATT_BEAM_KEYS = ('select', 'reorder', 'backtrace')
-
-
-def att_beam_counts(device=0):
-    """Launches of the beam search kernels on `device` since the last reset, summed over its handles
-    (asr_att_beam_counts).  Host counters: no device work, no synchronisation."""
-    return _counts3('att_beam_counts', _ATT_BEAM_KEYS, device)
-
-
-def reset_att_beam_counts(device=0):
-    _reset_counts3('att_beam_counts', device)
-
-
 # ---------------------------------------------------------------- joint CTC / attention beam search (an extension)
 def log_softmax_rows(x2d, out=None):
     """x - logsumexp(x) per row of an fp32 [rows, cols] array (asr_log_softmax_rows)."""
@@ -2829,19 +2648,6 @@ def att_decoder_beam_joint(a, W_av, W_out, b_out, embedding, eos, beam_width, y,
     return _beam_loop_done(out, issued, host, scratch)
 
 
-_ATT_JOINT_KEYS = ('score', 'advance', 'joint_select')
-
-
-def att_joint_counts(device=0):
-    """Launches of the joint-search entry points on `device` since the last reset, summed over its handles
-    (asr_att_joint_counts).  Host counters: no device work, no synchronisation."""
-    return _counts3('att_joint_counts', _ATT_JOINT_KEYS, device)
-
-
-def reset_att_joint_counts(device=0):
-    _reset_counts3('att_joint_counts', device)
-
-
 # ---------------------------------------------------------------- GRU decoder cell (decoder_type 'gru')
 GRU_CELL_GEMM = os.environ.get('ASR_DEC_GRU_GEMM', '1') != '0'   # A/B: 0 keeps every step on the four-launch form
 
@@ -2939,19 +2745,6 @@ def gru_cell_bwd(dcell, dh_c, gates, h_prev, W3, W_c, live, out_mask=None, dh_c2
     h.check(h.lib.asr_gru_cell_bwd(h.h, _p(dcell), _p(dh_c), p2, ld2, _p(out_mask), _p(live), _p(gates), _p(h_prev), _p(W3),
                                    W_ch, B, Din, U, _p(dpre), _p(carry), _p(d_in), Din, _p(work), _s()), 'asr_gru_cell_bwd')
     return dpre, carry, d_in
-
-
-_ATT_GRU_KEYS = ('fwd_fused', 'fwd_general', 'bwd')
-
-
-def att_gru_counts(device=0):
-    """GRU decoder steps on `device` since the last reset, summed over its handles (asr_att_gru_counts): two-launch forward
-    steps, four-launch forward steps, backward steps.  Host counters: no device work, no synchronisation."""
-    return _counts3('att_gru_counts', _ATT_GRU_KEYS, device)
-
-
-def reset_att_gru_counts(device=0):
-    _reset_counts3('att_gru_counts', device)
 
 
 # ---------------------------------------------------------------- multi-layer LSTM decoder (decoder_num_layers > 1)
@@ -3060,26 +2853,6 @@ def att_stack_reorder(parent, c, h, in_):
         k.up[i].c, k.up[i].h = ci.data_ptr(), hi.data_ptr()
         setattr(k.up[i], 'in', xi.data_ptr())
     hd.check(hd.lib.asr_att_stack_reorder(hd.h, C.byref(k), _p(parent), B, W, U, _s()), 'asr_att_stack_reorder')
-
-
-_ATT_STACK_KEYS = ('fwd_image', 'fwd_two_launch', 'bwd_fused', 'bwd_generic')
-
-
-def att_stack_counts(device=0):
-    """Upper-layer steps of decoder stacks on `device` since the last reset, summed over its handles
-    (asr_att_stack_counts): forward on the image (one launch), forward as product + cell, backward fused, backward generic.
-    Host counters: no device work, no synchronisation."""
-    tot = [0] * 4
-    for h in _device_handles(device):
-        out = (C.c_ulonglong * 4)()
-        h.check(h.lib.asr_att_stack_counts(h.h, out), 'asr_att_stack_counts')
-        tot = [x + int(y) for x, y in zip(tot, out)]
-    return dict(zip(_ATT_STACK_KEYS, tot))
-
-
-def reset_att_stack_counts(device=0):
-    for h in _device_handles(device):
-        h.check(h.lib.asr_reset_att_stack_counts(h.h), 'asr_reset_att_stack_counts')
 
 
 # ---------------------------------------------------------------- shallow fusion with an RNN language model (an extension)
@@ -3267,19 +3040,6 @@ def att_decoder_beam_lm(a, W_av, W_out, b_out, embedding, eos, beam_width, lm, l
     return _beam_loop_done(out, issued, host, scratch)
 
 
-_ATT_LM_KEYS = ('lm_step', 'fused_select', 'lm_reorder')
-
-
-def att_lm_counts(device=0):
-    """Calls of the LM-fusion entry points on `device` since the last reset, summed over its handles (asr_att_lm_counts).
-    Host counters: no device work, no synchronisation."""
-    return _counts3('att_lm_counts', _ATT_LM_KEYS, device)
-
-
-def reset_att_lm_counts(device=0):
-    _reset_counts3('att_lm_counts', device)
-
-
 # ------------------------------------------------- CTC prefix beam search with LM fusion / insertion bonus (an extension)
 def _ctc_lm_args(who, logits, seq_len, beam_width, lm_weight, insertion_bonus, blank):
     _chk(logits, torch.float32, 'logits')
@@ -3373,19 +3133,6 @@ class CtcBeamLmFrames(object):
                                             self.alpha, self.beta, _p(lm_logits), V, _p(parent), _p(word), _p(pb), _p(pnb),
                                             _p(lmt), _p(nb), _p(self.ws), self.nbytes, _s()), 'asr_ctc_beam_lm_frame')
         return parent, word, pb, pnb, lmt, nb
-
-
-_CTC_BEAM_LM_KEYS = ('frames', 'lm_steps', 'commits')
-
-
-def ctc_beam_lm_counts(device=0):
-    """Launches of the LM-fused CTC prefix search on `device` since the last reset, summed over its handles
-    (asr_ctc_beam_lm_counts): frame kernels, LM steps, commits.  Host counters: no device work, no synchronisation."""
-    return _counts3('ctc_beam_lm_counts', _CTC_BEAM_LM_KEYS, device)
-
-
-def reset_ctc_beam_lm_counts(device=0):
-    _reset_counts3('ctc_beam_lm_counts', device)
 
 
 def tanh_fwd(x):
@@ -3514,19 +3261,6 @@ def weight_noise_perturb(flat, backup, std, seed, offset):
     return flat
 
 
-_WEIGHT_NOISE_KEYS = ('calls', 'elements', 'vec_calls')
-
-
-def weight_noise_counts(device=0):
-    """weight_noise_perturb calls on `device` since the last reset (asr_weight_noise_counts): calls, elements, calls that
-    ran the 16-byte kernel.  Host counters: no device work, no synchronisation."""
-    return _counts3('weight_noise_counts', _WEIGHT_NOISE_KEYS, device)
-
-
-def reset_weight_noise_counts(device=0):
-    _reset_counts3('weight_noise_counts', device)
-
-
 def input_augment(x, seq_len, n_ch, noise_std=0.0, freq_masks=(0, 0), time_masks=(0, 0, 1.0), mask_value=0.0, seed=0,
                   offset=0, out=None):
     """EXTENSION: input augmentation of one training step (asr_input_augment), one pass, x untouched: y = x with Gaussian
@@ -3556,19 +3290,6 @@ def input_augment(x, seq_len, n_ch, noise_std=0.0, freq_masks=(0, 0), time_masks
                                     int(seed) & 0xFFFFFFFFFFFFFFFF, int(offset) & 0xFFFFFFFFFFFFFFFF, _s()),
             'asr_input_augment')
     return out
-
-
-_INPUT_AUGMENT_KEYS = ('calls', 'elements', 'vec_calls')
-
-
-def input_augment_counts(device=0):
-    """input_augment calls on `device` since the last reset (asr_input_augment_counts): calls, elements, calls that ran
-    the 16-byte kernel.  Host counters: no device work, no synchronisation."""
-    return _counts3('input_augment_counts', _INPUT_AUGMENT_KEYS, device)
-
-
-def reset_input_augment_counts(device=0):
-    _reset_counts3('input_augment_counts', device)
 
 
 def optimizer_step(opt_id, params, grads, slot0, slot1, lr, step):
