@@ -620,15 +620,15 @@ enum {
   ASR_LSTM_FWD_BF16_CU16 = 0,     /* bf16, H = 256 on clusters of 16 CUs (lstm_fwd_cluster16_kernel) */
   ASR_LSTM_FWD_BF16_HS32,         /* bf16 clusters, 32 units per CU (H = 256, 512) */
   ASR_LSTM_FWD_BF16_HS64,         /* bf16 clusters, 64 units per CU (H = 256, 320, 512) */
-  ASR_LSTM_FWD_F32_SPLIT,         /* fp32 as three bf16 terms, 32 units per CU (lstm_fwd_cluster_f32s_kernel; H = 128, 256) */
+  ASR_LSTM_FWD_F32_SPLIT,         /* fp32 as three bf16 terms, 32 units per CU (lstm_fwd_cluster_f32_kernel under OpSplit3; H = 128, 256) */
   ASR_LSTM_FWD_F32_HS32,          /* exact fp32 clusters, 32 units per CU (H = 128, 256, 320, 512) */
   ASR_LSTM_FWD_F32_HS64,          /* exact fp32 clusters, 64 units per CU (H = 128) */
   ASR_LSTM_FWD_SINGLE_BF16,       /* lstm_fwd_kernel<bf16>, one CU per (direction, tile) */
   ASR_LSTM_FWD_SINGLE_F32,        /* lstm_fwd_kernel<float> */
   ASR_LSTM_BWD_BF16_HS32,         /* bf16 BPTT clusters, 32 units per CU (H = 256, 512) */
   ASR_LSTM_BWD_BF16_HS64,         /* bf16 BPTT clusters, 64 units per CU (H = 256, 320, 512) */
-  ASR_LSTM_BWD_F32_SPLIT,         /* lstm_bwd_cluster_f32s_kernel (H = 128, 256) */
-  ASR_LSTM_BWD_F32_HS32,          /* lstm_bwd_cluster_f32_kernel, 32 units per CU (H = 128, 256, 320, 512) */
+  ASR_LSTM_BWD_F32_SPLIT,         /* lstm_bwd_cluster_f32_kernel under OpSplit3 (H = 128, 256) */
+  ASR_LSTM_BWD_F32_HS32,          /* lstm_bwd_cluster_f32_kernel under OpF32, 32 units per CU (H = 128, 256, 320, 512) */
   ASR_LSTM_BWD_F32_HS64,          /* lstm_bwd_cluster8_f32_kernel, 64 units per CU (H = 128) */
   ASR_LSTM_BWD_SINGLE_BF16,       /* lstm_bwd_kernel<bf16> */
   ASR_LSTM_BWD_SINGLE_F32,        /* lstm_bwd_kernel<float> */

@@ -7,6 +7,7 @@ between files, leaves the kernels' code untouched, so it can be committed withou
     python scripts/isa_diff.py <rev_a> <rev_b> [file.hip ...] [--b file.hip ...] [--rename old=new ...] [--work dir]
     e.g.  isa_diff.py HEAD~1 HEAD                                   (the default files: the cluster recurrence family)
           isa_diff.py HEAD~1 . csrc/gemm.hip --b csrc/gemm.hip csrc/conv.hip --rename conv3x5_nt_kernel=conv_nt_kernel
+          isa_diff.py HEAD~1 . --rename 'lstm_bwd_cluster_f32s_kernel<([^>]*)>=lstm_bwd_cluster_f32_kernel<\1, OpSplit3>'
 (file paths from the repository root).  Every file is compiled with the flags that build.py OF ITS OWN TREE gives it -- FLAGS
 and the file's FILE_FLAGS entry, ASR_BUILD_ABLATE=1 in the environment included -- so a file that exists only on side b
 takes tree b's flags and the verdict is about the code each tree ships.

@@ -9,14 +9,14 @@ namespace {
 // tf.contrib.rnn.GRUCell (models/encoders/core/gru.py:58-76):  [r | u] = sigmoid(xg + h W_gh),  c = tanh(xc + (r * h) W_ch),
 // h' = u h + (1 - u) c -- TWO dependent products per step, so two all-gathers: r * h between them, h' behind the second.
 // The single-CU persistent kernel (gru.hip) streams both recurrent blocks from L2 every step and multiplies on the fp32 MFMA:
-// 11.7 us of matrix work + the weight trips per step at H = 256.  Here the cluster machinery of lstm_fwd_cluster_f32s_kernel:
+// 11.7 us of matrix work + the weight trips per step at H = 256.  Here the cluster machinery of lstm_fwd_cluster_f32_kernel under OpSplit3:
 // H / 32 CUs per (direction, 16-utterance tile), four waves x 8 units, the CU's slices of W_gh ([H] x [r | u of its units])
 // and W_ch as three-bf16-term fragments in registers for the whole launch, h and r * h as three-term LDS images, both
 // exchanges in 8-byte self-tagged granules {hi | mid << 16, lo | tag << 16}.  Phase 1 is one 16-column tile per wave
 // ([r x 8 | u x 8], halves swapped over DPP as in the LSTM kernels), phase 2 one tile whose upper eight columns repeat the
 // lower ones (a 16-column MFMA for 8 units: the lanes col >= 8 read rows 2, 3 of the same unit from their own copy).
 // Saved activations r, u, c, r * h at the frame a row worked on; rows past their length store nothing but hout's zero
-// and keep h (their x loads are parked on a valid frame).  Same fp32-level arithmetic as the f32s LSTM kernels (six exact bf16 products per k = 32 chunk).
+// and keep h (their x loads are parked on a valid frame).  Same fp32-level arithmetic as the split (OpSplit3) LSTM kernels (six exact bf16 products per k = 32 chunk).
 template <int H>
 __global__ __launch_bounds__(256, 1) void gru_fwd_cluster_kernel(
     int T_, int B_, int ndir, const float* __restrict__ xg, const float* __restrict__ xc, const float* __restrict__ wgh,
